@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """Headline benchmark: 388x388 patches/s of the fused forward + backward + Momentum step (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
+
+A plain run does what the headline figure needs and nothing else: set up (explicit tile-shape tuning pass, untimed priming), W
+warm-up steps, K timed steps, the outputs of the last timed step written to DIR (--dump-outputs), one JSON line. The model state is
+reset to its seeded initial value behind the priming, so the last timed step is step W + K from the same weights on the same
+inputs in every run with the same arguments: two builds can be compared output for output. Everything else below (`sustained`,
+the instrumented roofline passes, the exchange proof for N > 1, the CPU baselines) runs behind --full only.
 
 Workload = BASELINE.json configs[1]: num_layers=5 root_size=64 patch_size=388 (input 572), bf16 storage / fp32
 accumulate, 4 patches per GPU (weak scaling: the global batch is 4*N), synthetic data of SURVEY.md section 8(d):
@@ -13,7 +19,7 @@ The weight-gradient launches of a step run on a second HIP stream beside the bac
 Inputs are resident in HBM before the timed region (the reference feeds host numpy arrays; the PCIe-inclusive figure is
 discussed in DESIGN.md and is never `value`).
 
-Besides the contract line the JSON carries
+Besides the contract line the JSON carries (plain run: `roofline` holds only `whole_step_frac`, which needs no run of its own)
   roofline     : the 3x3-conv MFMA kernels (forward, backward-data, backward-weight): algorithmic FLOPs
                  (2*B*Ho*Wo*Cout*Cin*9 per launch) / the CHIP TIME of those launches in the very schedule `value`
                  is timed on, measured with HIP events on each launch's own stream in an instrumented pass right behind the
@@ -31,6 +37,11 @@ Besides the contract line the JSON carries
                  host cores on a bounded sample of the same network, rank 0 / N=1 only.
   cpu_baseline_torch : the same step in stock PyTorch-CPU float32 (oneDNN, oracle/torch_ref.py; kind "stand-in").
   sustained    : the same loop run for >= 2 s behind the timed region (clocks and power at steady state).
+
+--dump-outputs DIR writes what a caller of the step receives from the last timed step (rank 0): loss.npy (float64, the global mean
+loss), predictions.npy (float32 [B, P, P] road probabilities of rank 0's patches), weights_sample.npy and momentum_sample.npy
+(float32: the updated variables and their Momentum slots, every live variable in name order, all of it up to 16384 values per
+variable and a fixed seeded sample of that many beyond).
 
 --workload c4 switches to BASELINE.json configs[3]'s per-GPU share (num_layers=6, 4 patches per GPU) for scaling runs of the
 data-parallel configuration; --workload c3 to configs[2] (num_layers=6, --dilated_layers, ONE patch per step: the reference's
@@ -146,6 +157,34 @@ def net_flops(L, root, dilated, P, B):
     return tot, conv3
 
 
+DUMP_PER_VARIABLE = 16384   # values of one variable written by --dump-outputs (all of them when it has no more)
+
+
+def sample_values(a, k, seed):
+    """a flattened, all of it when it has at most k values, else the values at k fixed positions (ascending) drawn with `seed`"""
+    a = np.asarray(a).reshape(-1)
+    if a.size <= k:
+        return a
+    return a[np.sort(np.random.RandomState(seed).choice(a.size, k, replace=False))]
+
+
+def dump_outputs(out_dir, loss, predictions, variables):
+    """--dump-outputs: loss (float64), predictions (float32) and the sampled variables / Momentum slots (float32) as out_dir/<name>.npy.
+    variables: [(name, weights, momentum)] of numpy arrays in a fixed order; each variable's sample positions are seeded by its index."""
+    os.makedirs(out_dir, exist_ok=True)
+    w = [sample_values(v, DUMP_PER_VARIABLE, 1000 + i) for i, (_, v, _) in enumerate(variables)]
+    a = [sample_values(v, DUMP_PER_VARIABLE, 1000 + i) for i, (_, _, v) in enumerate(variables)]
+    arrays = {"loss": np.asarray([loss], dtype=np.float64),
+              "predictions": np.asarray(predictions, dtype=np.float32),
+              "weights_sample": np.concatenate(w).astype(np.float32),
+              "momentum_sample": np.concatenate(a).astype(np.float32)}
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= 64 << 20, "--dump-outputs would write %d bytes (> 64 MB)" % total
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    return arrays
+
+
 def launch_ranks(nranks, script, script_args, timeout=None):
     """Start `script` under torch.distributed.run with `nranks` ranks on this node as a child process (never an exec: a process that
     has touched the GPU must not be replaced), relay its stdout / stderr and return its exit code. One rank per GPU over RCCL
@@ -180,7 +219,14 @@ def main():
     ap.add_argument("--prime_seconds", type=float, default=1.0,
                     help="untimed steps run for this long in front of the W warm-up steps: clocks and power reach their steady state (0: skip)")
     ap.add_argument("--cpu_sample_patch", type=int, default=196)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the sustained loop, the instrumented roofline passes, the exchange "
+                         "proof (N > 1) and the CPU baselines")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (loss, predictions, sampled weights / Momentum slots)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # bare `bench.py --gpus N`: this process becomes the launcher of N ranks (nothing has touched the GPU yet)
@@ -248,6 +294,9 @@ def main():
     # timed region only look shapes up), skipped when a table measured by this very build was imported; then one untimed priming step
     if not tune_imported:
         m.tune()
+    # the seeded initial state: restored behind the untimed steps below, whose number depends on timing, so that the warm-up and timed
+    # steps start from the same weights in every run
+    init_state = (m.flat_w.clone(), m.flat_acc.clone(), m.global_step)
     run_step(m, bucketer, lr, mu)
     dp_tune = None
     if bucketer is not None and "RSU_DP_OVERLAP" not in os.environ:
@@ -273,6 +322,12 @@ def main():
             nprime = int(tn.item())
         for _ in range(nprime):
             run_step(m, bucketer, lr, mu)
+    torch.cuda.synchronize()
+    m.flat_w.copy_(init_state[0])
+    m.flat_acc.copy_(init_state[1])
+    m.global_step = init_state[2]
+    m.repack()
+    del init_state
     for _ in range(args.warmup):
         run_step(m, bucketer, lr, mu)
     torch.cuda.synchronize()
@@ -295,9 +350,14 @@ def main():
     if world > 1:
         dist.all_reduce(loss_t)  # every rank holds the sum over ITS pixels; _inv_count is 1 / global pixel count
     loss = float(loss_t.item()) * m._inv_count
+    if args.dump_outputs and rank == 0:
+        live = [n for n in m.names if m._slices[n][0] < m.n_live]
+        dump_outputs(args.dump_outputs, loss, m.prob.cpu().numpy(),
+                     [(n, m.w[n].cpu().numpy(), m.acc[n].cpu().numpy()) for n in live])
+    # ---- everything below up to the result line runs with --full only
     # ---- sustained figure: the same loop for >= 2 s (the timed region above is ~0.1 s: too short for clocks / power to settle)
     sustained = None
-    if args.sustain_seconds > 0:
+    if args.full and args.sustain_seconds > 0:
         nsus = max(args.steps, int(args.sustain_seconds / (dt / args.steps)) + 1)
         torch.cuda.synchronize()
         if world > 1:
@@ -317,7 +377,7 @@ def main():
     # ---- proof of exchange (untimed, N > 1): one backward pass WITHOUT the exchange gives every rank's own gradient checksum; their sum
     # over the ranks must equal the checksum of the all-reduced buffer, which must be identical on every rank
     dp_proof = None
-    if bucketer is not None:
+    if args.full and bucketer is not None:
         on_grads, m.on_grads = m.on_grads, None
         m.forward_device()
         m.backward_device(m._inv_count)
@@ -339,109 +399,140 @@ def main():
                     "payload_MB": m.n_live * 4 / 1e6, "checksum_rank0_local": float(local.item()),
                     "checksum_sum_of_ranks": float(sum_local.item()), "checksum_allreduced_min_over_ranks": float(rmin.item()),
                     "checksum_allreduced_max_over_ranks": float(rmax.item())}
-    # ---- instrumented passes (HIP events on the launch's own stream around every 3x3-conv MFMA launch)
-    nprof = 3
-
-    def instrumented(label):
-        """nprof steps with events around every 3x3-conv launch -> (achieved TFLOP/s over chip time, by_kernel, launches, chip seconds)"""
-        run_step(m, bucketer, lr, mu)   # untimed
-        torch.cuda.synchronize()
-        m.prof = []
-        for _ in range(nprof):
-            run_step(m, bucketer, lr, mu)
-        torch.cuda.synchronize()
-        agg = {}
-        spans = []
-        ref = m.prof[0][2] if m.prof else None
-        for tag, fl, e0, e1, share in m.prof:
-            a = agg.setdefault(tag, [0.0, 0.0, 0, 0.0])
-            dur = e0.elapsed_time(e1) * 1e-3
-            a[0] += fl
-            a[1] += dur * share      # chip time: a launch planned for half of the CUs runs beside another one
-            a[2] += 1
-            a[3] += dur
-            t0_ = ref.elapsed_time(e0) * 1e-3
-            spans.append((t0_, t0_ + dur))
-        m.prof = None
-        # union of the launches' busy intervals over both streams: the time during which AT LEAST ONE 3x3-conv launch held (part of) the
-        # chip. FLOPs over it bills the whole chip for every such moment -- a LOWER bound of the kernels' efficiency, where `achieved`
-        # (duration x planned CU share) is an upper bound whenever the two backward streams do not overlap perfectly (ADVICE r4)
-        spans.sort()
-        union, cur0, cur1 = 0.0, None, None
-        for a0, a1 in spans:
-            if cur1 is None or a0 > cur1:
-                if cur1 is not None:
-                    union += cur1 - cur0
-                cur0, cur1 = a0, a1
-            else:
-                cur1 = max(cur1, a1)
-        if cur1 is not None:
-            union += cur1 - cur0
-        fl = sum(a[0] for a in agg.values())
-        t = sum(a[1] for a in agg.values())
-        n = sum(a[2] for a in agg.values())
-        by = {k: {"tflops": v[0] / v[1] / 1e12, "chip_ms_per_step": v[1] / nprof * 1e3, "wall_ms_per_step": v[3] / nprof * 1e3,
-                  "launches": v[2] // nprof} for k, v in agg.items()}
-        return {"achieved": fl / t / 1e12 if t > 0 else 0.0, "by_kernel": by, "launches": n, "chip_s": t, "flops": fl, "label": label,
-                "busy_union_s": union}
-
-    # (1) the timed schedule itself: two streams in the backward pass, every launch with the CU share it has there. The conv launches of a
-    # step cannot hold the chip for longer than the step lasts: a pass whose chip time exceeds the timed step by more than 15 % is not a
-    # measurement of that schedule (seen once in ~30 runs on the test pool: both backward queues reported ~6x their usual kernel durations
-    # for one pass, profiles/r04/bench_odd_pass.json) and is repeated, at most twice.
-    attempts = 0
-    while True:
-        attempts += 1
-        prof_timed = instrumented("timed schedule")
-        plausible = prof_timed["chip_s"] / nprof <= 1.15 * dt / args.steps
-        if world > 1:
-            # every rank repeats the pass or none does: its steps hold collectives (round 4: decided per rank, one rank ran a pass more than
-            # its peer and the run ended in "connection reset by peer" -- two of eight two-rank runs on a shared GPU)
-            ok = torch.tensor([1 if plausible else 0], dtype=torch.int32, device=dev if backend == "nccl" else "cpu")
-            dist.all_reduce(ok, op=dist.ReduceOp.MIN)
-            plausible = bool(ok.item())
-        if plausible or attempts >= 3:
-            break
-    # (2), (3) serialised single-stream passes, every launch alone on the chip: one weight-gradient launch per layer (rounds 1-2's
-    # figure), then the single-stream product schedule with grouped weight gradients (round 3's headline figure)
-    wstreams, m.wstreams = m.wstreams, []
-    if not tune_imported:
-        m.tune()                    # on one stream the backward launches plan for the whole chip: shapes not measured yet
-    wg_env = os.environ.get("RSU_WG_GROUP")
-    os.environ["RSU_WG_GROUP"] = "0"
-    prof_serial = instrumented("single stream, one weight-gradient launch per layer")
-    if wg_env is None:
-        del os.environ["RSU_WG_GROUP"]
-    else:
-        os.environ["RSU_WG_GROUP"] = wg_env
-    prof_grouped = instrumented("single stream, grouped weight gradients") if wstreams else prof_serial
-    m.wstreams = wstreams
-    # (the table of measured tile shapes: saved behind BOTH schedules -- they plan the backward launches for different CU budgets)
-    if tune_file and rank == 0 and not os.path.exists(tune_file):
-        cap = lib().rsu_autotune_entries()
-        arr = (ctypes.c_int * (17 * max(1, cap)))()
-        n = lib().rsu_autotune_export(arr, cap)
-        json.dump({"lib_sha16": lib_sha, "rows": list(arr[:17 * n])}, open(tune_file, "w"))
-
-    two_streams = bool(wstreams)
-    achieved = prof_timed["achieved"]
-    n_launch = prof_timed["launches"]
-    conv_t = prof_timed["chip_s"]
-    conv_fl = prof_timed["flops"]
     tot_fl, conv3_fl = net_flops(L, root, args.dilated_layers, P, B)
-    # HBM-side bytes per conv launch: PMC counters cannot be read from inside this process; the figure is the one measured with
-    # tools/pmc_traffic.sh on this same workload and committed under profiles/rNN/traffic.json (null for any other workload)
-    traffic, traffic_source = None, None
-    try:
-        import glob
-        for cand in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*", "traffic.json")), reverse=True):
-            tj = json.load(open(cand))
-            if tj.get("lib_sha16") == lib_sha and (L, root, P, B, args.dilated_layers) == (5, 64, 388, 4, False):
-                traffic = tj["kernels"]["conv3x3 all"]["hbm_bytes_per_launch"]
-                traffic_source = os.path.relpath(cand, ROOT) + " (PMC run of this build, lib_sha16 %s)" % lib_sha
+    # (plain run: the only roofline figure that needs no run of its own)
+    roofline = {"bound": "mfma", "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
+                "whole_step_frac": conv3_fl * world / (dt / args.steps) / 1e12 / (MFMA_BF16_PEAK_TFLOPS * world)}
+    if args.full:
+        # ---- instrumented passes (HIP events on the launch's own stream around every 3x3-conv MFMA launch)
+        nprof = 3
+
+        def instrumented(label):
+            """nprof steps with events around every 3x3-conv launch -> (achieved TFLOP/s over chip time, by_kernel, launches, chip seconds)"""
+            run_step(m, bucketer, lr, mu)   # untimed
+            torch.cuda.synchronize()
+            m.prof = []
+            for _ in range(nprof):
+                run_step(m, bucketer, lr, mu)
+            torch.cuda.synchronize()
+            agg = {}
+            spans = []
+            ref = m.prof[0][2] if m.prof else None
+            for tag, fl, e0, e1, share in m.prof:
+                a = agg.setdefault(tag, [0.0, 0.0, 0, 0.0])
+                dur = e0.elapsed_time(e1) * 1e-3
+                a[0] += fl
+                a[1] += dur * share      # chip time: a launch planned for half of the CUs runs beside another one
+                a[2] += 1
+                a[3] += dur
+                t0_ = ref.elapsed_time(e0) * 1e-3
+                spans.append((t0_, t0_ + dur))
+            m.prof = None
+            # union of the launches' busy intervals over both streams: the time during which AT LEAST ONE 3x3-conv launch held (part of) the
+            # chip. FLOPs over it bills the whole chip for every such moment -- a LOWER bound of the kernels' efficiency, where `achieved`
+            # (duration x planned CU share) is an upper bound whenever the two backward streams do not overlap perfectly (ADVICE r4)
+            spans.sort()
+            union, cur0, cur1 = 0.0, None, None
+            for a0, a1 in spans:
+                if cur1 is None or a0 > cur1:
+                    if cur1 is not None:
+                        union += cur1 - cur0
+                    cur0, cur1 = a0, a1
+                else:
+                    cur1 = max(cur1, a1)
+            if cur1 is not None:
+                union += cur1 - cur0
+            fl = sum(a[0] for a in agg.values())
+            t = sum(a[1] for a in agg.values())
+            n = sum(a[2] for a in agg.values())
+            by = {k: {"tflops": v[0] / v[1] / 1e12, "chip_ms_per_step": v[1] / nprof * 1e3, "wall_ms_per_step": v[3] / nprof * 1e3,
+                      "launches": v[2] // nprof} for k, v in agg.items()}
+            return {"achieved": fl / t / 1e12 if t > 0 else 0.0, "by_kernel": by, "launches": n, "chip_s": t, "flops": fl, "label": label,
+                    "busy_union_s": union}
+
+        # (1) the timed schedule itself: two streams in the backward pass, every launch with the CU share it has there. The conv launches of a
+        # step cannot hold the chip for longer than the step lasts: a pass whose chip time exceeds the timed step by more than 15 % is not a
+        # measurement of that schedule (seen once in ~30 runs on the test pool: both backward queues reported ~6x their usual kernel durations
+        # for one pass, profiles/r04/bench_odd_pass.json) and is repeated, at most twice.
+        attempts = 0
+        while True:
+            attempts += 1
+            prof_timed = instrumented("timed schedule")
+            plausible = prof_timed["chip_s"] / nprof <= 1.15 * dt / args.steps
+            if world > 1:
+                # every rank repeats the pass or none does: its steps hold collectives (round 4: decided per rank, one rank ran a pass more than
+                # its peer and the run ended in "connection reset by peer" -- two of eight two-rank runs on a shared GPU)
+                ok = torch.tensor([1 if plausible else 0], dtype=torch.int32, device=dev if backend == "nccl" else "cpu")
+                dist.all_reduce(ok, op=dist.ReduceOp.MIN)
+                plausible = bool(ok.item())
+            if plausible or attempts >= 3:
                 break
-    except Exception:
-        traffic = None
+        # (2), (3) serialised single-stream passes, every launch alone on the chip: one weight-gradient launch per layer (rounds 1-2's
+        # figure), then the single-stream product schedule with grouped weight gradients (round 3's headline figure)
+        wstreams, m.wstreams = m.wstreams, []
+        if not tune_imported:
+            m.tune()                    # on one stream the backward launches plan for the whole chip: shapes not measured yet
+        wg_env = os.environ.get("RSU_WG_GROUP")
+        os.environ["RSU_WG_GROUP"] = "0"
+        prof_serial = instrumented("single stream, one weight-gradient launch per layer")
+        if wg_env is None:
+            del os.environ["RSU_WG_GROUP"]
+        else:
+            os.environ["RSU_WG_GROUP"] = wg_env
+        prof_grouped = instrumented("single stream, grouped weight gradients") if wstreams else prof_serial
+        m.wstreams = wstreams
+        # (the table of measured tile shapes: saved behind BOTH schedules -- they plan the backward launches for different CU budgets)
+        if tune_file and rank == 0 and not os.path.exists(tune_file):
+            cap = lib().rsu_autotune_entries()
+            arr = (ctypes.c_int * (17 * max(1, cap)))()
+            n = lib().rsu_autotune_export(arr, cap)
+            json.dump({"lib_sha16": lib_sha, "rows": list(arr[:17 * n])}, open(tune_file, "w"))
+
+        two_streams = bool(wstreams)
+        achieved = prof_timed["achieved"]
+        n_launch = prof_timed["launches"]
+        conv_t = prof_timed["chip_s"]
+        conv_fl = prof_timed["flops"]
+        # HBM-side bytes per conv launch: PMC counters cannot be read from inside this process; the figure is the one measured with
+        # tools/pmc_traffic.sh on this same workload and committed under profiles/rNN/traffic.json (null for any other workload)
+        traffic, traffic_source = None, None
+        try:
+            import glob
+            for cand in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*", "traffic.json")), reverse=True):
+                tj = json.load(open(cand))
+                if tj.get("lib_sha16") == lib_sha and (L, root, P, B, args.dilated_layers) == (5, 64, 388, 4, False):
+                    traffic = tj["kernels"]["conv3x3 all"]["hbm_bytes_per_launch"]
+                    traffic_source = os.path.relpath(cand, ROOT) + " (PMC run of this build, lib_sha16 %s)" % lib_sha
+                    break
+        except Exception:
+            traffic = None
+        roofline = {"bound": "mfma", "achieved": achieved, "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
+                    "frac": achieved / MFMA_BF16_PEAK_TFLOPS, "traffic": traffic, "traffic_source": traffic_source,
+                    # the same algorithmic 3x3 FLOPs over the WHOLE timed step (everything else the step does included)
+                    "whole_step_frac": conv3_fl * world / (dt / args.steps) / 1e12 / (MFMA_BF16_PEAK_TFLOPS * world),
+                    "measured_in": ("the schedule `value` is timed on, instrumented: HIP events around every 3x3-conv launch on its own stream; "
+                                    + ("forward launches alone on the chip, in the backward pass one backward-data launch (main stream) beside "
+                                       "one weight-gradient launch per layer (side stream), each planned for its share of the CUs; "
+                                       if two_streams else "one stream, every launch alone on the chip; ")
+                                    + "achieved = algorithmic FLOPs / sum over launches of (duration x share of the 256 CUs the launch plans for)"),
+                    "kernel": "3x3 conv MFMA kernels: igemm_pp / igemm_fwd2 (forward, backward-data) + igemm_wgpp / igemm_wgrad / igemm_wg_group (weight gradient)",
+                    "timed_schedule_pass": {"attempts": attempts, "plausible": bool(plausible)},
+                    "launches_per_step": n_launch // nprof,
+                    "avg_launch_us": sum(v["wall_ms_per_step"] for v in prof_timed["by_kernel"].values()) / max(1, n_launch // nprof) * 1e3,
+                    "conv_chip_ms_per_step": conv_t / nprof * 1e3,
+                    # `frac` prices a launch by the CUs it PLANS for, so it can only overstate when the two backward streams do not overlap
+                    # perfectly (a half-chip launch beside an idle queue, an unconfined split-K launch): it is an UPPER bound of the
+                    # kernels' efficiency. The lower bound bills the whole chip whenever at least one 3x3-conv launch is running (union
+                    # of the launches' busy intervals over both streams); `whole_step_frac` bills it for the whole step.
+                    "frac_busy_union": conv_fl / prof_timed["busy_union_s"] / 1e12 / MFMA_BF16_PEAK_TFLOPS if prof_timed["busy_union_s"] > 0 else None,
+                    "conv_busy_union_ms_per_step": prof_timed["busy_union_s"] / nprof * 1e3,
+                    "algorithmic_gflop_per_step": conv_fl / nprof / 1e9,
+                    "by_kernel": prof_timed["by_kernel"],
+                    # every launch alone on the chip, one stream (no CU shares: chip time == wall time)
+                    "frac_serial_per_layer": prof_serial["achieved"] / MFMA_BF16_PEAK_TFLOPS,
+                    "by_kernel_serial_per_layer": prof_serial["by_kernel"],
+                    "frac_single_stream_grouped": prof_grouped["achieved"] / MFMA_BF16_PEAK_TFLOPS,
+                    "by_kernel_single_stream_grouped": prof_grouped["by_kernel"]}
 
     out = {
         "metric": "388x388 patches/sec fwd+bwd (1/2/4/8 GPU) + conv MFMA % of peak",
@@ -469,37 +560,11 @@ def main():
                                     "tuned_ms_per_step": None if dp_tune is None else {
                                         "%s/%dcu/%dMB" % ("overlapped" if k[0] else "single", k[1], k[2] * 4 >> 20): v
                                         for k, v in dp_tune["ms"].items()}})},
-        "roofline": {"bound": "mfma", "achieved": achieved, "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": achieved / MFMA_BF16_PEAK_TFLOPS, "traffic": traffic, "traffic_source": traffic_source,
-                     # the same algorithmic 3x3 FLOPs over the WHOLE timed step (everything else the step does included)
-                     "whole_step_frac": conv3_fl * world / (dt / args.steps) / 1e12 / (MFMA_BF16_PEAK_TFLOPS * world),
-                     "measured_in": ("the schedule `value` is timed on, instrumented: HIP events around every 3x3-conv launch on its own stream; "
-                                     + ("forward launches alone on the chip, in the backward pass one backward-data launch (main stream) beside "
-                                        "one weight-gradient launch per layer (side stream), each planned for its share of the CUs; "
-                                        if two_streams else "one stream, every launch alone on the chip; ")
-                                     + "achieved = algorithmic FLOPs / sum over launches of (duration x share of the 256 CUs the launch plans for)"),
-                     "kernel": "3x3 conv MFMA kernels: igemm_pp / igemm_fwd2 (forward, backward-data) + igemm_wgpp / igemm_wgrad / igemm_wg_group (weight gradient)",
-                     "timed_schedule_pass": {"attempts": attempts, "plausible": bool(plausible)},
-                     "launches_per_step": n_launch // nprof,
-                     "avg_launch_us": sum(v["wall_ms_per_step"] for v in prof_timed["by_kernel"].values()) / max(1, n_launch // nprof) * 1e3,
-                     "conv_chip_ms_per_step": conv_t / nprof * 1e3,
-                     # `frac` prices a launch by the CUs it PLANS for, so it can only overstate when the two backward streams do not overlap
-                     # perfectly (a half-chip launch beside an idle queue, an unconfined split-K launch): it is an UPPER bound of the
-                     # kernels' efficiency. The lower bound bills the whole chip whenever at least one 3x3-conv launch is running (union
-                     # of the launches' busy intervals over both streams); `whole_step_frac` bills it for the whole step.
-                     "frac_busy_union": conv_fl / prof_timed["busy_union_s"] / 1e12 / MFMA_BF16_PEAK_TFLOPS if prof_timed["busy_union_s"] > 0 else None,
-                     "conv_busy_union_ms_per_step": prof_timed["busy_union_s"] / nprof * 1e3,
-                     "algorithmic_gflop_per_step": conv_fl / nprof / 1e9,
-                     "by_kernel": prof_timed["by_kernel"],
-                     # every launch alone on the chip, one stream (no CU shares: chip time == wall time)
-                     "frac_serial_per_layer": prof_serial["achieved"] / MFMA_BF16_PEAK_TFLOPS,
-                     "by_kernel_serial_per_layer": prof_serial["by_kernel"],
-                     "frac_single_stream_grouped": prof_grouped["achieved"] / MFMA_BF16_PEAK_TFLOPS,
-                     "by_kernel_single_stream_grouped": prof_grouped["by_kernel"]},
+        "roofline": roofline,
     }
     if sustained is not None:
         out["sustained"] = sustained
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             from oracle import torch_ref
             from oracle import unet_oracle as U

@@ -1,4 +1,4 @@
-"""Generates tests/golden/real_crops_trained_params.npz: weights of the L=3, root=32 U-Net trained (HIP path, MI355X) on the 12 training
+"""Generates tests/golden/real_crops_trained_params.part*.npz: weights of the L=3, root=32 U-Net trained (HIP path, MI355X) on the 12 training
 crops of real_crops.npz until the held-out pixel-F1 passes 0.35 -- a fixed, reasonably trained network for the inference-parity test
 (tests/test_gpu_parity_full.py). Training from scratch inside the test made its F1 depend on the summation order of the weight
 gradients (0.38 / 0.15 / 0.0 after 240 steps for builds that differ in nothing else); the comparison HIP vs oracle needs weights, not a
@@ -12,6 +12,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 from road_segmentation_unet_amd.model import ConvolutionalModel, Options, pixel_f1  # noqa: E402
+from tests import golden_store  # noqa: E402
 
 z = np.load(os.path.join(HERE, "real_crops.npz"))
 x = z["x"].astype(np.float64) / 255.0
@@ -45,6 +46,6 @@ for epoch in range(400):
             best = f
             break
 params = {k: v for k, v in m.net.state_dict().items() if not k.endswith("/Momentum") and k != "global_step"}
-out = os.environ.get("OUT", os.path.join(HERE, "real_crops_trained_params.npz"))
-np.savez_compressed(out, **{k.replace("/", "__"): np.asarray(v, np.float32) for k, v in params.items()})
+out = os.environ.get("OUT", os.path.join(HERE, "real_crops_trained_params"))   # -> <out>.partNN.npz (tests/golden_store.py)
+golden_store.save(out, **{k.replace("/", "__"): np.asarray(v, np.float32) for k, v in params.items()})
 print("saved %s (held-out F1 %.4f, %d arrays, %.2f MB)" % (out, best, len(params), os.path.getsize(out) / 1e6))

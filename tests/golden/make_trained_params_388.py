@@ -1,4 +1,4 @@
-"""Generates tests/golden/real388_trained_params.npz + tests/golden/real388_heldout.npz: an L=5, root=16 U-Net (patch_size 388, input 572:
+"""Generates tests/golden/real388_trained_params.part*.npz + tests/golden/real388_heldout.part*.npz: an L=5, root=16 U-Net (patch_size 388, input 572:
 the BASELINE geometry at a quarter of the width) trained by the HIP path (MI355X) on 96 of the reference's 100 real 400-px training
 images until the pixel-F1 on the 4 held-out images passes 0.8, and those 4 held-out images with their ground truth. The inference-parity
 test (tests/test_gpu_parity_full.py::test_real_388_patches_pixel_f1_within_1e3_of_the_float32_oracle) runs the held-out 388-patches
@@ -18,6 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 from road_segmentation_unet_amd import images as dimages  # noqa: E402
 from road_segmentation_unet_amd.model import ConvolutionalModel, Options, pixel_f1  # noqa: E402
 from road_segmentation_unet_amd.unet import input_size_needed  # noqa: E402
+from tests import golden_store  # noqa: E402
 
 z = np.load(os.path.join(HERE, "_train388_data.npz"))
 x8, y8 = z["x"], z["y"]
@@ -79,7 +80,7 @@ for epoch in range(int(os.environ.get("EPOCHS", "120"))):
             params = {k_: v for k_, v in m.net.state_dict().items() if not k_.endswith("/Momentum") and k_ != "global_step"}
         if f >= target and epoch >= 19:
             break
-out = os.environ.get("OUT", os.path.join(HERE, "real388_trained_params.npz"))
-np.savez_compressed(out, **{k_.replace("/", "__"): np.asarray(v, np.float32) for k_, v in params.items()})
-np.savez_compressed(os.path.join(os.path.dirname(out), "real388_heldout.npz"), x=x8[held], y=y8[held], held=np.asarray(held), P=P, S=S, L=L, root=root)
+out = os.environ.get("OUT", os.path.join(HERE, "real388_trained_params"))   # -> <out>.partNN.npz (tests/golden_store.py)
+golden_store.save(out, **{k_.replace("/", "__"): np.asarray(v, np.float32) for k_, v in params.items()})
+golden_store.save(os.path.join(os.path.dirname(out), "real388_heldout"), x=x8[held], y=y8[held], held=np.asarray(held), P=P, S=S, L=L, root=root)
 print("saved %s (best held-out F1 %.4f, %.2f MB)" % (out, best, os.path.getsize(out) / 1e6))

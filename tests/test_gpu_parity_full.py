@@ -20,6 +20,7 @@ from oracle import tiler_oracle as T  # noqa: E402
 from oracle import unet_oracle as U  # noqa: E402
 from road_segmentation_unet_amd.model import ConvolutionalModel, Options, pixel_f1  # noqa: E402
 from road_segmentation_unet_amd.unet import UNet  # noqa: E402
+from tests import golden_store  # noqa: E402
 from tests import hiputil as hu  # noqa: E402
 from tests.parity_record import record  # noqa: E402
 
@@ -39,7 +40,7 @@ def _predict_hip(net, xs, B):
 
 
 def test_real_crops_pixel_f1_within_1e3_of_the_float32_oracle():
-    """Held-out real crops through a TRAINED network (tests/golden/real_crops_trained_params.npz: the L=3, root=32 net after 90 epochs
+    """Held-out real crops through a TRAINED network (tests/golden/real_crops_trained_params.part*.npz: the L=3, root=32 net after 90 epochs
     on the 12 training crops, written by tests/golden/make_trained_params.py): pixel-F1 of the HIP path within 1e-3 of the float32
     oracle with the same weights. (Training inside the test made the F1 hinge on the summation order of the weight gradients: 0.38,
     0.15 and 0.0 after 240 steps for three builds that differ in nothing else -- see the next test for the training side.)"""
@@ -50,8 +51,8 @@ def test_real_crops_pixel_f1_within_1e3_of_the_float32_oracle():
     L, root, B = 3, 32, 4
     assert S == U.input_size_needed(P, L)
     xte, yte = x[12:], y[12:]
-    pz = np.load(os.path.join(HERE, "golden", "real_crops_trained_params.npz"))
-    params = {k.replace("__", "/"): pz[k] for k in pz.files}
+    pz = golden_store.load(os.path.join(HERE, "golden", "real_crops_trained_params"))   # (stored in parts: tests/golden_store.py)
+    params = {k.replace("__", "/"): v for k, v in pz.items()}
     net = UNet(L, root, False, B, P, params=params, training=False)
     hip = _predict_hip(net, xte, B)
     ref = U.predict_probs(params, xte.astype(np.float32), L, root, False)                       # float32 oracle
@@ -242,12 +243,12 @@ def test_config4_share_full_size_backward_layers_match_oracle(B):
 
 def test_real_388_patches_pixel_f1_within_1e3_of_the_float32_oracle():
     """The north_star's F1 claim on 388-px patches: the 16 held-out 388-patches (4 real 400-px images of the reference's training set,
-    stride 12: 2.4 M pixels) through an L=5, root=16 U-Net trained on the other 96 images (tests/golden/real388_trained_params.npz,
+    stride 12: 2.4 M pixels) through an L=5, root=16 U-Net trained on the other 96 images (tests/golden/real388_trained_params.part*.npz,
     written by tests/golden/make_trained_params_388.py on the GPU): pixel-F1 of the HIP path within 1e-3 of the float32 oracle with
     the same weights, and the probabilities within the stated bf16 tolerance of the rounding-emulating oracle."""
-    z = np.load(os.path.join(HERE, "golden", "real388_heldout.npz"))
-    pz = np.load(os.path.join(HERE, "golden", "real388_trained_params.npz"))
-    params = {k.replace("__", "/"): pz[k] for k in pz.files}
+    z = golden_store.load(os.path.join(HERE, "golden", "real388_heldout"))
+    pz = golden_store.load(os.path.join(HERE, "golden", "real388_trained_params"))
+    params = {k.replace("__", "/"): v for k, v in pz.items()}
     L, root, P, S = int(z["L"]), int(z["root"]), int(z["P"]), int(z["S"])
     x = z["x"].astype(np.float32) / 255.0
     y = (z["y"].astype(np.float32) / 255.0 >= 0.5) * 1.0

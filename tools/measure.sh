@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (GPU box): tools/measure.sh  -> gpurun_out/${ROUND:-r06}/: the round's measured artefacts (copied to profiles/${ROUND:-r06}/ afterwards)
-#   bench.json            python bench.py (default flags: two-stream timed region, roofline = chip time of that schedule, CPU baselines)
-#   bench_c3.json / bench_c4.json   python bench.py --workload c3 / c4
+#   bench.json            python bench.py --full (default flags otherwise: two-stream timed region, roofline = chip time of that schedule, CPU baselines)
+#   bench_c3.json / bench_c4.json   python bench.py --full --workload c3 / c4
 #   kernel_stats.csv      rocprofv3 --kernel-trace --stats of the same command in the DEFAULT two-stream schedule (tile shapes imported: no timing
 #                         launches)
 #   traffic.json          two --pmc passes (FETCH_SIZE / WRITE_SIZE) over the same command, stamped with the library's hash
@@ -12,16 +12,16 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/${ROUND:-r06}
 mkdir -p $OUT $REPO/profiles/${ROUND:-r06}
 export RSU_AUTOTUNE_FILE=$OUT/autotune.json
-python3 $REPO/bench.py > $OUT/bench.json 2> $OUT/bench.err
+python3 $REPO/bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 unset RSU_AUTOTUNE_FILE
-python3 $REPO/bench.py --workload c4 --no_cpu_baseline > $OUT/bench_c4.json 2> $OUT/bench_c4.err
-python3 $REPO/bench.py --workload c3 --no_cpu_baseline > $OUT/bench_c3.json 2> $OUT/bench_c3.err
+python3 $REPO/bench.py --full --workload c4 --no_cpu_baseline > $OUT/bench_c4.json 2> $OUT/bench_c4.err
+python3 $REPO/bench.py --full --workload c3 --no_cpu_baseline > $OUT/bench_c3.json 2> $OUT/bench_c3.err
 export RSU_AUTOTUNE_FILE=$OUT/autotune.json
 cd /tmp && export TMPDIR=/tmp
 STEPS=10; WARM=2
-rocprofv3 --kernel-trace --stats -d $OUT/prof -o prof -- python3 $REPO/bench.py --steps $STEPS --warmup $WARM --no_cpu_baseline --sustain_seconds 0 > $OUT/prof.log 2>&1
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc -o rd -- python3 $REPO/bench.py --steps 3 --warmup 1 --no_cpu_baseline --sustain_seconds 0 > $OUT/log_rd.txt 2>&1
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc -o wr -- python3 $REPO/bench.py --steps 3 --warmup 1 --no_cpu_baseline --sustain_seconds 0 > $OUT/log_wr.txt 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/prof -o prof -- python3 $REPO/bench.py --full --steps $STEPS --warmup $WARM --no_cpu_baseline --sustain_seconds 0 > $OUT/prof.log 2>&1
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc -o rd -- python3 $REPO/bench.py --full --steps 3 --warmup 1 --no_cpu_baseline --sustain_seconds 0 > $OUT/log_rd.txt 2>&1
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc -o wr -- python3 $REPO/bench.py --full --steps 3 --warmup 1 --no_cpu_baseline --sustain_seconds 0 > $OUT/log_wr.txt 2>&1
 python3 - <<PY
 import sqlite3, glob, csv, collections, json, hashlib
 dbs = glob.glob("$OUT/prof/**/*.db", recursive=True)
@@ -52,7 +52,7 @@ if dbs:
         e = fam.setdefault(family(n), [0, 0])
         e[0] += c; e[1] += t
     with open("$OUT/kernel_stats_per_step.md", "w") as f:
-        f.write("Per-step view of kernel_stats.csv (rocprofv3 --kernel-trace --stats of \`python3 bench.py --steps $STEPS --warmup $WARM --no_cpu_baseline --sustain_seconds 0\`,\n"
+        f.write("Per-step view of kernel_stats.csv (rocprofv3 --kernel-trace --stats of \`python3 bench.py --full --steps $STEPS --warmup $WARM --no_cpu_baseline --sustain_seconds 0\`,\n"
                 "the default two-stream schedule: in the backward pass a backward-data and a weight-gradient kernel run side by side on 128 CUs each, so their durations are those beside the other; %d steps in the trace incl. warm-up, priming and the three instrumented passes, of which two are single-stream)\n\n" % nsteps)
         f.write("| kernel family | launches / step | ms / step | avg us |\n|---|---|---|---|\n")
         tt = 0.0
@@ -76,7 +76,7 @@ def wg(k):
 fams = {"igemm_pp + igemm_fwd2 3x3 + k_conv_first_fwd (forward, backward-data)": lambda k: conv3(k) and not wg(k),
         "weight gradient launches (igemm_wgpp / igemm_wgp64 / igemm_wgrad per layer; igemm_wg_group in the grouped instrumented pass; level-0 conv1 = igemm_wg1)": lambda k: conv3(k) and wg(k),
         "k_reduce_slabs*": lambda k: "k_reduce_slabs" in k, "conv3x3 all": conv3}
-out = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace) over python3 bench.py --steps 3 --warmup 1, default two-stream schedule, "
+out = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace) over python3 bench.py --full --steps 3 --warmup 1, default two-stream schedule, "
                  "tile shapes of the bench run imported (tools/measure.sh); raw counter unit KiB; gfx950: FETCH_SIZE x 2 for 16-byte-per-lane reads",
        "workload": "num_layers=5 root_size=64 patch_size=388 batch 4",
        "lib_sha16": hashlib.sha256(open("$REPO/road_segmentation_unet_amd/librsu_hip.so", "rb").read()).hexdigest()[:16], "kernels": {}}
@@ -96,7 +96,7 @@ rm -rf $OUT/prof $OUT/pmc
 cd $REPO
 # the contract line once more, now that traffic.json carries this library's hash (bench.py reads profiles/${ROUND:-r06}/traffic.json): this is bench.json
 cp $OUT/traffic.json $REPO/profiles/${ROUND:-r06}/traffic.json
-python3 $REPO/bench.py > $OUT/bench.json 2> $OUT/bench.err
+python3 $REPO/bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 python3 tools/bench_predict.py --L 6 --dilated --images 1 --stride 12 --size 604 --batch 8 2>/dev/null | tail -1 > $OUT/predict_c5.txt
 python3 tools/bench_predict.py --L 6 --dilated --images 10 --stride 110 --size 608 --batch 1 2>/dev/null | tail -1 > $OUT/predict_ref.txt
 python3 - <<PY

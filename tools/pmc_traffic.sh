@@ -6,8 +6,8 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/traffic_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT -o rd -- python3 $REPO/bench.py --steps 3 --warmup 1 --no_cpu_baseline > $OUT/log_rd.txt 2>&1
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT -o wr -- python3 $REPO/bench.py --steps 3 --warmup 1 --no_cpu_baseline > $OUT/log_wr.txt 2>&1
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT -o rd -- python3 $REPO/bench.py --full --steps 3 --warmup 1 --no_cpu_baseline > $OUT/log_rd.txt 2>&1
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT -o wr -- python3 $REPO/bench.py --full --steps 3 --warmup 1 --no_cpu_baseline > $OUT/log_wr.txt 2>&1
 python3 - <<PY
 import csv, glob, collections, json
 def agg(pat, name):

@@ -6,7 +6,7 @@ NAME=$1; shift
 LIBS=${@:-road_segmentation_unet_amd/librsu_hip.so}
 for lib in $LIBS; do
   echo "== $lib"
-  RSU_LIB_PATH=$REPO/$lib python3 bench.py --steps 20 --warmup 3 --no_cpu_baseline --sustain_seconds 12 > /tmp/pb.json 2>/dev/null &
+  RSU_LIB_PATH=$REPO/$lib python3 bench.py --full --steps 20 --warmup 3 --no_cpu_baseline --sustain_seconds 12 > /tmp/pb.json 2>/dev/null &
   BP=$!
   sleep 7
   for i in $(seq 1 14); do

@@ -6,7 +6,7 @@ TAG=$1; shift
 for kv in "$@"; do export "$kv"; done
 cd /tmp && export TMPDIR=/tmp
 rm -rf $OUT/prof_$TAG
-rocprofv3 --kernel-trace -d $OUT/prof_$TAG -o t -- python3 $REPO/bench.py --steps 6 --warmup 2 --no_cpu_baseline --sustain_seconds 0 $EXTRA_BENCH > $OUT/prof_$TAG.log 2>&1
+rocprofv3 --kernel-trace -d $OUT/prof_$TAG -o t -- python3 $REPO/bench.py --full --steps 6 --warmup 2 --no_cpu_baseline --sustain_seconds 0 $EXTRA_BENCH > $OUT/prof_$TAG.log 2>&1
 python3 - <<PY
 import sqlite3, glob
 dbs = glob.glob("$OUT/prof_$TAG/**/*.db", recursive=True)
