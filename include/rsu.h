@@ -323,6 +323,23 @@ int rsu_update_table_finish(void* host_table, int nentries, int* total_blocks);
 int rsu_update_table_run(const void* dev_table, int nentries, int total_blocks, float lr, float mu, float gscale,
                          rsu_stream_t stream);
 
+/* ---- optimizer: tf.train.AdamOptimizer (new; the reference trains with Momentum only) -------- */
+/* TensorFlow 1.x ApplyAdam, float32, in this order (IEEE sqrt and divide, no contraction):
+ *   g' = gscale*g ; m += (g' - m)*(1 - beta1) ; v += (g'*g' - v)*(1 - beta2) ; w -= (m*alpha) / (sqrt(v) + epsilon)
+ * with alpha = lr_t * sqrt(1 - beta2^t) / (1 - beta1^t) computed by the caller in float32 (AdamOptimizer._apply_dense; beta1^t and
+ * beta2^t are the float32 `beta1_power` / `beta2_power` accumulators, multiplied by beta1 / beta2 after every step as
+ * AdamOptimizer._finish does). gscale folds the 1/world_size of data-parallel averaging. w, m, v, g 16-byte aligned. */
+int rsu_adam_step(float* w, float* m, float* v, const float* g, float alpha, float beta1, float beta2, float epsilon, float gscale,
+                  long n, rsu_stream_t stream);
+/* The Adam step of every live variable and the re-pack of the MFMA copies in ONE launch: the table of rsu_update_table_add[_plain]
+ * (its `acc` is Adam's first slot m) plus, per entry, the second slot v given by rsu_update_table_set_second_slot (16-byte aligned,
+ * same extent as acc) before rsu_update_table_finish. Reads w, m, v, g once, writes w, m, v and the packed layouts: 32 B per weight of
+ * a packed conv kernel, 28 B per plain-range float (Momentum: 24 B and 20 B). Same arithmetic per element as rsu_adam_step, same
+ * packed bits as rsu_pack_*. */
+int rsu_update_table_set_second_slot(void* host_table, int index, float* v);
+int rsu_update_table_run_adam(const void* dev_table, int nentries, int total_blocks, float alpha, float beta1, float beta2,
+                              float epsilon, float gscale, rsu_stream_t stream);
+
 /* ---- patch / stride tiler (src/images.py) -------------------------------------------------- */
 /* images.py:269-281 mirror_border + :35-85 extract_patches fused, on device: tile t (x-outer,
  * y-inner order, images.py:76-77) of image n is the [S][S] window of the symmetric-padded image at

@@ -101,6 +101,9 @@ SIGNATURES = {
     "rsu_update_table_add": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, ctypes.POINTER(_vp), _i, _i, _PI, _i]),
     "rsu_update_table_finish": (_i, [_vp, _i, _PI]),
     "rsu_update_table_run": (_i, [_vp, _i, _i, _f, _f, _f, _vp]),
+    "rsu_adam_step": (_i, [_vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _l, _vp]),
+    "rsu_update_table_set_second_slot": (_i, [_vp, _i, _vp]),
+    "rsu_update_table_run_adam": (_i, [_vp, _i, _i, _f, _f, _f, _f, _f, _vp]),
     "rsu_extract_tiles": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _l, _l, _vp]),
     "rsu_overlap_add": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _l, _l, _vp]),
     "rsu_overlap_finish": (_i, [_vp, _vp, _vp, _l, _vp]),

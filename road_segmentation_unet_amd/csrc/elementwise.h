@@ -36,6 +36,17 @@ hipError_t ew_head(bool train, const void* act, const float* w, const float* b, 
                    float* db, float* loss_sum, float* ws, long npix, int C, float inv_count, hipStream_t st);
 hipError_t ew_color_adjust_bwd(const float* gx, const float* w1, float* dW0, float* db0, int Cout, float scale, int accumulate, hipStream_t st);
 hipError_t ew_momentum(float* w, float* acc, const float* g, float lr, float mu, float gscale, long n, hipStream_t st);
+// the update rules of the optimizer passes (template argument of k_update_pack_many): their scalars, passed by value to the kernels.
+// kSecondSlot: the rule keeps a second fp32 slot per weight (UpJob::v)
+struct MomentumRule {   // acc = mu * acc + gscale * g; w -= lr * acc
+    float lr, mu, gscale;
+    static constexpr bool kSecondSlot = false;
+};
+struct AdamRule {       // TensorFlow 1.x ApplyAdam with alpha = lr_t * sqrt(1 - beta2^t) / (1 - beta1^t) from the host (elementwise.hip, adam_elem)
+    float alpha, beta1, beta2, epsilon, gscale;
+    static constexpr bool kSecondSlot = true;
+};
+hipError_t ew_adam(float* w, float* m, float* v, const float* g, const AdamRule& h, long n, hipStream_t st);
 hipError_t ew_pack(const float* src, void* dst, const PackParams& pp, hipStream_t st);
 struct PackJob { PackParams pp; const float* src; bf16_t* dst; int block_start; int pad_; };
 hipError_t ew_pack_many(const PackJob* jobs_dev, int njobs, int total_blocks, hipStream_t st);
@@ -59,9 +70,11 @@ struct UpJob {
     int ndest;
     UpDest d[2];
     int block_start, pad_;
+    float* v;               // the second slot of a rule that keeps one (Adam: v; `acc` is its m), else unused
 };
 int ew_update_job_blocks(const UpJob& j);
 hipError_t ew_update_pack_many(const UpJob* jobs_dev, int njobs, int total_blocks, float lr, float mu, float gscale, hipStream_t st);
+hipError_t ew_update_pack_many_adam(const UpJob* jobs_dev, int njobs, int total_blocks, const AdamRule& h, hipStream_t st);
 // the same pass over ONE R1 segment of one tensor, its gradient = the ordered sum of `nsplit` weight-gradient slabs (k_update_pack_seg)
 hipError_t ew_update_pack_seg(const UpJob& J, int seg, const float* slab, long stride, int nsplit, float* gout, float* out2, int n2, float lr, float mu,
                               float gscale, hipStream_t st);

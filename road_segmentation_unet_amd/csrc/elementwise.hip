@@ -572,6 +572,42 @@ __global__ void __launch_bounds__(768) k_color_adjust_bwd(const float* __restric
 }
 
 // ---------------------------------------------------------------------------------------------
+// Adam (tf.train.AdamOptimizer, TensorFlow 1.x ApplyAdam): the per-element update of rsu_adam_step and of the Adam instantiation of
+// k_update_pack_many -- ONE function, so both give the same bits. float32 in TensorFlow's operation order, IEEE sqrt and divide, no
+// contraction (an FMA where ApplyAdam rounds twice would move the last bit between this kernel and a float32 restatement).
+// alpha = lr_t * sqrt(1 - beta2^t) / (1 - beta1^t) comes from the host (AdamRule).
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void adam_elem(float& w, float& m, float& v, float g, const AdamRule& h) {
+#pragma clang fp contract(off)
+    const float gs = h.gscale * g;
+    m += (gs - m) * (1.f - h.beta1);
+    v += (gs * gs - v) * (1.f - h.beta2);
+    w -= (m * h.alpha) / (sqrtf(v) + h.epsilon);
+}
+__device__ __forceinline__ void adam_elem4(f32x4& w, f32x4& m, f32x4& v, const f32x4 g, const AdamRule& h) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        float wj = w[j], mj = m[j], vj = v[j];
+        adam_elem(wj, mj, vj, g[j], h);
+        w[j] = wj; m[j] = mj; v[j] = vj;
+    }
+}
+__global__ void k_adam(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v, const float* __restrict__ g, AdamRule h, long n) {
+    const long n4 = n >> 2;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        f32x4 mv = ((f32x4*)m)[i], vv = ((f32x4*)v)[i], gv = ((const f32x4*)g)[i], wv = ((f32x4*)w)[i];
+        adam_elem4(wv, mv, vv, gv, h);
+        ((f32x4*)m)[i] = mv;
+        ((f32x4*)v)[i] = vv;
+        ((f32x4*)w)[i] = wv;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const long i = (n4 << 2) + threadIdx.x;
+        adam_elem(w[i], m[i], v[i], g[i], h);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // momentum SGD (tf_aerial_images.py:116-121)
 // ---------------------------------------------------------------------------------------------
 __global__ void k_momentum(float* __restrict__ w, float* __restrict__ acc, const float* __restrict__ g, float lr, float mu, float gscale, long n) {
@@ -907,6 +943,10 @@ hipError_t ew_momentum(float* w, float* acc, const float* g, float lr, float mu,
     hipLaunchKernelGGL(k_momentum, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0, st, w, acc, g, lr, mu, gscale, n);
     return hipGetLastError();
 }
+hipError_t ew_adam(float* w, float* m, float* v, const float* g, const AdamRule& h, long n, hipStream_t st) {
+    hipLaunchKernelGGL(k_adam, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0, st, w, m, v, g, h, n);
+    return hipGetLastError();
+}
 hipError_t ew_pack(const float* src, void* dst, const PackParams& pp, hipStream_t st) {
     const long total = (long)pp.nchunks * pp.ntap * pp.ntiles * 512;
     hipLaunchKernelGGL(k_pack, dim3(grid_for(total, 256)), dim3(256), 0, st, src, (bf16_t*)dst, pp);
@@ -943,13 +983,24 @@ __device__ __forceinline__ f32x4 up_ld_stream(const f32x4* p) { return UP_NT >= 
 __device__ __forceinline__ f32x4 up_ld_state(const f32x4* p) { return UP_NT >= 2 ? __builtin_nontemporal_load(p) : *p; }
 __device__ __forceinline__ void up_st_state(f32x4* p, f32x4 v) { if (UP_NT >= 2) __builtin_nontemporal_store(v, p); else *p = v; }
 __device__ __forceinline__ void up_st_stream(u32x4* p, u32x4 v) { if (UP_NT >= 1) __builtin_nontemporal_store(v, p); else *p = v; }
+// the update rules of the pass, on a float4 of weights (w, first slot a, second slot v, gradient g)
+__device__ __forceinline__ void up_step(const MomentumRule& h, f32x4& w, f32x4& a, f32x4&, const f32x4 g) {
+    a = h.mu * a + h.gscale * g;
+    w -= h.lr * a;
+}
+__device__ __forceinline__ void up_step(const AdamRule& h, f32x4& w, f32x4& a, f32x4& v, const f32x4 g) { adam_elem4(w, a, v, g, h); }
+__device__ __forceinline__ void up_step1(const MomentumRule& h, float* w, float* a, float*, const float* g) {
+    const float an = h.mu * *a + h.gscale * *g;
+    *a = an;
+    *w -= h.lr * an;
+}
+__device__ __forceinline__ void up_step1(const AdamRule& h, float* w, float* a, float* v, const float* g) { adam_elem(*w, *a, *v, *g, h); }
 }  // namespace
 // One workgroup of the packed-tensor path: block (tap, 32-row block rb, group cg of four 32-column blocks) of tensor J. `grad(i)` returns
 // the gradient float4 at float4 index i of the source tensor (k_update_pack_many: the gradient buffer; k_update_pack_seg: the ordered sum
-// of the weight-gradient slabs).
-template <typename GradFn>
-__device__ __forceinline__ void update_pack_block(const UpJob& J, float (*tile)[32][33], int tap, int rb, int cg, float lr, float mu, float gscale,
-                                                  GradFn grad) {
+// of the weight-gradient slabs). Rule: MomentumRule or AdamRule (the second slot J.v is read in the same batch as w, acc and g).
+template <typename Rule, typename GradFn>
+__device__ __forceinline__ void update_pack_block(const UpJob& J, float (*tile)[32][33], int tap, int rb, int cg, const Rule& h, GradFn grad) {
     int seg = 0;
     while (seg + 1 < J.nseg && rb >= J.seg_blk0[seg + 1]) ++seg;
     const int rbs = rb - J.seg_blk0[seg];                // 32-row block inside its segment
@@ -958,17 +1009,18 @@ __device__ __forceinline__ void update_pack_block(const UpJob& J, float (*tile)[
     const int r = threadIdx.x >> 3, c4 = (threadIdx.x & 7) * 4;
     // every load of the workgroup's four blocks is issued before the first store: w / acc are read and written through the same (non-restrict)
     // pointers, so a store in front of a later block's loads would order them -- four dependent round trips to memory instead of one
-    f32x4 av[4], gv[4], wv[4];
+    f32x4 av[4], gv[4], wv[4], vv[4];
     long idx[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int cb = cg * 4 + q, c0 = cb * 32;
         idx[q] = -1;
-        av[q] = gv[q] = wv[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+        av[q] = gv[q] = wv[q] = vv[q] = f32x4{0.f, 0.f, 0.f, 0.f};
         if (cb < J.ncb && r < vr && c0 + c4 < J.R2) {   // (R2 is a multiple of 4: a float4 is inside or outside as a whole)
             const long i = (((long)tap * J.R1 + r0 + r) * J.R2 + c0 + c4) >> 2;
             idx[q] = i;
             av[q] = up_ld_state((const f32x4*)J.acc + i);
+            if constexpr (Rule::kSecondSlot) vv[q] = up_ld_state((const f32x4*)J.v + i);
             gv[q] = grad(i);
             wv[q] = up_ld_state((const f32x4*)J.w + i);
         }
@@ -976,9 +1028,9 @@ __device__ __forceinline__ void update_pack_block(const UpJob& J, float (*tile)[
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         if (idx[q] >= 0) {
-            av[q] = mu * av[q] + gscale * gv[q];
-            wv[q] -= lr * av[q];
+            up_step(h, wv[q], av[q], vv[q], gv[q]);
             up_st_state((f32x4*)J.acc + idx[q], av[q]);
+            if constexpr (Rule::kSecondSlot) up_st_state((f32x4*)J.v + idx[q], vv[q]);
             up_st_state((f32x4*)J.w + idx[q], wv[q]);
         }
         tile[q][r][c4] = wv[q][0]; tile[q][r][c4 + 1] = wv[q][1]; tile[q][r][c4 + 2] = wv[q][2]; tile[q][r][c4 + 3] = wv[q][3];
@@ -1014,7 +1066,8 @@ __device__ __forceinline__ void update_pack_block(const UpJob& J, float (*tile)[
         up_st_stream((u32x4*)(base + e), o);
     }
 }
-__global__ void __launch_bounds__(256) k_update_pack_many(const UpJob* __restrict__ jobs, int njobs, float lr, float mu, float gscale) {
+template <typename Rule>
+__global__ void __launch_bounds__(256) k_update_pack_many(const UpJob* __restrict__ jobs, int njobs, Rule h) {
     __shared__ int sj;
     __shared__ float tile[4][32][33];
     if (threadIdx.x < 64) {
@@ -1028,24 +1081,23 @@ __global__ void __launch_bounds__(256) k_update_pack_many(const UpJob* __restric
     __syncthreads();
     const UpJob& J = jobs[sj];
     const int b = blockIdx.x - J.block_start;
-    if (J.kind == 0) {   // plain Momentum over a contiguous range (k_momentum's arithmetic)
+    if (J.kind == 0) {   // the rule over a contiguous range (the arithmetic of k_momentum / k_adam)
         const long n = J.n, n4 = n >> 2;
         const long i0 = (long)b * (UP_EPB / 4);
         for (int q = 0; q < UP_EPB / 4 / 256; ++q) {
             const long i = i0 + q * 256 + threadIdx.x;
             if (i < n4) {
-                f32x4 a = ((f32x4*)J.acc)[i], gv = ((const f32x4*)J.g)[i], wv = ((f32x4*)J.w)[i];
-                a = mu * a + gscale * gv;
-                wv -= lr * a;
+                f32x4 a = ((f32x4*)J.acc)[i], gv = ((const f32x4*)J.g)[i], wv = ((f32x4*)J.w)[i], vv = {0.f, 0.f, 0.f, 0.f};
+                if constexpr (Rule::kSecondSlot) vv = ((f32x4*)J.v)[i];
+                up_step(h, wv, a, vv, gv);
                 ((f32x4*)J.acc)[i] = a;
+                if constexpr (Rule::kSecondSlot) ((f32x4*)J.v)[i] = vv;
                 ((f32x4*)J.w)[i] = wv;
             }
         }
         if (b == 0 && threadIdx.x < (n & 3)) {
             const long i = (n4 << 2) + threadIdx.x;
-            const float a = mu * J.acc[i] + gscale * J.g[i];
-            J.acc[i] = a;
-            J.w[i] -= lr * a;
+            up_step1(h, J.w + i, J.acc + i, Rule::kSecondSlot ? J.v + i : nullptr, J.g + i);
         }
         return;
     }
@@ -1053,7 +1105,7 @@ __global__ void __launch_bounds__(256) k_update_pack_many(const UpJob* __restric
     const int ncg = (J.ncb + 3) >> 2;
     const int cg = b % ncg, rb = (b / ncg) % J.nrb, tap = b / (ncg * J.nrb);
     const float* gp = J.g;
-    update_pack_block(J, tile, tap, rb, cg, lr, mu, gscale, [gp](long i) { return up_ld_stream((const f32x4*)gp + i); });
+    update_pack_block(J, tile, tap, rb, cg, h, [gp](long i) { return up_ld_stream((const f32x4*)gp + i); });
 }
 // The same pass for ONE concat source (R1 segment `seg`) of ONE conv kernel, fed by the weight-gradient slabs of that source instead of a
 // finished gradient: the reduce launch of the slabs IS the update (the fp32 gradient is neither written nor re-read,
@@ -1094,7 +1146,7 @@ __global__ void __launch_bounds__(256) k_update_pack_seg(const UpJob J, int seg,
     const int ncg = (J.ncb + 3) >> 2;
     const int nrb_seg = (J.seg_c[seg] + 31) >> 5;
     const int cg = b % ncg, rb = J.seg_blk0[seg] + (b / ncg) % nrb_seg, tap = b / (ncg * nrb_seg);
-    update_pack_block(J, tile, tap, rb, cg, lr, mu, gscale, [=](long i) {
+    update_pack_block(J, tile, tap, rb, cg, MomentumRule{lr, mu, gscale}, [=](long i) {
         const f32x4 g = slab_sum(slab, stride, nsplit, i * 4);
         if (gout && nsplit > 1) *(f32x4*)(gout + i * 4) = g;
         return g;
@@ -1113,7 +1165,11 @@ int ew_update_job_blocks(const UpJob& j) {
     return j.ntap * j.nrb * ((j.ncb + 3) >> 2);
 }
 hipError_t ew_update_pack_many(const UpJob* jobs_dev, int njobs, int total_blocks, float lr, float mu, float gscale, hipStream_t st) {
-    hipLaunchKernelGGL(k_update_pack_many, dim3(total_blocks), dim3(256), 0, st, jobs_dev, njobs, lr, mu, gscale);
+    hipLaunchKernelGGL(k_update_pack_many<MomentumRule>, dim3(total_blocks), dim3(256), 0, st, jobs_dev, njobs, MomentumRule{lr, mu, gscale});
+    return hipGetLastError();
+}
+hipError_t ew_update_pack_many_adam(const UpJob* jobs_dev, int njobs, int total_blocks, const AdamRule& h, hipStream_t st) {
+    hipLaunchKernelGGL(k_update_pack_many<AdamRule>, dim3(total_blocks), dim3(256), 0, st, jobs_dev, njobs, h);
     return hipGetLastError();
 }
 hipError_t ew_extract_tiles(const float* imgs, float* tiles, int H, int S, int P, int stride, int pps, long t0, long ntiles, hipStream_t st) {

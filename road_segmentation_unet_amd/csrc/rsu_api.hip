@@ -398,6 +398,21 @@ extern "C" int rsu_update_table_run(const void* dev_table, int nentries, int tot
     HIP_CHECK_RET(ew_update_pack_many((const UpJob*)dev_table, nentries, total_blocks, lr, mu, gscale, (hipStream_t)stream));
     return RSU_OK;
 }
+// ---- the same pass under tf.train.AdamOptimizer: `acc` of an entry is m, v comes from rsu_update_table_set_second_slot
+extern "C" int rsu_update_table_set_second_slot(void* host_table, int index, float* v) {
+    if (!host_table || index < 0 || !v || ((uintptr_t)v & 15)) return RSU_EINVAL;
+    UpJob* t = (UpJob*)host_table + index;
+    if (!t->w || !t->acc || !t->g) return RSU_EINVAL;   // not an entry of rsu_update_table_add[_plain]
+    t->v = v;
+    return RSU_OK;
+}
+extern "C" int rsu_update_table_run_adam(const void* dev_table, int nentries, int total_blocks, float alpha, float beta1, float beta2, float epsilon,
+                                         float gscale, rsu_stream_t stream) {
+    if (!dev_table || nentries < 1 || total_blocks < 1) return RSU_EINVAL;
+    HIP_CHECK_RET(ew_update_pack_many_adam((const UpJob*)dev_table, nentries, total_blocks, AdamRule{alpha, beta1, beta2, epsilon, gscale},
+                                           (hipStream_t)stream));
+    return RSU_OK;
+}
 
 // ---------------------------------------------------------------------------------------------
 // VALU head / tail
@@ -1438,6 +1453,13 @@ extern "C" int rsu_momentum_step(float* w, float* acc, const float* g, float lr,
     if (!w || !acc || !g || n < 1) return RSU_EINVAL;
     if (((uintptr_t)w | (uintptr_t)acc | (uintptr_t)g) & 15) return RSU_EINVAL;
     HIP_CHECK_RET(ew_momentum(w, acc, g, lr, mu, gscale, n, (hipStream_t)stream));
+    return RSU_OK;
+}
+extern "C" int rsu_adam_step(float* w, float* m, float* v, const float* g, float alpha, float beta1, float beta2, float epsilon, float gscale,
+                             long n, rsu_stream_t stream) {
+    if (!w || !m || !v || !g || n < 1) return RSU_EINVAL;
+    if (((uintptr_t)w | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g) & 15) return RSU_EINVAL;
+    HIP_CHECK_RET(ew_adam(w, m, v, g, AdamRule{alpha, beta1, beta2, epsilon, gscale}, n, (hipStream_t)stream));
     return RSU_OK;
 }
 extern "C" int rsu_extract_tiles(const float* imgs, float* tiles, int nimg, int H, int S, int P, int stride, long t0, long ntiles,

@@ -62,6 +62,11 @@ EXTRA_FLAG_DEFS = [
     ("device_patch_pool", bool, True, "Keep the rotated training images in HBM and cut the patches of a batch on the GPU"),
     ("d4_augmentation", bool, False, "Stochastic flips / transpose / rot90 per training sample on the GPU (what the reference's "
                                      "--image_augmentation subgraph intended; that flag itself stays without effect, as in the reference)"),
+    ("optimizer", str, "momentum", "momentum|adam: the reference's MomentumOptimizer (--lr, --momentum) or tf.train.AdamOptimizer (--lr, "
+                                   "--adam_beta1, --adam_beta2, --adam_epsilon; --lr keeps the reference's default 0.01, TensorFlow's Adam default is 0.001)"),
+    ("adam_beta1", float, 0.9, "Adam: decay rate of the first-moment estimates"),
+    ("adam_beta2", float, 0.999, "Adam: decay rate of the second-moment estimates"),
+    ("adam_epsilon", float, 1e-8, "Adam: epsilon added to sqrt(v)"),
 ]
 
 
@@ -76,6 +81,8 @@ class Options(object):
             if not hasattr(self, k):
                 raise AttributeError("unknown option %r" % k)
             setattr(self, k, v)
+        if self.optimizer not in ("momentum", "adam"):
+            raise ValueError("--optimizer must be momentum or adam, not %r" % (self.optimizer,))
         ra = self.rotation_angles
         if isinstance(ra, str):
             self.rotation_angles = None if not ra else [int(i) for i in ra.split(",")]
@@ -109,7 +116,7 @@ class ConvolutionalModel:
             torch.cuda.set_device(torch.device(device))  # the library works on the HIP current device (rsu.h "devices")
         # the reference's graph is static in (batch, patch): one UNet serves training and (zero-padded) prediction batches
         self.net = UNet(opts.num_layers, opts.root_size, opts.dilated_layers, self.local_batch, opts.patch_size, device=device,
-                        params=params, seed=opts.seed, training=True)
+                        params=params, seed=opts.seed, training=True, optimizer=opts.optimizer)
         self.net.dropout_seed = int(opts.seed) + 7919 * self.rank  # independent masks on every rank's shard
         self._bucketer = None
         self._exchange_tuned = False
@@ -138,7 +145,7 @@ class ConvolutionalModel:
         return self._run_step()
 
     def _run_step(self):
-        """forward + loss + backward + gradient exchange + Momentum on the batch held in net.x / net.labels"""
+        """forward + loss + backward + gradient exchange + optimizer step (Momentum or Adam) on the batch held in net.x / net.labels"""
         opts, net = self._options, self.net
         if self._bucketer is not None and not self._exchange_tuned:
             # first step of a data-parallel run: time forward + backward + exchange (no optimizer step, so the trajectory is
@@ -161,13 +168,17 @@ class ConvolutionalModel:
         if self._bucketer is not None:
             self._bucketer.reset()
         # (single device: Momentum + re-pack of the conv kernels fused into their weight-gradient launches, rsu.h rsu_conv2d_bwd_weight_update)
+        adam = opts.optimizer == "adam"   # (Adam never rides on the weight-gradient launches)
         net.backward_device(1.0 / (opts.batch_size * opts.patch_size * opts.patch_size),
-                            update=(opts.lr, opts.momentum) if self._bucketer is None else None)
+                            update=(opts.lr, opts.momentum) if self._bucketer is None and not adam else None)
         loss = net.loss_sum / (opts.batch_size * opts.patch_size * opts.patch_size)
         if self._bucketer is not None:
             self._bucketer.finish()
             dist.all_reduce(loss)
-        net.apply_momentum(opts.lr, opts.momentum)
+        if adam:
+            net.apply_adam(opts.lr, opts.adam_beta1, opts.adam_beta2, opts.adam_epsilon)
+        else:
+            net.apply_momentum(opts.lr, opts.momentum)
         return loss, net.prob
 
     def _ensure_summary(self):
@@ -402,7 +413,7 @@ class ConvolutionalModel:
     # ------------------------------------------------------------------ checkpoints
     def save_as(self, path):
         """tf_aerial_images.py:458: the saver writing to an explicit path (`path`.npz: every variable under its TF name and layout,
-        its Momentum slot and global_step; '/' in a name is stored as '|' -- np.savez keys become file names)"""
+        its optimizer slots (UNet.state_dict) and global_step; '/' in a name is stored as '|' -- np.savez keys become file names)"""
         if self.rank == 0:
             os.makedirs(os.path.dirname(path), exist_ok=True)
             np.savez(path + ".npz", **{k.replace("/", "|"): v for k, v in self.net.state_dict().items()})
@@ -420,7 +431,8 @@ class ConvolutionalModel:
         """Load a checkpoint of the REFERENCE: `arrays` maps TensorFlow variable names to numpy arrays, as written by
         tools/export_tf_checkpoint.py on a machine that has TensorFlow (tf.train.load_checkpoint(...).get_tensor(name) for every
         name; tf_aerial_images.py:171 saves all global variables). Names and layouts are the reference's own, so this is a pure
-        rename: `<var>` -> weights, `<var>/Momentum` -> optimizer slots, `global_step` (tf_aerial_images.py:113) -> step counter.
+        rename: `<var>` -> weights, `<var>/Momentum` -> optimizer slots, `global_step` (tf_aerial_images.py:113) -> step counter; a run
+        with tf.train.AdamOptimizer: `<var>/Adam`, `<var>/Adam_1`, `beta1_power`, `beta2_power` (read by an Adam model; UNet.load_state_dict).
         A ':0' suffix and a leading scope are tolerated; missing variables raise KeyError."""
         clean = {}
         for k, v in arrays.items():
@@ -434,9 +446,14 @@ class ConvolutionalModel:
             d[n] = clean[hit[0]]
             if d[n].shape != tuple(self.net.w[n].shape):
                 raise ValueError("variable %r: checkpoint shape %s, network %s" % (n, d[n].shape, tuple(self.net.w[n].shape)))
-            mom = [k for k in clean if k == n + "/Momentum" or k.endswith("/" + n + "/Momentum")]
-            if mom:
-                d[n + "/Momentum"] = clean[mom[0]]
+            for slot in ("/Momentum", "/Adam", "/Adam_1"):
+                hit = [k for k in clean if k == n + slot or k.endswith("/" + n + slot)]
+                if hit:
+                    d[n + slot] = clean[hit[0]]
+        for scalar in ("beta1_power", "beta2_power"):
+            hit = [k for k in clean if k == scalar or k.endswith("/" + scalar)]
+            if hit:
+                d[scalar] = np.float32(clean[hit[0]])
         gs = [k for k in clean if k == "global_step" or k.endswith("/global_step")]
         d["global_step"] = int(clean[gs[0]]) if gs else 0
         self.net.load_state_dict(d)

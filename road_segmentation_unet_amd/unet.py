@@ -105,6 +105,19 @@ def cu_shares(full, parts):
     return [max(32, v * full // 256 // 8 * 8) for v in parts]
 
 
+def adam_scalars(lr_t, beta1_power, beta2_power, beta1, beta2):
+    """The host side of one tf.train.AdamOptimizer step, float32 as TensorFlow computes it: alpha = lr_t * sqrt(1 - beta2^t) / (1 - beta1^t)
+    (ApplyAdam's step size, from the powers BEFORE the step) and the powers after it (AdamOptimizer._finish: beta1_power * beta1,
+    beta2_power * beta2). Returns (alpha, next beta1_power, next beta2_power) as numpy float32 scalars."""
+    f = np.float32
+    b1p, b2p = f(beta1_power), f(beta2_power)
+    alpha = f(lr_t) * np.sqrt(f(1) - b2p) / (f(1) - b1p)
+    return f(alpha), f(b1p * f(beta1)), f(b2p * f(beta2))
+
+
+OPTIMIZERS = ("momentum", "adam")
+
+
 def _src(t, h, w):
     """window (h, w) centred in NHWC tensor t (crop offset floor((H-h)/2), unet.py:70-83)"""
     H, W, C = t.shape[1], t.shape[2], t.shape[3]
@@ -116,7 +129,12 @@ class UNet:
     static in exactly the same way (tf_aerial_images.py:133-138)."""
 
     def __init__(self, num_layers, root_size, dilated_layers, batch_size, patch_size, device="cuda:0", params=None, seed=2017,
-                 training=True):
+                 training=True, optimizer="momentum"):
+        """optimizer: "momentum" (the reference's MomentumOptimizer: apply_momentum) or "adam" (tf.train.AdamOptimizer: apply_adam; a
+        second fp32 slot per variable, flat_v)"""
+        if optimizer not in OPTIMIZERS:
+            raise _lib.RsuError("optimizer must be one of %s, not %r" % ("|".join(OPTIMIZERS), optimizer))
+        self.optimizer = optimizer
         assert root_size % 8 == 0 and (root_size // 8) & (root_size // 8 - 1) == 0, "root_size must be 8 * 2^k for the HIP path"
         self.L, self.root, self.dilated = num_layers, root_size, bool(dilated_layers)
         self.B, self.P = batch_size, patch_size
@@ -176,29 +194,60 @@ class UNet:
         self.n_flat = off
         dev = self.device
         self.flat_w = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.flat_acc = torch.zeros(off, dtype=torch.float32, device=dev)   # Momentum slots (tf_aerial_images.py:120)
+        self.flat_acc = torch.zeros(off, dtype=torch.float32, device=dev)   # Momentum slots (tf_aerial_images.py:120); Adam: m
         self.flat_g = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.w, self.acc, self.g = {}, {}, {}
+        # Adam's second slot v (a Momentum net has none)
+        self.flat_v = torch.zeros(off, dtype=torch.float32, device=dev) if self.optimizer == "adam" else None
+        self.w, self.acc, self.g, self.v = {}, {}, {}, {}
         for n, (o, cnt, s) in self._slices.items():
             self.w[n] = self.flat_w[o:o + cnt].view(s)
             self.acc[n] = self.flat_acc[o:o + cnt].view(s)
             self.g[n] = self.flat_g[o:o + cnt].view(s)
+            if self.flat_v is not None:
+                self.v[n] = self.flat_v[o:o + cnt].view(s)
             self.w[n].copy_(torch.from_numpy(np.ascontiguousarray(init[n], dtype=np.float32)))
         self.global_step = 0
+        # Adam's float32 accumulators beta1^t, beta2^t (None: not started -- the first apply_adam sets them to its (beta1, beta2),
+        # the initial values TensorFlow gives them)
+        self.beta1_power = self.beta2_power = None
 
     def state_dict(self):
-        """TF variable names, TF layouts (HWIO / [kh,kw,out,in]) + Momentum slots + global_step."""
+        """TF variable names, TF layouts (HWIO / [kh,kw,out,in]) + Momentum slots + global_step. An Adam net: the slots are
+        `<var>/Adam` (m) and `<var>/Adam_1` (v), plus the float32 scalars `beta1_power` and `beta2_power` once a step has set them."""
         d = {n: self.w[n].detach().cpu().numpy().copy() for n in self.names}
-        d.update({n + "/Momentum": self.acc[n].detach().cpu().numpy().copy() for n in self.names})
+        if self.optimizer == "adam":
+            d.update({n + "/Adam": self.acc[n].detach().cpu().numpy().copy() for n in self.names})
+            d.update({n + "/Adam_1": self.v[n].detach().cpu().numpy().copy() for n in self.names})
+            if self.beta1_power is not None:
+                d["beta1_power"], d["beta2_power"] = np.float32(self.beta1_power), np.float32(self.beta2_power)
+        else:
+            d.update({n + "/Momentum": self.acc[n].detach().cpu().numpy().copy() for n in self.names})
         d["global_step"] = np.int64(self.global_step)
         return d
 
     def load_state_dict(self, d):
+        """Weights, slots and global_step from a state_dict() (or a TensorFlow checkpoint renamed to it). A Momentum net reads the
+        `/Momentum` slots present and ignores Adam keys. An Adam net reads `/Adam`, `/Adam_1`, `beta1_power`, `beta2_power`; a checkpoint
+        without Adam slots (a Momentum run's) loads the weights and global_step, zeroes m and v and resets the powers: the next
+        apply_adam starts them at its (beta1, beta2), as a fresh AdamOptimizer does."""
         self._load_count = getattr(self, "_load_count", 0) + 1
+        adam = self.optimizer == "adam"
+        have_adam = adam and any(n + "/Adam" in d for n in self.names)
         for n in self.names:
             self.w[n].copy_(torch.from_numpy(np.ascontiguousarray(d[n], dtype=np.float32)))
-            if n + "/Momentum" in d:
+            if adam:
+                for slot, t in (("/Adam", self.acc[n]), ("/Adam_1", self.v[n])):
+                    if have_adam and n + slot in d:
+                        t.copy_(torch.from_numpy(np.ascontiguousarray(d[n + slot], dtype=np.float32)))
+                    else:
+                        t.zero_()
+            elif n + "/Momentum" in d:
                 self.acc[n].copy_(torch.from_numpy(np.ascontiguousarray(d[n + "/Momentum"], dtype=np.float32)))
+        if adam:
+            if have_adam and "beta1_power" in d and "beta2_power" in d:
+                self.beta1_power, self.beta2_power = np.float32(d["beta1_power"]), np.float32(d["beta2_power"])
+            else:
+                self.beta1_power = self.beta2_power = None
         self.global_step = int(d.get("global_step", 0))
         self.repack()
 
@@ -781,6 +830,9 @@ class UNet:
         B, L, st, a, g = self.B, self.L, self._stream(), self.act, self.grad
         keep = self.keep
         last = a[self.last_name]
+        if update is not None and self.optimizer != "momentum":
+            raise _lib.RsuError("backward_device(update=...) is the Momentum step; an %s net steps with apply_%s after the pass"
+                                % (self.optimizer, self.optimizer))
         self._begin_split()
         self._fused = self._fused_pending = None
         if (update is not None and self.training and self._wg_group == 0 and self.on_grads is None and self.device.type == "cuda"
@@ -939,10 +991,11 @@ class UNet:
         """tf.train.exponential_decay(lr, global_step, 1000, 0.95, staircase=True) (tf_aerial_images.py:116-117), float32"""
         return float(np.float32(lr0) * np.float32(0.95) ** np.float32(self.global_step // 1000))
 
-    def _build_update_table(self, pkset=0, rest_only=False):
+    def _build_update_table(self, pkset=0, rest_only=False, adam=False):
         """the job table of rsu_update_table_run: one entry per conv / transposed-conv kernel (with its packed copies; the backward-data
         packs of set `pkset`), the variables between them (biases, colour adjust, the 1x1 head) as plain Momentum ranges; covers [0, n_live)
-        of the flat buffers once. rest_only: without the kernels whose step rode on their weight-gradient launches (_fused_names)."""
+        of the flat buffers once. rest_only: without the kernels whose step rode on their weight-gradient launches (_fused_names).
+        adam: the table of rsu_update_table_run_adam (every entry also gets its slice of flat_v; acc holds m); cached apart."""
         lib = _lib.lib()
         if not hasattr(self, "pk"):
             self.repack()
@@ -968,6 +1021,7 @@ class UNet:
             if e[0] == "plain":
                 lo, hi = e[1], e[2]
                 rc = lib.rsu_update_table_add_plain(host, idx, _ptr(self.flat_w[lo:hi]), _ptr(self.flat_acc[lo:hi]), _ptr(self.flat_g[lo:hi]), hi - lo)
+                v = self.flat_v[lo:hi] if adam else None
             else:
                 n, sh = e[1], e[2]
                 w, a, g = _ptr(self.w[n]), _ptr(self.acc[n]), _ptr(self.g[n])
@@ -984,11 +1038,17 @@ class UNet:
                     bw = (ctypes.c_void_p * len(segs))(*[t.data_ptr() for t in packs]) if self.training else None
                     rc = lib.rsu_update_table_add(host, idx, 0, w, a, g, _ptr(self.pk[n, "fwd"]), bw, sh[2], sh[3], (ctypes.c_int * len(segs))(*segs), len(segs))
                 keep.append(bw)
+                v = self.v[n] if adam else None
             if rc != 1:
                 raise _lib.RsuError("rsu_update_table_add(%s) failed: %d" % (e[1], rc))
+            if adam:
+                _lib.check(lib.rsu_update_table_set_second_slot(host, idx, _ptr(v)), "rsu_update_table_set_second_slot(%s)" % (e[1],))
         nb = ctypes.c_int(0)
         _lib.check(lib.rsu_update_table_finish(host, len(entries), ctypes.byref(nb)), "rsu_update_table_finish")
         tab = (torch.frombuffer(bytearray(host.raw), dtype=torch.uint8).to(self.device), len(entries), nb.value)
+        if adam:
+            self._update_tables["adam", pkset] = tab
+            return tab
         self._update_tables[pkset, rest_only] = tab
         if pkset == 0 and not rest_only:
             self._update_table = tab   # (the name tools and probes know)
@@ -998,6 +1058,8 @@ class UNet:
         """MomentumOptimizer step on every live variable (tf_aerial_images.py:120-121) and the re-pack of the bf16 MFMA copies, in one
         pass over the parameters (rsu_update_table_run; RSU_FUSED_UPDATE=0: rsu_momentum_step, then the batched re-pack -- same bits).
         Behind backward_device(update=(lr0, momentum)) the 3x3 conv kernels have been stepped already: only the other variables are."""
+        if self.optimizer != "momentum":
+            raise _lib.RsuError("apply_momentum on a net built with optimizer=%r" % self.optimizer)
         pending, self._fused_pending = self._fused_pending, None
         if pending is not None:
             if pending != (float(lr0), float(momentum)) or gscale != 1.0:
@@ -1017,6 +1079,26 @@ class UNet:
         tab = self._update_tables.get((self._pkset, False)) or self._build_update_table(self._pkset, False)
         call("rsu_update_table_run", _ptr(tab[0]), tab[1], tab[2], self.learning_rate(lr0), momentum, gscale, self._stream())
         self.global_step += 1
+
+    def apply_adam(self, lr0, beta1=0.9, beta2=0.999, epsilon=1e-8, gscale=1.0):
+        """tf.train.AdamOptimizer step on every live variable (TensorFlow 1.x ApplyAdam at the decayed rate learning_rate(lr0)) and the
+        re-pack of the bf16 MFMA copies, in one pass over the parameters (rsu_update_table_run_adam; RSU_FUSED_UPDATE=0: rsu_adam_step,
+        then the batched re-pack -- same bits). alpha and the beta powers are float32 host arithmetic (adam_scalars); global_step and
+        the powers advance after the launch. The dead level-(L-1) dilated pair is never stepped."""
+        if self.optimizer != "adam":
+            raise _lib.RsuError("apply_adam on a net built with optimizer=%r" % self.optimizer)
+        if self.beta1_power is None:
+            self.beta1_power, self.beta2_power = np.float32(beta1), np.float32(beta2)
+        alpha, b1p, b2p = adam_scalars(self.learning_rate(lr0), self.beta1_power, self.beta2_power, beta1, beta2)
+        args = (float(alpha), float(np.float32(beta1)), float(np.float32(beta2)), float(np.float32(epsilon)), gscale)
+        if os.environ.get("RSU_FUSED_UPDATE", "1") == "0":
+            call("rsu_adam_step", _ptr(self.flat_w), _ptr(self.flat_acc), _ptr(self.flat_v), _ptr(self.flat_g), *args, self.n_live, self._stream())
+            self.repack()
+        else:
+            tab = self._update_tables.get(("adam", self._pkset)) or self._build_update_table(self._pkset, False, adam=True)
+            call("rsu_update_table_run_adam", _ptr(tab[0]), tab[1], tab[2], *args, self._stream())
+        self.global_step += 1
+        self.beta1_power, self.beta2_power = b1p, b2p
 
 
 _DEFAULT_MODELS = {}
