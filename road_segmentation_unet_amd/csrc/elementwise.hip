@@ -973,16 +973,7 @@ hipError_t ew_pack_many(const PackJob* jobs_dev, int njobs, int total_blocks, hi
 // from R2 ("B": conv backward-data, one buffer per concat source; transposed-conv forward, one buffer per tap).
 // ---------------------------------------------------------------------------------------------
 #define UP_EPB 4096   // floats per workgroup of a plain range
-// UP_NT (developer A/B switch): 1 = the gradient is read and the packed layouts are written with non-temporal hints (streamed once per
-// step); 2 = w and acc too
-#ifndef UP_NT
-#define UP_NT 0
-#endif
 namespace {
-__device__ __forceinline__ f32x4 up_ld_stream(const f32x4* p) { return UP_NT >= 1 ? __builtin_nontemporal_load(p) : *p; }
-__device__ __forceinline__ f32x4 up_ld_state(const f32x4* p) { return UP_NT >= 2 ? __builtin_nontemporal_load(p) : *p; }
-__device__ __forceinline__ void up_st_state(f32x4* p, f32x4 v) { if (UP_NT >= 2) __builtin_nontemporal_store(v, p); else *p = v; }
-__device__ __forceinline__ void up_st_stream(u32x4* p, u32x4 v) { if (UP_NT >= 1) __builtin_nontemporal_store(v, p); else *p = v; }
 // the update rules of the pass, on a float4 of weights (w, first slot a, second slot v, gradient g)
 __device__ __forceinline__ void up_step(const MomentumRule& h, f32x4& w, f32x4& a, f32x4&, const f32x4 g) {
     a = h.mu * a + h.gscale * g;
@@ -996,11 +987,10 @@ __device__ __forceinline__ void up_step1(const MomentumRule& h, float* w, float*
 }
 __device__ __forceinline__ void up_step1(const AdamRule& h, float* w, float* a, float* v, const float* g) { adam_elem(*w, *a, *v, *g, h); }
 }  // namespace
-// One workgroup of the packed-tensor path: block (tap, 32-row block rb, group cg of four 32-column blocks) of tensor J. `grad(i)` returns
-// the gradient float4 at float4 index i of the source tensor (k_update_pack_many: the gradient buffer; k_update_pack_seg: the ordered sum
-// of the weight-gradient slabs). Rule: MomentumRule or AdamRule (the second slot J.v is read in the same batch as w, acc and g).
-template <typename Rule, typename GradFn>
-__device__ __forceinline__ void update_pack_block(const UpJob& J, float (*tile)[32][33], int tap, int rb, int cg, const Rule& h, GradFn grad) {
+// One workgroup of the packed-tensor path: block (tap, 32-row block rb, group cg of four 32-column blocks) of tensor J, whose gradient is
+// `g`. Rule: MomentumRule or AdamRule (the second slot J.v is read in the same batch as w, acc and g).
+template <typename Rule>
+__device__ __forceinline__ void update_pack_block(const UpJob& J, float (*tile)[32][33], int tap, int rb, int cg, const Rule& h, const float* g) {
     int seg = 0;
     while (seg + 1 < J.nseg && rb >= J.seg_blk0[seg + 1]) ++seg;
     const int rbs = rb - J.seg_blk0[seg];                // 32-row block inside its segment
@@ -1019,19 +1009,19 @@ __device__ __forceinline__ void update_pack_block(const UpJob& J, float (*tile)[
         if (cb < J.ncb && r < vr && c0 + c4 < J.R2) {   // (R2 is a multiple of 4: a float4 is inside or outside as a whole)
             const long i = (((long)tap * J.R1 + r0 + r) * J.R2 + c0 + c4) >> 2;
             idx[q] = i;
-            av[q] = up_ld_state((const f32x4*)J.acc + i);
-            if constexpr (Rule::kSecondSlot) vv[q] = up_ld_state((const f32x4*)J.v + i);
-            gv[q] = grad(i);
-            wv[q] = up_ld_state((const f32x4*)J.w + i);
+            av[q] = ((const f32x4*)J.acc)[i];
+            if constexpr (Rule::kSecondSlot) vv[q] = ((const f32x4*)J.v)[i];
+            gv[q] = ((const f32x4*)g)[i];
+            wv[q] = ((const f32x4*)J.w)[i];
         }
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         if (idx[q] >= 0) {
             up_step(h, wv[q], av[q], vv[q], gv[q]);
-            up_st_state((f32x4*)J.acc + idx[q], av[q]);
-            if constexpr (Rule::kSecondSlot) up_st_state((f32x4*)J.v + idx[q], vv[q]);
-            up_st_state((f32x4*)J.w + idx[q], wv[q]);
+            ((f32x4*)J.acc)[idx[q]] = av[q];
+            if constexpr (Rule::kSecondSlot) ((f32x4*)J.v)[idx[q]] = vv[q];
+            ((f32x4*)J.w)[idx[q]] = wv[q];
         }
         tile[q][r][c4] = wv[q][0]; tile[q][r][c4 + 1] = wv[q][1]; tile[q][r][c4 + 2] = wv[q][2]; tile[q][r][c4 + 3] = wv[q][3];
     }
@@ -1063,7 +1053,7 @@ __device__ __forceinline__ void update_pack_block(const UpJob& J, float (*tile)[
         const int ntl = D.ntiles[D.orient == 0 || D.tapmode == 2 ? 0 : seg];
         const long e = ((((long)chunk * D.ntap + tapd) * ntl + 2 * pair + tl) << 9) + lane * 8;
         u32x4 o = {pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]), pack_bf2(v[4], v[5]), pack_bf2(v[6], v[7])};
-        up_st_stream((u32x4*)(base + e), o);
+        *(u32x4*)(base + e) = o;
     }
 }
 template <typename Rule>
@@ -1104,61 +1094,7 @@ __global__ void __launch_bounds__(256) k_update_pack_many(const UpJob* __restric
     // ---- a packed tensor: workgroup b = (tap, row block rb, group of four column blocks cg)
     const int ncg = (J.ncb + 3) >> 2;
     const int cg = b % ncg, rb = (b / ncg) % J.nrb, tap = b / (ncg * J.nrb);
-    const float* gp = J.g;
-    update_pack_block(J, tile, tap, rb, cg, h, [gp](long i) { return up_ld_stream((const f32x4*)gp + i); });
-}
-// The same pass for ONE concat source (R1 segment `seg`) of ONE conv kernel, fed by the weight-gradient slabs of that source instead of a
-// finished gradient: the reduce launch of the slabs IS the update (the fp32 gradient is neither written nor re-read,
-// 8 of 28 B per weight; and the Momentum pass of these tensors leaves the tail of the step). Summation orders are those of
-// k_reduce_slabs / k_reduce_slabs_wide (sequential below 16 splits; else eight interleaved partial sums combined in order), so w, acc and
-// the packed copies equal reduce -> k_update_pack_many bit for bit. nsplit == 1: `slab` is the gradient the weight-gradient kernel wrote
-// in place. gout (optional): the reduced gradient is stored too (tests, hosts that log gradient norms). The last blocks reduce the n2
-// float4 items of the bias row (behind the taps of every slab) into out2, as k_reduce_slabs does.
-__device__ __forceinline__ f32x4 slab_sum(const float* __restrict__ slab, long stride, int nsplit, long e) {
-    if (nsplit < 16) {
-        f32x4 t = {0.f, 0.f, 0.f, 0.f};
-        for (int z = 0; z < nsplit; ++z) t += *(const f32x4*)(slab + z * stride + e);
-        return t;
-    }
-    f32x4 part[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) part[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int z0 = 0; z0 < nsplit; z0 += 8) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q)
-            if (z0 + q < nsplit) part[q] += *(const f32x4*)(slab + (z0 + q) * stride + e);
-    }
-    f32x4 r = part[0];
-#pragma unroll
-    for (int q = 1; q < 8; ++q) r += part[q];
-    return r;
-}
-__global__ void __launch_bounds__(256) k_update_pack_seg(const UpJob J, int seg, const float* __restrict__ slab, long stride, int nsplit,
-                                                         float* __restrict__ gout, float* __restrict__ out2, int n2, int tensor_blocks, float lr, float mu,
-                                                         float gscale) {
-    __shared__ float tile[4][32][33];
-    const int b = blockIdx.x;
-    if (b >= tensor_blocks) {   // the bias row
-        const int c4 = (b - tensor_blocks) * 256 + threadIdx.x;
-        if (c4 < n2) *(f32x4*)(out2 + c4 * 4) = slab_sum(slab, stride, nsplit, (long)J.ntap * J.R1 * J.R2 + c4 * 4);
-        return;
-    }
-    const int ncg = (J.ncb + 3) >> 2;
-    const int nrb_seg = (J.seg_c[seg] + 31) >> 5;
-    const int cg = b % ncg, rb = J.seg_blk0[seg] + (b / ncg) % nrb_seg, tap = b / (ncg * nrb_seg);
-    update_pack_block(J, tile, tap, rb, cg, MomentumRule{lr, mu, gscale}, [=](long i) {
-        const f32x4 g = slab_sum(slab, stride, nsplit, i * 4);
-        if (gout && nsplit > 1) *(f32x4*)(gout + i * 4) = g;
-        return g;
-    });
-}
-hipError_t ew_update_pack_seg(const UpJob& J, int seg, const float* slab, long stride, int nsplit, float* gout, float* out2, int n2, float lr, float mu,
-                              float gscale, hipStream_t st) {
-    const int tensor_blocks = J.ntap * ((J.seg_c[seg] + 31) / 32) * ((J.ncb + 3) >> 2);
-    const int bias_blocks = (out2 && nsplit > 1) ? (n2 + 255) / 256 : 0;
-    hipLaunchKernelGGL(k_update_pack_seg, dim3(tensor_blocks + bias_blocks), dim3(256), 0, st, J, seg, slab, stride, nsplit, gout, out2, n2, tensor_blocks, lr, mu,
-                       gscale);
-    return hipGetLastError();
+    update_pack_block(J, tile, tap, rb, cg, h, J.g);
 }
 int ew_update_job_blocks(const UpJob& j) {
     if (j.kind == 0) return (int)((j.n + UP_EPB - 1) / UP_EPB);

@@ -33,17 +33,8 @@
 
 // PP_DIL: the dilation this translation unit is built for (1: igemm_pp.hip itself; 2: igemm_pp_d2.hip, which includes this file with the
 // exported names changed -- the dilated twin blocks of unet.py:32-39). The halo tile is 2 * DIL wider and higher, taps are DIL pixels apart.
-#ifndef PP_TRS
-#define PP_TRS 1      // developer A/B switch: backward-data's epilogue stores transposed across the lanes (see TRS below)
-#endif
 #ifndef PP_CLIP_PAD
 #define PP_CLIP_PAD 1   // developer A/B switch: the padding pixels of a halo block are not fetched (setup_a)
-#endif
-#ifndef PP_TRS_LA
-#define PP_TRS_LA 8    // ... with the exchanges of this many stores in flight ahead of the store being issued
-#endif
-#ifndef PP_TRS_FWD
-#define PP_TRS_FWD 0   // developer A/B switch: the transposed stores in the epilogue without a mask too (forward; measured slower in round 4)
 #endif
 #ifndef PP_DIL
 #define PP_DIL 1
@@ -533,7 +524,7 @@ igemm_pp_kernel(const IgFwdParams p) {
                 }
             };
             auto body = [&](const bool MASK) __attribute__((always_inline)) {   // (called with a constant: two straight-line copies)
-                const bool TRS = PP_TRS && (MASK || PP_TRS_FWD);
+                const bool TRS = MASK;   // backward-data's epilogue stores transposed across the lanes (forward: measured slower in round 4)
                 const int tr_src = (((lane & 3) << 4) | (lane >> 2)) << 2;   // ds_bpermute byte index of the lane whose words this lane stores
                 fill_voffs(TRS);
                 seg_end(6);
@@ -551,7 +542,7 @@ igemm_pp_kernel(const IgFwdParams p) {
                 // The packed results of LA stores ahead, their (TRS) lane exchanges in flight: a ds_bpermute_b32 comes back after ~150 cycles,
                 // four of them waited for in front of each store would cost the interval 8 x that. The exchanges are asm with counted
                 // waits of our own (LDS operations return in order; the "+v" of the wait statement keeps the uses behind it)
-                const int LA = TRS ? (NST < PP_TRS_LA ? NST : PP_TRS_LA) : 1;   // (without exchanges: convert, store, convert, store ... as before)
+                const int LA = TRS ? (NST < 8 ? NST : 8) : 1;   // (without exchanges: convert, store, convert, store ... as before)
                 u32x4 rr[NST];
                 auto pack = [&](const int e) __attribute__((always_inline)) {
                     const int pt = e / (CT / 2), pp = e % (CT / 2);

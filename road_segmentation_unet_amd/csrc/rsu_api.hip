@@ -464,7 +464,7 @@ static int pick_cob_group(int grid, int ncob, int ksplit, int TN, int ktot, int 
     return best_a == nck ? 0 : best_a;
 }
 static bool plan_fwd2(Fwd2Plan& best, int ncu, int N, int Ho, int Wo, int Cout, int ntap, int kh, int kw, int dil, int stride, int gy, int ktot,
-                      int force_cfg, bool shared_chip = false, bool pool = false) {
+                      int force_cfg, bool pool) {
     double best_cost = 1e300;
     bool have = false;
     // pass 0: channel-block width matched to Cout; pass 1 (only when no such shape fits its halo tile into LDS -- the 2x2 stride-2
@@ -473,7 +473,6 @@ static bool plan_fwd2(Fwd2Plan& best, int ncu, int N, int Ho, int Wo, int Cout, 
     for (int cfg = 0; cfg < IGF2_NCFG; ++cfg) {
         if (force_cfg >= 0 && cfg != force_cfg) continue;
         if (igemm_fwd2_cfg_info(cfg).TN == 0) continue;  // retired ids
-        if (force_cfg < 0 && (cfg == IGF2_CFG_128x320 || cfg == IGF2_CFG_64x640) && !env_int("RSU_CFG_320", 1)) continue;
         const IgFwdCfgInfo ci = igemm_fwd2_cfg_info(cfg);
         if (pass == 0 && Cout <= 64 && ci.TN > 64 && force_cfg < 0) continue;
         if (pass == 0 && Cout > 64 && ci.TN <= 64 && force_cfg < 0) continue;
@@ -498,15 +497,11 @@ static bool plan_fwd2(Fwd2Plan& best, int ncu, int N, int Ho, int Wo, int Cout, 
         double ovh = 4096.0 * 1152.0 / (double)(ktot > 0 ? ktot : 1152);
         if (ovh < 4096.0) ovh = 4096.0;
         if (ovh > 65536.0) ovh = 65536.0;
-        // shared_chip: the launch runs beside another stream's persistent kernel (backward-data beside the weight gradients), which
-        // fills the idle CUs of a partial last round -- price the rounds fractionally and let the more efficient big tiles win
-        const double nrounds = shared_chip ? (double)ntile_m / (double)workers : (double)rounds;
         // measured per-MAC cost of the shapes relative to 128x256: two pixel fragments per wave read 6 LDS fragments per 8 MFMAs
         // and stream twice the weight pieces per MFMA (x1.5 priced: it also covers their shorter stages); five fragments per wave are a little cheaper (x0.96)
         const int ptw = ci.TM / 16 / (ci.threads / 64 / (ci.TN / 64));
-        const double eff = ptw <= 2 ? (double)env_int("RSU_PLAN_PT2_PCT", 150) / 100.0
-                                    : (ptw == 3 ? (double)env_int("RSU_PLAN_PT3_PCT", 120) / 100.0 : (ptw >= 5 ? 0.96 : 1.0));
-        const double cost = nrounds * ((double)ci.TM * ci.TN * eff + ovh);
+        const double eff = ptw <= 2 ? 1.5 : (ptw == 3 ? 1.2 : (ptw >= 5 ? 0.96 : 1.0));
+        const double cost = (double)rounds * ((double)ci.TM * ci.TN * eff + ovh);
         const int nchunks = ktot / (32 * ntap);
         if (cost < best_cost) {
             best_cost = cost;
@@ -611,7 +606,6 @@ static int run_fwd(const rsu_src_t* srcs, int nsrc, const void* wp, long wp_y_st
     int ktot = 0;
     for (int i = 0; i < nsrc; ++i) ktot += rup(srcs[i].C, 32) * ntap;
     const int env_cfg = env_int("RSU_FWD2_CFG", -1);
-    const bool shared_chip = pad > 0 && env_int("RSU_PLAN_SHARED", 0) != 0;
     // measured tile-shape choice (see g_tuned): look the launch up, or -- first time -- mark it for tuning below
     const int tune_mode = env_int("RSU_AUTOTUNE", 1) != 0 ? g_autotune.load() : RSU_TUNE_OFF;
     const bool tunable = env_cfg < 0 && !accumulate && tune_mode != RSU_TUNE_OFF;
@@ -635,7 +629,7 @@ static int run_fwd(const rsu_src_t* srcs, int nsrc, const void* wp, long wp_y_st
     }
     if (split) {
         pl2 = pls;
-    } else if (!plan_fwd2(pl2, ncu, N, Ho, Wo, Cout, ntap, kh, kw, dil, stride, gy, ktot, tuned_cfg >= 0 ? tuned_cfg : env_cfg, shared_chip, pool)) {
+    } else if (!plan_fwd2(pl2, ncu, N, Ho, Wo, Cout, ntap, kh, kw, dil, stride, gy, ktot, tuned_cfg >= 0 ? tuned_cfg : env_cfg, pool)) {
         // a shape forced through RSU_FWD2_CFG, or a tuned shape (an imported table), whose halo tile does not fit this geometry: plan
         // freely instead (and forget the table entry)
         if (tuned_cfg >= 0) {
@@ -643,7 +637,7 @@ static int run_fwd(const rsu_src_t* srcs, int nsrc, const void* wp, long wp_y_st
             g_tuned.erase(tkey);
             tuned_pp = -1;
         }
-        if (!((env_cfg >= 0 || tuned_cfg >= 0) && plan_fwd2(pl2, ncu, N, Ho, Wo, Cout, ntap, kh, kw, dil, stride, gy, ktot, -1, shared_chip, pool)))
+        if (!((env_cfg >= 0 || tuned_cfg >= 0) && plan_fwd2(pl2, ncu, N, Ho, Wo, Cout, ntap, kh, kw, dil, stride, gy, ktot, -1, pool)))
             return RSU_EINVAL;
     }
     IgFwdParams p;
@@ -730,7 +724,7 @@ static int run_fwd(const rsu_src_t* srcs, int nsrc, const void* wp, long wp_y_st
             for (int cfg = 0; cfg < IGF2_NCFG; ++cfg) {
                 if (igemm_fwd2_cfg_info(cfg).TN != tn_model) continue;
                 Fwd2Plan pc;
-                if (!plan_fwd2(pc, ncu, N, Ho, Wo, Cout, ntap, kh, kw, dil, stride, gy, ktot, cfg, shared_chip, pool)) continue;
+                if (!plan_fwd2(pc, ncu, N, Ho, Wo, Cout, ntap, kh, kw, dil, stride, gy, ktot, cfg, pool)) continue;
                 IgFwdParams pt = p;
                 apply_plan(pt, pc);
                 for (int vpp = 0; vpp < 2; ++vpp) {  // the kernel generations of the shape
@@ -812,8 +806,8 @@ extern "C" int rsu_conv2d_fwd_pool_k(const rsu_src_t* srcs, int nsrc, const void
         (void)kt;
         Fwd2Plan sp;
         worth = n > 0 && !(kws && plan_split(sp, N, Ho, Wo, Cout, ktot, kws_floats)) &&   // (a layer that splits its reduction does not fold the pool)
-                plan_fwd2(a, n, N, Ho, Wo, Cout, 9, 3, 3, 1, 1, 1, ktot, -1, false, false) &&
-                plan_fwd2(b, n, N, Ho, Wo, Cout, 9, 3, 3, 1, 1, 1, ktot, -1, false, true) && b.cost <= 1.08 * a.cost;
+                plan_fwd2(a, n, N, Ho, Wo, Cout, 9, 3, 3, 1, 1, 1, ktot, -1, false) &&
+                plan_fwd2(b, n, N, Ho, Wo, Cout, 9, 3, 3, 1, 1, 1, ktot, -1, true) && b.cost <= 1.08 * a.cost;
     }
     if (keep == 1.f && even && worth && env_int("RSU_FWD_GEN", 3) >= 3 && env_int("RSU_FWD2_CFG", -1) < 0) {
         const int rc = run_fwd(srcs, nsrc, packed_fwd, 0, rup(Cout, 128) / 16, 0, bias, y, nullptr, N, Hin, Win, Ho, Wo, Cout, Cout, 9, 3, 1, 1, 0, Ho, Wo,
@@ -1043,10 +1037,8 @@ static void finish_wgrad(WgPrep& w, int nsplit, float* ws) {
     p.bslab = w.db ? (nsplit == 1 ? w.db : ws + w.main_elems) : nullptr;
     p.sbslab = w.dbs ? (nsplit == 1 ? w.dbs : ws + w.main_elems) : nullptr;
 }
-struct WgUpdate { const UpJob* job; int seg, keep_grad; float lr, mu, gscale; };
 static int run_wgrad(int cfg, const void* F, int Hf, int Wf, int Cf, const rsu_src_t* S, float* out, float* ws, int CsOut, int CfOut,
-                     int cs_off, int N, int ntap, int kw, int dil, int stride, int ncu_arg, hipStream_t st, float* db = nullptr, float* dbs = nullptr,
-                     const WgUpdate* upd = nullptr) {
+                     int cs_off, int N, int ntap, int kw, int dil, int stride, int ncu_arg, hipStream_t st, float* db = nullptr, float* dbs = nullptr) {
     const int ncu = launch_ncu(ncu_arg);
     if (ncu < 0) return RSU_EINVAL;
     WgPrep w;
@@ -1062,21 +1054,7 @@ static int run_wgrad(int cfg, const void* F, int Hf, int Wf, int Cf, const rsu_s
         HIP_CHECK_RET(igemm_wgp64_launch(p, w.gx, w.gy, nslab, st));
     else
         HIP_CHECK_RET(igemm_wgrad_launch(w.cfg, ntap, p, w.gx, w.gy, nslab, st));
-    if (upd) {
-        // the reduce launch IS the Momentum step + re-pack of the rows this source owns (k_update_pack_seg): nslab == 1 reads the gradient
-        // the kernel above wrote in place
-        // -- unless the launch has many slabs of a small kernel (>= 16: the 64- .. 256-channel layers): the update pass has one workgroup per
-        // 32 x 128 weights, far too few to stream 16 .. 128 slabs each (measured: c2 945 -> 750 patches/s); those keep the wide reduce launch and the
-        // update reads the finished gradient, L2-hot
-        const int fuse_max = env_int("RSU_FUSED_MAX_SPLIT", 15);
-        if (nslab > fuse_max) {
-            HIP_CHECK_RET(ew_reduce_slabs(ws, out, db ? db : dbs, w.extra / 4, nslab, p.slab_stride, ntap, CsOut, cs_off, S->C, CfOut, st));
-            HIP_CHECK_RET(ew_update_pack_seg(*upd->job, upd->seg, out, 0, 1, nullptr, nullptr, 0, upd->lr, upd->mu, upd->gscale, st));
-        } else {
-            HIP_CHECK_RET(ew_update_pack_seg(*upd->job, upd->seg, nslab > 1 ? ws : out, nslab > 1 ? p.slab_stride : 0, nslab, upd->keep_grad ? out : nullptr,
-                                             db ? db : dbs, w.extra / 4, upd->lr, upd->mu, upd->gscale, st));
-        }
-    } else if (nslab > 1) {
+    if (nslab > 1) {
         HIP_CHECK_RET(ew_reduce_slabs(ws, out, db ? db : dbs, w.extra / 4, nslab, p.slab_stride, ntap, CsOut, cs_off, S->C, CfOut, st));
     }
     return RSU_OK;
@@ -1092,21 +1070,6 @@ extern "C" int rsu_conv2d_bwd_weight(const rsu_src_t* src, const void* dz, float
     if (src->oy < 0 || src->ox < 0 || src->oy + Ho + 2 * dil > src->H || src->ox + Wo + 2 * dil > src->W || Wo < 2) return RSU_EINVAL;
     // F = dz (cf = co), S = layer input (cs = ci): slab[tap][ci][co] = HWIO
     return run_wgrad(IGW_CFG_64x64, dz, Ho, Wo, Cout, src, dw, ws, Cin_total, Cout, ci_off, N, 9, 3, dil, 1, ncu, (hipStream_t)stream, db);
-}
-
-extern "C" int rsu_conv2d_bwd_weight_update(const rsu_src_t* src, const void* dz, float* dw, float* db, float* ws, int N, int Ho, int Wo,
-                                            int Cin_total, int ci_off, int Cout, int dil, int ncu, const void* update_entry, int seg, float lr,
-                                            float mu, float gscale, int keep_grad, rsu_stream_t stream) {
-    if (!src || !src->ptr || !dz || !dw || !ws || src->C % 8 || Cout % 8 || ci_off + src->C > Cin_total || (dil != 1 && dil != 2))
-        return RSU_EINVAL;
-    if (src->oy < 0 || src->ox < 0 || src->oy + Ho + 2 * dil > src->H || src->ox + Wo + 2 * dil > src->W || Wo < 2) return RSU_EINVAL;
-    const UpJob* J = (const UpJob*)update_entry;
-    // the entry must describe THIS kernel (rsu_update_table_add, kind RSU_PACK_CONV_FWD, g = dw) and `seg` the source at hand
-    if (!J || J->kind != 1 || J->ntap != 9 || J->R1 != Cin_total || J->R2 != Cout || J->g != dw || seg < 0 || seg >= J->nseg ||
-        J->seg_r0[seg] != ci_off || J->seg_c[seg] != src->C)
-        return RSU_EINVAL;
-    WgUpdate u{J, seg, keep_grad, lr, mu, gscale};
-    return run_wgrad(IGW_CFG_64x64, dz, Ho, Wo, Cout, src, dw, ws, Cin_total, Cout, ci_off, N, 9, 3, dil, 1, ncu, (hipStream_t)stream, db, nullptr, &u);
 }
 
 extern "C" size_t rsu_convT2x2_bwd_weight_ws_floats(int Cin, int Cout) {

@@ -167,15 +167,12 @@ class ConvolutionalModel:
         net.forward_device(keep=float(opts.dropout))
         if self._bucketer is not None:
             self._bucketer.reset()
-        # (single device: Momentum + re-pack of the conv kernels fused into their weight-gradient launches, rsu.h rsu_conv2d_bwd_weight_update)
-        adam = opts.optimizer == "adam"   # (Adam never rides on the weight-gradient launches)
-        net.backward_device(1.0 / (opts.batch_size * opts.patch_size * opts.patch_size),
-                            update=(opts.lr, opts.momentum) if self._bucketer is None and not adam else None)
+        net.backward_device(1.0 / (opts.batch_size * opts.patch_size * opts.patch_size))
         loss = net.loss_sum / (opts.batch_size * opts.patch_size * opts.patch_size)
         if self._bucketer is not None:
             self._bucketer.finish()
             dist.all_reduce(loss)
-        if adam:
+        if opts.optimizer == "adam":
             net.apply_adam(opts.lr, opts.adam_beta1, opts.adam_beta2, opts.adam_epsilon)
         else:
             net.apply_momentum(opts.lr, opts.momentum)

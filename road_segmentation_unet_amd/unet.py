@@ -27,8 +27,6 @@ NUM_LABELS = 2    # src/constants.py:4
 _WG_GROUP_TWO_STREAMS, _WG_GROUP_ONE_STREAM = "0", "all"
 # RSU_RAW_EVENTS=0: fork the side stream through torch events (system-scope release) instead of _lib.hip_fork (agent scope)
 _RAW_EVENTS = os.environ.get("RSU_RAW_EVENTS", "1") != "0"
-_NO_FORK_PROBE = os.environ.get("RSU_NO_FORK_PROBE", "0") == "1"   # developer timing probe (profiles/r06/fork_bound.txt): NO dependency at all
-_WG_EVENTS = os.environ.get("RSU_WG_EVENTS", "0") == "1"   # grouped weight gradients: a torch event per queued job (rounds 2-3)
 _SPLIT_DEFAULT = "128,128"   # RSU_SPLIT_CHIP: CUs the main stream / each side stream plan for during the backward pass (UNet._Side)
 
 
@@ -154,7 +152,7 @@ class UNet:
         # grouped weight gradients (rsu.h rsu_wgrad_group_*): the launches of RSU_WG_GROUP consecutive levels / decoder stages of the
         # backward pass go out as ONE launch (0: one launch per layer, as in round 2; "all": one group behind the whole pass)
         self._wg_sizes, self._wg_group = [0], 0   # set per backward pass (_wg_policy)
-        self._wg_pending, self._wgT_pending, self._wg_levels, self._wg_event, self._wg_index = [], [], 0, None, 0
+        self._wg_pending, self._wgT_pending, self._wg_levels, self._wg_index = [], [], 0, 0
         self._side_active = False   # a weight-gradient launch has gone to the side stream in this backward pass
         self._wg_plans = {}
         self._side_rr = 0
@@ -163,10 +161,7 @@ class UNet:
             nside = max(1, len(os.environ.get("RSU_SPLIT_CHIP", _SPLIT_DEFAULT).split(",")) - 1)
             self.wstreams = [torch.cuda.Stream(device=self.device) for _ in range(nside)]
             self.wstream = self.wstreams[0]
-        # Momentum + re-pack fused into the weight-gradient side (backward_device(update=...), world size 1): the backward-data launches of
-        # step t read set `_pkset` of the backward-data packs while the fused updates of the same step write the other set
-        self._pkset, self.pk_alt, self._fused_tabs, self._fused, self._fused_pending = 0, {}, {}, None, None
-        self._update_tables, self._update_table = {}, None
+        self._update_table = None   # the job table of the optimizer's update pass (_build_update_table), built on first use
         self.pool_code = {}
         self.prof = None       # list collecting (tag, algorithmic flops, start event, end event, CU share) when profiling
         self.on_grads = None   # callback(lo): every gradient at flat position >= lo is final (see dist.GradBucketer)
@@ -396,7 +391,6 @@ class UNet:
             self._pack_n, self._pack_blocks = idx, nb.value
             self._pack_table = torch.frombuffer(bytearray(host.raw[:esz * idx]), dtype=torch.uint8).to(self.device)
         call("rsu_pack_table_run", _ptr(self._pack_table), self._pack_n, self._pack_blocks, st)
-        self._pkset = 0   # (the pack table writes set 0 of the backward-data packs)
 
     # ------------------------------------------------------------------ forward
     def _stream(self):
@@ -470,9 +464,8 @@ class UNet:
         """`with UNet._Side(net) as side:` -- launches inside go to the next side stream (round robin) and plan for that stream's share
         of the chip; side.ws is its workspace"""
 
-        def __init__(self, net, alone=False, after=None):
+        def __init__(self, net, alone=False):
             self.net, self.ctx, self.alone = net, None, alone  # alone: nothing is left to run beside it on the main stream
-            self.after = after   # event on the main stream behind which the side stream may start (None: everything issued so far)
             self.ws = net.ws if net.training else None
             self.saved_ncu = net._ncu
 
@@ -487,12 +480,7 @@ class UNet:
             self.ws = n.ws_side[k]
             if n._split is not None:
                 n._ncu = n._split[0] if self.alone else n._split[2][k]
-            ev = self.after
-            if _NO_FORK_PROBE and n._split is not None and n._side_active:
-                # (timing probe only: behind the first fork of a backward pass the side stream no longer waits for the main stream -- wrong
-                # numbers, the bound of a dependency that costs neither queue anything: profiles/r06/fork_bound.txt)
-                pass
-            elif ev is None and _RAW_EVENTS:
+            if _RAW_EVENTS:
                 # the fork costs the MAIN queue an idle gap per weight-gradient launch (the event's packet sits between two backward-data
                 # kernels): ~6 us with a torch event, less without the system-scope fence a same-device dependency does not need
                 try:
@@ -505,9 +493,8 @@ class UNet:
                     ev.record(torch.cuda.current_stream(n.device))
                     n.wstreams[k].wait_event(ev)
             else:
-                if ev is None:
-                    ev = torch.cuda.Event()
-                    ev.record(torch.cuda.current_stream(n.device))
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.current_stream(n.device))
                 n.wstreams[k].wait_event(ev)
             self.ctx = torch.cuda.stream(n.wstreams[k])
             self.ctx.__enter__()
@@ -591,24 +578,11 @@ class UNet:
         # 16-channel tensor is never built, same bits). A training step needs that tensor for the first conv's weight gradient anyway, and the
         # first conv reads it back hot from the Infinity Cache: measured (profiles/r06/kernel_stats_fused_first.md), the fused launch beside a
         # colour-adjust launch on the side stream takes 66 us against 14.5 + 48 us of the two launches in a row -- training keeps the two.
-        # RSU_FIRST_FUSED=0: never fuse; =2: fuse in training steps too (the measured variant).
-        ff = os.environ.get("RSU_FIRST_FUSED", "1")
-        fused_first = keep == 1.0 and (ff == "2" or (ff != "0" and not self.training))
+        fused_first = keep == 1.0 and not self.training
         xin = x if fused_first else None
-
-        def color_adjust():
-            call("rsu_color_adjust_fwd", _ptr(x), _ptr(self.w["color_space_adjust/kernel"]), _ptr(self.w["color_space_adjust/bias"]),
-                 _ptr(in16), nb * S * S, keep, self.dropout_key(0), self._stream())
         if not fused_first:
-            add(color_adjust)
-        elif self.training:
-            if len(self.wstreams) == 1:   # (one side stream: its later launches that read in16 follow in order; the main stream joins it before its own)
-                def color_adjust_side():
-                    with UNet._Side(self):
-                        color_adjust()
-                add(color_adjust_side)
-            else:
-                add(color_adjust)
+            add(lambda: call("rsu_color_adjust_fwd", _ptr(x), _ptr(self.w["color_space_adjust/kernel"]), _ptr(self.w["color_space_adjust/bias"]),
+                             _ptr(in16), nb * S * S, keep, self.dropout_key(0), self._stream()))
         cur, h = None, S
         for i in range(L):
             last = i == L - 1
@@ -674,46 +648,6 @@ class UNet:
         return steps
 
     # ------------------------------------------------------------------ backward
-    def _bwd_pack(self, kname, si, other=False):
-        """the backward-data pack of concat source si of conv kernel `kname` in the set the backward-data launches read now (other: the
-        set the fused updates of this step write; allocated on first use)"""
-        if (self._pkset == 0) != other:
-            return self.pk[kname, "bwd", si]
-        return self._bwd_pack_set1(kname, si)
-
-    def _fused_names(self):
-        """kernels whose Momentum step rides on their weight-gradient launches (backward_device(update=...)): every 3x3 conv kernel the
-        MFMA weight-gradient kernels serve -- all but the level-0 conv1 kernels (Cin = 3) and the transposed convs"""
-        return [n for n, (o, c, sh) in self._slices.items()
-                if o < self.n_live and n.endswith("kernel") and len(sh) == 4 and sh[0] == 3 and sh[2] != NUM_CHANNELS and not n.startswith("up_conv")]
-
-    def _fused_entry(self, kname):
-        """host pointer to the rsu_update_table_add entry of `kname` whose backward-data packs are the set NOT read in this step"""
-        tab = self._fused_tabs.get(kname)
-        lib = _lib.lib()
-        esz = lib.rsu_update_table_entry_bytes()
-        if tab is None:
-            sh = self._slices[kname][2]
-            segs = self._conv_sources_c(kname, sh)
-            host = ctypes.create_string_buffer(esz * 2)
-            keep = []
-            for st_ in (0, 1):   # entry st_ WRITES set st_
-                ptrs = [(self.pk[kname, "bwd", si] if st_ == 0 else self._bwd_pack_set1(kname, si)).data_ptr() for si in range(len(segs))]
-                bw = (ctypes.c_void_p * len(segs))(*ptrs)
-                keep.append(bw)
-                rc = lib.rsu_update_table_add(host, st_, 0, _ptr(self.w[kname]), _ptr(self.acc[kname]), _ptr(self.g[kname]), _ptr(self.pk[kname, "fwd"]), bw,
-                                              sh[2], sh[3], (ctypes.c_int * len(segs))(*segs), len(segs))
-                if rc != 1:
-                    raise _lib.RsuError("rsu_update_table_add(%s) failed: %d" % (kname, rc))
-            tab = self._fused_tabs[kname] = (host, keep)
-        return ctypes.c_void_p(ctypes.addressof(tab[0]) + esz * (1 - self._pkset))
-
-    def _bwd_pack_set1(self, kname, si):
-        t = self.pk_alt.get((kname, si))
-        if t is None:
-            t = self.pk_alt[kname, si] = torch.zeros_like(self.pk[kname, "bwd", si])
-        return t
-
     def _wgrad(self, name, srcs_t, dz, hout, dil=1):
         """dW (HWIO rows per source) + db of conv `name`; srcs_t = list of (tensor, window size). With grouping on (RSU_WG_GROUP) the
         launches are only queued here; _flush_wgrads sends a whole group to the side stream as one launch."""
@@ -727,11 +661,8 @@ class UNet:
                                   db.data_ptr() if db is not None else None, hout, hout, cin_total, off, cout, dil)
                 self._wg_pending.append((job, 2.0 * self.B * hout * hout * cout * t.shape[3] * 9, (name, off)))
                 off += t.shape[3]
-            # (rounds 2-3 recorded a torch event on the main stream here, per queued job, so that a group flushed later would not wait for
-            # more than it reads: every record costs the main queue ~5 us between two backward-data kernels -- RSU_WG_EVENTS=1 restores it.
-            # Now the group forks where it is flushed, through the raw event of _Side.)
-            if _WG_EVENTS:
-                self._wg_event = self._record_main()
+            # (no event per queued job: the group forks where it is flushed, through the raw event of _Side -- a torch event recorded here
+            # would cost the main queue ~5 us between two backward-data kernels)
             if name.endswith("conv2") and not (name.startswith("conv_0/") and not self.dilated):   # (the last group: flushed by the caller, which knows that nothing runs beside it)
                 # a group closes BEHIND a conv2 gradient: dz of a block's conv2 is there when the block's backward pass begins, so the
                 # group {conv1 (+ transposed conv) of the block before, conv2 of this one} can run beside ALL of this block's
@@ -742,19 +673,12 @@ class UNet:
             return
         with UNet._Side(self) as side:
             st = self._stream()
-            for si, (t, win) in enumerate(srcs_t):
+            for t, win in srcs_t:
                 s = _src(t, win, win)
                 db = _ptr(self.g[name + "/bias"]) if off == 0 else None  # BiasAddGrad rides along with the first source's launch
                 fl = 2.0 * self.B * hout * hout * cout * t.shape[3] * 9
-                if self._fused is not None:
-                    # the launch that sums the slabs is the Momentum step + re-pack of the rows this source owns (rsu.h)
-                    lr, mu, keep_grad = self._fused
-                    self._timed("conv3x3_bwd_weight", fl, "rsu_conv2d_bwd_weight_update", ctypes.byref(s), _ptr(dz), _ptr(self.g[name + "/kernel"]), db,
-                                _ptr(side.ws), self.B, hout, hout, cin_total, off, cout, dil, self._ncu, self._fused_entry(name + "/kernel"), si, lr, mu, 1.0,
-                                keep_grad, st)
-                else:
-                    self._timed("conv3x3_bwd_weight", fl, "rsu_conv2d_bwd_weight", ctypes.byref(s), _ptr(dz), _ptr(self.g[name + "/kernel"]), db,
-                                _ptr(side.ws), self.B, hout, hout, cin_total, off, cout, dil, self._ncu, st)
+                self._timed("conv3x3_bwd_weight", fl, "rsu_conv2d_bwd_weight", ctypes.byref(s), _ptr(dz), _ptr(self.g[name + "/kernel"]), db,
+                            _ptr(side.ws), self.B, hout, hout, cin_total, off, cout, dil, self._ncu, st)
                 off += t.shape[3]
 
     def _wgradT(self, i, upin, dup, hh, nf):
@@ -763,19 +687,10 @@ class UNet:
             job = RsuWgradJob(_lib.WGRAD_CONVT2X2, RsuSrc(upin.data_ptr(), hh, hh, upin.shape[3], 0, 0), dup.data_ptr(),
                               self.g["up_conv_%d/kernel" % i].data_ptr(), self.g["up_conv_%d/bias" % i].data_ptr(), 0, 0, 0, 0, nf, 1)
             self._wgT_pending.append((job, 0.0, ("up_conv_%d" % i, upin.data_ptr())))
-            if _WG_EVENTS:
-                self._wg_event = self._record_main()
             return
         with UNet._Side(self) as side:
             call("rsu_convT2x2_bwd_weight", _ptr(upin), _ptr(dup), _ptr(self.g["up_conv_%d/kernel" % i]), _ptr(self.g["up_conv_%d/bias" % i]),
                  _ptr(side.ws), self.B, hh, hh, upin.shape[3], nf, self._ncu, self._stream())
-
-    def _record_main(self):
-        if not self.wstreams:
-            return None
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.device))
-        return ev
 
     def _flush_wgrads(self, alone=False):
         """Launch the queued weight gradients as grouped launches on the side stream (everything they read has been produced by launches
@@ -790,7 +705,7 @@ class UNet:
                 chunk, rest = pending[:_lib.WGRAD_GROUP_MAX], pending[_lib.WGRAD_GROUP_MAX:]
                 del pending[:]
                 pending.extend(rest)
-                with UNet._Side(self, alone=alone, after=self._wg_event if _WG_EVENTS else None) as side:
+                with UNet._Side(self, alone=alone) as side:
                     key = (tuple(k for _, _, k in chunk), self._ncu, side.ws.data_ptr())
                     plan = self._wg_plans.get(key)
                     if plan is None:
@@ -814,19 +729,13 @@ class UNet:
         ho = hin - 2 * dil
         kws = self._kws()
         self._timed("conv3x3_bwd_data", 2.0 * self.B * ho * ho * cout * cnt * 9, "rsu_conv2d_bwd_data_k", _ptr(dz),
-                    _ptr(self._bwd_pack(name + "/kernel", src_index)), _ptr(dx), _ptr(relu_src), accumulate, self.B, hin, hin, cnt, 0, cnt,
+                    _ptr(self.pk[name + "/kernel", "bwd", src_index]), _ptr(dx), _ptr(relu_src), accumulate, self.B, hin, hin, cnt, 0, cnt,
                     cout, dil, self._ncu, _ptr(kws), kws.numel() if kws is not None else 0, self._stream())
 
-    def backward_device(self, inv_count, update=None, keep_grad=False):
+    def backward_device(self, inv_count, update=None):
         """loss + all gradients for self.x / self.labels; forward_device() must have run. inv_count = 1 / (global pixel count).
-        update = (lr0, momentum): single-device training -- the MomentumOptimizer step (tf_aerial_images.py:120-121) and the re-pack of every
-        3x3 conv kernel ride on the kernel's weight-gradient launches (rsu.h rsu_conv2d_bwd_weight_update: the gradient is neither written
-        nor re-read, the pass leaves the tail of the step); apply_momentum(lr0, momentum) MUST follow and then only steps the remaining
-        variables. Same bits as the plain pair of calls. keep_grad: self.g of those kernels is written as well (it is not otherwise).
-        OPT-IN (RSU_FUSED_WGRAD=1; otherwise, and where the weight gradients are grouped or a gradient exchange runs, the plain schedule
-        runs and apply_momentum steps everything): measured in round 6, the pass costs the weight-gradient stream -- which is as long as
-        the backward-data stream -- more than it saves behind the pass: c2 955 -> 888 patches/s, c3 212 -> 184 (profiles/r06/abenv_fused2_*.txt;
-        an HBM-bound pass on the half of the chip the weight-gradient kernel leaves it, beside a backward-data kernel)."""
+        update = (lr0, momentum): accepted from callers that name the Momentum step they will take; it changes nothing here -- the step
+        is apply_momentum's -- but a net built with another optimizer refuses it."""
         B, L, st, a, g = self.B, self.L, self._stream(), self.act, self.grad
         keep = self.keep
         last = a[self.last_name]
@@ -834,15 +743,9 @@ class UNet:
             raise _lib.RsuError("backward_device(update=...) is the Momentum step; an %s net steps with apply_%s after the pass"
                                 % (self.optimizer, self.optimizer))
         self._begin_split()
-        self._fused = self._fused_pending = None
-        if (update is not None and self.training and self._wg_group == 0 and self.on_grads is None and self.device.type == "cuda"
-                and os.environ.get("RSU_FUSED_WGRAD", "0") == "1" and os.environ.get("RSU_FUSED_UPDATE", "1") != "0"):
-            self._fused = (self.learning_rate(update[0]), float(update[1]), 1 if keep_grad else 0)
-            self._fused_pending = (float(update[0]), float(update[1]))
         try:
             self._backward_body(inv_count)
         finally:
-            self._fused = None
             self._end_split()   # (an exception inside must not leave later launches planned for a share of the chip)
         # ---- color_space_adjust (unet.py:22-23): its input gradient is never materialised (include/rsu.h, rsu_conv_first_bwd_weight):
         #   dW0[ci][cj] = 1/keep * sum_{t,co} W1[t][cj][co] * gxc[t][ci][cj][co];  db0[cj] = 1/keep * sum_{t,co} W1[t][cj][co] * gm[t][cj][co]
@@ -991,15 +894,14 @@ class UNet:
         """tf.train.exponential_decay(lr, global_step, 1000, 0.95, staircase=True) (tf_aerial_images.py:116-117), float32"""
         return float(np.float32(lr0) * np.float32(0.95) ** np.float32(self.global_step // 1000))
 
-    def _build_update_table(self, pkset=0, rest_only=False, adam=False):
-        """the job table of rsu_update_table_run: one entry per conv / transposed-conv kernel (with its packed copies; the backward-data
-        packs of set `pkset`), the variables between them (biases, colour adjust, the 1x1 head) as plain Momentum ranges; covers [0, n_live)
-        of the flat buffers once. rest_only: without the kernels whose step rode on their weight-gradient launches (_fused_names).
-        adam: the table of rsu_update_table_run_adam (every entry also gets its slice of flat_v; acc holds m); cached apart."""
+    def _build_update_table(self):
+        """the job table of rsu_update_table_run: one entry per conv / transposed-conv kernel (with its packed copies), the variables between
+        them (biases, colour adjust, the 1x1 head) as plain Momentum ranges; covers [0, n_live) of the flat buffers once. An Adam net: the
+        table of rsu_update_table_run_adam (every entry also gets its slice of flat_v; acc holds m). Cached as self._update_table."""
         lib = _lib.lib()
         if not hasattr(self, "pk"):
             self.repack()
-        skip = set(self._fused_names()) if rest_only else set()
+        adam = self.optimizer == "adam"
         entries, plain_lo = [], None   # ("plain", lo, hi) / ("tensor", name, kind)
         live = sorted(((o, c, n, sh) for n, (o, c, sh) in self._slices.items() if o < self.n_live), key=lambda t: t[0])
         for o, c, n, sh in live:
@@ -1010,8 +912,7 @@ class UNet:
             if plain_lo is not None:
                 entries.append(("plain", plain_lo, o))
                 plain_lo = None
-            if n not in skip:
-                entries.append(("tensor", n, sh))
+            entries.append(("tensor", n, sh))
         if plain_lo is not None:
             entries.append(("plain", plain_lo, self.n_live))
         esz = lib.rsu_update_table_entry_bytes()
@@ -1034,8 +935,7 @@ class UNet:
                     rc = lib.rsu_update_table_add(host, idx, 4, w, a, g, _ptr(self.pk[n, "fwd"]), None, 3, sh[3], None, 0)
                 else:
                     segs = self._conv_sources_c(n, sh)
-                    packs = [self.pk[n, "bwd", si] if pkset == 0 else self._bwd_pack_set1(n, si) for si in range(len(segs))]
-                    bw = (ctypes.c_void_p * len(segs))(*[t.data_ptr() for t in packs]) if self.training else None
+                    bw = (ctypes.c_void_p * len(segs))(*[self.pk[n, "bwd", si].data_ptr() for si in range(len(segs))]) if self.training else None
                     rc = lib.rsu_update_table_add(host, idx, 0, w, a, g, _ptr(self.pk[n, "fwd"]), bw, sh[2], sh[3], (ctypes.c_int * len(segs))(*segs), len(segs))
                 keep.append(bw)
                 v = self.v[n] if adam else None
@@ -1045,38 +945,21 @@ class UNet:
                 _lib.check(lib.rsu_update_table_set_second_slot(host, idx, _ptr(v)), "rsu_update_table_set_second_slot(%s)" % (e[1],))
         nb = ctypes.c_int(0)
         _lib.check(lib.rsu_update_table_finish(host, len(entries), ctypes.byref(nb)), "rsu_update_table_finish")
-        tab = (torch.frombuffer(bytearray(host.raw), dtype=torch.uint8).to(self.device), len(entries), nb.value)
-        if adam:
-            self._update_tables["adam", pkset] = tab
-            return tab
-        self._update_tables[pkset, rest_only] = tab
-        if pkset == 0 and not rest_only:
-            self._update_table = tab   # (the name tools and probes know)
-        return tab
+        self._update_table = (torch.frombuffer(bytearray(host.raw), dtype=torch.uint8).to(self.device), len(entries), nb.value)
+        return self._update_table
 
     def apply_momentum(self, lr0, momentum, gscale=1.0):
         """MomentumOptimizer step on every live variable (tf_aerial_images.py:120-121) and the re-pack of the bf16 MFMA copies, in one
-        pass over the parameters (rsu_update_table_run; RSU_FUSED_UPDATE=0: rsu_momentum_step, then the batched re-pack -- same bits).
-        Behind backward_device(update=(lr0, momentum)) the 3x3 conv kernels have been stepped already: only the other variables are."""
+        pass over the parameters (rsu_update_table_run; RSU_FUSED_UPDATE=0: rsu_momentum_step, then the batched re-pack -- same bits)."""
         if self.optimizer != "momentum":
             raise _lib.RsuError("apply_momentum on a net built with optimizer=%r" % self.optimizer)
-        pending, self._fused_pending = self._fused_pending, None
-        if pending is not None:
-            if pending != (float(lr0), float(momentum)) or gscale != 1.0:
-                raise _lib.RsuError("apply_momentum(%r, %r, gscale=%r) behind backward_device(update=%r): the step already applied to the conv kernels "
-                                    "used other hyper-parameters" % (lr0, momentum, gscale, pending))
-            tab = self._update_tables.get((0, True)) or self._build_update_table(0, True)
-            call("rsu_update_table_run", _ptr(tab[0]), tab[1], tab[2], self.learning_rate(lr0), momentum, gscale, self._stream())
-            self._pkset = 1 - self._pkset   # the fused updates wrote the other set of backward-data packs: the next step reads it
-            self.global_step += 1
-            return
         if os.environ.get("RSU_FUSED_UPDATE", "1") == "0":
             call("rsu_momentum_step", _ptr(self.flat_w), _ptr(self.flat_acc), _ptr(self.flat_g), self.learning_rate(lr0), momentum, gscale,
                  self.n_live, self._stream())
             self.global_step += 1
             self.repack()
             return
-        tab = self._update_tables.get((self._pkset, False)) or self._build_update_table(self._pkset, False)
+        tab = self._update_table or self._build_update_table()
         call("rsu_update_table_run", _ptr(tab[0]), tab[1], tab[2], self.learning_rate(lr0), momentum, gscale, self._stream())
         self.global_step += 1
 
@@ -1095,7 +978,7 @@ class UNet:
             call("rsu_adam_step", _ptr(self.flat_w), _ptr(self.flat_acc), _ptr(self.flat_v), _ptr(self.flat_g), *args, self.n_live, self._stream())
             self.repack()
         else:
-            tab = self._update_tables.get(("adam", self._pkset)) or self._build_update_table(self._pkset, False, adam=True)
+            tab = self._update_table or self._build_update_table()
             call("rsu_update_table_run_adam", _ptr(tab[0]), tab[1], tab[2], *args, self._stream())
         self.global_step += 1
         self.beta1_power, self.beta2_power = b1p, b2p

@@ -177,7 +177,7 @@ def test_optimizers_refuse_each_others_steps():
         m.apply_momentum(0.01, 0.9)
     m.forward_device()
     with pytest.raises(RsuError):
-        m.backward_device(1.0 / 800, update=(0.01, 0.9))   # the fused Momentum route is Momentum-only
+        m.backward_device(1.0 / 800, update=(0.01, 0.9))   # update= names a Momentum step
     mm = _net(2, 16, False, 20, 2, optimizer="momentum")
     assert mm.flat_v is None
     with pytest.raises(RsuError):
