@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Probe (GPU box): what a dependency between two HIP streams of one device costs, per mechanism. Main stream: 40 kernels of ~50 us back to
 back; behind every second one the side stream is released to run a ~40 us kernel. Variants: no dependency at all (floor), torch events,
-raw HIP events without timing / system fence (unet._Side today), hipStreamWriteValue32 + hipStreamWaitValue32 on signal memory."""
+raw HIP events without timing / system fence (schedule.BackwardSchedule.side today), hipStreamWriteValue32 + hipStreamWaitValue32 on signal memory."""
 import ctypes, time, sys, os
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

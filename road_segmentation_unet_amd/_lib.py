@@ -199,7 +199,7 @@ def hip_fork(main_stream, side_stream, device_index=None):
     """`side_stream` waits for everything issued on `main_stream` so far (both hipStream_t handles as integers), through a HIP event
     created with hipEventDisableTiming | hipEventDisableSystemFence. torch.cuda.Event releases at system scope (visible to the host and
     to other devices); a dependency between two streams of ONE device needs agent scope only, and the event's packet holds up the
-    recording queue for less (unet.UNet._Side: one fork per weight-gradient launch, +0.9 % on the step). A ring of 64 events PER DEVICE
+    recording queue for less (schedule.BackwardSchedule.side: one fork per weight-gradient launch, +0.9 % on the step). A ring of 64 events PER DEVICE
     (`device_index`: the device the two streams belong to; None = torch's current device) is re-used: an event is re-recorded long
     after its waiter has been enqueued (hipStreamWaitEvent captures the record in flight)."""
     import torch

@@ -15,19 +15,11 @@ import torch
 
 from . import _lib
 from ._lib import RsuSrc, RsuWgradJob, call
+from .schedule import BackwardSchedule, cu_shares  # noqa: F401  (cu_shares: importable from here as before)
 
 NUM_CHANNELS = 3  # src/constants.py:3
 NUM_LABELS = 2    # src/constants.py:4
-
-
-# RSU_WG_GROUP: how the weight gradients of a backward pass are launched (UNet._flush_wgrads). Default: one launch per layer where a
-# side stream runs them beside the backward-data launches (each kernel on half the chip: per layer they are as efficient there as a
-# group, and the fine grain keeps both streams busy to the end -- measured, profiles/r03/wg_group_schedules.txt), ONE grouped launch behind
-# the pass where everything runs on one stream (alone on the chip a layer's launch pays 75 MB of slabs and a partly filled last round)
-_WG_GROUP_TWO_STREAMS, _WG_GROUP_ONE_STREAM = "0", "all"
-# RSU_RAW_EVENTS=0: fork the side stream through torch events (system-scope release) instead of _lib.hip_fork (agent scope)
-_RAW_EVENTS = os.environ.get("RSU_RAW_EVENTS", "1") != "0"
-_SPLIT_DEFAULT = "128,128"   # RSU_SPLIT_CHIP: CUs the main stream / each side stream plan for during the backward pass (UNet._Side)
+_PACK_CONV_FWD, _PACK_CONV_BWD, _PACK_CONVT_FWD, _PACK_CONVT_BWD, _PACK_CONV_FIRST = range(5)   # rsu.h RSU_PACK_*
 
 
 def input_size_needed(output_size, num_layers):
@@ -91,18 +83,6 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
-def cu_shares(full, parts):
-    """CUs the backward streams plan for: `parts` = RSU_SPLIT_CHIP as integers ([main, side, ...] out of 256), `full` = the CUs the backward pass
-    may use in all (256, or a data-parallel budget that leaves CUs to RCCL's channel workgroups). With the default 128 + 128 and a budget of
-    224 .. 255 the weight-gradient stream keeps its 128 -- its pixel splits and workgroup counts per XCD are powers of two: 120 + 120 costs c2
-    8 % and c4 5 %, 112 + 128 costs 1.7 % and 3.6 % (profiles/r06/dp_budget.txt) -- and the backward-data stream, whose persistent kernels walk
-    tile lists of any length, takes the rest. Below 224 the backward-data stream would starve (80 + 128: -16 %): shares in proportion, in
-    steps of 8, at least 32 -- as for every other setting."""
-    if full < 256 and list(parts) == [128, 128] and full >= 224:
-        return [full - 128, 128]
-    return [max(32, v * full // 256 // 8 * 8) for v in parts]
-
-
 def adam_scalars(lr_t, beta1_power, beta2_power, beta1, beta2):
     """The host side of one tf.train.AdamOptimizer step, float32 as TensorFlow computes it: alpha = lr_t * sqrt(1 - beta2^t) / (1 - beta1^t)
     (ApplyAdam's step size, from the powers BEFORE the step) and the powers after it (AdamOptimizer._finish: beta1_power * beta1,
@@ -143,24 +123,11 @@ class UNet:
         self.training = training
         self.keep = 1.0        # dropout keep probability of the forward pass in flight (set by forward_device)
         self.dropout_seed = int(seed) if seed is not None else 0
-        self.wstream = None    # side stream for the weight-gradient launches (see _Side); wstreams: all of them
-        self.wstreams = []
-        self._split = None     # (full, main, [side ...]) CU budgets while a backward pass shares the chip between the streams
         self.backward_cu_budget = None   # CUs the backward launches may plan for in total (None: the library's default)
-        self._ncu = 0          # `ncu` argument of the MFMA launches issued now (0: the library's default budget)
         self._tuned = set()    # (training?, backward_cu_budget, dropout?) combinations the tuning pass has run for (tune / ensure_tuned)
-        # grouped weight gradients (rsu.h rsu_wgrad_group_*): the launches of RSU_WG_GROUP consecutive levels / decoder stages of the
-        # backward pass go out as ONE launch (0: one launch per layer, as in round 2; "all": one group behind the whole pass)
-        self._wg_sizes, self._wg_group = [0], 0   # set per backward pass (_wg_policy)
-        self._wg_pending, self._wgT_pending, self._wg_levels, self._wg_index = [], [], 0, 0
-        self._side_active = False   # a weight-gradient launch has gone to the side stream in this backward pass
-        self._wg_plans = {}
-        self._side_rr = 0
-        self._side_dirty = True
-        if training and self.device.type == "cuda" and os.environ.get("RSU_WGRAD_STREAM", "1") == "1":
-            nside = max(1, len(os.environ.get("RSU_SPLIT_CHIP", _SPLIT_DEFAULT).split(",")) - 1)
-            self.wstreams = [torch.cuda.Stream(device=self.device) for _ in range(nside)]
-            self.wstream = self.wstreams[0]
+        # which stream, CU share, weight-gradient group and workspace every launch gets; its side streams are `wstreams`
+        self.sched = BackwardSchedule(self.device, batch_size, training, self._timed)
+        self.wstream = self.wstreams[0] if self.wstreams else None   # the first side stream
         self._update_table = None   # the job table of the optimizer's update pass (_build_update_table), built on first use
         self.pool_code = {}
         self.prof = None       # list collecting (tag, algorithmic flops, start event, end event, CU share) when profiling
@@ -170,6 +137,15 @@ class UNet:
         self._alloc_params(params if params is not None else glorot_uniform_params(num_layers, root_size, dilated_layers, seed))
         self._alloc_buffers()
         self.repack()
+
+    @property
+    def wstreams(self):
+        """the side streams of the backward schedule: a host may assign [] for single-stream passes and assign the list back"""
+        return self.sched.streams
+
+    @wstreams.setter
+    def wstreams(self, streams):
+        self.sched.streams = streams
 
     # ------------------------------------------------------------------ parameters
     def _alloc_params(self, init):
@@ -299,9 +275,9 @@ class UNet:
         # workspace of the conv launches that cut their reduction into slices (rsu.h rsu_conv2d_fwd_k: the deep levels at small batches);
         # one per stream that issues conv launches -- the main stream, and the side stream of the dilated twin blocks in the forward pass
         nk = int(_lib.lib().rsu_conv_splitk_ws_floats()) if os.environ.get("RSU_KSPLIT", "1") != "0" else 0
-        self.kws = torch.zeros(nk, dtype=torch.float32, device=dev) if nk else None
+        self.sched.kws = torch.zeros(nk, dtype=torch.float32, device=dev) if nk else None
         # (one per side stream: whether a layer splits must never depend on which stream its launch went to)
-        self.kws_side = [torch.zeros(nk, dtype=torch.float32, device=dev) for _ in self.wstreams] if (nk and self.dilated) else []
+        self.sched.kws_side = [torch.zeros(nk, dtype=torch.float32, device=dev) for _ in self.wstreams] if (nk and self.dilated) else []
         if self.training:
             for k, t in self.act.items():
                 if k.startswith("up_") or k.startswith("c") or k.startswith("d") or k.startswith("pool_"):
@@ -314,18 +290,17 @@ class UNet:
                     self.grad["skipd_%d" % i] = torch.zeros_like(up)
             lib = _lib.lib()
             ws = [lib.rsu_head_ws_floats(B * self.P * self.P, self.root), lib.rsu_conv_first_bwd_ws_floats(self.root)]
-            for n, (_, _, s) in self._slices.items():
-                if n.endswith("kernel") and len(s) == 4 and s[0] == 3 and s[2] != 3:
-                    srcs = self._conv_sources_c(n, s)
-                    for c in srcs:
+            for kind, n, s, segs in self._packed_kernels():   # (the dead level L-1 dilated pair has the shapes of the level's live block)
+                if kind == _PACK_CONV_FWD:
+                    for c in segs:
                         ws.append(lib.rsu_conv2d_bwd_weight_ws_floats(s[2], c, s[3]))
                     ws.append(lib.rsu_bias_grad_ws_floats(B * S * S, s[3]))
-                if n.startswith("up_conv") and n.endswith("kernel"):
+                elif kind == _PACK_CONVT_FWD:
                     ws.append(lib.rsu_convT2x2_bwd_weight_ws_floats(s[3], s[2]))
             ws.append(lib.rsu_wgrad_group_ws_floats())
             self.ws = torch.zeros(int(max(ws)) + 64, dtype=torch.float32, device=dev)
             # (one workspace per stream that launches weight gradients: their slabs are live at the same time)
-            self.ws_side = [self.ws] + [torch.zeros_like(self.ws) for _ in self.wstreams[1:]]
+            self.sched.ws_side = [self.ws] + [torch.zeros_like(self.ws) for _ in self.wstreams[1:]]
             self.gfirst = torch.zeros((2, 9, 12, self.root), dtype=torch.float32, device=dev)  # gx of conv1 / atrous_conv1 (rsu.h)
             # code bytes of the max-pools (argmax + ReLU bits per pooled element, rsu_maxpool2x2_fwd_code): the gradient junction of a
             # level reads them instead of the level's conv2 activation. RSU_POOL_CODE=0: it reads the activation (same bits)
@@ -341,6 +316,19 @@ class UNet:
             return [cout] * (3 if self.dilated else 2)
         return [cin]
 
+    def _packed_kernels(self):
+        """(RSU_PACK_* kind of the forward pack, name, shape, concat segments or None) of every live variable that has bf16 MFMA copies,
+        in flat order: what repack(), _build_update_table() and the weight-gradient workspace sizing walk"""
+        for n, (_, _, s) in self._slices.items():
+            if not n.endswith("kernel") or _is_dead(n, self.L):
+                continue
+            if n.startswith("up_conv"):
+                yield _PACK_CONVT_FWD, n, s, None
+            elif s[0] == 3 and s[2] == NUM_CHANNELS:  # level-0 conv1 / atrous_conv1 over the 16-channel input tensor
+                yield _PACK_CONV_FIRST, n, s, None
+            elif s[0] == 3:
+                yield _PACK_CONV_FWD, n, s, self._conv_sources_c(n, s)
+
     # ------------------------------------------------------------------ packed bf16 weights
     def repack(self):
         """float32 master weights -> bf16 MFMA fragment order (after init / load / every optimizer step): ONE kernel launch
@@ -353,32 +341,29 @@ class UNet:
 
             def buf(nbytes):
                 return torch.zeros(nbytes // 2, dtype=torch.bfloat16, device=self.device)
-            for n, (_, _, s) in self._slices.items():
-                if not n.endswith("kernel") or _is_dead(n, self.L):
-                    continue
-                if n.startswith("up_conv"):
+            for kind, n, s, segs in self._packed_kernels():
+                if kind == _PACK_CONVT_FWD:
                     cout, cin = s[2], s[3]
                     self.pk[n, "fwd"] = buf(4 * lib.rsu_packed_bytes(1, cout, (ctypes.c_int * 1)(cin), 1))
                     self.pk[n, "bwd"] = buf(lib.rsu_packed_bytes(4, cin, (ctypes.c_int * 1)(cout), 1))
-                    jobs.append((2, n, self.pk[n, "fwd"], 2, cin, 0, cin, cout, None))
+                    jobs.append((kind, n, self.pk[n, "fwd"], 2, cin, 0, cin, cout, None))
                     if self.training:
-                        jobs.append((3, n, self.pk[n, "bwd"], 2, cin, 0, cin, cout, None))
-                elif s[0] == 3 and s[2] == NUM_CHANNELS:  # level-0 conv1 / atrous_conv1 over the 16-channel input tensor
+                        jobs.append((_PACK_CONVT_BWD, n, self.pk[n, "bwd"], 2, cin, 0, cin, cout, None))
+                elif kind == _PACK_CONV_FIRST:
                     self.pk[n, "fwd"] = buf(lib.rsu_packed_first_bytes(s[3]))
-                    jobs.append((4, n, self.pk[n, "fwd"], 3, 3, 0, 3, s[3], None))
-                elif s[0] == 3:
+                    jobs.append((kind, n, self.pk[n, "fwd"], 3, 3, 0, 3, s[3], None))
+                else:
                     cin, cout = s[2], s[3]
-                    segs = self._conv_sources_c(n, s)
                     self.pk[n, "fwd"] = buf(lib.rsu_packed_bytes(9, cout, (ctypes.c_int * len(segs))(*segs), len(segs)))
-                    jobs.append((0, n, self.pk[n, "fwd"], 3, cin, 0, cin, cout, segs))
+                    jobs.append((kind, n, self.pk[n, "fwd"], 3, cin, 0, cin, cout, segs))
                     off = 0
                     for si, c in enumerate(segs):  # one backward-data pack per concat source
                         self.pk[n, "bwd", si] = buf(lib.rsu_packed_bytes(9, c, (ctypes.c_int * 1)(cout), 1))
                         if self.training:
-                            jobs.append((1, n, self.pk[n, "bwd", si], 3, cin, off, c, cout, None))
+                            jobs.append((_PACK_CONV_BWD, n, self.pk[n, "bwd", si], 3, cin, off, c, cout, None))
                         off += c
             esz = lib.rsu_pack_table_entry_bytes()
-            host = ctypes.create_string_buffer(esz * (len(jobs) + 3 * sum(1 for j in jobs if j[0] == 2)))
+            host = ctypes.create_string_buffer(esz * (len(jobs) + 3 * sum(1 for j in jobs if j[0] == _PACK_CONVT_FWD)))
             idx = 0
             for kind, n, packed, k, cin, off, cnt, cout, segs in jobs:
                 seg = (ctypes.c_int * len(segs))(*segs) if segs else None
@@ -406,147 +391,33 @@ class UNet:
         call(fn, *args)
         e1.record()
         # (the share of the chip this launch plans for: bench.py prices a launch's duration by it -- two half-chip launches side by side)
-        self.prof.append((tag, flops, e0, e1, (self._ncu or _lib.lib().rsu_get_cu_budget()) / 256.0))
+        self.prof.append((tag, flops, e0, e1, (self.sched.ncu() or _lib.lib().rsu_get_cu_budget()) / 256.0))
 
     def _grads_ready(self, name):
         if self.on_grads is not None:  # (dist.GradBucketer waits for the weight-gradient stream itself: extra_streams)
-            self._flush_wgrads()       # queued weight gradients must be ON the side stream before the exchange may wait for it
+            self.sched.flush()         # queued weight gradients must be ON the side stream before the exchange may wait for it
             self.on_grads(self._slices[name][0])
-
-    # Weight-gradient launches can go to a second stream: they only READ what the main stream produced (dz, activations) and
-    # write gradients nobody reads before the optimizer. Two persistent kernels then share the chip and each fills the other's
-    # poorly occupied last round of tiles. RSU_WGRAD_STREAM=0 keeps everything on one stream.
-    #
-    # The two streams SHARE the chip by plan (RSU_SPLIT_CHIP, default _SPLIT_DEFAULT, of 256): while the backward pass runs, launches on
-    # the main stream (backward-data) plan their persistent workgroups for the first number of CUs, launches on the side stream
-    # (weight gradients) for the second, so a backward-data and a weight-gradient kernel are resident together, each on its
-    # own CUs, instead of taking turns on all of them. The weight gradient of a layer is a sum over one partial result PER
-    # WORKGROUP (a 295-KB slab each, written and read back by the reduce kernel): half the workgroups, half that traffic --
-    # and persistent kernels on fewer CUs lose less to their last, partly filled round of tiles. "0" = both plan for every CU.
-    def _wg_policy(self):
-        """RSU_WG_GROUP for this backward pass: "n" every group holds n blocks; "a,b,c" the first group a blocks, the second b, ... (the
-        last number repeats); "all" one group behind the whole pass; "0" one launch per layer"""
-        g = os.environ.get("RSU_WG_GROUP", _WG_GROUP_TWO_STREAMS if self.wstreams else _WG_GROUP_ONE_STREAM)
-        self._wg_sizes = [10 ** 6] if g == "all" else [max(0, int(v)) for v in g.split(",")]
-        self._wg_group = self._wg_sizes[0]
-
-    def _begin_split(self):
-        """CU shares of the backward pass: `backward_cu_budget` (set by the data-parallel host: CUs left to RCCL's channel workgroups
-        while the gradient exchange overlaps the backward pass; the forward pass keeps the whole chip) shared out between the
-        streams. Every launch carries its share as its own `ncu` argument (self._ncu): no library state changes between launches."""
-        self._split = None
-        self._wg_policy()
-        full = self.backward_cu_budget or _lib.lib().rsu_get_cu_budget()
-        spec = os.environ.get("RSU_SPLIT_CHIP", _SPLIT_DEFAULT)
-        parts = None
-        if self.wstreams and spec not in ("0", "") and self._wg_group < 10 ** 6:   # (RSU_WG_GROUP=all: nothing runs beside backward-data)
-            try:
-                parts = [int(v) for v in spec.split(",")]
-            except ValueError:
-                parts = None
-            if parts is not None and (len(parts) != len(self.wstreams) + 1 or min(parts) < 1):
-                parts = None
-        if parts is None:
-            self._ncu = full if self.backward_cu_budget else 0
-            return
-        parts = cu_shares(full, parts)
-        self._split = (full, parts[0], parts[1:])
-        # the main stream keeps the whole budget until the first weight-gradient launch has gone to the side stream
-        self._ncu = full if self.backward_cu_budget else 0
-
-    def _end_split(self):
-        self._split = None
-        self._ncu = 0
-        self._side_active = False
-        self._wg_index = 0
-
-    class _Side:
-        """`with UNet._Side(net) as side:` -- launches inside go to the next side stream (round robin) and plan for that stream's share
-        of the chip; side.ws is its workspace"""
-
-        def __init__(self, net, alone=False):
-            self.net, self.ctx, self.alone = net, None, alone  # alone: nothing is left to run beside it on the main stream
-            self.ws = net.ws if net.training else None
-            self.saved_ncu = net._ncu
-
-        def __enter__(self):
-            n = self.net
-            self.saved_ncu = n._ncu
-            if not n.wstreams:
-                return self
-            k = n._side_rr % len(n.wstreams)
-            n._side_rr += 1
-            n._side_dirty = True
-            self.ws = n.ws_side[k]
-            if n._split is not None:
-                n._ncu = n._split[0] if self.alone else n._split[2][k]
-            if _RAW_EVENTS:
-                # the fork costs the MAIN queue an idle gap per weight-gradient launch (the event's packet sits between two backward-data
-                # kernels): ~6 us with a torch event, less without the system-scope fence a same-device dependency does not need
-                try:
-                    _lib.hip_fork(torch.cuda.current_stream(n.device).cuda_stream, n.wstreams[k].cuda_stream, n.device.index)
-                except (_lib.RsuError, OSError, AttributeError) as ex:   # no usable runtime handle: torch's events do the same, a little slower
-                    import sys
-                    print("road_segmentation_unet_amd: raw HIP fork events unavailable (%r); using torch events" % (ex,), file=sys.stderr)
-                    globals()["_RAW_EVENTS"] = False
-                    ev = torch.cuda.Event()
-                    ev.record(torch.cuda.current_stream(n.device))
-                    n.wstreams[k].wait_event(ev)
-            else:
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream(n.device))
-                n.wstreams[k].wait_event(ev)
-            self.ctx = torch.cuda.stream(n.wstreams[k])
-            self.ctx.__enter__()
-            return self
-
-        def __exit__(self, *a):
-            try:
-                if self.ctx is not None:
-                    self.ctx.__exit__(*a)
-            finally:
-                n = self.net
-                n._ncu = self.saved_ncu   # on error paths too
-                if n._split is not None and self.ctx is not None and not n._side_active:
-                    n._side_active = True   # from here on the main stream's launches share the chip with the side stream's
-                    n._ncu = n._split[1]
-
-    def _join_side(self):
-        if not self._side_dirty:   # nothing has gone to a side stream since the last join: no wait packet on the main queue
-            return
-        for s in self.wstreams:
-            torch.cuda.current_stream(self.device).wait_stream(s)
-        self._side_dirty = False
 
     def _conv(self, name, srcs, hin, out, dil=1):
         arr = (RsuSrc * len(srcs))(*srcs)
         cout = out.shape[3]
         cin = sum(s.C for s in srcs)
         ho = hin - 2 * dil
-        kws = self._kws()
+        kws = self.sched.kws_here()
         nb = out.shape[0]   # (the batch of the tensors at hand: forward_device may run the two halves of a batch as two chains)
         self._timed("conv3x3_fwd", 2.0 * nb * ho * ho * cout * cin * 9, "rsu_conv2d_fwd_k", arr, len(srcs),
                     _ptr(self.pk[name + "/kernel", "fwd"]), _ptr(self.w[name + "/bias"]), _ptr(out), nb, hin, hin, cout, dil, 1,
-                    self._ncu, _ptr(kws), kws.numel() if kws is not None else 0, self._stream())
-
-    def _kws(self):
-        """the split-K workspace of the stream the next conv launch goes to (None: that launch never splits)"""
-        if self.kws is None or not self.wstreams:
-            return self.kws
-        cur = torch.cuda.current_stream(self.device)
-        for k, s in enumerate(self.wstreams):
-            if cur == s:
-                return self.kws_side[k] if k < len(self.kws_side) else None
-        return self.kws
+                    self.sched.ncu(), _ptr(kws), kws.numel() if kws is not None else 0, self._stream())
 
     def _conv_first(self, name, out, h, dil, st, in16=None, x=None):
         if x is not None:
             # colour adjust + first conv in one launch, straight from the f32 input (rsu.h rsu_color_conv_first_fwd; same bits, no dropout)
             call("rsu_color_conv_first_fwd", _ptr(x), _ptr(self.w["color_space_adjust/kernel"]), _ptr(self.w["color_space_adjust/bias"]),
-                 _ptr(self.pk[name + "/kernel", "fwd"]), _ptr(self.w[name + "/bias"]), _ptr(out), out.shape[0], h, h, self.root, dil, self._ncu, st)
+                 _ptr(self.pk[name + "/kernel", "fwd"]), _ptr(self.w[name + "/bias"]), _ptr(out), out.shape[0], h, h, self.root, dil,
+                 self.sched.ncu(), st)
             return
         call("rsu_conv_first_fwd", _ptr(self.in16 if in16 is None else in16), _ptr(self.pk[name + "/kernel", "fwd"]), _ptr(self.w[name + "/bias"]),
-             _ptr(out), out.shape[0], h, h, self.root, dil, self._ncu, st)
+             _ptr(out), out.shape[0], h, h, self.root, dil, self.sched.ncu(), st)
 
     def dropout_key(self, site):
         """32-bit key of dropout site `site` (encoder level i -> i, decoder stage i -> L + i: the 2L-1 tf.nn.dropout calls of
@@ -590,7 +461,7 @@ class UNet:
                 # the dilated twin block (unet.py:32-39) reads the level's input and feeds only a decoder skip: it runs on the second
                 # stream beside the main block (joined in front of the decoder)
                 def twin(i=i, cur=cur, h=h):
-                    with UNet._Side(self):
+                    with self.sched.side():
                         if i == 0:
                             self._conv_first("conv_dilut_0/atrous_conv1", a["d1_0"], h, 2, self._stream(), in16, xin)
                         else:
@@ -610,16 +481,16 @@ class UNet:
                     c1, c2 = a["c1_%d" % i], a["c2_%d" % i]
                     nf_ = c2.shape[3]
                     src = (RsuSrc * 1)(_src(c1, h - 2, h - 2))
-                    kws = self._kws()
+                    kws = self.sched.kws_here()
                     self._timed("conv3x3_fwd", 2.0 * nb * (h - 4) * (h - 4) * nf_ * c1.shape[3] * 9, "rsu_conv2d_fwd_pool_k", src, 1,
                                 _ptr(self.pk["conv_%d/conv2/kernel" % i, "fwd"]), _ptr(self.w["conv_%d/conv2/bias" % i]), _ptr(c2),
-                                _ptr(a["pool_%d" % i]), _ptr(code.get(i)), nb, h - 2, h - 2, nf_, keep, self.dropout_key(i + 1), self._ncu,
+                                _ptr(a["pool_%d" % i]), _ptr(code.get(i)), nb, h - 2, h - 2, nf_, keep, self.dropout_key(i + 1), self.sched.ncu(),
                                 _ptr(kws), kws.numel() if kws is not None else 0, self._stream())
                 add(conv2_pool)
                 cur, h = a["pool_%d" % i], (h - 4) // 2
         net, h = a["c2_%d" % (L - 1)], h - 4
         if self.dilated:
-            add(self._join_side)
+            add(self.sched.join)
         for i in range(L - 1):
             j, lvl = L + i, L - 2 - i
             up = a["up_%d" % i]
@@ -630,7 +501,7 @@ class UNet:
                 add(lambda net=net, drop=drop, i=i: call("rsu_dropout_fwd", _ptr(net), _ptr(drop), net.numel(), keep, self.dropout_key(L + i), self._stream()))
                 net = drop
             add(lambda net=net, up=up, i=i, h=h: call("rsu_convT2x2_fwd", _ptr(net), _ptr(self.pk["up_conv_%d/kernel" % i, "fwd"]),
-                                                     _ptr(self.w["up_conv_%d/bias" % i]), _ptr(up), nb, h, h, net.shape[3], up.shape[3], self._ncu, self._stream()))
+                                                     _ptr(self.w["up_conv_%d/bias" % i]), _ptr(up), nb, h, h, net.shape[3], up.shape[3], self.sched.ncu(), self._stream()))
             h = 2 * h
 
             def dec(j=j, lvl=lvl, up=up, h=h):
@@ -648,111 +519,80 @@ class UNet:
         return steps
 
     # ------------------------------------------------------------------ backward
-    def _wgrad(self, name, srcs_t, dz, hout, dil=1):
+    def _wgrad(self, name, srcs_t, dz, hout, dil=1, block_done=False):
         """dW (HWIO rows per source) + db of conv `name`; srcs_t = list of (tensor, window size). With grouping on (RSU_WG_GROUP) the
-        launches are only queued here; _flush_wgrads sends a whole group to the side stream as one launch."""
+        launches are only queued here; the schedule sends a whole group to the side stream as one launch. block_done: this is a
+        block's conv2 gradient, behind which a group may close (BackwardSchedule.block_done)."""
         cout = dz.shape[3]
         cin_total = self.w[name + "/kernel"].shape[2]
         off = 0
-        if self._wg_group > 0:
+        if self.sched.grouped:
             for t, win in srcs_t:
                 db = self.g[name + "/bias"] if off == 0 else None  # BiasAddGrad rides along with the first source's launch
                 job = RsuWgradJob(_lib.WGRAD_CONV3X3, _src(t, win, win), dz.data_ptr(), self.g[name + "/kernel"].data_ptr(),
                                   db.data_ptr() if db is not None else None, hout, hout, cin_total, off, cout, dil)
-                self._wg_pending.append((job, 2.0 * self.B * hout * hout * cout * t.shape[3] * 9, (name, off)))
+                self.sched.queue(job, 2.0 * self.B * hout * hout * cout * t.shape[3] * 9, (name, off))
                 off += t.shape[3]
-            # (no event per queued job: the group forks where it is flushed, through the raw event of _Side -- a torch event recorded here
-            # would cost the main queue ~5 us between two backward-data kernels)
-            if name.endswith("conv2") and not (name.startswith("conv_0/") and not self.dilated):   # (the last group: flushed by the caller, which knows that nothing runs beside it)
-                # a group closes BEHIND a conv2 gradient: dz of a block's conv2 is there when the block's backward pass begins, so the
-                # group {conv1 (+ transposed conv) of the block before, conv2 of this one} can run beside ALL of this block's
-                # backward-data launches; closing it behind conv1 would make it wait for the block's first backward-data launch
-                self._wg_levels += 1
-                if self._wg_levels >= self._wg_sizes[min(self._wg_index, len(self._wg_sizes) - 1)]:
-                    self._flush_wgrads()
+            if block_done:
+                self.sched.block_done()
             return
-        with UNet._Side(self) as side:
+        with self.sched.side() as ws:
             st = self._stream()
             for t, win in srcs_t:
                 s = _src(t, win, win)
                 db = _ptr(self.g[name + "/bias"]) if off == 0 else None  # BiasAddGrad rides along with the first source's launch
                 fl = 2.0 * self.B * hout * hout * cout * t.shape[3] * 9
                 self._timed("conv3x3_bwd_weight", fl, "rsu_conv2d_bwd_weight", ctypes.byref(s), _ptr(dz), _ptr(self.g[name + "/kernel"]), db,
-                            _ptr(side.ws), self.B, hout, hout, cin_total, off, cout, dil, self._ncu, st)
+                            _ptr(ws), self.B, hout, hout, cin_total, off, cout, dil, self.sched.ncu(), st)
                 off += t.shape[3]
 
     def _wgradT(self, i, upin, dup, hh, nf):
         """dK + db of up_conv_i (queued like _wgrad when grouping is on)"""
-        if self._wg_group > 0:
+        if self.sched.grouped:
             job = RsuWgradJob(_lib.WGRAD_CONVT2X2, RsuSrc(upin.data_ptr(), hh, hh, upin.shape[3], 0, 0), dup.data_ptr(),
                               self.g["up_conv_%d/kernel" % i].data_ptr(), self.g["up_conv_%d/bias" % i].data_ptr(), 0, 0, 0, 0, nf, 1)
-            self._wgT_pending.append((job, 0.0, ("up_conv_%d" % i, upin.data_ptr())))
+            self.sched.queue(job, 0.0, ("up_conv_%d" % i, upin.data_ptr()), transposed=True)
             return
-        with UNet._Side(self) as side:
+        with self.sched.side() as ws:
             call("rsu_convT2x2_bwd_weight", _ptr(upin), _ptr(dup), _ptr(self.g["up_conv_%d/kernel" % i]), _ptr(self.g["up_conv_%d/bias" % i]),
-                 _ptr(side.ws), self.B, hh, hh, upin.shape[3], nf, self._ncu, self._stream())
+                 _ptr(ws), self.B, hh, hh, upin.shape[3], nf, self.sched.ncu(), self._stream())
 
-    def _flush_wgrads(self, alone=False):
-        """Launch the queued weight gradients as grouped launches on the side stream (everything they read has been produced by launches
-        issued on the main stream before this point; _Side makes the side stream wait for them). The plan of a group -- which layers,
-        which CU share, which workspace -- is made once and kept (host table + its device copy, rsu.h rsu_wgrad_group_plan)."""
-        if not self._wg_pending and not self._wgT_pending:
-            return   # (the data-parallel host asks per bucket boundary: an empty flush must not advance the group schedule)
-        self._wg_levels = 0
-        self._wg_index += 1
-        for pending, tag in ((self._wg_pending, "conv3x3_bwd_weight"), (self._wgT_pending, None)):
-            while pending:
-                chunk, rest = pending[:_lib.WGRAD_GROUP_MAX], pending[_lib.WGRAD_GROUP_MAX:]
-                del pending[:]
-                pending.extend(rest)
-                with UNet._Side(self, alone=alone) as side:
-                    key = (tuple(k for _, _, k in chunk), self._ncu, side.ws.data_ptr())
-                    plan = self._wg_plans.get(key)
-                    if plan is None:
-                        lib = _lib.lib()
-                        nb = lib.rsu_wgrad_group_table_bytes()
-                        host = ctypes.create_string_buffer(nb)
-                        arr = (RsuWgradJob * len(chunk))(*[j for j, _, _ in chunk])
-                        _lib.check(lib.rsu_wgrad_group_plan(arr, len(chunk), _ptr(side.ws), self.B, self._ncu, host), "rsu_wgrad_group_plan")
-                        devt = torch.frombuffer(bytearray(host.raw), dtype=torch.uint8).to(self.device)
-                        plan = self._wg_plans[key] = (host, devt)
-                    flops = sum(f for _, f, _ in chunk)
-                    if tag is None:
-                        call("rsu_wgrad_group_run", plan[0], _ptr(plan[1]), self._stream())
-                    else:
-                        self._timed(tag, flops, "rsu_wgrad_group_run", plan[0], _ptr(plan[1]), self._stream())
+    def _wgrad_first(self, name, dz, h, dil, where):
+        """dW + db + gx (gfirst[0]; the dilated twin, dil 2: gfirst[1]) of a level-0 first conv: a launch of its own inside `where`,
+        the schedule's context that gives it a stream, a CU share and a workspace"""
+        with where as ws:
+            call("rsu_conv_first_bwd_weight", _ptr(self.in16), _ptr(dz), _ptr(self.g[name + "/kernel"]), _ptr(self.gfirst[dil - 1]),
+                 _ptr(self.g[name + "/bias"]), _ptr(ws), self.B, h, h, self.root, dil, self.sched.ncu(), self._stream())
 
     def _bwd_data(self, name, dz, dx, hin, relu_src=None, accumulate=0, src_index=0, dil=1):
         """Conv2DBackpropInput towards concat source `src_index` of conv `name` (its own weight pack)"""
         cout = self.w[name + "/kernel"].shape[3]
         cnt = dx.shape[3]
         ho = hin - 2 * dil
-        kws = self._kws()
+        kws = self.sched.kws_here()
         self._timed("conv3x3_bwd_data", 2.0 * self.B * ho * ho * cout * cnt * 9, "rsu_conv2d_bwd_data_k", _ptr(dz),
                     _ptr(self.pk[name + "/kernel", "bwd", src_index]), _ptr(dx), _ptr(relu_src), accumulate, self.B, hin, hin, cnt, 0, cnt,
-                    cout, dil, self._ncu, _ptr(kws), kws.numel() if kws is not None else 0, self._stream())
+                    cout, dil, self.sched.ncu(), _ptr(kws), kws.numel() if kws is not None else 0, self._stream())
 
     def backward_device(self, inv_count, update=None):
         """loss + all gradients for self.x / self.labels; forward_device() must have run. inv_count = 1 / (global pixel count).
         update = (lr0, momentum): accepted from callers that name the Momentum step they will take; it changes nothing here -- the step
         is apply_momentum's -- but a net built with another optimizer refuses it."""
-        B, L, st, a, g = self.B, self.L, self._stream(), self.act, self.grad
-        keep = self.keep
-        last = a[self.last_name]
         if update is not None and self.optimizer != "momentum":
             raise _lib.RsuError("backward_device(update=...) is the Momentum step; an %s net steps with apply_%s after the pass"
                                 % (self.optimizer, self.optimizer))
-        self._begin_split()
+        st = self._stream()
+        self.sched.begin(self.backward_cu_budget)
         try:
             self._backward_body(inv_count)
         finally:
-            self._end_split()   # (an exception inside must not leave later launches planned for a share of the chip)
+            self.sched.end()   # (an exception inside must not leave later launches planned for a share of the chip)
         # ---- color_space_adjust (unet.py:22-23): its input gradient is never materialised (include/rsu.h, rsu_conv_first_bwd_weight):
         #   dW0[ci][cj] = 1/keep * sum_{t,co} W1[t][cj][co] * gxc[t][ci][cj][co];  db0[cj] = 1/keep * sum_{t,co} W1[t][cj][co] * gm[t][cj][co]
-        inv_keep = float(np.float32(1.0) / np.float32(keep))
+        inv_keep = float(np.float32(1.0) / np.float32(self.keep))
         gk, gb = self.g["color_space_adjust/kernel"], self.g["color_space_adjust/bias"]
         call("rsu_color_adjust_bwd", _ptr(self.gfirst[0]), _ptr(self.w["conv_0/conv1/kernel"]), _ptr(gk), _ptr(gb), self.root, inv_keep, 0, st)
-        if self.dilated and L > 1:
+        if self.dilated and self.L > 1:
             call("rsu_color_adjust_bwd", _ptr(self.gfirst[1]), _ptr(self.w["conv_dilut_0/atrous_conv1/kernel"]), _ptr(gk), _ptr(gb), self.root,
                  inv_keep, 1, st)
 
@@ -771,7 +611,7 @@ class UNet:
             h = up.shape[1]
             nf = c2.shape[3]
             dz2, dz1 = g["c2_%d" % j], g["c1_%d" % j]
-            self._wgrad("conv_%d/conv2" % j, [(c1, h - 2)], dz2, h - 4)
+            self._wgrad("conv_%d/conv2" % j, [(c1, h - 2)], dz2, h - 4, block_done=True)
             self._bwd_data("conv_%d/conv2" % j, dz2, dz1, h - 2, relu_src=c1)
             srcs = [(a["c2_%d" % lvl], h)] + ([(a["d2_%d" % lvl], h)] if self.dilated else []) + [(up, h)]
             self._wgrad("conv_%d/conv1" % j, srcs, dz1, h - 2)
@@ -788,7 +628,7 @@ class UNet:
             hh = h // 2
             self._wgradT(i, upin, dup, hh, nf)
             call("rsu_convT2x2_bwd_data", _ptr(dup), _ptr(self.pk["up_conv_%d/kernel" % i, "bwd"]), _ptr(gin), _ptr(upin), float(np.float32(1.0) / np.float32(keep)), B, hh, hh,
-                 upin.shape[3], nf, self._ncu, st)
+                 upin.shape[3], nf, self.sched.ncu(), st)
             self._grads_ready("up_conv_%d/kernel" % i)  # up_conv_i, conv_{L+i} and everything created later are final
         # ---- encoder, level L-1 .. 0
         for i in reversed(range(L)):
@@ -801,7 +641,8 @@ class UNet:
                 hs = a["up_%d" % dec].shape[1]
                 call("rsu_pool_skip_relu_bwd_code", _ptr(c2), _ptr(self.pool_code.get(i)), _ptr(g["pool_%d" % i]), _ptr(g["skip_%d" % dec]), _ptr(dz2), B, h - 4, h - 4, nf, hs, hs,
                      keep, self.dropout_key(i + 1), st)
-            self._wgrad("conv_%d/conv2" % i, [(c1, h - 2)], dz2, h - 4)
+            # (level 0 of a net without dilated twins: its conv2 gradient joins the pass's last group, flushed below)
+            self._wgrad("conv_%d/conv2" % i, [(c1, h - 2)], dz2, h - 4, block_done=i > 0 or self.dilated)
             self._bwd_data("conv_%d/conv2" % i, dz2, dz1, h - 2, relu_src=c1)
             if i > 0:
                 pin = a["pool_%d" % (i - 1)]
@@ -810,42 +651,30 @@ class UNet:
             else:
                 # the last group: nothing is left to run beside it on the main stream (unless the dilated twin of level 0 follows), so
                 # it plans for the whole chip; the level-0 conv1 gradient below is a launch of its own
-                self._flush_wgrads(alone=not (self.dilated and L > 1))
-                if self.wstreams and self._split is not None and not (self.dilated and L > 1) and os.environ.get("RSU_TAIL_MAIN", "1") != "0":
-                    # the pass's last launch needs the backward-data kernel that has just gone out on THIS stream and nothing runs beside
-                    # it: on the main stream it follows back to back -- on the side stream it cost a fork and a join (~24 us of latency in
-                    # the timeline). The side stream's last reduction must be done before the workspace is re-used: joined first.
-                    self._join_side()
-                    call("rsu_conv_first_bwd_weight", _ptr(self.in16), _ptr(dz1), _ptr(self.g["conv_0/conv1/kernel"]), _ptr(self.gfirst[0]),
-                         _ptr(self.g["conv_0/conv1/bias"]), _ptr(self.ws_side[0]), B, h, h, nf, 1, self._split[0], st)
-                else:
-                    with UNet._Side(self, alone=not (self.dilated and L > 1)) as side:
-                        call("rsu_conv_first_bwd_weight", _ptr(self.in16), _ptr(dz1), _ptr(self.g["conv_0/conv1/kernel"]), _ptr(self.gfirst[0]),
-                             _ptr(self.g["conv_0/conv1/bias"]), _ptr(side.ws), B, h, h, nf, 1, self._ncu, self._stream())
+                alone = not (self.dilated and L > 1)
+                self.sched.flush(alone=alone)
+                self._wgrad_first("conv_0/conv1", dz1, h, 1, self.sched.tail(alone))
             if self.dilated and i < L - 1:
                 d1, d2 = a["d1_%d" % i], a["d2_%d" % i]
                 dzd2, dzd1 = g["d2_%d" % i], g["d1_%d" % i]
                 dec = L - 2 - i
                 hs = a["up_%d" % dec].shape[1]
                 call("rsu_pool_skip_relu_bwd", _ptr(d2), None, _ptr(g["skipd_%d" % dec]), _ptr(dzd2), B, h - 8, h - 8, nf, hs, hs, 1.0, 0, st)
-                self._wgrad("conv_dilut_%d/atrous_conv2" % i, [(d1, h - 4)], dzd2, h - 8, dil=2)
+                self._wgrad("conv_dilut_%d/atrous_conv2" % i, [(d1, h - 4)], dzd2, h - 8, dil=2, block_done=True)
                 self._bwd_data("conv_dilut_%d/atrous_conv2" % i, dzd2, dzd1, h - 4, relu_src=d1, dil=2)
                 if i > 0:
                     pin = a["pool_%d" % (i - 1)]
                     self._wgrad("conv_dilut_%d/atrous_conv1" % i, [(pin, h)], dzd1, h - 4, dil=2)
                     self._bwd_data("conv_dilut_%d/atrous_conv1" % i, dzd1, g["pool_%d" % (i - 1)], h, accumulate=1, dil=2)
                 else:
-                    with UNet._Side(self, alone=True) as side:
-                        call("rsu_conv_first_bwd_weight", _ptr(self.in16), _ptr(dzd1), _ptr(self.g["conv_dilut_0/atrous_conv1/kernel"]),
-                             _ptr(self.gfirst[1]), _ptr(self.g["conv_dilut_0/atrous_conv1/bias"]), _ptr(side.ws), B, h, h, nf, 2, self._ncu,
-                             self._stream())
+                    self._wgrad_first("conv_dilut_0/atrous_conv1", dzd1, h, 2, self.sched.side(alone=True))
             if i > 0:
                 # first LIVE variable of the level in creation order: the dilated pair of level L-1 is dead and sits behind n_live
                 # (marking it ready launched nothing, and the largest block waited for level L-2)
                 first_name = ("conv_dilut_%d/atrous_conv1/kernel" if (self.dilated and i < L - 1) else "conv_%d/conv1/kernel") % i
                 self._grads_ready(first_name)
-        self._flush_wgrads(alone=True)
-        self._join_side()
+        self.sched.flush(alone=True)
+        self.sched.join()
 
     def tune(self, training=None, keep=1.0):
         """The explicit tile-shape tuning pass (rsu.h rsu_set_autotune): ONE untimed forward (+ backward) over random data with the
@@ -902,18 +731,14 @@ class UNet:
         if not hasattr(self, "pk"):
             self.repack()
         adam = self.optimizer == "adam"
-        entries, plain_lo = [], None   # ("plain", lo, hi) / ("tensor", name, kind)
-        live = sorted(((o, c, n, sh) for n, (o, c, sh) in self._slices.items() if o < self.n_live), key=lambda t: t[0])
-        for o, c, n, sh in live:
-            packed = n.endswith("kernel") and (n.startswith("up_conv") or (len(sh) == 4 and sh[0] == 3))
-            if not packed:
-                plain_lo = o if plain_lo is None else plain_lo
-                continue
-            if plain_lo is not None:
+        entries, plain_lo = [], 0   # ("plain", lo, hi) / ("tensor", name, (kind, shape, segments))
+        for kind, n, sh, segs in self._packed_kernels():
+            o, c, _ = self._slices[n]
+            if plain_lo < o:
                 entries.append(("plain", plain_lo, o))
-                plain_lo = None
-            entries.append(("tensor", n, sh))
-        if plain_lo is not None:
+            entries.append(("tensor", n, (kind, sh, segs)))
+            plain_lo = (o + c + 3) // 4 * 4   # (the 16-byte aligned start of the next variable)
+        if plain_lo < self.n_live:
             entries.append(("plain", plain_lo, self.n_live))
         esz = lib.rsu_update_table_entry_bytes()
         host = ctypes.create_string_buffer(esz * len(entries))
@@ -924,19 +749,18 @@ class UNet:
                 rc = lib.rsu_update_table_add_plain(host, idx, _ptr(self.flat_w[lo:hi]), _ptr(self.flat_acc[lo:hi]), _ptr(self.flat_g[lo:hi]), hi - lo)
                 v = self.flat_v[lo:hi] if adam else None
             else:
-                n, sh = e[1], e[2]
+                n, (kind, sh, segs) = e[1], e[2]
                 w, a, g = _ptr(self.w[n]), _ptr(self.acc[n]), _ptr(self.g[n])
                 bw = None
-                if n.startswith("up_conv"):
+                if kind == _PACK_CONVT_FWD:
                     cout, cin = sh[2], sh[3]
                     bw = (ctypes.c_void_p * 1)(self.pk[n, "bwd"].data_ptr()) if self.training else None
-                    rc = lib.rsu_update_table_add(host, idx, 2, w, a, g, _ptr(self.pk[n, "fwd"]), bw, cin, cout, None, 0)
-                elif sh[2] == NUM_CHANNELS:
-                    rc = lib.rsu_update_table_add(host, idx, 4, w, a, g, _ptr(self.pk[n, "fwd"]), None, 3, sh[3], None, 0)
+                    rc = lib.rsu_update_table_add(host, idx, kind, w, a, g, _ptr(self.pk[n, "fwd"]), bw, cin, cout, None, 0)
+                elif kind == _PACK_CONV_FIRST:
+                    rc = lib.rsu_update_table_add(host, idx, kind, w, a, g, _ptr(self.pk[n, "fwd"]), None, 3, sh[3], None, 0)
                 else:
-                    segs = self._conv_sources_c(n, sh)
                     bw = (ctypes.c_void_p * len(segs))(*[self.pk[n, "bwd", si].data_ptr() for si in range(len(segs))]) if self.training else None
-                    rc = lib.rsu_update_table_add(host, idx, 0, w, a, g, _ptr(self.pk[n, "fwd"]), bw, sh[2], sh[3], (ctypes.c_int * len(segs))(*segs), len(segs))
+                    rc = lib.rsu_update_table_add(host, idx, kind, w, a, g, _ptr(self.pk[n, "fwd"]), bw, sh[2], sh[3], (ctypes.c_int * len(segs))(*segs), len(segs))
                 keep.append(bw)
                 v = self.v[n] if adam else None
             if rc != 1:
