@@ -171,6 +171,22 @@ size_t rsu_head_ws_floats(long npix, int C);
 int rsu_head_fwd_bwd(const void* act, const float* w, const float* b, const int64_t* labels, float* prob,
                      float* loss_sum, void* dact, float* dw, float* db, float* ws, long npix, int C,
                      float inv_count, rsu_stream_t stream);
+/* The weighted form of tf_aerial_images.py:103-110: tf.losses.sparse_softmax_cross_entropy(labels, logits, weights) with
+ * reduction SUM_OVER_BATCH_SIZE, the U-Net paper's weight-map loss. Per pixel p with label l_p and CE_p = -log softmax(z_p)[l_p]:
+ *   omega_p = 0 if l_p is neither 0 nor 1 (an IGNORED pixel; the test is made on all 64 bits of the label),
+ *           = class_w[l_p] * pixel_w[p] otherwise   (class_w: device f32[2] or NULL = {1, 1}; pixel_w: device f32[npix] or NULL = 1)
+ *   loss_sum += sum_p omega_p CE_p;  weight_sum (f32[1] or NULL) += sum_p omega_p;  dlogits_p = omega_p (softmax(z_p) - onehot(l_p)) inv_count
+ * inv_count stays 1 / (global pixel count): NOT 1 / sum omega (no second pass, no device-side scalar in front of the gradient, and the
+ * SUM all-reduce of per-rank gradients stays correct); weight_sum lets a host REPORT loss_sum / weight_sum. The caller zeroes loss_sum
+ * and weight_sum. prob is written for every pixel; an ignored pixel's dact row is +0 and it adds nothing to dw, db, loss_sum,
+ * weight_sum, whatever its pixel_w holds (it is never multiplied). dact, dw, db, prob, inv_count, C and the error codes are
+ * rsu_head_fwd_bwd's. Same grid, pixel-to-thread mapping and fixed summation orders: results are deterministic, and with every
+ * omega_p == 1 (class_w {1, 1} or NULL, pixel_w all ones or NULL, labels in {0,1}) they equal rsu_head_fwd_bwd's bit for bit.
+ * ws: rsu_head_w_ws_floats(npix, C) floats (one more partial per workgroup than rsu_head_ws_floats). */
+size_t rsu_head_w_ws_floats(long npix, int C);
+int rsu_head_fwd_bwd_w(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w,
+                       const float* pixel_w, float* prob, float* loss_sum, float* weight_sum, void* dact, float* dw, float* db,
+                       float* ws, long npix, int C, float inv_count, rsu_stream_t stream);
 
 /* ---- 3x3 convolution, MFMA implicit GEMM -------------------------------------------------- */
 /* unet.py:34-39,42-45,88-91: y = relu(conv3x3_valid(concat(srcs), W, dilation) + b).

@@ -35,7 +35,7 @@ def main(argv=None):
     import torch
     import torch.distributed as dist
     from . import hostio
-    from .model import ConvolutionalModel
+    from .model import ConvolutionalModel, balanced_class_weights
     from .pool import DevicePatchPool
     from .unet import input_size_needed
     opts = parse_options(argv)
@@ -43,6 +43,16 @@ def main(argv=None):
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
         dist.init_process_group("nccl")
     rank = dist.get_rank() if dist.is_initialized() else 0
+    train_data = None
+    if opts.class_weights == "balanced":
+        # the model takes its class weights at construction: this case alone loads the training set in front of it. Without a
+        # training epoch the loss is never evaluated and the flag has no effect
+        if opts.num_epoch > 0:
+            train_data = hostio.load_train_data(opts.train_data_dir)
+            opts.class_weights = balanced_class_weights(train_data[1])
+            print("Balanced class weights: background {:.4f}, road {:.4f}".format(*opts.class_weights))
+        else:
+            opts.class_weights = None
     model = ConvolutionalModel(opts)
     print("Running on device {}".format(model.net.device))
 
@@ -55,7 +65,7 @@ def main(argv=None):
             model.restore(date=opts.restore_date, epoch=opts.restore_epoch)
 
     if opts.num_epoch > 0:
-        train_images, train_groundtruth = hostio.load_train_data(opts.train_data_dir)
+        train_images, train_groundtruth = train_data if train_data is not None else hostio.load_train_data(opts.train_data_dir)
         input_size = input_size_needed(opts.patch_size, opts.num_layers)
         offset = int((input_size - opts.patch_size) / 2)
         extended = hostio.expand_and_rotate(train_images, opts.rotation_angles, offset)

@@ -34,6 +34,9 @@ hipError_t ew_reduce_slabs_many(const ReduceJob* jobs_dev, int njobs, int total_
 int ew_head_blocks(long npix, int C);
 hipError_t ew_head(bool train, const void* act, const float* w, const float* b, const int64_t* labels, float* prob, float* logits, void* dact, float* dw,
                    float* db, float* loss_sum, float* ws, long npix, int C, float inv_count, hipStream_t st);
+// the weighted training head (rsu.h rsu_head_fwd_bwd_w): same grid, ws of ew_head_blocks() * (2 C + 4) floats
+hipError_t ew_head_w(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w, const float* pixel_w, float* prob,
+                     void* dact, float* dw, float* db, float* loss_sum, float* weight_sum, float* ws, long npix, int C, float inv_count, hipStream_t st);
 hipError_t ew_color_adjust_bwd(const float* gx, const float* w1, float* dW0, float* db0, int Cout, float scale, int accumulate, hipStream_t st);
 hipError_t ew_momentum(float* w, float* acc, const float* g, float lr, float mu, float gscale, long n, hipStream_t st);
 // the update rules of the optimizer passes (template argument of k_update_pack_many): their scalars, passed by value to the kernels.

@@ -1412,6 +1412,15 @@ extern "C" int rsu_head_fwd_bwd(const void* act, const float* w, const float* b,
     HIP_CHECK_RET(ew_head(true, act, w, b, labels, prob, nullptr, dact, dw, db, loss_sum, ws, npix, C, inv_count, (hipStream_t)stream));
     return RSU_OK;
 }
+extern "C" size_t rsu_head_w_ws_floats(long npix, int C) { return (size_t)ew_head_blocks(npix, C) * (2 * C + 4); }
+extern "C" int rsu_head_fwd_bwd_w(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w,
+                                  const float* pixel_w, float* prob, float* loss_sum, float* weight_sum, void* dact, float* dw, float* db,
+                                  float* ws, long npix, int C, float inv_count, rsu_stream_t stream) {
+    if (!act || !w || !b || !labels || !prob || !loss_sum || !dact || !dw || !db || !ws || !head_c_ok(C) || npix < 1) return RSU_EINVAL;
+    HIP_CHECK_RET(ew_head_w(act, w, b, labels, class_w, pixel_w, prob, dact, dw, db, loss_sum, weight_sum, ws, npix, C, inv_count,
+                            (hipStream_t)stream));
+    return RSU_OK;
+}
 extern "C" int rsu_momentum_step(float* w, float* acc, const float* g, float lr, float mu, float gscale, long n, rsu_stream_t stream) {
     if (!w || !acc || !g || n < 1) return RSU_EINVAL;
     if (((uintptr_t)w | (uintptr_t)acc | (uintptr_t)g) & 15) return RSU_EINVAL;

@@ -67,7 +67,45 @@ EXTRA_FLAG_DEFS = [
     ("adam_beta1", float, 0.9, "Adam: decay rate of the first-moment estimates"),
     ("adam_beta2", float, 0.999, "Adam: decay rate of the second-moment estimates"),
     ("adam_epsilon", float, 1e-8, "Adam: epsilon added to sqrt(v)"),
+    ("class_weights", str, None, "Loss weights of the classes background,road: 'w0,w1' (two finite floats >= 0, not both 0) or 'balanced' "
+                                 "(N / (2 N_c) from the training ground truth: mean weight 1, so --lr keeps its scale); default: the "
+                                 "reference's unweighted loss. The loss stays normalised by the pixel count, not by the sum of the weights"),
 ]
+
+
+def parse_class_weights(value):
+    """The --class_weights value: None -> None; "balanced" -> "balanced" (resolved from the training ground truth by the caller:
+    balanced_class_weights); "w0,w1" or a pair of numbers -> (w0, w1) as floats. Anything else raises ValueError."""
+    if value is None:
+        return None
+    if isinstance(value, str):
+        if value.strip() == "balanced":
+            return "balanced"
+        parts = value.split(",")
+    else:
+        try:
+            parts = list(value)
+        except TypeError:
+            parts = [value]
+    try:
+        cw = tuple(float(v) for v in parts)
+    except (TypeError, ValueError):
+        cw = ()
+    if len(cw) != 2 or not all(math.isfinite(v) and v >= 0.0 for v in cw) or cw == (0.0, 0.0):
+        raise ValueError("--class_weights must be 'w0,w1' (two finite floats >= 0, not both 0) or 'balanced', not %r" % (value,))
+    return cw
+
+
+def balanced_class_weights(groundtruth):
+    """(N / (2 N_0), N / (2 N_1)) over the labels of `groundtruth` binarised at 0.5 (tf_aerial_images.py:220), scikit-learn's "balanced"
+    rule: each class carries half of the total weight and the mean weight over the data is 1, so the loss scale and a tuned --lr
+    stay comparable with the unweighted loss. A class without pixels raises ValueError."""
+    road = np.asarray(groundtruth) >= 0.5
+    n, n1 = int(road.size), int(road.sum())
+    n0 = n - n1
+    if n0 == 0 or n1 == 0:
+        raise ValueError("balanced class weights need both classes in the ground truth (background %d, road %d pixels)" % (n0, n1))
+    return n / (2.0 * n0), n / (2.0 * n1)
 
 
 class Options(object):
@@ -83,6 +121,7 @@ class Options(object):
             setattr(self, k, v)
         if self.optimizer not in ("momentum", "adam"):
             raise ValueError("--optimizer must be momentum or adam, not %r" % (self.optimizer,))
+        self.class_weights = parse_class_weights(self.class_weights)   # None, (w0, w1) or "balanced" (cli.main resolves it)
         ra = self.rotation_angles
         if isinstance(ra, str):
             self.rotation_angles = None if not ra else [int(i) for i in ra.split(",")]
@@ -115,8 +154,11 @@ class ConvolutionalModel:
         if torch.device(device).type == "cuda":
             torch.cuda.set_device(torch.device(device))  # the library works on the HIP current device (rsu.h "devices")
         # the reference's graph is static in (batch, patch): one UNet serves training and (zero-padded) prediction batches
+        if opts.class_weights == "balanced":
+            raise ValueError("class_weights='balanced' must be resolved from the training ground truth before the model is built: "
+                             "options.class_weights = balanced_class_weights(groundtruth) (cli.main does)")
         self.net = UNet(opts.num_layers, opts.root_size, opts.dilated_layers, self.local_batch, opts.patch_size, device=device,
-                        params=params, seed=opts.seed, training=True, optimizer=opts.optimizer)
+                        params=params, seed=opts.seed, training=True, optimizer=opts.optimizer, class_weights=opts.class_weights)
         self.net.dropout_seed = int(opts.seed) + 7919 * self.rank  # independent masks on every rank's shard
         self._bucketer = None
         self._exchange_tuned = False
@@ -135,13 +177,17 @@ class ConvolutionalModel:
             self.net.repack()
 
     # ------------------------------------------------------------------ training
-    def train_step(self, patches, labels):
+    def train_step(self, patches, labels, weights=None):
         """One session.run([train, loss, predictions]) (tf_aerial_images.py:241-244) on this rank's shard.
         patches [b,S,S,3] float, labels [b,P,P] in {0,1}; returns (global mean loss tensor, predictions [b,P,P] device tensor).
+        weights: an optional per-pixel weight map [b,P,P] for this step's loss (UNet.set_pixel_weights; it multiplies the model's
+        class weights); None: no map, also after a step that had one. With class weights or a map the loss is the weighted sum over the
+        GLOBAL pixel count (UNet.backward_device), and a label other than 0 and 1 then ignores its pixel: no loss, no gradient.
         (Synchronous upload: the train() loop stages its batches one step ahead instead, see pool.BatchUploader.)"""
         net = self.net
         net.x.copy_(torch.as_tensor(np.asarray(patches, dtype=np.float32)).to(net.device))
         net.labels.copy_(torch.as_tensor(np.asarray(labels)).to(net.device, torch.int64))
+        net.set_pixel_weights(None if weights is None else torch.as_tensor(np.asarray(weights, dtype=np.float32)))
         return self._run_step()
 
     def _run_step(self):

@@ -107,9 +107,11 @@ class UNet:
     static in exactly the same way (tf_aerial_images.py:133-138)."""
 
     def __init__(self, num_layers, root_size, dilated_layers, batch_size, patch_size, device="cuda:0", params=None, seed=2017,
-                 training=True, optimizer="momentum"):
+                 training=True, optimizer="momentum", class_weights=None):
         """optimizer: "momentum" (the reference's MomentumOptimizer: apply_momentum) or "adam" (tf.train.AdamOptimizer: apply_adam; a
-        second fp32 slot per variable, flat_v)"""
+        second fp32 slot per variable, flat_v).
+        class_weights: None or a pair (w0, w1) of finite floats >= 0, not both 0: the weighted cross-entropy of rsu.h
+        rsu_head_fwd_bwd_w (see backward_device). None and (1, 1) are the reference's unweighted loss."""
         if optimizer not in OPTIMIZERS:
             raise _lib.RsuError("optimizer must be one of %s, not %r" % ("|".join(OPTIMIZERS), optimizer))
         self.optimizer = optimizer
@@ -121,6 +123,8 @@ class UNet:
         if self.device.type == "cuda":
             torch.cuda.set_device(self.device)  # the library works on the HIP current device (rsu.h "devices")
         self.training = training
+        self.class_weights = class_weights   # (a property: validated, mirrored to the device as f32[2])
+        self.pixel_weights = None            # the weight map [B, P, P] float32 on the device, or None (set_pixel_weights)
         self.keep = 1.0        # dropout keep probability of the forward pass in flight (set by forward_device)
         self.dropout_seed = int(seed) if seed is not None else 0
         self.backward_cu_budget = None   # CUs the backward launches may plan for in total (None: the library's default)
@@ -137,6 +141,41 @@ class UNet:
         self._alloc_params(params if params is not None else glorot_uniform_params(num_layers, root_size, dilated_layers, seed))
         self._alloc_buffers()
         self.repack()
+
+    @property
+    def class_weights(self):
+        """None or the pair (w0, w1) that scales the loss of the pixels labelled 0 / 1 (backward_device)"""
+        return self._class_weights
+
+    @class_weights.setter
+    def class_weights(self, cw):
+        if cw is not None:
+            cw = tuple(float(v) for v in cw)
+            if len(cw) != 2 or not all(math.isfinite(v) and v >= 0.0 for v in cw) or cw == (0.0, 0.0):
+                raise _lib.RsuError("class_weights must be None or two finite floats >= 0, not both 0; got %r" % (cw,))
+        self._class_weights = cw
+        self._class_w_dev = torch.tensor(cw, dtype=torch.float32, device=self.device) if cw is not None else None
+
+    def set_pixel_weights(self, t):
+        """The per-pixel weight map of the loss (backward_device): `t` [B, P, P] (tensor or array, any float type) is copied into the
+        device tensor `pixel_weights` (float32, allocated on first use; later calls reuse it, so a captured or queued step keeps reading
+        the same memory); None removes the map. Training nets only."""
+        if t is None:
+            self.pixel_weights = None
+            return
+        if not self.training:
+            raise _lib.RsuError("a forward-only net has no loss to weight")
+        if self.__dict__.get("_pixel_w_buf") is None:
+            self._pixel_w_buf = torch.ones((self.B, self.P, self.P), dtype=torch.float32, device=self.device)
+        src = torch.as_tensor(t)
+        if tuple(src.shape) != tuple(self._pixel_w_buf.shape):
+            raise _lib.RsuError("pixel weights must have shape %s, not %s" % (tuple(self._pixel_w_buf.shape), tuple(src.shape)))
+        self._pixel_w_buf.copy_(src)
+        self.pixel_weights = self._pixel_w_buf
+
+    def loss_is_weighted(self):
+        """whether the next backward pass takes the weighted head (rsu_head_fwd_bwd_w): class weights other than (1, 1), or a weight map"""
+        return (self._class_weights is not None and self._class_weights != (1.0, 1.0)) or self.pixel_weights is not None
 
     @property
     def wstreams(self):
@@ -271,7 +310,10 @@ class UNet:
         self.prob = torch.zeros((B, self.P, self.P), dtype=torch.float32, device=dev)
         self.logits = torch.zeros((B, self.P, self.P, 2), dtype=torch.float32, device=dev)
         self.labels = torch.zeros((B, self.P, self.P), dtype=torch.int64, device=dev)
-        self.loss_sum = torch.zeros(1, dtype=torch.float32, device=dev)
+        # loss_sum and, next to it, weight_sum (the sum of the pixels' loss weights; written by the weighted head only): one buffer, zeroed
+        # by one launch in front of the head
+        self._loss_acc = torch.zeros(2, dtype=torch.float32, device=dev)
+        self.loss_sum, self.weight_sum = self._loss_acc[0:1], self._loss_acc[1:2]
         # workspace of the conv launches that cut their reduction into slices (rsu.h rsu_conv2d_fwd_k: the deep levels at small batches);
         # one per stream that issues conv launches -- the main stream, and the side stream of the dilated twin blocks in the forward pass
         nk = int(_lib.lib().rsu_conv_splitk_ws_floats()) if os.environ.get("RSU_KSPLIT", "1") != "0" else 0
@@ -289,7 +331,8 @@ class UNet:
                 if self.dilated:
                     self.grad["skipd_%d" % i] = torch.zeros_like(up)
             lib = _lib.lib()
-            ws = [lib.rsu_head_ws_floats(B * self.P * self.P, self.root), lib.rsu_conv_first_bwd_ws_floats(self.root)]
+            ws = [lib.rsu_head_ws_floats(B * self.P * self.P, self.root), lib.rsu_head_w_ws_floats(B * self.P * self.P, self.root),
+                  lib.rsu_conv_first_bwd_ws_floats(self.root)]
             for kind, n, s, segs in self._packed_kernels():   # (the dead level L-1 dilated pair has the shapes of the level's live block)
                 if kind == _PACK_CONV_FWD:
                     for c in segs:
@@ -576,6 +619,12 @@ class UNet:
 
     def backward_device(self, inv_count, update=None):
         """loss + all gradients for self.x / self.labels; forward_device() must have run. inv_count = 1 / (global pixel count).
+        The loss is the reference's mean softmax cross-entropy unless class weights other than (1, 1) or a weight map are set
+        (class_weights, set_pixel_weights): then pixel p counts omega_p = class_weights[label_p] * pixel_weights[p] times in loss_sum and
+        in the gradients, weight_sum receives sum omega, and inv_count STAYS 1 / pixel count (rsu.h rsu_head_fwd_bwd_w;
+        loss_sum / weight_sum is the weighted mean, for reporting). A label in self.labels other than 0 and 1 IGNORES its pixel in that
+        weighted pass: no loss, no gradient, no weight (prob is still written). The unweighted pass expects labels in {0, 1}; to ignore
+        pixels without weighting the others, set a map of ones. After an unweighted pass weight_sum is 0.
         update = (lr0, momentum): accepted from callers that name the Momentum step they will take; it changes nothing here -- the step
         is apply_momentum's -- but a net built with another optimizer refuses it."""
         if update is not None and self.optimizer != "momentum":
@@ -600,10 +649,16 @@ class UNet:
         B, L, st, a, g = self.B, self.L, self._stream(), self.act, self.grad
         keep = self.keep
         last = a[self.last_name]
-        self.loss_sum.zero_()
-        call("rsu_head_fwd_bwd", _ptr(last), _ptr(self.w["weight_output/kernel"]), _ptr(self.w["weight_output/bias"]), _ptr(self.labels),
-             _ptr(self.prob), _ptr(self.loss_sum), _ptr(g[self.last_name]), _ptr(self.g["weight_output/kernel"]),
-             _ptr(self.g["weight_output/bias"]), _ptr(self.ws), B * self.P * self.P, self.root, inv_count, st)
+        self._loss_acc.zero_()
+        if self.loss_is_weighted():
+            call("rsu_head_fwd_bwd_w", _ptr(last), _ptr(self.w["weight_output/kernel"]), _ptr(self.w["weight_output/bias"]), _ptr(self.labels),
+                 _ptr(self._class_w_dev), _ptr(self.pixel_weights), _ptr(self.prob),
+                 _ptr(self.loss_sum), _ptr(self.weight_sum), _ptr(g[self.last_name]), _ptr(self.g["weight_output/kernel"]),
+                 _ptr(self.g["weight_output/bias"]), _ptr(self.ws), B * self.P * self.P, self.root, inv_count, st)
+        else:
+            call("rsu_head_fwd_bwd", _ptr(last), _ptr(self.w["weight_output/kernel"]), _ptr(self.w["weight_output/bias"]), _ptr(self.labels),
+                 _ptr(self.prob), _ptr(self.loss_sum), _ptr(g[self.last_name]), _ptr(self.g["weight_output/kernel"]),
+                 _ptr(self.g["weight_output/bias"]), _ptr(self.ws), B * self.P * self.P, self.root, inv_count, st)
         # ---- decoder, stage L-2 .. 0
         for i in reversed(range(L - 1)):
             j, lvl = L + i, L - 2 - i
@@ -680,7 +735,8 @@ class UNet:
         """The explicit tile-shape tuning pass (rsu.h rsu_set_autotune): ONE untimed forward (+ backward) over random data with the
         library in RSU_TUNE_MEASURE mode -- every conv geometry of this network at the CU shares its launches use is timed once on an
         idle device -- then back to RSU_TUNE_LOOKUP, in which the launch entry points never measure nor synchronise. Weights, Momentum
-        slots and the step counter are untouched; x / labels are restored. All shapes give the same bits: this only moves time. Under
+        slots and the step counter are untouched; x / labels are restored; class weights and the weight map stay as set (the pass
+        takes the head they select). All shapes give the same bits: this only moves time. Under
         data parallelism call it before the first collective is in flight (and again after changing backward_cu_budget).
         `keep` is the dropout keep probability of the steps that follow: with keep < 1 the encoder's conv2 launches take the unfused
         conv + max-pool pair (rsu.h rsu_conv2d_fwd_pool folds the pool only at keep == 1), whose tuning keys differ from the fused
