@@ -187,6 +187,32 @@ size_t rsu_head_w_ws_floats(long npix, int C);
 int rsu_head_fwd_bwd_w(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w,
                        const float* pixel_w, float* prob, float* loss_sum, float* weight_sum, void* dact, float* dw, float* db,
                        float* ws, long npix, int C, float inv_count, rsu_stream_t stream);
+/* The soft-Dice (soft-F1) term next to that cross-entropy: loss = sum_p omega_p CE_p inv_count + dice_scale (1 - D). With
+ * p_i = softmax(z_i)[1] (the value written to prob), y_i = 1 for label 1 and 0 otherwise, and the Dice mass of a pixel
+ *   m_i = 0 if its label is neither 0 nor 1 (all 64 bits tested; by selection, never by multiplication),
+ *       = pixel_w[i] otherwise (1 where pixel_w is NULL); class_w does NOT enter the Dice term, it stays the cross-entropy's:
+ *   I = sum m_i p_i y_i    P = sum m_i p_i    Y = sum m_i y_i    (over the npix pixels of the call: the rank's batch)
+ *   U = P + Y + smooth     D = (2 I + smooth) / U                 (smooth > 0)
+ *   d(1 - D)/dz_i[1] = m_i (D - 2 y_i) / U p_i (1 - p_i) = -d(1 - D)/dz_i[0]
+ * Every pixel's gradient needs the three batch-wide sums, so the head runs twice, and a device-resident scalar buffer sits between the
+ * two launches (the one exception to "no device-side scalar in front of the gradient" above; only a step that asks for Dice pays it):
+ *   rsu_head_dice_sums     forward only: writes prob and OVERWRITES dice_sums[0..2] = {I, P, Y} (f32[3]; nothing to zero), fixed orders.
+ *   rsu_head_fwd_bwd_dice  rsu_head_fwd_bwd_w plus dice_scale * d(1 - D)/dz on the logits' gradients in front of dact, dw and db; it READS
+ *                          {I, P, Y} from dice_sums and recomputes none of them. loss_sum and weight_sum keep rsu_head_fwd_bwd_w's
+ *                          meaning (cross-entropy only, caller zeroes them); a host adds dice_scale (1 - D) from dice_sums for reporting.
+ * The two calls on one stream need no host synchronisation and no device-to-host copy between them. dice_sums is an ordinary device
+ * buffer that the caller owns between the calls: a host may combine it across ranks there (nothing here does: each rank's term is its
+ * own batch's Dice, and dice_scale = lambda / world keeps the SUM all-reduce of gradients the gradient of the mean of the ranks' terms).
+ * An ignored pixel's dact row is +0 and it adds nothing to any sum, whatever its pixel_w holds. Errors: rsu_head_fwd_bwd_w's, plus
+ * RSU_EINVAL for dice_sums == NULL, a smooth that is not finite and > 0, a dice_scale that is not finite and >= 0 -- returned before
+ * anything is launched or written. ws: rsu_head_dice_ws_floats(npix, C) floats, enough for either call. */
+size_t rsu_head_dice_ws_floats(long npix, int C);
+int rsu_head_dice_sums(const void* act, const float* w, const float* b, const int64_t* labels, const float* pixel_w, float* prob,
+                       float* dice_sums, float* ws, long npix, int C, rsu_stream_t stream);
+int rsu_head_fwd_bwd_dice(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w,
+                          const float* pixel_w, const float* dice_sums, float dice_scale, float smooth, float* prob, float* loss_sum,
+                          float* weight_sum, void* dact, float* dw, float* db, float* ws, long npix, int C, float inv_count,
+                          rsu_stream_t stream);
 
 /* ---- 3x3 convolution, MFMA implicit GEMM -------------------------------------------------- */
 /* unet.py:34-39,42-45,88-91: y = relu(conv3x3_valid(concat(srcs), W, dilation) + b).

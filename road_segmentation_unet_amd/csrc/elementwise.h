@@ -37,6 +37,12 @@ hipError_t ew_head(bool train, const void* act, const float* w, const float* b, 
 // the weighted training head (rsu.h rsu_head_fwd_bwd_w): same grid, ws of ew_head_blocks() * (2 C + 4) floats
 hipError_t ew_head_w(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w, const float* pixel_w, float* prob,
                      void* dact, float* dw, float* db, float* loss_sum, float* weight_sum, float* ws, long npix, int C, float inv_count, hipStream_t st);
+// the soft-Dice head (rsu.h rsu_head_dice_sums, rsu_head_fwd_bwd_dice): same grid; ws of ew_head_blocks() * 3 / * (2 C + 4) floats
+hipError_t ew_head_dice_sums(const void* act, const float* w, const float* b, const int64_t* labels, const float* pixel_w, float* prob,
+                             float* dice_sums, float* ws, long npix, int C, hipStream_t st);
+hipError_t ew_head_dice(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w, const float* pixel_w,
+                        const float* dice_sums, float dice_scale, float smooth, float* prob, void* dact, float* dw, float* db, float* loss_sum,
+                        float* weight_sum, float* ws, long npix, int C, float inv_count, hipStream_t st);
 hipError_t ew_color_adjust_bwd(const float* gx, const float* w1, float* dW0, float* db0, int Cout, float scale, int accumulate, hipStream_t st);
 hipError_t ew_momentum(float* w, float* acc, const float* g, float lr, float mu, float gscale, long n, hipStream_t st);
 // the update rules of the optimizer passes (template argument of k_update_pack_many): their scalars, passed by value to the kernels.

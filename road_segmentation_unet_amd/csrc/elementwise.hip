@@ -682,6 +682,234 @@ __global__ void __launch_bounds__(256) k_head_final_w(const float* __restrict__ 
     }
 }
 
+// The soft-Dice head (rsu.h rsu_head_dice_sums, rsu_head_fwd_bwd_dice): the Dice gradient of a pixel needs three sums over the whole batch,
+// so the head runs twice. Pass A, k_head_dice_sums: k_head_w's grid, pixel-to-thread mapping, load batching and logit / softmax expressions
+// (prob gets the same bits), no backward; per thread the three sums I = sum m p y, P = sum m p, Y = sum m y with the pixel's mass
+// m = pixel_w (1 without a map), 0 BY SELECTION for a label that is neither 0 nor 1 (all 64 bits). 3 partials per block.
+// Siblings of k_head_w, for its reason: the bodies of the kernels on the critical queue are pinned.
+__global__ void __launch_bounds__(256, 4) k_head_dice_sums(const bf16_t* __restrict__ act, const float* __restrict__ w, const float* __restrict__ b,
+                                                        const int64_t* __restrict__ labels, const float* __restrict__ pixel_w,
+                                                        float* __restrict__ prob, float* __restrict__ partial, long npix, int C) {
+    const int LP = C >> 3;
+    const int sub = threadIdx.x % LP;
+    const int ppb = 256 / LP;  // pixels per block iteration
+    float w0[8], w1[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        w0[i] = w[(sub * 8 + i) * 2];
+        w1[i] = w[(sub * 8 + i) * 2 + 1];
+    }
+    const float b0 = b[0], b1 = b[1];
+    float si = 0.f, sp = 0.f, sy = 0.f;
+    const long niter = (npix + (long)gridDim.x * ppb - 1) / ((long)gridDim.x * ppb);
+    constexpr int HU = 4;
+    for (long it0 = 0; it0 < niter; it0 += HU) {
+        long pp[HU];
+        bool okk[HU];
+        u32x4 raw[HU];
+        int64_t labv[HU];
+        float pwv[HU];
+#pragma unroll
+        for (int u = 0; u < HU; ++u) {
+            pp[u] = ((it0 + u) * gridDim.x + blockIdx.x) * ppb + threadIdx.x / LP;
+            okk[u] = (it0 + u < niter) && pp[u] < npix;
+            raw[u] = okk[u] ? *(const u32x4*)(act + pp[u] * C + sub * 8) : u32x4{0u, 0u, 0u, 0u};
+            labv[u] = okk[u] ? labels[pp[u]] : 0;
+            pwv[u] = (okk[u] && pixel_w) ? pixel_w[pp[u]] : 1.f;
+        }
+#pragma unroll
+        for (int u = 0; u < HU; ++u) {
+            float a[8];
+            unpack8(raw[u], a);
+            float l0 = 0.f, l1 = 0.f;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                l0 = fmaf(a[i], w0[i], l0);
+                l1 = fmaf(a[i], w1[i], l1);
+            }
+            for (int o = 1; o < LP; o <<= 1) {
+                l0 += __shfl_xor(l0, o);
+                l1 += __shfl_xor(l1, o);
+            }
+            l0 += b0;
+            l1 += b1;
+            const float m = fmaxf(l0, l1);
+            const float e0 = expf(l0 - m), e1 = expf(l1 - m);
+            const float s = e0 + e1;
+            const float p1 = e1 / s;
+            if (!okk[u] || sub != 0) continue;
+            prob[pp[u]] = p1;
+            const int64_t lab = labv[u];
+            if (lab != 0 && lab != 1) continue;   // ignored: no mass, whatever its pixel_w holds
+            const float mp = pwv[u] * p1;
+            sp += mp;
+            if (lab) {
+                si += mp;
+                sy += pwv[u];
+            }
+        }
+    }
+    // block reduce: the threads with sub == 0 hold the sums, added in the order of k_head_w's scalar outputs
+    __shared__ float red[256 * 3];
+    red[threadIdx.x * 3] = si;
+    red[threadIdx.x * 3 + 1] = sp;
+    red[threadIdx.x * 3 + 2] = sy;
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        float t = 0.f;
+        for (int q = 0; q < ppb; ++q) t += red[(q * LP) * 3 + threadIdx.x];
+        partial[(long)blockIdx.x * 3 + threadIdx.x] = t;
+    }
+}
+// one wave per sum, k_head_final's lanes and order; dice_sums[0..2] = {I, P, Y} is OVERWRITTEN (the caller zeroes nothing)
+__global__ void __launch_bounds__(256) k_head_final_dice_sums(const float* __restrict__ partial, float* __restrict__ dice_sums, int nblk) {
+    const int o = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (o >= 3) return;
+    float t = 0.f;
+    for (int bk = lane; bk < nblk; bk += 64) t += partial[(long)bk * 3 + o];
+    for (int m = 32; m > 0; m >>= 1) t += __shfl_xor(t, m);
+    if (lane == 0) dice_sums[o] = t;
+}
+
+// Pass B, k_head_dice: k_head_w plus, for every counted pixel, the gradient of dice_scale * (1 - D) wrt its logits,
+//   g = dice_scale * m (D - 2 y) / U * p0 p1   added to dlogit 1 and taken from dlogit 0,   U = P + Y + smooth, D = (2 I + smooth) / U,
+// in front of the weight / bias gradients and dact. {I, P, Y} are READ from dice_sums (three uniform loads per thread; what pass A left
+// there, or what a host made of it): nothing is recomputed here. The class weights do not enter g; loss_sum and weight_sum keep their
+// cross-entropy meaning and k_head_w's orders.
+__global__ void __launch_bounds__(256, 4) k_head_dice(const bf16_t* __restrict__ act, const float* __restrict__ w, const float* __restrict__ b,
+                                                   const int64_t* __restrict__ labels, const float* __restrict__ class_w,
+                                                   const float* __restrict__ pixel_w, const float* __restrict__ dice_sums, float dice_scale,
+                                                   float smooth, float* __restrict__ prob, bf16_t* __restrict__ dact,
+                                                   float* __restrict__ partial, long npix, int C, float inv_count) {
+    const int LP = C >> 3;
+    const int sub = threadIdx.x % LP;
+    const int ppb = 256 / LP;  // pixels per block iteration
+    float w0[8], w1[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        w0[i] = w[(sub * 8 + i) * 2];
+        w1[i] = w[(sub * 8 + i) * 2 + 1];
+    }
+    const float b0 = b[0], b1 = b[1];
+    const float cw0 = class_w ? class_w[0] : 1.f, cw1 = class_w ? class_w[1] : 1.f;
+    const float dU = dice_sums[1] + dice_sums[2] + smooth;
+    const float dD = (2.f * dice_sums[0] + smooth) / dU;
+    // dice_scale (D - 2 y) / U for y = 0 and y = 1: the same in every lane, so kept in scalar registers and multiplied in before the label
+    // selects (a select between the two would copy one into a vector register). k_head_w sits at 128 VGPRs, this kernel has none to spare
+    // at 4 waves per SIMD: with the two factors as plain floats and k_head_w's 64-bit trip count it spilled 7 registers to scratch.
+    const float gq0 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(dice_scale * dD / dU)));
+    const float gq1 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(dice_scale * (dD - 2.f) / dU)));
+    float gw0[8], gw1[8], gb0 = 0.f, gb1 = 0.f, lsum = 0.f, osum = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) gw0[i] = gw1[i] = 0.f;
+    // (a 32-bit trip count: at most 8 below 1024 blocks, npix / (1024 ppb) above; two vector registers less than k_head_w's 64-bit one)
+    const int niter = (int)((npix + (long)gridDim.x * ppb - 1) / ((long)gridDim.x * ppb));
+    constexpr int HU = 4;
+    for (int it0 = 0; it0 < niter; it0 += HU) {
+        long pp[HU];
+        bool okk[HU];
+        u32x4 raw[HU];
+        int64_t labv[HU];
+        float pwv[HU];
+#pragma unroll
+        for (int u = 0; u < HU; ++u) {
+            pp[u] = ((long)(it0 + u) * gridDim.x + blockIdx.x) * ppb + threadIdx.x / LP;
+            okk[u] = (it0 + u < niter) && pp[u] < npix;
+            raw[u] = okk[u] ? *(const u32x4*)(act + pp[u] * C + sub * 8) : u32x4{0u, 0u, 0u, 0u};
+            labv[u] = okk[u] ? labels[pp[u]] : 0;
+            pwv[u] = (okk[u] && pixel_w) ? pixel_w[pp[u]] : 1.f;
+        }
+#pragma unroll
+        for (int u = 0; u < HU; ++u) {
+            const long p = pp[u];
+            const bool ok = okk[u];
+            float a[8];
+            unpack8(raw[u], a);
+            float l0 = 0.f, l1 = 0.f;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                l0 = fmaf(a[i], w0[i], l0);
+                l1 = fmaf(a[i], w1[i], l1);
+            }
+            for (int o = 1; o < LP; o <<= 1) {
+                l0 += __shfl_xor(l0, o);
+                l1 += __shfl_xor(l1, o);
+            }
+            l0 += b0;
+            l1 += b1;
+            const float m = fmaxf(l0, l1);
+            const float e0 = expf(l0 - m), e1 = expf(l1 - m);
+            const float s = e0 + e1;
+            const float p1 = e1 / s, p0 = e0 / s;
+            if (ok && sub == 0) prob[p] = p1;
+            if (!ok) continue;
+            const int64_t lab = labv[u];
+            if (lab != 0 && lab != 1) {   // ignored
+                *(u32x4*)(dact + p * C + sub * 8) = u32x4{0u, 0u, 0u, 0u};
+                continue;
+            }
+            const float omega = (lab ? cw1 : cw0) * pwv[u];
+            const float gt = pwv[u] * (p0 * p1);
+            const float g = lab ? gt * gq1 : gt * gq0;
+            const float d0 = (p0 - (lab == 0 ? 1.f : 0.f)) * inv_count * omega - g;
+            const float d1 = (p1 - (lab == 1 ? 1.f : 0.f)) * inv_count * omega + g;
+            float da[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                gw0[i] = fmaf(a[i], d0, gw0[i]);
+                gw1[i] = fmaf(a[i], d1, gw1[i]);
+                da[i] = a[i] > 0.f ? fmaf(d0, w0[i], d1 * w1[i]) : 0.f;
+            }
+            *(u32x4*)(dact + p * C + sub * 8) = pack8(da);
+            if (sub == 0) {
+                gb0 += d0;
+                gb1 += d1;
+                lsum += omega * -((lab ? l1 : l0) - m - logf(s));
+                osum += omega;
+            }
+        }
+    }
+    // block reduce as in k_head_w
+    constexpr int NV = 21;
+    __shared__ float red[256 * NV];
+    float* my = red + threadIdx.x * NV;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        my[i] = gw0[i];
+        my[8 + i] = gw1[i];
+    }
+    my[16] = gb0; my[17] = gb1; my[18] = lsum; my[19] = osum;
+    __syncthreads();
+    const int nout = 2 * C + 4;  // [C][2] dw, db[2], loss, weight sum
+    for (int o = threadIdx.x; o < nout; o += 256) {
+        float t = 0.f;
+        if (o < 2 * C) {
+            const int c = o >> 1, k = o & 1, sg = c >> 3, i = c & 7;
+            for (int q = 0; q < ppb; ++q) t += red[(q * LP + sg) * NV + k * 8 + i];
+        } else {
+            const int j = 16 + (o - 2 * C);
+            for (int q = 0; q < ppb; ++q) t += red[(q * LP) * NV + j];
+        }
+        partial[(long)blockIdx.x * nout + o] = t;
+    }
+}
+// k_head_final_w for pass B: same outputs, lanes and order
+__global__ void __launch_bounds__(256) k_head_final_dice(const float* __restrict__ partial, float* __restrict__ dw, float* __restrict__ db,
+                                                         float* __restrict__ loss_sum, float* __restrict__ weight_sum, int nblk, int C) {
+    const int nout = 2 * C + 4;
+    const int o = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (o >= nout) return;
+    float t = 0.f;
+    for (int bk = lane; bk < nblk; bk += 64) t += partial[(long)bk * nout + o];
+    for (int m = 32; m > 0; m >>= 1) t += __shfl_xor(t, m);
+    if (lane == 0) {
+        if (o < 2 * C) dw[o] = t;
+        else if (o < 2 * C + 2) db[o - 2 * C] = t;
+        else if (o == 2 * C + 2) loss_sum[0] += t;
+        else if (weight_sum) weight_sum[0] += t;
+    }
+}
+
 // color_space_adjust gradients from the first conv's scatter buffer (include/rsu.h, rsu_color_adjust_bwd): 12 outputs, each a
 // 9 x Cout sum in a fixed order (lane-strided partials, then an LDS tree): one block of 12 x 64 threads
 __global__ void __launch_bounds__(768) k_color_adjust_bwd(const float* __restrict__ gx, const float* __restrict__ w1, float* __restrict__ dW0,
@@ -1073,6 +1301,22 @@ hipError_t ew_head_w(const void* act, const float* w, const float* b, const int6
     hipLaunchKernelGGL(k_head_w, dim3(nb), dim3(256), 0, st, (const bf16_t*)act, w, b, labels, class_w, pixel_w, prob, (bf16_t*)dact, ws, npix, C,
                        inv_count);
     hipLaunchKernelGGL(k_head_final_w, dim3((2 * C + 4 + 3) / 4), dim3(256), 0, st, ws, dw, db, loss_sum, weight_sum, nb, C);
+    return hipGetLastError();
+}
+hipError_t ew_head_dice_sums(const void* act, const float* w, const float* b, const int64_t* labels, const float* pixel_w, float* prob,
+                             float* dice_sums, float* ws, long npix, int C, hipStream_t st) {
+    const int nb = ew_head_blocks(npix, C);
+    hipLaunchKernelGGL(k_head_dice_sums, dim3(nb), dim3(256), 0, st, (const bf16_t*)act, w, b, labels, pixel_w, prob, ws, npix, C);
+    hipLaunchKernelGGL(k_head_final_dice_sums, dim3(1), dim3(256), 0, st, ws, dice_sums, nb);
+    return hipGetLastError();
+}
+hipError_t ew_head_dice(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w, const float* pixel_w,
+                        const float* dice_sums, float dice_scale, float smooth, float* prob, void* dact, float* dw, float* db, float* loss_sum,
+                        float* weight_sum, float* ws, long npix, int C, float inv_count, hipStream_t st) {
+    const int nb = ew_head_blocks(npix, C);
+    hipLaunchKernelGGL(k_head_dice, dim3(nb), dim3(256), 0, st, (const bf16_t*)act, w, b, labels, class_w, pixel_w, dice_sums, dice_scale, smooth,
+                       prob, (bf16_t*)dact, ws, npix, C, inv_count);
+    hipLaunchKernelGGL(k_head_final_dice, dim3((2 * C + 4 + 3) / 4), dim3(256), 0, st, ws, dw, db, loss_sum, weight_sum, nb, C);
     return hipGetLastError();
 }
 hipError_t ew_color_adjust_bwd(const float* gx, const float* w1, float* dW0, float* db0, int Cout, float scale, int accumulate, hipStream_t st) {

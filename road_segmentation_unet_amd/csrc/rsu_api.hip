@@ -3,6 +3,7 @@
 // caller's; the only library-owned device memory is a 4-KiB page of zeros used for out-of-window reads.
 #include <array>
 #include <atomic>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
@@ -1419,6 +1420,23 @@ extern "C" int rsu_head_fwd_bwd_w(const void* act, const float* w, const float* 
     if (!act || !w || !b || !labels || !prob || !loss_sum || !dact || !dw || !db || !ws || !head_c_ok(C) || npix < 1) return RSU_EINVAL;
     HIP_CHECK_RET(ew_head_w(act, w, b, labels, class_w, pixel_w, prob, dact, dw, db, loss_sum, weight_sum, ws, npix, C, inv_count,
                             (hipStream_t)stream));
+    return RSU_OK;
+}
+extern "C" size_t rsu_head_dice_ws_floats(long npix, int C) { return (size_t)ew_head_blocks(npix, C) * (2 * C + 4); }
+extern "C" int rsu_head_dice_sums(const void* act, const float* w, const float* b, const int64_t* labels, const float* pixel_w, float* prob,
+                                  float* dice_sums, float* ws, long npix, int C, rsu_stream_t stream) {
+    if (!act || !w || !b || !labels || !prob || !dice_sums || !ws || !head_c_ok(C) || npix < 1) return RSU_EINVAL;
+    HIP_CHECK_RET(ew_head_dice_sums(act, w, b, labels, pixel_w, prob, dice_sums, ws, npix, C, (hipStream_t)stream));
+    return RSU_OK;
+}
+extern "C" int rsu_head_fwd_bwd_dice(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w,
+                                     const float* pixel_w, const float* dice_sums, float dice_scale, float smooth, float* prob, float* loss_sum,
+                                     float* weight_sum, void* dact, float* dw, float* db, float* ws, long npix, int C, float inv_count,
+                                     rsu_stream_t stream) {
+    if (!act || !w || !b || !labels || !prob || !loss_sum || !dact || !dw || !db || !ws || !head_c_ok(C) || npix < 1) return RSU_EINVAL;
+    if (!dice_sums || !std::isfinite(smooth) || !(smooth > 0.f) || !std::isfinite(dice_scale) || !(dice_scale >= 0.f)) return RSU_EINVAL;
+    HIP_CHECK_RET(ew_head_dice(act, w, b, labels, class_w, pixel_w, dice_sums, dice_scale, smooth, prob, dact, dw, db, loss_sum, weight_sum, ws,
+                               npix, C, inv_count, (hipStream_t)stream));
     return RSU_OK;
 }
 extern "C" int rsu_momentum_step(float* w, float* acc, const float* g, float lr, float mu, float gscale, long n, rsu_stream_t stream) {

@@ -70,6 +70,9 @@ EXTRA_FLAG_DEFS = [
     ("class_weights", str, None, "Loss weights of the classes background,road: 'w0,w1' (two finite floats >= 0, not both 0) or 'balanced' "
                                  "(N / (2 N_c) from the training ground truth: mean weight 1, so --lr keeps its scale); default: the "
                                  "reference's unweighted loss. The loss stays normalised by the pixel count, not by the sum of the weights"),
+    ("dice_weight", float, 0.0, "lambda >= 0 of a soft-Dice (soft-F1) term: loss = cross-entropy + lambda * (1 - Dice), Dice over each GPU's "
+                                "batch; 0 = off (the reference's loss). Ignored pixels and the weight map enter Dice, class weights do not"),
+    ("dice_smooth", float, 1.0, "Smoothing constant s > 0 of Dice = (2 I + s) / (P + Y + s)"),
 ]
 
 
@@ -94,6 +97,34 @@ def parse_class_weights(value):
     if len(cw) != 2 or not all(math.isfinite(v) and v >= 0.0 for v in cw) or cw == (0.0, 0.0):
         raise ValueError("--class_weights must be 'w0,w1' (two finite floats >= 0, not both 0) or 'balanced', not %r" % (value,))
     return cw
+
+
+def parse_dice_weight(value):
+    """The --dice_weight value as a float: finite and >= 0 (0.0 = no Dice term). Anything else raises ValueError."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if not (math.isfinite(v) and v >= 0.0):
+        raise ValueError("--dice_weight must be a finite float >= 0, not %r" % (value,))
+    return v
+
+
+def parse_dice_smooth(value):
+    """The --dice_smooth value as a float: finite and > 0. Anything else raises ValueError."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if not (math.isfinite(v) and v > 0.0):
+        raise ValueError("--dice_smooth must be a finite float > 0, not %r" % (value,))
+    return v
+
+
+def dice_from_sums(I, P, Y, smooth):
+    """Soft Dice D = (2 I + s) / (P + Y + s) from the sums I = sum m p y, P = sum m p, Y = sum m y that the head leaves in UNet.dice_sums
+    (rsu.h rsu_head_dice_sums). Plain arithmetic: floats, numpy arrays and tensors alike; empty sums give D = 1."""
+    return (2.0 * I + smooth) / (P + Y + smooth)
 
 
 def balanced_class_weights(groundtruth):
@@ -122,6 +153,7 @@ class Options(object):
         if self.optimizer not in ("momentum", "adam"):
             raise ValueError("--optimizer must be momentum or adam, not %r" % (self.optimizer,))
         self.class_weights = parse_class_weights(self.class_weights)   # None, (w0, w1) or "balanced" (cli.main resolves it)
+        self.dice_weight, self.dice_smooth = parse_dice_weight(self.dice_weight), parse_dice_smooth(self.dice_smooth)
         ra = self.rotation_angles
         if isinstance(ra, str):
             self.rotation_angles = None if not ra else [int(i) for i in ra.split(",")]
@@ -158,7 +190,8 @@ class ConvolutionalModel:
             raise ValueError("class_weights='balanced' must be resolved from the training ground truth before the model is built: "
                              "options.class_weights = balanced_class_weights(groundtruth) (cli.main does)")
         self.net = UNet(opts.num_layers, opts.root_size, opts.dilated_layers, self.local_batch, opts.patch_size, device=device,
-                        params=params, seed=opts.seed, training=True, optimizer=opts.optimizer, class_weights=opts.class_weights)
+                        params=params, seed=opts.seed, training=True, optimizer=opts.optimizer, class_weights=opts.class_weights,
+                        dice_weight=opts.dice_weight, dice_smooth=opts.dice_smooth)
         self.net.dropout_seed = int(opts.seed) + 7919 * self.rank  # independent masks on every rank's shard
         self._bucketer = None
         self._exchange_tuned = False
@@ -183,6 +216,8 @@ class ConvolutionalModel:
         weights: an optional per-pixel weight map [b,P,P] for this step's loss (UNet.set_pixel_weights; it multiplies the model's
         class weights); None: no map, also after a step that had one. With class weights or a map the loss is the weighted sum over the
         GLOBAL pixel count (UNet.backward_device), and a label other than 0 and 1 then ignores its pixel: no loss, no gradient.
+        With --dice_weight > 0 the returned loss is that cross-entropy + dice_weight * (1 - D), D the soft Dice of each rank's batch
+        (averaged over the ranks), and labels other than 0 and 1 are ignored as well.
         (Synchronous upload: the train() loop stages its batches one step ahead instead, see pool.BatchUploader.)"""
         net = self.net
         net.x.copy_(torch.as_tensor(np.asarray(patches, dtype=np.float32)).to(net.device))
@@ -213,8 +248,14 @@ class ConvolutionalModel:
         net.forward_device(keep=float(opts.dropout))
         if self._bucketer is not None:
             self._bucketer.reset()
-        net.backward_device(1.0 / (opts.batch_size * opts.patch_size * opts.patch_size))
+        # the Dice term is each rank's own batch Dice, scaled by 1 / world: the SUM all-reduce of the gradients and of the loss below then
+        # give the mean over the ranks, with no collective inside the backward pass
+        dice_scale = net.dice_weight / self.world
+        net.backward_device(1.0 / (opts.batch_size * opts.patch_size * opts.patch_size), dice_scale=dice_scale)
         loss = net.loss_sum / (opts.batch_size * opts.patch_size * opts.patch_size)
+        if dice_scale > 0.0:   # (device arithmetic on net.dice_sums: no synchronisation)
+            s = net.dice_sums
+            loss = loss + dice_scale * (1.0 - dice_from_sums(s[0:1], s[1:2], s[2:3], net.dice_smooth))
         if self._bucketer is not None:
             self._bucketer.finish()
             dist.all_reduce(loss)

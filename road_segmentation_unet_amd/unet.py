@@ -107,11 +107,13 @@ class UNet:
     static in exactly the same way (tf_aerial_images.py:133-138)."""
 
     def __init__(self, num_layers, root_size, dilated_layers, batch_size, patch_size, device="cuda:0", params=None, seed=2017,
-                 training=True, optimizer="momentum", class_weights=None):
+                 training=True, optimizer="momentum", class_weights=None, dice_weight=0.0, dice_smooth=1.0):
         """optimizer: "momentum" (the reference's MomentumOptimizer: apply_momentum) or "adam" (tf.train.AdamOptimizer: apply_adam; a
         second fp32 slot per variable, flat_v).
         class_weights: None or a pair (w0, w1) of finite floats >= 0, not both 0: the weighted cross-entropy of rsu.h
-        rsu_head_fwd_bwd_w (see backward_device). None and (1, 1) are the reference's unweighted loss."""
+        rsu_head_fwd_bwd_w (see backward_device). None and (1, 1) are the reference's unweighted loss.
+        dice_weight: lambda >= 0 of the soft-Dice term, loss = cross-entropy + lambda (1 - Dice) (rsu.h rsu_head_fwd_bwd_dice); 0.0: no such
+        term, the step issues the launches it always did. dice_smooth: the term's smoothing constant, > 0."""
         if optimizer not in OPTIMIZERS:
             raise _lib.RsuError("optimizer must be one of %s, not %r" % ("|".join(OPTIMIZERS), optimizer))
         self.optimizer = optimizer
@@ -125,6 +127,7 @@ class UNet:
         self.training = training
         self.class_weights = class_weights   # (a property: validated, mirrored to the device as f32[2])
         self.pixel_weights = None            # the weight map [B, P, P] float32 on the device, or None (set_pixel_weights)
+        self.dice_weight, self.dice_smooth = dice_weight, dice_smooth   # (properties: validated)
         self.keep = 1.0        # dropout keep probability of the forward pass in flight (set by forward_device)
         self.dropout_seed = int(seed) if seed is not None else 0
         self.backward_cu_budget = None   # CUs the backward launches may plan for in total (None: the library's default)
@@ -155,6 +158,36 @@ class UNet:
                 raise _lib.RsuError("class_weights must be None or two finite floats >= 0, not both 0; got %r" % (cw,))
         self._class_weights = cw
         self._class_w_dev = torch.tensor(cw, dtype=torch.float32, device=self.device) if cw is not None else None
+
+    @property
+    def dice_weight(self):
+        """lambda of the soft-Dice term: the default dice_scale of backward_device (0.0: the cross-entropy alone)"""
+        return self._dice_weight
+
+    @dice_weight.setter
+    def dice_weight(self, v):
+        try:
+            v = float(v)
+        except (TypeError, ValueError):
+            v = float("nan")
+        if not (math.isfinite(v) and v >= 0.0):
+            raise _lib.RsuError("dice_weight must be a finite float >= 0")
+        self._dice_weight = v
+
+    @property
+    def dice_smooth(self):
+        """the smoothing constant s of D = (2 I + s) / (P + Y + s)"""
+        return self._dice_smooth
+
+    @dice_smooth.setter
+    def dice_smooth(self, v):
+        try:
+            v = float(v)
+        except (TypeError, ValueError):
+            v = float("nan")
+        if not (math.isfinite(v) and v > 0.0):
+            raise _lib.RsuError("dice_smooth must be a finite float > 0")
+        self._dice_smooth = v
 
     def set_pixel_weights(self, t):
         """The per-pixel weight map of the loss (backward_device): `t` [B, P, P] (tensor or array, any float type) is copied into the
@@ -314,6 +347,9 @@ class UNet:
         # by one launch in front of the head
         self._loss_acc = torch.zeros(2, dtype=torch.float32, device=dev)
         self.loss_sum, self.weight_sum = self._loss_acc[0:1], self._loss_acc[1:2]
+        # {I, P, Y} of the soft-Dice term: overwritten by the first of the Dice head's two launches, read by the second (rsu.h
+        # rsu_head_dice_sums); all zero (D = 1) until a pass with dice_scale > 0 has run
+        self.dice_sums = torch.zeros(3, dtype=torch.float32, device=dev)
         # workspace of the conv launches that cut their reduction into slices (rsu.h rsu_conv2d_fwd_k: the deep levels at small batches);
         # one per stream that issues conv launches -- the main stream, and the side stream of the dilated twin blocks in the forward pass
         nk = int(_lib.lib().rsu_conv_splitk_ws_floats()) if os.environ.get("RSU_KSPLIT", "1") != "0" else 0
@@ -332,6 +368,7 @@ class UNet:
                     self.grad["skipd_%d" % i] = torch.zeros_like(up)
             lib = _lib.lib()
             ws = [lib.rsu_head_ws_floats(B * self.P * self.P, self.root), lib.rsu_head_w_ws_floats(B * self.P * self.P, self.root),
+                  lib.rsu_head_dice_ws_floats(B * self.P * self.P, self.root),
                   lib.rsu_conv_first_bwd_ws_floats(self.root)]
             for kind, n, s, segs in self._packed_kernels():   # (the dead level L-1 dilated pair has the shapes of the level's live block)
                 if kind == _PACK_CONV_FWD:
@@ -617,7 +654,7 @@ class UNet:
                     _ptr(self.pk[name + "/kernel", "bwd", src_index]), _ptr(dx), _ptr(relu_src), accumulate, self.B, hin, hin, cnt, 0, cnt,
                     cout, dil, self.sched.ncu(), _ptr(kws), kws.numel() if kws is not None else 0, self._stream())
 
-    def backward_device(self, inv_count, update=None):
+    def backward_device(self, inv_count, update=None, dice_scale=None):
         """loss + all gradients for self.x / self.labels; forward_device() must have run. inv_count = 1 / (global pixel count).
         The loss is the reference's mean softmax cross-entropy unless class weights other than (1, 1) or a weight map are set
         (class_weights, set_pixel_weights): then pixel p counts omega_p = class_weights[label_p] * pixel_weights[p] times in loss_sum and
@@ -625,15 +662,23 @@ class UNet:
         loss_sum / weight_sum is the weighted mean, for reporting). A label in self.labels other than 0 and 1 IGNORES its pixel in that
         weighted pass: no loss, no gradient, no weight (prob is still written). The unweighted pass expects labels in {0, 1}; to ignore
         pixels without weighting the others, set a map of ones. After an unweighted pass weight_sum is 0.
+        dice_scale (None: self.dice_weight) > 0 adds dice_scale * (1 - D) to the objective, D the soft Dice of THIS net's batch (rsu.h
+        rsu_head_fwd_bwd_dice): the head then runs as two launches with the device buffer dice_sums = {I, P, Y} between them (no host
+        synchronisation), labels other than 0 / 1 are ignored, the weight map enters D and the class weights do not. loss_sum and weight_sum
+        stay the cross-entropy's; the term's value is dice_scale * (1 - D) with D from dice_sums. A data-parallel host passes
+        dice_weight / world. With dice_scale == 0 the pass is exactly the one described above.
         update = (lr0, momentum): accepted from callers that name the Momentum step they will take; it changes nothing here -- the step
         is apply_momentum's -- but a net built with another optimizer refuses it."""
         if update is not None and self.optimizer != "momentum":
             raise _lib.RsuError("backward_device(update=...) is the Momentum step; an %s net steps with apply_%s after the pass"
                                 % (self.optimizer, self.optimizer))
+        dice_scale = self._dice_weight if dice_scale is None else float(dice_scale)
+        if not (math.isfinite(dice_scale) and dice_scale >= 0.0):
+            raise _lib.RsuError("dice_scale must be a finite float >= 0, not %r" % (dice_scale,))
         st = self._stream()
         self.sched.begin(self.backward_cu_budget)
         try:
-            self._backward_body(inv_count)
+            self._backward_body(inv_count, dice_scale)
         finally:
             self.sched.end()   # (an exception inside must not leave later launches planned for a share of the chip)
         # ---- color_space_adjust (unet.py:22-23): its input gradient is never materialised (include/rsu.h, rsu_conv_first_bwd_weight):
@@ -645,12 +690,19 @@ class UNet:
             call("rsu_color_adjust_bwd", _ptr(self.gfirst[1]), _ptr(self.w["conv_dilut_0/atrous_conv1/kernel"]), _ptr(gk), _ptr(gb), self.root,
                  inv_keep, 1, st)
 
-    def _backward_body(self, inv_count):
+    def _backward_body(self, inv_count, dice_scale=0.0):
         B, L, st, a, g = self.B, self.L, self._stream(), self.act, self.grad
         keep = self.keep
         last = a[self.last_name]
         self._loss_acc.zero_()
-        if self.loss_is_weighted():
+        if dice_scale > 0.0:
+            head = (_ptr(last), _ptr(self.w["weight_output/kernel"]), _ptr(self.w["weight_output/bias"]), _ptr(self.labels))
+            npix = B * self.P * self.P
+            call("rsu_head_dice_sums", *head, _ptr(self.pixel_weights), _ptr(self.prob), _ptr(self.dice_sums), _ptr(self.ws), npix, self.root, st)
+            call("rsu_head_fwd_bwd_dice", *head, _ptr(self._class_w_dev), _ptr(self.pixel_weights), _ptr(self.dice_sums), dice_scale,
+                 self._dice_smooth, _ptr(self.prob), _ptr(self.loss_sum), _ptr(self.weight_sum), _ptr(g[self.last_name]),
+                 _ptr(self.g["weight_output/kernel"]), _ptr(self.g["weight_output/bias"]), _ptr(self.ws), npix, self.root, inv_count, st)
+        elif self.loss_is_weighted():
             call("rsu_head_fwd_bwd_w", _ptr(last), _ptr(self.w["weight_output/kernel"]), _ptr(self.w["weight_output/bias"]), _ptr(self.labels),
                  _ptr(self._class_w_dev), _ptr(self.pixel_weights), _ptr(self.prob),
                  _ptr(self.loss_sum), _ptr(self.weight_sum), _ptr(g[self.last_name]), _ptr(self.g["weight_output/kernel"]),
@@ -735,8 +787,8 @@ class UNet:
         """The explicit tile-shape tuning pass (rsu.h rsu_set_autotune): ONE untimed forward (+ backward) over random data with the
         library in RSU_TUNE_MEASURE mode -- every conv geometry of this network at the CU shares its launches use is timed once on an
         idle device -- then back to RSU_TUNE_LOOKUP, in which the launch entry points never measure nor synchronise. Weights, Momentum
-        slots and the step counter are untouched; x / labels are restored; class weights and the weight map stay as set (the pass
-        takes the head they select). All shapes give the same bits: this only moves time. Under
+        slots and the step counter are untouched; x / labels are restored; class weights, the weight map and dice_weight stay as
+        set (the pass takes the head they select). All shapes give the same bits: this only moves time. Under
         data parallelism call it before the first collective is in flight (and again after changing backward_cu_budget).
         `keep` is the dropout keep probability of the steps that follow: with keep < 1 the encoder's conv2 launches take the unfused
         conv + max-pool pair (rsu.h rsu_conv2d_fwd_pool folds the pool only at keep == 1), whose tuning keys differ from the fused
