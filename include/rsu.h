@@ -213,6 +213,24 @@ int rsu_head_fwd_bwd_dice(const void* act, const float* w, const float* b, const
                           const float* pixel_w, const float* dice_sums, float dice_scale, float smooth, float* prob, float* loss_sum,
                           float* weight_sum, void* dact, float* dw, float* db, float* ws, long npix, int C, float inv_count,
                           rsu_stream_t stream);
+/* The evaluation head, for held-out data: forward only (no dact, dw, db), one call per batch, every output an ACCUMULATOR that the
+ * caller zeroes once in front of a whole validation set and reads back once behind it. Logits, softmax and prob are the other heads'
+ * (same bits). With omega_p of rsu_head_fwd_bwd_w and {I, P, Y}, m_i of rsu_head_dice_sums over the npix pixels of the call:
+ *   sums[0..4] (f32[5]) += {sum omega CE, sum omega, I, P, Y}
+ *   hist[l][min(RSU_EVAL_BINS - 1, (int)(p * RSU_EVAL_BINS))] += 1   for every pixel with label l in {0, 1} (whatever its weights are),
+ *                                                                   p the f32 value written to prob; hist is u64 [2][RSU_EVAL_BINS]
+ * A label that is neither 0 nor 1 (all 64 bits tested) ignores its pixel by selection: prob is written, nothing else sees it, whatever
+ * its pixel_w holds. class_w (f32[2]) and pixel_w (f32[npix]) may be NULL (= 1). Same grid, pixel-to-thread mapping and fixed summation
+ * orders as the training heads: from zeroed accumulators sums[0..1] equal rsu_head_fwd_bwd_w's loss_sum / weight_sum and sums[2..4]
+ * equal rsu_head_dice_sums's dice_sums bit for bit; the histogram holds integer counts (vector 64-bit atomics of per-launch totals),
+ * so every output is deterministic. With a threshold t = k / RSU_EVAL_BINS, "p >= t" is "bin >= k" exactly: the confusion counts at
+ * every such threshold follow from hist on the host. Errors: RSU_EINVAL for a NULL act, w, b, labels, prob, sums, hist or ws, a C
+ * the other heads refuse, npix < 1 -- returned before anything is launched or written.
+ * ws: rsu_head_eval_ws_floats(npix, C) floats (0 for a refused C or npix). */
+#define RSU_EVAL_BINS 256
+size_t rsu_head_eval_ws_floats(long npix, int C);
+int rsu_head_eval(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w, const float* pixel_w,
+                  float* prob, float* sums, unsigned long long* hist, float* ws, long npix, int C, rsu_stream_t stream);
 
 /* ---- 3x3 convolution, MFMA implicit GEMM -------------------------------------------------- */
 /* unet.py:34-39,42-45,88-91: y = relu(conv3x3_valid(concat(srcs), W, dilation) + b).

@@ -44,11 +44,16 @@ def main(argv=None):
         dist.init_process_group("nccl")
     rank = dist.get_rank() if dist.is_initialized() else 0
     train_data = None
+    if opts.validation_images > 0 and opts.num_epoch > 0:
+        # whole images leave the training set before anything is derived from it (the balanced class weights, rotation, patches)
+        train_data, held_out = hostio.split_validation(*hostio.load_train_data(opts.train_data_dir), opts.validation_images)
+    else:
+        held_out = None
     if opts.class_weights == "balanced":
         # the model takes its class weights at construction: this case alone loads the training set in front of it. Without a
         # training epoch the loss is never evaluated and the flag has no effect
         if opts.num_epoch > 0:
-            train_data = hostio.load_train_data(opts.train_data_dir)
+            train_data = train_data if train_data is not None else hostio.load_train_data(opts.train_data_dir)
             opts.class_weights = balanced_class_weights(train_data[1])
             print("Balanced class weights: background {:.4f}, road {:.4f}".format(*opts.class_weights))
         else:
@@ -83,6 +88,10 @@ def main(argv=None):
             print("Train on {} patches of size {}x{}".format(patches.shape[0], patches.shape[1], patches.shape[2]))
             labels_patches = hostio.extract_patches(gt_exp, patch_size=opts.patch_size, stride=opts.stride)
             print("Train on {} groundtruth patches of size {}x{}".format(*labels_patches.shape[:3]))
+        validation = None
+        if held_out is not None:
+            validation = hostio.validation_patches(held_out[0], held_out[1], input_size, opts.patch_size)
+            print("Validate on {} patches of {} held-out images".format(validation[0].shape[0], len(held_out[0])))
         summary = model._ensure_summary()
         if summary is not None:
             summary.add_to_eval_patch_summary(train_groundtruth)
@@ -90,7 +99,7 @@ def main(argv=None):
             print("==== Train epoch: {} ====".format(i))
             if summary is not None:
                 summary.reset()  # tf.local_variables_initializer().run(): reset scores
-            stats = model.train(patches, labels_patches, train_images, train_groundtruth)
+            stats = model.train(patches, labels_patches, train_images, train_groundtruth, validation=validation)
             if rank == 0:
                 print("\nepoch {} : {}".format(i, stats))
             model.save(i)

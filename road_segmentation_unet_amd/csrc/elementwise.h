@@ -43,6 +43,13 @@ hipError_t ew_head_dice_sums(const void* act, const float* w, const float* b, co
 hipError_t ew_head_dice(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w, const float* pixel_w,
                         const float* dice_sums, float dice_scale, float smooth, float* prob, void* dact, float* dw, float* db, float* loss_sum,
                         float* weight_sum, float* ws, long npix, int C, float inv_count, hipStream_t st);
+// the evaluation head (rsu.h rsu_head_eval): same grid, forward only; ws of ew_head_eval_ws_floats() floats (5 partial sums and one
+// 2 x EW_EVAL_BINS row of u32 counters per workgroup). EW_EVAL_BINS is rsu.h's RSU_EVAL_BINS.
+constexpr int EW_EVAL_BINS = 256;
+constexpr int EW_EVAL_SLICES = 8;   // k_head_eval_final: workgroups per 64-bin group (= adds per address of hist per call)
+size_t ew_head_eval_ws_floats(long npix, int C);
+hipError_t ew_head_eval(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w, const float* pixel_w,
+                        float* prob, float* sums, unsigned long long* hist, float* ws, long npix, int C, hipStream_t st);
 hipError_t ew_color_adjust_bwd(const float* gx, const float* w1, float* dW0, float* db0, int Cout, float scale, int accumulate, hipStream_t st);
 hipError_t ew_momentum(float* w, float* acc, const float* g, float lr, float mu, float gscale, long n, hipStream_t st);
 // the update rules of the optimizer passes (template argument of k_update_pack_many): their scalars, passed by value to the kernels.

@@ -910,6 +910,139 @@ __global__ void __launch_bounds__(256) k_head_final_dice(const float* __restrict
     }
 }
 
+// The evaluation head (rsu.h rsu_head_eval): forward only, for held-out data. k_head_dice_sums's grid, pixel-to-thread mapping, load batching
+// and logit / softmax expressions (prob gets the same bits); per thread the five sums {omega CE, omega, I, P, Y} -- the first two with
+// k_head_w's expressions and order, the last three with k_head_dice_sums's, so from zeroed accumulators they have those kernels' bits -- and,
+// for every counted pixel, one count in the block's LDS histogram hist[label][min(255, (int)(p * 256))]. No dact, no dw, no db.
+// A sibling of k_head_w / k_head_dice_sums, for their reason: the bodies of the kernels on the critical queue are pinned.
+// The histogram: one LDS counter array per block (2 x 256 u32), bumped by the pixel's sub == 0 lane only -- at most 64 / LP lanes of a
+// wave, so a trained network that sends every pixel to bin 0 or bin 255 costs a wave at most that many serialised LDS adds per pixel
+// trip, next to 64 16-byte HBM loads. Blocks never meet on a global address: each stores its 512 counters as a plain row of the
+// workspace (2 KB per block, 2 MB at 1024 blocks against 77 MB of activations read), and k_head_eval_final sums the rows. 1024 blocks
+// adding to the two hot addresses of a saturated histogram at the same moment is exactly what this avoids.
+__global__ void __launch_bounds__(256, 4) k_head_eval(const bf16_t* __restrict__ act, const float* __restrict__ w, const float* __restrict__ b,
+                                                   const int64_t* __restrict__ labels, const float* __restrict__ class_w,
+                                                   const float* __restrict__ pixel_w, float* __restrict__ prob, float* __restrict__ partial,
+                                                   unsigned* __restrict__ hpart, long npix, int C) {
+    const int LP = C >> 3;
+    const int sub = threadIdx.x % LP;
+    const int ppb = 256 / LP;  // pixels per block iteration
+    __shared__ unsigned hist[2 * EW_EVAL_BINS];
+    for (int i = threadIdx.x; i < 2 * EW_EVAL_BINS; i += 256) hist[i] = 0u;
+    float w0[8], w1[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        w0[i] = w[(sub * 8 + i) * 2];
+        w1[i] = w[(sub * 8 + i) * 2 + 1];
+    }
+    const float b0 = b[0], b1 = b[1];
+    const float cw0 = class_w ? class_w[0] : 1.f, cw1 = class_w ? class_w[1] : 1.f;
+    float lsum = 0.f, osum = 0.f, si = 0.f, sp = 0.f, sy = 0.f;
+    __syncthreads();
+    const long niter = (npix + (long)gridDim.x * ppb - 1) / ((long)gridDim.x * ppb);
+    constexpr int HU = 4;
+    for (long it0 = 0; it0 < niter; it0 += HU) {
+        long pp[HU];
+        bool okk[HU];
+        u32x4 raw[HU];
+        int64_t labv[HU];
+        float pwv[HU];
+#pragma unroll
+        for (int u = 0; u < HU; ++u) {
+            pp[u] = ((it0 + u) * gridDim.x + blockIdx.x) * ppb + threadIdx.x / LP;
+            okk[u] = (it0 + u < niter) && pp[u] < npix;
+            raw[u] = okk[u] ? *(const u32x4*)(act + pp[u] * C + sub * 8) : u32x4{0u, 0u, 0u, 0u};
+            labv[u] = okk[u] ? labels[pp[u]] : 0;
+            pwv[u] = (okk[u] && pixel_w) ? pixel_w[pp[u]] : 1.f;
+        }
+#pragma unroll
+        for (int u = 0; u < HU; ++u) {
+            float a[8];
+            unpack8(raw[u], a);
+            float l0 = 0.f, l1 = 0.f;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                l0 = fmaf(a[i], w0[i], l0);
+                l1 = fmaf(a[i], w1[i], l1);
+            }
+            for (int o = 1; o < LP; o <<= 1) {
+                l0 += __shfl_xor(l0, o);
+                l1 += __shfl_xor(l1, o);
+            }
+            l0 += b0;
+            l1 += b1;
+            const float m = fmaxf(l0, l1);
+            const float e0 = expf(l0 - m), e1 = expf(l1 - m);
+            const float s = e0 + e1;
+            const float p1 = e1 / s;
+            if (!okk[u] || sub != 0) continue;
+            prob[pp[u]] = p1;
+            const int64_t lab = labv[u];
+            if (lab != 0 && lab != 1) continue;   // ignored: no loss, no weight, no mass, no count, whatever its pixel_w holds
+            {
+                // The compiler contracts k_head_w's `lsum += omega * -(...)` and k_head_dice_sums's `sp += mp`, `si += mp` into one fused
+                // multiply-add each and adds a ROUNDED omega to osum. Left to itself here, with five sums side by side, it chose otherwise
+                // (lsum and osum as a packed add behind a rounded product, or omega's product fused into osum): one ulp apart on a block's
+                // sum. So nothing in this block is contracted and the siblings' fused forms are written out: the bits are theirs.
+#pragma clang fp contract(off)
+                const float omega = (lab ? cw1 : cw0) * pwv[u];
+                lsum = fmaf(-((lab ? l1 : l0) - m - logf(s)), omega, lsum);
+                osum += omega;
+                sp = fmaf(pwv[u], p1, sp);
+                if (lab) {
+                    si = fmaf(pwv[u], p1, si);
+                    sy += pwv[u];
+                }
+            }
+            // p1 is in [0, 1] (or NaN from non-finite logits, which converts to 0): the clamp keeps the index inside the array regardless
+            const int bin = max(0, min(EW_EVAL_BINS - 1, (int)(p1 * (float)EW_EVAL_BINS)));
+            atomicAdd(&hist[(int)lab * EW_EVAL_BINS + bin], 1u);
+        }
+    }
+    // block reduce: the threads with sub == 0 hold the sums, added in the order of k_head_w's scalar outputs
+    __shared__ float red[256 * 5];
+    red[threadIdx.x * 5] = lsum;
+    red[threadIdx.x * 5 + 1] = osum;
+    red[threadIdx.x * 5 + 2] = si;
+    red[threadIdx.x * 5 + 3] = sp;
+    red[threadIdx.x * 5 + 4] = sy;
+    __syncthreads();
+    if (threadIdx.x < 5) {
+        float t = 0.f;
+        for (int q = 0; q < ppb; ++q) t += red[(q * LP) * 5 + threadIdx.x];
+        partial[(long)blockIdx.x * 5 + threadIdx.x] = t;
+    }
+    for (int i = threadIdx.x; i < 2 * EW_EVAL_BINS; i += 256) hpart[(long)blockIdx.x * (2 * EW_EVAL_BINS) + i] = hist[i];
+}
+// Workgroups 0 and 1: one wave per sum, k_head_final's lanes and order; sums[0..4] ACCUMULATE (+=: a validation set sums on the device).
+// Workgroups 2 .. 2 + 8 * EW_EVAL_SLICES - 1: the histogram rows. Workgroup (g, s) owns the 64 bins of group g and the rows
+// bk = 4 s + wave (mod 4 * EW_EVAL_SLICES): a wave reads 256 contiguous bytes per row, the four waves meet in LDS, and 64 lanes add the
+// slice's 64 totals to hist with one vector 64-bit atomic each (512 contiguous bytes; EW_EVAL_SLICES adds per address per call, whatever
+// the input). Integer adds: the result does not depend on their order.
+__global__ void __launch_bounds__(256) k_head_eval_final(const float* __restrict__ partial, const unsigned* __restrict__ hpart,
+                                                         float* __restrict__ sums, unsigned long long* __restrict__ hist, int nblk) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (blockIdx.x < 2) {
+        const int o = blockIdx.x * 4 + wave;
+        if (o >= 5) return;
+        float t = 0.f;
+        for (int bk = lane; bk < nblk; bk += 64) t += partial[(long)bk * 5 + o];
+        for (int m = 32; m > 0; m >>= 1) t += __shfl_xor(t, m);
+        if (lane == 0) sums[o] += t;
+        return;
+    }
+    const int hb = blockIdx.x - 2, g = hb & 7, s = hb >> 3;
+    unsigned long long t = 0ull;
+    for (int bk = 4 * s + wave; bk < nblk; bk += 4 * EW_EVAL_SLICES) t += hpart[(long)bk * (2 * EW_EVAL_BINS) + g * 64 + lane];
+    __shared__ unsigned long long acc[4 * 64];
+    acc[threadIdx.x] = t;
+    __syncthreads();
+    if (wave == 0) {
+        t = acc[lane] + acc[64 + lane] + acc[128 + lane] + acc[192 + lane];
+        if (t) atomicAdd(&hist[g * 64 + lane], t);
+    }
+}
+
 // color_space_adjust gradients from the first conv's scatter buffer (include/rsu.h, rsu_color_adjust_bwd): 12 outputs, each a
 // 9 x Cout sum in a fixed order (lane-strided partials, then an LDS tree): one block of 12 x 64 threads
 __global__ void __launch_bounds__(768) k_color_adjust_bwd(const float* __restrict__ gx, const float* __restrict__ w1, float* __restrict__ dW0,
@@ -1317,6 +1450,16 @@ hipError_t ew_head_dice(const void* act, const float* w, const float* b, const i
     hipLaunchKernelGGL(k_head_dice, dim3(nb), dim3(256), 0, st, (const bf16_t*)act, w, b, labels, class_w, pixel_w, dice_sums, dice_scale, smooth,
                        prob, (bf16_t*)dact, ws, npix, C, inv_count);
     hipLaunchKernelGGL(k_head_final_dice, dim3((2 * C + 4 + 3) / 4), dim3(256), 0, st, ws, dw, db, loss_sum, weight_sum, nb, C);
+    return hipGetLastError();
+}
+size_t ew_head_eval_ws_floats(long npix, int C) { return (size_t)ew_head_blocks(npix, C) * (5 + 2 * EW_EVAL_BINS); }
+hipError_t ew_head_eval(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w, const float* pixel_w,
+                        float* prob, float* sums, unsigned long long* hist, float* ws, long npix, int C, hipStream_t st) {
+    static_assert(2 * EW_EVAL_BINS == 8 * 64, "k_head_eval_final cuts the histogram into 8 groups of 64 bins");
+    const int nb = ew_head_blocks(npix, C);
+    unsigned* hpart = (unsigned*)(ws + (size_t)nb * 5);   // [nb][2][EW_EVAL_BINS] behind the [nb][5] partial sums
+    hipLaunchKernelGGL(k_head_eval, dim3(nb), dim3(256), 0, st, (const bf16_t*)act, w, b, labels, class_w, pixel_w, prob, ws, hpart, npix, C);
+    hipLaunchKernelGGL(k_head_eval_final, dim3(2 + 8 * EW_EVAL_SLICES), dim3(256), 0, st, ws, hpart, sums, hist, nb);
     return hipGetLastError();
 }
 hipError_t ew_color_adjust_bwd(const float* gx, const float* w1, float* dW0, float* db0, int Cout, float scale, int accumulate, hipStream_t st) {

@@ -1439,6 +1439,15 @@ extern "C" int rsu_head_fwd_bwd_dice(const void* act, const float* w, const floa
                                npix, C, inv_count, (hipStream_t)stream));
     return RSU_OK;
 }
+static_assert(RSU_EVAL_BINS == EW_EVAL_BINS, "rsu.h and elementwise.h must agree on the histogram's size");
+extern "C" size_t rsu_head_eval_ws_floats(long npix, int C) { return (head_c_ok(C) && npix >= 1) ? ew_head_eval_ws_floats(npix, C) : 0; }
+extern "C" int rsu_head_eval(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w,
+                             const float* pixel_w, float* prob, float* sums, unsigned long long* hist, float* ws, long npix, int C,
+                             rsu_stream_t stream) {
+    if (!act || !w || !b || !labels || !prob || !sums || !hist || !ws || !head_c_ok(C) || npix < 1) return RSU_EINVAL;
+    HIP_CHECK_RET(ew_head_eval(act, w, b, labels, class_w, pixel_w, prob, sums, hist, ws, npix, C, (hipStream_t)stream));
+    return RSU_OK;
+}
 extern "C" int rsu_momentum_step(float* w, float* acc, const float* g, float lr, float mu, float gscale, long n, rsu_stream_t stream) {
     if (!w || !acc || !g || n < 1) return RSU_EINVAL;
     if (((uintptr_t)w | (uintptr_t)acc | (uintptr_t)g) & 15) return RSU_EINVAL;

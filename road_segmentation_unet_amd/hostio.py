@@ -179,3 +179,39 @@ def img_to_label_patches(img, patch_size=IMG_PATCH_SIZE):
     out = np.zeros(lab.shape[0] * patch_size * patch_size, dtype=lab.dtype)
     out[:lab.shape[0]] = lab
     return out.reshape(lab.shape[0], patch_size, patch_size)
+
+
+def split_validation(images, groundtruth, k):
+    """Hold out the LAST k training images, whole: ((train images, train ground truth), (held-out images, held-out ground truth)).
+    Whole images, because the training patches of one image overlap at --stride: a patch held out on its own shares most of its
+    pixels with patches that stay. k == 0 holds out nothing (the second pair is None); k must leave at least one training image."""
+    k, n = int(k), len(images)
+    if len(groundtruth) != n:
+        raise ValueError("%d images but %d ground-truth masks" % (n, len(groundtruth)))
+    if k < 0 or (k > 0 and k >= n):
+        raise ValueError("--validation_images=%d must be >= 0 and leave at least one of the %d training images" % (k, n))
+    if k == 0:
+        return (images, groundtruth), None
+    return (images[:n - k], groundtruth[:n - k]), (images[n - k:], groundtruth[n - k:])
+
+
+def validation_patches(images, groundtruth, input_size, patch_size):
+    """The validation set of held-out images: the images mirror-expanded like the training images (expand_and_rotate at angle 0 is
+    mirror_border by (input_size - patch_size) / 2) but not rotated, tiled WITHOUT overlap (stride = patch_size, extract_patches and
+    its x-outer order). H // patch_size tiles per axis, centred; the H % patch_size border pixels belong to no tile (they still feed
+    the tiles' context). Returns (patches float32 [n, input_size, input_size, 3], labels int64 [n, patch_size, patch_size] binarised
+    at 0.5); label tile k is groundtruth[i, y:y + patch_size, x:x + patch_size] of the tile's own (i, x, y)."""
+    images, groundtruth = np.asarray(images), np.asarray(groundtruth)
+    assert (input_size - patch_size) % 2 == 0 and patch_size <= input_size
+    n, h = images.shape[0], images.shape[1]
+    if groundtruth.shape[:3] != images.shape[:3]:
+        raise ValueError("images %s and ground truth %s differ in shape" % (images.shape[:3], groundtruth.shape[:3]))
+    per_axis = h // patch_size
+    if n < 1 or per_axis < 1:
+        raise ValueError("validation needs at least one image of at least patch_size = %d pixels (got %d of %d)" % (patch_size, n, h))
+    offset, span = (input_size - patch_size) // 2, per_axis * patch_size
+    c0 = (h - span) // 2
+    expanded = mirror_border(images, offset)[:, c0:c0 + span + 2 * offset, c0:c0 + span + 2 * offset]
+    patches = extract_patches(expanded, patch_size=input_size, predict_patch_size=patch_size, stride=patch_size)
+    labels = extract_patches(groundtruth[:, c0:c0 + span, c0:c0 + span], patch_size=patch_size, stride=patch_size)
+    return patches.astype(np.float32), (labels >= 0.5).astype(np.int64)

@@ -73,6 +73,10 @@ EXTRA_FLAG_DEFS = [
     ("dice_weight", float, 0.0, "lambda >= 0 of a soft-Dice (soft-F1) term: loss = cross-entropy + lambda * (1 - Dice), Dice over each GPU's "
                                 "batch; 0 = off (the reference's loss). Ignored pixels and the weight map enter Dice, class weights do not"),
     ("dice_smooth", float, 1.0, "Smoothing constant s > 0 of Dice = (2 I + s) / (P + Y + s)"),
+    ("validation_images", int, 0, "Hold out the last K training images, whole, as a validation set (0 = off); K must leave at least one "
+                                  "training image, and --class_weights=balanced counts the remaining images only"),
+    ("validate_every", int, 0, "Number of steps between validations on the held-out images; 0 = once at the end of each epoch"),
+    ("save_best", bool, False, "Keep <save_path>/<experiment>-best.chkpt, rewritten whenever the validation F1 improves"),
 ]
 
 
@@ -127,6 +131,62 @@ def dice_from_sums(I, P, Y, smooth):
     return (2.0 * I + smooth) / (P + Y + smooth)
 
 
+def metrics_from_eval(sums, hist, n_pixels, dice_weight=0.0, dice_smooth=1.0, threshold=0.5):
+    """What a validation pass reports, from the accumulators of rsu.h rsu_head_eval read back once (numpy and python floats only).
+    sums = {sum omega CE, sum omega, I, P, Y}; hist [2][256]: per label, the count of pixels whose probability fell into bin
+    min(255, int(p * 256)); n_pixels: the number of real pixels evaluated (padding excluded, ignored pixels included), the training
+    loss's divisor. Returns a dict:
+      loss = sums[0] / n_pixels; weighted_mean_loss = sums[0] / sums[1] (0 where sums[1] is 0); dice = dice_from_sums(I, P, Y, dice_smooth)
+      (1 for an empty set); objective = loss + dice_weight * (1 - dice): the training objective over the whole set;
+      tp, fp, fn, tn at `threshold`, which must be a multiple of 1/256 in [0, 1] (ValueError otherwise): a pixel is predicted road iff its
+      bin >= round(threshold * 256), i.e. iff p >= threshold, exactly; accuracy, precision, recall, f1 with summary.StreamingMetrics.values'
+      conventions (0 where a denominator is 0; f1 = 0 where recall or precision is), iou = tp / (tp + fp + fn) (0 where empty);
+      best_threshold, best_f1 over the 255 interior thresholds k / 256, the lowest threshold winning ties; n_pixels, n_counted."""
+    sums = np.asarray(sums, dtype=np.float64).reshape(-1)
+    hist = np.asarray(hist)
+    nbins = hist.shape[-1] if hist.ndim == 2 else 0
+    if sums.size != 5 or hist.ndim != 2 or hist.shape[0] != 2 or nbins < 2:
+        raise ValueError("metrics_from_eval needs sums of 5 values and a histogram [2][bins], not %s and %s" % (sums.shape, hist.shape))
+    hist = hist.astype(np.int64)
+    threshold = float(threshold)
+    k = int(round(threshold * nbins)) if math.isfinite(threshold) else -1
+    if not (0 <= k <= nbins) or k != threshold * nbins:
+        raise ValueError("threshold must be a multiple of 1/%d in [0, 1], not %r: the counts come from a %d-bin histogram" % (nbins, threshold, nbins))
+    n_pixels = int(n_pixels)
+    loss = float(sums[0]) / n_pixels if n_pixels > 0 else 0.0
+    dice = float(dice_from_sums(float(sums[2]), float(sums[3]), float(sums[4]), float(dice_smooth)))
+
+    def scores(tp, fp, fn, tn):
+        total = tp + fp + fn + tn
+        accuracy = (tp + tn) / total if total else 0.0
+        recall = tp / (tp + fn) if tp + fn else 0.0
+        precision = tp / (tp + fp) if tp + fp else 0.0
+        f1 = 0.0 if recall == 0.0 or precision == 0.0 else 2.0 / (1.0 / recall + 1.0 / precision)
+        iou = tp / (tp + fp + fn) if tp + fp + fn else 0.0
+        return accuracy, precision, recall, f1, iou
+
+    # above[l][k] = pixels of label l in bins >= k, for k = 0 .. nbins
+    above = np.concatenate([np.cumsum(hist[:, ::-1], axis=1)[:, ::-1], np.zeros((2, 1), np.int64)], axis=1)
+    n0, n1 = int(hist[0].sum()), int(hist[1].sum())
+
+    def counts(kk):
+        tp, fp = int(above[1, kk]), int(above[0, kk])
+        return float(tp), float(fp), float(n1 - tp), float(n0 - fp)
+
+    tp, fp, fn, tn = counts(k)
+    accuracy, precision, recall, f1, iou = scores(tp, fp, fn, tn)
+    best_k, best_f1 = 1, -1.0
+    for kk in range(1, nbins):
+        f = scores(*counts(kk))[3]
+        if f > best_f1:
+            best_k, best_f1 = kk, f
+    return {"loss": loss, "weighted_mean_loss": float(sums[0]) / float(sums[1]) if sums[1] != 0 else 0.0, "dice": dice,
+            "objective": loss + float(dice_weight) * (1.0 - dice), "threshold": threshold,
+            "tp": int(tp), "fp": int(fp), "fn": int(fn), "tn": int(tn),
+            "accuracy": accuracy, "precision": precision, "recall": recall, "f1": f1, "iou": iou,
+            "best_threshold": best_k / float(nbins), "best_f1": best_f1, "n_pixels": n_pixels, "n_counted": n0 + n1}
+
+
 def balanced_class_weights(groundtruth):
     """(N / (2 N_0), N / (2 N_1)) over the labels of `groundtruth` binarised at 0.5 (tf_aerial_images.py:220), scikit-learn's "balanced"
     rule: each class carries half of the total weight and the mean weight over the data is 1, so the loss scale and a tuned --lr
@@ -154,6 +214,12 @@ class Options(object):
             raise ValueError("--optimizer must be momentum or adam, not %r" % (self.optimizer,))
         self.class_weights = parse_class_weights(self.class_weights)   # None, (w0, w1) or "balanced" (cli.main resolves it)
         self.dice_weight, self.dice_smooth = parse_dice_weight(self.dice_weight), parse_dice_smooth(self.dice_smooth)
+        for name in ("validation_images", "validate_every"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+                raise ValueError("--%s must be an integer >= 0, not %r" % (name, v))
+            setattr(self, name, int(v))
+        self.save_best = bool(self.save_best)
         ra = self.rotation_angles
         if isinstance(ra, str):
             self.rotation_angles = None if not ra else [int(i) for i in ra.split(",")]
@@ -201,6 +267,7 @@ class ConvolutionalModel:
         # (created by the first train() call, so that prediction-only models leave no log directory behind)
         self._summary = None
         self._pending_scalars = []
+        self.best_val_f1 = None   # the best validation F1 seen by train() (--save_best keeps that model)
         if self.world > 1:
             self._bucketer = GradBucketer(self.net.flat_g, self.net.n_live)
             self._bucketer.extra_streams = list(self.net.wstreams)
@@ -265,6 +332,75 @@ class ConvolutionalModel:
             net.apply_momentum(opts.lr, opts.momentum)
         return loss, net.prob
 
+    # ------------------------------------------------------------------ held-out validation
+    @torch.no_grad()
+    def evaluate(self, patches, labels, weights=None, threshold=0.5):
+        """The training objective and the pixel metrics over a held-out set, forward only: `patches` [N,S,S,3] float, `labels` [N,P,P]
+        (already 0 / 1; any other value ignores its pixel), `weights` an optional weight map [N,P,P] (None: no map). Every rank must call
+        it with the same set. The set is sharded contiguously over the ranks and run in local_batch chunks -- the last one padded with
+        zero patches whose labels are -1, which the head ignores: the padding adds exactly nothing -- through UNet.forward_device(keep=1)
+        and UNet.evaluate_device (one rsu_head_eval launch per chunk). Everything accumulates on the device; the two accumulators are
+        SUM-all-reduced (the sums as float64) and read back ONCE. Returns metrics_from_eval(...) of them, with the net's dice_weight /
+        dice_smooth, plus "sums" (float64 [5]) and "hist" (int64 [2, 256]).
+        Training is left as it was: weights, optimizer slots, global_step (and with it the dropout keys), the gradient buffers, net.x /
+        net.labels, net.pixel_weights and a batch the uploader has staged; net.prob holds the last chunk's probabilities afterwards."""
+        net, B = self.net, self.local_batch
+        patches, labels = np.asarray(patches), np.asarray(labels)
+        N = int(patches.shape[0])
+        if labels.shape[0] != N or (weights is not None and len(weights) != N):
+            raise ValueError("evaluate: %d patches, %d label tiles%s" % (N, labels.shape[0], "" if weights is None else ", %d weight maps" % len(weights)))
+        metrics_from_eval(np.zeros(5), np.zeros((2, net.eval_hist.shape[1]), np.int64), 0, threshold=threshold)   # a bad threshold fails before any work
+        per = -(-N // self.world)
+        lo, hi = min(self.rank * per, N), min((self.rank + 1) * per, N)
+        net.ensure_tuned(training=False, keep=1.0)   # (an untimed pass of its own kind; under data parallelism no collective is in flight here)
+        x0, l0 = net.x.clone(), net.labels.clone()
+        pw0 = net.pixel_weights.clone() if net.pixel_weights is not None else None
+        try:
+            net.reset_eval()
+            for t0 in range(lo, hi, B):
+                nb = min(B, hi - t0)
+                if nb < B:
+                    net.x.zero_()
+                    net.labels.fill_(-1)
+                net.x[:nb].copy_(torch.as_tensor(np.asarray(patches[t0:t0 + nb], dtype=np.float32)))
+                net.labels[:nb].copy_(torch.as_tensor(np.asarray(labels[t0:t0 + nb])).to(torch.int64))
+                if weights is not None:
+                    wmap = np.ones((B,) + tuple(labels.shape[1:]), dtype=np.float32)
+                    wmap[:nb] = np.asarray(weights[t0:t0 + nb], dtype=np.float32)
+                    net.set_pixel_weights(torch.from_numpy(wmap))
+                else:
+                    net.set_pixel_weights(None)
+                net.forward_device(keep=1.0)
+                net.evaluate_device()
+            sums, hist = net.eval_sums.to(torch.float64), net.eval_hist.clone()
+            if self.world > 1:
+                dist.all_reduce(sums)
+                dist.all_reduce(hist)
+            sums, hist = sums.cpu().numpy(), hist.cpu().numpy()   # the one synchronisation
+        finally:
+            net.x.copy_(x0)
+            net.labels.copy_(l0)
+            net.set_pixel_weights(pw0)
+        out = metrics_from_eval(sums, hist, N * int(np.prod(labels.shape[1:])), net.dice_weight, net.dice_smooth, threshold)
+        out["sums"], out["hist"] = sums, hist
+        return out
+
+    def _validate(self, validation, step):
+        """one validation pass inside train(): evaluate, print and log on rank 0, keep the best model with --save_best"""
+        opts = self._options
+        v = self.evaluate(validation[0], validation[1])
+        if self.rank == 0:
+            print("\nstep {} validation: loss {:.5f} objective {:.5f} dice {:.4f} f1 {:.4f} iou {:.4f} best threshold {:.4f} (f1 {:.4f}) on {} patches"
+                  .format(step, v["loss"], v["objective"], v["dice"], v["f1"], v["iou"], v["best_threshold"], v["best_f1"], len(validation[0])))
+            if self._summary is not None:
+                self._summary.add({"val_loss": v["loss"], "val_objective": v["objective"], "val_dice": v["dice"], "val_f1": v["f1"],
+                                   "val_iou": v["iou"], "val_best_threshold": v["best_threshold"]}, global_step=step)
+        if self.best_val_f1 is None or v["f1"] > self.best_val_f1:   # (the same numbers on every rank: they come out of the all-reduce)
+            self.best_val_f1 = v["f1"]
+            if opts.save_best:
+                self.save_as(os.path.abspath(os.path.join(opts.save_path, self.experiment_name + "-best.chkpt")))
+        return {k: v[k] for k in v if k not in ("sums", "hist")}
+
     def _ensure_summary(self):
         opts = self._options
         if self._summary is None and self.rank == 0 and getattr(opts, "logdir", None):
@@ -285,12 +421,17 @@ class ConvolutionalModel:
                 self._summary.add_to_pixel_missclassification_summary(float(err_t), total, step)
         self._pending_scalars = []
 
-    def train(self, patches, labels_patches, imgs, labels):
+    def train(self, patches, labels_patches, imgs, labels, validation=None):
         """Train the model for one epoch (tf_aerial_images.py:212-269): binarise labels at 0.5, shuffle with np.random,
         `for offset in range(0, N - batch_size, batch_size)` (the final batch is dropped even when full).
         `patches` is the reference's [N,S,S,3] array (then `labels_patches` its [N,P,P] labels) or a pool.PatchPool /
-        pool.DevicePatchPool holding the same patches as an index (then `labels_patches` is ignored)."""
+        pool.DevicePatchPool holding the same patches as an index (then `labels_patches` is ignored).
+        validation: None (the default: the epoch issues exactly the launches it always did) or a held-out (patches [n,S,S,3], labels
+        [n,P,P] in {0,1}) pair (hostio.validation_patches): evaluate() runs on it every --validate_every steps, or once at the end of the
+        epoch with --validate_every=0; rank 0 prints one line and logs val_loss, val_objective, val_dice, val_f1, val_iou and
+        val_best_threshold; last_epoch_stats gains "validation" (the last pass's metrics); --save_best keeps the best model by val_f1."""
         opts, net = self._options, self.net
+        val_stats = None
         self._ensure_summary()
         pool = patches if isinstance(patches, PatchPool) else None
         if pool is None:
@@ -348,10 +489,16 @@ class ConvolutionalModel:
                 train_masks = self.predict(np.asarray(imgs))  # tf_aerial_images.py:266-267
                 if self._summary is not None:
                     self._summary.add_to_training_summary(train_masks, labels, step)
+            if validation is not None and opts.validate_every > 0 and step > 0 and step % opts.validate_every == 0:
+                val_stats = self._validate(validation, step)
+        if validation is not None and opts.validate_every == 0:
+            val_stats = self._validate(validation, net.global_step)
         if self._summary is not None:
             self._flush_scalars()
             self._summary.flush()
         self.last_epoch_stats = {"loss": None if last is None else float(last), "soft_errors": float(num_errors), "patches": total}
+        if val_stats is not None:
+            self.last_epoch_stats["validation"] = val_stats
         return self.last_epoch_stats
 
     # ------------------------------------------------------------------ inference

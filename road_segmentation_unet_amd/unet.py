@@ -350,6 +350,10 @@ class UNet:
         # {I, P, Y} of the soft-Dice term: overwritten by the first of the Dice head's two launches, read by the second (rsu.h
         # rsu_head_dice_sums); all zero (D = 1) until a pass with dice_scale > 0 has run
         self.dice_sums = torch.zeros(3, dtype=torch.float32, device=dev)
+        # accumulators of held-out validation (rsu.h rsu_head_eval; evaluate_device adds to them, reset_eval zeroes them): the sums
+        # {sum omega CE, sum omega, I, P, Y} and the per-class histogram of the probabilities. Not part of state_dict
+        self.eval_sums = torch.zeros(5, dtype=torch.float32, device=dev)
+        self.eval_hist = torch.zeros((2, _lib.EVAL_BINS), dtype=torch.int64, device=dev)
         # workspace of the conv launches that cut their reduction into slices (rsu.h rsu_conv2d_fwd_k: the deep levels at small batches);
         # one per stream that issues conv launches -- the main stream, and the side stream of the dilated twin blocks in the forward pass
         nk = int(_lib.lib().rsu_conv_splitk_ws_floats()) if os.environ.get("RSU_KSPLIT", "1") != "0" else 0
@@ -368,7 +372,7 @@ class UNet:
                     self.grad["skipd_%d" % i] = torch.zeros_like(up)
             lib = _lib.lib()
             ws = [lib.rsu_head_ws_floats(B * self.P * self.P, self.root), lib.rsu_head_w_ws_floats(B * self.P * self.P, self.root),
-                  lib.rsu_head_dice_ws_floats(B * self.P * self.P, self.root),
+                  lib.rsu_head_dice_ws_floats(B * self.P * self.P, self.root), lib.rsu_head_eval_ws_floats(B * self.P * self.P, self.root),
                   lib.rsu_conv_first_bwd_ws_floats(self.root)]
             for kind, n, s, segs in self._packed_kernels():   # (the dead level L-1 dilated pair has the shapes of the level's live block)
                 if kind == _PACK_CONV_FWD:
@@ -597,6 +601,29 @@ class UNet:
             add(lambda net=net: call("rsu_head_fwd", _ptr(net), _ptr(self.w["weight_output/kernel"]), _ptr(self.w["weight_output/bias"]), _ptr(prob),
                                      _ptr(logits) if want_logits else None, nb * self.P * self.P, self.root, self._stream()))
         return steps
+
+    # ------------------------------------------------------------------ held-out validation
+    def reset_eval(self):
+        """zero the validation accumulators eval_sums / eval_hist (on the current stream)"""
+        self.eval_sums.zero_()
+        self.eval_hist.zero_()
+
+    def evaluate_device(self):
+        """The forward-only loss and metric counts of self.x / self.labels, for data the optimizer does not see: ONE rsu_head_eval launch
+        (rsu.h) behind a forward_device(keep=1.0) of a training net, which itself runs no head. It fills self.prob and ADDS to
+        eval_sums (f32[5]) += {sum omega CE, sum omega, I, P, Y} -- omega and the sums as backward_device defines them, with this net's
+        class weights and weight map -- and to eval_hist (int64 [2, 256]): hist[label][min(255, int(p * 256))] += 1 for every pixel whose
+        label is 0 or 1; any other label ignores its pixel. No gradient buffer, loss_sum, weight_sum or dice_sums is written, and nothing
+        is read back: a caller sums a whole set on the device (reset_eval first) and synchronises once. ensure_tuned(training=False)
+        belongs in front of the first such forward pass: at keep == 1 the encoder takes the fused conv + pool launches, whose tuning
+        keys differ from a dropout step's."""
+        if not self.training:
+            raise _lib.RsuError("evaluate_device needs a training net (labels and the head's workspace); a forward-only net has no loss")
+        if self.keep != 1.0:
+            raise _lib.RsuError("evaluate_device follows forward_device(keep=1.0): the activations in flight were made with dropout")
+        call("rsu_head_eval", _ptr(self.act[self.last_name]), _ptr(self.w["weight_output/kernel"]), _ptr(self.w["weight_output/bias"]),
+             _ptr(self.labels), _ptr(self._class_w_dev), _ptr(self.pixel_weights), _ptr(self.prob), _ptr(self.eval_sums), _ptr(self.eval_hist),
+             _ptr(self.ws), self.B * self.P * self.P, self.root, self._stream())
 
     # ------------------------------------------------------------------ backward
     def _wgrad(self, name, srcs_t, dz, hout, dil=1, block_done=False):
