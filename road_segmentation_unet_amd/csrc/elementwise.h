@@ -34,15 +34,14 @@ hipError_t ew_reduce_slabs_many(const ReduceJob* jobs_dev, int njobs, int total_
 int ew_head_blocks(long npix, int C);
 hipError_t ew_head(bool train, const void* act, const float* w, const float* b, const int64_t* labels, float* prob, float* logits, void* dact, float* dw,
                    float* db, float* loss_sum, float* ws, long npix, int C, float inv_count, hipStream_t st);
-// the weighted training head (rsu.h rsu_head_fwd_bwd_w): same grid, ws of ew_head_blocks() * (2 C + 4) floats
-hipError_t ew_head_w(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w, const float* pixel_w, float* prob,
-                     void* dact, float* dw, float* db, float* loss_sum, float* weight_sum, float* ws, long npix, int C, float inv_count, hipStream_t st);
-// the soft-Dice head (rsu.h rsu_head_dice_sums, rsu_head_fwd_bwd_dice): same grid; ws of ew_head_blocks() * 3 / * (2 C + 4) floats
-hipError_t ew_head_dice_sums(const void* act, const float* w, const float* b, const int64_t* labels, const float* pixel_w, float* prob,
-                             float* dice_sums, float* ws, long npix, int C, hipStream_t st);
-hipError_t ew_head_dice(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w, const float* pixel_w,
+// the weighted training head and pass B of the soft-Dice head (rsu.h rsu_head_fwd_bwd_w, rsu_head_fwd_bwd_dice): same grid, ws of
+// ew_head_blocks() * (2 C + 4) floats; dice_sums == nullptr: no Dice term (dice_scale and smooth are not read)
+hipError_t ew_head_loss(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w, const float* pixel_w,
                         const float* dice_sums, float dice_scale, float smooth, float* prob, void* dact, float* dw, float* db, float* loss_sum,
                         float* weight_sum, float* ws, long npix, int C, float inv_count, hipStream_t st);
+// pass A of the soft-Dice head (rsu.h rsu_head_dice_sums): same grid, ws of ew_head_blocks() * 3 floats
+hipError_t ew_head_dice_sums(const void* act, const float* w, const float* b, const int64_t* labels, const float* pixel_w, float* prob,
+                             float* dice_sums, float* ws, long npix, int C, hipStream_t st);
 // the evaluation head (rsu.h rsu_head_eval): same grid, forward only; ws of ew_head_eval_ws_floats() floats (5 partial sums and one
 // 2 x EW_EVAL_BINS row of u32 counters per workgroup). EW_EVAL_BINS is rsu.h's RSU_EVAL_BINS.
 constexpr int EW_EVAL_BINS = 256;

@@ -2,6 +2,8 @@
 // the channel axis of NHWC; wave-level shuffles for the per-pixel reductions of the head.
 #include "elementwise.h"
 
+#include <type_traits>
+
 static __device__ __forceinline__ void unpack8(const u32x4 v, float* f) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -417,6 +419,12 @@ __global__ void __launch_bounds__(256) k_reduce_slabs_many(const ReduceJob* __re
 // ---------------------------------------------------------------------------------------------
 // head: 1x1 conv (C -> 2) + softmax[...,1] (+ mean CE loss and its backward)
 // LP = C/8 lanes per pixel, partial logits reduced with wave shuffles
+// Two sets of kernels. k_head<TRAIN> and k_head_final are PINNED: the unweighted step is on the critical queue, and sharing k_head's body
+// through an inlined function template moved its register allocation (1500 of 1585 ISA lines), so they are written out and nothing
+// below is shared with them. The opt-in heads form one family built from the head_* device helpers below (per-thread setup, the batched
+// load, logits + softmax, the LDS block reduce, the final kernels' sum): k_head_loss<DICE> (weighted training head / pass B of the
+// soft-Dice head) with k_head_final_loss, and the forward-only k_head_sums<EVAL> (pass A of the soft-Dice head / the evaluation head)
+// with k_head_final_dice_sums and k_head_eval_final. Their grid, pixel-to-thread mapping and the order of every sum are k_head<true>'s.
 // ---------------------------------------------------------------------------------------------
 template <bool TRAIN>
 __global__ void __launch_bounds__(256) k_head(const bf16_t* __restrict__ act, const float* __restrict__ w, const float* __restrict__ b,
@@ -550,233 +558,86 @@ __global__ void __launch_bounds__(256) k_head_final(const float* __restrict__ pa
     }
 }
 
-// The weighted training head (rsu.h rsu_head_fwd_bwd_w): k_head<true> with omega = class_w[label] * pixel_w[pixel] in front of the pixel's
-// loss and dlogits. A label that is neither 0 nor 1 (tested on all 64 bits) means omega = 0 BY SELECTION, never by multiplication: the
-// pixel's dact row is stored as +0 and it is left out of every sum, whatever its pixel_w holds. One more per-thread sum (omega ->
-// weight_sum) rides through the block reduce: 2 C + 4 partials per block. Grid, pixel-to-thread mapping and the order of every sum are
-// k_head<true>'s, and x * 1.0f is exact: with every omega == 1 the outputs have its bits (tests/test_gpu_weighted_loss.py).
-// A sibling kernel, not a template argument of k_head or a shared inlined body: the unweighted step is on the critical queue and its
-// code is pinned -- sharing the body through an inlined function template moved its register allocation (1500 of 1585 ISA lines).
-// 4 waves per SIMD asked for (<= 128 VGPRs, k_head<true>'s occupancy): the 64-bit labels and the weights in flight cost 131 without.
-__global__ void __launch_bounds__(256, 4) k_head_w(const bf16_t* __restrict__ act, const float* __restrict__ w, const float* __restrict__ b,
-                                                const int64_t* __restrict__ labels, const float* __restrict__ class_w,
-                                                const float* __restrict__ pixel_w, float* __restrict__ prob, bf16_t* __restrict__ dact,
-                                                float* __restrict__ partial, long npix, int C, float inv_count) {
-    const int LP = C >> 3;
-    const int sub = threadIdx.x % LP;
-    const int ppb = 256 / LP;  // pixels per block iteration
-    float w0[8], w1[8];
+// ---- the opt-in family: stages shared by k_head_loss<DICE> and k_head_sums<EVAL> (see the head of this section) ----
+// per-thread setup: the thread's 8 channels of both weight columns and the two biases
+static __device__ __forceinline__ void head_setup(const float* __restrict__ w, const float* __restrict__ b, int sub, float (&w0)[8], float (&w1)[8],
+                                                  float& b0, float& b1) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         w0[i] = w[(sub * 8 + i) * 2];
         w1[i] = w[(sub * 8 + i) * 2 + 1];
     }
-    const float b0 = b[0], b1 = b[1];
-    const float cw0 = class_w ? class_w[0] : 1.f, cw1 = class_w ? class_w[1] : 1.f;
-    float gw0[8], gw1[8], gb0 = 0.f, gb1 = 0.f, lsum = 0.f, osum = 0.f;
+    b0 = b[0];
+    b1 = b[1];
+}
+// HU pixels per thread and trip as in k_head; the pixel's 64-bit label and its weight are requested with its activations, before any is used
+constexpr int HEAD_HU = 4;
+template <typename IT>
+static __device__ __forceinline__ void head_load(const bf16_t* __restrict__ act, const int64_t* __restrict__ labels, const float* __restrict__ pixel_w,
+                                                 IT it0, IT niter, long npix, int C, int LP, int sub, int ppb, long (&pp)[HEAD_HU],
+                                                 bool (&okk)[HEAD_HU], u32x4 (&raw)[HEAD_HU], int64_t (&labv)[HEAD_HU], float (&pwv)[HEAD_HU]) {
 #pragma unroll
-    for (int i = 0; i < 8; ++i) gw0[i] = gw1[i] = 0.f;
-    const long niter = (npix + (long)gridDim.x * ppb - 1) / ((long)gridDim.x * ppb);
-    // HU pixels per thread and trip as in k_head; the pixel's weight is requested with its activations and label, before any is used
-    constexpr int HU = 4;
-    for (long it0 = 0; it0 < niter; it0 += HU) {
-        long pp[HU];
-        bool okk[HU];
-        u32x4 raw[HU];
-        int64_t labv[HU];
-        float pwv[HU];
-#pragma unroll
-        for (int u = 0; u < HU; ++u) {
-            pp[u] = ((it0 + u) * gridDim.x + blockIdx.x) * ppb + threadIdx.x / LP;
-            okk[u] = (it0 + u < niter) && pp[u] < npix;
-            raw[u] = okk[u] ? *(const u32x4*)(act + pp[u] * C + sub * 8) : u32x4{0u, 0u, 0u, 0u};
-            labv[u] = okk[u] ? labels[pp[u]] : 0;
-            pwv[u] = (okk[u] && pixel_w) ? pixel_w[pp[u]] : 1.f;
-        }
-#pragma unroll
-        for (int u = 0; u < HU; ++u) {
-            const long p = pp[u];
-            const bool ok = okk[u];
-            float a[8];
-            unpack8(raw[u], a);
-            float l0 = 0.f, l1 = 0.f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                l0 = fmaf(a[i], w0[i], l0);
-                l1 = fmaf(a[i], w1[i], l1);
-            }
-            for (int o = 1; o < LP; o <<= 1) {
-                l0 += __shfl_xor(l0, o);
-                l1 += __shfl_xor(l1, o);
-            }
-            l0 += b0;
-            l1 += b1;
-            const float m = fmaxf(l0, l1);
-            const float e0 = expf(l0 - m), e1 = expf(l1 - m);
-            const float s = e0 + e1;
-            const float p1 = e1 / s, p0 = e0 / s;
-            if (ok && sub == 0) prob[p] = p1;
-            if (!ok) continue;
-            const int64_t lab = labv[u];
-            if (lab != 0 && lab != 1) {   // ignored
-                *(u32x4*)(dact + p * C + sub * 8) = u32x4{0u, 0u, 0u, 0u};
-                continue;
-            }
-            const float omega = (lab ? cw1 : cw0) * pwv[u];
-            const float d0 = (p0 - (lab == 0 ? 1.f : 0.f)) * inv_count * omega;
-            const float d1 = (p1 - (lab == 1 ? 1.f : 0.f)) * inv_count * omega;
-            float da[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                gw0[i] = fmaf(a[i], d0, gw0[i]);
-                gw1[i] = fmaf(a[i], d1, gw1[i]);
-                da[i] = a[i] > 0.f ? fmaf(d0, w0[i], d1 * w1[i]) : 0.f;
-            }
-            *(u32x4*)(dact + p * C + sub * 8) = pack8(da);
-            if (sub == 0) {
-                gb0 += d0;
-                gb1 += d1;
-                lsum += omega * -((lab ? l1 : l0) - m - logf(s));
-                osum += omega;
-            }
-        }
-    }
-    // block reduce as in k_head, one more value per thread (21 floats: an odd stride keeps the threads' rows on different LDS banks)
-    constexpr int NV = 21;
-    __shared__ float red[256 * NV];
-    float* my = red + threadIdx.x * NV;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        my[i] = gw0[i];
-        my[8 + i] = gw1[i];
-    }
-    my[16] = gb0; my[17] = gb1; my[18] = lsum; my[19] = osum;
-    __syncthreads();
-    const int nout = 2 * C + 4;  // [C][2] dw, db[2], loss, weight sum
-    for (int o = threadIdx.x; o < nout; o += 256) {
-        float t = 0.f;
-        if (o < 2 * C) {
-            const int c = o >> 1, k = o & 1, sg = c >> 3, i = c & 7;
-            for (int q = 0; q < ppb; ++q) t += red[(q * LP + sg) * NV + k * 8 + i];
-        } else {
-            const int j = 16 + (o - 2 * C);
-            for (int q = 0; q < ppb; ++q) t += red[(q * LP) * NV + j];
-        }
-        partial[(long)blockIdx.x * nout + o] = t;
+    for (int u = 0; u < HEAD_HU; ++u) {
+        pp[u] = ((long)(it0 + u) * gridDim.x + blockIdx.x) * ppb + threadIdx.x / LP;
+        okk[u] = (it0 + u < niter) && pp[u] < npix;
+        raw[u] = okk[u] ? *(const u32x4*)(act + pp[u] * C + sub * 8) : u32x4{0u, 0u, 0u, 0u};
+        labv[u] = okk[u] ? labels[pp[u]] : 0;
+        pwv[u] = (okk[u] && pixel_w) ? pixel_w[pp[u]] : 1.f;
     }
 }
-// k_head_final over 2 C + 4 outputs: the last one is the sum of the weights (weight_sum may be NULL: not wanted). Same lanes, same order.
-__global__ void __launch_bounds__(256) k_head_final_w(const float* __restrict__ partial, float* __restrict__ dw, float* __restrict__ db,
-                                                      float* __restrict__ loss_sum, float* __restrict__ weight_sum, int nblk, int C) {
-    const int nout = 2 * C + 4;
-    const int o = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (o >= nout) return;
+// logits (partial dot products met with wave shuffles) and the two-way softmax: k_head's expressions, so prob gets its bits
+static __device__ __forceinline__ void head_softmax(const u32x4 raw, const float (&w0)[8], const float (&w1)[8], float b0, float b1, int LP,
+                                                    float (&a)[8], float& l0, float& l1, float& m, float& s, float& p0, float& p1) {
+    unpack8(raw, a);
+    l0 = 0.f;
+    l1 = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        l0 = fmaf(a[i], w0[i], l0);
+        l1 = fmaf(a[i], w1[i], l1);
+    }
+    for (int o = 1; o < LP; o <<= 1) {
+        l0 += __shfl_xor(l0, o);
+        l1 += __shfl_xor(l1, o);
+    }
+    l0 += b0;
+    l1 += b1;
+    m = fmaxf(l0, l1);
+    const float e0 = expf(l0 - m), e1 = expf(l1 - m);
+    s = e0 + e1;
+    p1 = e1 / s;
+    p0 = e0 / s;
+}
+// block reduce over rows of NV floats, one row per thread (an odd NV keeps the rows on different LDS banks): value j of the threads that
+// hold channel group sg, in the order of their pixels
+template <int NV>
+static __device__ __forceinline__ float head_block_sum(const float* red, int sg, int j, int ppb, int LP) {
+    float t = 0.f;
+    for (int q = 0; q < ppb; ++q) t += red[(q * LP + sg) * NV + j];
+    return t;
+}
+// k_head_final's sum of output o over the blocks' partials: lane l adds partials l, l + 64, ... (independent loads), then a fixed-order butterfly
+static __device__ __forceinline__ float head_final_sum(const float* __restrict__ partial, int nblk, int nout, int o, int lane) {
     float t = 0.f;
     for (int bk = lane; bk < nblk; bk += 64) t += partial[(long)bk * nout + o];
     for (int m = 32; m > 0; m >>= 1) t += __shfl_xor(t, m);
-    if (lane == 0) {
-        if (o < 2 * C) dw[o] = t;
-        else if (o < 2 * C + 2) db[o - 2 * C] = t;
-        else if (o == 2 * C + 2) loss_sum[0] += t;
-        else if (weight_sum) weight_sum[0] += t;
-    }
+    return t;
 }
 
-// The soft-Dice head (rsu.h rsu_head_dice_sums, rsu_head_fwd_bwd_dice): the Dice gradient of a pixel needs three sums over the whole batch,
-// so the head runs twice. Pass A, k_head_dice_sums: k_head_w's grid, pixel-to-thread mapping, load batching and logit / softmax expressions
-// (prob gets the same bits), no backward; per thread the three sums I = sum m p y, P = sum m p, Y = sum m y with the pixel's mass
-// m = pixel_w (1 without a map), 0 BY SELECTION for a label that is neither 0 nor 1 (all 64 bits). 3 partials per block.
-// Siblings of k_head_w, for its reason: the bodies of the kernels on the critical queue are pinned.
-__global__ void __launch_bounds__(256, 4) k_head_dice_sums(const bf16_t* __restrict__ act, const float* __restrict__ w, const float* __restrict__ b,
-                                                        const int64_t* __restrict__ labels, const float* __restrict__ pixel_w,
-                                                        float* __restrict__ prob, float* __restrict__ partial, long npix, int C) {
-    const int LP = C >> 3;
-    const int sub = threadIdx.x % LP;
-    const int ppb = 256 / LP;  // pixels per block iteration
-    float w0[8], w1[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        w0[i] = w[(sub * 8 + i) * 2];
-        w1[i] = w[(sub * 8 + i) * 2 + 1];
-    }
-    const float b0 = b[0], b1 = b[1];
-    float si = 0.f, sp = 0.f, sy = 0.f;
-    const long niter = (npix + (long)gridDim.x * ppb - 1) / ((long)gridDim.x * ppb);
-    constexpr int HU = 4;
-    for (long it0 = 0; it0 < niter; it0 += HU) {
-        long pp[HU];
-        bool okk[HU];
-        u32x4 raw[HU];
-        int64_t labv[HU];
-        float pwv[HU];
-#pragma unroll
-        for (int u = 0; u < HU; ++u) {
-            pp[u] = ((it0 + u) * gridDim.x + blockIdx.x) * ppb + threadIdx.x / LP;
-            okk[u] = (it0 + u < niter) && pp[u] < npix;
-            raw[u] = okk[u] ? *(const u32x4*)(act + pp[u] * C + sub * 8) : u32x4{0u, 0u, 0u, 0u};
-            labv[u] = okk[u] ? labels[pp[u]] : 0;
-            pwv[u] = (okk[u] && pixel_w) ? pixel_w[pp[u]] : 1.f;
-        }
-#pragma unroll
-        for (int u = 0; u < HU; ++u) {
-            float a[8];
-            unpack8(raw[u], a);
-            float l0 = 0.f, l1 = 0.f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                l0 = fmaf(a[i], w0[i], l0);
-                l1 = fmaf(a[i], w1[i], l1);
-            }
-            for (int o = 1; o < LP; o <<= 1) {
-                l0 += __shfl_xor(l0, o);
-                l1 += __shfl_xor(l1, o);
-            }
-            l0 += b0;
-            l1 += b1;
-            const float m = fmaxf(l0, l1);
-            const float e0 = expf(l0 - m), e1 = expf(l1 - m);
-            const float s = e0 + e1;
-            const float p1 = e1 / s;
-            if (!okk[u] || sub != 0) continue;
-            prob[pp[u]] = p1;
-            const int64_t lab = labv[u];
-            if (lab != 0 && lab != 1) continue;   // ignored: no mass, whatever its pixel_w holds
-            const float mp = pwv[u] * p1;
-            sp += mp;
-            if (lab) {
-                si += mp;
-                sy += pwv[u];
-            }
-        }
-    }
-    // block reduce: the threads with sub == 0 hold the sums, added in the order of k_head_w's scalar outputs
-    __shared__ float red[256 * 3];
-    red[threadIdx.x * 3] = si;
-    red[threadIdx.x * 3 + 1] = sp;
-    red[threadIdx.x * 3 + 2] = sy;
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        float t = 0.f;
-        for (int q = 0; q < ppb; ++q) t += red[(q * LP) * 3 + threadIdx.x];
-        partial[(long)blockIdx.x * 3 + threadIdx.x] = t;
-    }
-}
-// one wave per sum, k_head_final's lanes and order; dice_sums[0..2] = {I, P, Y} is OVERWRITTEN (the caller zeroes nothing)
-__global__ void __launch_bounds__(256) k_head_final_dice_sums(const float* __restrict__ partial, float* __restrict__ dice_sums, int nblk) {
-    const int o = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (o >= 3) return;
-    float t = 0.f;
-    for (int bk = lane; bk < nblk; bk += 64) t += partial[(long)bk * 3 + o];
-    for (int m = 32; m > 0; m >>= 1) t += __shfl_xor(t, m);
-    if (lane == 0) dice_sums[o] = t;
-}
-
-// Pass B, k_head_dice: k_head_w plus, for every counted pixel, the gradient of dice_scale * (1 - D) wrt its logits,
+// The training heads with weights. k_head_loss<false> (rsu.h rsu_head_fwd_bwd_w): k_head<true> with omega = class_w[label] * pixel_w[pixel]
+// in front of the pixel's loss and dlogits. A label that is neither 0 nor 1 (tested on all 64 bits) means omega = 0 BY SELECTION, never by
+// multiplication: the pixel's dact row is stored as +0 and it is left out of every sum, whatever its pixel_w holds. One more per-thread sum
+// (omega -> weight_sum) rides through the block reduce: 2 C + 4 partials per block. Grid, pixel-to-thread mapping and the order of every sum
+// are k_head<true>'s, and x * 1.0f is exact: with every omega == 1 the outputs have its bits (tests/test_gpu_weighted_loss.py).
+// k_head_loss<true> (rsu.h rsu_head_fwd_bwd_dice, pass B of the soft-Dice head) adds, for every counted pixel, the gradient of
+// dice_scale * (1 - D) wrt its logits,
 //   g = dice_scale * m (D - 2 y) / U * p0 p1   added to dlogit 1 and taken from dlogit 0,   U = P + Y + smooth, D = (2 I + smooth) / U,
 // in front of the weight / bias gradients and dact. {I, P, Y} are READ from dice_sums (three uniform loads per thread; what pass A left
 // there, or what a host made of it): nothing is recomputed here. The class weights do not enter g; loss_sum and weight_sum keep their
-// cross-entropy meaning and k_head_w's orders.
-__global__ void __launch_bounds__(256, 4) k_head_dice(const bf16_t* __restrict__ act, const float* __restrict__ w, const float* __restrict__ b,
+// cross-entropy meaning. <false> never touches dice_sums, dice_scale or smooth.
+// 4 waves per SIMD asked for (<= 128 VGPRs, k_head<true>'s occupancy): the 64-bit labels and the weights in flight cost 131 without.
+template <bool DICE>
+__global__ void __launch_bounds__(256, 4) k_head_loss(const bf16_t* __restrict__ act, const float* __restrict__ w, const float* __restrict__ b,
                                                    const int64_t* __restrict__ labels, const float* __restrict__ class_w,
                                                    const float* __restrict__ pixel_w, const float* __restrict__ dice_sums, float dice_scale,
                                                    float smooth, float* __restrict__ prob, bf16_t* __restrict__ dact,
@@ -784,63 +645,39 @@ __global__ void __launch_bounds__(256, 4) k_head_dice(const bf16_t* __restrict__
     const int LP = C >> 3;
     const int sub = threadIdx.x % LP;
     const int ppb = 256 / LP;  // pixels per block iteration
-    float w0[8], w1[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        w0[i] = w[(sub * 8 + i) * 2];
-        w1[i] = w[(sub * 8 + i) * 2 + 1];
-    }
-    const float b0 = b[0], b1 = b[1];
+    float w0[8], w1[8], b0, b1;
+    head_setup(w, b, sub, w0, w1, b0, b1);
     const float cw0 = class_w ? class_w[0] : 1.f, cw1 = class_w ? class_w[1] : 1.f;
-    const float dU = dice_sums[1] + dice_sums[2] + smooth;
-    const float dD = (2.f * dice_sums[0] + smooth) / dU;
-    // dice_scale (D - 2 y) / U for y = 0 and y = 1: the same in every lane, so kept in scalar registers and multiplied in before the label
-    // selects (a select between the two would copy one into a vector register). k_head_w sits at 128 VGPRs, this kernel has none to spare
-    // at 4 waves per SIMD: with the two factors as plain floats and k_head_w's 64-bit trip count it spilled 7 registers to scratch.
-    const float gq0 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(dice_scale * dD / dU)));
-    const float gq1 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(dice_scale * (dD - 2.f) / dU)));
+    float gq0 = 0.f, gq1 = 0.f;
+    if constexpr (DICE) {
+        const float dU = dice_sums[1] + dice_sums[2] + smooth;
+        const float dD = (2.f * dice_sums[0] + smooth) / dU;
+        // dice_scale (D - 2 y) / U for y = 0 and y = 1: the same in every lane, so kept in scalar registers and multiplied in before the
+        // label selects (a select between the two would copy one into a vector register). <false> sits at 128 VGPRs, <true> has none to
+        // spare at 4 waves per SIMD: with the two factors as plain floats and a 64-bit trip count it spilled 7 registers to scratch.
+        gq0 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(dice_scale * dD / dU)));
+        gq1 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(dice_scale * (dD - 2.f) / dU)));
+    }
     float gw0[8], gw1[8], gb0 = 0.f, gb1 = 0.f, lsum = 0.f, osum = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) gw0[i] = gw1[i] = 0.f;
-    // (a 32-bit trip count: at most 8 below 1024 blocks, npix / (1024 ppb) above; two vector registers less than k_head_w's 64-bit one)
-    const int niter = (int)((npix + (long)gridDim.x * ppb - 1) / ((long)gridDim.x * ppb));
-    constexpr int HU = 4;
-    for (int it0 = 0; it0 < niter; it0 += HU) {
-        long pp[HU];
-        bool okk[HU];
-        u32x4 raw[HU];
-        int64_t labv[HU];
-        float pwv[HU];
+    // (<true>: a 32-bit trip count: at most 8 below 1024 blocks, npix / (1024 ppb) above; two vector registers less than the 64-bit one,
+    // which <false> keeps: its code is the one that shipped)
+    using IT = std::conditional_t<DICE, int, long>;
+    const IT niter = (IT)((npix + (long)gridDim.x * ppb - 1) / ((long)gridDim.x * ppb));
+    for (IT it0 = 0; it0 < niter; it0 += HEAD_HU) {
+        long pp[HEAD_HU];
+        bool okk[HEAD_HU];
+        u32x4 raw[HEAD_HU];
+        int64_t labv[HEAD_HU];
+        float pwv[HEAD_HU];
+        head_load<IT>(act, labels, pixel_w, it0, niter, npix, C, LP, sub, ppb, pp, okk, raw, labv, pwv);
 #pragma unroll
-        for (int u = 0; u < HU; ++u) {
-            pp[u] = ((long)(it0 + u) * gridDim.x + blockIdx.x) * ppb + threadIdx.x / LP;
-            okk[u] = (it0 + u < niter) && pp[u] < npix;
-            raw[u] = okk[u] ? *(const u32x4*)(act + pp[u] * C + sub * 8) : u32x4{0u, 0u, 0u, 0u};
-            labv[u] = okk[u] ? labels[pp[u]] : 0;
-            pwv[u] = (okk[u] && pixel_w) ? pixel_w[pp[u]] : 1.f;
-        }
-#pragma unroll
-        for (int u = 0; u < HU; ++u) {
+        for (int u = 0; u < HEAD_HU; ++u) {
             const long p = pp[u];
             const bool ok = okk[u];
-            float a[8];
-            unpack8(raw[u], a);
-            float l0 = 0.f, l1 = 0.f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                l0 = fmaf(a[i], w0[i], l0);
-                l1 = fmaf(a[i], w1[i], l1);
-            }
-            for (int o = 1; o < LP; o <<= 1) {
-                l0 += __shfl_xor(l0, o);
-                l1 += __shfl_xor(l1, o);
-            }
-            l0 += b0;
-            l1 += b1;
-            const float m = fmaxf(l0, l1);
-            const float e0 = expf(l0 - m), e1 = expf(l1 - m);
-            const float s = e0 + e1;
-            const float p1 = e1 / s, p0 = e0 / s;
+            float a[8], l0, l1, m, s, p0, p1;
+            head_softmax(raw[u], w0, w1, b0, b1, LP, a, l0, l1, m, s, p0, p1);
             if (ok && sub == 0) prob[p] = p1;
             if (!ok) continue;
             const int64_t lab = labv[u];
@@ -849,10 +686,15 @@ __global__ void __launch_bounds__(256, 4) k_head_dice(const bf16_t* __restrict__
                 continue;
             }
             const float omega = (lab ? cw1 : cw0) * pwv[u];
-            const float gt = pwv[u] * (p0 * p1);
-            const float g = lab ? gt * gq1 : gt * gq0;
-            const float d0 = (p0 - (lab == 0 ? 1.f : 0.f)) * inv_count * omega - g;
-            const float d1 = (p1 - (lab == 1 ? 1.f : 0.f)) * inv_count * omega + g;
+            float d0 = (p0 - (lab == 0 ? 1.f : 0.f)) * inv_count * omega;
+            float d1 = (p1 - (lab == 1 ? 1.f : 0.f)) * inv_count * omega;
+            if constexpr (DICE) {
+                const float gt = pwv[u] * (p0 * p1);
+                const float g = lab ? gt * gq1 : gt * gq0;
+                d0 -= g;
+                d1 += g;
+            }
+            // the pixel's backward: weight gradients, and dact through the ReLU in front of the head
             float da[8];
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
@@ -869,7 +711,7 @@ __global__ void __launch_bounds__(256, 4) k_head_dice(const bf16_t* __restrict__
             }
         }
     }
-    // block reduce as in k_head_w
+    // block reduce as in k_head, one more value per thread: threads with equal `sub` hold partials for the same 8 channels
     constexpr int NV = 21;
     __shared__ float red[256 * NV];
     float* my = red + threadIdx.x * NV;
@@ -882,26 +724,18 @@ __global__ void __launch_bounds__(256, 4) k_head_dice(const bf16_t* __restrict__
     __syncthreads();
     const int nout = 2 * C + 4;  // [C][2] dw, db[2], loss, weight sum
     for (int o = threadIdx.x; o < nout; o += 256) {
-        float t = 0.f;
-        if (o < 2 * C) {
-            const int c = o >> 1, k = o & 1, sg = c >> 3, i = c & 7;
-            for (int q = 0; q < ppb; ++q) t += red[(q * LP + sg) * NV + k * 8 + i];
-        } else {
-            const int j = 16 + (o - 2 * C);
-            for (int q = 0; q < ppb; ++q) t += red[(q * LP) * NV + j];
-        }
-        partial[(long)blockIdx.x * nout + o] = t;
+        const int c = o >> 1;
+        partial[(long)blockIdx.x * nout + o] = o < 2 * C ? head_block_sum<NV>(red, c >> 3, (o & 1) * 8 + (c & 7), ppb, LP)
+                                                         : head_block_sum<NV>(red, 0, 16 + (o - 2 * C), ppb, LP);
     }
 }
-// k_head_final_w for pass B: same outputs, lanes and order
-__global__ void __launch_bounds__(256) k_head_final_dice(const float* __restrict__ partial, float* __restrict__ dw, float* __restrict__ db,
+// k_head_final over 2 C + 4 outputs: the last one is the sum of the weights (weight_sum may be NULL: not wanted). Same lanes, same order.
+__global__ void __launch_bounds__(256) k_head_final_loss(const float* __restrict__ partial, float* __restrict__ dw, float* __restrict__ db,
                                                          float* __restrict__ loss_sum, float* __restrict__ weight_sum, int nblk, int C) {
     const int nout = 2 * C + 4;
     const int o = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (o >= nout) return;
-    float t = 0.f;
-    for (int bk = lane; bk < nblk; bk += 64) t += partial[(long)bk * nout + o];
-    for (int m = 32; m > 0; m >>= 1) t += __shfl_xor(t, m);
+    const float t = head_final_sum(partial, nblk, nout, o, lane);
     if (lane == 0) {
         if (o < 2 * C) dw[o] = t;
         else if (o < 2 * C + 2) db[o - 2 * C] = t;
@@ -910,109 +744,103 @@ __global__ void __launch_bounds__(256) k_head_final_dice(const float* __restrict
     }
 }
 
-// The evaluation head (rsu.h rsu_head_eval): forward only, for held-out data. k_head_dice_sums's grid, pixel-to-thread mapping, load batching
-// and logit / softmax expressions (prob gets the same bits); per thread the five sums {omega CE, omega, I, P, Y} -- the first two with
-// k_head_w's expressions and order, the last three with k_head_dice_sums's, so from zeroed accumulators they have those kernels' bits -- and,
-// for every counted pixel, one count in the block's LDS histogram hist[label][min(255, (int)(p * 256))]. No dact, no dw, no db.
-// A sibling of k_head_w / k_head_dice_sums, for their reason: the bodies of the kernels on the critical queue are pinned.
+// The forward-only heads: k_head_loss's grid, pixel-to-thread mapping, load batching and logit / softmax expressions (prob gets the same
+// bits); no dact, no dw, no db. Per thread (the sub == 0 lane of a pixel) the sums
+//   I = sum m p y, P = sum m p, Y = sum m y   with the pixel's mass m = pixel_w (1 without a map),
+// and with EVAL in front of them {omega CE, omega} in k_head_loss's expressions and order; everything 0 BY SELECTION for a label that is
+// neither 0 nor 1 (all 64 bits). NS = 3 or 5 partials per block, in the order of k_head_loss's scalar outputs.
+// k_head_sums<false> (rsu.h rsu_head_dice_sums) is pass A of the soft-Dice head: the Dice gradient of a pixel needs {I, P, Y} over the
+// whole batch, so the head runs twice. class_w and hpart are not touched.
+// k_head_sums<true> (rsu.h rsu_head_eval) is the evaluation head for held-out data: it also keeps, for every counted pixel, one count in the
+// block's LDS histogram hist[label][min(255, (int)(p * 256))].
 // The histogram: one LDS counter array per block (2 x 256 u32), bumped by the pixel's sub == 0 lane only -- at most 64 / LP lanes of a
 // wave, so a trained network that sends every pixel to bin 0 or bin 255 costs a wave at most that many serialised LDS adds per pixel
 // trip, next to 64 16-byte HBM loads. Blocks never meet on a global address: each stores its 512 counters as a plain row of the
 // workspace (2 KB per block, 2 MB at 1024 blocks against 77 MB of activations read), and k_head_eval_final sums the rows. 1024 blocks
 // adding to the two hot addresses of a saturated histogram at the same moment is exactly what this avoids.
-__global__ void __launch_bounds__(256, 4) k_head_eval(const bf16_t* __restrict__ act, const float* __restrict__ w, const float* __restrict__ b,
+template <bool EVAL>
+__global__ void __launch_bounds__(256, 4) k_head_sums(const bf16_t* __restrict__ act, const float* __restrict__ w, const float* __restrict__ b,
                                                    const int64_t* __restrict__ labels, const float* __restrict__ class_w,
                                                    const float* __restrict__ pixel_w, float* __restrict__ prob, float* __restrict__ partial,
                                                    unsigned* __restrict__ hpart, long npix, int C) {
+    constexpr int NS = EVAL ? 5 : 3;
     const int LP = C >> 3;
     const int sub = threadIdx.x % LP;
     const int ppb = 256 / LP;  // pixels per block iteration
-    __shared__ unsigned hist[2 * EW_EVAL_BINS];
-    for (int i = threadIdx.x; i < 2 * EW_EVAL_BINS; i += 256) hist[i] = 0u;
-    float w0[8], w1[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        w0[i] = w[(sub * 8 + i) * 2];
-        w1[i] = w[(sub * 8 + i) * 2 + 1];
+    __shared__ unsigned hist[EVAL ? 2 * EW_EVAL_BINS : 1];   // (<false> never names it: no LDS is set aside)
+    if constexpr (EVAL)
+        for (int i = threadIdx.x; i < 2 * EW_EVAL_BINS; i += 256) hist[i] = 0u;
+    float w0[8], w1[8], b0, b1;
+    head_setup(w, b, sub, w0, w1, b0, b1);
+    float cw0 = 1.f, cw1 = 1.f;
+    if constexpr (EVAL) {
+        cw0 = class_w ? class_w[0] : 1.f;
+        cw1 = class_w ? class_w[1] : 1.f;
     }
-    const float b0 = b[0], b1 = b[1];
-    const float cw0 = class_w ? class_w[0] : 1.f, cw1 = class_w ? class_w[1] : 1.f;
     float lsum = 0.f, osum = 0.f, si = 0.f, sp = 0.f, sy = 0.f;
-    __syncthreads();
+    if constexpr (EVAL) __syncthreads();
     const long niter = (npix + (long)gridDim.x * ppb - 1) / ((long)gridDim.x * ppb);
-    constexpr int HU = 4;
-    for (long it0 = 0; it0 < niter; it0 += HU) {
-        long pp[HU];
-        bool okk[HU];
-        u32x4 raw[HU];
-        int64_t labv[HU];
-        float pwv[HU];
+    for (long it0 = 0; it0 < niter; it0 += HEAD_HU) {
+        long pp[HEAD_HU];
+        bool okk[HEAD_HU];
+        u32x4 raw[HEAD_HU];
+        int64_t labv[HEAD_HU];
+        float pwv[HEAD_HU];
+        head_load<long>(act, labels, pixel_w, it0, niter, npix, C, LP, sub, ppb, pp, okk, raw, labv, pwv);
 #pragma unroll
-        for (int u = 0; u < HU; ++u) {
-            pp[u] = ((it0 + u) * gridDim.x + blockIdx.x) * ppb + threadIdx.x / LP;
-            okk[u] = (it0 + u < niter) && pp[u] < npix;
-            raw[u] = okk[u] ? *(const u32x4*)(act + pp[u] * C + sub * 8) : u32x4{0u, 0u, 0u, 0u};
-            labv[u] = okk[u] ? labels[pp[u]] : 0;
-            pwv[u] = (okk[u] && pixel_w) ? pixel_w[pp[u]] : 1.f;
-        }
-#pragma unroll
-        for (int u = 0; u < HU; ++u) {
-            float a[8];
-            unpack8(raw[u], a);
-            float l0 = 0.f, l1 = 0.f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                l0 = fmaf(a[i], w0[i], l0);
-                l1 = fmaf(a[i], w1[i], l1);
-            }
-            for (int o = 1; o < LP; o <<= 1) {
-                l0 += __shfl_xor(l0, o);
-                l1 += __shfl_xor(l1, o);
-            }
-            l0 += b0;
-            l1 += b1;
-            const float m = fmaxf(l0, l1);
-            const float e0 = expf(l0 - m), e1 = expf(l1 - m);
-            const float s = e0 + e1;
-            const float p1 = e1 / s;
+        for (int u = 0; u < HEAD_HU; ++u) {
+            float a[8], l0, l1, m, s, p0, p1;
+            head_softmax(raw[u], w0, w1, b0, b1, LP, a, l0, l1, m, s, p0, p1);
             if (!okk[u] || sub != 0) continue;
             prob[pp[u]] = p1;
             const int64_t lab = labv[u];
             if (lab != 0 && lab != 1) continue;   // ignored: no loss, no weight, no mass, no count, whatever its pixel_w holds
             {
-                // The compiler contracts k_head_w's `lsum += omega * -(...)` and k_head_dice_sums's `sp += mp`, `si += mp` into one fused
-                // multiply-add each and adds a ROUNDED omega to osum. Left to itself here, with five sums side by side, it chose otherwise
-                // (lsum and osum as a packed add behind a rounded product, or omega's product fused into osum): one ulp apart on a block's
-                // sum. So nothing in this block is contracted and the siblings' fused forms are written out: the bits are theirs.
+                // Left to itself the compiler contracts k_head_loss's `lsum += omega * -(...)` and, with three sums, `sp += m p`, `si += m p`
+                // into one fused multiply-add each and adds a ROUNDED omega to osum; with five sums side by side it chose otherwise (lsum
+                // and osum as a packed add behind a rounded product, or omega's product fused into osum): one ulp apart on a block's sum.
+                // So nothing in this block is contracted and the fused forms are written out: both instantiations give the same bits, and
+                // <true>'s first two sums are k_head_loss's.
 #pragma clang fp contract(off)
-                const float omega = (lab ? cw1 : cw0) * pwv[u];
-                lsum = fmaf(-((lab ? l1 : l0) - m - logf(s)), omega, lsum);
-                osum += omega;
+                if constexpr (EVAL) {
+                    const float omega = (lab ? cw1 : cw0) * pwv[u];
+                    lsum = fmaf(-((lab ? l1 : l0) - m - logf(s)), omega, lsum);
+                    osum += omega;
+                }
                 sp = fmaf(pwv[u], p1, sp);
                 if (lab) {
                     si = fmaf(pwv[u], p1, si);
                     sy += pwv[u];
                 }
             }
-            // p1 is in [0, 1] (or NaN from non-finite logits, which converts to 0): the clamp keeps the index inside the array regardless
-            const int bin = max(0, min(EW_EVAL_BINS - 1, (int)(p1 * (float)EW_EVAL_BINS)));
-            atomicAdd(&hist[(int)lab * EW_EVAL_BINS + bin], 1u);
+            if constexpr (EVAL) {
+                // p1 is in [0, 1] (or NaN from non-finite logits, which converts to 0): the clamp keeps the index inside the array regardless
+                const int bin = max(0, min(EW_EVAL_BINS - 1, (int)(p1 * (float)EW_EVAL_BINS)));
+                atomicAdd(&hist[(int)lab * EW_EVAL_BINS + bin], 1u);
+            }
         }
     }
-    // block reduce: the threads with sub == 0 hold the sums, added in the order of k_head_w's scalar outputs
-    __shared__ float red[256 * 5];
-    red[threadIdx.x * 5] = lsum;
-    red[threadIdx.x * 5 + 1] = osum;
-    red[threadIdx.x * 5 + 2] = si;
-    red[threadIdx.x * 5 + 3] = sp;
-    red[threadIdx.x * 5 + 4] = sy;
-    __syncthreads();
-    if (threadIdx.x < 5) {
-        float t = 0.f;
-        for (int q = 0; q < ppb; ++q) t += red[(q * LP) * 5 + threadIdx.x];
-        partial[(long)blockIdx.x * 5 + threadIdx.x] = t;
+    // block reduce: the threads with sub == 0 hold the sums
+    __shared__ float red[256 * NS];
+    float* my = red + threadIdx.x * NS;
+    if constexpr (EVAL) {
+        my[0] = lsum;
+        my[1] = osum;
     }
-    for (int i = threadIdx.x; i < 2 * EW_EVAL_BINS; i += 256) hpart[(long)blockIdx.x * (2 * EW_EVAL_BINS) + i] = hist[i];
+    my[NS - 3] = si;
+    my[NS - 2] = sp;
+    my[NS - 1] = sy;
+    __syncthreads();
+    if (threadIdx.x < NS) partial[(long)blockIdx.x * NS + threadIdx.x] = head_block_sum<NS>(red, 0, threadIdx.x, ppb, LP);
+    if constexpr (EVAL)
+        for (int i = threadIdx.x; i < 2 * EW_EVAL_BINS; i += 256) hpart[(long)blockIdx.x * (2 * EW_EVAL_BINS) + i] = hist[i];
+}
+// one wave per sum, k_head_final's lanes and order; dice_sums[0..2] = {I, P, Y} is OVERWRITTEN (the caller zeroes nothing)
+__global__ void __launch_bounds__(256) k_head_final_dice_sums(const float* __restrict__ partial, float* __restrict__ dice_sums, int nblk) {
+    const int o = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (o >= 3) return;
+    const float t = head_final_sum(partial, nblk, 3, o, lane);
+    if (lane == 0) dice_sums[o] = t;
 }
 // Workgroups 0 and 1: one wave per sum, k_head_final's lanes and order; sums[0..4] ACCUMULATE (+=: a validation set sums on the device).
 // Workgroups 2 .. 2 + 8 * EW_EVAL_SLICES - 1: the histogram rows. Workgroup (g, s) owns the 64 bins of group g and the rows
@@ -1025,9 +853,7 @@ __global__ void __launch_bounds__(256) k_head_eval_final(const float* __restrict
     if (blockIdx.x < 2) {
         const int o = blockIdx.x * 4 + wave;
         if (o >= 5) return;
-        float t = 0.f;
-        for (int bk = lane; bk < nblk; bk += 64) t += partial[(long)bk * 5 + o];
-        for (int m = 32; m > 0; m >>= 1) t += __shfl_xor(t, m);
+        const float t = head_final_sum(partial, nblk, 5, o, lane);
         if (lane == 0) sums[o] += t;
         return;
     }
@@ -1428,28 +1254,21 @@ hipError_t ew_head(bool train, const void* act, const float* w, const float* b, 
     }
     return hipGetLastError();
 }
-hipError_t ew_head_w(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w, const float* pixel_w, float* prob,
-                     void* dact, float* dw, float* db, float* loss_sum, float* weight_sum, float* ws, long npix, int C, float inv_count, hipStream_t st) {
+// dice_sums == nullptr: the weighted head alone (k_head_loss<false>); else pass B of the soft-Dice head
+hipError_t ew_head_loss(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w, const float* pixel_w,
+                        const float* dice_sums, float dice_scale, float smooth, float* prob, void* dact, float* dw, float* db, float* loss_sum,
+                        float* weight_sum, float* ws, long npix, int C, float inv_count, hipStream_t st) {
     const int nb = ew_head_blocks(npix, C);
-    hipLaunchKernelGGL(k_head_w, dim3(nb), dim3(256), 0, st, (const bf16_t*)act, w, b, labels, class_w, pixel_w, prob, (bf16_t*)dact, ws, npix, C,
-                       inv_count);
-    hipLaunchKernelGGL(k_head_final_w, dim3((2 * C + 4 + 3) / 4), dim3(256), 0, st, ws, dw, db, loss_sum, weight_sum, nb, C);
+    hipLaunchKernelGGL(dice_sums ? k_head_loss<true> : k_head_loss<false>, dim3(nb), dim3(256), 0, st, (const bf16_t*)act, w, b, labels, class_w,
+                       pixel_w, dice_sums, dice_scale, smooth, prob, (bf16_t*)dact, ws, npix, C, inv_count);
+    hipLaunchKernelGGL(k_head_final_loss, dim3((2 * C + 4 + 3) / 4), dim3(256), 0, st, ws, dw, db, loss_sum, weight_sum, nb, C);
     return hipGetLastError();
 }
 hipError_t ew_head_dice_sums(const void* act, const float* w, const float* b, const int64_t* labels, const float* pixel_w, float* prob,
                              float* dice_sums, float* ws, long npix, int C, hipStream_t st) {
     const int nb = ew_head_blocks(npix, C);
-    hipLaunchKernelGGL(k_head_dice_sums, dim3(nb), dim3(256), 0, st, (const bf16_t*)act, w, b, labels, pixel_w, prob, ws, npix, C);
+    hipLaunchKernelGGL(k_head_sums<false>, dim3(nb), dim3(256), 0, st, (const bf16_t*)act, w, b, labels, nullptr, pixel_w, prob, ws, nullptr, npix, C);
     hipLaunchKernelGGL(k_head_final_dice_sums, dim3(1), dim3(256), 0, st, ws, dice_sums, nb);
-    return hipGetLastError();
-}
-hipError_t ew_head_dice(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w, const float* pixel_w,
-                        const float* dice_sums, float dice_scale, float smooth, float* prob, void* dact, float* dw, float* db, float* loss_sum,
-                        float* weight_sum, float* ws, long npix, int C, float inv_count, hipStream_t st) {
-    const int nb = ew_head_blocks(npix, C);
-    hipLaunchKernelGGL(k_head_dice, dim3(nb), dim3(256), 0, st, (const bf16_t*)act, w, b, labels, class_w, pixel_w, dice_sums, dice_scale, smooth,
-                       prob, (bf16_t*)dact, ws, npix, C, inv_count);
-    hipLaunchKernelGGL(k_head_final_dice, dim3((2 * C + 4 + 3) / 4), dim3(256), 0, st, ws, dw, db, loss_sum, weight_sum, nb, C);
     return hipGetLastError();
 }
 size_t ew_head_eval_ws_floats(long npix, int C) { return (size_t)ew_head_blocks(npix, C) * (5 + 2 * EW_EVAL_BINS); }
@@ -1458,7 +1277,7 @@ hipError_t ew_head_eval(const void* act, const float* w, const float* b, const i
     static_assert(2 * EW_EVAL_BINS == 8 * 64, "k_head_eval_final cuts the histogram into 8 groups of 64 bins");
     const int nb = ew_head_blocks(npix, C);
     unsigned* hpart = (unsigned*)(ws + (size_t)nb * 5);   // [nb][2][EW_EVAL_BINS] behind the [nb][5] partial sums
-    hipLaunchKernelGGL(k_head_eval, dim3(nb), dim3(256), 0, st, (const bf16_t*)act, w, b, labels, class_w, pixel_w, prob, ws, hpart, npix, C);
+    hipLaunchKernelGGL(k_head_sums<true>, dim3(nb), dim3(256), 0, st, (const bf16_t*)act, w, b, labels, class_w, pixel_w, prob, ws, hpart, npix, C);
     hipLaunchKernelGGL(k_head_eval_final, dim3(2 + 8 * EW_EVAL_SLICES), dim3(256), 0, st, ws, hpart, sums, hist, nb);
     return hipGetLastError();
 }

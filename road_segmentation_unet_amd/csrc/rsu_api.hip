@@ -1393,6 +1393,11 @@ extern "C" int rsu_pool_skip_relu_bwd(const void* y_act, const void* dpool, cons
     return rsu_pool_skip_relu_bwd_code(y_act, nullptr, dpool, dskip, dz, N, H, W, C, Hs, Ws, keep, key, stream);
 }
 static bool head_c_ok(int C) { return C >= 8 && C <= 512 && (C % 8) == 0 && ((C / 8) & (C / 8 - 1)) == 0; }
+// what rsu_head_fwd_bwd, _w and _dice all require
+static bool head_train_args_ok(const void* act, const float* w, const float* b, const int64_t* labels, const float* prob, const float* loss_sum,
+                               const void* dact, const float* dw, const float* db, const float* ws, long npix, int C) {
+    return act && w && b && labels && prob && loss_sum && dact && dw && db && ws && head_c_ok(C) && npix >= 1;
+}
 extern "C" int rsu_color_adjust_bwd(const float* gx, const float* w1, float* dW0, float* db0, int Cout, float scale, int accumulate,
                                     rsu_stream_t stream) {
     if (!gx || !w1 || !dW0 || !db0 || Cout < 1 || !(scale > 0.f)) return RSU_EINVAL;
@@ -1409,7 +1414,7 @@ extern "C" int rsu_head_fwd(const void* act, const float* w, const float* b, flo
 extern "C" size_t rsu_head_ws_floats(long npix, int C) { return (size_t)ew_head_blocks(npix, C) * (2 * C + 3); }
 extern "C" int rsu_head_fwd_bwd(const void* act, const float* w, const float* b, const int64_t* labels, float* prob, float* loss_sum,
                                 void* dact, float* dw, float* db, float* ws, long npix, int C, float inv_count, rsu_stream_t stream) {
-    if (!act || !w || !b || !labels || !prob || !loss_sum || !dact || !dw || !db || !ws || !head_c_ok(C) || npix < 1) return RSU_EINVAL;
+    if (!head_train_args_ok(act, w, b, labels, prob, loss_sum, dact, dw, db, ws, npix, C)) return RSU_EINVAL;
     HIP_CHECK_RET(ew_head(true, act, w, b, labels, prob, nullptr, dact, dw, db, loss_sum, ws, npix, C, inv_count, (hipStream_t)stream));
     return RSU_OK;
 }
@@ -1417,9 +1422,9 @@ extern "C" size_t rsu_head_w_ws_floats(long npix, int C) { return (size_t)ew_hea
 extern "C" int rsu_head_fwd_bwd_w(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w,
                                   const float* pixel_w, float* prob, float* loss_sum, float* weight_sum, void* dact, float* dw, float* db,
                                   float* ws, long npix, int C, float inv_count, rsu_stream_t stream) {
-    if (!act || !w || !b || !labels || !prob || !loss_sum || !dact || !dw || !db || !ws || !head_c_ok(C) || npix < 1) return RSU_EINVAL;
-    HIP_CHECK_RET(ew_head_w(act, w, b, labels, class_w, pixel_w, prob, dact, dw, db, loss_sum, weight_sum, ws, npix, C, inv_count,
-                            (hipStream_t)stream));
+    if (!head_train_args_ok(act, w, b, labels, prob, loss_sum, dact, dw, db, ws, npix, C)) return RSU_EINVAL;
+    HIP_CHECK_RET(ew_head_loss(act, w, b, labels, class_w, pixel_w, nullptr, 0.f, 0.f, prob, dact, dw, db, loss_sum, weight_sum, ws, npix, C,
+                               inv_count, (hipStream_t)stream));
     return RSU_OK;
 }
 extern "C" size_t rsu_head_dice_ws_floats(long npix, int C) { return (size_t)ew_head_blocks(npix, C) * (2 * C + 4); }
@@ -1433,9 +1438,9 @@ extern "C" int rsu_head_fwd_bwd_dice(const void* act, const float* w, const floa
                                      const float* pixel_w, const float* dice_sums, float dice_scale, float smooth, float* prob, float* loss_sum,
                                      float* weight_sum, void* dact, float* dw, float* db, float* ws, long npix, int C, float inv_count,
                                      rsu_stream_t stream) {
-    if (!act || !w || !b || !labels || !prob || !loss_sum || !dact || !dw || !db || !ws || !head_c_ok(C) || npix < 1) return RSU_EINVAL;
+    if (!head_train_args_ok(act, w, b, labels, prob, loss_sum, dact, dw, db, ws, npix, C)) return RSU_EINVAL;
     if (!dice_sums || !std::isfinite(smooth) || !(smooth > 0.f) || !std::isfinite(dice_scale) || !(dice_scale >= 0.f)) return RSU_EINVAL;
-    HIP_CHECK_RET(ew_head_dice(act, w, b, labels, class_w, pixel_w, dice_sums, dice_scale, smooth, prob, dact, dw, db, loss_sum, weight_sum, ws,
+    HIP_CHECK_RET(ew_head_loss(act, w, b, labels, class_w, pixel_w, dice_sums, dice_scale, smooth, prob, dact, dw, db, loss_sum, weight_sum, ws,
                                npix, C, inv_count, (hipStream_t)stream));
     return RSU_OK;
 }

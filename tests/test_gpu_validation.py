@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import unet_oracle as U  # noqa: E402
 from tests import hiputil as hu  # noqa: E402
-from tests.test_gpu_dice_loss import NPIX, Ref, _bits, _dev_labels, _inputs, _weight_map, _with_ignored  # noqa: E402
+from tests.head_util import NPIX, Ref, _bits, _dev_labels, _inputs, _weight_map, _with_ignored  # noqa: E402
 from road_segmentation_unet_amd._lib import EVAL_BINS, call, lib  # noqa: E402
 
 RSU_EINVAL = -22   # include/rsu.h

@@ -9,29 +9,10 @@ pytestmark = pytest.mark.gpu
 
 from oracle import unet_oracle as U  # noqa: E402
 from tests import hiputil as hu  # noqa: E402
+from tests.head_util import NETS, NPIX, RSU_EINVAL, _batch, _bits, _inputs, _model, _net, _weight_map  # noqa: E402
+from tests.head_util import _step as head_step  # noqa: E402
 from road_segmentation_unet_amd._lib import RsuError, call, lib  # noqa: E402
 
-RSU_EINVAL = -22   # include/rsu.h
-NPIX = 3 * 37 * 41
-
-
-def _rand(rng, *shape, scale=1.0):
-    return (rng.standard_normal(shape) * scale).astype(np.float32)
-
-
-def _inputs(C):
-    """test_head's inputs"""
-    rng = np.random.RandomState(C)
-    act = hu.q(np.maximum(_rand(rng, NPIX, C), 0))
-    w = _rand(rng, C, 2, scale=0.3)
-    b = _rand(rng, 2, scale=0.1)
-    labels = (rng.rand(NPIX) < 0.2).astype(np.int64)
-    return rng, act, w, b, labels
-
-
-def _bits(t):
-    """the tensor's bits as integers (bit-for-bit comparisons: -0 != +0, NaNs compare by payload)"""
-    return t.contiguous().view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32)
 
 
 class Out:
@@ -79,12 +60,6 @@ def _check_against_reference(o, act, w, b, labels, omega, what):
     hu.assert_bf16_close(hu.host(o.dact), U.relu_bwd(act, rdx), what + " dact")
     hu.assert_f32_close(hu.host(o.dw), rdw, what + " dw")
     hu.assert_f32_close(hu.host(o.db), rdb, what + " db")
-
-
-def _weight_map(rng):
-    pw = (0.25 + rng.rand(NPIX)).astype(np.float32)
-    pw[rng.rand(NPIX) < 0.05] = 0.0
-    return pw
 
 
 # ------------------------------------------------------------------------------------------- the op
@@ -182,25 +157,8 @@ def test_weighted_head_argument_checks():
 
 
 # ------------------------------------------------------------------------------------------- the network
-NETS = [(3, 16, True, 20), (2, 16, False, 20)]
-
-
-def _net(L, root, dilated, P, class_weights=None, B=2):
-    from road_segmentation_unet_amd.unet import UNet
-    return UNet(L, root, dilated, B, P, seed=17, training=True, class_weights=class_weights)
-
-
-def _batch(m, seed=6):
-    gen = torch.Generator(device="cpu").manual_seed(seed)
-    m.x.copy_(torch.rand((m.B, m.S, m.S, 3), generator=gen))
-    m.labels.copy_((torch.rand((m.B, m.P, m.P), generator=gen) < 0.3).to(torch.int64))
-
-
 def _step(m):
-    m.forward_device()
-    m.backward_device(1.0 / (m.B * m.P * m.P))
-    torch.cuda.synchronize()
-    return m.flat_g.clone(), m.prob.clone(), m.loss_sum.clone(), m.weight_sum.clone()
+    return head_step(m)[:4]   # (without the Dice sums)
 
 
 @pytest.mark.parametrize("L,root,dilated,P", NETS)
@@ -278,13 +236,6 @@ def test_net_weighted_step_is_deterministic_and_tune_keeps_the_map(L, root, dila
 
 
 # ------------------------------------------------------------------------------------------- the model
-def _model(**kw):
-    from road_segmentation_unet_amd.model import ConvolutionalModel, Options
-    o = dict(num_layers=3, root_size=16, patch_size=20, batch_size=2, dilated_layers=True, dropout=1.0, lr=0.01, seed=5, logdir=None)
-    o.update(kw)
-    return ConvolutionalModel(Options(**o), device="cuda:0", params=U.init_params(3, 16, True, seed=13, bias_scale=0.05))
-
-
 def test_model_train_step_with_class_weights_and_a_map():
     m = _model(class_weights="1,3")
     assert m.net.class_weights == (1.0, 3.0)
