@@ -232,6 +232,31 @@ size_t rsu_head_eval_ws_floats(long npix, int C);
 int rsu_head_eval(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w, const float* pixel_w,
                   float* prob, float* sums, unsigned long long* hist, float* ws, long npix, int C, rsu_stream_t stream);
 
+/* The border-distance weight map (new): the producer of pixel_w above, the U-Net paper's w0 exp(-(d1 + d2)^2 / (2 sigma^2)) restated for a
+ * two-class semantic mask (no instances: the distance is to the other class; the paper's class-balancing term w_c stays class_w).
+ * For a batch of label tiles labels int64 [N][H][W], per tile n, PATCH-LOCAL (only pixels of the same tile are looked at: a training patch
+ * does not see the ground truth outside its window, so a border just beyond the patch edge is not felt):
+ *   a label is VALID if it is 0 or 1 (all 64 bits tested, as in the heads);
+ *   D2(p) = min (dy^2 + dx^2) over the valid pixels q of the tile with label 1 - l_p, for a valid p: the exact integer squared Euclidean
+ *           distance to the other class (border pixels have D2 = 1); RSU_BORDER_D2_INF where the tile holds no valid pixel of that class;
+ *   border(p) = 1 + w0 exp(-D2(p) / (2 sigma^2)) in float32, exactly 1 where D2 is infinite;
+ *   out[p] = (mul ? mul[p] : 1) * border(p)       mul: an optional caller map f32 [N][H][W] (how a caller's own weight map combines);
+ *   an IGNORED pixel (any other label): out = +0, d2 = RSU_BORDER_D2_INF; it is never anyone's "other class" and its mul is never read
+ *   (selection, not multiplication, as everywhere in the head family).
+ * out f32 [N][H][W]; d2 int32 [N][H][W] or NULL; ws: rsu_border_map_ws_bytes(N, H, W) bytes (0 for a refused size).
+ * Exact separable transform in integer arithmetic (a column pass into ws, a row pass from LDS): d2 is exact and no output depends on the
+ * grid, the wave order or the box; exp is a fixed sequence of float32 operations (no library call), which hostio.border_weight_map
+ * restates: out is reproducible bit for bit on the host. Two launches on `stream`, no host synchronisation, no allocation, no atomics.
+ * Supported: 1 <= H, W <= RSU_BORDER_MAX_SIDE (every patch_size of the training hosts; 388 included), N >= 1. Errors, returned before
+ * anything is launched or written: RSU_EINVAL for a NULL labels, out or ws, N, H or W below 1, H or W above RSU_BORDER_MAX_SIDE (the
+ * row staging; there is no slower path), a w0 that is not finite and >= 0, a sigma that is not finite and > 0; RSU_E2BIG when the label
+ * tensor reaches 2 GiB. */
+#define RSU_BORDER_D2_INF 0x7fffffff
+#define RSU_BORDER_MAX_SIDE 1024
+size_t rsu_border_map_ws_bytes(int N, int H, int W);
+int rsu_border_map(const int64_t* labels, const float* mul, float* out, int32_t* d2 /* may be NULL */, void* ws,
+                   int N, int H, int W, float w0, float sigma, rsu_stream_t stream);
+
 /* ---- 3x3 convolution, MFMA implicit GEMM -------------------------------------------------- */
 /* unet.py:34-39,42-45,88-91: y = relu(conv3x3_valid(concat(srcs), W, dilation) + b).
  * All sources share the window size (Hin, Win); y is bf16 [N][Hin-2d][Win-2d][Cout]. */

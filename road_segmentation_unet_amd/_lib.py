@@ -78,6 +78,8 @@ SIGNATURES = {
     "rsu_head_fwd_bwd_dice": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _f, _vp]),
     "rsu_head_eval_ws_floats": (_sz, [_l, _i]),
     "rsu_head_eval": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _vp]),
+    "rsu_border_map_ws_bytes": (_sz, [_i, _i, _i]),
+    "rsu_border_map": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp]),
     "rsu_conv2d_fwd": (_i, [_PS, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "rsu_conv2d_fwd_pool": (_i, [_PS, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _u, _i, _vp]),
     "rsu_conv2d_bwd_data": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
@@ -144,6 +146,7 @@ def lib():
 
 TUNE_OFF, TUNE_LOOKUP, TUNE_MEASURE = 0, 1, 2   # rsu.h RSU_TUNE_*
 EVAL_BINS = 256   # rsu.h RSU_EVAL_BINS
+BORDER_D2_INF, BORDER_MAX_SIDE = 0x7fffffff, 1024   # rsu.h RSU_BORDER_D2_INF, RSU_BORDER_MAX_SIDE
 E2BIG = -7
 
 

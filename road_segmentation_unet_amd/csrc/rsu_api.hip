@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/rsu.h"
+#include "border_map.h"
 #include "elementwise.h"
 #include "igemm.h"
 
@@ -1451,6 +1452,19 @@ extern "C" int rsu_head_eval(const void* act, const float* w, const float* b, co
                              rsu_stream_t stream) {
     if (!act || !w || !b || !labels || !prob || !sums || !hist || !ws || !head_c_ok(C) || npix < 1) return RSU_EINVAL;
     HIP_CHECK_RET(ew_head_eval(act, w, b, labels, class_w, pixel_w, prob, sums, hist, ws, npix, C, (hipStream_t)stream));
+    return RSU_OK;
+}
+static_assert(RSU_BORDER_MAX_SIDE == BM_MAX_SIDE, "rsu.h and border_map.h must agree on the supported tile size");
+static bool border_size_ok(int N, int H, int W) { return N >= 1 && H >= 1 && W >= 1 && H <= BM_MAX_SIDE && W <= BM_MAX_SIDE; }
+extern "C" size_t rsu_border_map_ws_bytes(int N, int H, int W) { return border_size_ok(N, H, W) ? bm_ws_bytes(N, H, W) : 0; }
+extern "C" int rsu_border_map(const int64_t* labels, const float* mul, float* out, int32_t* d2, void* ws, int N, int H, int W, float w0,
+                              float sigma, rsu_stream_t stream) {
+    if (!labels || !out || !ws || !border_size_ok(N, H, W)) return RSU_EINVAL;
+    if (!std::isfinite(w0) || !(w0 >= 0.f) || !std::isfinite(sigma) || !(sigma > 0.f)) return RSU_EINVAL;
+    if ((long)N * H * W * 8 >= 0x7ffffff0L) return RSU_E2BIG;
+    // -1 / (2 sigma^2), in double and rounded once: the host mirror forms the same float
+    const float neg_inv_2s2 = (float)(-1.0 / (2.0 * (double)sigma * (double)sigma));
+    HIP_CHECK_RET(bm_border_map(labels, mul, out, d2, ws, N, H, W, w0, neg_inv_2s2, (hipStream_t)stream));
     return RSU_OK;
 }
 extern "C" int rsu_momentum_step(float* w, float* acc, const float* g, float lr, float mu, float gscale, long n, rsu_stream_t stream) {

@@ -215,3 +215,78 @@ def validation_patches(images, groundtruth, input_size, patch_size):
     patches = extract_patches(expanded, patch_size=input_size, predict_patch_size=patch_size, stride=patch_size)
     labels = extract_patches(groundtruth[:, c0:c0 + span, c0:c0 + span], patch_size=patch_size, stride=patch_size)
     return patches.astype(np.float32), (labels >= 0.5).astype(np.int64)
+
+
+BORDER_D2_INF = 0x7fffffff   # include/rsu.h RSU_BORDER_D2_INF
+
+
+def _f32_bits(u):
+    return np.array(u, dtype=np.uint32).view(np.float32)[()]
+
+
+def _border_exp(t):
+    """exp(t) for a float32 array t <= 0, by the sequence of float32 operations rsu_border_map's kernel runs (csrc/border_map.hip bm_exp;
+    numpy rounds every float32 operation on its own, as that file is compiled to do): bit for bit the device's values."""
+    t = np.asarray(t, dtype=np.float32)
+    tt = np.maximum(t, np.float32(-87.0))
+    k = np.rint(tt * _f32_bits(0x3fb8aa3b))                      # log2(e)
+    r = tt - k * _f32_bits(0x3f317200)                           # ln2, high part
+    r = r - k * _f32_bits(0x35bfbe8e)                            # ln2, low part
+    p = np.full_like(r, _f32_bits(0x39500d01))                   # 1/5040
+    for c in (_f32_bits(0x3ab60b61), _f32_bits(0x3c088889), _f32_bits(0x3d2aaaab), _f32_bits(0x3e2aaaab), np.float32(0.5),
+              np.float32(1.0), np.float32(1.0)):                 # 1/720, 1/120, 1/24, 1/6, 1/2, 1, 1
+        p = p * r + c
+    scale = ((k.astype(np.int32) + 127) << 23).astype(np.uint32).view(np.float32)
+    return np.where(t < np.float32(-87.0), np.float32(0.0), p * scale).astype(np.float32)
+
+
+def border_weight_map(labels, w0, sigma, mul=None):
+    """The border-distance weight map of the loss, on the host: the CPU statement of include/rsu.h rsu_border_map (what --border_weight
+    computes on the device per batch). labels: integer [N, H, W] (or [H, W]); per tile, PATCH-LOCAL:
+      a label is valid if it is 0 or 1; D2(p) = the exact squared Euclidean distance of a valid pixel to the nearest valid pixel of the
+      other class in its tile (BORDER_D2_INF where the tile has none); border(p) = 1 + w0 exp(-D2(p) / (2 sigma^2)) in float32, exactly 1
+      where D2 is infinite; out = (mul if given else 1) * border for a valid pixel; an ignored pixel (any other label) has out = +0 and
+      d2 = BORDER_D2_INF, is nobody's other class, and its `mul` is never used (it may be NaN).
+    Returns (out float32, d2 int32), shaped like labels. Separable: nearest valid pixel of each class per column (running maxima down and
+    up), then per row min over x' of (x - x')^2 + g(x')^2. The float32 arithmetic is the device kernel's, operation for operation: out
+    equals rsu_border_map's bit for bit."""
+    lab = np.asarray(labels)
+    shape = lab.shape
+    if lab.ndim == 2:
+        lab = lab[None]
+    if lab.ndim != 3 or lab.dtype.kind not in "iu":
+        raise ValueError("border_weight_map: labels must be an integer array [N, H, W] or [H, W], not %s %s" % (lab.dtype, shape))
+    w0f, sf = np.float32(w0), np.float32(sigma)
+    if not (np.isfinite(w0f) and w0f >= 0 and np.isfinite(sf) and sf > 0):
+        raise ValueError("border_weight_map: w0 must be finite and >= 0, sigma finite and > 0 (got %r, %r)" % (w0, sigma))
+    N, H, W = lab.shape
+    big = np.int64(1) << 40
+    ys = np.arange(H, dtype=np.int64)[None, :, None]
+    sq = []   # per class: squared vertical distance to the nearest valid pixel of that class in the column (big where none)
+    for c in (0, 1):
+        m = lab == c
+        above = np.maximum.accumulate(np.where(m, ys, -big), axis=1)                      # the down sweep
+        below = np.minimum.accumulate(np.where(m, ys, big)[:, ::-1], axis=1)[:, ::-1]     # the up sweep
+        g = np.minimum(ys - above, below - ys)
+        sq.append(np.where(g < big // 2, g * g, big))
+    xs = np.arange(W, dtype=np.int64)
+    dx2 = (xs[:, None] - xs[None, :]) ** 2                                                # [x][x']
+    d2 = np.full((N, H, W), BORDER_D2_INF, dtype=np.int64)
+    rows = max(1, (1 << 22) // max(1, W * W))
+    for n in range(N):
+        for y0 in range(0, H, rows):
+            sl = slice(y0, min(H, y0 + rows))
+            for c in (0, 1):   # pixels of class c look at the other class's column distances
+                best = (sq[1 - c][n, sl][:, None, :] + dx2[None]).min(axis=2)
+                d2[n, sl] = np.where((lab[n, sl] == c) & (best < big), best, d2[n, sl])
+    valid = (lab == 0) | (lab == 1)
+    finite = d2 < BORDER_D2_INF
+    c = np.float32(-1.0 / (2.0 * float(sf) * float(sf)))
+    e = _border_exp(np.where(finite, d2, 0).astype(np.float32) * c)
+    border = np.where(finite, np.float32(1.0) + w0f * e, np.float32(1.0)).astype(np.float32)
+    if mul is not None:
+        mulf = np.asarray(mul, dtype=np.float32).reshape(lab.shape)
+        with np.errstate(invalid="ignore"):
+            border = np.where(valid, mulf, np.float32(1.0)) * border
+    out = np.where(valid, border, np.float32(0.0)).astype(np.float32)
+    return out.reshape(shape), d2.astype(np.int32).reshape(shape)

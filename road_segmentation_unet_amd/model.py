@@ -73,6 +73,11 @@ EXTRA_FLAG_DEFS = [
     ("dice_weight", float, 0.0, "lambda >= 0 of a soft-Dice (soft-F1) term: loss = cross-entropy + lambda * (1 - Dice), Dice over each GPU's "
                                 "batch; 0 = off (the reference's loss). Ignored pixels and the weight map enter Dice, class weights do not"),
     ("dice_smooth", float, 1.0, "Smoothing constant s > 0 of Dice = (2 I + s) / (P + Y + s)"),
+    ("border_weight", float, 0.0, "w0 >= 0 of a border-distance weight map computed on the GPU from each batch's labels: a pixel counts "
+                                  "1 + w0 * exp(-d^2 / (2 border_sigma^2)) times in the loss, d its distance to the other class inside its patch; "
+                                  "0 = off (the U-Net paper uses 10). The loss stays normalised by the pixel count and the mean weight is above 1, "
+                                  "so the effective step size rises with w0: retune --lr. It multiplies --class_weights and enters the Dice term"),
+    ("border_sigma", float, 5.0, "Width sigma > 0, in pixels, of the border weight (the U-Net paper uses 5)"),
     ("validation_images", int, 0, "Hold out the last K training images, whole, as a validation set (0 = off); K must leave at least one "
                                   "training image, and --class_weights=balanced counts the remaining images only"),
     ("validate_every", int, 0, "Number of steps between validations on the held-out images; 0 = once at the end of each epoch"),
@@ -122,6 +127,28 @@ def parse_dice_smooth(value):
         v = float("nan")
     if not (math.isfinite(v) and v > 0.0):
         raise ValueError("--dice_smooth must be a finite float > 0, not %r" % (value,))
+    return v
+
+
+def parse_border_weight(value):
+    """The --border_weight value as a float: finite and >= 0 (0.0 = no border map). Anything else raises ValueError."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if not (math.isfinite(v) and v >= 0.0):
+        raise ValueError("--border_weight must be a finite float >= 0, not %r" % (value,))
+    return v
+
+
+def parse_border_sigma(value):
+    """The --border_sigma value as a float: finite and > 0. Anything else raises ValueError."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if not (math.isfinite(v) and v > 0.0):
+        raise ValueError("--border_sigma must be a finite float > 0, not %r" % (value,))
     return v
 
 
@@ -214,6 +241,7 @@ class Options(object):
             raise ValueError("--optimizer must be momentum or adam, not %r" % (self.optimizer,))
         self.class_weights = parse_class_weights(self.class_weights)   # None, (w0, w1) or "balanced" (cli.main resolves it)
         self.dice_weight, self.dice_smooth = parse_dice_weight(self.dice_weight), parse_dice_smooth(self.dice_smooth)
+        self.border_weight, self.border_sigma = parse_border_weight(self.border_weight), parse_border_sigma(self.border_sigma)
         for name in ("validation_images", "validate_every"):
             v = getattr(self, name)
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
@@ -257,7 +285,8 @@ class ConvolutionalModel:
                              "options.class_weights = balanced_class_weights(groundtruth) (cli.main does)")
         self.net = UNet(opts.num_layers, opts.root_size, opts.dilated_layers, self.local_batch, opts.patch_size, device=device,
                         params=params, seed=opts.seed, training=True, optimizer=opts.optimizer, class_weights=opts.class_weights,
-                        dice_weight=opts.dice_weight, dice_smooth=opts.dice_smooth)
+                        dice_weight=opts.dice_weight, dice_smooth=opts.dice_smooth, border_weight=opts.border_weight,
+                        border_sigma=opts.border_sigma)
         self.net.dropout_seed = int(opts.seed) + 7919 * self.rank  # independent masks on every rank's shard
         self._bucketer = None
         self._exchange_tuned = False

@@ -107,13 +107,17 @@ class UNet:
     static in exactly the same way (tf_aerial_images.py:133-138)."""
 
     def __init__(self, num_layers, root_size, dilated_layers, batch_size, patch_size, device="cuda:0", params=None, seed=2017,
-                 training=True, optimizer="momentum", class_weights=None, dice_weight=0.0, dice_smooth=1.0):
+                 training=True, optimizer="momentum", class_weights=None, dice_weight=0.0, dice_smooth=1.0, border_weight=0.0, border_sigma=5.0):
         """optimizer: "momentum" (the reference's MomentumOptimizer: apply_momentum) or "adam" (tf.train.AdamOptimizer: apply_adam; a
         second fp32 slot per variable, flat_v).
         class_weights: None or a pair (w0, w1) of finite floats >= 0, not both 0: the weighted cross-entropy of rsu.h
         rsu_head_fwd_bwd_w (see backward_device). None and (1, 1) are the reference's unweighted loss.
         dice_weight: lambda >= 0 of the soft-Dice term, loss = cross-entropy + lambda (1 - Dice) (rsu.h rsu_head_fwd_bwd_dice); 0.0: no such
-        term, the step issues the launches it always did. dice_smooth: the term's smoothing constant, > 0."""
+        term, the step issues the launches it always did. dice_smooth: the term's smoothing constant, > 0.
+        border_weight: w0 >= 0 of the border-distance weight map (rsu.h rsu_border_map): with w0 > 0 every backward_device and
+        evaluate_device first turns self.labels into the map (1 + w0 exp(-D2 / (2 border_sigma^2)), D2 the squared distance to the other
+        class inside the patch) times the map of set_pixel_weights, if any, and hands it to the head as its pixel weights; 0.0: no
+        buffer, no launch, the passes are what they always were. border_sigma: > 0, in pixels. Training nets only."""
         if optimizer not in OPTIMIZERS:
             raise _lib.RsuError("optimizer must be one of %s, not %r" % ("|".join(OPTIMIZERS), optimizer))
         self.optimizer = optimizer
@@ -128,6 +132,8 @@ class UNet:
         self.class_weights = class_weights   # (a property: validated, mirrored to the device as f32[2])
         self.pixel_weights = None            # the weight map [B, P, P] float32 on the device, or None (set_pixel_weights)
         self.dice_weight, self.dice_smooth = dice_weight, dice_smooth   # (properties: validated)
+        self.border_weight, self.border_sigma = self._border_args(border_weight, border_sigma)
+        self.border_map = None               # the generated weight map [B, P, P] float32 (derived from labels per pass), with border_weight > 0
         self.keep = 1.0        # dropout keep probability of the forward pass in flight (set by forward_device)
         self.dropout_seed = int(seed) if seed is not None else 0
         self.backward_cu_budget = None   # CUs the backward launches may plan for in total (None: the library's default)
@@ -189,6 +195,19 @@ class UNet:
             raise _lib.RsuError("dice_smooth must be a finite float > 0")
         self._dice_smooth = v
 
+    def _border_args(self, w0, sigma):
+        try:
+            w0, sigma = float(w0), float(sigma)
+        except (TypeError, ValueError):
+            w0 = sigma = float("nan")
+        if not (math.isfinite(w0) and w0 >= 0.0 and math.isfinite(sigma) and sigma > 0.0):
+            raise _lib.RsuError("border_weight must be a finite float >= 0 and border_sigma a finite float > 0")
+        if w0 > 0.0 and not self.training:
+            raise _lib.RsuError("a forward-only net has no loss to weight")
+        if w0 > 0.0 and self.P > _lib.BORDER_MAX_SIDE:
+            raise _lib.RsuError("border_weight needs patch_size <= %d (rsu.h rsu_border_map), not %d" % (_lib.BORDER_MAX_SIDE, self.P))
+        return w0, sigma
+
     def set_pixel_weights(self, t):
         """The per-pixel weight map of the loss (backward_device): `t` [B, P, P] (tensor or array, any float type) is copied into the
         device tensor `pixel_weights` (float32, allocated on first use; later calls reuse it, so a captured or queued step keeps reading
@@ -207,8 +226,20 @@ class UNet:
         self.pixel_weights = self._pixel_w_buf
 
     def loss_is_weighted(self):
-        """whether the next backward pass takes the weighted head (rsu_head_fwd_bwd_w): class weights other than (1, 1), or a weight map"""
-        return (self._class_weights is not None and self._class_weights != (1.0, 1.0)) or self.pixel_weights is not None
+        """whether the next backward pass takes the weighted head (rsu_head_fwd_bwd_w): class weights other than (1, 1), a weight map, or
+        the generated border map (border_weight > 0)"""
+        return ((self._class_weights is not None and self._class_weights != (1.0, 1.0)) or self.pixel_weights is not None
+                or self.border_weight > 0.0)
+
+    def _head_pixel_weights(self):
+        """The head's pixel weights for the pass being issued: the caller's map (or None), or -- border_weight > 0 -- the border map of
+        self.labels times it, computed here, on the current stream, in front of the head launch (rsu.h rsu_border_map: two short launches,
+        no synchronisation; measured beside the head in profiles/r07/border_map.txt)."""
+        if self.border_weight <= 0.0:
+            return self.pixel_weights
+        call("rsu_border_map", _ptr(self.labels), _ptr(self.pixel_weights), _ptr(self.border_map), None, _ptr(self._border_ws), self.B, self.P,
+             self.P, self.border_weight, self.border_sigma, self._stream())
+        return self.border_map
 
     @property
     def wstreams(self):
@@ -386,6 +417,9 @@ class UNet:
             # (one workspace per stream that launches weight gradients: their slabs are live at the same time)
             self.sched.ws_side = [self.ws] + [torch.zeros_like(self.ws) for _ in self.wstreams[1:]]
             self.gfirst = torch.zeros((2, 9, 12, self.root), dtype=torch.float32, device=dev)  # gx of conv1 / atrous_conv1 (rsu.h)
+            if self.border_weight > 0.0:   # the generated weight map and the column distances between its two launches (rsu.h rsu_border_map)
+                self.border_map = torch.zeros((B, self.P, self.P), dtype=torch.float32, device=dev)
+                self._border_ws = torch.zeros(int(lib.rsu_border_map_ws_bytes(B, self.P, self.P)) // 4, dtype=torch.int32, device=dev)
             # code bytes of the max-pools (argmax + ReLU bits per pooled element, rsu_maxpool2x2_fwd_code): the gradient junction of a
             # level reads them instead of the level's conv2 activation. RSU_POOL_CODE=0: it reads the activation (same bits)
             if os.environ.get("RSU_POOL_CODE", "1") == "1":
@@ -622,7 +656,7 @@ class UNet:
         if self.keep != 1.0:
             raise _lib.RsuError("evaluate_device follows forward_device(keep=1.0): the activations in flight were made with dropout")
         call("rsu_head_eval", _ptr(self.act[self.last_name]), _ptr(self.w["weight_output/kernel"]), _ptr(self.w["weight_output/bias"]),
-             _ptr(self.labels), _ptr(self._class_w_dev), _ptr(self.pixel_weights), _ptr(self.prob), _ptr(self.eval_sums), _ptr(self.eval_hist),
+             _ptr(self.labels), _ptr(self._class_w_dev), _ptr(self._head_pixel_weights()), _ptr(self.prob), _ptr(self.eval_sums), _ptr(self.eval_hist),
              _ptr(self.ws), self.B * self.P * self.P, self.root, self._stream())
 
     # ------------------------------------------------------------------ backward
@@ -722,16 +756,17 @@ class UNet:
         keep = self.keep
         last = a[self.last_name]
         self._loss_acc.zero_()
+        pixel_w = self._head_pixel_weights()
         if dice_scale > 0.0:
             head = (_ptr(last), _ptr(self.w["weight_output/kernel"]), _ptr(self.w["weight_output/bias"]), _ptr(self.labels))
             npix = B * self.P * self.P
-            call("rsu_head_dice_sums", *head, _ptr(self.pixel_weights), _ptr(self.prob), _ptr(self.dice_sums), _ptr(self.ws), npix, self.root, st)
-            call("rsu_head_fwd_bwd_dice", *head, _ptr(self._class_w_dev), _ptr(self.pixel_weights), _ptr(self.dice_sums), dice_scale,
+            call("rsu_head_dice_sums", *head, _ptr(pixel_w), _ptr(self.prob), _ptr(self.dice_sums), _ptr(self.ws), npix, self.root, st)
+            call("rsu_head_fwd_bwd_dice", *head, _ptr(self._class_w_dev), _ptr(pixel_w), _ptr(self.dice_sums), dice_scale,
                  self._dice_smooth, _ptr(self.prob), _ptr(self.loss_sum), _ptr(self.weight_sum), _ptr(g[self.last_name]),
                  _ptr(self.g["weight_output/kernel"]), _ptr(self.g["weight_output/bias"]), _ptr(self.ws), npix, self.root, inv_count, st)
         elif self.loss_is_weighted():
             call("rsu_head_fwd_bwd_w", _ptr(last), _ptr(self.w["weight_output/kernel"]), _ptr(self.w["weight_output/bias"]), _ptr(self.labels),
-                 _ptr(self._class_w_dev), _ptr(self.pixel_weights), _ptr(self.prob),
+                 _ptr(self._class_w_dev), _ptr(pixel_w), _ptr(self.prob),
                  _ptr(self.loss_sum), _ptr(self.weight_sum), _ptr(g[self.last_name]), _ptr(self.g["weight_output/kernel"]),
                  _ptr(self.g["weight_output/bias"]), _ptr(self.ws), B * self.P * self.P, self.root, inv_count, st)
         else:
