@@ -413,6 +413,46 @@ int rsu_update_table_set_second_slot(void* host_table, int index, float* v);
 int rsu_update_table_run_adam(const void* dev_table, int nentries, int total_blocks, float alpha, float beta1, float beta2,
                               float epsilon, float gscale, rsu_stream_t stream);
 
+/* ---- optimizer: clipping by the global norm, with a guard against a gradient that is not finite (new) -------- */
+/* rsu_grad_norm leaves the squared norm of g[0, n), the clipping factor for max_norm and three counters in a 32-byte STATE RECORD in
+ * device memory; the two _clip update passes below read their scale from that record, so a clipped step needs no host synchronisation.
+ * The record (rsu_clip_state_bytes() == RSU_CLIP_STATE_BYTES; 4-byte aligned; the caller zeroes it ONCE, before the first call):
+ *   float    sumsq           sum of g[i]^2 (below)
+ *   float    norm            (float)sqrt((double)sumsq)
+ *   float    scale           norm > max_norm ? (float)((double)max_norm / (double)norm) : 1.0f; 0.0f when bit 1 of flags is set
+ *   uint32_t flags           bit 0 RSU_CLIP_CLIPPED: norm > max_norm, scale < 1; bit 1 RSU_CLIP_NONFINITE: an element of g is inf or nan, or
+ *                            sumsq is not finite -- an OVERFLOW of the sum of squares included (finite elements near 1e19 and above):
+ *                            such a step cannot be scaled and is skipped like one with a nan. The two bits exclude each other
+ *   uint32_t steps           calls so far
+ *   uint32_t clipped_steps   calls that set bit 0
+ *   uint32_t skipped_steps   calls that set bit 1
+ *   uint32_t pad             0
+ * sumsq, norm, scale and flags describe the last call, the three counters accumulate over the calls.
+ * The sum: two launches on `stream`. Pass 1 cuts g into shares of RSU_GRAD_NORM_BLOCK_FLOATS floats, one per 256-lane workgroup -- a grid
+ * that depends on n ALONE, not on the CU budget, the device or the autotuner; a lane sums the squares of its 16 float4 in float32 in a
+ * fixed order, a fixed tree adds the lanes, and the workgroup writes one partial sum and one "saw inf or nan" word. Pass 2, one
+ * workgroup, adds the partials in double in a fixed order and one thread writes the record. The same g, n and max_norm therefore
+ * give the same bits on every call, device and rank. Only g[0, n) is read (the n & 3 scalars behind the last float4 singly).
+ * ws: rsu_grad_norm_ws_floats(n) floats (2 per workgroup; 0 for n < 1), written in full, nothing behind them.
+ * Errors, returned before anything is launched: RSU_EINVAL for a NULL g, ws or state, n < 1, a max_norm that is not > 0 (nan included;
+ * +inf is allowed: the call then only measures and guards), a g that is not 16-byte aligned, a ws or state that is not 4-byte aligned. */
+#define RSU_CLIP_STATE_BYTES 32
+#define RSU_CLIP_CLIPPED 1u
+#define RSU_CLIP_NONFINITE 2u
+#define RSU_GRAD_NORM_BLOCK_FLOATS 16384
+size_t rsu_clip_state_bytes(void);
+size_t rsu_grad_norm_ws_floats(long n);
+int rsu_grad_norm(const float* g, long n, float max_norm, float* ws, void* state, rsu_stream_t stream);
+/* rsu_update_table_run / rsu_update_table_run_adam with gscale * state->scale for gscale (one float32 multiply, made once per
+ * workgroup; everything behind it is the arithmetic of the plain pass, so a _clip run whose record holds scale s gives the bits of the
+ * plain run with gscale * s). `state` is a record rsu_grad_norm wrote earlier on the same stream. With RSU_CLIP_NONFINITE set in it
+ * every workgroup returns before its first load: weights, optimizer slots and packed copies stay as they are, consistent with each
+ * other. RSU_EINVAL for a NULL or misaligned state (and what the plain run rejects), before anything is launched. */
+int rsu_update_table_run_clip(const void* dev_table, int nentries, int total_blocks, float lr, float mu, float gscale,
+                              const void* state, rsu_stream_t stream);
+int rsu_update_table_run_adam_clip(const void* dev_table, int nentries, int total_blocks, float alpha, float beta1, float beta2,
+                                   float epsilon, float gscale, const void* state, rsu_stream_t stream);
+
 /* ---- patch / stride tiler (src/images.py) -------------------------------------------------- */
 /* images.py:269-281 mirror_border + :35-85 extract_patches fused, on device: tile t (x-outer,
  * y-inner order, images.py:76-77) of image n is the [S][S] window of the symmetric-padded image at

@@ -112,6 +112,11 @@ SIGNATURES = {
     "rsu_adam_step": (_i, [_vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _l, _vp]),
     "rsu_update_table_set_second_slot": (_i, [_vp, _i, _vp]),
     "rsu_update_table_run_adam": (_i, [_vp, _i, _i, _f, _f, _f, _f, _f, _vp]),
+    "rsu_clip_state_bytes": (_sz, []),
+    "rsu_grad_norm_ws_floats": (_sz, [_l]),
+    "rsu_grad_norm": (_i, [_vp, _l, _f, _vp, _vp, _vp]),
+    "rsu_update_table_run_clip": (_i, [_vp, _i, _i, _f, _f, _f, _vp, _vp]),
+    "rsu_update_table_run_adam_clip": (_i, [_vp, _i, _i, _f, _f, _f, _f, _f, _vp, _vp]),
     "rsu_extract_tiles": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _l, _l, _vp]),
     "rsu_overlap_add": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _l, _l, _vp]),
     "rsu_overlap_finish": (_i, [_vp, _vp, _vp, _l, _vp]),
@@ -147,6 +152,7 @@ def lib():
 TUNE_OFF, TUNE_LOOKUP, TUNE_MEASURE = 0, 1, 2   # rsu.h RSU_TUNE_*
 EVAL_BINS = 256   # rsu.h RSU_EVAL_BINS
 BORDER_D2_INF, BORDER_MAX_SIDE = 0x7fffffff, 1024   # rsu.h RSU_BORDER_D2_INF, RSU_BORDER_MAX_SIDE
+CLIP_STATE_BYTES, CLIP_CLIPPED, CLIP_NONFINITE, GRAD_NORM_BLOCK_FLOATS = 32, 1, 2, 16384   # rsu.h RSU_CLIP_*, RSU_GRAD_NORM_BLOCK_FLOATS
 E2BIG = -7
 
 

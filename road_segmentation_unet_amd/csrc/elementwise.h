@@ -53,14 +53,40 @@ hipError_t ew_color_adjust_bwd(const float* gx, const float* w1, float* dW0, flo
 hipError_t ew_momentum(float* w, float* acc, const float* g, float lr, float mu, float gscale, long n, hipStream_t st);
 // the update rules of the optimizer passes (template argument of k_update_pack_many): their scalars, passed by value to the kernels.
 // kSecondSlot: the rule keeps a second fp32 slot per weight (UpJob::v)
+// kClip: the rule takes a factor of gscale, and the decision to step at all, from a ClipState in device memory (k_update_pack_many's head)
 struct MomentumRule {   // acc = mu * acc + gscale * g; w -= lr * acc
     float lr, mu, gscale;
     static constexpr bool kSecondSlot = false;
+    static constexpr bool kClip = false;
 };
 struct AdamRule {       // TensorFlow 1.x ApplyAdam with alpha = lr_t * sqrt(1 - beta2^t) / (1 - beta1^t) from the host (elementwise.hip, adam_elem)
     float alpha, beta1, beta2, epsilon, gscale;
     static constexpr bool kSecondSlot = true;
+    static constexpr bool kClip = false;
 };
+// Global-norm gradient clipping (rsu.h rsu_grad_norm): the 32-byte state record, rsu.h's layout field by field. One thread of
+// k_grad_norm_final writes it; the clipping rules below read scale and flags from it, so the host never has to.
+struct ClipState {
+    float sumsq, norm, scale;
+    unsigned flags;                                 // EW_CLIP_CLIPPED | EW_CLIP_NONFINITE
+    unsigned steps, clipped_steps, skipped_steps;   // accumulate over the calls
+    unsigned pad;
+};
+constexpr unsigned EW_CLIP_CLIPPED = 1u, EW_CLIP_NONFINITE = 2u;
+// the same two rules with gscale * state->scale for gscale; a workgroup returns before its first load when state->flags has EW_CLIP_NONFINITE
+struct ClipMomentumRule : MomentumRule {
+    const ClipState* state;
+    static constexpr bool kClip = true;
+};
+struct ClipAdamRule : AdamRule {
+    const ClipState* state;
+    static constexpr bool kClip = true;
+};
+// floats of g per workgroup of the norm's pass 1: 256 lanes x 16 float4. The grid, cdiv(n / 4, EW_GN_EPB / 4) (at least 1), depends on
+// n alone -- not on the CU budget, the device or the autotuner -- so the order of every sum, and with it the bits of the norm, do too.
+constexpr int EW_GN_EPB = 16384;
+int ew_grad_norm_blocks(long n);
+hipError_t ew_grad_norm(const float* g, long n, float max_norm, float* ws, ClipState* state, hipStream_t st);
 hipError_t ew_adam(float* w, float* m, float* v, const float* g, const AdamRule& h, long n, hipStream_t st);
 hipError_t ew_pack(const float* src, void* dst, const PackParams& pp, hipStream_t st);
 struct PackJob { PackParams pp; const float* src; bf16_t* dst; int block_start; int pad_; };
@@ -90,6 +116,8 @@ struct UpJob {
 int ew_update_job_blocks(const UpJob& j);
 hipError_t ew_update_pack_many(const UpJob* jobs_dev, int njobs, int total_blocks, float lr, float mu, float gscale, hipStream_t st);
 hipError_t ew_update_pack_many_adam(const UpJob* jobs_dev, int njobs, int total_blocks, const AdamRule& h, hipStream_t st);
+hipError_t ew_update_pack_many_clip(const UpJob* jobs_dev, int njobs, int total_blocks, const ClipMomentumRule& h, hipStream_t st);
+hipError_t ew_update_pack_many_adam_clip(const UpJob* jobs_dev, int njobs, int total_blocks, const ClipAdamRule& h, hipStream_t st);
 hipError_t ew_extract_tiles(const float* imgs, float* tiles, int H, int S, int P, int stride, int pps, long t0, long ntiles, hipStream_t st);
 hipError_t ew_overlap_add(const float* prob, float* acc, float* hits, int nimg, int H, int P, int stride, int pps, long t0, long ntiles, hipStream_t st);
 hipError_t ew_overlap_finish(const float* acc, const float* hits, float* out, long n, hipStream_t st);

@@ -1404,6 +1404,13 @@ __device__ __forceinline__ void update_pack_block(const UpJob& J, float (*tile)[
 }
 template <typename Rule>
 __global__ void __launch_bounds__(256) k_update_pack_many(const UpJob* __restrict__ jobs, int njobs, Rule h) {
+    if constexpr (Rule::kClip) {
+        // a clipping rule is resolved here, once per workgroup, from the record k_grad_norm_final left on this stream: a step whose
+        // gradient is not finite is skipped before the first load (weights, slots and packed copies stay as they are, and consistent
+        // with each other), any other step runs the arithmetic below unchanged with gscale * scale for gscale (one fp32 multiply)
+        if (h.state->flags & EW_CLIP_NONFINITE) return;
+        h.gscale *= h.state->scale;
+    }
     __shared__ int sj;
     __shared__ float tile[4][32][33];
     if (threadIdx.x < 64) {
@@ -1452,6 +1459,114 @@ hipError_t ew_update_pack_many(const UpJob* jobs_dev, int njobs, int total_block
 }
 hipError_t ew_update_pack_many_adam(const UpJob* jobs_dev, int njobs, int total_blocks, const AdamRule& h, hipStream_t st) {
     hipLaunchKernelGGL(k_update_pack_many<AdamRule>, dim3(total_blocks), dim3(256), 0, st, jobs_dev, njobs, h);
+    return hipGetLastError();
+}
+hipError_t ew_update_pack_many_clip(const UpJob* jobs_dev, int njobs, int total_blocks, const ClipMomentumRule& h, hipStream_t st) {
+    hipLaunchKernelGGL(k_update_pack_many<ClipMomentumRule>, dim3(total_blocks), dim3(256), 0, st, jobs_dev, njobs, h);
+    return hipGetLastError();
+}
+hipError_t ew_update_pack_many_adam_clip(const UpJob* jobs_dev, int njobs, int total_blocks, const ClipAdamRule& h, hipStream_t st) {
+    hipLaunchKernelGGL(k_update_pack_many<ClipAdamRule>, dim3(total_blocks), dim3(256), 0, st, jobs_dev, njobs, h);
+    return hipGetLastError();
+}
+// ---------------------------------------------------------------------------------------------
+// Global norm of the gradient (rsu.h rsu_grad_norm): sum g^2 over g[0, n), read once (4 B per weight, full 128-byte rows), in an order
+// that n alone fixes. The caller passes the contiguous [0, n_live) of the flat gradient buffer: the padding floats between its
+// variables are zero-initialised and never written, so they add exactly nothing and this is the norm of the live variables (the
+// unfused rsu_momentum_step steps the same range on the same grounds).
+// Pass 1, workgroup b: float4s [b * EW_GN_EPB / 4, +EW_GN_EPB / 4) of g. A lane issues its 16 loads (float4 q * 256 + lane of the
+// share), keeps one fp32 chain per float4 component (16 terms each, q ascending), adds the four chains as (0 + 1) + (2 + 3); the
+// n & 3 scalars behind the last float4 go to lanes 0..2 of workgroup 0 as one more term, as in k_update_pack_many. Then a 6-level
+// xor tree over the wave and (w0 + w1) + (w2 + w3) over the four waves: ws[b] is the workgroup's sum, ws[nb + b] (as u32) whether one of
+// its elements was inf or nan.
+// Pass 2, one workgroup: the nb partials in double -- lane t takes t, t + 256, ... ascending, then an 8-level tree in LDS -- and ONE
+// thread writes the state record. A second short launch instead of a last-block counter inside pass 1: the counter needs a
+// device-scope atomic and a fence per workgroup and a word somebody has to re-zero, and which workgroup comes last is not fixed, so the
+// reproducibility of the result would rest on the finisher re-reading every partial in a fixed order anyway -- which is this launch.
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_grad_norm_partial(const float* __restrict__ g, long n, float* __restrict__ ws, int nb) {
+    const long n4 = n >> 2;
+    const long i0 = (long)blockIdx.x * (EW_GN_EPB / 4) + threadIdx.x;
+    f32x4 v[EW_GN_EPB / 4 / 256];
+#pragma unroll
+    for (int q = 0; q < EW_GN_EPB / 4 / 256; ++q) {
+        const long i = i0 + q * 256;
+        v[q] = i < n4 ? ((const f32x4*)g)[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+    unsigned bad = 0u;   // an exponent of all ones: inf or nan
+#pragma unroll
+    for (int q = 0; q < EW_GN_EPB / 4 / 256; ++q) {
+        s += v[q] * v[q];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bad |= (__float_as_uint(v[q][j]) & 0x7f800000u) == 0x7f800000u ? 1u : 0u;
+    }
+    float t = (s[0] + s[1]) + (s[2] + s[3]);
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const float x = g[(n4 << 2) + threadIdx.x];
+        t += x * x;
+        bad |= (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u ? 1u : 0u;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        t += __shfl_xor(t, o);
+        bad |= __shfl_xor(bad, o);
+    }
+    __shared__ float ssum[4];
+    __shared__ unsigned sbad[4];
+    if ((threadIdx.x & 63) == 0) {
+        ssum[threadIdx.x >> 6] = t;
+        sbad[threadIdx.x >> 6] = bad;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        ws[blockIdx.x] = (ssum[0] + ssum[1]) + (ssum[2] + ssum[3]);
+        ((unsigned*)ws)[nb + blockIdx.x] = sbad[0] | sbad[1] | sbad[2] | sbad[3];
+    }
+}
+__global__ void __launch_bounds__(256) k_grad_norm_final(const float* __restrict__ ws, int nb, float max_norm, ClipState* __restrict__ state) {
+    __shared__ double dsum[256];
+    __shared__ unsigned dbad[256];
+    double t = 0.0;
+    unsigned bad = 0u;
+    for (int b = threadIdx.x; b < nb; b += 256) {
+        t += (double)ws[b];
+        bad |= ((const unsigned*)ws)[nb + b];
+    }
+    dsum[threadIdx.x] = t;
+    dbad[threadIdx.x] = bad;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            dsum[threadIdx.x] += dsum[threadIdx.x + o];
+            dbad[threadIdx.x] |= dbad[threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {   // the single writer of the record
+        const float sumsq = (float)dsum[0];   // (a double sum above FLT_MAX rounds to inf: an overflow counts as not finite)
+        const float norm = (float)sqrt((double)sumsq);
+        const bool nonfinite = dbad[0] != 0u || (__float_as_uint(sumsq) & 0x7f800000u) == 0x7f800000u;
+        const bool clipped = !nonfinite && norm > max_norm;
+        ClipState r = *state;
+        r.sumsq = sumsq;
+        r.norm = norm;
+        r.scale = nonfinite ? 0.f : (clipped ? (float)((double)max_norm / (double)norm) : 1.f);
+        r.flags = (clipped ? EW_CLIP_CLIPPED : 0u) | (nonfinite ? EW_CLIP_NONFINITE : 0u);
+        r.steps += 1u;
+        r.clipped_steps += clipped ? 1u : 0u;
+        r.skipped_steps += nonfinite ? 1u : 0u;
+        r.pad = 0u;
+        *state = r;
+    }
+}
+int ew_grad_norm_blocks(long n) {
+    const long nb = ((n >> 2) + EW_GN_EPB / 4 - 1) / (EW_GN_EPB / 4);
+    return (int)(nb < 1 ? 1 : nb);
+}
+hipError_t ew_grad_norm(const float* g, long n, float max_norm, float* ws, ClipState* state, hipStream_t st) {
+    const int nb = ew_grad_norm_blocks(n);
+    hipLaunchKernelGGL(k_grad_norm_partial, dim3(nb), dim3(256), 0, st, g, n, ws, nb);
+    hipLaunchKernelGGL(k_grad_norm_final, dim3(1), dim3(256), 0, st, ws, nb, max_norm, state);
     return hipGetLastError();
 }
 hipError_t ew_extract_tiles(const float* imgs, float* tiles, int H, int S, int P, int stride, int pps, long t0, long ntiles, hipStream_t st) {

@@ -415,6 +415,33 @@ extern "C" int rsu_update_table_run_adam(const void* dev_table, int nentries, in
                                            (hipStream_t)stream));
     return RSU_OK;
 }
+// ---- global-norm gradient clipping: the norm into a device-resident state record, and the two update passes that take their scale from it
+static_assert(sizeof(ClipState) == RSU_CLIP_STATE_BYTES, "rsu.h documents the state record as 32 bytes");
+static_assert(RSU_CLIP_CLIPPED == EW_CLIP_CLIPPED && RSU_CLIP_NONFINITE == EW_CLIP_NONFINITE, "rsu.h and elementwise.h must agree on the flag bits");
+static_assert(RSU_GRAD_NORM_BLOCK_FLOATS == EW_GN_EPB, "rsu.h and elementwise.h must agree on a workgroup's share");
+extern "C" size_t rsu_clip_state_bytes(void) { return sizeof(ClipState); }
+extern "C" size_t rsu_grad_norm_ws_floats(long n) { return n >= 1 ? 2 * (size_t)ew_grad_norm_blocks(n) : 0; }
+extern "C" int rsu_grad_norm(const float* g, long n, float max_norm, float* ws, void* state, rsu_stream_t stream) {
+    if (!g || !ws || !state || n < 1 || !(max_norm > 0.f)) return RSU_EINVAL;
+    if (((uintptr_t)g & 15) || ((uintptr_t)ws & 3) || ((uintptr_t)state & 3)) return RSU_EINVAL;
+    if ((n >> 2) / (EW_GN_EPB / 4) >= 0x7fffffffL) return RSU_E2BIG;
+    HIP_CHECK_RET(ew_grad_norm(g, n, max_norm, ws, (ClipState*)state, (hipStream_t)stream));
+    return RSU_OK;
+}
+extern "C" int rsu_update_table_run_clip(const void* dev_table, int nentries, int total_blocks, float lr, float mu, float gscale,
+                                         const void* state, rsu_stream_t stream) {
+    if (!dev_table || nentries < 1 || total_blocks < 1 || !state || ((uintptr_t)state & 3)) return RSU_EINVAL;
+    ClipMomentumRule h{{lr, mu, gscale}, (const ClipState*)state};
+    HIP_CHECK_RET(ew_update_pack_many_clip((const UpJob*)dev_table, nentries, total_blocks, h, (hipStream_t)stream));
+    return RSU_OK;
+}
+extern "C" int rsu_update_table_run_adam_clip(const void* dev_table, int nentries, int total_blocks, float alpha, float beta1, float beta2,
+                                              float epsilon, float gscale, const void* state, rsu_stream_t stream) {
+    if (!dev_table || nentries < 1 || total_blocks < 1 || !state || ((uintptr_t)state & 3)) return RSU_EINVAL;
+    ClipAdamRule h{{alpha, beta1, beta2, epsilon, gscale}, (const ClipState*)state};
+    HIP_CHECK_RET(ew_update_pack_many_adam_clip((const UpJob*)dev_table, nentries, total_blocks, h, (hipStream_t)stream));
+    return RSU_OK;
+}
 
 // ---------------------------------------------------------------------------------------------
 // VALU head / tail

@@ -78,6 +78,10 @@ EXTRA_FLAG_DEFS = [
                                   "0 = off (the U-Net paper uses 10). The loss stays normalised by the pixel count and the mean weight is above 1, "
                                   "so the effective step size rises with w0: retune --lr. It multiplies --class_weights and enters the Dice term"),
     ("border_sigma", float, 5.0, "Width sigma > 0, in pixels, of the border weight (the U-Net paper uses 5)"),
+    ("clip_grad_norm", float, 0.0, "Clip the gradient to this global L2 norm (over all variables, after the data-parallel average) before the "
+                                   "optimizer step, and skip a step whose gradient is not finite; 0 = off. Computed on the GPU without a host "
+                                   "synchronisation; grad_norm is logged per step and the clipped / skipped counts per epoch. A huge value "
+                                   "(1e30) only measures and guards"),
     ("validation_images", int, 0, "Hold out the last K training images, whole, as a validation set (0 = off); K must leave at least one "
                                   "training image, and --class_weights=balanced counts the remaining images only"),
     ("validate_every", int, 0, "Number of steps between validations on the held-out images; 0 = once at the end of each epoch"),
@@ -149,6 +153,17 @@ def parse_border_sigma(value):
         v = float("nan")
     if not (math.isfinite(v) and v > 0.0):
         raise ValueError("--border_sigma must be a finite float > 0, not %r" % (value,))
+    return v
+
+
+def parse_clip_grad_norm(value):
+    """The --clip_grad_norm value as a float: 0 (off) or finite and > 0. Anything else raises ValueError."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if isinstance(value, bool) or not (math.isfinite(v) and v >= 0.0):
+        raise ValueError("--clip_grad_norm must be 0 (off) or a finite float > 0, not %r" % (value,))
     return v
 
 
@@ -242,6 +257,7 @@ class Options(object):
         self.class_weights = parse_class_weights(self.class_weights)   # None, (w0, w1) or "balanced" (cli.main resolves it)
         self.dice_weight, self.dice_smooth = parse_dice_weight(self.dice_weight), parse_dice_smooth(self.dice_smooth)
         self.border_weight, self.border_sigma = parse_border_weight(self.border_weight), parse_border_sigma(self.border_sigma)
+        self.clip_grad_norm = parse_clip_grad_norm(self.clip_grad_norm)
         for name in ("validation_images", "validate_every"):
             v = getattr(self, name)
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
@@ -286,7 +302,7 @@ class ConvolutionalModel:
         self.net = UNet(opts.num_layers, opts.root_size, opts.dilated_layers, self.local_batch, opts.patch_size, device=device,
                         params=params, seed=opts.seed, training=True, optimizer=opts.optimizer, class_weights=opts.class_weights,
                         dice_weight=opts.dice_weight, dice_smooth=opts.dice_smooth, border_weight=opts.border_weight,
-                        border_sigma=opts.border_sigma)
+                        border_sigma=opts.border_sigma, clip_grad_norm=opts.clip_grad_norm if opts.clip_grad_norm > 0.0 else None)
         self.net.dropout_seed = int(opts.seed) + 7919 * self.rank  # independent masks on every rank's shard
         self._bucketer = None
         self._exchange_tuned = False
@@ -438,15 +454,20 @@ class ConvolutionalModel:
             self._summary.initialize_train_summary()
             self._summary.initialize_overlap_summary()
             self._summary.initialize_missclassification_summary()
-            self.summary_op = self._summary.get_summary_op({"loss": None, "learning_rate": None})
+            tags = {"loss": None, "learning_rate": None}
+            if self.net.clip_state is not None:
+                tags["grad_norm"] = None
+            self.summary_op = self._summary.get_summary_op(tags)
         return self._summary
 
     def _flush_scalars(self):
         """the per-step scalars are kept as device tensors and written in batches: reading them back every step would serialise
         the host with the GPU (the reference's session.run does exactly that)"""
         if self._summary is not None:
-            for step, loss_t, err_t, total, lr in self._pending_scalars:
+            for step, loss_t, err_t, total, lr, norm_t in self._pending_scalars:
                 self._summary.add({"loss": float(loss_t), "learning_rate": lr}, global_step=step)
+                if norm_t is not None:   # --clip_grad_norm: the norm of the step's gradient, before clipping
+                    self._summary.add({"grad_norm": float(norm_t)}, global_step=step)
                 self._summary.add_to_pixel_missclassification_summary(float(err_t), total, step)
         self._pending_scalars = []
 
@@ -499,7 +520,9 @@ class ConvolutionalModel:
             total += opts.batch_size
             last = loss
             if self._summary is not None:
-                self._pending_scalars.append((step, loss.clone(), num_errors.clone(), total, net.learning_rate(opts.lr)))
+                # (with --clip_grad_norm also a clone of the norm in the device-resident state record: device work, no synchronisation)
+                norm = net.clip_state.view(torch.float32)[1].clone() if net.clip_state is not None else None
+                self._pending_scalars.append((step, loss.clone(), num_errors.clone(), total, net.learning_rate(opts.lr), norm))
                 if len(self._pending_scalars) >= 64:
                     self._flush_scalars()
             # from time to time do full prediction on some images (tf_aerial_images.py:253-264)
@@ -528,6 +551,8 @@ class ConvolutionalModel:
         self.last_epoch_stats = {"loss": None if last is None else float(last), "soft_errors": float(num_errors), "patches": total}
         if val_stats is not None:
             self.last_epoch_stats["validation"] = val_stats
+        if net.clip_state is not None:   # --clip_grad_norm: steps / clipped / skipped so far, norm and scale of the last step
+            self.last_epoch_stats["clip"] = net.clip_stats()
         return self.last_epoch_stats
 
     # ------------------------------------------------------------------ inference

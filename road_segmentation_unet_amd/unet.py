@@ -93,6 +93,33 @@ def adam_scalars(lr_t, beta1_power, beta2_power, beta1, beta2):
     return f(alpha), f(b1p * f(beta1)), f(b2p * f(beta2))
 
 
+def clip_scale(sumsq, max_norm):
+    """The host mirror of the record rsu.h rsu_grad_norm writes: from the float32 sum of squares and max_norm (rounded to float32, as the
+    ABI takes it) the pair (norm, scale) as numpy float32 scalars, norm = (float)sqrt((double)sumsq) and scale = norm > max_norm ?
+    (float)((double)max_norm / (double)norm) : 1 -- exactly 1 at norm == max_norm. A sumsq that is not finite (an overflow included) is
+    the skipped step: scale 0."""
+    f = np.float32
+    s, c = f(sumsq), np.float64(f(max_norm))
+    with np.errstate(invalid="ignore"):
+        norm = f(np.sqrt(np.float64(s)))
+    if not np.isfinite(s):
+        return norm, f(0.0)
+    return norm, (f(c / np.float64(norm)) if np.float64(norm) > c else f(1.0))
+
+
+def _clip_arg(value):
+    """UNet's clip_grad_norm: None (no clipping), or a finite float > 0"""
+    if value is None:
+        return None
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if isinstance(value, bool) or not (math.isfinite(v) and v > 0.0):
+        raise _lib.RsuError("clip_grad_norm must be None or a finite float > 0, not %r" % (value,))
+    return v
+
+
 OPTIMIZERS = ("momentum", "adam")
 
 
@@ -107,7 +134,8 @@ class UNet:
     static in exactly the same way (tf_aerial_images.py:133-138)."""
 
     def __init__(self, num_layers, root_size, dilated_layers, batch_size, patch_size, device="cuda:0", params=None, seed=2017,
-                 training=True, optimizer="momentum", class_weights=None, dice_weight=0.0, dice_smooth=1.0, border_weight=0.0, border_sigma=5.0):
+                 training=True, optimizer="momentum", class_weights=None, dice_weight=0.0, dice_smooth=1.0, border_weight=0.0, border_sigma=5.0,
+                 clip_grad_norm=None):
         """optimizer: "momentum" (the reference's MomentumOptimizer: apply_momentum) or "adam" (tf.train.AdamOptimizer: apply_adam; a
         second fp32 slot per variable, flat_v).
         class_weights: None or a pair (w0, w1) of finite floats >= 0, not both 0: the weighted cross-entropy of rsu.h
@@ -117,10 +145,16 @@ class UNet:
         border_weight: w0 >= 0 of the border-distance weight map (rsu.h rsu_border_map): with w0 > 0 every backward_device and
         evaluate_device first turns self.labels into the map (1 + w0 exp(-D2 / (2 border_sigma^2)), D2 the squared distance to the other
         class inside the patch) times the map of set_pixel_weights, if any, and hands it to the head as its pixel weights; 0.0: no
-        buffer, no launch, the passes are what they always were. border_sigma: > 0, in pixels. Training nets only."""
+        buffer, no launch, the passes are what they always were. border_sigma: > 0, in pixels. Training nets only.
+        clip_grad_norm: None, or c > 0 (finite): apply_momentum / apply_adam first take the global norm of the live gradient on the
+        device (rsu.h rsu_grad_norm) and step with the gradient scaled by min(1, c / norm); a step whose gradient holds an inf or a nan, or
+        whose sum of squares overflows, changes nothing (see apply_momentum). No host synchronisation; clip_stats() reads the counters.
+        A huge c only measures and guards. None: no buffer, no launch, the step is what it always was."""
         if optimizer not in OPTIMIZERS:
             raise _lib.RsuError("optimizer must be one of %s, not %r" % ("|".join(OPTIMIZERS), optimizer))
         self.optimizer = optimizer
+        self.clip_grad_norm = _clip_arg(clip_grad_norm)
+        self.clip_state = self._clip_ws = None   # the device-resident state record (rsu.h, 8 x 32 bit) and the norm's workspace, with clipping
         assert root_size % 8 == 0 and (root_size // 8) & (root_size // 8 - 1) == 0, "root_size must be 8 * 2^k for the HIP path"
         self.L, self.root, self.dilated = num_layers, root_size, bool(dilated_layers)
         self.B, self.P = batch_size, patch_size
@@ -272,6 +306,13 @@ class UNet:
         self.flat_g = torch.zeros(off, dtype=torch.float32, device=dev)
         # Adam's second slot v (a Momentum net has none)
         self.flat_v = torch.zeros(off, dtype=torch.float32, device=dev) if self.optimizer == "adam" else None
+        if self.clip_grad_norm is not None:
+            # the norm runs over the contiguous flat_g[0:n_live): the padding floats between the variables are zero here and never
+            # written, so they add nothing, and the dead dilated pair behind n_live is left out as it is for the update
+            lib = _lib.lib()
+            assert lib.rsu_clip_state_bytes() == _lib.CLIP_STATE_BYTES
+            self.clip_state = torch.zeros(_lib.CLIP_STATE_BYTES // 4, dtype=torch.int32, device=dev)   # zeroed once: its counters accumulate
+            self._clip_ws = torch.empty(lib.rsu_grad_norm_ws_floats(self.n_live), dtype=torch.float32, device=dev)
         self.w, self.acc, self.g, self.v = {}, {}, {}, {}
         for n, (o, cnt, s) in self._slices.items():
             self.w[n] = self.flat_w[o:o + cnt].view(s)
@@ -942,11 +983,42 @@ class UNet:
         self._update_table = (torch.frombuffer(bytearray(host.raw), dtype=torch.uint8).to(self.device), len(entries), nb.value)
         return self._update_table
 
+    def _grad_norm(self):
+        """a clipping net, in front of its update pass and on the same stream: the norm of flat_g[0:n_live) and the factor for
+        clip_grad_norm into self.clip_state (rsu.h rsu_grad_norm). Under data parallelism the caller has finished the gradient exchange,
+        so every rank reads the same all-reduced gradient and computes the same bits: no collective of its own."""
+        if os.environ.get("RSU_FUSED_UPDATE", "1") == "0":
+            raise _lib.RsuError("clip_grad_norm needs the fused update pass: RSU_FUSED_UPDATE=0 (rsu_momentum_step / rsu_adam_step) has no "
+                                "clipped variant")
+        call("rsu_grad_norm", _ptr(self.flat_g), self.n_live, self.clip_grad_norm, _ptr(self._clip_ws), _ptr(self.clip_state), self._stream())
+
+    def clip_stats(self):
+        """The state record of a clipping net, read back once (a synchronisation: call it per epoch, not per step): steps, clipped and
+        skipped count the updates so far, norm / scale / sumsq and the two flags describe the last one. None on a net without clipping."""
+        if self.clip_state is None:
+            return None
+        raw = self.clip_state.cpu().numpy()
+        f = raw.view(np.float32)
+        flags = int(raw[3])
+        return {"steps": int(raw[4]), "clipped": int(raw[5]), "skipped": int(raw[6]), "norm": float(f[1]), "scale": float(f[2]),
+                "sumsq": float(f[0]), "last_clipped": bool(flags & _lib.CLIP_CLIPPED), "last_skipped": bool(flags & _lib.CLIP_NONFINITE)}
+
     def apply_momentum(self, lr0, momentum, gscale=1.0):
         """MomentumOptimizer step on every live variable (tf_aerial_images.py:120-121) and the re-pack of the bf16 MFMA copies, in one
-        pass over the parameters (rsu_update_table_run; RSU_FUSED_UPDATE=0: rsu_momentum_step, then the batched re-pack -- same bits)."""
+        pass over the parameters (rsu_update_table_run; RSU_FUSED_UPDATE=0: rsu_momentum_step, then the batched re-pack -- same bits).
+        A net built with clip_grad_norm: rsu_grad_norm, then rsu_update_table_run_clip, whose gscale is this gscale times the factor on
+        the device. A step whose gradient is not finite leaves weights, slots and packed copies as they are but STILL COUNTS as a step:
+        the host does not know (that is the point), so global_step and the decay staircase advance -- and under Adam the beta powers,
+        while m and v stay untouched; clip_stats() tells how often it happened."""
         if self.optimizer != "momentum":
             raise _lib.RsuError("apply_momentum on a net built with optimizer=%r" % self.optimizer)
+        if self.clip_grad_norm is not None:
+            self._grad_norm()
+            tab = self._update_table or self._build_update_table()
+            call("rsu_update_table_run_clip", _ptr(tab[0]), tab[1], tab[2], self.learning_rate(lr0), momentum, gscale, _ptr(self.clip_state),
+                 self._stream())
+            self.global_step += 1
+            return
         if os.environ.get("RSU_FUSED_UPDATE", "1") == "0":
             call("rsu_momentum_step", _ptr(self.flat_w), _ptr(self.flat_acc), _ptr(self.flat_g), self.learning_rate(lr0), momentum, gscale,
                  self.n_live, self._stream())
@@ -961,14 +1033,21 @@ class UNet:
         """tf.train.AdamOptimizer step on every live variable (TensorFlow 1.x ApplyAdam at the decayed rate learning_rate(lr0)) and the
         re-pack of the bf16 MFMA copies, in one pass over the parameters (rsu_update_table_run_adam; RSU_FUSED_UPDATE=0: rsu_adam_step,
         then the batched re-pack -- same bits). alpha and the beta powers are float32 host arithmetic (adam_scalars); global_step and
-        the powers advance after the launch. The dead level-(L-1) dilated pair is never stepped."""
+        the powers advance after the launch. The dead level-(L-1) dilated pair is never stepped.
+        A net built with clip_grad_norm: rsu_grad_norm, then rsu_update_table_run_adam_clip; a skipped step still advances global_step
+        and the beta powers (see apply_momentum)."""
         if self.optimizer != "adam":
             raise _lib.RsuError("apply_adam on a net built with optimizer=%r" % self.optimizer)
+        if self.clip_grad_norm is not None:
+            self._grad_norm()   # (raises under RSU_FUSED_UPDATE=0, before the powers are touched)
         if self.beta1_power is None:
             self.beta1_power, self.beta2_power = np.float32(beta1), np.float32(beta2)
         alpha, b1p, b2p = adam_scalars(self.learning_rate(lr0), self.beta1_power, self.beta2_power, beta1, beta2)
         args = (float(alpha), float(np.float32(beta1)), float(np.float32(beta2)), float(np.float32(epsilon)), gscale)
-        if os.environ.get("RSU_FUSED_UPDATE", "1") == "0":
+        if self.clip_grad_norm is not None:
+            tab = self._update_table or self._build_update_table()
+            call("rsu_update_table_run_adam_clip", _ptr(tab[0]), tab[1], tab[2], *args, _ptr(self.clip_state), self._stream())
+        elif os.environ.get("RSU_FUSED_UPDATE", "1") == "0":
             call("rsu_adam_step", _ptr(self.flat_w), _ptr(self.flat_acc), _ptr(self.flat_v), _ptr(self.flat_g), *args, self.n_live, self._stream())
             self.repack()
         else:
