@@ -453,6 +453,22 @@ int rsu_update_table_run_clip(const void* dev_table, int nentries, int total_blo
 int rsu_update_table_run_adam_clip(const void* dev_table, int nentries, int total_blocks, float alpha, float beta1, float beta2,
                                    float epsilon, float gscale, const void* state, rsu_stream_t stream);
 
+/* ---- optimizer: moving average of the weights (new) -------- */
+/* tf.train.ExponentialMovingAverage's assign_moving_average over ema[0, n) and w[0, n), per element, float32, in this order, no
+ * contraction:
+ *   ema[i] = ema[i] - (ema[i] - w[i]) * one_minus_decay
+ * The caller computes one_minus_decay = 1 - decay_t in float32 (with TensorFlow's num_updates rule decay_t = min(decay, (1 + t) /
+ * (10 + t))). ONE launch on `stream`, behind the update pass whose weights it averages: 256-lane workgroups over shares of 8192 floats,
+ * a grid that depends on n ALONE -- not on the CU budget, the device or the autotuner. Reads ema and w once, writes ema: 12 B per
+ * weight. Only ema[0, n) is written and only w[0, n) is read (the n & 3 scalars behind the last float4 singly).
+ * clip_state: NULL, or the record rsu_grad_norm wrote earlier on the same stream. With RSU_CLIP_NONFINITE set in it every workgroup
+ * returns before its first load, exactly as the _clip update passes do: a skipped step leaves weights, slots, packed copies AND
+ * averages as they were. Any other record behaves as NULL (the scale is the gradient's business, not the average's).
+ * Errors, returned before anything is launched: RSU_EINVAL for a NULL ema or w, n < 1, a one_minus_decay that is not in (0, 1] (nan
+ * included), an ema or w that is not 16-byte aligned, overlapping ema and w ranges, a clip_state that is not 4-byte aligned. */
+int rsu_ema_step(float* ema, const float* w, long n, float one_minus_decay, const void* clip_state /* may be NULL */,
+                 rsu_stream_t stream);
+
 /* ---- patch / stride tiler (src/images.py) -------------------------------------------------- */
 /* images.py:269-281 mirror_border + :35-85 extract_patches fused, on device: tile t (x-outer,
  * y-inner order, images.py:76-77) of image n is the [S][S] window of the symmetric-padded image at

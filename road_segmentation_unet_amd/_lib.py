@@ -117,6 +117,7 @@ SIGNATURES = {
     "rsu_grad_norm": (_i, [_vp, _l, _f, _vp, _vp, _vp]),
     "rsu_update_table_run_clip": (_i, [_vp, _i, _i, _f, _f, _f, _vp, _vp]),
     "rsu_update_table_run_adam_clip": (_i, [_vp, _i, _i, _f, _f, _f, _f, _f, _vp, _vp]),
+    "rsu_ema_step": (_i, [_vp, _vp, _l, _f, _vp, _vp]),
     "rsu_extract_tiles": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _l, _l, _vp]),
     "rsu_overlap_add": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _l, _l, _vp]),
     "rsu_overlap_finish": (_i, [_vp, _vp, _vp, _l, _vp]),

@@ -87,6 +87,11 @@ struct ClipAdamRule : AdamRule {
 constexpr int EW_GN_EPB = 16384;
 int ew_grad_norm_blocks(long n);
 hipError_t ew_grad_norm(const float* g, long n, float max_norm, float* ws, ClipState* state, hipStream_t st);
+// Moving average of the weights (rsu.h rsu_ema_step): floats per workgroup, 256 lanes x 8 float4 of each of the two arrays. The grid,
+// cdiv(n / 4, EW_EMA_EPB / 4) (at least 1), depends on n alone. state: nullptr, or the record of ew_grad_norm (a skipped step skips here too)
+constexpr int EW_EMA_EPB = 8192;
+int ew_ema_blocks(long n);
+hipError_t ew_ema(float* ema, const float* w, long n, float one_minus_decay, const ClipState* state, hipStream_t st);
 hipError_t ew_adam(float* w, float* m, float* v, const float* g, const AdamRule& h, long n, hipStream_t st);
 hipError_t ew_pack(const float* src, void* dst, const PackParams& pp, hipStream_t st);
 struct PackJob { PackParams pp; const float* src; bf16_t* dst; int block_start; int pad_; };

@@ -1569,6 +1569,60 @@ hipError_t ew_grad_norm(const float* g, long n, float max_norm, float* ws, ClipS
     hipLaunchKernelGGL(k_grad_norm_final, dim3(1), dim3(256), 0, st, ws, nb, max_norm, state);
     return hipGetLastError();
 }
+// ---------------------------------------------------------------------------------------------
+// Exponential moving average of the weights (rsu.h rsu_ema_step): ema -= (ema - w) * one_minus_decay over [0, n), TensorFlow's
+// assign_moving_average in float32, two roundings per step besides the subtraction's (no contraction: an FMA would move the last bit
+// against a float32 restatement). Reads ema and w once, writes ema: 12 B per weight, full 128-byte rows. The grid is
+// k_grad_norm_partial's, cdiv(n / 4, EW_EMA_EPB / 4) (at least 1): workgroup b owns float4s [b * EW_EMA_EPB / 4, +EW_EMA_EPB / 4), a
+// lane float4 q * 256 + lane of that share, and issues its 2 x EW_EMA_EPB / 1024 loads before its first store (ema is read and written
+// through one pointer: a store in front of a later load would order them). The n & 3 scalars behind the last float4 go to lanes 0..2
+// of workgroup 0. `state`, when not NULL, is the record k_grad_norm_final left on this stream: with EW_CLIP_NONFINITE set the update
+// pass skipped its step, and every workgroup here returns before its first load as well -- the averages of a skipped step do not move.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ float ema_elem(float e, float w, float omd) {
+#pragma clang fp contract(off)
+    return e - (e - w) * omd;
+}
+// one lane's part of a workgroup's share; FULL: the whole share lies inside [0, n4), no lane tests anything (every workgroup but the last)
+template <bool FULL>
+__device__ __forceinline__ void ema_share(float* ema, const float* __restrict__ w, long i0, long n4, float omd) {
+    constexpr int NQ = EW_EMA_EPB / 4 / 256;
+    f32x4 ev[NQ], wv[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        const long i = i0 + q * 256;
+        const bool in = FULL || i < n4;
+        ev[q] = in ? ((const f32x4*)ema)[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+        wv[q] = in ? ((const f32x4*)w)[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        const long i = i0 + q * 256;
+        f32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = ema_elem(ev[q][j], wv[q][j], omd);
+        if (FULL || i < n4) ((f32x4*)ema)[i] = o;
+    }
+}
+__global__ void __launch_bounds__(256) k_ema(float* ema, const float* __restrict__ w, long n, float omd, const ClipState* __restrict__ state) {
+    if (state && (state->flags & EW_CLIP_NONFINITE)) return;
+    const long n4 = n >> 2;
+    const long b0 = (long)blockIdx.x * (EW_EMA_EPB / 4);
+    if (b0 + EW_EMA_EPB / 4 <= n4) ema_share<true>(ema, w, b0 + threadIdx.x, n4, omd);
+    else ema_share<false>(ema, w, b0 + threadIdx.x, n4, omd);
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const long i = (n4 << 2) + threadIdx.x;
+        ema[i] = ema_elem(ema[i], w[i], omd);
+    }
+}
+int ew_ema_blocks(long n) {
+    const long nb = ((n >> 2) + EW_EMA_EPB / 4 - 1) / (EW_EMA_EPB / 4);
+    return (int)(nb < 1 ? 1 : nb);
+}
+hipError_t ew_ema(float* ema, const float* w, long n, float one_minus_decay, const ClipState* state, hipStream_t st) {
+    hipLaunchKernelGGL(k_ema, dim3(ew_ema_blocks(n)), dim3(256), 0, st, ema, w, n, one_minus_decay, state);
+    return hipGetLastError();
+}
 hipError_t ew_extract_tiles(const float* imgs, float* tiles, int H, int S, int P, int stride, int pps, long t0, long ntiles, hipStream_t st) {
     hipLaunchKernelGGL(k_extract_tiles, dim3(grid_for(ntiles * S * S, 256)), dim3(256), 0, st, imgs, tiles, H, S, P, stride, pps, t0, ntiles);
     return hipGetLastError();

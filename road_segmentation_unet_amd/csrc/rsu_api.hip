@@ -442,6 +442,17 @@ extern "C" int rsu_update_table_run_adam_clip(const void* dev_table, int nentrie
     HIP_CHECK_RET(ew_update_pack_many_adam_clip((const UpJob*)dev_table, nentries, total_blocks, h, (hipStream_t)stream));
     return RSU_OK;
 }
+// ---- moving average of the weights: one pass of its own behind the update pass (ema and w must not overlap: w is read through a
+// __restrict__ pointer)
+extern "C" int rsu_ema_step(float* ema, const float* w, long n, float one_minus_decay, const void* clip_state, rsu_stream_t stream) {
+    if (!ema || !w || n < 1 || !(one_minus_decay > 0.f && one_minus_decay <= 1.f)) return RSU_EINVAL;
+    if (((uintptr_t)ema & 15) || ((uintptr_t)w & 15) || ((uintptr_t)clip_state & 3)) return RSU_EINVAL;
+    if ((n >> 2) / (EW_EMA_EPB / 4) >= 0x7fffffffL) return RSU_E2BIG;
+    const uintptr_t e0 = (uintptr_t)ema, w0 = (uintptr_t)w, bytes = (uintptr_t)n * sizeof(float);
+    if (e0 < w0 + bytes && w0 < e0 + bytes) return RSU_EINVAL;
+    HIP_CHECK_RET(ew_ema(ema, w, n, one_minus_decay, (const ClipState*)clip_state, (hipStream_t)stream));
+    return RSU_OK;
+}
 
 // ---------------------------------------------------------------------------------------------
 // VALU head / tail

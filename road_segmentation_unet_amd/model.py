@@ -5,6 +5,7 @@ argument meaning, batch/tiling conventions and quirks that matter for parity -- 
 Data parallelism (new; the reference is single-device): when torch.distributed is initialised, `batch_size` is the GLOBAL
 minibatch, sharded contiguously over ranks; gradients are all-reduced (dist.GradBucketer); predict() shards tiles.
 """
+import contextlib
 import glob
 import math
 import os
@@ -20,7 +21,7 @@ from ._lib import call
 from .dist import GradBucketer, shard_indices, tune_overlap
 from .pool import BatchUploader, DevicePatchPool, PatchPool
 from .summary import Summary
-from .unet import UNet, input_size_needed
+from .unet import EMA_SUFFIX, UNet, input_size_needed
 
 # (name, type, default, help) -- tf_aerial_images.py:15-46, same order
 FLAG_DEFS = [
@@ -86,6 +87,10 @@ EXTRA_FLAG_DEFS = [
                                   "training image, and --class_weights=balanced counts the remaining images only"),
     ("validate_every", int, 0, "Number of steps between validations on the held-out images; 0 = once at the end of each epoch"),
     ("save_best", bool, False, "Keep <save_path>/<experiment>-best.chkpt, rewritten whenever the validation F1 improves"),
+    ("ema_decay", float, 0.0, "Decay d (0 <= d < 1) of an exponential moving average of the weights, tf.train.ExponentialMovingAverage, "
+                              "updated on the GPU after every optimizer step; 0 = off. Validation, --save_best, prediction and the final "
+                              "inference then use the averaged weights; checkpoints hold both the raw weights and the averages"),
+    ("ema_warmup", bool, True, "TensorFlow's num_updates rule for --ema_decay: the decay of update t is min(d, (1 + t) / (10 + t))"),
 ]
 
 
@@ -164,6 +169,17 @@ def parse_clip_grad_norm(value):
         v = float("nan")
     if isinstance(value, bool) or not (math.isfinite(v) and v >= 0.0):
         raise ValueError("--clip_grad_norm must be 0 (off) or a finite float > 0, not %r" % (value,))
+    return v
+
+
+def parse_ema_decay(value):
+    """The --ema_decay value as a float: 0 (off) or in (0, 1). Anything else raises ValueError."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if isinstance(value, bool) or not (0.0 <= v and np.float32(v) < np.float32(1.0)):
+        raise ValueError("--ema_decay must be 0 (off) or a float in (0, 1), not %r" % (value,))
     return v
 
 
@@ -258,6 +274,7 @@ class Options(object):
         self.dice_weight, self.dice_smooth = parse_dice_weight(self.dice_weight), parse_dice_smooth(self.dice_smooth)
         self.border_weight, self.border_sigma = parse_border_weight(self.border_weight), parse_border_sigma(self.border_sigma)
         self.clip_grad_norm = parse_clip_grad_norm(self.clip_grad_norm)
+        self.ema_decay, self.ema_warmup = parse_ema_decay(self.ema_decay), bool(self.ema_warmup)
         for name in ("validation_images", "validate_every"):
             v = getattr(self, name)
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
@@ -302,7 +319,8 @@ class ConvolutionalModel:
         self.net = UNet(opts.num_layers, opts.root_size, opts.dilated_layers, self.local_batch, opts.patch_size, device=device,
                         params=params, seed=opts.seed, training=True, optimizer=opts.optimizer, class_weights=opts.class_weights,
                         dice_weight=opts.dice_weight, dice_smooth=opts.dice_smooth, border_weight=opts.border_weight,
-                        border_sigma=opts.border_sigma, clip_grad_norm=opts.clip_grad_norm if opts.clip_grad_norm > 0.0 else None)
+                        border_sigma=opts.border_sigma, clip_grad_norm=opts.clip_grad_norm if opts.clip_grad_norm > 0.0 else None,
+                        ema_decay=opts.ema_decay if opts.ema_decay > 0.0 else None, ema_warmup=opts.ema_warmup)
         self.net.dropout_seed = int(opts.seed) + 7919 * self.rank  # independent masks on every rank's shard
         self._bucketer = None
         self._exchange_tuned = False
@@ -319,6 +337,8 @@ class ConvolutionalModel:
             self.net.on_grads = self._bucketer.ready
             # identical initial weights on every rank (the reference has one copy; ranks must start from the same point)
             dist.broadcast(self.net.flat_w, 0)
+            if self.net.flat_ema is not None:
+                self.net.flat_ema.copy_(self.net.flat_w)   # (the shadows start at the broadcast weights)
             self.net.repack()
 
     # ------------------------------------------------------------------ training
@@ -378,8 +398,17 @@ class ConvolutionalModel:
         return loss, net.prob
 
     # ------------------------------------------------------------------ held-out validation
+    def _averaged_ctx(self, averaged, what):
+        """(context, averaged?) for the device work of evaluate() / predict(): net.averaged_weights() for averaged=True, or None on a net
+        that has averages; the raw weights (a no-op context) for False, or None on a net without. True on a net without averages raises."""
+        has = self.net.flat_ema is not None
+        if averaged and not has:
+            raise ValueError("%s(averaged=True) on a model without averaged weights (--ema_decay=0)" % what)
+        use = has if averaged is None else bool(averaged)
+        return (self.net.averaged_weights() if use else contextlib.nullcontext()), use
+
     @torch.no_grad()
-    def evaluate(self, patches, labels, weights=None, threshold=0.5):
+    def evaluate(self, patches, labels, weights=None, threshold=0.5, averaged=None):
         """The training objective and the pixel metrics over a held-out set, forward only: `patches` [N,S,S,3] float, `labels` [N,P,P]
         (already 0 / 1; any other value ignores its pixel), `weights` an optional weight map [N,P,P] (None: no map). Every rank must call
         it with the same set. The set is sharded contiguously over the ranks and run in local_batch chunks -- the last one padded with
@@ -387,8 +416,11 @@ class ConvolutionalModel:
         and UNet.evaluate_device (one rsu_head_eval launch per chunk). Everything accumulates on the device; the two accumulators are
         SUM-all-reduced (the sums as float64) and read back ONCE. Returns metrics_from_eval(...) of them, with the net's dice_weight /
         dice_smooth, plus "sums" (float64 [5]) and "hist" (int64 [2, 256]).
-        Training is left as it was: weights, optimizer slots, global_step (and with it the dropout keys), the gradient buffers, net.x /
-        net.labels, net.pixel_weights and a batch the uploader has staged; net.prob holds the last chunk's probabilities afterwards."""
+        averaged: None scores the averaged weights when the net has them (--ema_decay), True demands them (ValueError on a net without),
+        False forces the raw weights; the device work runs inside net.averaged_weights(), and the result carries "averaged" (bool).
+        Training is left as it was: weights, the averages and every packed copy (the exchange of averaged_weights() is undone), optimizer
+        slots, global_step (and with it the dropout keys), the gradient buffers, net.x / net.labels, net.pixel_weights and a batch the
+        uploader has staged; net.prob holds the last chunk's probabilities afterwards."""
         net, B = self.net, self.local_batch
         patches, labels = np.asarray(patches), np.asarray(labels)
         N = int(patches.shape[0])
@@ -397,46 +429,50 @@ class ConvolutionalModel:
         metrics_from_eval(np.zeros(5), np.zeros((2, net.eval_hist.shape[1]), np.int64), 0, threshold=threshold)   # a bad threshold fails before any work
         per = -(-N // self.world)
         lo, hi = min(self.rank * per, N), min((self.rank + 1) * per, N)
+        ctx, averaged = self._averaged_ctx(averaged, "evaluate")
         net.ensure_tuned(training=False, keep=1.0)   # (an untimed pass of its own kind; under data parallelism no collective is in flight here)
         x0, l0 = net.x.clone(), net.labels.clone()
         pw0 = net.pixel_weights.clone() if net.pixel_weights is not None else None
         try:
-            net.reset_eval()
-            for t0 in range(lo, hi, B):
-                nb = min(B, hi - t0)
-                if nb < B:
-                    net.x.zero_()
-                    net.labels.fill_(-1)
-                net.x[:nb].copy_(torch.as_tensor(np.asarray(patches[t0:t0 + nb], dtype=np.float32)))
-                net.labels[:nb].copy_(torch.as_tensor(np.asarray(labels[t0:t0 + nb])).to(torch.int64))
-                if weights is not None:
-                    wmap = np.ones((B,) + tuple(labels.shape[1:]), dtype=np.float32)
-                    wmap[:nb] = np.asarray(weights[t0:t0 + nb], dtype=np.float32)
-                    net.set_pixel_weights(torch.from_numpy(wmap))
-                else:
-                    net.set_pixel_weights(None)
-                net.forward_device(keep=1.0)
-                net.evaluate_device()
-            sums, hist = net.eval_sums.to(torch.float64), net.eval_hist.clone()
-            if self.world > 1:
-                dist.all_reduce(sums)
-                dist.all_reduce(hist)
-            sums, hist = sums.cpu().numpy(), hist.cpu().numpy()   # the one synchronisation
+            with ctx:
+                net.reset_eval()
+                for t0 in range(lo, hi, B):
+                    nb = min(B, hi - t0)
+                    if nb < B:
+                        net.x.zero_()
+                        net.labels.fill_(-1)
+                    net.x[:nb].copy_(torch.as_tensor(np.asarray(patches[t0:t0 + nb], dtype=np.float32)))
+                    net.labels[:nb].copy_(torch.as_tensor(np.asarray(labels[t0:t0 + nb])).to(torch.int64))
+                    if weights is not None:
+                        wmap = np.ones((B,) + tuple(labels.shape[1:]), dtype=np.float32)
+                        wmap[:nb] = np.asarray(weights[t0:t0 + nb], dtype=np.float32)
+                        net.set_pixel_weights(torch.from_numpy(wmap))
+                    else:
+                        net.set_pixel_weights(None)
+                    net.forward_device(keep=1.0)
+                    net.evaluate_device()
+                sums, hist = net.eval_sums.to(torch.float64), net.eval_hist.clone()
+                if self.world > 1:
+                    dist.all_reduce(sums)
+                    dist.all_reduce(hist)
+                sums, hist = sums.cpu().numpy(), hist.cpu().numpy()   # the one synchronisation
         finally:
             net.x.copy_(x0)
             net.labels.copy_(l0)
             net.set_pixel_weights(pw0)
         out = metrics_from_eval(sums, hist, N * int(np.prod(labels.shape[1:])), net.dice_weight, net.dice_smooth, threshold)
-        out["sums"], out["hist"] = sums, hist
+        out["sums"], out["hist"], out["averaged"] = sums, hist, averaged
         return out
 
     def _validate(self, validation, step):
-        """one validation pass inside train(): evaluate, print and log on rank 0, keep the best model with --save_best"""
+        """one validation pass inside train(): evaluate (the averaged weights with --ema_decay), print and log on rank 0, keep the best model
+        with --save_best (its checkpoint holds the raw weights and the averages)"""
         opts = self._options
         v = self.evaluate(validation[0], validation[1])
         if self.rank == 0:
-            print("\nstep {} validation: loss {:.5f} objective {:.5f} dice {:.4f} f1 {:.4f} iou {:.4f} best threshold {:.4f} (f1 {:.4f}) on {} patches"
-                  .format(step, v["loss"], v["objective"], v["dice"], v["f1"], v["iou"], v["best_threshold"], v["best_f1"], len(validation[0])))
+            print("\nstep {} validation: loss {:.5f} objective {:.5f} dice {:.4f} f1 {:.4f} iou {:.4f} best threshold {:.4f} (f1 {:.4f}) on {} patches{}"
+                  .format(step, v["loss"], v["objective"], v["dice"], v["f1"], v["iou"], v["best_threshold"], v["best_f1"], len(validation[0]),
+                          " (averaged weights)" if v["averaged"] else ""))
             if self._summary is not None:
                 self._summary.add({"val_loss": v["loss"], "val_objective": v["objective"], "val_dice": v["dice"], "val_f1": v["f1"],
                                    "val_iou": v["iou"], "val_best_threshold": v["best_threshold"]}, global_step=step)
@@ -557,13 +593,16 @@ class ConvolutionalModel:
 
     # ------------------------------------------------------------------ inference
     @torch.no_grad()
-    def predict(self, imgs):
+    def predict(self, imgs, averaged=None):
         """Run inference on `imgs` and return predicted masks (tf_aerial_images.py:271-328).
+        averaged: None predicts with the averaged weights when the net has them (--ema_decay), True demands them (ValueError on a net
+        without), False forces the raw weights (evaluate has the same argument); the forward passes run inside net.averaged_weights().
         imgs: [num_images, H, H, 3] in [0,1]; returns numpy [num_images, H, H, 1] road probabilities.
         Ensemble x6 -> mirror border -> tiles (x-outer order) -> batched forward -> overlap average -> inverse ensemble.
         Tiles are sharded contiguously over ranks; the accumulators are summed with one all-reduce."""
         opts, net = self._options, self.net
         dev = net.device
+        ctx, _ = self._averaged_ctx(averaged, "predict")
         imgs_t = torch.as_tensor(np.asarray(imgs)).to(dev, torch.float32)
         num_images = imgs_t.shape[0]
         if opts.ensemble_prediction:
@@ -577,26 +616,27 @@ class ConvolutionalModel:
         was_training = net.training
         net.training = False
         reduced = False
-        if os.environ.get("RSU_PREDICT_SHARED", "1") == "1" and pps > 1:
-            # every rank fills the tiles of its own phase classes (zeros elsewhere) and overlap-adds the lot locally: the hit counts are
-            # then complete on every rank, and ONE all-reduce of the accumulator (H*H floats per image variant, 1.4 MB at 604 px --
-            # not the 1.3 GB of tiles) completes the sums
-            tiles = self._shared_window_tiles(imgs_t, pps)
-            acc.add(tiles.view(-1, P, P), 0)
-            if self.world > 1:
-                dist.all_reduce(acc.acc)
-            reduced = True
-        else:
-            per = -(-num_patches // self.world)
-            lo, hi = min(self.rank * per, num_patches), min((self.rank + 1) * per, num_patches)
-            net.ensure_tuned(training=False)
-            for t0 in range(lo, hi, B):
-                nb = min(B, hi - t0)
-                if nb < B:
-                    net.x.zero_()  # the reference pads the last batch with zero patches (tf_aerial_images.py:298-301)
-                dimages.extract_mirrored_patches(imgs_t, S, P, opts.stride, t0=t0, ntiles=nb, out=net.x[:nb])
-                net.forward_device()
-                acc.add(net.prob[:nb], t0)
+        with ctx:
+            if os.environ.get("RSU_PREDICT_SHARED", "1") == "1" and pps > 1:
+                # every rank fills the tiles of its own phase classes (zeros elsewhere) and overlap-adds the lot locally: the hit counts are
+                # then complete on every rank, and ONE all-reduce of the accumulator (H*H floats per image variant, 1.4 MB at 604 px --
+                # not the 1.3 GB of tiles) completes the sums
+                tiles = self._shared_window_tiles(imgs_t, pps)
+                acc.add(tiles.view(-1, P, P), 0)
+                if self.world > 1:
+                    dist.all_reduce(acc.acc)
+                reduced = True
+            else:
+                per = -(-num_patches // self.world)
+                lo, hi = min(self.rank * per, num_patches), min((self.rank + 1) * per, num_patches)
+                net.ensure_tuned(training=False)
+                for t0 in range(lo, hi, B):
+                    nb = min(B, hi - t0)
+                    if nb < B:
+                        net.x.zero_()  # the reference pads the last batch with zero patches (tf_aerial_images.py:298-301)
+                    dimages.extract_mirrored_patches(imgs_t, S, P, opts.stride, t0=t0, ntiles=nb, out=net.x[:nb])
+                    net.forward_device()
+                    acc.add(net.prob[:nb], t0)
         net.training = was_training
         if self.world > 1 and not reduced:
             dist.all_reduce(acc.acc)
@@ -661,7 +701,8 @@ class ConvolutionalModel:
         return tiles
 
     def _window_net(self, Pk, Bw):
-        """a forward-only network for a larger output window, sharing this model's current weights"""
+        """a forward-only network for a larger output window, sharing this model's current weights: flat_w, which inside
+        net.averaged_weights() holds the averages -- the version key tells the two apart"""
         nets = self.__dict__.setdefault("_win_nets", {})
         opts = self._options
         wn = nets.get((Pk, Bw))
@@ -669,7 +710,7 @@ class ConvolutionalModel:
             wn = nets[Pk, Bw] = UNet(opts.num_layers, opts.root_size, opts.dilated_layers, Bw, Pk, device=self.net.device,
                                      params=None, seed=opts.seed, training=False)
             wn._weights_version = None
-        ver = (self.net.global_step, getattr(self.net, "_load_count", 0))
+        ver = (self.net.global_step, getattr(self.net, "_load_count", 0), self.net._averaged)
         if wn._weights_version != ver:
             wn.flat_w.copy_(self.net.flat_w)
             wn.repack()
@@ -717,7 +758,8 @@ class ConvolutionalModel:
         tools/export_tf_checkpoint.py on a machine that has TensorFlow (tf.train.load_checkpoint(...).get_tensor(name) for every
         name; tf_aerial_images.py:171 saves all global variables). Names and layouts are the reference's own, so this is a pure
         rename: `<var>` -> weights, `<var>/Momentum` -> optimizer slots, `global_step` (tf_aerial_images.py:113) -> step counter; a run
-        with tf.train.AdamOptimizer: `<var>/Adam`, `<var>/Adam_1`, `beta1_power`, `beta2_power` (read by an Adam model; UNet.load_state_dict).
+        with tf.train.AdamOptimizer: `<var>/Adam`, `<var>/Adam_1`, `beta1_power`, `beta2_power` (read by an Adam model; UNet.load_state_dict);
+        a run with tf.train.ExponentialMovingAverage: `<var>/ExponentialMovingAverage` (read by a model with --ema_decay).
         A ':0' suffix and a leading scope are tolerated; missing variables raise KeyError."""
         clean = {}
         for k, v in arrays.items():
@@ -731,7 +773,7 @@ class ConvolutionalModel:
             d[n] = clean[hit[0]]
             if d[n].shape != tuple(self.net.w[n].shape):
                 raise ValueError("variable %r: checkpoint shape %s, network %s" % (n, d[n].shape, tuple(self.net.w[n].shape)))
-            for slot in ("/Momentum", "/Adam", "/Adam_1"):
+            for slot in ("/Momentum", "/Adam", "/Adam_1", EMA_SUFFIX):
                 hit = [k for k in clean if k == n + slot or k.endswith("/" + n + slot)]
                 if hit:
                     d[n + slot] = clean[hit[0]]

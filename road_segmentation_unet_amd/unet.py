@@ -6,6 +6,7 @@ layouts, float32), their Momentum slots, the activation buffers and the backward
 (tf_aerial_images.py:103-122). PyTorch is only the device-memory / stream / collective plumbing: every
 arithmetic kernel on the path is a hand-written HIP kernel reached through librsu_hip.so.
 """
+import contextlib
 import ctypes
 import math
 import os
@@ -120,6 +121,31 @@ def _clip_arg(value):
     return v
 
 
+def _ema_arg(value):
+    """UNet's ema_decay: None or 0 (no averaging), or a float in (0, 1)"""
+    if value is None:
+        return None
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if isinstance(value, bool) or not (0.0 <= v and np.float32(v) < np.float32(1.0)):   # (below 1 as the float32 the kernel's scalar comes from)
+        raise _lib.RsuError("ema_decay must be None or a float in [0, 1), not %r" % (value,))
+    return v if v > 0.0 else None
+
+
+def ema_decay_at(decay, t, warmup=True):
+    """The decay of the moving average's update number t (t = 1 for the first: the global_step the optimizer step has just produced),
+    float32 as tf.train.ExponentialMovingAverage computes it: with warm-up (its num_updates rule) min(f32(decay), f32(1 + t) / f32(10 + t)),
+    else f32(decay). Returns a numpy float32; the kernel gets f32(1) - it."""
+    f = np.float32
+    d = f(decay)
+    if warmup:
+        d = min(d, f(1 + int(t)) / f(10 + int(t)))
+    return f(d)
+
+
+EMA_SUFFIX = "/ExponentialMovingAverage"   # TensorFlow's name of a variable's shadow
 OPTIMIZERS = ("momentum", "adam")
 
 
@@ -135,7 +161,7 @@ class UNet:
 
     def __init__(self, num_layers, root_size, dilated_layers, batch_size, patch_size, device="cuda:0", params=None, seed=2017,
                  training=True, optimizer="momentum", class_weights=None, dice_weight=0.0, dice_smooth=1.0, border_weight=0.0, border_sigma=5.0,
-                 clip_grad_norm=None):
+                 clip_grad_norm=None, ema_decay=None, ema_warmup=True):
         """optimizer: "momentum" (the reference's MomentumOptimizer: apply_momentum) or "adam" (tf.train.AdamOptimizer: apply_adam; a
         second fp32 slot per variable, flat_v).
         class_weights: None or a pair (w0, w1) of finite floats >= 0, not both 0: the weighted cross-entropy of rsu.h
@@ -149,11 +175,20 @@ class UNet:
         clip_grad_norm: None, or c > 0 (finite): apply_momentum / apply_adam first take the global norm of the live gradient on the
         device (rsu.h rsu_grad_norm) and step with the gradient scaled by min(1, c / norm); a step whose gradient holds an inf or a nan, or
         whose sum of squares overflows, changes nothing (see apply_momentum). No host synchronisation; clip_stats() reads the counters.
-        A huge c only measures and guards. None: no buffer, no launch, the step is what it always was."""
+        A huge c only measures and guards. None: no buffer, no launch, the step is what it always was.
+        ema_decay: None (or 0), or d in (0, 1): apply_momentum / apply_adam end with one rsu_ema_step launch (rsu.h) that moves flat_ema,
+        a float32 shadow of flat_w initialised to the initial weights, by tf.train.ExponentialMovingAverage's rule at the decay
+        ema_decay_at(d, global_step, ema_warmup); averaged_weights() evaluates with it; state_dict() carries it as
+        `<var>/ExponentialMovingAverage`. ema_warmup: TensorFlow's num_updates rule, min(d, (1 + t) / (10 + t)). Training nets only.
+        None: no buffer, no launch, the step is what it always was."""
         if optimizer not in OPTIMIZERS:
             raise _lib.RsuError("optimizer must be one of %s, not %r" % ("|".join(OPTIMIZERS), optimizer))
         self.optimizer = optimizer
         self.clip_grad_norm = _clip_arg(clip_grad_norm)
+        self.ema_decay, self.ema_warmup = _ema_arg(ema_decay), bool(ema_warmup)
+        if self.ema_decay is not None and not training:
+            raise _lib.RsuError("a forward-only net takes no optimizer step: it has nothing to average")
+        self.flat_ema, self.ema, self._averaged = None, {}, False   # the shadow of flat_w, its per-variable views; inside averaged_weights()?
         self.clip_state = self._clip_ws = None   # the device-resident state record (rsu.h, 8 x 32 bit) and the norm's workspace, with clipping
         assert root_size % 8 == 0 and (root_size // 8) & (root_size // 8 - 1) == 0, "root_size must be 8 * 2^k for the HIP path"
         self.L, self.root, self.dilated = num_layers, root_size, bool(dilated_layers)
@@ -321,6 +356,10 @@ class UNet:
             if self.flat_v is not None:
                 self.v[n] = self.flat_v[o:o + cnt].view(s)
             self.w[n].copy_(torch.from_numpy(np.ascontiguousarray(init[n], dtype=np.float32)))
+        if self.ema_decay is not None:
+            # TensorFlow initialises a shadow to its variable's initial value; the dead dilated pair behind n_live keeps that value
+            self.flat_ema = self.flat_w.clone()
+            self.ema = {n: self.flat_ema[o:o + cnt].view(s) for n, (o, cnt, s) in self._slices.items()}
         self.global_step = 0
         # Adam's float32 accumulators beta1^t, beta2^t (None: not started -- the first apply_adam sets them to its (beta1, beta2),
         # the initial values TensorFlow gives them)
@@ -328,8 +367,11 @@ class UNet:
 
     def state_dict(self):
         """TF variable names, TF layouts (HWIO / [kh,kw,out,in]) + Momentum slots + global_step. An Adam net: the slots are
-        `<var>/Adam` (m) and `<var>/Adam_1` (v), plus the float32 scalars `beta1_power` and `beta2_power` once a step has set them."""
+        `<var>/Adam` (m) and `<var>/Adam_1` (v), plus the float32 scalars `beta1_power` and `beta2_power` once a step has set them.
+        An averaging net (ema_decay): `<var>/ExponentialMovingAverage`, TensorFlow's shadow-variable name, for every variable."""
+        self._not_averaged("state_dict")
         d = {n: self.w[n].detach().cpu().numpy().copy() for n in self.names}
+        d.update({n + EMA_SUFFIX: self.ema[n].detach().cpu().numpy().copy() for n in self.ema})
         if self.optimizer == "adam":
             d.update({n + "/Adam": self.acc[n].detach().cpu().numpy().copy() for n in self.names})
             d.update({n + "/Adam_1": self.v[n].detach().cpu().numpy().copy() for n in self.names})
@@ -344,7 +386,10 @@ class UNet:
         """Weights, slots and global_step from a state_dict() (or a TensorFlow checkpoint renamed to it). A Momentum net reads the
         `/Momentum` slots present and ignores Adam keys. An Adam net reads `/Adam`, `/Adam_1`, `beta1_power`, `beta2_power`; a checkpoint
         without Adam slots (a Momentum run's) loads the weights and global_step, zeroes m and v and resets the powers: the next
-        apply_adam starts them at its (beta1, beta2), as a fresh AdamOptimizer does."""
+        apply_adam starts them at its (beta1, beta2), as a fresh AdamOptimizer does. An averaging net reads
+        `<var>/ExponentialMovingAverage`; a variable whose key is missing gets the loaded weights as its average (a shadow starts at its
+        variable's value). A net without averaging ignores those keys."""
+        self._not_averaged("load_state_dict")
         self._load_count = getattr(self, "_load_count", 0) + 1
         adam = self.optimizer == "adam"
         have_adam = adam and any(n + "/Adam" in d for n in self.names)
@@ -358,6 +403,8 @@ class UNet:
                         t.zero_()
             elif n + "/Momentum" in d:
                 self.acc[n].copy_(torch.from_numpy(np.ascontiguousarray(d[n + "/Momentum"], dtype=np.float32)))
+            if self.flat_ema is not None:
+                self.ema[n].copy_(torch.from_numpy(np.ascontiguousarray(d.get(n + EMA_SUFFIX, d[n]), dtype=np.float32)))
         if adam:
             if have_adam and "beta1_power" in d and "beta2_power" in d:
                 self.beta1_power, self.beta2_power = np.float32(d["beta1_power"]), np.float32(d["beta2_power"])
@@ -771,6 +818,7 @@ class UNet:
         dice_weight / world. With dice_scale == 0 the pass is exactly the one described above.
         update = (lr0, momentum): accepted from callers that name the Momentum step they will take; it changes nothing here -- the step
         is apply_momentum's -- but a net built with another optimizer refuses it."""
+        self._not_averaged("backward_device")
         if update is not None and self.optimizer != "momentum":
             raise _lib.RsuError("backward_device(update=...) is the Momentum step; an %s net steps with apply_%s after the pass"
                                 % (self.optimizer, self.optimizer))
@@ -1003,6 +1051,53 @@ class UNet:
         return {"steps": int(raw[4]), "clipped": int(raw[5]), "skipped": int(raw[6]), "norm": float(f[1]), "scale": float(f[2]),
                 "sumsq": float(f[0]), "last_clipped": bool(flags & _lib.CLIP_CLIPPED), "last_skipped": bool(flags & _lib.CLIP_NONFINITE)}
 
+    # ------------------------------------------------------------------ moving average of the weights
+    def _ema_step(self):
+        """an averaging net, at the end of its optimizer step, on the update pass's stream and behind it: flat_ema[0:n_live) moves towards
+        the weights the step has just written, at the decay of update number global_step (already advanced). One launch (rsu.h
+        rsu_ema_step), no host synchronisation. A clipping net hands its record on: a step the update pass skipped moves no average.
+        Under data parallelism every rank averages the same weights: nothing is exchanged."""
+        if self.flat_ema is None:
+            return
+        omd = np.float32(1.0) - ema_decay_at(self.ema_decay, self.global_step, self.ema_warmup)
+        call("rsu_ema_step", _ptr(self.flat_ema), _ptr(self.flat_w), self.n_live, float(omd), _ptr(self.clip_state), self._stream())
+
+    def _not_averaged(self, what):
+        if self._averaged:
+            raise _lib.RsuError("%s inside averaged_weights(): flat_w holds the averages there, forward passes only" % what)
+
+    def _swap_averages(self):
+        tmp = self.flat_w.clone()
+        self.flat_w.copy_(self.flat_ema)
+        self.flat_ema.copy_(tmp)
+        self.repack()
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """Forward-only use of the averages: on entry flat_w and flat_ema exchange their contents (all n_flat floats, device copies
+        through a temporary, on the current stream) and repack() rebuilds the bf16 MFMA copies, so every forward launch inside -- packed
+        convs, biases, colour adjust, the 1x1 head -- reads the averages; on exit they exchange back and repack() runs again.
+        apply_momentum, apply_adam, backward_device, state_dict, load_state_dict and a nested entry raise RsuError inside. A net without
+        averages: a no-op context.
+        What the exit leaves, checked against the code: flat_w and flat_ema hold their earlier bits (three whole-buffer copies each way);
+        the optimizer slots, flat_g and global_step are never touched; every packed buffer is rewritten by repack() from the restored
+        flat_w. There is ONE set of packed buffers (self.pk: no double-buffered backward packs exist in this tree), the pack table is
+        built once in __init__ and covers every pk tensor a training net has, backward packs included, and rsu_pack_table_run writes
+        the bits the update pass writes for the same weights (rsu.h; tests/test_gpu_ops.py, tests/test_gpu_adam.py) -- so the packed
+        copies are those a following training step expects, and the update table, which holds pointers to the same buffers, stays
+        valid. tests/test_gpu_ema.py compares all of it bit for bit and takes one more step beside a twin."""
+        if self.flat_ema is None:
+            yield self
+            return
+        self._not_averaged("averaged_weights")
+        self._swap_averages()
+        self._averaged = True
+        try:
+            yield self
+        finally:
+            self._averaged = False
+            self._swap_averages()
+
     def apply_momentum(self, lr0, momentum, gscale=1.0):
         """MomentumOptimizer step on every live variable (tf_aerial_images.py:120-121) and the re-pack of the bf16 MFMA copies, in one
         pass over the parameters (rsu_update_table_run; RSU_FUSED_UPDATE=0: rsu_momentum_step, then the batched re-pack -- same bits).
@@ -1012,22 +1107,21 @@ class UNet:
         while m and v stay untouched; clip_stats() tells how often it happened."""
         if self.optimizer != "momentum":
             raise _lib.RsuError("apply_momentum on a net built with optimizer=%r" % self.optimizer)
+        self._not_averaged("apply_momentum")
         if self.clip_grad_norm is not None:
             self._grad_norm()
             tab = self._update_table or self._build_update_table()
             call("rsu_update_table_run_clip", _ptr(tab[0]), tab[1], tab[2], self.learning_rate(lr0), momentum, gscale, _ptr(self.clip_state),
                  self._stream())
-            self.global_step += 1
-            return
-        if os.environ.get("RSU_FUSED_UPDATE", "1") == "0":
+        elif os.environ.get("RSU_FUSED_UPDATE", "1") == "0":
             call("rsu_momentum_step", _ptr(self.flat_w), _ptr(self.flat_acc), _ptr(self.flat_g), self.learning_rate(lr0), momentum, gscale,
                  self.n_live, self._stream())
-            self.global_step += 1
             self.repack()
-            return
-        tab = self._update_table or self._build_update_table()
-        call("rsu_update_table_run", _ptr(tab[0]), tab[1], tab[2], self.learning_rate(lr0), momentum, gscale, self._stream())
+        else:
+            tab = self._update_table or self._build_update_table()
+            call("rsu_update_table_run", _ptr(tab[0]), tab[1], tab[2], self.learning_rate(lr0), momentum, gscale, self._stream())
         self.global_step += 1
+        self._ema_step()
 
     def apply_adam(self, lr0, beta1=0.9, beta2=0.999, epsilon=1e-8, gscale=1.0):
         """tf.train.AdamOptimizer step on every live variable (TensorFlow 1.x ApplyAdam at the decayed rate learning_rate(lr0)) and the
@@ -1038,6 +1132,7 @@ class UNet:
         and the beta powers (see apply_momentum)."""
         if self.optimizer != "adam":
             raise _lib.RsuError("apply_adam on a net built with optimizer=%r" % self.optimizer)
+        self._not_averaged("apply_adam")
         if self.clip_grad_norm is not None:
             self._grad_norm()   # (raises under RSU_FUSED_UPDATE=0, before the powers are touched)
         if self.beta1_power is None:
@@ -1055,6 +1150,7 @@ class UNet:
             call("rsu_update_table_run_adam", _ptr(tab[0]), tab[1], tab[2], *args, self._stream())
         self.global_step += 1
         self.beta1_power, self.beta2_power = b1p, b2p
+        self._ema_step()
 
 
 _DEFAULT_MODELS = {}
