@@ -482,6 +482,42 @@ int rsu_overlap_add(const float* prob, float* acc, float* hits, int nimg, int H,
                     long ntiles, rsu_stream_t stream);
 int rsu_overlap_finish(const float* acc, const float* hits, float* out, long n, rsu_stream_t stream);
 
+/* ---- training input: one launch per batch, with rotation and scale (new) -------------------- */
+/* Cuts the input windows and label patches of a batch out of the resident training images, each sample through a 2x2 matrix of its own
+ * about its window's centre. images f32 [nimg][He][He][3]: the mirror-extended images of the patch pool; labels uint8 [nimg][Hl][Hl] in
+ * {0, 1}; offset = (He - Hl) / 2 = (S - P) / 2 (both differences even). recs: nrec records in HOST memory, read before the call returns;
+ * x_out f32 [nrec][S][S][3]; labels_out int64 [nrec][P][P].
+ * Record r: `image` in [0, nimg); (cy, cx) the centre of the window in the EXTENDED image's pixel coordinates, row and column (the pool's
+ * patch at (x0, y0): cy = y0 + (S - 1) / 2, cx = x0 + (S - 1) / 2); M = [[m00, m01], [m10, m11]] maps an output offset (rows, columns)
+ * to a source offset. Input pixel (i, j), all arithmetic float32, every operation rounded on its own, in this order:
+ *   di = i - (S - 1) / 2,  dj = j - (S - 1) / 2
+ *   sy = (cy - offset) + (m00 * di + m01 * dj),  sx = (cx - offset) + (m10 * di + m11 * dj)      (the ORIGINAL image's frame)
+ *   y0 = floorf(sy), fy = sy - y0; x0 = floorf(sx), fx = sx - x0; taps: rows y0, y0 + 1, columns x0, x0 + 1
+ *   each tap index t reflected on its own into [0, Hl): m = ((t % 2Hl) + 2Hl) % 2Hl, index = m < Hl ? m : 2Hl - 1 - m (numpy's
+ *   "symmetric" padding, images.py mirror_border, repeated as often as needed), then read at (index + offset) of the extended image
+ *   value, per channel = (v00 * (1 - fx) + v01 * fx) * (1 - fy) + (v10 * (1 - fx) + v11 * fx) * fy      (v<row tap><column tap>)
+ * With fx = fy = 0 this is the source pixel bit for bit (finite data; a -0.0 may come out as +0.0). Label pixel (i, j): the same with
+ * (P - 1) / 2 in place of (S - 1) / 2, the uint8 labels read as floats and reflected in their own [Hl][Hl] frame; 1 where the
+ * interpolated value is >= 0.5, else 0. Window and patch are concentric, and image and labels reflect about the same edges: a rotated
+ * window never pairs mirrored pixels with unmirrored labels. The identity matrix gives the pool's plain window, the eight signed
+ * permutation matrices its D4 symmetries, (1 / s) R(theta) a rotation by theta with zoom s. hostio.affine_patches restates the rule in
+ * numpy float32: the outputs are reproducible bit for bit on the host.
+ * The records travel as kernel arguments, RSU_AFFINE_MAX_LAUNCH per launch: ceil(nrec / 32) launches on `stream`, no device table, no
+ * copy, no synchronisation, no allocation. A sample's output depends on its own record alone, not on its neighbours or on where the
+ * record list is cut. Errors, returned before anything is launched or written: RSU_EINVAL for a NULL images, labels, recs, x_out or
+ * labels_out, nrec, nimg, Hl or P below 1, S < P, He - Hl or S - P odd or different, an `image` outside [0, nimg), a record field that
+ * is not finite, max |m| > 64 or a centre beyond +-2^22 (together they keep every coordinate far inside float32's exact-integer range);
+ * RSU_E2BIG where one image or one output tensor reaches 2 GiB (the image base is 64-bit: the pool as a whole may exceed 2 GiB). */
+typedef struct {
+    int image;
+    float cy, cx;
+    float m00, m01, m10, m11;
+    int pad_;
+} rsu_affine_t; /* 32 bytes */
+#define RSU_AFFINE_MAX_LAUNCH 32
+int rsu_affine_patches(const float* images, const uint8_t* labels, const rsu_affine_t* recs /* HOST pointer */, int nrec, int nimg, int He,
+                       int Hl, int S, int P, float* x_out, int64_t* labels_out, rsu_stream_t stream);
+
 /* ---- post-processing wire format (src/images.py) and metric counters (src/summary.py) ------ */
 /* images.py:256-266 quantize_mask: per patch_size block of masks f32 [nimg][S][S] (channel axis squeezed), label =
  * mean(mask >= 0.5) > threshold, written over the block of `out` (out == masks is allowed: a block is read completely before it

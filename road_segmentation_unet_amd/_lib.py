@@ -35,6 +35,11 @@ class RsuPlanTotals(ctypes.Structure):
     _fields_ = [("input_size", _i), ("num_params", _l), ("activation_elems", _l), ("workspace_floats", _sz)]
 
 
+class RsuAffine(ctypes.Structure):
+    """rsu_affine_t: one sample of rsu_affine_patches (32 bytes; AFFINE_DTYPE is the same record as a numpy dtype)"""
+    _fields_ = [("image", _i), ("cy", _f), ("cx", _f), ("m00", _f), ("m01", _f), ("m10", _f), ("m11", _f), ("pad_", _i)]
+
+
 _PS = ctypes.POINTER(RsuSrc)
 _PI = ctypes.POINTER(ctypes.c_int)
 
@@ -121,6 +126,7 @@ SIGNATURES = {
     "rsu_extract_tiles": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _l, _l, _vp]),
     "rsu_overlap_add": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _l, _l, _vp]),
     "rsu_overlap_finish": (_i, [_vp, _vp, _vp, _l, _vp]),
+    "rsu_affine_patches": (_i, [_vp, _vp, ctypes.POINTER(RsuAffine), _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "rsu_quantize_mask": (_i, [_vp, _vp, _i, _i, _i, _f, _vp]),
     "rsu_labels_for_patches": (_i, [_vp, _vp, _i, _i, _i, _f, _vp]),
     "rsu_confusion_counts": (_i, [_vp, _vp, _l, _vp, _vp]),
@@ -154,6 +160,7 @@ TUNE_OFF, TUNE_LOOKUP, TUNE_MEASURE = 0, 1, 2   # rsu.h RSU_TUNE_*
 EVAL_BINS = 256   # rsu.h RSU_EVAL_BINS
 BORDER_D2_INF, BORDER_MAX_SIDE = 0x7fffffff, 1024   # rsu.h RSU_BORDER_D2_INF, RSU_BORDER_MAX_SIDE
 CLIP_STATE_BYTES, CLIP_CLIPPED, CLIP_NONFINITE, GRAD_NORM_BLOCK_FLOATS = 32, 1, 2, 16384   # rsu.h RSU_CLIP_*, RSU_GRAD_NORM_BLOCK_FLOATS
+AFFINE_MAX_LAUNCH = 32   # rsu.h RSU_AFFINE_MAX_LAUNCH
 E2BIG = -7
 
 

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/rsu.h"
+#include "affine_patches.h"
 #include "border_map.h"
 #include "elementwise.h"
 #include "igemm.h"
@@ -1503,6 +1504,23 @@ extern "C" int rsu_border_map(const int64_t* labels, const float* mul, float* ou
     // -1 / (2 sigma^2), in double and rounded once: the host mirror forms the same float
     const float neg_inv_2s2 = (float)(-1.0 / (2.0 * (double)sigma * (double)sigma));
     HIP_CHECK_RET(bm_border_map(labels, mul, out, d2, ws, N, H, W, w0, neg_inv_2s2, (hipStream_t)stream));
+    return RSU_OK;
+}
+static_assert(RSU_AFFINE_MAX_LAUNCH == AP_MAX_LAUNCH && sizeof(rsu_affine_t) == sizeof(ApRec) && sizeof(rsu_affine_t) == 32,
+              "rsu.h and affine_patches.h must agree on the record and on the records per launch");
+extern "C" int rsu_affine_patches(const float* images, const uint8_t* labels, const rsu_affine_t* recs, int nrec, int nimg, int He, int Hl, int S,
+                                  int P, float* x_out, int64_t* labels_out, rsu_stream_t stream) {
+    if (!images || !labels || !recs || !x_out || !labels_out || nrec < 1 || nimg < 1 || Hl < 1 || P < 1 || S < P) return RSU_EINVAL;
+    if (He < Hl || ((He - Hl) & 1) || ((S - P) & 1) || He - Hl != S - P) return RSU_EINVAL;
+    for (int r = 0; r < nrec; ++r) {
+        const rsu_affine_t& a = recs[r];
+        if (a.image < 0 || a.image >= nimg) return RSU_EINVAL;
+        const float f[6] = {a.cy, a.cx, a.m00, a.m01, a.m10, a.m11};
+        for (int k = 0; k < 6; ++k)
+            if (!std::isfinite(f[k]) || std::fabs(f[k]) > (k < 2 ? 4194304.f : 64.f)) return RSU_EINVAL;
+    }
+    if ((long)He * He * 12 >= 0x7ffffff0L || (long)nrec * S * S * 12 >= 0x7ffffff0L || (long)nrec * P * P * 8 >= 0x7ffffff0L) return RSU_E2BIG;
+    HIP_CHECK_RET(ap_affine_patches(images, labels, (const ApRec*)recs, nrec, He, Hl, S, P, x_out, labels_out, (hipStream_t)stream));
     return RSU_OK;
 }
 extern "C" int rsu_momentum_step(float* w, float* acc, const float* g, float lr, float mu, float gscale, long n, rsu_stream_t stream) {

@@ -290,3 +290,82 @@ def border_weight_map(labels, w0, sigma, mul=None):
             border = np.where(valid, mulf, np.float32(1.0)) * border
     out = np.where(valid, border, np.float32(0.0)).astype(np.float32)
     return out.reshape(shape), d2.astype(np.int32).reshape(shape)
+
+
+# include/rsu.h rsu_affine_t as a numpy record (32 bytes) and the bounds rsu_affine_patches checks
+AFFINE_DTYPE = np.dtype([("image", "<i4"), ("cy", "<f4"), ("cx", "<f4"), ("m00", "<f4"), ("m01", "<f4"), ("m10", "<f4"), ("m11", "<f4"),
+                         ("pad_", "<i4")])
+AFFINE_MAX_M, AFFINE_MAX_CENTRE = 64.0, float(1 << 22)
+
+
+def affine_records(recs):
+    """recs as an AFFINE_DTYPE array [n]: such an array itself, or a sequence of (image, cy, cx, m00, m01, m10, m11)"""
+    if isinstance(recs, np.ndarray) and recs.dtype == AFFINE_DTYPE:
+        return np.ascontiguousarray(recs.reshape(-1))
+    out = np.zeros(len(recs), dtype=AFFINE_DTYPE)
+    for k, r in enumerate(recs):
+        out[k] = tuple(r)[:7] + (0,)
+    return out
+
+
+def _affine_source(rec, n, offset, Hl):
+    """per pixel of an [n][n] output centred at (n - 1) / 2: the reflected tap rows y0, y1 and columns x0, x1 ([n][n] int64) and the
+    fractions fy, fx ([n][n] float32), by the float32 operations of csrc/affine_patches.hip ap_source, one numpy operation each"""
+    f = np.float32
+    d = np.arange(n, dtype=np.float32) - f(n - 1) * f(0.5)
+    di, dj = d[:, None], d[None, :]
+    off = f(offset)
+    sy = (f(rec["cy"]) - off) + (f(rec["m00"]) * di + f(rec["m01"]) * dj)
+    sx = (f(rec["cx"]) - off) + (f(rec["m10"]) * di + f(rec["m11"]) * dj)
+    ty, tx = np.floor(sy), np.floor(sx)
+    fy, fx = sy - ty, sx - tx
+
+    def reflect(t):
+        m = np.mod(t, 2 * Hl)   # (numpy's mod is the floored one: ((t % 2Hl) + 2Hl) % 2Hl of C)
+        return np.where(m < Hl, m, 2 * Hl - 1 - m)
+    ty, tx = ty.astype(np.int64), tx.astype(np.int64)
+    return reflect(ty), reflect(ty + 1), reflect(tx), reflect(tx + 1), fy.astype(np.float32), fx.astype(np.float32)
+
+
+def _affine_lerp(v00, v01, v10, v11, fy, fx):
+    gy, gx = np.float32(1.0) - fy, np.float32(1.0) - fx
+    return (v00 * gx + v01 * fx) * gy + (v10 * gx + v11 * fx) * fy
+
+
+def affine_patches(images, labels, recs, S, P):
+    """The one-launch batch loader on the host: the numpy float32 statement of include/rsu.h rsu_affine_patches, operation for operation
+    (numpy rounds every float32 operation on its own, as csrc/affine_patches.hip is compiled to do): x and labels equal the device's bit
+    for bit. images: float32 [nimg, He, He, 3], the mirror-extended images; labels: [nimg, Hl, Hl] in {0, 1}; recs: an AFFINE_DTYPE array
+    or a sequence of (image, cy, cx, m00, m01, m10, m11), with (cy, cx) the window's centre in the extended image (row, column) and
+    M = [[m00, m01], [m10, m11]] mapping an output offset to a source offset. Every tap is reflected about the ORIGINAL image's edges
+    (symmetric padding, repeated). Returns (x float32 [n, S, S, 3], labels int64 [n, P, P]). ValueError for what the ABI refuses."""
+    img = np.asarray(images)
+    lab = np.asarray(labels)
+    S, P = int(S), int(P)
+    if img.ndim != 4 or img.shape[3] != 3 or img.shape[1] != img.shape[2] or lab.ndim != 3 or lab.shape[1] != lab.shape[2] \
+            or lab.shape[0] != img.shape[0] or img.dtype != np.float32:
+        raise ValueError("affine_patches: images must be float32 [n, He, He, 3] and labels [n, Hl, Hl], not %s %s and %s"
+                         % (img.dtype, img.shape, lab.shape))
+    nimg, He, Hl = img.shape[0], img.shape[1], lab.shape[1]
+    if P < 1 or S < P or He < Hl or (He - Hl) % 2 or (S - P) % 2 or He - Hl != S - P:
+        raise ValueError("affine_patches: He - Hl = %d and S - P = %d must be even and equal, with S >= P >= 1" % (He - Hl, S - P))
+    recs = affine_records(recs)
+    if recs.size < 1:
+        raise ValueError("affine_patches: no records")
+    vals = np.stack([recs[k] for k in ("cy", "cx", "m00", "m01", "m10", "m11")], axis=1)
+    if not np.all(np.isfinite(vals)) or np.abs(vals[:, 2:]).max() > AFFINE_MAX_M or np.abs(vals[:, :2]).max() > AFFINE_MAX_CENTRE \
+            or recs["image"].min() < 0 or recs["image"].max() >= nimg:
+        raise ValueError("affine_patches: every record needs an image in [0, %d), finite fields, |m| <= 64 and a centre within 2^22" % nimg)
+    offset = (He - Hl) // 2
+    labf = lab.astype(np.float32)
+    x = np.empty((recs.size, S, S, 3), np.float32)
+    y = np.empty((recs.size, P, P), np.int64)
+    for k, rec in enumerate(recs):
+        n = int(rec["image"])
+        y0, y1, x0, x1, fy, fx = _affine_source(rec, S, offset, Hl)
+        im = img[n, offset:offset + Hl, offset:offset + Hl]   # (index + offset) of the extended image
+        x[k] = _affine_lerp(im[y0, x0], im[y0, x1], im[y1, x0], im[y1, x1], fy[..., None], fx[..., None])
+        y0, y1, x0, x1, fy, fx = _affine_source(rec, P, offset, Hl)
+        lf = labf[n]
+        y[k] = _affine_lerp(lf[y0, x0], lf[y0, x1], lf[y1, x0], lf[y1, x1], fy, fx) >= np.float32(0.5)
+    return x, y

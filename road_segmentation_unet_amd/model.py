@@ -91,6 +91,14 @@ EXTRA_FLAG_DEFS = [
                               "updated on the GPU after every optimizer step; 0 = off. Validation, --save_best, prediction and the final "
                               "inference then use the averaged weights; checkpoints hold both the raw weights and the averages"),
     ("ema_warmup", bool, True, "TensorFlow's num_updates rule for --ema_decay: the decay of update t is min(d, (1 + t) / (10 + t))"),
+    ("random_rotation", float, 0.0, "Rotate every training sample by a random angle in [-DEG, DEG] degrees (finite, >= 0; 0 = off; 180 = any "
+                                    "orientation), bilinear, mirrored at the image's edges, on the GPU as the batch is cut: no further copy of "
+                                    "the training set. Needs --device_patch_pool; composes with --d4_augmentation and --random_scale"),
+    ("random_scale", str, "1,1", "LO,HI: zoom every training sample by a random log-uniform factor in [LO, HI] (1/64 < LO <= HI <= 64; "
+                                 "1,1 = off), in the same launch as --random_rotation. Needs --device_patch_pool"),
+    ("one_launch_loader", bool, False, "Cut plain and --d4_augmentation batches with the one-launch loader kernel too: the bits of the "
+                                       "per-sample copies it replaces for unrotated images; in the border band of a --rotation_angles copy "
+                                       "it shows the mirror of the image instead of rotated content. Needs --device_patch_pool"),
 ]
 
 
@@ -181,6 +189,36 @@ def parse_ema_decay(value):
     if isinstance(value, bool) or not (0.0 <= v and np.float32(v) < np.float32(1.0)):
         raise ValueError("--ema_decay must be 0 (off) or a float in (0, 1), not %r" % (value,))
     return v
+
+
+def parse_random_rotation(value):
+    """The --random_rotation value as a float of degrees: finite and >= 0 (0.0 = off). Anything else raises ValueError."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if isinstance(value, bool) or not (math.isfinite(v) and v >= 0.0):
+        raise ValueError("--random_rotation must be a finite number of degrees >= 0, not %r" % (value,))
+    return v
+
+
+def parse_random_scale(value):
+    """The --random_scale value: "LO,HI" or a pair of numbers -> (lo, hi) as floats with 1/64 < lo <= hi <= 64 ((1.0, 1.0) = off).
+    Anything else raises ValueError."""
+    if isinstance(value, str):
+        parts = value.split(",")
+    else:
+        try:
+            parts = list(value)
+        except TypeError:
+            parts = [value]
+    try:
+        sc = tuple(float(v) for v in parts)
+    except (TypeError, ValueError):
+        sc = ()
+    if len(sc) != 2 or not all(math.isfinite(v) for v in sc) or not (1.0 / 64 < sc[0] <= sc[1] <= 64.0):
+        raise ValueError("--random_scale must be 'LO,HI' with 1/64 < LO <= HI <= 64, not %r" % (value,))
+    return sc
 
 
 def dice_from_sums(I, P, Y, smooth):
@@ -281,6 +319,13 @@ class Options(object):
                 raise ValueError("--%s must be an integer >= 0, not %r" % (name, v))
             setattr(self, name, int(v))
         self.save_best = bool(self.save_best)
+        self.random_rotation, self.random_scale = parse_random_rotation(self.random_rotation), parse_random_scale(self.random_scale)
+        self.one_launch_loader = bool(self.one_launch_loader)
+        loader_flags = [name for name, on in (("--random_rotation", self.random_rotation > 0.0), ("--random_scale", self.random_scale != (1.0, 1.0)),
+                                              ("--one_launch_loader", self.one_launch_loader)) if on]
+        if loader_flags and not self.device_patch_pool:   # (not silently ignored, the way --d4_augmentation is there)
+            raise ValueError("%s cannot be combined with --nodevice_patch_pool: the kernel that applies them cuts the batches of the device "
+                             "patch pool; the host pool cuts plain windows only" % ", ".join(loader_flags))
         ra = self.rotation_angles
         if isinstance(ra, str):
             self.rotation_angles = None if not ra else [int(i) for i in ra.split(",")]

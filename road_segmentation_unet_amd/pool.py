@@ -14,7 +14,15 @@ patches in the same order, cut when a batch asks for them.
                    the graph feeds the augmented tensor itself, so the subgraph is bypassed): per sample,
                    flip up-down / flip left-right / transpose with probability 1/2 each, then rot90 by a uniform k in 0..3, applied
                    alike to the input window and its label patch. Off by default (parity with the reference's actual behaviour).
+                   With rotation > 0, scale != (1, 1) or one_launch, load_batch() is ONE rsu_affine_patches call (include/rsu.h) for the
+                   whole batch instead: every sample goes through a 2x2 matrix of its own, M = (1 / s) R(theta) D -- a random zoom s,
+                   a random rotation theta, the sample's D4 draw D -- with bilinear taps reflected about the original image's edges.
+                   Continuous rotation and zoom then cost no further copy of the training set; the plain window (M = 1) and D4 (M = D)
+                   are the same launch and deliver the loop's bits.
 """
+import ctypes
+import math
+
 import numpy as np
 import torch
 
@@ -73,17 +81,112 @@ def d4_apply(t, op):
     return t
 
 
+def d4_matrix(op):
+    """The 2x2 integer matrix D with d4_apply(t, op)[p] = t[D p] for pixel offsets p = (row, column) from the centre of the square: the
+    flips negate a coordinate, the transpose swaps them, one rot90 (counter-clockwise) reads (row, column) at (column, -row); d4_apply
+    runs them in that order, so the source offset of an output offset is U L T R^k p."""
+    ud, lr, tr, k = op
+    D = np.eye(2, dtype=np.int64)
+    if ud:
+        D = D @ np.array([[-1, 0], [0, 1]])
+    if lr:
+        D = D @ np.array([[1, 0], [0, -1]])
+    if tr:
+        D = D @ np.array([[0, 1], [1, 0]])
+    for _ in range(int(k) % 4):
+        D = D @ np.array([[0, 1], [-1, 0]])
+    return D
+
+
+def check_rotation_scale(rotation, scale):
+    """(rotation in degrees, (lo, hi)) as floats; ValueError unless rotation is finite and >= 0 and 1/64 < lo <= hi <= 64"""
+    try:
+        rot = float(rotation)
+        lo, hi = (float(v) for v in scale)
+    except (TypeError, ValueError):
+        rot = lo = hi = float("nan")
+    if not (math.isfinite(rot) and rot >= 0.0):
+        raise ValueError("rotation must be a finite number of degrees >= 0, not %r" % (rotation,))
+    if not (math.isfinite(lo) and math.isfinite(hi) and 1.0 / 64 < lo <= hi <= 64.0):
+        raise ValueError("scale must be (lo, hi) with 1/64 < lo <= hi <= 64, not %r" % (scale,))
+    return rot, (lo, hi)
+
+
+def affine_draw(rng, count, rotation=0.0, scale=(1.0, 1.0), d4=False):
+    """Per sample, in this order from `rng`: the four D4 uniforms of d4_draw (only with d4, so a D4-only draw consumes the stream exactly
+    as d4_draw does), u for the angle theta = (2u - 1) * rotation degrees (only with rotation > 0), u for the zoom s = exp(U(log lo,
+    log hi)) (only with scale != (1, 1)). Returns float32 [count, 2, 2]: M = (1 / s) R(theta) D, R(theta) = [[cos, -sin], [sin, cos]] on
+    (row, column) offsets, D = d4_matrix of the sample's draw; float64 arithmetic, rounded once. M maps an output offset to a source offset:
+    the sample shows its source zoomed IN by s."""
+    rot, (lo, hi) = check_rotation_scale(rotation, scale)
+    zoom = (lo, hi) != (1.0, 1.0)
+    ncol = (4 if d4 else 0) + (1 if rot > 0.0 else 0) + (1 if zoom else 0)
+    M = np.empty((count, 2, 2), np.float32)
+    u = rng.random_sample((count, ncol)) if ncol else np.zeros((count, 0))
+    for j in range(count):
+        col = 0
+        D = np.eye(2)
+        if d4:
+            a, b, c, d = u[j, :4]
+            D = d4_matrix((bool(a > 0.5), bool(b > 0.5), bool(c > 0.5), int(np.floor(d * 4)))).astype(np.float64)
+            col = 4
+        theta, s = 0.0, 1.0
+        if rot > 0.0:
+            theta = math.radians((2.0 * u[j, col] - 1.0) * rot)
+            col += 1
+        if zoom:
+            s = math.exp(math.log(lo) + u[j, col] * (math.log(hi) - math.log(lo)))
+        R = np.array([[math.cos(theta), -math.sin(theta)], [math.sin(theta), math.cos(theta)]])
+        M[j] = ((1.0 / s) * R) @ D
+    return M
+
+
 class DevicePatchPool(PatchPool):
-    def __init__(self, extended_images, extended_labels, input_size, patch_size, stride, device, augment=False, seed=2017):
+    def __init__(self, extended_images, extended_labels, input_size, patch_size, stride, device, augment=False, seed=2017,
+                 rotation=0.0, scale=(1.0, 1.0), one_launch=False):
+        """rotation: degrees; a sample is rotated by a uniform angle in [-rotation, rotation] (0 = off). scale: (lo, hi); a sample is
+        zoomed by a log-uniform factor in [lo, hi] ((1, 1) = off). one_launch: send plain and D4-only batches through the kernel too."""
         super().__init__(extended_images, extended_labels, input_size, patch_size, stride)
         self.device = torch.device(device)
         self.dev_images = torch.from_numpy(self.images).to(self.device)
         self.dev_labels = torch.from_numpy(self.labels).to(self.device)
         self.augment = bool(augment)
         self._rng = np.random.RandomState(seed)
+        self.rotation, self.scale = check_rotation_scale(rotation, scale)
+        self.one_launch = bool(one_launch) or self.rotation > 0.0 or self.scale != (1.0, 1.0)
+        if self.one_launch and self.images.shape[-1] != 3:
+            raise ValueError("the one-launch loader cuts 3-channel images, not %d channels" % self.images.shape[-1])
+
+    def affine_records(self, indices, matrices):
+        """the rsu_affine_t records (hostio.AFFINE_DTYPE) of patches `indices` under float32 `matrices` [b, 2, 2]"""
+        from .hostio import AFFINE_DTYPE
+        recs = np.zeros(len(indices), dtype=AFFINE_DTYPE)
+        half = (self.S - 1) / 2.0
+        for j, k in enumerate(indices):
+            n, x0, y0 = self.locate(k)
+            recs[j] = (n, y0 + half, x0 + half, matrices[j, 0, 0], matrices[j, 0, 1], matrices[j, 1, 0], matrices[j, 1, 1], 0)
+        return recs
+
+    def _load_batch_one_launch(self, indices, x_out, labels_out):
+        from . import _lib
+        b = len(indices)
+        if tuple(x_out.shape) != (b, self.S, self.S, 3) or x_out.dtype != torch.float32 or not x_out.is_contiguous() \
+                or tuple(labels_out.shape) != (b, self.P, self.P) or labels_out.dtype != torch.int64 or not labels_out.is_contiguous() \
+                or x_out.device != self.dev_images.device or labels_out.device != self.dev_images.device:
+            raise ValueError("load_batch: x_out must be a contiguous float32 [%d, %d, %d, 3] and labels_out a contiguous int64 [%d, %d, %d] "
+                             "on %s" % (b, self.S, self.S, b, self.P, self.P, self.dev_images.device))
+        recs = self.affine_records(indices, affine_draw(self._rng, b, self.rotation, self.scale, self.augment))
+        st = ctypes.c_void_p(torch.cuda.current_stream(self.dev_images.device).cuda_stream)
+        _lib.call("rsu_affine_patches", self.dev_images.data_ptr(), self.dev_labels.data_ptr(),
+                  recs.ctypes.data_as(ctypes.POINTER(_lib.RsuAffine)), b, self.images.shape[0], self.images.shape[1], self.labels.shape[1],
+                  self.S, self.P, x_out.data_ptr(), labels_out.data_ptr(), st)
+        return recs
 
     def load_batch(self, indices, x_out, labels_out):
-        """x_out f32 [b, S, S, C], labels_out int64 [b, P, P] (device tensors: the network's input buffers)"""
+        """x_out f32 [b, S, S, C], labels_out int64 [b, P, P] (device tensors: the network's input buffers). Returns the D4 draws (None
+        without augmentation), or the batch's records where the batch went through the one-launch loader."""
+        if self.one_launch:
+            return self._load_batch_one_launch(indices, x_out, labels_out)
         ops = d4_draw(self._rng, len(indices)) if self.augment else None
         for j, k in enumerate(indices):
             n, x0, y0 = self.locate(k)
