@@ -518,6 +518,48 @@ typedef struct {
 int rsu_affine_patches(const float* images, const uint8_t* labels, const rsu_affine_t* recs /* HOST pointer */, int nrec, int nimg, int He,
                        int Hl, int S, int P, float* x_out, int64_t* labels_out, rsu_stream_t stream);
 
+/* ---- training input: colour jitter and noise per sample, behind the loader (new) ------------- */
+/* Photometric augmentation of a finished batch, in place: sample n of x f32 [nrec][S][S][3] is transformed by record n alone. recs: nrec
+ * records in HOST memory, read before the call returns. Pixel p = i * S + j of a sample has channels x0, x1, x2. All arithmetic is
+ * float32, every operation rounded on its own, in the order written:
+ *   means   skipped when all nine k[] of the record are zero: then m = 0 and ws is never read for the sample. Otherwise, with
+ *             q(v)  = (int64) rintf(fminf(fmaxf(v, -256.f), 256.f) * 16777216.f)
+ *             sum_c = the exact int64 sum of q(x_c) over the sample's S * S pixels
+ *             m_c   = (float)((double)sum_c / ((double)(S * S) * 16777216.0))
+ *           (integer sums: the result does not depend on the order of summation, so the kernel is free in how it cuts the work, and the
+ *           host restates it with np.rint and an int64 sum)
+ *   colour  d_r = (k[3r] * m0 + k[3r+1] * m1) + k[3r+2] * m2
+ *           y_r = ((a[3r] * x0 + a[3r+1] * x1) + a[3r+2] * x2) + d_r
+ *   noise   only when sigma > 0. Element index e = 3 * p + r as unsigned; mix(v): v ^= v >> 16; v *= 0x85ebca6b; v ^= v >> 13;
+ *           v *= 0xc2b2ae35; v ^= v >> 16 (the finaliser the dropout hash uses);
+ *             h1 = mix(e ^ key), h2 = mix(h1 ^ 0x9e3779b9)
+ *             n  = (h1 & 0xffff) + (h1 >> 16) + (h2 & 0xffff) + (h2 >> 16)     an Irwin-Hall sum of four 16-bit uniforms: mean 131070,
+ *                                                                              standard deviation sqrt((65536^2 - 1) / 3) = 37837.227...
+ *             g  = ((float)n - 131070.f) * C,  C = the float with bits 0x37ddb3d7 (1 / 37837.227...)
+ *             y_r = y_r + sigma * g
+ *   clamp   out_r = fminf(fmaxf(y_r, 0.f), 1.f)      (a -0.0 may come out as +0.0)
+ * The identity record (A = I, K = 0, sigma = 0) returns data in [0, 1] bit for bit. With A = c b H Sat and K = (1 - c) b H Sat this is
+ * brightness b, contrast c about the sample's own per-channel mean (tf.image.adjust_contrast), saturation and hue in one pass
+ * (pool.jitter_draw). hostio.color_jitter restates the rule in numpy float32: the output is reproducible bit for bit on the host.
+ * Launches on `stream`, per RSU_JITTER_MAX_LAUNCH records (they travel as kernel arguments): one that sums (only when a record of the
+ * launch has a non-zero k[]) and one that applies; no memset, copy, allocation, atomics or synchronisation. ws: rsu_color_jitter_ws_bytes(nrec,
+ * S) bytes (0 for nrec or S below 1), 8-byte aligned: three int64 partial sums per 4096-pixel share of a sample, for the records of one
+ * launch -- every launch of a call re-uses it, stream order keeps them apart -- written before they are read, nothing to zero. A
+ * sample's output depends on its own record alone, not on its neighbours or on where the record list is cut.
+ * Errors, returned before anything is launched or written: RSU_EINVAL for a NULL x or recs, nrec or S below 1, a record field that is
+ * not finite, |a| or |k| above 64, sigma outside [0, 1], a NULL ws while some record has a non-zero k[], a ws that is not 8-byte aligned;
+ * RSU_E2BIG where x reaches 2 GiB. */
+typedef struct {
+    float a[9];    /* A, row-major: output channel r, input channel k at a[3r + k] */
+    float k[9];    /* K, likewise: the weight of the sample's channel means */
+    float sigma;   /* noise amplitude, >= 0 */
+    unsigned key;  /* noise key */
+} rsu_jitter_t;    /* 80 bytes */
+#define RSU_JITTER_MAX_LAUNCH 32
+size_t rsu_color_jitter_ws_bytes(int nrec, int S);
+int rsu_color_jitter(float* x /* f32 [nrec][S][S][3], in place */, const rsu_jitter_t* recs /* HOST pointer */,
+                     int nrec, int S, void* ws /* may be NULL when every k[] is zero */, rsu_stream_t stream);
+
 /* ---- post-processing wire format (src/images.py) and metric counters (src/summary.py) ------ */
 /* images.py:256-266 quantize_mask: per patch_size block of masks f32 [nimg][S][S] (channel axis squeezed), label =
  * mean(mask >= 0.5) > threshold, written over the block of `out` (out == masks is allowed: a block is read completely before it

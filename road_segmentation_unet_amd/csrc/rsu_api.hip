@@ -14,6 +14,7 @@
 
 #include "../../include/rsu.h"
 #include "affine_patches.h"
+#include "color_jitter.h"
 #include "border_map.h"
 #include "elementwise.h"
 #include "igemm.h"
@@ -1521,6 +1522,25 @@ extern "C" int rsu_affine_patches(const float* images, const uint8_t* labels, co
     }
     if ((long)He * He * 12 >= 0x7ffffff0L || (long)nrec * S * S * 12 >= 0x7ffffff0L || (long)nrec * P * P * 8 >= 0x7ffffff0L) return RSU_E2BIG;
     HIP_CHECK_RET(ap_affine_patches(images, labels, (const ApRec*)recs, nrec, He, Hl, S, P, x_out, labels_out, (hipStream_t)stream));
+    return RSU_OK;
+}
+static_assert(RSU_JITTER_MAX_LAUNCH == CJ_MAX_LAUNCH && sizeof(rsu_jitter_t) == sizeof(CjRec) && sizeof(rsu_jitter_t) == 80,
+              "rsu.h and color_jitter.h must agree on the record and on the records per launch");
+extern "C" size_t rsu_color_jitter_ws_bytes(int nrec, int S) { return (nrec >= 1 && S >= 1) ? cj_ws_bytes(nrec, S) : 0; }
+extern "C" int rsu_color_jitter(float* x, const rsu_jitter_t* recs, int nrec, int S, void* ws, rsu_stream_t stream) {
+    if (!x || !recs || nrec < 1 || S < 1) return RSU_EINVAL;
+    bool any_k = false;
+    for (int r = 0; r < nrec; ++r) {
+        const rsu_jitter_t& j = recs[r];
+        for (int i = 0; i < 9; ++i) {
+            if (!std::isfinite(j.a[i]) || std::fabs(j.a[i]) > 64.f || !std::isfinite(j.k[i]) || std::fabs(j.k[i]) > 64.f) return RSU_EINVAL;
+            any_k = any_k || j.k[i] != 0.f;
+        }
+        if (!std::isfinite(j.sigma) || !(j.sigma >= 0.f) || !(j.sigma <= 1.f)) return RSU_EINVAL;
+    }
+    if ((any_k && !ws) || ((uintptr_t)ws & 7)) return RSU_EINVAL;
+    if ((long)nrec * S * S * 12 >= 0x7ffffff0L) return RSU_E2BIG;
+    HIP_CHECK_RET(cj_color_jitter(x, (const CjRec*)recs, nrec, S, ws, (hipStream_t)stream));
     return RSU_OK;
 }
 extern "C" int rsu_momentum_step(float* w, float* acc, const float* g, float lr, float mu, float gscale, long n, rsu_stream_t stream) {

@@ -369,3 +369,81 @@ def affine_patches(images, labels, recs, S, P):
         lf = labf[n]
         y[k] = _affine_lerp(lf[y0, x0], lf[y0, x1], lf[y1, x0], lf[y1, x1], fy, fx) >= np.float32(0.5)
     return x, y
+
+
+# include/rsu.h rsu_jitter_t as a numpy record (80 bytes) and the bounds rsu_color_jitter checks
+JITTER_DTYPE = np.dtype([("a", "<f4", (9,)), ("k", "<f4", (9,)), ("sigma", "<f4"), ("key", "<u4")])
+JITTER_MAX_AK = 64.0
+JITTER_NOISE_SCALE = np.uint32(0x37ddb3d7).view(np.float32)   # 1 / sqrt((65536^2 - 1) / 3), the Irwin-Hall sum's standard deviation
+
+
+def jitter_records(recs):
+    """recs as a JITTER_DTYPE array [n]: such an array itself, or a sequence of (A [3][3] or [9], K likewise, sigma, key)"""
+    if isinstance(recs, np.ndarray) and recs.dtype == JITTER_DTYPE:
+        return np.ascontiguousarray(recs.reshape(-1))
+    out = np.zeros(len(recs), dtype=JITTER_DTYPE)
+    for j, (a, k, sigma, key) in enumerate(recs):
+        out[j] = (np.asarray(a, dtype=np.float32).reshape(9), np.asarray(k, dtype=np.float32).reshape(9), sigma, int(key) & 0xffffffff)
+    return out
+
+
+def _jitter_mix(v):
+    """the murmur3 finaliser on a uint32 array (csrc/color_jitter.hip cj_mix; products wrap modulo 2^32)"""
+    v = v ^ (v >> np.uint32(16))
+    v = v * np.uint32(0x85ebca6b)
+    v = v ^ (v >> np.uint32(13))
+    v = v * np.uint32(0xc2b2ae35)
+    return v ^ (v >> np.uint32(16))
+
+
+def jitter_noise_int(key, count):
+    """n of include/rsu.h rsu_color_jitter for the elements e = 0 .. count - 1 under `key`: uint32 [count], the sum of the four 16-bit
+    halves of h1 = mix(e ^ key) and h2 = mix(h1 ^ 0x9e3779b9)"""
+    e = np.arange(count, dtype=np.uint32)
+    h1 = _jitter_mix(e ^ np.uint32(int(key) & 0xffffffff))
+    h2 = _jitter_mix(h1 ^ np.uint32(0x9e3779b9))
+    m = np.uint32(0xffff)
+    return (h1 & m) + (h1 >> np.uint32(16)) + (h2 & m) + (h2 >> np.uint32(16))
+
+
+def color_jitter(x, recs):
+    """Per-sample colour jitter and noise on the host: the numpy float32 statement of include/rsu.h rsu_color_jitter, operation for
+    operation (numpy rounds every float32 operation on its own, as csrc/color_jitter.hip is compiled to do; the means come from exact
+    int64 sums): the result equals the device's bit for bit. x: float32 [n, S, S, 3]; recs: a JITTER_DTYPE array or a sequence of
+    (A, K, sigma, key), one per sample. Returns a new float32 array; x is left as it is. ValueError for what the ABI refuses."""
+    xs = np.asarray(x)
+    if xs.ndim != 4 or xs.shape[3] != 3 or xs.shape[1] != xs.shape[2] or xs.dtype != np.float32 or xs.shape[0] < 1 or xs.shape[1] < 1:
+        raise ValueError("color_jitter: x must be float32 [n, S, S, 3] with n, S >= 1, not %s %s" % (xs.dtype, xs.shape))
+    recs = jitter_records(recs)
+    if recs.size != xs.shape[0]:
+        raise ValueError("color_jitter: %d records for %d samples" % (recs.size, xs.shape[0]))
+    ak = np.concatenate([recs["a"], recs["k"]], axis=1)
+    if not np.all(np.isfinite(ak)) or np.abs(ak).max() > JITTER_MAX_AK or not np.all(np.isfinite(recs["sigma"])) \
+            or recs["sigma"].min() < 0.0 or recs["sigma"].max() > 1.0:
+        raise ValueError("color_jitter: every record needs finite fields, |a| and |k| <= 64 and sigma in [0, 1]")
+    if xs.size * 4 >= 0x7ffffff0:
+        raise ValueError("color_jitter: x reaches 2 GiB")
+    f = np.float32
+    n, S = xs.shape[0], xs.shape[1]
+    out = np.empty_like(xs)
+    for j, rec in enumerate(recs):
+        a, k, sigma = rec["a"], rec["k"], f(rec["sigma"])
+        px = xs[j].reshape(S * S, 3)
+        x0, x1, x2 = px[:, 0], px[:, 1], px[:, 2]
+        m = np.zeros(3, np.float32)
+        if np.any(k != 0):
+            q = np.rint(np.fmin(np.fmax(px, f(-256.0)), f(256.0)) * f(16777216.0)).astype(np.int64)
+            sums = q.sum(axis=0, dtype=np.int64)
+            m = (sums.astype(np.float64) / (np.float64(S * S) * 16777216.0)).astype(np.float32)
+        g = None
+        if sigma > 0:
+            g = ((jitter_noise_int(rec["key"], S * S * 3).astype(np.float32) - f(131070.0)) * JITTER_NOISE_SCALE).reshape(S * S, 3)
+        y = np.empty((S * S, 3), np.float32)
+        for r in range(3):
+            d = (k[3 * r] * m[0] + k[3 * r + 1] * m[1]) + k[3 * r + 2] * m[2]
+            yr = ((a[3 * r] * x0 + a[3 * r + 1] * x1) + a[3 * r + 2] * x2) + d
+            if g is not None:
+                yr = yr + sigma * g[:, r]
+            y[:, r] = np.fmin(np.fmax(yr, f(0.0)), f(1.0))
+        out[j] = y.reshape(S, S, 3)
+    return out

@@ -99,6 +99,12 @@ EXTRA_FLAG_DEFS = [
     ("one_launch_loader", bool, False, "Cut plain and --d4_augmentation batches with the one-launch loader kernel too: the bits of the "
                                        "per-sample copies it replaces for unrotated images; in the border band of a --rotation_angles copy "
                                        "it shows the mirror of the image instead of rotated content. Needs --device_patch_pool"),
+    ("color_jitter", str, "0,0,0,0", "B,C,S,H: per training sample, on the GPU behind the loader, a random brightness factor in [1-B, 1+B], "
+                                     "contrast factor in [1-C, 1+C] about the sample's own channel means, saturation factor in [1-S, 1+S] "
+                                     "and hue rotation in [-H, H] degrees (B, C, S in [0, 1), H in [0, 180]; 0,0,0,0 = off), clamped to "
+                                     "[0, 1] once at the end. Needs --device_patch_pool; labels and geometric draws do not change"),
+    ("random_noise", float, 0.0, "SIGMA in [0, 1]: add per-element noise of standard deviation SIGMA (a sum of four uniforms, a key per "
+                                 "sample) to every training sample, in the same pass as --color_jitter; 0 = off. Needs --device_patch_pool"),
 ]
 
 
@@ -221,6 +227,36 @@ def parse_random_scale(value):
     return sc
 
 
+def parse_color_jitter(value):
+    """The --color_jitter value: "B,C,S,H" or four numbers -> (B, C, S, H) as floats with B, C, S finite in [0, 1) and H in [0, 180]
+    ((0.0, 0.0, 0.0, 0.0) = off). Anything else raises ValueError."""
+    if isinstance(value, str):
+        parts = value.split(",")
+    else:
+        try:
+            parts = list(value)
+        except TypeError:
+            parts = [value]
+    try:
+        cj = () if any(isinstance(v, bool) for v in parts) else tuple(float(v) for v in parts)
+    except (TypeError, ValueError):
+        cj = ()
+    if len(cj) != 4 or not all(math.isfinite(v) for v in cj) or not all(0.0 <= v < 1.0 for v in cj[:3]) or not 0.0 <= cj[3] <= 180.0:
+        raise ValueError("--color_jitter must be 'B,C,S,H' with B, C, S in [0, 1) and H in [0, 180] degrees, not %r" % (value,))
+    return cj
+
+
+def parse_random_noise(value):
+    """The --random_noise value as a float in [0, 1] (0.0 = off). Anything else raises ValueError."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if isinstance(value, bool) or not (math.isfinite(v) and 0.0 <= v <= 1.0):
+        raise ValueError("--random_noise must be a float in [0, 1], not %r" % (value,))
+    return v
+
+
 def dice_from_sums(I, P, Y, smooth):
     """Soft Dice D = (2 I + s) / (P + Y + s) from the sums I = sum m p y, P = sum m p, Y = sum m y that the head leaves in UNet.dice_sums
     (rsu.h rsu_head_dice_sums). Plain arithmetic: floats, numpy arrays and tensors alike; empty sums give D = 1."""
@@ -321,10 +357,13 @@ class Options(object):
         self.save_best = bool(self.save_best)
         self.random_rotation, self.random_scale = parse_random_rotation(self.random_rotation), parse_random_scale(self.random_scale)
         self.one_launch_loader = bool(self.one_launch_loader)
+        self.color_jitter, self.random_noise = parse_color_jitter(self.color_jitter), parse_random_noise(self.random_noise)
         loader_flags = [name for name, on in (("--random_rotation", self.random_rotation > 0.0), ("--random_scale", self.random_scale != (1.0, 1.0)),
-                                              ("--one_launch_loader", self.one_launch_loader)) if on]
+                                              ("--one_launch_loader", self.one_launch_loader),
+                                              ("--color_jitter", any(v > 0.0 for v in self.color_jitter)),
+                                              ("--random_noise", self.random_noise > 0.0)) if on]
         if loader_flags and not self.device_patch_pool:   # (not silently ignored, the way --d4_augmentation is there)
-            raise ValueError("%s cannot be combined with --nodevice_patch_pool: the kernel that applies them cuts the batches of the device "
+            raise ValueError("%s cannot be combined with --nodevice_patch_pool: the kernels that apply them work on the batches of the device "
                              "patch pool; the host pool cuts plain windows only" % ", ".join(loader_flags))
         ra = self.rotation_angles
         if isinstance(ra, str):

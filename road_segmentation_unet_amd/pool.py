@@ -19,6 +19,9 @@ patches in the same order, cut when a batch asks for them.
                    a random rotation theta, the sample's D4 draw D -- with bilinear taps reflected about the original image's edges.
                    Continuous rotation and zoom then cost no further copy of the training set; the plain window (M = 1) and D4 (M = D)
                    are the same launch and deliver the loop's bits.
+                   With jitter = (B, C, S, H) or noise above zero, load_batch() then makes ONE rsu_color_jitter call on the finished input
+                   windows: brightness, contrast about the sample's own mean, saturation, hue and noise, drawn per sample from a
+                   generator of their own (the geometric draws, and with them the labels, do not move).
 """
 import ctypes
 import math
@@ -141,10 +144,81 @@ def affine_draw(rng, count, rotation=0.0, scale=(1.0, 1.0), d4=False):
     return M
 
 
+LUMA = (0.299, 0.587, 0.114)   # the weights saturation mixes towards (ITU-R BT.601, tf.image.rgb_to_grayscale)
+
+
+def check_jitter(jitter, noise):
+    """((B, C, S, H), sigma) as floats; ValueError unless B, C, S are finite and in [0, 1), H is in [0, 180] and sigma in [0, 1]"""
+    try:
+        jit = tuple(float(v) for v in jitter)
+    except (TypeError, ValueError):
+        jit = ()
+    if len(jit) != 4 or any(isinstance(v, bool) for v in jitter) or not all(math.isfinite(v) for v in jit) \
+            or not all(0.0 <= v < 1.0 for v in jit[:3]) or not 0.0 <= jit[3] <= 180.0:
+        raise ValueError("jitter must be (B, C, S, H) with B, C, S in [0, 1) and H in [0, 180] degrees, not %r" % (jitter,))
+    try:
+        sigma = float(noise)
+    except (TypeError, ValueError):
+        sigma = float("nan")
+    if isinstance(noise, bool) or not (math.isfinite(sigma) and 0.0 <= sigma <= 1.0):
+        raise ValueError("noise must be a float in [0, 1], not %r" % (noise,))
+    return jit, sigma
+
+
+_I3 = np.eye(3)
+_LUMA_ROWS = np.outer(np.ones(3), np.array(LUMA))                                                  # 1 w^T
+_THIRDS = np.full((3, 3), 1.0 / 3.0)                                                               # u u^T, u = (1, 1, 1) / sqrt 3
+_CROSS = np.array([[0.0, -1.0, 1.0], [1.0, 0.0, -1.0], [-1.0, 1.0, 0.0]]) / math.sqrt(3.0)         # [u]x
+
+
+def _jitter_matrices(b, c, s, cos_t, sin_t):
+    """jitter_matrices from the angle's cosine and sine; scalars, or arrays [n] for (A, K) [n][3][3]. Products and sums of float64 only,
+    in one order: a sample's matrices are the same bits whether formed alone or in a batch."""
+    b, c, s, cos_t, sin_t = (np.asarray(v, dtype=np.float64)[..., None, None] for v in (b, c, s, cos_t, sin_t))
+    sat = s * _I3 + (1.0 - s) * _LUMA_ROWS
+    hue = cos_t * _I3 + (1.0 - cos_t) * _THIRDS + sin_t * _CROSS
+    hs = (hue[..., :, 0:1] * sat[..., 0:1, :] + hue[..., :, 1:2] * sat[..., 1:2, :]) + hue[..., :, 2:3] * sat[..., 2:3, :]
+    return (c * b) * hs, ((1.0 - c) * b) * hs
+
+
+def jitter_matrices(b, c, s, theta):
+    """(A, K) float64 [3][3] of include/rsu.h rsu_color_jitter for brightness b, contrast c, saturation s and a hue angle theta in degrees:
+    A = c b Hue Sat, K = (1 - c) b Hue Sat with Sat = s I + (1 - s) 1 w^T (w = LUMA) and Hue the rotation by theta about (1, 1, 1) / sqrt 3
+    (Rodrigues: cos I + (1 - cos) u u^T + sin [u]x). x -> A x + K mean(x) is brightness, then contrast about the per-channel mean
+    (tf.image.adjust_contrast), then saturation towards luma, then hue, without clamps in between; grey stays grey under Sat and Hue."""
+    t = math.radians(theta)
+    return _jitter_matrices(b, c, s, math.cos(t), math.sin(t))
+
+
+def jitter_draw(rng, count, brightness=0.0, contrast=0.0, saturation=0.0, hue=0.0, noise=0.0):
+    """Per sample, in this order from `rng`, each only when its strength is above zero: u for b = 1 + (2u - 1) brightness, u for
+    c = 1 + (2u - 1) contrast, u for s = 1 + (2u - 1) saturation, u for theta = (2u - 1) hue degrees, key = rng.randint(0, 2**32) (with
+    noise). Uniform 32-bit keys: the noise hash XORs the key in, so keys that differ in low bits only would give locally permuted copies
+    of one field. Returns hostio.JITTER_DTYPE records [count]: jitter_matrices formed in float64 and rounded once, sigma = noise."""
+    from .hostio import JITTER_DTYPE
+    (B, C, S, H), sigma = check_jitter((brightness, contrast, saturation, hue), noise)
+    recs = np.zeros(count, dtype=JITTER_DTYPE)
+    p = np.empty((5, count))
+    for j in range(count):
+        p[0, j] = 1.0 + (2.0 * rng.random_sample() - 1.0) * B if B > 0.0 else 1.0
+        p[1, j] = 1.0 + (2.0 * rng.random_sample() - 1.0) * C if C > 0.0 else 1.0
+        p[2, j] = 1.0 + (2.0 * rng.random_sample() - 1.0) * S if S > 0.0 else 1.0
+        t = math.radians((2.0 * rng.random_sample() - 1.0) * H) if H > 0.0 else 0.0
+        p[3, j], p[4, j] = math.cos(t), math.sin(t)
+        if sigma > 0.0:
+            recs["key"][j] = rng.randint(0, 2 ** 32)
+    A, K = _jitter_matrices(*p)
+    recs["a"], recs["k"], recs["sigma"] = A.reshape(count, 9), K.reshape(count, 9), sigma
+    return recs
+
+
 class DevicePatchPool(PatchPool):
     def __init__(self, extended_images, extended_labels, input_size, patch_size, stride, device, augment=False, seed=2017,
-                 rotation=0.0, scale=(1.0, 1.0), one_launch=False):
-        """rotation: degrees; a sample is rotated by a uniform angle in [-rotation, rotation] (0 = off). scale: (lo, hi); a sample is
+                 rotation=0.0, scale=(1.0, 1.0), one_launch=False, jitter=(0.0, 0.0, 0.0, 0.0), noise=0.0):
+        """jitter: (B, C, S, H), the strengths of brightness, contrast, saturation (each in [0, 1): a factor uniform in [1 - v, 1 + v]) and
+        hue (degrees, a uniform angle in [-H, H]); noise: sigma in [0, 1] of the per-element noise. All zero = off: nothing is drawn,
+        allocated or launched. The draws come from RandomState((seed + 0x6a09e667) % 2**32), not from the geometric stream.
+        rotation: degrees; a sample is rotated by a uniform angle in [-rotation, rotation] (0 = off). scale: (lo, hi); a sample is
         zoomed by a log-uniform factor in [lo, hi] ((1, 1) = off). one_launch: send plain and D4-only batches through the kernel too."""
         super().__init__(extended_images, extended_labels, input_size, patch_size, stride)
         self.device = torch.device(device)
@@ -156,6 +230,18 @@ class DevicePatchPool(PatchPool):
         self.one_launch = bool(one_launch) or self.rotation > 0.0 or self.scale != (1.0, 1.0)
         if self.one_launch and self.images.shape[-1] != 3:
             raise ValueError("the one-launch loader cuts 3-channel images, not %d channels" % self.images.shape[-1])
+        self.jitter, self.noise = check_jitter(jitter, noise)
+        self.jitter_on = any(v > 0.0 for v in self.jitter) or self.noise > 0.0
+        self.last_jitter = None   # the rsu_jitter_t records (hostio.JITTER_DTYPE) of the last batch
+        self._jitter_ws = None
+        if self.jitter_on:
+            from . import _lib
+            if self.images.shape[-1] != 3:
+                raise ValueError("colour jitter and noise need 3-channel images, not %d channels" % self.images.shape[-1])
+            self._jitter_rng = np.random.RandomState((int(seed) + 0x6a09e667) % 2 ** 32)
+            if self.jitter[1] > 0.0:   # only contrast needs the means: the partial sums of one launch, whatever the batch size
+                nbytes = _lib.lib().rsu_color_jitter_ws_bytes(_lib.JITTER_MAX_LAUNCH, self.S)
+                self._jitter_ws = torch.empty(nbytes // 8, dtype=torch.int64, device=self.device)
 
     def affine_records(self, indices, matrices):
         """the rsu_affine_t records (hostio.AFFINE_DTYPE) of patches `indices` under float32 `matrices` [b, 2, 2]"""
@@ -182,9 +268,30 @@ class DevicePatchPool(PatchPool):
                   self.S, self.P, x_out.data_ptr(), labels_out.data_ptr(), st)
         return recs
 
+    def _jitter_batch(self, x_out):
+        """one rsu_color_jitter call on the finished input windows of a batch; its records stay in self.last_jitter"""
+        from . import _lib
+        b = x_out.shape[0]
+        if tuple(x_out.shape) != (b, self.S, self.S, 3) or x_out.dtype != torch.float32 or not x_out.is_contiguous() \
+                or x_out.device != self.dev_images.device:
+            raise ValueError("load_batch: colour jitter needs x_out as a contiguous float32 [b, %d, %d, 3] on %s"
+                             % (self.S, self.S, self.dev_images.device))
+        recs = jitter_draw(self._jitter_rng, b, *self.jitter, noise=self.noise)
+        st = ctypes.c_void_p(torch.cuda.current_stream(self.dev_images.device).cuda_stream)
+        ws = self._jitter_ws.data_ptr() if self._jitter_ws is not None else None
+        _lib.call("rsu_color_jitter", x_out.data_ptr(), recs.ctypes.data_as(ctypes.POINTER(_lib.RsuJitter)), b, self.S, ws, st)
+        self.last_jitter = recs
+
     def load_batch(self, indices, x_out, labels_out):
         """x_out f32 [b, S, S, C], labels_out int64 [b, P, P] (device tensors: the network's input buffers). Returns the D4 draws (None
-        without augmentation), or the batch's records where the batch went through the one-launch loader."""
+        without augmentation), or the batch's records where the batch went through the one-launch loader. With jitter or noise on, the
+        input windows are then transformed in place (self.last_jitter: the records)."""
+        ret = self._load_batch(indices, x_out, labels_out)
+        if self.jitter_on:
+            self._jitter_batch(x_out)
+        return ret
+
+    def _load_batch(self, indices, x_out, labels_out):
         if self.one_launch:
             return self._load_batch_one_launch(indices, x_out, labels_out)
         ops = d4_draw(self._rng, len(indices)) if self.augment else None
