@@ -73,9 +73,9 @@ def assert_bf16_close(got, ref, what, ulps=1.0, atol_scale=2e-5):
     scale = float(np.abs(refq).max()) if refq.size else 1.0
     tol = ulps * BF16_ULP * np.abs(refq) + atol_scale * max(scale, 1e-30)
     err = np.abs(got - refq)
-    bad = err > tol
+    bad = ~(err <= tol)   # (a NaN left in the output is out of tolerance too: NaN > tol is False)
     if bad.any():
-        idx = np.unravel_index(np.argmax(err - tol), err.shape)
+        idx = np.unravel_index(np.argmax(np.where(np.isnan(err), np.inf, err - tol)), err.shape)
         raise AssertionError("%s: %d/%d elements out of tolerance; worst at %s got %r ref %r (max|ref| %g); exact-match frac %.4f"
                              % (what, int(bad.sum()), bad.size, idx, got[idx], refq[idx], scale, float((got == refq).mean())))
     return float((got == refq).mean())
@@ -87,7 +87,8 @@ def assert_f32_close(got, ref, what, rtol=1e-4, atol_scale=1e-5):
     scale = float(np.abs(ref).max()) if ref.size else 1.0
     tol = rtol * np.abs(ref) + atol_scale * max(scale, 1e-30)
     err = np.abs(got - ref)
-    if (err > tol).any():
-        idx = np.unravel_index(np.argmax(err - tol), err.shape)
+    bad = ~(err <= tol)   # (NaN included)
+    if bad.any():
+        idx = np.unravel_index(np.argmax(np.where(np.isnan(err), np.inf, err - tol)), err.shape)
         raise AssertionError("%s: %d/%d out of tolerance; worst at %s got %r ref %r (max|ref| %g)"
-                             % (what, int((err > tol).sum()), err.size, idx, got[idx], ref[idx], scale))
+                             % (what, int(bad.sum()), err.size, idx, got[idx], ref[idx], scale))

@@ -59,8 +59,25 @@ def test_conv3x3_fwd_and_bwd_data_every_shape(forced_cfg, N, H, W, Cin, Cout):
         hu.assert_bf16_close(hu.host(dx), rdx, "conv2d_bwd_data cfg %d rep %d" % (forced_cfg, rep))
 
 
+@pytest.fixture
+def generic_convT(monkeypatch):
+    """RSU_CT_GEN=1: the transposed conv through igemm_fwd2's tap launches (1 tap per output phase forward, 4 taps at stride 2 backward) --
+    what a transposed conv with Cout % 32 != 0 takes. The default, igemm_ct, has no tile shapes: it ignores RSU_FWD2_CFG."""
+    monkeypatch.setenv("RSU_CT_GEN", "1")
+    monkeypatch.setenv("RSU_PLAN_DEBUG", "1")
+
+
+def _plan_line(capfd):
+    lines = [ln for ln in capfd.readouterr().err.splitlines() if ln.startswith("[plan fwd2]")]
+    assert lines, "no plan line: the launch did not go through igemm_fwd2's planner"
+    return lines[-1]
+
+
 @pytest.mark.parametrize("N,H,W,Cin,Cout", [(1, 28, 28, 256, 128), (2, 100, 100, 256, 128), (1, 60, 60, 128, 64)])
-def test_convT_fwd_every_shape(forced_cfg, N, H, W, Cin, Cout):
+def test_convT_fwd_every_shape(forced_cfg, generic_convT, capfd, N, H, W, Cin, Cout):
+    # every shape but 64x640 is admissible for the 1-tap launch at any size (the halo tile is the pixel tile itself); 64x640's four-slot
+    # ring of 640 pixels x 64 B beside the weight stages exceeds the 160 KiB of LDS: the planner then chooses freely
+    admissible = forced_cfg != 7
     rng = np.random.RandomState(Cin + H)
     x = hu.q(np.maximum(_rand(rng, N, H, W, Cin), 0))
     K = _rand(rng, 2, 2, Cout, Cin, scale=1.0 / np.sqrt(Cin))
@@ -71,8 +88,67 @@ def test_convT_fwd_every_shape(forced_cfg, N, H, W, Cin, Cout):
     ref = U.convT_fwd(x, hu.q(K), b)
     for rep in range(3):
         y = torch.full((N, 2 * H, 2 * W, Cout), float("nan"), dtype=torch.bfloat16, device=hu.DEV)
+        capfd.readouterr()
         call("rsu_convT2x2_fwd", hu.ptr(xd), hu.ptr(pf), hu.ptr(bd), hu.ptr(y), N, H, W, Cin, Cout, 0, hu.stream())
+        line = _plan_line(capfd)
+        assert " ntap1 " in line, "not the generic 1-tap launch: " + line
+        assert not admissible or " cfg%d " % forced_cfg in line, "RSU_FWD2_CFG=%d was not used: %s" % (forced_cfg, line)
         hu.assert_bf16_close(hu.host(y), ref, "convT fwd cfg %d rep %d" % (forced_cfg, rep))
+
+
+def _convT_case(rng, N, H, W, Cin, Cout):
+    x = hu.q(np.maximum(_rand(rng, N, H, W, Cin), 0))
+    K = _rand(rng, 2, 2, Cout, Cin, scale=1.0 / np.sqrt(Cin))
+    b = _rand(rng, Cout, scale=0.1)
+    dy = hu.q(_rand(rng, N, 2 * H, 2 * W, Cout, scale=0.1))
+    pf = torch.zeros(4 * lib().rsu_packed_bytes(1, Cout, (ctypes.c_int * 1)(Cin), 1) // 2, dtype=torch.bfloat16, device=hu.DEV)
+    pb = torch.zeros(lib().rsu_packed_bytes(4, Cin, (ctypes.c_int * 1)(Cout), 1) // 2, dtype=torch.bfloat16, device=hu.DEV)
+    Kd = hu.dev_f32(K)
+    call("rsu_pack_convT_fwd", hu.ptr(Kd), hu.ptr(pf), Cin, Cout, hu.stream())
+    call("rsu_pack_convT_bwd", hu.ptr(Kd), hu.ptr(pb), Cin, Cout, hu.stream())
+    return x, K, b, dy, pf, pb
+
+
+@pytest.mark.parametrize("N,H,W,Cin,Cout", [(1, 28, 28, 256, 128), (1, 60, 60, 128, 64)])
+def test_convT_bwd_data_generic_launch(generic_convT, capfd, N, H, W, Cin, Cout):
+    """the generic 4-tap stride-2 backward-data launch of igemm_fwd2 (RSU_CT_GEN=1) with the ReLU mask, at the planner's tile shape,
+    against the oracle as test_convT checks igemm_ct's"""
+    rng = np.random.RandomState(Cin + H + 1)
+    x, K, b, dy, pf, pb = _convT_case(rng, N, H, W, Cin, Cout)
+    xd, dyd = hu.dev_bf16(x), hu.dev_bf16(dy)
+    ref = U.relu_bwd(x, U.convT_bwd(x, hu.q(K), dy)[0])
+    for rep in range(3):
+        dx = torch.full((N, H, W, Cin), float("nan"), dtype=torch.bfloat16, device=hu.DEV)
+        capfd.readouterr()
+        call("rsu_convT2x2_bwd_data", hu.ptr(dyd), hu.ptr(pb), hu.ptr(dx), hu.ptr(xd), 1.0, N, H, W, Cin, Cout, 0, hu.stream())
+        line = _plan_line(capfd)
+        assert " ntap4 " in line, "not the generic 4-tap launch: " + line
+        hu.assert_bf16_close(hu.host(dx), ref, "convT bwd_data, generic launch, rep %d" % rep)
+
+
+def test_convT_both_generations_against_the_oracle(capfd, monkeypatch):
+    """igemm_ct (RSU_CT_GEN=2, the default) and igemm_fwd2's tap launches (1) on one shape, forward and backward-data, each against the
+    oracle (they sum in different orders: nothing claims equal bits)"""
+    N, H, W, Cin, Cout = 2, 52, 50, 96, 96
+    rng = np.random.RandomState(Cin + H)
+    x, K, b, dy, pf, pb = _convT_case(rng, N, H, W, Cin, Cout)
+    xd, bd, dyd = hu.dev_bf16(x), hu.dev_f32(b), hu.dev_bf16(dy)
+    ref_y = U.convT_fwd(x, hu.q(K), b)
+    ref_dx = U.relu_bwd(x, U.convT_bwd(x, hu.q(K), dy)[0])
+    monkeypatch.setenv("RSU_PLAN_DEBUG", "1")
+    for gen in ("1", "2"):
+        monkeypatch.setenv("RSU_CT_GEN", gen)
+        y = torch.full((N, 2 * H, 2 * W, Cout), float("nan"), dtype=torch.bfloat16, device=hu.DEV)
+        dx = torch.full((N, H, W, Cin), float("nan"), dtype=torch.bfloat16, device=hu.DEV)
+        capfd.readouterr()
+        call("rsu_convT2x2_fwd", hu.ptr(xd), hu.ptr(pf), hu.ptr(bd), hu.ptr(y), N, H, W, Cin, Cout, 0, hu.stream())
+        call("rsu_convT2x2_bwd_data", hu.ptr(dyd), hu.ptr(pb), hu.ptr(dx), hu.ptr(xd), 1.0, N, H, W, Cin, Cout, 0, hu.stream())
+        lines = [ln for ln in capfd.readouterr().err.splitlines() if ln.startswith("[plan fwd2]")]
+        assert len(lines) == (2 if gen == "1" else 0), (gen, lines)   # igemm_ct does not go through igemm_fwd2's planner
+        got_y, got_dx = hu.host(y), hu.host(dx)
+        assert not np.isnan(got_y).any() and not np.isnan(got_dx).any()
+        hu.assert_bf16_close(got_y, ref_y, "convT fwd, RSU_CT_GEN=" + gen)
+        hu.assert_bf16_close(got_dx, ref_dx, "convT bwd_data, RSU_CT_GEN=" + gen)
 
 
 def test_dilated_three_source_and_accumulate_every_shape(forced_cfg):
