@@ -469,6 +469,23 @@ int rsu_update_table_run_adam_clip(const void* dev_table, int nentries, int tota
 int rsu_ema_step(float* ema, const float* w, long n, float one_minus_decay, const void* clip_state /* may be NULL */,
                  rsu_stream_t stream);
 
+/* ---- optimizer: gradient accumulation over micro-batches (new) -------- */
+/* dst[i] = assign ? src[i] : dst[i] + src[i] over [0, n), per element, float32, one rounding. What a host needs to take one optimizer
+ * step over K backward passes, each of which OVERWRITES its gradient buffer g: with a second buffer gsum of the same size,
+ *   pass 0:          rsu_grad_accumulate(gsum, g, n, 1)      gsum  = g_0            (whatever gsum held is forgotten, a nan included)
+ *   pass 0 < j < K-1: rsu_grad_accumulate(gsum, g, n, 0)      gsum += g_j
+ *   pass K-1:        rsu_grad_accumulate(g, gsum, n, 0)      g     = gsum + g_{K-1}
+ * leaves ((g_0 + g_1) + ...) + g_{K-1} in g, where the exchange, rsu_grad_norm and the update tables read it (float32 addition
+ * commutes, so the last line's operand order changes no bit). ONE launch on `stream`: 256-lane workgroups over shares of
+ * RSU_GRAD_ACCUMULATE_BLOCK_FLOATS floats, a grid that depends on n ALONE -- not on the CU budget, the device or the autotuner. No
+ * atomics, no LDS. assign == 0 reads dst and src once and writes dst: 12 B per element; assign != 0 does NOT read dst: 8 B per element.
+ * Only dst[0, n) is written and only src[0, n) is read (the n & 3 scalars behind the last float4 singly). inf and nan pass through by
+ * the IEEE rules and nothing is filtered: the non-finite guard of rsu_grad_norm sees them in the accumulated gradient.
+ * Errors, returned before anything is launched: RSU_EINVAL for a NULL dst or src, n < 1, a dst or src that is not 16-byte aligned,
+ * overlapping [dst, dst + n) and [src, src + n); RSU_E2BIG for an n whose grid would not fit 31 bits. */
+#define RSU_GRAD_ACCUMULATE_BLOCK_FLOATS 8192
+int rsu_grad_accumulate(float* dst, const float* src, long n, int assign, rsu_stream_t stream);
+
 /* ---- patch / stride tiler (src/images.py) -------------------------------------------------- */
 /* images.py:269-281 mirror_border + :35-85 extract_patches fused, on device: tile t (x-outer,
  * y-inner order, images.py:76-77) of image n is the [S][S] window of the symmetric-padded image at

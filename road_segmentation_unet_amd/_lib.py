@@ -128,6 +128,7 @@ SIGNATURES = {
     "rsu_update_table_run_clip": (_i, [_vp, _i, _i, _f, _f, _f, _vp, _vp]),
     "rsu_update_table_run_adam_clip": (_i, [_vp, _i, _i, _f, _f, _f, _f, _f, _vp, _vp]),
     "rsu_ema_step": (_i, [_vp, _vp, _l, _f, _vp, _vp]),
+    "rsu_grad_accumulate": (_i, [_vp, _vp, _l, _i, _vp]),
     "rsu_extract_tiles": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _l, _l, _vp]),
     "rsu_overlap_add": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _l, _l, _vp]),
     "rsu_overlap_finish": (_i, [_vp, _vp, _vp, _l, _vp]),
@@ -167,6 +168,7 @@ TUNE_OFF, TUNE_LOOKUP, TUNE_MEASURE = 0, 1, 2   # rsu.h RSU_TUNE_*
 EVAL_BINS = 256   # rsu.h RSU_EVAL_BINS
 BORDER_D2_INF, BORDER_MAX_SIDE = 0x7fffffff, 1024   # rsu.h RSU_BORDER_D2_INF, RSU_BORDER_MAX_SIDE
 CLIP_STATE_BYTES, CLIP_CLIPPED, CLIP_NONFINITE, GRAD_NORM_BLOCK_FLOATS = 32, 1, 2, 16384   # rsu.h RSU_CLIP_*, RSU_GRAD_NORM_BLOCK_FLOATS
+GRAD_ACCUMULATE_BLOCK_FLOATS = 8192   # rsu.h RSU_GRAD_ACCUMULATE_BLOCK_FLOATS
 AFFINE_MAX_LAUNCH = 32   # rsu.h RSU_AFFINE_MAX_LAUNCH
 JITTER_MAX_LAUNCH = 32   # rsu.h RSU_JITTER_MAX_LAUNCH
 E2BIG = -7

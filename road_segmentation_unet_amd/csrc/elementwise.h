@@ -92,6 +92,11 @@ hipError_t ew_grad_norm(const float* g, long n, float max_norm, float* ws, ClipS
 constexpr int EW_EMA_EPB = 8192;
 int ew_ema_blocks(long n);
 hipError_t ew_ema(float* ema, const float* w, long n, float one_minus_decay, const ClipState* state, hipStream_t st);
+// Gradient accumulation (rsu.h rsu_grad_accumulate): floats per workgroup, 256 lanes x 8 float4 of src (and, when adding, of dst). The
+// grid, cdiv(n / 4, EW_ACC_EPB / 4) (at least 1), depends on n alone. assign: dst = src and dst is never read; else dst += src
+constexpr int EW_ACC_EPB = 8192;
+int ew_grad_accumulate_blocks(long n);
+hipError_t ew_grad_accumulate(float* dst, const float* src, long n, bool assign, hipStream_t st);
 hipError_t ew_adam(float* w, float* m, float* v, const float* g, const AdamRule& h, long n, hipStream_t st);
 hipError_t ew_pack(const float* src, void* dst, const PackParams& pp, hipStream_t st);
 struct PackJob { PackParams pp; const float* src; bf16_t* dst; int block_start; int pad_; };

@@ -1623,6 +1623,58 @@ hipError_t ew_ema(float* ema, const float* w, long n, float one_minus_decay, con
     hipLaunchKernelGGL(k_ema, dim3(ew_ema_blocks(n)), dim3(256), 0, st, ema, w, n, one_minus_decay, state);
     return hipGetLastError();
 }
+// ---------------------------------------------------------------------------------------------
+// Gradient accumulation (rsu.h rsu_grad_accumulate): dst[i] = src[i] (ASSIGN) or dst[i] + src[i] over [0, n), float32, one rounding
+// per element. The shape of k_ema: the grid cdiv(n / 4, EW_ACC_EPB / 4) (at least 1) depends on n alone, workgroup b owns float4s
+// [b * EW_ACC_EPB / 4, +EW_ACC_EPB / 4), a lane float4 q * 256 + lane of that share, and a lane issues all its loads before its first
+// store (dst is read and written through one pointer). ASSIGN never reads dst -- whatever it held, a nan included, is forgotten -- and
+// moves 8 B per weight instead of 12. The n & 3 scalars behind the last float4 go to lanes 0..2 of workgroup 0. inf and nan pass by the
+// IEEE rules; nothing is filtered.
+// ---------------------------------------------------------------------------------------------
+// one lane's part of a workgroup's share; FULL: the whole share lies inside [0, n4), no lane tests anything (every workgroup but the last)
+template <bool FULL, bool ASSIGN>
+__device__ __forceinline__ void acc_share(float* dst, const float* __restrict__ src, long i0, long n4) {
+    constexpr int NQ = EW_ACC_EPB / 4 / 256;
+    f32x4 dv[NQ], sv[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        const long i = i0 + q * 256;
+        const bool in = FULL || i < n4;
+        if (!ASSIGN) dv[q] = in ? ((const f32x4*)dst)[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+        sv[q] = in ? ((const f32x4*)src)[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        const long i = i0 + q * 256;
+        f32x4 o = sv[q];
+        if (!ASSIGN) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = dv[q][j] + sv[q][j];
+        }
+        if (FULL || i < n4) ((f32x4*)dst)[i] = o;
+    }
+}
+template <bool ASSIGN>
+__global__ void __launch_bounds__(256) k_grad_accumulate(float* dst, const float* __restrict__ src, long n) {
+    const long n4 = n >> 2;
+    const long b0 = (long)blockIdx.x * (EW_ACC_EPB / 4);
+    if (b0 + EW_ACC_EPB / 4 <= n4) acc_share<true, ASSIGN>(dst, src, b0 + threadIdx.x, n4);
+    else acc_share<false, ASSIGN>(dst, src, b0 + threadIdx.x, n4);
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const long i = (n4 << 2) + threadIdx.x;
+        dst[i] = ASSIGN ? src[i] : dst[i] + src[i];
+    }
+}
+int ew_grad_accumulate_blocks(long n) {
+    const long nb = ((n >> 2) + EW_ACC_EPB / 4 - 1) / (EW_ACC_EPB / 4);
+    return (int)(nb < 1 ? 1 : nb);
+}
+hipError_t ew_grad_accumulate(float* dst, const float* src, long n, bool assign, hipStream_t st) {
+    const dim3 grid(ew_grad_accumulate_blocks(n));
+    if (assign) hipLaunchKernelGGL(k_grad_accumulate<true>, grid, dim3(256), 0, st, dst, src, n);
+    else hipLaunchKernelGGL(k_grad_accumulate<false>, grid, dim3(256), 0, st, dst, src, n);
+    return hipGetLastError();
+}
 hipError_t ew_extract_tiles(const float* imgs, float* tiles, int H, int S, int P, int stride, int pps, long t0, long ntiles, hipStream_t st) {
     hipLaunchKernelGGL(k_extract_tiles, dim3(grid_for(ntiles * S * S, 256)), dim3(256), 0, st, imgs, tiles, H, S, P, stride, pps, t0, ntiles);
     return hipGetLastError();

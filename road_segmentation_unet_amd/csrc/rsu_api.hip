@@ -455,6 +455,18 @@ extern "C" int rsu_ema_step(float* ema, const float* w, long n, float one_minus_
     HIP_CHECK_RET(ew_ema(ema, w, n, one_minus_decay, (const ClipState*)clip_state, (hipStream_t)stream));
     return RSU_OK;
 }
+// ---- gradient accumulation: dst = src or dst += src in one pass (dst and src must not overlap: src is read through a __restrict__
+// pointer)
+static_assert(RSU_GRAD_ACCUMULATE_BLOCK_FLOATS == EW_ACC_EPB, "rsu.h and elementwise.h must agree on a workgroup's share");
+extern "C" int rsu_grad_accumulate(float* dst, const float* src, long n, int assign, rsu_stream_t stream) {
+    if (!dst || !src || n < 1) return RSU_EINVAL;
+    if (((uintptr_t)dst & 15) || ((uintptr_t)src & 15)) return RSU_EINVAL;
+    if ((n >> 2) / (EW_ACC_EPB / 4) >= 0x7fffffffL) return RSU_E2BIG;
+    const uintptr_t d0 = (uintptr_t)dst, s0 = (uintptr_t)src, bytes = (uintptr_t)n * sizeof(float);
+    if (d0 < s0 + bytes && s0 < d0 + bytes) return RSU_EINVAL;
+    HIP_CHECK_RET(ew_grad_accumulate(dst, src, n, assign != 0, (hipStream_t)stream));
+    return RSU_OK;
+}
 
 // ---------------------------------------------------------------------------------------------
 // VALU head / tail

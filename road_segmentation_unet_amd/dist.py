@@ -24,6 +24,19 @@ def shard_indices(indices, offset, global_batch, rank, world_size):
     return indices[lo:lo + per]
 
 
+def micro_indices(indices, offset, global_batch, rank, world_size, micro, accumulate_steps):
+    """Indices of micro-batch `micro` (0..accumulate_steps-1) of rank `rank` for the optimizer step starting at `offset`: the rank's
+    contiguous share, as shard_indices cuts it, cut contiguously again into accumulate_steps equal parts. With accumulate_steps == 1 it
+    is shard_indices."""
+    if global_batch % (world_size * accumulate_steps) != 0:
+        raise ValueError("global batch %d does not divide over %d ranks x %d accumulation steps" % (global_batch, world_size, accumulate_steps))
+    if not 0 <= micro < accumulate_steps:
+        raise ValueError("micro-batch %d of %d" % (micro, accumulate_steps))
+    per = global_batch // (world_size * accumulate_steps)
+    lo = offset + (rank * accumulate_steps + micro) * per
+    return indices[lo:lo + per]
+
+
 class GradBucketer:
     """All-reduce a flat gradient buffer in tail-first buckets, overlapped with the producer.
 

@@ -18,7 +18,7 @@ import torch.distributed as dist
 from . import hostio
 from . import images as dimages
 from ._lib import call
-from .dist import GradBucketer, shard_indices, tune_overlap
+from .dist import GradBucketer, micro_indices, shard_indices, tune_overlap  # noqa: F401  (shard_indices: importable from here as before)
 from .pool import BatchUploader, DevicePatchPool, PatchPool
 from .summary import Summary
 from .unet import EMA_SUFFIX, UNet, input_size_needed
@@ -105,6 +105,11 @@ EXTRA_FLAG_DEFS = [
                                      "[0, 1] once at the end. Needs --device_patch_pool; labels and geometric draws do not change"),
     ("random_noise", float, 0.0, "SIGMA in [0, 1]: add per-element noise of standard deviation SIGMA (a sum of four uniforms, a key per "
                                  "sample) to every training sample, in the same pass as --color_jitter; 0 = off. Needs --device_patch_pool"),
+    ("accumulate_steps", int, 1, "K >= 1: take one optimizer step over K micro-batches, summing their gradients on the GPU; 1 = off. "
+                                 "--batch_size stays the effective (global) batch of one optimizer step and must divide by GPUs x K: "
+                                 "each GPU runs K passes over batch_size / (GPUs x K) patches, so the 2-GiB limit on a batch applies to "
+                                 "the micro-batch. Steps, --eval_every and the learning-rate decay count optimizer steps. The Dice term "
+                                 "(--dice_weight) is taken per micro-batch, as it is per GPU, and dropout draws new masks per micro-batch"),
 ]
 
 
@@ -257,6 +262,21 @@ def parse_random_noise(value):
     return v
 
 
+def parse_accumulate_steps(value):
+    """The --accumulate_steps value as an int >= 1 (1 = off). Anything else raises ValueError."""
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < 1:
+        raise ValueError("--accumulate_steps must be an integer >= 1, not %r" % (value,))
+    return int(value)
+
+
+def micro_batch_size(batch_size, world, accumulate_steps):
+    """Patches per GPU and backward pass: batch_size / (world x accumulate_steps), which must divide (ValueError otherwise)."""
+    if batch_size < 1 or batch_size % (world * accumulate_steps) != 0:
+        raise ValueError("--batch_size=%d must be a positive multiple of %d GPU(s) x --accumulate_steps=%d: it is the effective batch "
+                         "of one optimizer step" % (batch_size, world, accumulate_steps))
+    return batch_size // (world * accumulate_steps)
+
+
 def dice_from_sums(I, P, Y, smooth):
     """Soft Dice D = (2 I + s) / (P + Y + s) from the sums I = sum m p y, P = sum m p, Y = sum m y that the head leaves in UNet.dice_sums
     (rsu.h rsu_head_dice_sums). Plain arithmetic: floats, numpy arrays and tensors alike; empty sums give D = 1."""
@@ -358,6 +378,9 @@ class Options(object):
         self.random_rotation, self.random_scale = parse_random_rotation(self.random_rotation), parse_random_scale(self.random_scale)
         self.one_launch_loader = bool(self.one_launch_loader)
         self.color_jitter, self.random_noise = parse_color_jitter(self.color_jitter), parse_random_noise(self.random_noise)
+        self.accumulate_steps = parse_accumulate_steps(self.accumulate_steps)
+        if self.accumulate_steps > 1:   # (the number of GPUs is known where the model is built: it checks again with it)
+            micro_batch_size(self.batch_size, 1, self.accumulate_steps)
         loader_flags = [name for name, on in (("--random_rotation", self.random_rotation > 0.0), ("--random_scale", self.random_scale != (1.0, 1.0)),
                                               ("--one_launch_loader", self.one_launch_loader),
                                               ("--color_jitter", any(v > 0.0 for v in self.color_jitter)),
@@ -391,7 +414,9 @@ class ConvolutionalModel:
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         self.rank = dist.get_rank() if dist.is_initialized() else 0
         assert opts.batch_size % self.world == 0, "global batch_size must divide evenly over ranks"
-        self.local_batch = opts.batch_size // self.world
+        # --accumulate_steps=K: one optimizer step over K passes per GPU; local_batch is the micro-batch, the batch of one pass
+        self.accumulate_steps = K = int(getattr(opts, "accumulate_steps", 1))
+        self.local_batch = micro_batch_size(opts.batch_size, self.world, K) if K > 1 else opts.batch_size // self.world
         if device is None:
             device = "cuda:%d" % (opts.gpu if opts.gpu >= 0 else int(os.environ.get("LOCAL_RANK", "0")))
         if torch.device(device).type == "cuda":
@@ -404,7 +429,8 @@ class ConvolutionalModel:
                         params=params, seed=opts.seed, training=True, optimizer=opts.optimizer, class_weights=opts.class_weights,
                         dice_weight=opts.dice_weight, dice_smooth=opts.dice_smooth, border_weight=opts.border_weight,
                         border_sigma=opts.border_sigma, clip_grad_norm=opts.clip_grad_norm if opts.clip_grad_norm > 0.0 else None,
-                        ema_decay=opts.ema_decay if opts.ema_decay > 0.0 else None, ema_warmup=opts.ema_warmup)
+                        ema_decay=opts.ema_decay if opts.ema_decay > 0.0 else None, ema_warmup=opts.ema_warmup,
+                        accumulate_steps=K if K > 1 else None)
         self.net.dropout_seed = int(opts.seed) + 7919 * self.rank  # independent masks on every rank's shard
         self._bucketer = None
         self._exchange_tuned = False
@@ -418,7 +444,12 @@ class ConvolutionalModel:
         if self.world > 1:
             self._bucketer = GradBucketer(self.net.flat_g, self.net.n_live)
             self._bucketer.extra_streams = list(self.net.wstreams)
-            self.net.on_grads = self._bucketer.ready
+            if K > 1:
+                # a bucket launched during the last backward pass would send g_{K-1} without the local sum: on_grads stays unhooked,
+                # the schedule is not tuned, and finish() all-reduces the whole buffer once, behind the K-th accumulate_gradients()
+                self._exchange_tuned = True
+            else:
+                self.net.on_grads = self._bucketer.ready
             # identical initial weights on every rank (the reference has one copy; ranks must start from the same point)
             dist.broadcast(self.net.flat_w, 0)
             if self.net.flat_ema is not None:
@@ -434,16 +465,43 @@ class ConvolutionalModel:
         GLOBAL pixel count (UNet.backward_device), and a label other than 0 and 1 then ignores its pixel: no loss, no gradient.
         With --dice_weight > 0 the returned loss is that cross-entropy + dice_weight * (1 - D), D the soft Dice of each rank's batch
         (averaged over the ranks), and labels other than 0 and 1 are ignored as well.
+        With --accumulate_steps=K > 1 the three arrays hold the rank's whole share of the effective batch, [K*b, ...]: micro-batch j is
+        rows [j*b, (j+1)*b), the step is ONE optimizer step, and the predictions come back as a new tensor [K*b,P,P].
         (Synchronous upload: the train() loop stages its batches one step ahead instead, see pool.BatchUploader.)"""
-        net = self.net
-        net.x.copy_(torch.as_tensor(np.asarray(patches, dtype=np.float32)).to(net.device))
-        net.labels.copy_(torch.as_tensor(np.asarray(labels)).to(net.device, torch.int64))
-        net.set_pixel_weights(None if weights is None else torch.as_tensor(np.asarray(weights, dtype=np.float32)))
-        return self._run_step()
+        net, K, b = self.net, self.accumulate_steps, self.local_batch
+        x = torch.as_tensor(np.asarray(patches, dtype=np.float32))
+        y = torch.as_tensor(np.asarray(labels))
+        w = None if weights is None else torch.as_tensor(np.asarray(weights, dtype=np.float32))
+        if K == 1:
+            net.x.copy_(x.to(net.device))
+            net.labels.copy_(y.to(net.device, torch.int64))
+            net.set_pixel_weights(w)
+            return self._run_step()
+        if x.shape[0] != K * b or y.shape[0] != K * b or (w is not None and w.shape[0] != K * b):
+            raise ValueError("train_step with --accumulate_steps=%d takes the rank's whole share: %d x %d patches, not %d" % (K, K, b, x.shape[0]))
+        predictions = torch.empty((K * b,) + tuple(net.prob.shape[1:]), dtype=net.prob.dtype, device=net.device)
 
-    def _run_step(self):
-        """forward + loss + backward + gradient exchange + optimizer step (Momentum or Adam) on the batch held in net.x / net.labels"""
-        opts, net = self._options, self.net
+        def load(micro):
+            sl = slice(micro * b, (micro + 1) * b)
+            net.x.copy_(x[sl].to(net.device))
+            net.labels.copy_(y[sl].to(net.device, torch.int64))
+            net.set_pixel_weights(None if w is None else w[sl])
+
+        def between(micro):
+            predictions[micro * b:(micro + 1) * b].copy_(net.prob)
+
+        loss, _ = self._run_step(load, between)
+        between(K - 1)
+        return loss, predictions
+
+    def _run_step(self, load=None, between=None):
+        """forward + loss + backward + gradient exchange + optimizer step (Momentum or Adam) on the batch held in net.x / net.labels.
+        With --accumulate_steps=K > 1: K times load(micro) (which puts micro-batch `micro` there), forward, backward and
+        net.accumulate_gradients(), the losses added up on the device, between(micro) behind every micro-batch but the last (whose
+        labels and probabilities are still in the net when this returns, as they always were); then ONE exchange and ONE optimizer step."""
+        opts, net, K = self._options, self.net, self.accumulate_steps
+        if load is not None:
+            load(0)   # (in front of the exchange tuning below, which times passes over the batch in the net)
         if self._bucketer is not None and not self._exchange_tuned:
             # first step of a data-parallel run: time forward + backward + exchange (no optimizer step, so the trajectory is
             # untouched) under both schedules and keep the faster one (dist.tune_overlap)
@@ -458,20 +516,29 @@ class ConvolutionalModel:
                     net.backward_cu_budget = n
                     net.ensure_tuned(keep=float(opts.dropout))
                 self.exchange_schedule = tune_overlap(self._bucketer, probe, trials=2, set_cu_budget=set_budget)
-        net.ensure_tuned(keep=float(opts.dropout))   # the explicit tile-shape tuning pass (untimed, weights untouched): once, in front of the first step
-        # feed_dict dropout_keep: opts.dropout (tf_aerial_images.py:237); the masks come from a counter-based hash of
-        # (seed, rank, dropout site, global step, element) instead of TF's Philox stream
-        net.forward_device(keep=float(opts.dropout))
         if self._bucketer is not None:
-            self._bucketer.reset()
-        # the Dice term is each rank's own batch Dice, scaled by 1 / world: the SUM all-reduce of the gradients and of the loss below then
-        # give the mean over the ranks, with no collective inside the backward pass
-        dice_scale = net.dice_weight / self.world
-        net.backward_device(1.0 / (opts.batch_size * opts.patch_size * opts.patch_size), dice_scale=dice_scale)
-        loss = net.loss_sum / (opts.batch_size * opts.patch_size * opts.patch_size)
-        if dice_scale > 0.0:   # (device arithmetic on net.dice_sums: no synchronisation)
-            s = net.dice_sums
-            loss = loss + dice_scale * (1.0 - dice_from_sums(s[0:1], s[1:2], s[2:3], net.dice_smooth))
+            self._bucketer.reset()   # (nothing is in flight between two steps: finish() has drained the last exchange)
+        # the Dice term is each rank's own batch Dice -- with --accumulate_steps each micro-batch's -- scaled by 1 / (world * K): the SUM
+        # all-reduce of the gradients and of the loss below, and the sum over the micro-batches, then give the mean over all of them,
+        # with no collective inside the backward pass
+        dice_scale = net.dice_weight / (self.world * K)
+        loss = None
+        for micro in range(K):
+            if load is not None and micro > 0:
+                load(micro)
+            net.ensure_tuned(keep=float(opts.dropout))   # the explicit tile-shape tuning pass (untimed, weights untouched): once, in front of the first step
+            # feed_dict dropout_keep: opts.dropout (tf_aerial_images.py:237); the masks come from a counter-based hash of
+            # (seed, rank, dropout site, global step, micro-batch, element) instead of TF's Philox stream
+            net.forward_device(keep=float(opts.dropout))
+            net.backward_device(1.0 / (opts.batch_size * opts.patch_size * opts.patch_size), dice_scale=dice_scale)
+            net.accumulate_gradients()   # (K == 1: nothing)
+            part = net.loss_sum / (opts.batch_size * opts.patch_size * opts.patch_size)
+            if dice_scale > 0.0:   # (device arithmetic on net.dice_sums: no synchronisation)
+                s = net.dice_sums
+                part = part + dice_scale * (1.0 - dice_from_sums(s[0:1], s[1:2], s[2:3], net.dice_smooth))
+            loss = part if loss is None else loss + part
+            if between is not None and micro < K - 1:
+                between(micro)
         if self._bucketer is not None:
             self._bucketer.finish()
             dist.all_reduce(loss)
@@ -619,20 +686,33 @@ class ConvolutionalModel:
         if not device_pool and self._uploader is None and net.device.type == "cuda":
             self._uploader = BatchUploader(net)
 
-        def host_batch(offset):
-            idx = shard_indices(indices, offset, opts.batch_size, self.rank, self.world)
+        K = self.accumulate_steps   # micro-batches per optimizer step (--accumulate_steps; 1: the rank's share is one batch, as ever)
+
+        def batch_indices(offset, micro):
+            return micro_indices(indices, offset, opts.batch_size, self.rank, self.world, micro, K)   # (K == 1: shard_indices)
+
+        def host_batch(offset, micro=0):
+            idx = batch_indices(offset, micro)
             return pool.gather(idx) if pool is not None else (patches[idx], labels_patches[idx])
 
         if offsets and not device_pool:
             self._uploader.stage(0, *host_batch(offsets[0]))
         for batch_i, offset in enumerate(offsets):
-            if device_pool:
-                pool.load_batch(shard_indices(indices, offset, opts.batch_size, self.rank, self.world), net.x, net.labels)
-            else:
-                self._uploader.commit(batch_i & 1)
-            loss, predictions = self._run_step()
+            # the uploader's slot is the running (micro-)batch counter & 1: every batch is staged one ahead of the pass that reads it
+            def load(micro, offset=offset, count=batch_i * K):
+                if device_pool:
+                    pool.load_batch(batch_indices(offset, micro), net.x, net.labels)
+                else:
+                    self._uploader.commit((count + micro) & 1)
+
+            def between(micro, offset=offset, count=batch_i * K):   # behind every micro-batch but the step's last: never with K == 1
+                if not device_pool:
+                    self._uploader.stage((count + micro + 1) & 1, *host_batch(offset, micro + 1))  # rides beside the pass just launched
+                num_errors.add_((net.labels.to(torch.float64) - net.prob.to(torch.float64)).abs().sum())
+
+            loss, predictions = self._run_step(load, between)
             if not device_pool and batch_i + 1 < len(offsets):
-                self._uploader.stage((batch_i + 1) & 1, *host_batch(offsets[batch_i + 1]))  # rides beside the step just launched
+                self._uploader.stage(((batch_i + 1) * K) & 1, *host_batch(offsets[batch_i + 1]))  # rides beside the step just launched
             step = net.global_step
             if self.rank == 0:
                 print("Batch {} Step {}".format(batch_i, step), end="\r")

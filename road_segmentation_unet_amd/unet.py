@@ -145,6 +145,21 @@ def ema_decay_at(decay, t, warmup=True):
     return f(d)
 
 
+def _accumulate_arg(value):
+    """UNet's accumulate_steps: None or 1 (one backward pass per optimizer step), or an int K > 1"""
+    if value is None:
+        return 1
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < 1:
+        raise _lib.RsuError("accumulate_steps must be None or an int >= 1, not %r" % (value,))
+    return int(value)
+
+
+def dropout_key_value(seed, site, global_step, micro_step=0):
+    """The 32-bit dropout key of (seed, dropout site, optimizer step, micro-batch of that step): a sum of the four, each times an odd
+    32-bit constant of its own, modulo 2^32. micro_step 0 adds nothing: a net that does not accumulate keeps the keys it always had."""
+    return (seed * 0x9E3779B9 + site * 0x85EBCA6B + global_step * 0xC2B2AE35 + micro_step * 0x27D4EB2F) & 0xFFFFFFFF
+
+
 EMA_SUFFIX = "/ExponentialMovingAverage"   # TensorFlow's name of a variable's shadow
 OPTIMIZERS = ("momentum", "adam")
 
@@ -161,7 +176,7 @@ class UNet:
 
     def __init__(self, num_layers, root_size, dilated_layers, batch_size, patch_size, device="cuda:0", params=None, seed=2017,
                  training=True, optimizer="momentum", class_weights=None, dice_weight=0.0, dice_smooth=1.0, border_weight=0.0, border_sigma=5.0,
-                 clip_grad_norm=None, ema_decay=None, ema_warmup=True):
+                 clip_grad_norm=None, ema_decay=None, ema_warmup=True, accumulate_steps=None):
         """optimizer: "momentum" (the reference's MomentumOptimizer: apply_momentum) or "adam" (tf.train.AdamOptimizer: apply_adam; a
         second fp32 slot per variable, flat_v).
         class_weights: None or a pair (w0, w1) of finite floats >= 0, not both 0: the weighted cross-entropy of rsu.h
@@ -180,10 +195,20 @@ class UNet:
         a float32 shadow of flat_w initialised to the initial weights, by tf.train.ExponentialMovingAverage's rule at the decay
         ema_decay_at(d, global_step, ema_warmup); averaged_weights() evaluates with it; state_dict() carries it as
         `<var>/ExponentialMovingAverage`. ema_warmup: TensorFlow's num_updates rule, min(d, (1 + t) / (10 + t)). Training nets only.
-        None: no buffer, no launch, the step is what it always was."""
+        None: no buffer, no launch, the step is what it always was.
+        accumulate_steps: None (or 1), or an int K > 1: one optimizer step takes K backward passes over K micro-batches of batch_size
+        patches each, with accumulate_gradients() behind every backward_device(); the K-th call leaves the float32 sum of the K
+        gradients, ((g_0 + g_1) + ...) + g_{K-1}, in flat_g, where the exchange, the norm and the update pass read it, and
+        apply_momentum / apply_adam refuse to step before it. backward_device's inv_count stays 1 / (pixel count of the WHOLE effective
+        batch). One more float32 buffer, flat_gsum (4 B per weight), and one rsu_grad_accumulate launch per micro-batch (rsu.h).
+        micro_step (0..K-1) enters the dropout keys. Training nets only. None: no buffer, no launch, the step is what it always was."""
         if optimizer not in OPTIMIZERS:
             raise _lib.RsuError("optimizer must be one of %s, not %r" % ("|".join(OPTIMIZERS), optimizer))
         self.optimizer = optimizer
+        self.accumulate_steps = _accumulate_arg(accumulate_steps)
+        if self.accumulate_steps > 1 and not training:
+            raise _lib.RsuError("a forward-only net takes no optimizer step: it has no gradients to accumulate")
+        self.flat_gsum, self._accum_calls = None, 0   # the running sum of the micro-batch gradients; accumulate_gradients() calls since the last step
         self.clip_grad_norm = _clip_arg(clip_grad_norm)
         self.ema_decay, self.ema_warmup = _ema_arg(ema_decay), bool(ema_warmup)
         if self.ema_decay is not None and not training:
@@ -360,6 +385,8 @@ class UNet:
             # TensorFlow initialises a shadow to its variable's initial value; the dead dilated pair behind n_live keeps that value
             self.flat_ema = self.flat_w.clone()
             self.ema = {n: self.flat_ema[o:o + cnt].view(s) for n, (o, cnt, s) in self._slices.items()}
+        if self.accumulate_steps > 1:
+            self.flat_gsum = torch.zeros(off, dtype=torch.float32, device=dev)
         self.global_step = 0
         # Adam's float32 accumulators beta1^t, beta2^t (None: not started -- the first apply_adam sets them to its (beta1, beta2),
         # the initial values TensorFlow gives them)
@@ -411,6 +438,7 @@ class UNet:
             else:
                 self.beta1_power = self.beta2_power = None
         self.global_step = int(d.get("global_step", 0))
+        self._accum_calls = 0   # (a half-accumulated step belongs to the weights that were replaced)
         self.repack()
 
     def _check_tensor_sizes(self):
@@ -627,8 +655,15 @@ class UNet:
 
     def dropout_key(self, site):
         """32-bit key of dropout site `site` (encoder level i -> i, decoder stage i -> L + i: the 2L-1 tf.nn.dropout calls of
-        unet.py:29-30,64-65) for the current global step; the hash of (key, element index) replaces TF's Philox stream"""
-        return (self.dropout_seed * 0x9E3779B9 + site * 0x85EBCA6B + self.global_step * 0xC2B2AE35) & 0xFFFFFFFF
+        unet.py:29-30,64-65) for the current global step -- and, on an accumulating net, the current micro-batch of it, so that the
+        micro-batches of one step draw different masks; the hash of (key, element index) replaces TF's Philox stream"""
+        return dropout_key_value(self.dropout_seed, site, self.global_step, self.micro_step)
+
+    @property
+    def micro_step(self):
+        """which micro-batch of the current optimizer step the next forward / backward pass belongs to: 0..accumulate_steps-1, the count
+        of accumulate_gradients() calls since the last step; always 0 on a net that does not accumulate"""
+        return min(self._accum_calls, self.accumulate_steps - 1)
 
     def forward_device(self, want_logits=False, keep=1.0):
         """unet.forward (unet.py:12-97) on self.x (already on device); keep = dropout_keep (1.0: none); fills self.prob."""
@@ -1040,6 +1075,36 @@ class UNet:
                                 "clipped variant")
         call("rsu_grad_norm", _ptr(self.flat_g), self.n_live, self.clip_grad_norm, _ptr(self._clip_ws), _ptr(self.clip_state), self._stream())
 
+    # ------------------------------------------------------------------ gradient accumulation
+    def accumulate_gradients(self):
+        """an accumulating net (accumulate_steps = K > 1), behind every backward_device() and on the current stream -- the main stream,
+        which has joined the side streams at the end of the pass, and which every side-stream launch of the NEXT pass waits for
+        (schedule.side), so no gradient is overwritten before it has been read here. One rsu_grad_accumulate launch (rsu.h), no host
+        synchronisation: call 0 of a step assigns flat_gsum = flat_g (the previous step's sum is forgotten, not zeroed), calls 0 < j < K-1
+        add flat_gsum += flat_g, call K-1 adds the other way, flat_g += flat_gsum: flat_g[0:n_live) then holds
+        ((g_0 + g_1) + ...) + g_{K-1} in float32 and the exchange, _grad_norm, the update tables and _ema_step read the buffer they
+        always read. Under data parallelism the exchange comes after the K-th call. A (K+1)-th call without a step raises. On a net
+        that does not accumulate: nothing, no launch."""
+        K = self.accumulate_steps
+        if K == 1:
+            return
+        self._not_averaged("accumulate_gradients")
+        j = self._accum_calls
+        if j >= K:
+            raise _lib.RsuError("accumulate_gradients: %d calls since the last optimizer step on a net with accumulate_steps=%d; "
+                                "apply_%s comes first" % (j, K, self.optimizer))
+        if j < K - 1:
+            call("rsu_grad_accumulate", _ptr(self.flat_gsum), _ptr(self.flat_g), self.n_live, 1 if j == 0 else 0, self._stream())
+        else:
+            call("rsu_grad_accumulate", _ptr(self.flat_g), _ptr(self.flat_gsum), self.n_live, 0, self._stream())
+        self._accum_calls = j + 1
+
+    def _accumulated(self, what):
+        """apply_momentum / apply_adam on an accumulating net: flat_g holds the sum only after exactly accumulate_steps calls"""
+        if self.accumulate_steps > 1 and self._accum_calls != self.accumulate_steps:
+            raise _lib.RsuError("%s after %d of %d accumulate_gradients() calls: flat_g does not hold the sum of the step's gradients yet"
+                                % (what, self._accum_calls, self.accumulate_steps))
+
     def clip_stats(self):
         """The state record of a clipping net, read back once (a synchronisation: call it per epoch, not per step): steps, clipped and
         skipped count the updates so far, norm / scale / sumsq and the two flags describe the last one. None on a net without clipping."""
@@ -1108,6 +1173,7 @@ class UNet:
         if self.optimizer != "momentum":
             raise _lib.RsuError("apply_momentum on a net built with optimizer=%r" % self.optimizer)
         self._not_averaged("apply_momentum")
+        self._accumulated("apply_momentum")
         if self.clip_grad_norm is not None:
             self._grad_norm()
             tab = self._update_table or self._build_update_table()
@@ -1121,6 +1187,7 @@ class UNet:
             tab = self._update_table or self._build_update_table()
             call("rsu_update_table_run", _ptr(tab[0]), tab[1], tab[2], self.learning_rate(lr0), momentum, gscale, self._stream())
         self.global_step += 1
+        self._accum_calls = 0
         self._ema_step()
 
     def apply_adam(self, lr0, beta1=0.9, beta2=0.999, epsilon=1e-8, gscale=1.0):
@@ -1133,6 +1200,7 @@ class UNet:
         if self.optimizer != "adam":
             raise _lib.RsuError("apply_adam on a net built with optimizer=%r" % self.optimizer)
         self._not_averaged("apply_adam")
+        self._accumulated("apply_adam")
         if self.clip_grad_norm is not None:
             self._grad_norm()   # (raises under RSU_FUSED_UPDATE=0, before the powers are touched)
         if self.beta1_power is None:
@@ -1149,6 +1217,7 @@ class UNet:
             tab = self._update_table or self._build_update_table()
             call("rsu_update_table_run_adam", _ptr(tab[0]), tab[1], tab[2], *args, self._stream())
         self.global_step += 1
+        self._accum_calls = 0
         self.beta1_power, self.beta2_power = b1p, b2p
         self._ema_step()
 
