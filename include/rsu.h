@@ -535,6 +535,59 @@ typedef struct {
 int rsu_affine_patches(const float* images, const uint8_t* labels, const rsu_affine_t* recs /* HOST pointer */, int nrec, int nimg, int He,
                        int Hl, int S, int P, float* x_out, int64_t* labels_out, rsu_stream_t stream);
 
+/* ---- training input: the same launch with an elastic deformation per sample (new) ------------ */
+/* rsu_affine_patches with a smooth random displacement of every output pixel in front of the matrix: the U-Net paper's elastic deformation
+ * (displacement vectors on a coarse grid, interpolated smoothly), formed per pixel inside the loader kernel -- no further copy of the
+ * training set and no further pass over the batch. images, labels, nrec, nimg, He, Hl, S, P, offset, x_out, labels_out and the record
+ * fields image, cy, cx, m00 .. m11 are rsu_affine_patches'. Further fields of record r: alpha >= 0, the standard deviation of the CONTROL
+ * POINTS in OUTPUT pixels (the interpolated field's deviation is smaller: a cubic B-spline averages its 16 neighbours); key, the key of the
+ * sample's lattice; grid = G, the lattice's cells per axis across the input window, 1 .. RSU_ELASTIC_MAX_GRID. The padding is not read.
+ * All arithmetic float32, every operation rounded on its own, in this order:
+ *   lattice  (G + 3) x (G + 3) control points of two components, stored nowhere. Component `axis` (0 = rows, 1 = columns) of point (a, b),
+ *            0 <= a, b < G + 3, is c_axis[a][b] = alpha * g with g the noise value of rsu_color_jitter below for the element index
+ *            e = (a * 32 + b) * 2 + axis under `key`: h1 = mix(e ^ key), h2 = mix(h1 ^ 0x9e3779b9), n = the sum of their four 16-bit halves,
+ *            g = ((float)n - 131070.f) * C with that entry's C. |g| <= 131070 C < 3.4641. The key is XORed in: keys must be uniform 32-bit
+ *            draws (pool.elastic_draw), keys that differ in low bits only give permuted copies of one lattice.
+ *   cell     per axis, for the INPUT WINDOW's pixel index iw in [0, S): q = (float)((double)G / (double)S), formed on the host inside the
+ *            call and passed to the kernel (the device never divides);
+ *              t = ((float)iw + 0.5f) * q,  k = (int)floorf(t) clamped to [0, G - 1],  f = t - (float)k
+ *   weights  of the uniform cubic B-spline, with g1 = 1.0f - f, f2 = f * f, f3 = f2 * f and SIXTH = the float with bits 0x3e2aaaab (1 / 6
+ *            rounded; a product, not a quotient):
+ *              w[0] = ((g1 * g1) * g1) * SIXTH                              (1 - f)^3 / 6
+ *              w[1] = ((3.0f * f3 - 6.0f * f2) + 4.0f) * SIXTH              (3 f^3 - 6 f^2 + 4) / 6
+ *              w[2] = (((3.0f * f2 - 3.0f * f3) + 3.0f * f) + 1.0f) * SIXTH (-3 f^3 + 3 f^2 + 3 f + 1) / 6
+ *              w[3] = f3 * SIXTH                                            f^3 / 6
+ *            (ky, wy[]) from the row index, (kx, wx[]) from the column index
+ *   field    row_a  = ((wx[0] * c_axis[ky + a][kx] + wx[1] * c_axis[ky + a][kx + 1]) + wx[2] * c_axis[ky + a][kx + 2]) + wx[3] * c_axis[ky + a][kx + 3]
+ *            u_axis = ((wy[0] * row_0 + wy[1] * row_1) + wy[2] * row_2) + wy[3] * row_3
+ *            The weights are a partition of unity up to rounding (their sum is within 2^-22 of 1), so |u| <= 3.47 alpha.
+ *   use      input pixel (i, j): iw = i, jw = j; di = (i - (S - 1) / 2) + u_0, dj = (j - (S - 1) / 2) + u_1; everything behind that is
+ *            rsu_affine_patches from "sy =" on, unchanged: M, the centre, floor and fractions, every tap reflected on its own about the
+ *            ORIGINAL image's edges, the interpolation. The displacement is an OUTPUT offset: it rotates and zooms with the sample.
+ *            Label pixel (i, j): iw = i + offset, jw = j + offset -- its own pixel of the window -- and (P - 1) / 2 in place of
+ *            (S - 1) / 2: the same float operations on the same integers (i - (P - 1) / 2 and (i + offset) - (S - 1) / 2 are the same
+ *            float), so a label is displaced by exactly the field its window pixel sees.
+ * alpha = 0 gives c = +-0 and u = +-0: di and dj keep their bits and the sample equals rsu_affine_patches' bit for bit. A large alpha on a
+ * fine grid (alpha above about S / (3 G)) can FOLD the field -- neighbouring output pixels read the source in reversed order; nothing here
+ * prevents it, the choice is the caller's. hostio.elastic_patches restates the rule in numpy float32: the outputs are reproducible bit for
+ * bit on the host. The records travel as kernel arguments, RSU_ELASTIC_MAX_LAUNCH per launch (1.5 KB): ceil(nrec / 32) launches on
+ * `stream`, no device table, no copy, no synchronisation, no allocation. A sample's output depends on its own record alone, not on its
+ * neighbours or on where the record list is cut. Errors, returned before anything is launched or written: everything rsu_affine_patches
+ * refuses, with the same codes; RSU_EINVAL for an alpha that is not finite, negative or above 64, a grid outside [1, RSU_ELASTIC_MAX_GRID]. */
+typedef struct {
+    int image;
+    float cy, cx;
+    float m00, m01, m10, m11;
+    float alpha;   /* standard deviation of the control points, in output pixels, >= 0 */
+    unsigned key;  /* key of this sample's lattice */
+    int grid;      /* G: cells per axis across the input window */
+    int pad_[2];
+} rsu_elastic_t; /* 48 bytes */
+#define RSU_ELASTIC_MAX_LAUNCH 32
+#define RSU_ELASTIC_MAX_GRID 16
+int rsu_elastic_patches(const float* images, const uint8_t* labels, const rsu_elastic_t* recs /* HOST pointer */, int nrec, int nimg, int He,
+                        int Hl, int S, int P, float* x_out, int64_t* labels_out, rsu_stream_t stream);
+
 /* ---- training input: colour jitter and noise per sample, behind the loader (new) ------------- */
 /* Photometric augmentation of a finished batch, in place: sample n of x f32 [nrec][S][S][3] is transformed by record n alone. recs: nrec
  * records in HOST memory, read before the call returns. Pixel p = i * S + j of a sample has channels x0, x1, x2. All arithmetic is

@@ -40,6 +40,12 @@ class RsuAffine(ctypes.Structure):
     _fields_ = [("image", _i), ("cy", _f), ("cx", _f), ("m00", _f), ("m01", _f), ("m10", _f), ("m11", _f), ("pad_", _i)]
 
 
+class RsuElastic(ctypes.Structure):
+    """rsu_elastic_t: one sample of rsu_elastic_patches (48 bytes; ELASTIC_DTYPE is the same record as a numpy dtype)"""
+    _fields_ = [("image", _i), ("cy", _f), ("cx", _f), ("m00", _f), ("m01", _f), ("m10", _f), ("m11", _f), ("alpha", _f), ("key", _u),
+                ("grid", _i), ("pad_", _i * 2)]
+
+
 class RsuJitter(ctypes.Structure):
     """rsu_jitter_t: one sample of rsu_color_jitter (80 bytes; JITTER_DTYPE is the same record as a numpy dtype)"""
     _fields_ = [("a", _f * 9), ("k", _f * 9), ("sigma", _f), ("key", _u)]
@@ -133,6 +139,7 @@ SIGNATURES = {
     "rsu_overlap_add": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _l, _l, _vp]),
     "rsu_overlap_finish": (_i, [_vp, _vp, _vp, _l, _vp]),
     "rsu_affine_patches": (_i, [_vp, _vp, ctypes.POINTER(RsuAffine), _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "rsu_elastic_patches": (_i, [_vp, _vp, ctypes.POINTER(RsuElastic), _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "rsu_color_jitter_ws_bytes": (_sz, [_i, _i]),
     "rsu_color_jitter": (_i, [_vp, ctypes.POINTER(RsuJitter), _i, _i, _vp, _vp]),
     "rsu_quantize_mask": (_i, [_vp, _vp, _i, _i, _i, _f, _vp]),
@@ -170,6 +177,7 @@ BORDER_D2_INF, BORDER_MAX_SIDE = 0x7fffffff, 1024   # rsu.h RSU_BORDER_D2_INF, R
 CLIP_STATE_BYTES, CLIP_CLIPPED, CLIP_NONFINITE, GRAD_NORM_BLOCK_FLOATS = 32, 1, 2, 16384   # rsu.h RSU_CLIP_*, RSU_GRAD_NORM_BLOCK_FLOATS
 GRAD_ACCUMULATE_BLOCK_FLOATS = 8192   # rsu.h RSU_GRAD_ACCUMULATE_BLOCK_FLOATS
 AFFINE_MAX_LAUNCH = 32   # rsu.h RSU_AFFINE_MAX_LAUNCH
+ELASTIC_MAX_LAUNCH, ELASTIC_MAX_GRID = 32, 16   # rsu.h RSU_ELASTIC_MAX_LAUNCH, RSU_ELASTIC_MAX_GRID
 JITTER_MAX_LAUNCH = 32   # rsu.h RSU_JITTER_MAX_LAUNCH
 E2BIG = -7
 

@@ -81,7 +81,7 @@ def main(argv=None):
             patches = DevicePatchPool(extended, gt_exp, input_size, opts.patch_size, opts.stride, device=model.net.device,
                                       augment=opts.d4_augmentation, seed=opts.seed, rotation=opts.random_rotation,
                                       scale=opts.random_scale, one_launch=opts.one_launch_loader, jitter=opts.color_jitter,
-                                      noise=opts.random_noise)
+                                      noise=opts.random_noise, elastic=opts.elastic_deformation)
             labels_patches = None
             print("Train on {} patches of size {}x{}".format(patches.shape[0], patches.shape[1], patches.shape[2]))
             print("Train on {} groundtruth patches of size {}x{}".format(patches.shape[0], opts.patch_size, opts.patch_size))

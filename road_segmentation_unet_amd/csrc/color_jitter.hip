@@ -60,23 +60,6 @@ __device__ __forceinline__ long long cj_q(float v) {
     return (long long)rintf(fminf(fmaxf(v, -256.f), 256.f) * 16777216.f);
 }
 
-__device__ __forceinline__ unsigned cj_mix(unsigned v) {
-    v ^= v >> 16;
-    v *= 0x85ebca6bu;
-    v ^= v >> 13;
-    v *= 0xc2b2ae35u;
-    v ^= v >> 16;
-    return v;
-}
-
-// the unit-variance noise value of element e under `key`: an Irwin-Hall sum of four 16-bit uniforms, centred and scaled
-__device__ __forceinline__ float cj_noise(unsigned e, unsigned key) {
-#pragma clang fp contract(off)
-    const unsigned h1 = cj_mix(e ^ key), h2 = cj_mix(h1 ^ 0x9e3779b9u);
-    const unsigned n = (h1 & 0xffffu) + (h1 >> 16) + (h2 & 0xffffu) + (h2 >> 16);
-    return ((float)n - 131070.f) * __uint_as_float(0x37ddb3d7u);
-}
-
 __global__ void __launch_bounds__(256) k_jitter_sums(const float* __restrict__ x, long long* __restrict__ ws, int npix, int nchunk, unsigned kmask) {
     if (!((kmask >> blockIdx.y) & 1u)) return;   // (the whole workgroup: a record without contrast needs no means)
     __shared__ long long lds[4][3];

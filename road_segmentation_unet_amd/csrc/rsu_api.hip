@@ -1536,6 +1536,27 @@ extern "C" int rsu_affine_patches(const float* images, const uint8_t* labels, co
     HIP_CHECK_RET(ap_affine_patches(images, labels, (const ApRec*)recs, nrec, He, Hl, S, P, x_out, labels_out, (hipStream_t)stream));
     return RSU_OK;
 }
+static_assert(RSU_ELASTIC_MAX_LAUNCH == EP_MAX_LAUNCH && RSU_ELASTIC_MAX_GRID == EP_MAX_GRID && sizeof(rsu_elastic_t) == sizeof(EpRec) &&
+                  sizeof(rsu_elastic_t) == 48,
+              "rsu.h and affine_patches.h must agree on the elastic record, the records per launch and the finest grid");
+extern "C" int rsu_elastic_patches(const float* images, const uint8_t* labels, const rsu_elastic_t* recs, int nrec, int nimg, int He, int Hl, int S,
+                                   int P, float* x_out, int64_t* labels_out, rsu_stream_t stream) {
+    if (!images || !labels || !recs || !x_out || !labels_out || nrec < 1 || nimg < 1 || Hl < 1 || P < 1 || S < P) return RSU_EINVAL;
+    if (He < Hl || ((He - Hl) & 1) || ((S - P) & 1) || He - Hl != S - P) return RSU_EINVAL;
+    for (int r = 0; r < nrec; ++r) {
+        const rsu_elastic_t& a = recs[r];
+        if (a.image < 0 || a.image >= nimg) return RSU_EINVAL;
+        const float f[6] = {a.cy, a.cx, a.m00, a.m01, a.m10, a.m11};
+        for (int k = 0; k < 6; ++k)
+            if (!std::isfinite(f[k]) || std::fabs(f[k]) > (k < 2 ? 4194304.f : 64.f)) return RSU_EINVAL;
+        if (!std::isfinite(a.alpha) || !(a.alpha >= 0.f) || !(a.alpha <= 64.f)) return RSU_EINVAL;
+        if (a.grid < 1 || a.grid > RSU_ELASTIC_MAX_GRID) return RSU_EINVAL;
+    }
+    if ((long)He * He * 12 >= 0x7ffffff0L || (long)nrec * S * S * 12 >= 0x7ffffff0L || (long)nrec * P * P * 8 >= 0x7ffffff0L) return RSU_E2BIG;
+    // (q = (float)(grid / (double)S), the one quotient of the rule, is formed per record where the launcher copies the records into its arguments)
+    HIP_CHECK_RET(ep_elastic_patches(images, labels, (const EpRec*)recs, nrec, He, Hl, S, P, x_out, labels_out, (hipStream_t)stream));
+    return RSU_OK;
+}
 static_assert(RSU_JITTER_MAX_LAUNCH == CJ_MAX_LAUNCH && sizeof(rsu_jitter_t) == sizeof(CjRec) && sizeof(rsu_jitter_t) == 80,
               "rsu.h and color_jitter.h must agree on the record and on the records per launch");
 extern "C" size_t rsu_color_jitter_ws_bytes(int nrec, int S) { return (nrec >= 1 && S >= 1) ? cj_ws_bytes(nrec, S) : 0; }

@@ -308,12 +308,22 @@ def affine_records(recs):
     return out
 
 
+def _affine_offsets(n):
+    """the output offsets from the centre of an [n][n] output, (n - 1) / 2: (di [n][1], dj [1][n]) float32"""
+    d = np.arange(n, dtype=np.float32) - np.float32(n - 1) * np.float32(0.5)
+    return d[:, None], d[None, :]
+
+
 def _affine_source(rec, n, offset, Hl):
     """per pixel of an [n][n] output centred at (n - 1) / 2: the reflected tap rows y0, y1 and columns x0, x1 ([n][n] int64) and the
     fractions fy, fx ([n][n] float32), by the float32 operations of csrc/affine_patches.hip ap_source, one numpy operation each"""
+    return _affine_source_tail(rec, *_affine_offsets(n), offset, Hl)
+
+
+def _affine_source_tail(rec, di, dj, offset, Hl):
+    """_affine_source from the output offsets (di, dj) on (csrc/affine_patches.hip ap_source_tail): the rule of rsu_affine_patches from
+    "sy =" on, which rsu_elastic_patches enters with displaced offsets"""
     f = np.float32
-    d = np.arange(n, dtype=np.float32) - f(n - 1) * f(0.5)
-    di, dj = d[:, None], d[None, :]
     off = f(offset)
     sy = (f(rec["cy"]) - off) + (f(rec["m00"]) * di + f(rec["m01"]) * dj)
     sx = (f(rec["cx"]) - off) + (f(rec["m10"]) * di + f(rec["m11"]) * dj)
@@ -332,6 +342,27 @@ def _affine_lerp(v00, v01, v10, v11, fy, fx):
     return (v00 * gx + v01 * fx) * gy + (v10 * gx + v11 * fx) * fy
 
 
+def _affine_check(what, images, labels, recs, S, P):
+    """what rsu_affine_patches refuses, for the mirror `what` (recs: a record array with AFFINE_DTYPE's fields): ValueError, or
+    (images, labels as arrays, offset)"""
+    img = np.asarray(images)
+    lab = np.asarray(labels)
+    if img.ndim != 4 or img.shape[3] != 3 or img.shape[1] != img.shape[2] or lab.ndim != 3 or lab.shape[1] != lab.shape[2] \
+            or lab.shape[0] != img.shape[0] or img.dtype != np.float32:
+        raise ValueError("%s: images must be float32 [n, He, He, 3] and labels [n, Hl, Hl], not %s %s and %s"
+                         % (what, img.dtype, img.shape, lab.shape))
+    nimg, He, Hl = img.shape[0], img.shape[1], lab.shape[1]
+    if P < 1 or S < P or He < Hl or (He - Hl) % 2 or (S - P) % 2 or He - Hl != S - P:
+        raise ValueError("%s: He - Hl = %d and S - P = %d must be even and equal, with S >= P >= 1" % (what, He - Hl, S - P))
+    if recs.size < 1:
+        raise ValueError("%s: no records" % what)
+    vals = np.stack([recs[k] for k in ("cy", "cx", "m00", "m01", "m10", "m11")], axis=1)
+    if not np.all(np.isfinite(vals)) or np.abs(vals[:, 2:]).max() > AFFINE_MAX_M or np.abs(vals[:, :2]).max() > AFFINE_MAX_CENTRE \
+            or recs["image"].min() < 0 or recs["image"].max() >= nimg:
+        raise ValueError("%s: every record needs an image in [0, %d), finite fields, |m| <= 64 and a centre within 2^22" % (what, nimg))
+    return img, lab, (He - Hl) // 2
+
+
 def affine_patches(images, labels, recs, S, P):
     """The one-launch batch loader on the host: the numpy float32 statement of include/rsu.h rsu_affine_patches, operation for operation
     (numpy rounds every float32 operation on its own, as csrc/affine_patches.hip is compiled to do): x and labels equal the device's bit
@@ -339,24 +370,10 @@ def affine_patches(images, labels, recs, S, P):
     or a sequence of (image, cy, cx, m00, m01, m10, m11), with (cy, cx) the window's centre in the extended image (row, column) and
     M = [[m00, m01], [m10, m11]] mapping an output offset to a source offset. Every tap is reflected about the ORIGINAL image's edges
     (symmetric padding, repeated). Returns (x float32 [n, S, S, 3], labels int64 [n, P, P]). ValueError for what the ABI refuses."""
-    img = np.asarray(images)
-    lab = np.asarray(labels)
     S, P = int(S), int(P)
-    if img.ndim != 4 or img.shape[3] != 3 or img.shape[1] != img.shape[2] or lab.ndim != 3 or lab.shape[1] != lab.shape[2] \
-            or lab.shape[0] != img.shape[0] or img.dtype != np.float32:
-        raise ValueError("affine_patches: images must be float32 [n, He, He, 3] and labels [n, Hl, Hl], not %s %s and %s"
-                         % (img.dtype, img.shape, lab.shape))
-    nimg, He, Hl = img.shape[0], img.shape[1], lab.shape[1]
-    if P < 1 or S < P or He < Hl or (He - Hl) % 2 or (S - P) % 2 or He - Hl != S - P:
-        raise ValueError("affine_patches: He - Hl = %d and S - P = %d must be even and equal, with S >= P >= 1" % (He - Hl, S - P))
     recs = affine_records(recs)
-    if recs.size < 1:
-        raise ValueError("affine_patches: no records")
-    vals = np.stack([recs[k] for k in ("cy", "cx", "m00", "m01", "m10", "m11")], axis=1)
-    if not np.all(np.isfinite(vals)) or np.abs(vals[:, 2:]).max() > AFFINE_MAX_M or np.abs(vals[:, :2]).max() > AFFINE_MAX_CENTRE \
-            or recs["image"].min() < 0 or recs["image"].max() >= nimg:
-        raise ValueError("affine_patches: every record needs an image in [0, %d), finite fields, |m| <= 64 and a centre within 2^22" % nimg)
-    offset = (He - Hl) // 2
+    img, lab, offset = _affine_check("affine_patches", images, labels, recs, S, P)
+    Hl = lab.shape[1]
     labf = lab.astype(np.float32)
     x = np.empty((recs.size, S, S, 3), np.float32)
     y = np.empty((recs.size, P, P), np.int64)
@@ -447,3 +464,105 @@ def color_jitter(x, recs):
             y[:, r] = np.fmin(np.fmax(yr, f(0.0)), f(1.0))
         out[j] = y.reshape(S, S, 3)
     return out
+
+
+# include/rsu.h rsu_elastic_t as a numpy record (48 bytes) and the bounds rsu_elastic_patches checks
+ELASTIC_DTYPE = np.dtype([("image", "<i4"), ("cy", "<f4"), ("cx", "<f4"), ("m00", "<f4"), ("m01", "<f4"), ("m10", "<f4"), ("m11", "<f4"),
+                          ("alpha", "<f4"), ("key", "<u4"), ("grid", "<i4"), ("pad_", "<i4", (2,))])
+ELASTIC_MAX_ALPHA, ELASTIC_MAX_GRID = 64.0, 16
+ELASTIC_SIXTH = np.uint32(0x3e2aaaab).view(np.float32)   # 1 / 6 rounded: the spline's weights are products, not quotients
+
+
+def elastic_records(recs):
+    """recs as an ELASTIC_DTYPE array [n]: such an array itself, or a sequence of (image, cy, cx, m00, m01, m10, m11, alpha, key, grid)"""
+    if isinstance(recs, np.ndarray) and recs.dtype == ELASTIC_DTYPE:
+        return np.ascontiguousarray(recs.reshape(-1))
+    out = np.zeros(len(recs), dtype=ELASTIC_DTYPE)
+    for k, r in enumerate(recs):
+        r = tuple(r)
+        out[k] = r[:8] + (int(r[8]) & 0xffffffff, r[9], (0, 0))
+    return out
+
+
+def elastic_lattice(key, alpha, G):
+    """The control lattice of include/rsu.h rsu_elastic_patches: float32 [G + 3][G + 3][2], component `axis` of point (a, b) = alpha * g
+    with g the noise value of rsu_color_jitter for the element index (a * 32 + b) * 2 + axis under `key`"""
+    G = int(G)
+    a, b, axis = np.meshgrid(np.arange(G + 3, dtype=np.uint32), np.arange(G + 3, dtype=np.uint32), np.arange(2, dtype=np.uint32), indexing="ij")
+    e = (a * np.uint32(32) + b) * np.uint32(2) + axis
+    h1 = _jitter_mix(e ^ np.uint32(int(key) & 0xffffffff))
+    h2 = _jitter_mix(h1 ^ np.uint32(0x9e3779b9))
+    m = np.uint32(0xffff)
+    n = (h1 & m) + (h1 >> np.uint32(16)) + (h2 & m) + (h2 >> np.uint32(16))
+    g = (n.astype(np.float32) - np.float32(131070.0)) * JITTER_NOISE_SCALE
+    return (np.float32(alpha) * g).astype(np.float32)
+
+
+def elastic_weights(f):
+    """the four cubic B-spline weights of the fractions f (float32 array): float32 [4] + f.shape, in the order of operations rsu.h states"""
+    f = np.asarray(f, dtype=np.float32)
+    one, three = np.float32(1.0), np.float32(3.0)
+    g1, f2 = one - f, f * f
+    f3 = f2 * f
+    return np.stack([((g1 * g1) * g1) * ELASTIC_SIXTH,
+                     ((three * f3 - np.float32(6.0) * f2) + np.float32(4.0)) * ELASTIC_SIXTH,
+                     (((three * f2 - three * f3) + three * f) + one) * ELASTIC_SIXTH,
+                     f3 * ELASTIC_SIXTH]).astype(np.float32)
+
+
+def _elastic_axis(S, G):
+    """per window pixel index 0 .. S - 1 of one axis: (cell k int64 [S] in [0, G - 1], weights float32 [4][S])"""
+    q = np.float32(np.float64(G) / np.float64(S))
+    t = (np.arange(S, dtype=np.float32) + np.float32(0.5)) * q
+    k = np.clip(np.floor(t).astype(np.int64), 0, G - 1)
+    return k, elastic_weights(t - k.astype(np.float32))
+
+
+def elastic_field(lattice, S):
+    """The displacement field of include/rsu.h rsu_elastic_patches over an input window of S pixels: float32 [2][S][S], [axis][iw][jw], the
+    uniform cubic B-spline over `lattice` (float32 [G + 3][G + 3][2], elastic_lattice) with both sums in index order, one numpy operation
+    per float32 operation of the kernel"""
+    lat = np.asarray(lattice, dtype=np.float32)
+    if lat.ndim != 3 or lat.shape[0] != lat.shape[1] or lat.shape[2] != 2 or not 1 <= lat.shape[0] - 3 <= ELASTIC_MAX_GRID or int(S) < 1:
+        raise ValueError("elastic_field: lattice must be [G + 3, G + 3, 2] with G in [1, 16] and S >= 1, not %s and %r" % (lat.shape, S))
+    S, G = int(S), lat.shape[0] - 3
+    k, w = _elastic_axis(S, G)
+    ky, kx = k[:, None], k[None, :]
+    wy, wx = w[:, :, None], w[:, None, :]
+    u = np.empty((2, S, S), np.float32)
+    for axis in range(2):
+        c = lat[:, :, axis]
+        row = [((wx[0] * c[ky + a, kx] + wx[1] * c[ky + a, kx + 1]) + wx[2] * c[ky + a, kx + 2]) + wx[3] * c[ky + a, kx + 3] for a in range(4)]
+        u[axis] = ((wy[0] * row[0] + wy[1] * row[1]) + wy[2] * row[2]) + wy[3] * row[3]
+    return u
+
+
+def elastic_patches(images, labels, recs, S, P):
+    """The one-launch batch loader with elastic deformation on the host: the numpy float32 statement of include/rsu.h rsu_elastic_patches,
+    operation for operation: x and labels equal the device's bit for bit. images, labels, S, P as affine_patches; recs: an ELASTIC_DTYPE
+    array or a sequence of (image, cy, cx, m00, m01, m10, m11, alpha, key, grid). Input pixel (i, j) is displaced by the field at (i, j),
+    label pixel (i, j) by the field at (i + offset, j + offset): the centre crop of the same field. Returns (x float32 [n, S, S, 3],
+    labels int64 [n, P, P]). ValueError for what the ABI refuses."""
+    S, P = int(S), int(P)
+    recs = elastic_records(recs)
+    img, lab, offset = _affine_check("elastic_patches", images, labels, recs, S, P)
+    if not np.all(np.isfinite(recs["alpha"])) or recs["alpha"].min() < 0.0 or recs["alpha"].max() > ELASTIC_MAX_ALPHA \
+            or recs["grid"].min() < 1 or recs["grid"].max() > ELASTIC_MAX_GRID:
+        raise ValueError("elastic_patches: every record needs a finite alpha in [0, 64] and a grid in [1, 16]")
+    Hl = lab.shape[1]
+    labf = lab.astype(np.float32)
+    x = np.empty((recs.size, S, S, 3), np.float32)
+    y = np.empty((recs.size, P, P), np.int64)
+    for k, rec in enumerate(recs):
+        n = int(rec["image"])
+        u = elastic_field(elastic_lattice(rec["key"], rec["alpha"], rec["grid"]), S)
+        di, dj = _affine_offsets(S)
+        y0, y1, x0, x1, fy, fx = _affine_source_tail(rec, di + u[0], dj + u[1], offset, Hl)
+        im = img[n, offset:offset + Hl, offset:offset + Hl]   # (index + offset) of the extended image
+        x[k] = _affine_lerp(im[y0, x0], im[y0, x1], im[y1, x0], im[y1, x1], fy[..., None], fx[..., None])
+        ul = u[:, offset:offset + P, offset:offset + P]
+        di, dj = _affine_offsets(P)
+        y0, y1, x0, x1, fy, fx = _affine_source_tail(rec, di + ul[0], dj + ul[1], offset, Hl)
+        lf = labf[n]
+        y[k] = _affine_lerp(lf[y0, x0], lf[y0, x1], lf[y1, x0], lf[y1, x1], fy, fx) >= np.float32(0.5)
+    return x, y

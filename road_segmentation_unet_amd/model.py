@@ -105,6 +105,13 @@ EXTRA_FLAG_DEFS = [
                                      "[0, 1] once at the end. Needs --device_patch_pool; labels and geometric draws do not change"),
     ("random_noise", float, 0.0, "SIGMA in [0, 1]: add per-element noise of standard deviation SIGMA (a sum of four uniforms, a key per "
                                  "sample) to every training sample, in the same pass as --color_jitter; 0 = off. Needs --device_patch_pool"),
+    ("elastic_deformation", str, "0,3", "ALPHA,GRID: bend every training sample by a smooth random displacement field, the U-Net paper's "
+                                        "elastic deformation, inside the one-launch loader kernel: control points of standard deviation "
+                                        "ALPHA pixels (0 <= ALPHA <= 64; 0 = off) on a lattice of GRID cells per axis across the input "
+                                        "window (an integer, 1..16), interpolated by a cubic B-spline; labels move with the image. The "
+                                        "interpolated field's deviation is smaller than ALPHA; a large ALPHA on a fine GRID can fold the "
+                                        "field. Needs --device_patch_pool; composes with --random_rotation, --random_scale and "
+                                        "--d4_augmentation"),
     ("accumulate_steps", int, 1, "K >= 1: take one optimizer step over K micro-batches, summing their gradients on the GPU; 1 = off. "
                                  "--batch_size stays the effective (global) batch of one optimizer step and must divide by GPUs x K: "
                                  "each GPU runs K passes over batch_size / (GPUs x K) patches, so the 2-GiB limit on a batch applies to "
@@ -262,6 +269,29 @@ def parse_random_noise(value):
     return v
 
 
+def parse_elastic_deformation(value):
+    """The --elastic_deformation value: "ALPHA,GRID" or a pair -> (alpha, grid) as (float, int) with alpha finite in [0, 64] (0.0 = off) and
+    grid an integer in [1, 16]. Anything else raises ValueError."""
+    if isinstance(value, str):
+        parts = value.split(",")
+    else:
+        try:
+            parts = list(value)
+        except TypeError:
+            parts = [value]
+    try:
+        if len(parts) != 2 or any(isinstance(v, bool) for v in parts):
+            raise ValueError
+        alpha = float(parts[0])
+        grid = int(parts[1].strip()) if isinstance(parts[1], str) else parts[1]   # ("3.0" and 3.5 are not integers)
+        if not isinstance(grid, (int, np.integer)) or not (math.isfinite(alpha) and 0.0 <= alpha <= 64.0) or not 1 <= grid <= 16:
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError("--elastic_deformation must be 'ALPHA,GRID' with ALPHA in [0, 64] pixels and an integer GRID in [1, 16], not %r"
+                         % (value,)) from None
+    return alpha, int(grid)
+
+
 def parse_accumulate_steps(value):
     """The --accumulate_steps value as an int >= 1 (1 = off). Anything else raises ValueError."""
     if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < 1:
@@ -378,13 +408,15 @@ class Options(object):
         self.random_rotation, self.random_scale = parse_random_rotation(self.random_rotation), parse_random_scale(self.random_scale)
         self.one_launch_loader = bool(self.one_launch_loader)
         self.color_jitter, self.random_noise = parse_color_jitter(self.color_jitter), parse_random_noise(self.random_noise)
+        self.elastic_deformation = parse_elastic_deformation(self.elastic_deformation)
         self.accumulate_steps = parse_accumulate_steps(self.accumulate_steps)
         if self.accumulate_steps > 1:   # (the number of GPUs is known where the model is built: it checks again with it)
             micro_batch_size(self.batch_size, 1, self.accumulate_steps)
         loader_flags = [name for name, on in (("--random_rotation", self.random_rotation > 0.0), ("--random_scale", self.random_scale != (1.0, 1.0)),
                                               ("--one_launch_loader", self.one_launch_loader),
                                               ("--color_jitter", any(v > 0.0 for v in self.color_jitter)),
-                                              ("--random_noise", self.random_noise > 0.0)) if on]
+                                              ("--random_noise", self.random_noise > 0.0),
+                                              ("--elastic_deformation", self.elastic_deformation[0] > 0.0)) if on]
         if loader_flags and not self.device_patch_pool:   # (not silently ignored, the way --d4_augmentation is there)
             raise ValueError("%s cannot be combined with --nodevice_patch_pool: the kernels that apply them work on the batches of the device "
                              "patch pool; the host pool cuts plain windows only" % ", ".join(loader_flags))

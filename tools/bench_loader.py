@@ -2,10 +2,11 @@
 """Developer tool (GPU box): what DevicePatchPool.load_batch costs in front of a training step, per loader.
 
   bench_loader.py [--images N] [--reps R]
-      config 2's shapes (B = 4, S = 572, P = 388) over a pool of N mirror-extended 608-pixel images, eleven arms in one process:
+      config 2's shapes (B = 4, S = 572, P = 388) over a pool of N mirror-extended 608-pixel images, twelve arms in one process:
         loop plain, loop D4                the per-sample torch copies (the default path, unchanged)
         one launch plain, one launch D4    --one_launch_loader: one rsu_affine_patches call per batch
         one launch rot 180 scale 0.8-1.25  --random_rotation=180 --random_scale=0.8,1.25 --d4_augmentation
+        + elastic 10 px on 3 cells         the same with --elastic_deformation=10,3: one rsu_elastic_patches call per batch instead
         + jitter, no contrast              --color_jitter=0.2,0,0.2,10: one rsu_color_jitter call behind the loader, one launch (apply)
         + jitter                           --color_jitter=0.2,0.2,0.2,10: two launches (sums, apply)
         + jitter + noise                   the same with --random_noise=0.02
@@ -16,9 +17,10 @@
       and 12 B for its sums pass -- to be read against the copy rate of profiles/*/hbm_rates.txt. Every pool is built and warmed first;
       then the arms ALTERNATE: repetition i times one batch of every arm in turn, so that a drift of the box moves all arms alike. Every
       arm cuts the same sequence of patches.
-      Then the kernels alone: 50 back-to-back rsu_affine_patches / rsu_color_jitter calls on prebuilt records between two events, per kind
-      of record (the Python of load_batch -- the draws, the records -- is outside; what is left per call is one ctypes call and the
-      launches), and one jittered batch compared with hostio.color_jitter at this size.
+      Then the kernels alone: 50 back-to-back rsu_affine_patches / rsu_elastic_patches / rsu_color_jitter calls on prebuilt records between
+      two events, per kind of record (the Python of load_batch -- the draws, the records -- is outside; what is left per call is one
+      ctypes call and the launches); the loader's kinds ALTERNATE over seven rounds and the median round is reported. One elastic and
+      one jittered batch are compared with hostio.elastic_patches / hostio.color_jitter at this size.
 The record goes to standard output: keep it under profiles/rNN/.
 """
 import argparse
@@ -38,7 +40,7 @@ a = ap.parse_args()
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 from road_segmentation_unet_amd import _lib, hostio  # noqa: E402
-from road_segmentation_unet_amd.pool import DevicePatchPool, affine_draw, jitter_draw  # noqa: E402
+from road_segmentation_unet_amd.pool import DevicePatchPool, affine_draw, elastic_draw, jitter_draw  # noqa: E402
 
 B, S, P, HE, STRIDE = 4, 572, 388, 608, 12
 OFFSET = (S - P) // 2
@@ -59,6 +61,8 @@ JITTERS = [("jitter, no contrast", dict(jitter=(0.2, 0.0, 0.2, 10.0))), ("jitter
            ("jitter + noise", dict(jitter=(0.2, 0.2, 0.2, 10.0), noise=0.02))]
 ARMS = [("loop plain", dict()), ("loop D4", dict(augment=True)), ("one launch plain", dict(one_launch=True)),
         ("one launch D4", dict(one_launch=True, augment=True)), ("one launch rot 180 scale 0.8-1.25", ROT)]
+ELASTIC = (10.0, 3)
+ARMS += [("rot 180 + elastic 10 px on 3 cells", dict(ROT, elastic=ELASTIC))]
 ARMS += [("loop plain + " + n, dict(kw)) for n, kw in JITTERS] + [("rot 180 + " + n, dict(ROT, **kw)) for n, kw in JITTERS]
 
 
@@ -95,32 +99,58 @@ for name, kw, pl in pools:
 print("one launch / loop: plain %.2f x, D4 %.2f x the loop's time; rotation and scale cost %.2f x the one-launch D4 batch"
       % (us["one launch plain"] / us["loop plain"], us["one launch D4"] / us["loop D4"],
          us["one launch rot 180 scale 0.8-1.25"] / us["one launch D4"]))
+print("elastic deformation on top of the rotation arm: %+.1f us per batch (%.2f x)"
+      % (us["rot 180 + elastic 10 px on 3 cells"] - us["one launch rot 180 scale 0.8-1.25"],
+         us["rot 180 + elastic 10 px on 3 cells"] / us["one launch rot 180 scale 0.8-1.25"]))
 print("jitter on top of its loader (us): " + "; ".join(
     "%s %+.1f rotation off, %+.1f rotation on" % (n, us["loop plain + " + n] - us["loop plain"],
                                                    us["rot 180 + " + n] - us["one launch rot 180 scale 0.8-1.25"]) for n, _ in JITTERS))
 del pools
 
-pl = DevicePatchPool(ext, lab, S, P, STRIDE, device=DEV, seed=1, one_launch=True)
+pl = DevicePatchPool(ext, lab, S, P, STRIDE, device=DEV, seed=1, one_launch=True, elastic=(0.0, ELASTIC[1]))
 idx = [int(k) for k in np.random.RandomState(2).randint(0, len(pl), size=B)]
 st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-for name, kw in (("plain", dict()), ("D4", dict(d4=True)), ("rot 180 scale 0.8-1.25", dict(d4=True, rotation=180.0, scale=(0.8, 1.25)))):
-    recs = pl.affine_records(idx, affine_draw(np.random.RandomState(3), B, **kw))
-    rp = recs.ctypes.data_as(ctypes.POINTER(_lib.RsuAffine))
+ROTKW = dict(d4=True, rotation=180.0, scale=(0.8, 1.25))
+KINDS = []
+for name, kw, alpha in (("plain", dict(), 0.0), ("D4", dict(d4=True), 0.0), ("rot 180 scale 0.8-1.25", ROTKW, 0.0),
+                        ("rot 180 + elastic 10 px on 3 cells", ROTKW, ELASTIC[0])):
+    M = affine_draw(np.random.RandomState(3), B, **kw)
+    if alpha > 0.0:
+        recs = pl.elastic_records(idx, M, elastic_draw(np.random.RandomState(5), B, *ELASTIC))
+        recs["alpha"] = alpha
+        KINDS.append((name, "rsu_elastic_patches", recs, recs.ctypes.data_as(ctypes.POINTER(_lib.RsuElastic))))
+    else:
+        recs = pl.affine_records(idx, M)
+        KINDS.append((name, "rsu_affine_patches", recs, recs.ctypes.data_as(ctypes.POINTER(_lib.RsuAffine))))
 
-    def launch():
-        _lib.call("rsu_affine_patches", pl.dev_images.data_ptr(), pl.dev_labels.data_ptr(), rp, B, a.images, HE, HL, S, P, x.data_ptr(),
-                  y.data_ptr(), st)
-    for _ in range(5):
-        launch()
-    torch.cuda.synchronize()
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record()
-    for _ in range(50):
-        launch()
-    e.record()
-    e.synchronize()
-    t = s.elapsed_time(e) * 1e3 / 50
-    print("kernel alone, %-24s %6.1f us per call (50 calls back to back) = %6.0f GB/s" % (name + ":", t, nbytes / t / 1e3))
+
+def loader_launch(entry, rp):
+    _lib.call(entry, pl.dev_images.data_ptr(), pl.dev_labels.data_ptr(), rp, B, a.images, HE, HL, S, P, x.data_ptr(), y.data_ptr(), st)
+
+
+ROUNDS = 7
+alone = {name: [] for name, _, _, _ in KINDS}
+for rnd in range(ROUNDS + 1):   # (round 0 warms every kind up and is dropped)
+    for name, entry, recs, rp in KINDS:
+        torch.cuda.synchronize()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(50):
+            loader_launch(entry, rp)
+        e.record()
+        e.synchronize()
+        if rnd:
+            alone[name].append(s.elapsed_time(e) * 1e3 / 50)
+for name, entry, recs, rp in KINDS:
+    t = sorted(alone[name])[ROUNDS // 2]
+    print("kernel alone, %-36s %6.1f us per call (median of %d alternated rounds of 50 calls back to back; min %.1f, max %.1f) = %6.0f GB/s"
+          % (name + ":", t, ROUNDS, min(alone[name]), max(alone[name]), nbytes / t / 1e3))
+name, entry, recs, rp = KINDS[-1]
+loader_launch(entry, rp)
+torch.cuda.synchronize()
+hx, hy = hostio.elastic_patches(ext, lab, recs, S, P)
+print("    one elastic batch equals hostio.elastic_patches at %d x %d^2: inputs %s, labels %s"
+      % (B, S, np.array_equal(x.cpu().numpy().view(np.int32), hx.view(np.int32)), np.array_equal(y.cpu().numpy(), hy)))
 
 # the jitter's kernels alone, on the batch the last loader call left in x (restored before every call would cost a copy: the values drift to
 # the clamp over 55 calls, which changes no instruction count -- the kernels have no data-dependent branch)
