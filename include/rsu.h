@@ -499,6 +499,28 @@ int rsu_overlap_add(const float* prob, float* acc, float* hits, int nimg, int H,
                     long ntiles, rsu_stream_t stream);
 int rsu_overlap_finish(const float* acc, const float* hits, float* out, long n, rsu_stream_t stream);
 
+/* ---- the tiler for images of any size: rectangular, any stride, clamped last tile (new) ----- */
+/* The tile grid of an H x W image. Along an axis of length L >= P with stride s >= 1 the tile origins are 0, s, 2s, ... while
+ * o + P <= L; where (L - P) % s != 0 one more tile follows at L - P, the CLAMPED last tile, which overlaps its neighbour by more than
+ * the others do. n = ceil((L - P) / s) + 1 tiles, the origin of tile i is min(i * s, L - P); an axis with (L - P) % s == 0 has exactly
+ * the grid of rsu_extract_tiles. Tile order as there: image-major, then x (column) outer, y (row) inner, ny x nx tiles per image.
+ * Host only. RSU_EINVAL for a NULL ny or nx, P < 1, P > H, P > W, stride < 1. */
+int rsu_tile_grid(int H, int W, int P, int stride, int* ny, int* nx);
+/* rsu_extract_tiles on that grid. imgs f32 [nimg][H][W][3]; tiles f32 [ntiles][S][S][3] for the tile indices [t0, t0 + ntiles) of the
+ * flattened (img, x index, y index) list. The mirror border (S - P) / 2 is np.pad(..., "symmetric") of ANY width: the source index of
+ * coordinate c along an axis of length L is m < L ? m : 2L - 1 - m with m = c mod 2L (non-negative), so a border wider than the image
+ * reflects repeatedly. Pure data movement; every index is 64-bit. On an input rsu_extract_tiles accepts the tiles are its tiles.
+ * Errors, returned before anything is launched: RSU_EINVAL for a NULL imgs or tiles, nimg < 1, P > H, P > W, P > S, an odd S - P,
+ * stride < 1, t0 < 0, ntiles < 1, t0 + ntiles > nimg * nx * ny. */
+int rsu_extract_tiles_rect(const float* imgs, float* tiles, int nimg, int H, int W, int S, int P, int stride, long t0,
+                           long ntiles, rsu_stream_t stream);
+/* rsu_overlap_add on that grid: acc and hits f32 [nimg][H][W]. Gather form, one thread per output pixel, no atomics: the pixel's
+ * covering tiles of [t0, t0 + ntiles) are summed in increasing tile index (per axis the regular tiles, then the clamped one, each
+ * counted once) in double and added to acc once per call; hits += their number. On an input rsu_overlap_add accepts acc and hits get
+ * its bits. The division is rsu_overlap_finish. Errors as rsu_extract_tiles_rect (without S), for a NULL prob, acc or hits. */
+int rsu_overlap_add_rect(const float* prob, float* acc, float* hits, int nimg, int H, int W, int P, int stride, long t0,
+                         long ntiles, rsu_stream_t stream);
+
 /* ---- training input: one launch per batch, with rotation and scale (new) -------------------- */
 /* Cuts the input windows and label patches of a batch out of the resident training images, each sample through a 2x2 matrix of its own
  * about its window's centre. images f32 [nimg][He][He][3]: the mirror-extended images of the patch pool; labels uint8 [nimg][Hl][Hl] in
@@ -635,6 +657,11 @@ int rsu_color_jitter(float* x /* f32 [nrec][S][S][3], in place */, const rsu_jit
  * mean(mask >= 0.5) > threshold, written over the block of `out` (out == masks is allowed: a block is read completely before it
  * is written). patch_size <= 64. */
 int rsu_quantize_mask(const float* masks, float* out, int nimg, int S, int patch_size, float threshold, rsu_stream_t stream);
+/* rsu_quantize_mask on masks f32 [nimg][H][W]: the same rule per patch_size block; a block cut by the image's edge takes the mean over
+ * the pixels it holds. out == masks is allowed; patch_size <= 64. RSU_EINVAL for a NULL masks or out, nimg, H, W or patch_size below 1,
+ * patch_size above 64; RSU_E2BIG for more than 2^31 - 1 blocks. */
+int rsu_quantize_mask_rect(const float* masks, float* out, int nimg, int H, int W, int patch_size, float threshold,
+                           rsu_stream_t stream);
 /* images.py:88-99 labels_for_patches over images.py:35-85 extract_patches(masks, patch_size): labels int64
  * [nimg][S/ps][S/ps] in the reference's patch order (x outer, y inner), label = mean(patch) > threshold. */
 int rsu_labels_for_patches(const float* masks, int64_t* labels, int nimg, int S, int patch_size, float threshold,

@@ -138,11 +138,15 @@ SIGNATURES = {
     "rsu_extract_tiles": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _l, _l, _vp]),
     "rsu_overlap_add": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _l, _l, _vp]),
     "rsu_overlap_finish": (_i, [_vp, _vp, _vp, _l, _vp]),
+    "rsu_tile_grid": (_i, [_i, _i, _i, _i, _PI, _PI]),
+    "rsu_extract_tiles_rect": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _l, _l, _vp]),
+    "rsu_overlap_add_rect": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _l, _l, _vp]),
     "rsu_affine_patches": (_i, [_vp, _vp, ctypes.POINTER(RsuAffine), _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "rsu_elastic_patches": (_i, [_vp, _vp, ctypes.POINTER(RsuElastic), _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "rsu_color_jitter_ws_bytes": (_sz, [_i, _i]),
     "rsu_color_jitter": (_i, [_vp, ctypes.POINTER(RsuJitter), _i, _i, _vp, _vp]),
     "rsu_quantize_mask": (_i, [_vp, _vp, _i, _i, _i, _f, _vp]),
+    "rsu_quantize_mask_rect": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "rsu_labels_for_patches": (_i, [_vp, _vp, _i, _i, _i, _f, _vp]),
     "rsu_confusion_counts": (_i, [_vp, _vp, _l, _vp, _vp]),
     "rsu_plan": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(RsuPlanRow), _i, _PI, ctypes.POINTER(RsuPlanTotals)]),

@@ -126,7 +126,7 @@ def main(argv=None):
 
     if opts.eval_data_dir and not opts.eval_train:
         print("Running inference on eval data {}".format(opts.eval_data_dir))
-        eval_images = hostio.load(opts.eval_data_dir)
+        eval_images = hostio.load(opts.eval_data_dir)   # one common shape, any H x W (ValueError for a directory of mixed shapes)
         start = time.time()
         masks = model.predict_batchwise(eval_images, opts.pred_batch_size)
         print("Prediction time:{} mins".format((time.time() - start) / 60))
@@ -135,7 +135,11 @@ def main(argv=None):
             save_dir = os.path.abspath(os.path.join(opts.save_path, model.experiment_name))
             overlays = hostio.overlays(eval_images, masks, fade=0.4)
             hostio.save_all(overlays, save_dir)
-            hostio.save_submission_csv(masks, save_dir, hostio.IMG_PATCH_SIZE)
+            if masks.shape[1] % hostio.IMG_PATCH_SIZE or masks.shape[2] % hostio.IMG_PATCH_SIZE:
+                print("No submission.csv: {} x {} images are not made of whole {}-pixel patches".format(
+                    masks.shape[1], masks.shape[2], hostio.IMG_PATCH_SIZE))
+            else:
+                hostio.save_submission_csv(masks, save_dir, hostio.IMG_PATCH_SIZE)
             model.save_as(save_dir + "-model.chkpt")  # the model used for the submission
     if dist.is_initialized():
         dist.destroy_process_group()

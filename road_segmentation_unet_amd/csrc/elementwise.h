@@ -131,5 +131,10 @@ hipError_t ew_update_pack_many_adam_clip(const UpJob* jobs_dev, int njobs, int t
 hipError_t ew_extract_tiles(const float* imgs, float* tiles, int H, int S, int P, int stride, int pps, long t0, long ntiles, hipStream_t st);
 hipError_t ew_overlap_add(const float* prob, float* acc, float* hits, int nimg, int H, int P, int stride, int pps, long t0, long ntiles, hipStream_t st);
 hipError_t ew_overlap_finish(const float* acc, const float* hits, float* out, long n, hipStream_t st);
+void ew_tile_grid(int H, int W, int P, int stride, int* ny, int* nx);
+hipError_t ew_extract_tiles_rect(const float* imgs, float* tiles, int H, int W, int S, int P, int stride, long t0, long ntiles, hipStream_t st);
+hipError_t ew_overlap_add_rect(const float* prob, float* acc, float* hits, int nimg, int H, int W, int P, int stride, long t0, long ntiles,
+                               hipStream_t st);
+hipError_t ew_block_label_rect(const float* mask, float* out, int nimg, int H, int W, int ps, float thr, hipStream_t st);
 hipError_t ew_block_label(const float* mask, float* out, int64_t* labels, int nimg, int S, int ps, float thr, int mode, hipStream_t st);
 hipError_t ew_confusion(const int64_t* pred, const int64_t* truth, long n, unsigned long long* counts, hipStream_t st);

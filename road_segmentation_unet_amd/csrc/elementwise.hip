@@ -1146,6 +1146,92 @@ __global__ void k_overlap_finish(const float* __restrict__ acc, const float* __r
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) out[i] = acc[i] / hits[i];
 }
 
+// ---- the same tiler for [nimg][H][W] images of any size and any stride (rsu.h "tile grid of an H x W image") ----
+// Along an axis of length L: n_reg = (L - P) / stride + 1 regular tiles at i * stride, and, where (L - P) % stride != 0, one clamped tile
+// behind them at L - P. The origin of tile i is min(i * stride, L - P) either way.
+struct RectAxis {
+    int L;       // axis length
+    int nreg;    // regular tiles
+    int n;       // all tiles: nreg + (clamped ? 1 : 0)
+    int last;    // L - P: the clamped tile's origin (the last regular tile's where there is none)
+};
+static __host__ __device__ inline RectAxis rect_axis(int L, int P, int stride) {
+    RectAxis a;
+    a.L = L;
+    a.last = L - P;
+    a.nreg = (L - P) / stride + 1;
+    a.n = a.nreg + ((L - P) % stride ? 1 : 0);
+    return a;
+}
+static __device__ inline int rect_origin(const RectAxis& a, int i, int stride) {
+    const long o = (long)i * stride;
+    return o < a.last ? (int)o : a.last;
+}
+// np.pad 'symmetric' of any width: period 2L, the second half runs backwards
+static __device__ inline int rect_reflect(long c, int L) {
+    long m = c % (2L * L);
+    if (m < 0) m += 2L * L;
+    return (int)(m < L ? m : 2L * L - 1 - m);
+}
+
+__global__ void k_extract_tiles_rect(const float* __restrict__ imgs, float* __restrict__ tiles, RectAxis ay, RectAxis ax, int S, int P, int stride,
+                                     long t0, long ntiles) {
+    const int off = (S - P) / 2;
+    const long total = ntiles * S * S, per = (long)ax.n * ay.n;
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(e % S);
+        long r = e / S;
+        const int yy = (int)(r % S);
+        const long tg = t0 + r / S;
+        const long img = tg / per, tt = tg % per;
+        const int x0 = rect_origin(ax, (int)(tt / ay.n), stride), y0 = rect_origin(ay, (int)(tt % ay.n), stride);  // x outer, y inner
+        const int sy = rect_reflect((long)y0 + yy - off, ay.L), sx = rect_reflect((long)x0 + x - off, ax.L);
+        const float* s = imgs + ((img * ay.L + sy) * ax.L + sx) * 3;
+        float* d = tiles + e * 3;
+        d[0] = s[0]; d[1] = s[1]; d[2] = s[2];
+    }
+}
+
+// the regular tiles [lo, hi] of an axis that cover coordinate c (hi < lo: none), and whether the clamped tile does
+static __device__ inline void rect_cover(const RectAxis& a, int c, int P, int stride, int& lo, int& hi, int& clamped) {
+    lo = c - P + 1 <= 0 ? 0 : (int)(((long)c - P + stride) / stride);
+    hi = c / stride;
+    if (hi > a.nreg - 1) hi = a.nreg - 1;
+    clamped = a.n > a.nreg && c >= a.last;
+}
+
+// k_overlap_add's gather with the clamped tiles: per axis the regular tiles in increasing index, then the clamped one (it has the highest
+// index), x outer and y inner, so the sum still runs in increasing tile index; double within the call, one float add per call
+__global__ void k_overlap_add_rect(const float* __restrict__ prob, float* __restrict__ acc, float* __restrict__ hits, int nimg, RectAxis ay,
+                                   RectAxis ax, int P, int stride, long t0, long ntiles) {
+    const long total = (long)nimg * ay.L * ax.L, per = (long)ax.n * ay.n;
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(e % ax.L);
+        long r = e / ax.L;
+        const int y = (int)(r % ay.L);
+        const long img = r / ay.L;
+        int xi_lo, xi_hi, xc, yi_lo, yi_hi, yc;
+        rect_cover(ax, x, P, stride, xi_lo, xi_hi, xc);
+        rect_cover(ay, y, P, stride, yi_lo, yi_hi, yc);
+        double s = 0.0;
+        int cnt = 0;
+        for (int a = xi_lo; a <= xi_hi + xc; ++a) {
+            const int xi = a <= xi_hi ? a : ax.nreg, ox = a <= xi_hi ? a * stride : ax.last;
+            for (int b = yi_lo; b <= yi_hi + yc; ++b) {
+                const int yi = b <= yi_hi ? b : ay.nreg, oy = b <= yi_hi ? b * stride : ay.last;
+                const long t = img * per + (long)xi * ay.n + yi;
+                if (t < t0 || t >= t0 + ntiles) continue;
+                s += (double)prob[((t - t0) * P + (y - oy)) * P + (x - ox)];
+                ++cnt;
+            }
+        }
+        if (cnt) {
+            acc[e] += (float)s;
+            hits[e] += (float)cnt;
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // host-side launchers
 // ---------------------------------------------------------------------------------------------
@@ -1687,6 +1773,21 @@ hipError_t ew_overlap_finish(const float* acc, const float* hits, float* out, lo
     hipLaunchKernelGGL(k_overlap_finish, dim3(grid_for(n, 256)), dim3(256), 0, st, acc, hits, out, n);
     return hipGetLastError();
 }
+void ew_tile_grid(int H, int W, int P, int stride, int* ny, int* nx) {
+    *ny = rect_axis(H, P, stride).n;
+    *nx = rect_axis(W, P, stride).n;
+}
+hipError_t ew_extract_tiles_rect(const float* imgs, float* tiles, int H, int W, int S, int P, int stride, long t0, long ntiles, hipStream_t st) {
+    hipLaunchKernelGGL(k_extract_tiles_rect, dim3(grid_for(ntiles * S * S, 256)), dim3(256), 0, st, imgs, tiles, rect_axis(H, P, stride),
+                       rect_axis(W, P, stride), S, P, stride, t0, ntiles);
+    return hipGetLastError();
+}
+hipError_t ew_overlap_add_rect(const float* prob, float* acc, float* hits, int nimg, int H, int W, int P, int stride, long t0, long ntiles,
+                               hipStream_t st) {
+    hipLaunchKernelGGL(k_overlap_add_rect, dim3(grid_for((long)nimg * H * W, 256)), dim3(256), 0, st, prob, acc, hits, nimg,
+                       rect_axis(H, P, stride), rect_axis(W, P, stride), P, stride, t0, ntiles);
+    return hipGetLastError();
+}
 
 // ---------------------------------------------------------------------------------------------
 // post-processing (src/images.py:88-99, 256-266; src/summary.py:134-147)
@@ -1725,6 +1826,30 @@ __global__ void __launch_bounds__(256) k_block_label(const float* mask, float* o
 hipError_t ew_block_label(const float* mask, float* out, int64_t* labels, int nimg, int S, int ps, float thr, int mode, hipStream_t st) {
     const int nb = (S + ps - 1) / ps;
     hipLaunchKernelGGL(k_block_label, dim3(nimg * nb * nb), dim3(256), 0, st, mask, out, labels, S, ps, nb, thr, mode);
+    return hipGetLastError();
+}
+// k_block_label's mode 0 on a mask [nimg][H][W]: the same per-thread sums, reduction and rule, with a block grid of nby x nbx
+// (mask and out may be the same buffer, as there)
+__global__ void __launch_bounds__(256) k_block_label_rect(const float* mask, float* out, int H, int W, int ps, int nby, int nbx, float thr) {
+    const int b = blockIdx.x, by = b % nby, bx = (b / nby) % nbx;
+    const long img = b / (nby * nbx);
+    const int y0 = by * ps, x0 = bx * ps;
+    const int hh = min(ps, H - y0), ww = min(ps, W - x0);
+    float sum = 0.f;
+    for (int i = threadIdx.x; i < hh * ww; i += 256) sum += mask[(img * H + y0 + i / ww) * W + x0 + i % ww] >= 0.5f ? 1.f : 0.f;
+    __shared__ float red[256];
+    red[threadIdx.x] = sum;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    const float lab = (red[0] / (float)(hh * ww)) > thr ? 1.f : 0.f;
+    for (int i = threadIdx.x; i < hh * ww; i += 256) out[(img * H + y0 + i / ww) * W + x0 + i % ww] = lab;
+}
+hipError_t ew_block_label_rect(const float* mask, float* out, int nimg, int H, int W, int ps, float thr, hipStream_t st) {
+    const int nby = (H + ps - 1) / ps, nbx = (W + ps - 1) / ps;
+    hipLaunchKernelGGL(k_block_label_rect, dim3((unsigned)((long)nimg * nby * nbx)), dim3(256), 0, st, mask, out, H, W, ps, nby, nbx, thr);
     return hipGetLastError();
 }
 // tf.metrics.{accuracy, recall, precision} counters (summary.py:141-147): counts[0..3] += TP, FP, FN, TN over n int64 labels

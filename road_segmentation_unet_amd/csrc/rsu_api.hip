@@ -1606,6 +1606,32 @@ extern "C" int rsu_overlap_add(const float* prob, float* acc, float* hits, int n
     HIP_CHECK_RET(ew_overlap_add(prob, acc, hits, nimg, H, P, stride, pps, t0, ntiles, (hipStream_t)stream));
     return RSU_OK;
 }
+extern "C" int rsu_tile_grid(int H, int W, int P, int stride, int* ny, int* nx) {
+    if (!ny || !nx || P < 1 || P > H || P > W || stride < 1) return RSU_EINVAL;
+    ew_tile_grid(H, W, P, stride, ny, nx);
+    return RSU_OK;
+}
+// the checks the two rect tiler entries share: the grid, and a tile range inside the nimg * nx * ny tiles of the flattened list
+static int rect_tile_range_ok(int nimg, int H, int W, int P, int stride, long t0, long ntiles) {
+    int ny = 0, nx = 0;
+    if (nimg < 1 || rsu_tile_grid(H, W, P, stride, &ny, &nx) != RSU_OK) return 0;
+    const long per = (long)nx * ny;
+    if (per > 0x7fffffffffffffffL / nimg) return 0;
+    return t0 >= 0 && ntiles >= 1 && ntiles <= (long)nimg * per && t0 <= (long)nimg * per - ntiles;
+}
+extern "C" int rsu_extract_tiles_rect(const float* imgs, float* tiles, int nimg, int H, int W, int S, int P, int stride, long t0, long ntiles,
+                                      rsu_stream_t stream) {
+    if (!imgs || !tiles || P > S || (S - P) % 2 || !rect_tile_range_ok(nimg, H, W, P, stride, t0, ntiles)) return RSU_EINVAL;
+    if (ntiles > 0x7fffffffffffffffL / 3 / S / S) return RSU_E2BIG;
+    HIP_CHECK_RET(ew_extract_tiles_rect(imgs, tiles, H, W, S, P, stride, t0, ntiles, (hipStream_t)stream));
+    return RSU_OK;
+}
+extern "C" int rsu_overlap_add_rect(const float* prob, float* acc, float* hits, int nimg, int H, int W, int P, int stride, long t0, long ntiles,
+                                    rsu_stream_t stream) {
+    if (!prob || !acc || !hits || !rect_tile_range_ok(nimg, H, W, P, stride, t0, ntiles)) return RSU_EINVAL;
+    HIP_CHECK_RET(ew_overlap_add_rect(prob, acc, hits, nimg, H, W, P, stride, t0, ntiles, (hipStream_t)stream));
+    return RSU_OK;
+}
 extern "C" int rsu_overlap_finish(const float* acc, const float* hits, float* out, long n, rsu_stream_t stream) {
     if (!acc || !hits || !out || n < 1) return RSU_EINVAL;
     HIP_CHECK_RET(ew_overlap_finish(acc, hits, out, n, (hipStream_t)stream));
@@ -1618,6 +1644,14 @@ extern "C" int rsu_overlap_finish(const float* acc, const float* hits, float* ou
 extern "C" int rsu_quantize_mask(const float* masks, float* out, int nimg, int S, int patch_size, float threshold, rsu_stream_t stream) {
     if (!masks || !out || nimg < 1 || S < 1 || patch_size < 1 || patch_size > 64) return RSU_EINVAL;
     HIP_CHECK_RET(ew_block_label(masks, out, nullptr, nimg, S, patch_size, threshold, 0, (hipStream_t)stream));
+    return RSU_OK;
+}
+extern "C" int rsu_quantize_mask_rect(const float* masks, float* out, int nimg, int H, int W, int patch_size, float threshold,
+                                      rsu_stream_t stream) {
+    if (!masks || !out || nimg < 1 || H < 1 || W < 1 || patch_size < 1 || patch_size > 64) return RSU_EINVAL;
+    const long blocks = (long)nimg * ((H + patch_size - 1) / patch_size) * ((W + patch_size - 1) / patch_size);
+    if (blocks > 0x7fffffffL) return RSU_E2BIG;
+    HIP_CHECK_RET(ew_block_label_rect(masks, out, nimg, H, W, patch_size, threshold, (hipStream_t)stream));
     return RSU_OK;
 }
 extern "C" int rsu_labels_for_patches(const float* masks, int64_t* labels, int nimg, int S, int patch_size, float threshold,

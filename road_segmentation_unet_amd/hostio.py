@@ -24,6 +24,10 @@ def load(directory):
         a = np.asarray(Image.open(path))
         out.append(a.astype(np.float32) / (65535.0 if a.dtype == np.uint16 else 255.0))
     print("Loaded {} images from {}".format(len(out), directory))
+    shapes = sorted({a.shape for a in out})
+    if len(shapes) > 1:
+        raise ValueError("the images of {} differ in shape ({}): one call handles images of one common shape, put each shape into a "
+                         "directory of its own".format(directory, ", ".join("x".join(str(d) for d in sh) for sh in shapes)))
     return np.asarray(out)
 
 
@@ -36,6 +40,21 @@ def mirror_border(images, n):
     """images.py:269-281 (numpy 'symmetric' pad)"""
     pad = ((0, 0), (n, n), (n, n)) + (((0, 0),) if images.ndim == 4 else ())
     return np.pad(images, pad, "symmetric")
+
+
+def tile_origins(length, patch_size, stride):
+    """The prediction tiles' origins along one axis (include/rsu.h rsu_tile_grid): 0, stride, 2 stride, ... while origin + patch_size <=
+    length and, where (length - patch_size) % stride != 0, one more tile at length - patch_size: the clamped last tile. An axis with
+    (length - patch_size) % stride == 0 has the reference's grid, range(0, length - patch_size + 1, stride)."""
+    length, patch_size, stride = int(length), int(patch_size), int(stride)
+    if patch_size < 1 or stride < 1:
+        raise ValueError("tile_origins: patch_size %d and stride %d must be at least 1" % (patch_size, stride))
+    if length < patch_size:
+        raise ValueError("tile_origins: a side of %d pixels is shorter than --patch_size=%d" % (length, patch_size))
+    origins = list(range(0, length - patch_size + 1, stride))
+    if origins[-1] != length - patch_size:
+        origins.append(length - patch_size)
+    return origins
 
 
 def extract_patches(images, patch_size, stride=None, predict_patch_size=None):
@@ -84,9 +103,9 @@ def expand_and_rotate(imgs, angles, offset=0):
 def quantize_mask(masks, threshold, patch_size):
     """images.py:256-266: per patch_size block, label = mean(mask >= 0.5) > threshold"""
     out = masks.copy()
-    n, size = masks.shape[0], masks.shape[1]
-    for y in range(0, size, patch_size):
-        for x in range(0, size, patch_size):
+    n, height, width = masks.shape[:3]
+    for y in range(0, height, patch_size):
+        for x in range(0, width, patch_size):
             lab = (masks[:, y:y + patch_size, x:x + patch_size, 0] >= 0.5).reshape(n, -1).mean(axis=1) > threshold
             out[:, y:y + patch_size, x:x + patch_size, 0] = lab[:, None, None]
     return out
@@ -98,15 +117,25 @@ def labels_for_patches(patches):
 
 
 def submission_rows(masks, patch_size=IMG_PATCH_SIZE):
-    """body of images.save_submission_csv (images.py:206-237): '{img:03d}_{x}_{y},{label}' with x the outer index"""
+    """body of images.save_submission_csv (images.py:206-237): '{img:03d}_{x}_{y},{label}' with x the outer index. masks [n, H, W(, 1)]
+    with H and W multiples of patch_size (ValueError otherwise); H != W gives (W / patch_size) x (H / patch_size) rows per image."""
     if masks.ndim == 4:
         masks = masks.squeeze(-1)
     n, h, w = masks.shape
-    assert h == w, "images should be square"
-    pps = h // patch_size
-    labels = labels_for_patches(extract_patches(masks, patch_size)).reshape(n, pps, pps)
+    if h < patch_size or w < patch_size or h % patch_size or w % patch_size:
+        raise ValueError("submission rows need masks whose sides are multiples of %d, not %d x %d" % (patch_size, h, w))
+    nx, ny = w // patch_size, h // patch_size
+    if h == w:
+        patches = extract_patches(masks, patch_size)
+    else:   # extract_patches' order and float64 patches on a rectangle
+        patches = np.zeros((n * nx * ny, patch_size, patch_size))
+        for k in range(n):
+            for j in range(nx):
+                for i in range(ny):
+                    patches[(k * nx + j) * ny + i] = masks[k, i * patch_size:(i + 1) * patch_size, j * patch_size:(j + 1) * patch_size]
+    labels = labels_for_patches(patches).reshape(n, nx, ny)
     return ["{:03d}_{}_{},{}".format(k + 1, patch_size * j, patch_size * i, labels[k, j, i])
-            for k in range(n) for j in range(pps) for i in range(pps)]
+            for k in range(n) for j in range(nx) for i in range(ny)]
 
 
 def save_submission_csv(masks, path, patch_size=IMG_PATCH_SIZE):

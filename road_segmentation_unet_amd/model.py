@@ -793,56 +793,71 @@ class ConvolutionalModel:
         """Run inference on `imgs` and return predicted masks (tf_aerial_images.py:271-328).
         averaged: None predicts with the averaged weights when the net has them (--ema_decay), True demands them (ValueError on a net
         without), False forces the raw weights (evaluate has the same argument); the forward passes run inside net.averaged_weights().
-        imgs: [num_images, H, H, 3] in [0,1]; returns numpy [num_images, H, H, 1] road probabilities.
-        Ensemble x6 -> mirror border -> tiles (x-outer order) -> batched forward -> overlap average -> inverse ensemble.
+        imgs: [num_images, H, W, 3] in [0,1], one shape per call, H and W at least --patch_size (ValueError otherwise) and any --stride:
+        where the stride does not cover an axis its last tile is clamped to the image's edge (hostio.tile_origins). Returns numpy
+        [num_images, H, W, 1] road probabilities.
+        Ensemble x6 -> mirror border -> tiles (x-outer order) -> batched forward -> overlap average -> inverse ensemble. With H != W the
+        quarter turns are W x H images: they are predicted in a pass of their own and the six terms added in the reference's order.
         Tiles are sharded contiguously over ranks; the accumulators are summed with one all-reduce."""
         opts, net = self._options, self.net
-        dev = net.device
         ctx, _ = self._averaged_ctx(averaged, "predict")
-        imgs_t = torch.as_tensor(np.asarray(imgs)).to(dev, torch.float32)
-        num_images = imgs_t.shape[0]
-        if opts.ensemble_prediction:
-            imgs_t = dimages.image_augmentation_ensemble(imgs_t).contiguous()
-            num_images = imgs_t.shape[0]
-        H, P, S, B = imgs_t.shape[1], opts.patch_size, self.input_size, self.local_batch
-        assert (H - P) % opts.stride == 0, "Stride sliding should cover the whole image"
-        pps = (H - P) // opts.stride + 1
-        num_patches = num_images * pps * pps
-        acc = dimages.OverlapAccumulator(num_images, H, P, opts.stride, device=dev)
+        imgs_t = torch.as_tensor(np.asarray(imgs)).to(net.device, torch.float32)
+        if imgs_t.dim() != 4 or imgs_t.shape[3] != 3:
+            raise ValueError("predict: images must be [n, H, W, 3], not %s" % (tuple(imgs_t.shape),))
+        H, W = int(imgs_t.shape[1]), int(imgs_t.shape[2])
+        if H < opts.patch_size or W < opts.patch_size:
+            raise ValueError("predict: an image of %d x %d pixels is smaller than --patch_size=%d: predict with a smaller --patch_size "
+                             "(the weights do not depend on it)" % (H, W, opts.patch_size))
         was_training = net.training
         net.training = False
-        reduced = False
-        with ctx:
-            if os.environ.get("RSU_PREDICT_SHARED", "1") == "1" and pps > 1:
-                # every rank fills the tiles of its own phase classes (zeros elsewhere) and overlap-adds the lot locally: the hit counts are
-                # then complete on every rank, and ONE all-reduce of the accumulator (H*H floats per image variant, 1.4 MB at 604 px --
-                # not the 1.3 GB of tiles) completes the sums
-                tiles = self._shared_window_tiles(imgs_t, pps)
-                acc.add(tiles.view(-1, P, P), 0)
-                if self.world > 1:
-                    dist.all_reduce(acc.acc)
-                reduced = True
-            else:
-                per = -(-num_patches // self.world)
-                lo, hi = min(self.rank * per, num_patches), min((self.rank + 1) * per, num_patches)
-                net.ensure_tuned(training=False)
-                for t0 in range(lo, hi, B):
-                    nb = min(B, hi - t0)
-                    if nb < B:
-                        net.x.zero_()  # the reference pads the last batch with zero patches (tf_aerial_images.py:298-301)
-                    dimages.extract_mirrored_patches(imgs_t, S, P, opts.stride, t0=t0, ntiles=nb, out=net.x[:nb])
-                    net.forward_device()
-                    acc.add(net.prob[:nb], t0)
-        net.training = was_training
-        if self.world > 1 and not reduced:
-            dist.all_reduce(acc.acc)
-            dist.all_reduce(acc.hits)
-        masks = acc.finish()
-        if opts.ensemble_prediction:
-            masks = dimages.invert_image_augmentation_ensemble(masks)
+        try:
+            with ctx:
+                if not opts.ensemble_prediction:
+                    masks = self._predict_masks(imgs_t)
+                elif H == W:
+                    masks = dimages.invert_image_augmentation_ensemble(self._predict_masks(dimages.image_augmentation_ensemble(imgs_t).contiguous()))
+                else:
+                    upright, turned = dimages.image_augmentation_ensemble_rect(imgs_t)
+                    masks = dimages.invert_image_augmentation_ensemble_rect(self._predict_masks(upright.contiguous()),
+                                                                            self._predict_masks(turned.contiguous()))
+        finally:
+            net.training = was_training
         return masks.cpu().numpy()
 
-    def _shared_window_tiles(self, imgs_t, pps):
+    def _predict_masks(self, imgs_t):
+        """predict() behind the ensemble, for device images [n, H, W, 3] of one shape: the device masks [n, H, W, 1]. Runs inside predict's
+        weight context with net.training off."""
+        opts, net = self._options, self.net
+        dev = net.device
+        num_images, H, W = imgs_t.shape[0], imgs_t.shape[1], imgs_t.shape[2]
+        P, S, B = opts.patch_size, self.input_size, self.local_batch
+        acc = dimages.OverlapAccumulator(num_images, (H, W), P, opts.stride, device=dev)
+        num_patches = num_images * acc.nx * acc.ny
+        if os.environ.get("RSU_PREDICT_SHARED", "1") == "1" and acc.nx * acc.ny > 1:
+            # every rank fills the tiles of its own phase classes (zeros elsewhere) and overlap-adds the lot locally: the hit counts are
+            # then complete on every rank, and ONE all-reduce of the accumulator (H*W floats per image variant, 1.4 MB at 604 px --
+            # not the 1.3 GB of tiles) completes the sums
+            tiles = self._shared_window_tiles(imgs_t)
+            acc.add(tiles.view(-1, P, P), 0)
+            if self.world > 1:
+                dist.all_reduce(acc.acc)
+        else:
+            per = -(-num_patches // self.world)
+            lo, hi = min(self.rank * per, num_patches), min((self.rank + 1) * per, num_patches)
+            net.ensure_tuned(training=False)
+            for t0 in range(lo, hi, B):
+                nb = min(B, hi - t0)
+                if nb < B:
+                    net.x.zero_()  # the reference pads the last batch with zero patches (tf_aerial_images.py:298-301)
+                dimages.extract_mirrored_patches(imgs_t, S, P, opts.stride, t0=t0, ntiles=nb, out=net.x[:nb])
+                net.forward_device()
+                acc.add(net.prob[:nb], t0)
+            if self.world > 1:
+                dist.all_reduce(acc.acc)
+                dist.all_reduce(acc.hits)
+        return acc.finish()
+
+    def _shared_window_tiles(self, imgs_t, pps=None):
         """The sliding window of tf_aerial_images.py:288-320 without its redundancy. The network is fully convolutional with VALID
         convolutions; its L-1 pools tie the result to the input offset modulo 2^(L-1) only. Tiles whose offsets agree modulo that
         period (on both axes) are therefore sub-windows of ONE forward pass over the union of their input windows: with stride 12
@@ -851,49 +866,67 @@ class ConvolutionalModel:
         Every output element sees exactly the arithmetic of the per-tile pass (the reduction order of an output element does not
         depend on the tile it lies in), so the tiles are bit-identical; they are assembled in the reference's tile order and
         averaged by the same overlap kernel. Phase classes are dealt round-robin to the ranks.
-        Returns float32 [n, pps, pps, P, P] indexed [image][x index][y index] (this rank's classes; zeros elsewhere)."""
+        The tiles are those of hostio.tile_origins per axis (the x and y lists differ for H != W): a clamped last tile joins the class
+        of its phase behind that class's regular tiles, or is a class of its own. A tile's sub-window sits at its origin minus the first
+        origin of its run. `pps` (the tiles per side of a square image covered exactly) is implied by the image and accepted for callers
+        that pass it.
+        Returns float32 [n, nx, ny, P, P] indexed [image][x index][y index] (this rank's classes; zeros elsewhere)."""
         opts, net = self._options, self.net
         dev = net.device
-        n, H = imgs_t.shape[0], imgs_t.shape[1]
+        n, H, W = imgs_t.shape[0], imgs_t.shape[1], imgs_t.shape[2]
         P, S, L, stride = opts.patch_size, self.input_size, opts.num_layers, opts.stride
         off = (S - P) // 2
         period = 2 ** (L - 1)
-        g = stride * period // math.gcd(stride, period)   # spacing of same-phase tiles
-        # symmetric ("mirror_border", images.py:269-281) padding by index arithmetic; one extra window of zeros behind it
-        c = torch.arange(-off, H + off, device=dev)
-        idx = torch.where(c < 0, -c - 1, torch.where(c >= H, 2 * H - c - 1, c))
-        padded = imgs_t[:, idx][:, :, idx].contiguous()           # [n, Hp, Hp, 3]
-        Hp = padded.shape[1]
+        origins_x, origins_y = hostio.tile_origins(W, P, stride), hostio.tile_origins(H, P, stride)
+        assert pps is None or (H == W and pps == len(origins_x) == len(origins_y))
+
+        def mirror(length):
+            # symmetric ("mirror_border", images.py:269-281) padding of any width by index arithmetic: period 2 * length
+            m = torch.remainder(torch.arange(-off, length + off, device=dev), 2 * length)
+            return torch.where(m < length, m, 2 * length - 1 - m)
+        padded = imgs_t[:, mirror(H)][:, :, mirror(W)].contiguous()           # [n, Hp, Wp, 3]; windows reaching past it are zero-filled
+        Hp, Wp = padded.shape[1], padded.shape[2]
         smax = int(os.environ.get("RSU_PREDICT_MAX_WINDOW", "1100"))   # largest input window (memory: ~1.7 GB per image at L = 6)
-        kmax = max(1, 1 + (smax - S) // g)
-        # per axis: tile indices of each phase class, cut into runs of <= kmax tiles spaced g apart
-        step = g // stride
-        runs = []
-        for first in range(min(step, pps)):
-            cls = list(range(first, pps, step))
-            runs += [cls[i:i + kmax] for i in range(0, len(cls), kmax)]
-        tiles = torch.zeros((n, pps, pps, P, P), dtype=torch.float32, device=dev)   # [img][xi][yi] = the reference's tile order
-        jobs = [(rx, ry) for rx in runs for ry in runs]
+
+        def runs_of(origins):
+            # per axis: the tile indices of each phase class in the order the classes first appear, cut into runs whose input window
+            # S + (last origin - first origin) stays within smax (a run of one tile always fits)
+            classes = {}
+            for i, o in enumerate(origins):
+                classes.setdefault(o % period, []).append(i)
+            runs = []
+            for cls in classes.values():
+                run = [cls[0]]
+                for i in cls[1:]:
+                    if S + origins[i] - origins[run[0]] <= smax:
+                        run.append(i)
+                    else:
+                        runs.append(run)
+                        run = [i]
+                runs.append(run)
+            return runs
+        tiles = torch.zeros((n, len(origins_x), len(origins_y), P, P), dtype=torch.float32, device=dev)   # [img][xi][yi] = the reference's tile order
+        jobs = [(rx, ry) for rx in runs_of(origins_x) for ry in runs_of(origins_y)]
         bmax = max(1, int(os.environ.get("RSU_PREDICT_WINDOW_BATCH", "6")))   # ~2 GB of activations per window image at L = 6
         Bw = max(d for d in range(1, min(n, bmax) + 1) if n % d == 0)
         for ji, (rx, ry) in enumerate(jobs):
             if ji % self.world != self.rank:
                 continue
-            k = max(len(rx), len(ry))
-            Pk = P + (k - 1) * g
+            ox0, oy0 = origins_x[rx[0]], origins_y[ry[0]]
+            Pk = P + max(origins_x[rx[-1]] - ox0, origins_y[ry[-1]] - oy0)
             wn = self._window_net(Pk, Bw)
             wn.ensure_tuned(training=False)   # the window nets have geometries of their own: one untimed tuning pass each
             Sk = wn.S
-            ox0, oy0 = rx[0] * stride, ry[0] * stride
-            h, w = min(Sk, Hp - oy0), min(Sk, Hp - ox0)
+            h, w = min(Sk, Hp - oy0), min(Sk, Wp - ox0)
             for b0 in range(0, n, Bw):
                 if h < Sk or w < Sk:
                     wn.x.zero_()
                 wn.x[:, :h, :w] = padded[b0:b0 + Bw, oy0:oy0 + h, ox0:ox0 + w]
                 wn.forward_device()
-                for a, xi in enumerate(rx):
-                    for bb, yi in enumerate(ry):
-                        tiles[b0:b0 + Bw, xi, yi] = wn.prob[:, bb * g:bb * g + P, a * g:a * g + P]
+                for xi in rx:
+                    for yi in ry:
+                        dy, dx = origins_y[yi] - oy0, origins_x[xi] - ox0
+                        tiles[b0:b0 + Bw, xi, yi] = wn.prob[:, dy:dy + P, dx:dx + P]
         return tiles
 
     def _window_net(self, Pk, Bw):
@@ -922,14 +955,18 @@ class ConvolutionalModel:
         return np.concatenate(masks, axis=0) if len(masks) > 1 else masks[0]
 
     def quantize_mask(self, masks, threshold, patch_size):
-        """images.quantize_mask (images.py:256-266) on the device: masks [n, H, H, 1] float -> same shape, every patch_size block
-        overwritten with its label mean(mask >= 0.5) > threshold"""
+        """images.quantize_mask (images.py:256-266) on the device: masks [n, H, W, 1] float -> same shape, every patch_size block
+        overwritten with its label mean(mask >= 0.5) > threshold (a block cut by the image's edge: over the pixels it holds)"""
         import ctypes
         a = np.asarray(masks)
         t = torch.as_tensor(np.ascontiguousarray(a[..., 0], dtype=np.float32)).to(self.net.device)
         st = ctypes.c_void_p(torch.cuda.current_stream(self.net.device).cuda_stream)
-        call("rsu_quantize_mask", ctypes.c_void_p(t.data_ptr()), ctypes.c_void_p(t.data_ptr()), t.shape[0], t.shape[1], int(patch_size),
-             float(threshold), st)
+        if t.shape[1] == t.shape[2]:
+            call("rsu_quantize_mask", ctypes.c_void_p(t.data_ptr()), ctypes.c_void_p(t.data_ptr()), t.shape[0], t.shape[1], int(patch_size),
+                 float(threshold), st)
+        else:
+            call("rsu_quantize_mask_rect", ctypes.c_void_p(t.data_ptr()), ctypes.c_void_p(t.data_ptr()), t.shape[0], t.shape[1], t.shape[2],
+                 int(patch_size), float(threshold), st)
         return t.cpu().numpy()[..., None].astype(a.dtype)
 
     # ------------------------------------------------------------------ checkpoints
