@@ -366,7 +366,9 @@ int rsu_dropout_fwd(const void* x, void* y, long n, float keep, unsigned key, rs
 /* ---- 2x2 stride-2 transposed convolution (unet.py:67-68) ---------------------------------- */
 int rsu_convT2x2_fwd(const void* x, const void* packed_fwd, const float* bias, void* y, int N, int H, int W,
                      int Cin, int Cout, int ncu, rsu_stream_t stream);
-/* dx bf16 [N][H][W][Cin] = out_scale * sum_{a,b,co} dy[2i+a][2j+b][co] K[a][b][co][ci], times (relu_src > 0) if given */
+/* dx bf16 [N][H][W][Cin] = out_scale * sum_{a,b,co} dy[2i+a][2j+b][co] K[a][b][co][ci], times (relu_src > 0) if given.
+ * out_scale != 1 is applied by a second pass over the stored tensor: dx = bf16(out_scale * bf16(sum)), two roundings by design
+ * (tests/test_gpu_rounding.py holds it to exactly these two). */
 int rsu_convT2x2_bwd_data(const void* dy, const void* packed_bwd, void* dx, const void* relu_src, float out_scale,
                           int N, int H, int W, int Cin, int Cout, int ncu, rsu_stream_t stream);
 /* dK f32 [2][2][Cout][Cin] and, when db != NULL, db f32 [Cout] = sum over all pixels of dy (BiasAddGrad of the transposed

@@ -1127,7 +1127,12 @@ extern "C" int rsu_conv2d_bwd_weight(const rsu_src_t* src, const void* dz, float
 }
 
 extern "C" size_t rsu_convT2x2_bwd_weight_ws_floats(int Cin, int Cout) {
-    return wgrad_max_slabs(IGW_CFG_64x64, Cin, Cout) * (4 * (size_t)Cout * Cin + Cout);
+    // either kernel the launch may take: igemm_wgrad's shapes, or igemm_wgt, whose workgroups own 128 input channels -- for 64 < Cin < 128
+    // it has half the blocks of the 64x64 shape and so up to twice the pixel splits (Cin = Cout = 96: 128 against 64 slabs)
+    size_t slabs = wgrad_max_slabs(IGW_CFG_64x64, Cin, Cout);
+    const size_t wgt = (size_t)(256 / igemm_wgt_blocks(Cin, Cout));
+    if (wgt > slabs) slabs = wgt;
+    return slabs * (4 * (size_t)Cout * Cin + Cout);
 }
 extern "C" int rsu_convT2x2_bwd_weight(const void* x, const void* dy, float* dK, float* db, float* ws, int N, int H, int W, int Cin,
                                        int Cout, int ncu, rsu_stream_t stream) {

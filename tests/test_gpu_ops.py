@@ -133,7 +133,7 @@ def test_conv2d_fwd_split_k(N, H, W, segs, Cout, capfd, monkeypatch):
     y1 = torch.full((N, Ho, Wo, Cout), float("nan"), dtype=torch.bfloat16, device=hu.DEV)
     call("rsu_conv2d_fwd", srcs, len(segs), hu.ptr(wp), hu.ptr(bd), hu.ptr(y1), N, H, W, Cout, 1, 1, 0, hu.stream())
     hu.assert_bf16_close(outs[0], hu.host(y1).astype(np.float64), "split-K vs unsplit", ulps=1.0)
-    assert (outs[0] != hu.host(y1)).mean() < 0.05
+    assert (outs[0] != hu.host(y1)).mean() <= 0.01   # (a correct fp32 finish: ~3e-4; partial sums kept in bf16: a third. tests/test_gpu_rounding.py)
 
 
 @pytest.mark.parametrize("H,Cin,Cout", [(32, 512, 1024), (30, 1024, 1024), (20, 1024, 2048)])
@@ -168,7 +168,7 @@ def test_split_k_plan_depends_on_the_batch_and_by_how_much(H, Cin, Cout, capfd, 
         np.testing.assert_array_equal(outs[4][n], outs[4][0])
     hu.assert_bf16_close(outs[4][:1], ref, "N = 4")
     hu.assert_bf16_close(outs[4][:1], outs[1].astype(np.float64), "N = 4 vs N = 1", ulps=1.0)
-    assert (outs[4][:1] != outs[1]).mean() < 0.05
+    assert (outs[4][:1] != outs[1]).mean() <= 0.01
 
 
 @pytest.mark.parametrize("N,H,W,Cin,Cout", [(1, 20, 20, 512, 512), (2, 14, 14, 256, 1024)])
@@ -216,7 +216,7 @@ def test_conv2d_bwd_data(N, H, W, Cin, Cout, dil):
     hu.assert_bf16_close(hu.host(dx2), g, "conv2d_bwd_data")
     first = hu.host(dx2).copy()
     call("rsu_conv2d_bwd_data", hu.ptr(dzd), hu.ptr(wp), hu.ptr(dx2), None, 1, N, H, W, Cin, 0, Cin, Cout, dil, 0, hu.stream())
-    hu.assert_bf16_close(hu.host(dx2), first + g, "conv2d_bwd_data accumulate", ulps=2.0)
+    hu.assert_bf16_close(hu.host(dx2), first.astype(np.float64) + g, "conv2d_bwd_data accumulate")   # q(stored + sum): one more rounding of an fp32 value
 
 
 def test_conv2d_bwd_data_source_slice():
@@ -667,9 +667,12 @@ def test_convT(N, H, W, Cin, Cout):
     call("rsu_convT2x2_bwd_data", hu.ptr(dyd), hu.ptr(pb), hu.ptr(dx), hu.ptr(xdrop), float(inv), N, H, W, Cin, Cout, 0, hu.stream())
     hu.assert_bf16_close(hu.host(dx), U.relu_bwd(x, rdx * m * inv), "convT bwd_data with dropout")
     dK = torch.full((2, 2, Cout, Cin), float("nan"), dtype=torch.float32, device=hu.DEV)
-    ws = torch.zeros(lib().rsu_convT2x2_bwd_weight_ws_floats(Cin, Cout), dtype=torch.float32, device=hu.DEV)
+    nws = lib().rsu_convT2x2_bwd_weight_ws_floats(Cin, Cout)
+    ws = torch.zeros(nws + 4096, dtype=torch.float32, device=hu.DEV)
+    ws[nws:] = 12345.0  # guard band: at 64 < Cin < 128 igemm_wgt splits the pixels further than the generic kernel the workspace was once sized for
     dbT = torch.full((Cout,), float("nan"), dtype=torch.float32, device=hu.DEV)
     call("rsu_convT2x2_bwd_weight", hu.ptr(xd), hu.ptr(dyd), hu.ptr(dK), hu.ptr(dbT), hu.ptr(ws), N, H, W, Cin, Cout, 0, hu.stream())
+    assert bool((ws[nws:] == 12345.0).all()), "workspace overrun"
     hu.assert_f32_close(hu.host(dK), rdK, "convT bwd_weight")
     hu.assert_f32_close(hu.host(dbT), rdb, "convT bias grad fused in bwd_weight")
 
