@@ -25,6 +25,16 @@
  *   - MFMA kernels read bf16 copies of the weights in "fragment order" produced by the
  *     rsu_pack_* calls (re-pack after every optimizer step).
  *   - return value: 0 on success, negative errno-style code otherwise (never throws).
+ *
+ * Memory contract
+ *   An entry point reads and writes only [ptr, ptr + size) of the tensors it is given, with the sizes this header states for them (of a
+ *   cropped rsu_src_t: the whole [N][H][W][C] tensor, its window included), and only [0, advertised) of a workspace, `advertised` being
+ *   what the entry's rsu_*_ws_floats / rsu_*_ws_bytes function returns; a packed weight buffer has exactly rsu_packed_bytes /
+ *   rsu_packed_first_bytes bytes. It writes nothing to its inputs, and its results do not depend on whatever lies around any of these
+ *   ranges: a caller may place its buffers back to back. The kernels' buffer descriptors do not bound anything: the
+ *   contract rests on the kernels' own predicates, and tests/test_gpu_fenced.py holds every launching entry point to it inside an arena
+ *   whose every byte outside the payloads is a NaN pattern. Base pointers are 256-byte aligned there; the 16-byte (4-byte, 8-byte)
+ *   alignment notes at the entries below are what the ABI requires.
  */
 #ifndef RSU_H_
 #define RSU_H_
@@ -90,7 +100,8 @@ int rsu_autotune_import(const int* rows, int nrows);
 int rsu_input_size_needed(int output_size, int num_layers, int* input_size);
 
 /* ---- weight packing (float32 reference layout -> bf16 MFMA fragment order) -------------- */
-/* Bytes of a packed buffer: taps * roundup(sum_i roundup(seg_c[i],32)) * roundup(rows,64) * 2 */
+/* Bytes of a packed buffer: taps * sum_i roundup(seg_c[i],32) * roundup(rows,128) * 2. The rsu_pack_* calls and rsu_pack_table_run write
+ * every byte of it, the zero padding of the fragment order included: the buffer needs no initialisation. */
 size_t rsu_packed_bytes(int taps, int rows, const int* seg_c, int nseg);
 /* conv forward (unet.py:34-45,88-91): A[tap][co][ci]; seg_c = channel count of each concat source */
 int rsu_pack_conv_fwd(const float* w_hwio, void* packed, int k, int Cin, int Cout, const int* seg_c, int nseg,
@@ -389,7 +400,10 @@ int rsu_momentum_step(float* w, float* acc, const float* g, float lr, float mu, 
  * (kind RSU_PACK_CONV_FWD: packed_fwd + one backward-data pack per concat source in packed_bwd[0..nseg), or packed_bwd = NULL for a
  * forward-only net; RSU_PACK_CONVT_FWD: packed_fwd (four matrices) + packed_bwd[0]; RSU_PACK_CONV_FIRST: packed_fwd only),
  * rsu_update_table_add_plain for everything no MFMA kernel reads (biases, colour adjust, the 1x1 head; w / acc / g 16-byte aligned) --
- * then rsu_update_table_finish, copy the table to the device once, and rsu_update_table_run after every backward pass. */
+ * then rsu_update_table_finish, copy the table to the device once, and rsu_update_table_run after every backward pass. The pass
+ * rewrites the 32 x 32 blocks of a packed buffer that hold weights; the zero padding beyond them (rows up to a multiple of 128) is not
+ * written again (rewriting it every step would cost the pass bandwidth for bytes that never change): every packed buffer of a table must
+ * have been packed ONCE by rsu_pack_* / rsu_pack_table_run (from the initial weights) before the first run. */
 size_t rsu_update_table_entry_bytes(void);
 int rsu_update_table_add_plain(void* host_table, int index, float* w, float* acc, const float* g, long n);
 int rsu_update_table_add(void* host_table, int index, int kind, float* w, float* acc, const float* g, void* packed_fwd,

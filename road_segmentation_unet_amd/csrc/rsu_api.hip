@@ -752,10 +752,10 @@ static int run_fwd(const rsu_src_t* srcs, int nsrc, const void* wp, long wp_y_st
             const long tiles = (long)N * pl2.g.nstrips * pl2.g.tiles_per_strip;
             const long workers = pl2.grid_x / (pl2.ncob * pl2.ksplit);
             const long rounds = (tiles + workers - 1) / workers;
-            fprintf(stderr, "[plan fwd2] N%d %dx%d Cout%d ntap%d pad%d: cfg%d TN%d TM%d SW%d strips%d tps%d halo%d tiles%ld grid%d rounds%ld ksplit%d cgrp%d pix_util %.3f total_util %.3f\n",
+            fprintf(stderr, "[plan fwd2] N%d %dx%d Cout%d ntap%d pad%d: cfg%d TN%d TM%d SW%d strips%d tps%d halo%d tiles%ld grid%d rounds%ld ksplit%d cgrp%d pix_util %.3f total_util %.3f pool%d\n",
                     N, Ho, Wo, Cout, ntap, pad, pl2.cfg, ci.TN, ci.TM, pl2.g.SW, pl2.g.nstrips, pl2.g.tiles_per_strip, pl2.g.npix_max, tiles,
                     pl2.grid_x, rounds, pl2.ksplit, pl2.cob_group, (double)N * Ho * Wo / ((double)tiles * ci.TM),
-                    (double)N * Ho * Wo * Cout / ((double)rounds * pl2.grid_x * ci.TM * ci.TN) * pl2.ksplit);
+                    (double)N * Ho * Wo * Cout / ((double)rounds * pl2.grid_x * ci.TM * ci.TN) * pl2.ksplit, pool ? 1 : 0);   // pool1: the max-pool is folded into this launch
         }
         if (tune_now && !split) {
             // time every admissible shape of the same channel-block width (1 untimed + 5 timed launches each, fastest counts, device idle; the
