@@ -1,4 +1,4 @@
-"""ctypes binding of librsu_hip.so (the C ABI of include/rsu.h).
+"""ctypes binding of librsu_hip.so (the C ABI of include/rsu.h and include/rsu_optim.h).
 
 The library is REQUIRED: there is no CPU or eager-PyTorch fallback anywhere in this package. If the
 shared object is missing or a symbol cannot be resolved, importing/using the product path raises."""
@@ -152,6 +152,12 @@ SIGNATURES = {
     "rsu_plan": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(RsuPlanRow), _i, _PI, ctypes.POINTER(RsuPlanTotals)]),
 }
 
+# the same for include/rsu_optim.h, the second public header of the same library
+SIGNATURES_OPTIM = {
+    "rsu_update_table_run_decay": (_i, [_vp, _i, _i, _f, _f, _f, _f, _i, _vp, _vp]),
+    "rsu_update_table_run_adam_decay": (_i, [_vp, _i, _i, _f, _f, _f, _f, _f, _f, _i, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -167,7 +173,7 @@ def lib():
             raise RsuError("HIP extension missing: %s (build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            "or `make -C road_segmentation_unet_amd/csrc`); there is no fallback path" % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_OPTIM.items()):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -180,6 +186,7 @@ EVAL_BINS = 256   # rsu.h RSU_EVAL_BINS
 BORDER_D2_INF, BORDER_MAX_SIDE = 0x7fffffff, 1024   # rsu.h RSU_BORDER_D2_INF, RSU_BORDER_MAX_SIDE
 CLIP_STATE_BYTES, CLIP_CLIPPED, CLIP_NONFINITE, GRAD_NORM_BLOCK_FLOATS = 32, 1, 2, 16384   # rsu.h RSU_CLIP_*, RSU_GRAD_NORM_BLOCK_FLOATS
 GRAD_ACCUMULATE_BLOCK_FLOATS = 8192   # rsu.h RSU_GRAD_ACCUMULATE_BLOCK_FLOATS
+DECAY_L2, DECAY_DECOUPLED = 0, 1   # rsu_optim.h RSU_DECAY_*
 AFFINE_MAX_LAUNCH = 32   # rsu.h RSU_AFFINE_MAX_LAUNCH
 ELASTIC_MAX_LAUNCH, ELASTIC_MAX_GRID = 32, 16   # rsu.h RSU_ELASTIC_MAX_LAUNCH, RSU_ELASTIC_MAX_GRID
 JITTER_MAX_LAUNCH = 32   # rsu.h RSU_JITTER_MAX_LAUNCH

@@ -60,6 +60,10 @@ def main(argv=None):
             opts.class_weights = None
     model = ConvolutionalModel(opts)
     print("Running on device {}".format(model.net.device))
+    if opts.weight_decay > 0.0:
+        decays, live = model.net.decaying_parameters()
+        print("Weight decay: {} lambda {:g}, {} of {} live parameters decay (conv kernels; biases, colour adjust and the head do not); "
+              "the reported loss excludes the penalty".format(opts.weight_decay_mode, opts.weight_decay, decays, live))
 
     if opts.restore_model:
         if opts.model_path is not None:
@@ -90,6 +94,12 @@ def main(argv=None):
             print("Train on {} patches of size {}x{}".format(patches.shape[0], patches.shape[1], patches.shape[2]))
             labels_patches = hostio.extract_patches(gt_exp, patch_size=opts.patch_size, stride=opts.stride)
             print("Train on {} groundtruth patches of size {}x{}".format(*labels_patches.shape[:3]))
+        if opts.lr_schedule in ("cosine", "linear"):
+            given = opts.lr_total_steps
+            total = model.resolve_lr_total_steps(patches.shape[0])
+            print("Learning-rate schedule: {} over {} optimizer steps{}, warm-up {} steps, final {:g} x lr".format(
+                opts.lr_schedule, total, "" if given else " ({} epoch(s) x {} steps)".format(opts.num_epoch, total // opts.num_epoch),
+                opts.lr_warmup_steps, opts.lr_final))
         validation = None
         if held_out is not None:
             validation = hostio.validation_patches(held_out[0], held_out[1], input_size, opts.patch_size)

@@ -54,15 +54,18 @@ hipError_t ew_momentum(float* w, float* acc, const float* g, float lr, float mu,
 // the update rules of the optimizer passes (template argument of k_update_pack_many): their scalars, passed by value to the kernels.
 // kSecondSlot: the rule keeps a second fp32 slot per weight (UpJob::v)
 // kClip: the rule takes a factor of gscale, and the decision to step at all, from a ClipState in device memory (k_update_pack_many's head)
+// kDecay: the rule decays the weights of the packed tensors (DecayMomentumRule / DecayAdamRule below)
 struct MomentumRule {   // acc = mu * acc + gscale * g; w -= lr * acc
     float lr, mu, gscale;
     static constexpr bool kSecondSlot = false;
     static constexpr bool kClip = false;
+    static constexpr bool kDecay = false;
 };
 struct AdamRule {       // TensorFlow 1.x ApplyAdam with alpha = lr_t * sqrt(1 - beta2^t) / (1 - beta1^t) from the host (elementwise.hip, adam_elem)
     float alpha, beta1, beta2, epsilon, gscale;
     static constexpr bool kSecondSlot = true;
     static constexpr bool kClip = false;
+    static constexpr bool kDecay = false;
 };
 // Global-norm gradient clipping (rsu.h rsu_grad_norm): the 32-byte state record, rsu.h's layout field by field. One thread of
 // k_grad_norm_final writes it; the clipping rules below read scale and flags from it, so the host never has to.
@@ -81,6 +84,24 @@ struct ClipMomentumRule : MomentumRule {
 struct ClipAdamRule : AdamRule {
     const ClipState* state;
     static constexpr bool kClip = true;
+};
+// Weight decay inside the update pass (rsu_optim.h rsu_update_table_run_decay / _adam_decay): the two rules with a decay step on every
+// element of a PACKED tensor (UpJob::kind != 0); plain ranges run the plain rule. mode (uniform; both forms are computed and one selected):
+//   EW_DECAY_DECOUPLED  w1 = w - (decay * w), then the rule on (w1, slots, g)
+//   EW_DECAY_L2         g1 = (gscale * g) + (decay * w), then the rule with g1 for gscale * g
+// each operation one float32 rounding (no contraction). state: nullptr, or the record of ew_grad_norm, read as a clipping rule reads it.
+constexpr int EW_DECAY_L2 = 0, EW_DECAY_DECOUPLED = 1;
+struct DecayMomentumRule : MomentumRule {
+    const ClipState* state;   // (first: the layout of the clipping rules, base + pointer, which the compiler keeps in registers)
+    float decay;
+    int mode;
+    static constexpr bool kDecay = true;
+};
+struct DecayAdamRule : AdamRule {
+    const ClipState* state;   // (first: the layout of the clipping rules, base + pointer, which the compiler keeps in registers)
+    float decay;
+    int mode;
+    static constexpr bool kDecay = true;
 };
 // floats of g per workgroup of the norm's pass 1: 256 lanes x 16 float4. The grid, cdiv(n / 4, EW_GN_EPB / 4) (at least 1), depends on
 // n alone -- not on the CU budget, the device or the autotuner -- so the order of every sum, and with it the bits of the norm, do too.
@@ -128,6 +149,8 @@ hipError_t ew_update_pack_many(const UpJob* jobs_dev, int njobs, int total_block
 hipError_t ew_update_pack_many_adam(const UpJob* jobs_dev, int njobs, int total_blocks, const AdamRule& h, hipStream_t st);
 hipError_t ew_update_pack_many_clip(const UpJob* jobs_dev, int njobs, int total_blocks, const ClipMomentumRule& h, hipStream_t st);
 hipError_t ew_update_pack_many_adam_clip(const UpJob* jobs_dev, int njobs, int total_blocks, const ClipAdamRule& h, hipStream_t st);
+hipError_t ew_update_pack_many_decay(const UpJob* jobs_dev, int njobs, int total_blocks, const DecayMomentumRule& h, hipStream_t st);
+hipError_t ew_update_pack_many_adam_decay(const UpJob* jobs_dev, int njobs, int total_blocks, const DecayAdamRule& h, hipStream_t st);
 hipError_t ew_extract_tiles(const float* imgs, float* tiles, int H, int S, int P, int stride, int pps, long t0, long ntiles, hipStream_t st);
 hipError_t ew_overlap_add(const float* prob, float* acc, float* hits, int nimg, int H, int P, int stride, int pps, long t0, long ntiles, hipStream_t st);
 hipError_t ew_overlap_finish(const float* acc, const float* hits, float* out, long n, hipStream_t st);

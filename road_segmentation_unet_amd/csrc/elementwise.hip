@@ -1418,9 +1418,34 @@ __device__ __forceinline__ void up_step1(const MomentumRule& h, float* w, float*
     *w -= h.lr * an;
 }
 __device__ __forceinline__ void up_step1(const AdamRule& h, float* w, float* a, float* v, const float* g) { adam_elem(*w, *a, *v, *g, h); }
+// a decaying rule on a float4 of a packed tensor: the decay step (elementwise.h, DecayMomentumRule), every operation rounded on its own,
+// then the base rule's own up_step -- decoupled: on the decayed weight; L2: on the gradient that already holds gscale and the decay
+// term, with 1 for gscale (1 * g1 is exact)
+template <typename Base, typename Rule>
+__device__ __forceinline__ void up_step_decay(const Rule& h, f32x4& w, f32x4& a, f32x4& v, f32x4 g) {
+#pragma clang fp contract(off)
+    // no branch on the mode: both forms are computed and one is selected per component, so the four blocks of a workgroup stay one
+    // straight run of arithmetic behind their loads, as in the plain pass (a branch here cost 7 % of the pass: profiles/r17/decay.txt)
+    const bool l2 = h.mode != EW_DECAY_DECOUPLED;
+    Base b = h;
+    b.gscale = l2 ? 1.f : h.gscale;
+    const f32x4 dw = h.decay * w, sg = h.gscale * g, g1 = sg + dw, w1 = w - dw;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        w[j] = l2 ? w[j] : w1[j];
+        g[j] = l2 ? g1[j] : g[j];
+    }
+    up_step(b, w, a, v, g);
+}
+__device__ __forceinline__ void up_step_packed(const DecayMomentumRule& h, f32x4& w, f32x4& a, f32x4& v, const f32x4 g) {
+    up_step_decay<MomentumRule>(h, w, a, v, g);
+}
+__device__ __forceinline__ void up_step_packed(const DecayAdamRule& h, f32x4& w, f32x4& a, f32x4& v, const f32x4 g) {
+    up_step_decay<AdamRule>(h, w, a, v, g);
+}
 }  // namespace
 // One workgroup of the packed-tensor path: block (tap, 32-row block rb, group cg of four 32-column blocks) of tensor J, whose gradient is
-// `g`. Rule: MomentumRule or AdamRule (the second slot J.v is read in the same batch as w, acc and g).
+// `g`. Rule: MomentumRule or AdamRule (the second slot J.v is read in the same batch as w, acc and g), or one of their decaying forms.
 template <typename Rule>
 __device__ __forceinline__ void update_pack_block(const UpJob& J, float (*tile)[32][33], int tap, int rb, int cg, const Rule& h, const float* g) {
     int seg = 0;
@@ -1450,7 +1475,8 @@ __device__ __forceinline__ void update_pack_block(const UpJob& J, float (*tile)[
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         if (idx[q] >= 0) {
-            up_step(h, wv[q], av[q], vv[q], gv[q]);
+            if constexpr (Rule::kDecay) up_step_packed(h, wv[q], av[q], vv[q], gv[q]);
+            else up_step(h, wv[q], av[q], vv[q], gv[q]);
             ((f32x4*)J.acc)[idx[q]] = av[q];
             if constexpr (Rule::kSecondSlot) ((f32x4*)J.v)[idx[q]] = vv[q];
             ((f32x4*)J.w)[idx[q]] = wv[q];
@@ -1490,7 +1516,13 @@ __device__ __forceinline__ void update_pack_block(const UpJob& J, float (*tile)[
 }
 template <typename Rule>
 __global__ void __launch_bounds__(256) k_update_pack_many(const UpJob* __restrict__ jobs, int njobs, Rule h) {
-    if constexpr (Rule::kClip) {
+    if constexpr (Rule::kDecay) {
+        // a decaying rule may come with the record of a clipping rule (below) or without one: the same two lines behind a uniform test
+        if (h.state) {
+            if (h.state->flags & EW_CLIP_NONFINITE) return;
+            h.gscale *= h.state->scale;
+        }
+    } else if constexpr (Rule::kClip) {
         // a clipping rule is resolved here, once per workgroup, from the record k_grad_norm_final left on this stream: a step whose
         // gradient is not finite is skipped before the first load (weights, slots and packed copies stay as they are, and consistent
         // with each other), any other step runs the arithmetic below unchanged with gscale * scale for gscale (one fp32 multiply)
@@ -1553,6 +1585,14 @@ hipError_t ew_update_pack_many_clip(const UpJob* jobs_dev, int njobs, int total_
 }
 hipError_t ew_update_pack_many_adam_clip(const UpJob* jobs_dev, int njobs, int total_blocks, const ClipAdamRule& h, hipStream_t st) {
     hipLaunchKernelGGL(k_update_pack_many<ClipAdamRule>, dim3(total_blocks), dim3(256), 0, st, jobs_dev, njobs, h);
+    return hipGetLastError();
+}
+hipError_t ew_update_pack_many_decay(const UpJob* jobs_dev, int njobs, int total_blocks, const DecayMomentumRule& h, hipStream_t st) {
+    hipLaunchKernelGGL(k_update_pack_many<DecayMomentumRule>, dim3(total_blocks), dim3(256), 0, st, jobs_dev, njobs, h);
+    return hipGetLastError();
+}
+hipError_t ew_update_pack_many_adam_decay(const UpJob* jobs_dev, int njobs, int total_blocks, const DecayAdamRule& h, hipStream_t st) {
+    hipLaunchKernelGGL(k_update_pack_many<DecayAdamRule>, dim3(total_blocks), dim3(256), 0, st, jobs_dev, njobs, h);
     return hipGetLastError();
 }
 // ---------------------------------------------------------------------------------------------

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/rsu.h"
+#include "../../include/rsu_optim.h"
 #include "affine_patches.h"
 #include "color_jitter.h"
 #include "border_map.h"
@@ -442,6 +443,28 @@ extern "C" int rsu_update_table_run_adam_clip(const void* dev_table, int nentrie
     if (!dev_table || nentries < 1 || total_blocks < 1 || !state || ((uintptr_t)state & 3)) return RSU_EINVAL;
     ClipAdamRule h{{alpha, beta1, beta2, epsilon, gscale}, (const ClipState*)state};
     HIP_CHECK_RET(ew_update_pack_many_adam_clip((const UpJob*)dev_table, nentries, total_blocks, h, (hipStream_t)stream));
+    return RSU_OK;
+}
+// ---- weight decay inside the update pass (rsu_optim.h): the two rules with a decay step on the packed tensors; clip_state may be NULL
+static_assert(RSU_DECAY_L2 == EW_DECAY_L2 && RSU_DECAY_DECOUPLED == EW_DECAY_DECOUPLED, "rsu_optim.h and elementwise.h must agree on the modes");
+static bool decay_args_ok(const void* dev_table, int nentries, int total_blocks, float decay, int mode, const void* clip_state) {
+    if (!dev_table || nentries < 1 || total_blocks < 1 || ((uintptr_t)clip_state & 3)) return false;
+    if (!(std::isfinite(decay) && decay > 0.f)) return false;
+    return mode == RSU_DECAY_L2 || mode == RSU_DECAY_DECOUPLED;
+}
+extern "C" int rsu_update_table_run_decay(const void* dev_table, int nentries, int total_blocks, float lr, float mu, float gscale, float decay,
+                                          int mode, const void* clip_state, rsu_stream_t stream) {
+    if (!decay_args_ok(dev_table, nentries, total_blocks, decay, mode, clip_state)) return RSU_EINVAL;
+    DecayMomentumRule h{{lr, mu, gscale}, (const ClipState*)clip_state, decay, mode};
+    HIP_CHECK_RET(ew_update_pack_many_decay((const UpJob*)dev_table, nentries, total_blocks, h, (hipStream_t)stream));
+    return RSU_OK;
+}
+extern "C" int rsu_update_table_run_adam_decay(const void* dev_table, int nentries, int total_blocks, float alpha, float beta1, float beta2,
+                                               float epsilon, float gscale, float decay, int mode, const void* clip_state,
+                                               rsu_stream_t stream) {
+    if (!decay_args_ok(dev_table, nentries, total_blocks, decay, mode, clip_state)) return RSU_EINVAL;
+    DecayAdamRule h{{alpha, beta1, beta2, epsilon, gscale}, (const ClipState*)clip_state, decay, mode};
+    HIP_CHECK_RET(ew_update_pack_many_adam_decay((const UpJob*)dev_table, nentries, total_blocks, h, (hipStream_t)stream));
     return RSU_OK;
 }
 // ---- moving average of the weights: one pass of its own behind the update pass (ema and w must not overlap: w is read through a

@@ -21,7 +21,7 @@ from ._lib import call
 from .dist import GradBucketer, micro_indices, shard_indices, tune_overlap  # noqa: F401  (shard_indices: importable from here as before)
 from .pool import BatchUploader, DevicePatchPool, PatchPool
 from .summary import Summary
-from .unet import EMA_SUFFIX, UNet, input_size_needed
+from .unet import DECAY_MODES, EMA_SUFFIX, LR_SCHEDULES, UNet, input_size_needed
 
 # (name, type, default, help) -- tf_aerial_images.py:15-46, same order
 FLAG_DEFS = [
@@ -117,6 +117,20 @@ EXTRA_FLAG_DEFS = [
                                  "each GPU runs K passes over batch_size / (GPUs x K) patches, so the 2-GiB limit on a batch applies to "
                                  "the micro-batch. Steps, --eval_every and the learning-rate decay count optimizer steps. The Dice term "
                                  "(--dice_weight) is taken per micro-batch, as it is per GPU, and dropout draws new masks per micro-batch"),
+    ("weight_decay", float, 0.0, "lambda >= 0 (finite) of a weight decay applied inside the optimizer's update launch, at no extra pass over "
+                                 "the weights; 0 = off. The 3x3, first and transposed conv kernels decay; biases, the colour-adjust matrix "
+                                 "and the 1x1 head do not. The reported loss never includes the L2 penalty"),
+    ("weight_decay_mode", str, "decoupled", "decoupled|l2: decoupled (AdamW; the same step in front of the Momentum rule) takes lr * lambda * w "
+                                            "off every decaying weight at the scheduled rate; l2 adds lambda * w to its gradient, behind "
+                                            "--clip_grad_norm's factor (the penalty lambda / 2 |w|^2)"),
+    ("lr_schedule", str, "staircase", "staircase|constant|cosine|linear: the learning-rate curve over optimizer steps. staircase is the "
+                                      "reference's lr * 0.95 ^ (step // 1000); cosine and linear fall from --lr to --lr_final * lr over "
+                                      "--lr_total_steps steps and stay there"),
+    ("lr_warmup_steps", int, 0, "W >= 0: scale the rate of step t by min(1, (t + 1) / W), a linear ramp over the first W optimizer steps, on "
+                                "top of any --lr_schedule; 0 = off"),
+    ("lr_total_steps", int, 0, "T >= 0: the horizon of --lr_schedule=cosine|linear in optimizer steps; 0 = this run's own length, --num_epoch "
+                               "times the optimizer steps of an epoch (printed once the patches are known)"),
+    ("lr_final", float, 0.0, "F in [0, 1]: the fraction of --lr at which --lr_schedule=cosine|linear end"),
 ]
 
 
@@ -207,6 +221,56 @@ def parse_ema_decay(value):
     if isinstance(value, bool) or not (0.0 <= v and np.float32(v) < np.float32(1.0)):
         raise ValueError("--ema_decay must be 0 (off) or a float in (0, 1), not %r" % (value,))
     return v
+
+
+def parse_weight_decay(value):
+    """The --weight_decay value as a float: 0 (off) or finite and > 0. Anything else raises ValueError."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if isinstance(value, bool) or not (math.isfinite(v) and v >= 0.0):
+        raise ValueError("--weight_decay must be 0 (off) or a finite float > 0, not %r" % (value,))
+    return v
+
+
+def parse_weight_decay_mode(value):
+    """The --weight_decay_mode value: "decoupled" or "l2". Anything else raises ValueError."""
+    if value not in DECAY_MODES:
+        raise ValueError("--weight_decay_mode must be one of %s, not %r" % ("|".join(DECAY_MODES), value))
+    return value
+
+
+def parse_lr_schedule(value):
+    """The --lr_schedule value: one of unet.LR_SCHEDULES. Anything else raises ValueError."""
+    if value not in LR_SCHEDULES:
+        raise ValueError("--lr_schedule must be one of %s, not %r" % ("|".join(LR_SCHEDULES), value))
+    return value
+
+
+def parse_lr_steps(value, flag):
+    """The --lr_warmup_steps / --lr_total_steps value as an int >= 0. Anything else raises ValueError."""
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < 0:
+        raise ValueError("--%s must be an integer >= 0, not %r" % (flag, value))
+    return int(value)
+
+
+def parse_lr_final(value):
+    """The --lr_final value as a float in [0, 1]. Anything else raises ValueError."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if isinstance(value, bool) or not (0.0 <= v <= 1.0):
+        raise ValueError("--lr_final must be a float in [0, 1], not %r" % (value,))
+    return v
+
+
+def steps_per_epoch(num_patches, batch_size):
+    """Optimizer steps of one train() call over num_patches patches: the length of the reference's `range(0, N - batch_size, batch_size)`
+    (the final batch is dropped even when full). batch_size is the effective global batch of one step, so neither the number of GPUs
+    nor --accumulate_steps changes the count."""
+    return len(range(0, int(num_patches) - int(batch_size), int(batch_size)))
 
 
 def parse_random_rotation(value):
@@ -412,6 +476,10 @@ class Options(object):
         self.accumulate_steps = parse_accumulate_steps(self.accumulate_steps)
         if self.accumulate_steps > 1:   # (the number of GPUs is known where the model is built: it checks again with it)
             micro_batch_size(self.batch_size, 1, self.accumulate_steps)
+        self.weight_decay, self.weight_decay_mode = parse_weight_decay(self.weight_decay), parse_weight_decay_mode(self.weight_decay_mode)
+        self.lr_schedule, self.lr_final = parse_lr_schedule(self.lr_schedule), parse_lr_final(self.lr_final)
+        self.lr_warmup_steps = parse_lr_steps(self.lr_warmup_steps, "lr_warmup_steps")
+        self.lr_total_steps = parse_lr_steps(self.lr_total_steps, "lr_total_steps")   # (0 with cosine | linear: resolved by cli.main)
         loader_flags = [name for name, on in (("--random_rotation", self.random_rotation > 0.0), ("--random_scale", self.random_scale != (1.0, 1.0)),
                                               ("--one_launch_loader", self.one_launch_loader),
                                               ("--color_jitter", any(v > 0.0 for v in self.color_jitter)),
@@ -462,8 +530,14 @@ class ConvolutionalModel:
                         dice_weight=opts.dice_weight, dice_smooth=opts.dice_smooth, border_weight=opts.border_weight,
                         border_sigma=opts.border_sigma, clip_grad_norm=opts.clip_grad_norm if opts.clip_grad_norm > 0.0 else None,
                         ema_decay=opts.ema_decay if opts.ema_decay > 0.0 else None, ema_warmup=opts.ema_warmup,
-                        accumulate_steps=K if K > 1 else None)
+                        accumulate_steps=K if K > 1 else None,
+                        weight_decay=opts.weight_decay if getattr(opts, "weight_decay", 0.0) > 0.0 else None,
+                        weight_decay_mode=getattr(opts, "weight_decay_mode", "decoupled"))
         self.net.dropout_seed = int(opts.seed) + 7919 * self.rank  # independent masks on every rank's shard
+        # --lr_schedule: cosine | linear with --lr_total_steps=0 wait for resolve_lr_total_steps() (the patches are not known yet)
+        self._lr_unresolved = getattr(opts, "lr_schedule", "staircase") in ("cosine", "linear") and getattr(opts, "lr_total_steps", 0) < 1
+        if not self._lr_unresolved:
+            self._set_lr_schedule()
         self._bucketer = None
         self._exchange_tuned = False
         self.exchange_schedule = None
@@ -489,6 +563,27 @@ class ConvolutionalModel:
             self.net.repack()
 
     # ------------------------------------------------------------------ training
+    def _set_lr_schedule(self):
+        opts = self._options
+        self.net.set_lr_schedule(getattr(opts, "lr_schedule", "staircase"), getattr(opts, "lr_warmup_steps", 0), getattr(opts, "lr_total_steps", 0),
+                                 getattr(opts, "lr_final", 0.0))
+
+    def resolve_lr_total_steps(self, num_patches):
+        """--lr_schedule=cosine|linear with --lr_total_steps=0: the horizon becomes this run's own length, --num_epoch times
+        steps_per_epoch(num_patches, --batch_size), written back into the options and handed to the net; returns it. With any other
+        combination of the two flags: nothing, returns --lr_total_steps as given. ValueError for a run that takes no step."""
+        opts = self._options
+        if not self._lr_unresolved:
+            return opts.lr_total_steps
+        total = int(opts.num_epoch) * steps_per_epoch(num_patches, opts.batch_size)
+        if total < 1:
+            raise ValueError("--lr_schedule=%s with --lr_total_steps=0 needs a run of at least one optimizer step: --num_epoch=%d over %d "
+                             "patches at --batch_size=%d takes none" % (opts.lr_schedule, opts.num_epoch, num_patches, opts.batch_size))
+        opts.lr_total_steps = total
+        self._lr_unresolved = False
+        self._set_lr_schedule()
+        return total
+
     def train_step(self, patches, labels, weights=None):
         """One session.run([train, loss, predictions]) (tf_aerial_images.py:241-244) on this rank's shard.
         patches [b,S,S,3] float, labels [b,P,P] in {0,1}; returns (global mean loss tensor, predictions [b,P,P] device tensor).
@@ -700,6 +795,9 @@ class ConvolutionalModel:
         epoch with --validate_every=0; rank 0 prints one line and logs val_loss, val_objective, val_dice, val_f1, val_iou and
         val_best_threshold; last_epoch_stats gains "validation" (the last pass's metrics); --save_best keeps the best model by val_f1."""
         opts, net = self._options, self.net
+        if self._lr_unresolved:
+            raise ValueError("--lr_schedule=%s with --lr_total_steps=0: call resolve_lr_total_steps(number of patches) before train() "
+                             "(cli.main does)" % opts.lr_schedule)
         val_stats = None
         self._ensure_summary()
         pool = patches if isinstance(patches, PatchPool) else None

@@ -145,6 +145,70 @@ def ema_decay_at(decay, t, warmup=True):
     return f(d)
 
 
+LR_SCHEDULES = ("staircase", "constant", "cosine", "linear")
+DECAY_MODES = ("decoupled", "l2")
+DEFAULT_LR_SCHEDULE = ("staircase", 0, 0, 0.0)   # lr_at's defaults: the reference's curve
+
+
+def _int_arg(value, what, lowest=0):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < lowest:
+        raise ValueError("%s must be an integer >= %d, not %r" % (what, lowest, value))
+    return int(value)
+
+
+def lr_at(step, lr0, schedule="staircase", warmup_steps=0, total_steps=0, final=0.0):
+    """The learning rate of the optimizer step taken after `step` steps (t = step, the global_step in front of the step), as the
+    float the update pass receives: float(np.float32(base * warm)), base and warm in float64, rounded once.
+    base, by schedule:
+      staircase  the reference's tf.train.exponential_decay(lr0, t, 1000, 0.95, staircase=True) (tf_aerial_images.py:116-117), the
+                 float32 expression f32(lr0) * f32(0.95) ** f32(t // 1000)
+      constant   lr0
+      cosine     lr0 * (F + (1 - F) * 0.5 * (1 + cos(pi * min(t, T) / T)))
+      linear     lr0 * (F + (1 - F) * (1 - min(t, T) / T))
+    with T = total_steps >= 1 (cosine and linear; the other two ignore it) and F = final in [0, 1], the fraction of lr0 the two end at.
+    warm = min(1, (t + 1) / W) for W = warmup_steps > 0, else 1: a linear ramp over the first W steps, on top of any schedule.
+    The defaults (staircase, no warm-up) return the bits the reference's expression has. Bad arguments raise ValueError."""
+    t = _int_arg(step, "step")
+    W, T = _int_arg(warmup_steps, "warmup_steps"), _int_arg(total_steps, "total_steps")
+    try:
+        lr0f, F = float(lr0), float(final)
+    except (TypeError, ValueError):
+        lr0f = F = float("nan")
+    if isinstance(lr0, bool) or isinstance(final, bool) or not (math.isfinite(lr0f) and lr0f >= 0.0):
+        raise ValueError("lr0 must be a finite float >= 0, not %r" % (lr0,))
+    if not (0.0 <= F <= 1.0):
+        raise ValueError("final must be a float in [0, 1], not %r" % (final,))
+    if schedule not in LR_SCHEDULES:
+        raise ValueError("schedule must be one of %s, not %r" % ("|".join(LR_SCHEDULES), schedule))
+    if schedule in ("cosine", "linear") and T < 1:
+        raise ValueError("the %s schedule needs total_steps >= 1, not %r" % (schedule, total_steps))
+    if schedule == "staircase":
+        base = float(np.float32(lr0f) * np.float32(0.95) ** np.float32(t // 1000))
+    elif schedule == "constant":
+        base = lr0f
+    elif schedule == "cosine":
+        base = lr0f * (F + (1.0 - F) * 0.5 * (1.0 + math.cos(math.pi * min(t, T) / T)))
+    else:
+        base = lr0f * (F + (1.0 - F) * (1.0 - min(t, T) / T))
+    warm = min(1.0, (t + 1) / W) if W > 0 else 1.0
+    return float(np.float32(base * warm))
+
+
+def _decay_args(value, mode):
+    """UNet's weight_decay and weight_decay_mode: (None or a finite lambda > 0, "decoupled" or "l2")"""
+    if mode not in DECAY_MODES:
+        raise ValueError("weight_decay_mode must be one of %s, not %r" % ("|".join(DECAY_MODES), mode))
+    if value is None:
+        return None, mode
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if isinstance(value, bool) or not (math.isfinite(v) and v > 0.0):
+        raise ValueError("weight_decay must be None or a finite float > 0, not %r" % (value,))
+    return v, mode
+
+
 def _accumulate_arg(value):
     """UNet's accumulate_steps: None or 1 (one backward pass per optimizer step), or an int K > 1"""
     if value is None:
@@ -176,7 +240,7 @@ class UNet:
 
     def __init__(self, num_layers, root_size, dilated_layers, batch_size, patch_size, device="cuda:0", params=None, seed=2017,
                  training=True, optimizer="momentum", class_weights=None, dice_weight=0.0, dice_smooth=1.0, border_weight=0.0, border_sigma=5.0,
-                 clip_grad_norm=None, ema_decay=None, ema_warmup=True, accumulate_steps=None):
+                 clip_grad_norm=None, ema_decay=None, ema_warmup=True, accumulate_steps=None, weight_decay=None, weight_decay_mode="decoupled"):
         """optimizer: "momentum" (the reference's MomentumOptimizer: apply_momentum) or "adam" (tf.train.AdamOptimizer: apply_adam; a
         second fp32 slot per variable, flat_v).
         class_weights: None or a pair (w0, w1) of finite floats >= 0, not both 0: the weighted cross-entropy of rsu.h
@@ -201,13 +265,27 @@ class UNet:
         gradients, ((g_0 + g_1) + ...) + g_{K-1}, in flat_g, where the exchange, the norm and the update pass read it, and
         apply_momentum / apply_adam refuse to step before it. backward_device's inv_count stays 1 / (pixel count of the WHOLE effective
         batch). One more float32 buffer, flat_gsum (4 B per weight), and one rsu_grad_accumulate launch per micro-batch (rsu.h).
-        micro_step (0..K-1) enters the dropout keys. Training nets only. None: no buffer, no launch, the step is what it always was."""
+        micro_step (0..K-1) enters the dropout keys. Training nets only. None: no buffer, no launch, the step is what it always was.
+        weight_decay: None, or lambda > 0 (finite): apply_momentum / apply_adam run the decaying update pass (rsu_optim.h
+        rsu_update_table_run_decay / rsu_update_table_run_adam_decay) in place of the plain or clipping one -- one launch, the same grid,
+        the same bytes. The packed kernels decay (3x3 convs, the first conv, transposed convs: decaying_parameters() of them); biases, the
+        colour-adjust matrix and the 1x1 head do not. weight_decay_mode: "decoupled" (AdamW; under Momentum the same step in front of
+        the rule): w -= f32(lr_t) * f32(lambda) * w at the scheduled rate lr_t = learning_rate(lr0), then the rule; or "l2": lambda * w
+        joins the gradient behind gscale and the clipping factor (the penalty lambda / 2 |w|^2; loss_sum never includes it). No buffer,
+        nothing in state_dict(). The moving average, gradient accumulation and the data-parallel exchange sit in front of or behind
+        the update pass and are what they were. Training nets only (ValueError otherwise; bad values raise ValueError too). None: the
+        step is what it always was.
+        The learning-rate curve is set_lr_schedule()'s; the default is the reference's staircase."""
         if optimizer not in OPTIMIZERS:
             raise _lib.RsuError("optimizer must be one of %s, not %r" % ("|".join(OPTIMIZERS), optimizer))
         self.optimizer = optimizer
         self.accumulate_steps = _accumulate_arg(accumulate_steps)
         if self.accumulate_steps > 1 and not training:
             raise _lib.RsuError("a forward-only net takes no optimizer step: it has no gradients to accumulate")
+        self.weight_decay, self.weight_decay_mode = _decay_args(weight_decay, weight_decay_mode)
+        if self.weight_decay is not None and not training:
+            raise ValueError("a forward-only net takes no optimizer step: it has no weights to decay")
+        self.lr_schedule = DEFAULT_LR_SCHEDULE   # (schedule, warmup_steps, total_steps, final) of lr_at (set_lr_schedule)
         self.flat_gsum, self._accum_calls = None, 0   # the running sum of the micro-batch gradients; accumulate_gradients() calls since the last step
         self.clip_grad_norm = _clip_arg(clip_grad_norm)
         self.ema_decay, self.ema_warmup = _ema_arg(ema_decay), bool(ema_warmup)
@@ -1013,9 +1091,39 @@ class UNet:
             self.tune(training, keep=keep)
 
     # ------------------------------------------------------------------ optimizer
+    def set_lr_schedule(self, schedule="staircase", warmup_steps=0, total_steps=0, final=0.0):
+        """the learning-rate curve of learning_rate(): the arguments of lr_at (validated here, ValueError). The default is the
+        reference's tf.train.exponential_decay staircase. Not part of state_dict(): the curve is a function of global_step, which is."""
+        lr_at(0, 0.0, schedule, warmup_steps, total_steps, final)
+        self.lr_schedule = (schedule, int(warmup_steps), int(total_steps), float(final))
+
     def learning_rate(self, lr0):
-        """tf.train.exponential_decay(lr, global_step, 1000, 0.95, staircase=True) (tf_aerial_images.py:116-117), float32"""
-        return float(np.float32(lr0) * np.float32(0.95) ** np.float32(self.global_step // 1000))
+        """the rate of the next optimizer step, lr_at(global_step, lr0, *lr_schedule) -- by default tf.train.exponential_decay(lr,
+        global_step, 1000, 0.95, staircase=True) (tf_aerial_images.py:116-117), float32. apply_momentum / apply_adam and the logged
+        `learning_rate` scalar both read it here."""
+        return lr_at(self.global_step, lr0, *getattr(self, "lr_schedule", DEFAULT_LR_SCHEDULE))
+
+    def decaying_parameters(self):
+        """(parameters that weight decay touches, live parameters): the packed kernels of the update table against everything stepped"""
+        decays = sum(self._slices[n][1] for _kind, n, _sh, _segs in self._packed_kernels())
+        return decays, sum(self._slices[n][1] for n in self.names if self._slices[n][0] < self.n_live)
+
+    def _decay_call(self, lr_t):
+        """the (decay, mode) arguments of the decaying update pass at the scheduled rate lr_t (rsu_optim.h): decoupled: f32(lr_t) *
+        f32(lambda), one float32 product; l2: lambda. None where the decoupled product is zero -- a schedule that has reached a rate of 0
+        -- and the step is the plain one (the entry takes no decay of 0). Raises where there is no such pass (RSU_FUSED_UPDATE=0)."""
+        if os.environ.get("RSU_FUSED_UPDATE", "1") == "0":
+            raise _lib.RsuError("weight_decay needs the fused update pass: RSU_FUSED_UPDATE=0 (rsu_momentum_step / rsu_adam_step) has no "
+                                "decaying variant")
+        if self.weight_decay_mode == "l2":
+            return float(np.float32(self.weight_decay)), _lib.DECAY_L2
+        d = float(np.float32(lr_t) * np.float32(self.weight_decay))
+        if d == 0.0:
+            return None
+        if not (math.isfinite(d) and d > 0.0):
+            raise _lib.RsuError("weight_decay: f32(lr) * f32(lambda) = %r at step %d is not a finite float32 (lr %r, lambda %r)"
+                                % (d, self.global_step, lr_t, self.weight_decay))
+        return d, _lib.DECAY_DECOUPLED
 
     def _build_update_table(self):
         """the job table of rsu_update_table_run: one entry per conv / transposed-conv kernel (with its packed copies), the variables between
@@ -1169,12 +1277,22 @@ class UNet:
         A net built with clip_grad_norm: rsu_grad_norm, then rsu_update_table_run_clip, whose gscale is this gscale times the factor on
         the device. A step whose gradient is not finite leaves weights, slots and packed copies as they are but STILL COUNTS as a step:
         the host does not know (that is the point), so global_step and the decay staircase advance -- and under Adam the beta powers,
-        while m and v stay untouched; clip_stats() tells how often it happened."""
+        while m and v stay untouched; clip_stats() tells how often it happened.
+        A net built with weight_decay: rsu_update_table_run_decay in place of either pass (behind rsu_grad_norm on a clipping net, whose
+        record it reads: a skipped step decays nothing)."""
         if self.optimizer != "momentum":
             raise _lib.RsuError("apply_momentum on a net built with optimizer=%r" % self.optimizer)
         self._not_averaged("apply_momentum")
         self._accumulated("apply_momentum")
-        if self.clip_grad_norm is not None:
+        lr_t = self.learning_rate(lr0)
+        decay = self._decay_call(lr_t) if self.weight_decay is not None else None
+        if decay is not None:
+            if self.clip_grad_norm is not None:
+                self._grad_norm()
+            tab = self._update_table or self._build_update_table()
+            call("rsu_update_table_run_decay", _ptr(tab[0]), tab[1], tab[2], lr_t, momentum, gscale, decay[0], decay[1], _ptr(self.clip_state),
+                 self._stream())
+        elif self.clip_grad_norm is not None:
             self._grad_norm()
             tab = self._update_table or self._build_update_table()
             call("rsu_update_table_run_clip", _ptr(tab[0]), tab[1], tab[2], self.learning_rate(lr0), momentum, gscale, _ptr(self.clip_state),
@@ -1196,18 +1314,25 @@ class UNet:
         then the batched re-pack -- same bits). alpha and the beta powers are float32 host arithmetic (adam_scalars); global_step and
         the powers advance after the launch. The dead level-(L-1) dilated pair is never stepped.
         A net built with clip_grad_norm: rsu_grad_norm, then rsu_update_table_run_adam_clip; a skipped step still advances global_step
-        and the beta powers (see apply_momentum)."""
+        and the beta powers (see apply_momentum).
+        A net built with weight_decay: rsu_update_table_run_adam_decay in place of either pass; the decoupled decay is taken at the
+        scheduled rate learning_rate(lr0), not at the bias-corrected alpha."""
         if self.optimizer != "adam":
             raise _lib.RsuError("apply_adam on a net built with optimizer=%r" % self.optimizer)
         self._not_averaged("apply_adam")
         self._accumulated("apply_adam")
+        lr_t = self.learning_rate(lr0)
+        decay = self._decay_call(lr_t) if self.weight_decay is not None else None   # (raises under RSU_FUSED_UPDATE=0, before the powers are touched)
         if self.clip_grad_norm is not None:
             self._grad_norm()   # (raises under RSU_FUSED_UPDATE=0, before the powers are touched)
         if self.beta1_power is None:
             self.beta1_power, self.beta2_power = np.float32(beta1), np.float32(beta2)
-        alpha, b1p, b2p = adam_scalars(self.learning_rate(lr0), self.beta1_power, self.beta2_power, beta1, beta2)
+        alpha, b1p, b2p = adam_scalars(lr_t, self.beta1_power, self.beta2_power, beta1, beta2)
         args = (float(alpha), float(np.float32(beta1)), float(np.float32(beta2)), float(np.float32(epsilon)), gscale)
-        if self.clip_grad_norm is not None:
+        if decay is not None:
+            tab = self._update_table or self._build_update_table()
+            call("rsu_update_table_run_adam_decay", _ptr(tab[0]), tab[1], tab[2], *args, decay[0], decay[1], _ptr(self.clip_state), self._stream())
+        elif self.clip_grad_norm is not None:
             tab = self._update_table or self._build_update_table()
             call("rsu_update_table_run_adam_clip", _ptr(tab[0]), tab[1], tab[2], *args, _ptr(self.clip_state), self._stream())
         elif os.environ.get("RSU_FUSED_UPDATE", "1") == "0":
