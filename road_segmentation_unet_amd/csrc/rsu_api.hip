@@ -18,6 +18,7 @@
 #include "color_jitter.h"
 #include "border_map.h"
 #include "elementwise.h"
+#include "optim.h"
 #include "igemm.h"
 
 static std::atomic<int> g_last_hip_error{0};
@@ -398,10 +399,15 @@ extern "C" int rsu_update_table_finish(void* host_table, int nentries, int* tota
     *total_blocks = b;
     return RSU_OK;
 }
-extern "C" int rsu_update_table_run(const void* dev_table, int nentries, int total_blocks, float lr, float mu, float gscale, rsu_stream_t stream) {
+// the six rsu_update_table_run* entries: each checks what its rule adds and launches the pass with that rule through update_table_run
+template <typename Rule>
+static int update_table_run(const void* dev_table, int nentries, int total_blocks, const Rule& h, rsu_stream_t stream) {
     if (!dev_table || nentries < 1 || total_blocks < 1) return RSU_EINVAL;
-    HIP_CHECK_RET(ew_update_pack_many((const UpJob*)dev_table, nentries, total_blocks, lr, mu, gscale, (hipStream_t)stream));
+    HIP_CHECK_RET(ew_update_pack_many((const UpJob*)dev_table, nentries, total_blocks, h, (hipStream_t)stream));
     return RSU_OK;
+}
+extern "C" int rsu_update_table_run(const void* dev_table, int nentries, int total_blocks, float lr, float mu, float gscale, rsu_stream_t stream) {
+    return update_table_run(dev_table, nentries, total_blocks, MomentumRule{lr, mu, gscale}, stream);
 }
 // ---- the same pass under tf.train.AdamOptimizer: `acc` of an entry is m, v comes from rsu_update_table_set_second_slot
 extern "C" int rsu_update_table_set_second_slot(void* host_table, int index, float* v) {
@@ -413,15 +419,12 @@ extern "C" int rsu_update_table_set_second_slot(void* host_table, int index, flo
 }
 extern "C" int rsu_update_table_run_adam(const void* dev_table, int nentries, int total_blocks, float alpha, float beta1, float beta2, float epsilon,
                                          float gscale, rsu_stream_t stream) {
-    if (!dev_table || nentries < 1 || total_blocks < 1) return RSU_EINVAL;
-    HIP_CHECK_RET(ew_update_pack_many_adam((const UpJob*)dev_table, nentries, total_blocks, AdamRule{alpha, beta1, beta2, epsilon, gscale},
-                                           (hipStream_t)stream));
-    return RSU_OK;
+    return update_table_run(dev_table, nentries, total_blocks, AdamRule{alpha, beta1, beta2, epsilon, gscale}, stream);
 }
 // ---- global-norm gradient clipping: the norm into a device-resident state record, and the two update passes that take their scale from it
 static_assert(sizeof(ClipState) == RSU_CLIP_STATE_BYTES, "rsu.h documents the state record as 32 bytes");
-static_assert(RSU_CLIP_CLIPPED == EW_CLIP_CLIPPED && RSU_CLIP_NONFINITE == EW_CLIP_NONFINITE, "rsu.h and elementwise.h must agree on the flag bits");
-static_assert(RSU_GRAD_NORM_BLOCK_FLOATS == EW_GN_EPB, "rsu.h and elementwise.h must agree on a workgroup's share");
+static_assert(RSU_CLIP_CLIPPED == EW_CLIP_CLIPPED && RSU_CLIP_NONFINITE == EW_CLIP_NONFINITE, "rsu.h and optim.h must agree on the flag bits");
+static_assert(RSU_GRAD_NORM_BLOCK_FLOATS == EW_GN_EPB, "rsu.h and optim.h must agree on a workgroup's share");
 extern "C" size_t rsu_clip_state_bytes(void) { return sizeof(ClipState); }
 extern "C" size_t rsu_grad_norm_ws_floats(long n) { return n >= 1 ? 2 * (size_t)ew_grad_norm_blocks(n) : 0; }
 extern "C" int rsu_grad_norm(const float* g, long n, float max_norm, float* ws, void* state, rsu_stream_t stream) {
@@ -431,41 +434,34 @@ extern "C" int rsu_grad_norm(const float* g, long n, float max_norm, float* ws, 
     HIP_CHECK_RET(ew_grad_norm(g, n, max_norm, ws, (ClipState*)state, (hipStream_t)stream));
     return RSU_OK;
 }
+static bool clip_state_ok(const void* state) { return state && !((uintptr_t)state & 3); }
 extern "C" int rsu_update_table_run_clip(const void* dev_table, int nentries, int total_blocks, float lr, float mu, float gscale,
                                          const void* state, rsu_stream_t stream) {
-    if (!dev_table || nentries < 1 || total_blocks < 1 || !state || ((uintptr_t)state & 3)) return RSU_EINVAL;
-    ClipMomentumRule h{{lr, mu, gscale}, (const ClipState*)state};
-    HIP_CHECK_RET(ew_update_pack_many_clip((const UpJob*)dev_table, nentries, total_blocks, h, (hipStream_t)stream));
-    return RSU_OK;
+    if (!clip_state_ok(state)) return RSU_EINVAL;
+    return update_table_run(dev_table, nentries, total_blocks, ClipMomentumRule{{lr, mu, gscale}, (const ClipState*)state}, stream);
 }
 extern "C" int rsu_update_table_run_adam_clip(const void* dev_table, int nentries, int total_blocks, float alpha, float beta1, float beta2,
                                               float epsilon, float gscale, const void* state, rsu_stream_t stream) {
-    if (!dev_table || nentries < 1 || total_blocks < 1 || !state || ((uintptr_t)state & 3)) return RSU_EINVAL;
-    ClipAdamRule h{{alpha, beta1, beta2, epsilon, gscale}, (const ClipState*)state};
-    HIP_CHECK_RET(ew_update_pack_many_adam_clip((const UpJob*)dev_table, nentries, total_blocks, h, (hipStream_t)stream));
-    return RSU_OK;
+    if (!clip_state_ok(state)) return RSU_EINVAL;
+    return update_table_run(dev_table, nentries, total_blocks, ClipAdamRule{{alpha, beta1, beta2, epsilon, gscale}, (const ClipState*)state}, stream);
 }
 // ---- weight decay inside the update pass (rsu_optim.h): the two rules with a decay step on the packed tensors; clip_state may be NULL
-static_assert(RSU_DECAY_L2 == EW_DECAY_L2 && RSU_DECAY_DECOUPLED == EW_DECAY_DECOUPLED, "rsu_optim.h and elementwise.h must agree on the modes");
-static bool decay_args_ok(const void* dev_table, int nentries, int total_blocks, float decay, int mode, const void* clip_state) {
-    if (!dev_table || nentries < 1 || total_blocks < 1 || ((uintptr_t)clip_state & 3)) return false;
-    if (!(std::isfinite(decay) && decay > 0.f)) return false;
+static_assert(RSU_DECAY_L2 == EW_DECAY_L2 && RSU_DECAY_DECOUPLED == EW_DECAY_DECOUPLED, "rsu_optim.h and optim.h must agree on the modes");
+static bool decay_args_ok(float decay, int mode, const void* clip_state) {
+    if (((uintptr_t)clip_state & 3) || !(std::isfinite(decay) && decay > 0.f)) return false;
     return mode == RSU_DECAY_L2 || mode == RSU_DECAY_DECOUPLED;
 }
 extern "C" int rsu_update_table_run_decay(const void* dev_table, int nentries, int total_blocks, float lr, float mu, float gscale, float decay,
                                           int mode, const void* clip_state, rsu_stream_t stream) {
-    if (!decay_args_ok(dev_table, nentries, total_blocks, decay, mode, clip_state)) return RSU_EINVAL;
-    DecayMomentumRule h{{lr, mu, gscale}, (const ClipState*)clip_state, decay, mode};
-    HIP_CHECK_RET(ew_update_pack_many_decay((const UpJob*)dev_table, nentries, total_blocks, h, (hipStream_t)stream));
-    return RSU_OK;
+    if (!decay_args_ok(decay, mode, clip_state)) return RSU_EINVAL;
+    return update_table_run(dev_table, nentries, total_blocks, DecayMomentumRule{{lr, mu, gscale}, (const ClipState*)clip_state, decay, mode}, stream);
 }
 extern "C" int rsu_update_table_run_adam_decay(const void* dev_table, int nentries, int total_blocks, float alpha, float beta1, float beta2,
                                                float epsilon, float gscale, float decay, int mode, const void* clip_state,
                                                rsu_stream_t stream) {
-    if (!decay_args_ok(dev_table, nentries, total_blocks, decay, mode, clip_state)) return RSU_EINVAL;
-    DecayAdamRule h{{alpha, beta1, beta2, epsilon, gscale}, (const ClipState*)clip_state, decay, mode};
-    HIP_CHECK_RET(ew_update_pack_many_adam_decay((const UpJob*)dev_table, nentries, total_blocks, h, (hipStream_t)stream));
-    return RSU_OK;
+    if (!decay_args_ok(decay, mode, clip_state)) return RSU_EINVAL;
+    return update_table_run(dev_table, nentries, total_blocks,
+                            DecayAdamRule{{alpha, beta1, beta2, epsilon, gscale}, (const ClipState*)clip_state, decay, mode}, stream);
 }
 // ---- moving average of the weights: one pass of its own behind the update pass (ema and w must not overlap: w is read through a
 // __restrict__ pointer)
@@ -480,7 +476,7 @@ extern "C" int rsu_ema_step(float* ema, const float* w, long n, float one_minus_
 }
 // ---- gradient accumulation: dst = src or dst += src in one pass (dst and src must not overlap: src is read through a __restrict__
 // pointer)
-static_assert(RSU_GRAD_ACCUMULATE_BLOCK_FLOATS == EW_ACC_EPB, "rsu.h and elementwise.h must agree on a workgroup's share");
+static_assert(RSU_GRAD_ACCUMULATE_BLOCK_FLOATS == EW_ACC_EPB, "rsu.h and optim.h must agree on a workgroup's share");
 extern "C" int rsu_grad_accumulate(float* dst, const float* src, long n, int assign, rsu_stream_t stream) {
     if (!dst || !src || n < 1) return RSU_EINVAL;
     if (((uintptr_t)dst & 15) || ((uintptr_t)src & 15)) return RSU_EINVAL;

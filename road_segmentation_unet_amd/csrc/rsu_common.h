@@ -81,7 +81,15 @@ struct TileGeo {
     unsigned inv_SW, inv_CW;  // div_magic constants
 };
 
-#define HIP_CHECK_RET(x)                     \
+// grid of a grid-stride launch: cdiv(total, block) workgroups, at most `cap`, at least 1
+static inline int grid_for(long total, int block, int cap = 256 * 16) {
+    long g = (total + block - 1) / block;
+    if (g > cap) g = cap;
+    if (g < 1) g = 1;
+    return (int)g;
+}
+
+#define HIP_CHECK_RET(x)                   \
     do {                                     \
         hipError_t e__ = (x);                \
         if (e__ != hipSuccess) {             \

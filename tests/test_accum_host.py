@@ -135,7 +135,7 @@ def test_symbol_is_declared_and_exported():
     assert len(m.group(1).split(",")) == 5 == len(_lib.SIGNATURES["rsu_grad_accumulate"][1])
     share = re.search(r"#define RSU_GRAD_ACCUMULATE_BLOCK_FLOATS (\d+)", code)
     assert share and int(share.group(1)) == _lib.GRAD_ACCUMULATE_BLOCK_FLOATS
-    hdr = open(os.path.join(ROOT, "road_segmentation_unet_amd", "csrc", "elementwise.h")).read()
+    hdr = open(os.path.join(ROOT, "road_segmentation_unet_amd", "csrc", "optim.h")).read()
     assert re.search(r"constexpr int EW_ACC_EPB = (\d+);", hdr).group(1) == share.group(1)
     assert hasattr(_lib.lib(), "rsu_grad_accumulate")
 

@@ -11,6 +11,7 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
+from road_segmentation_unet_amd import optim as optim_mod
 from road_segmentation_unet_amd import unet as unet_mod
 from road_segmentation_unet_amd._lib import RsuError, call
 from road_segmentation_unet_amd.unet import UNet, ema_decay_at
@@ -201,7 +202,8 @@ def test_arguments_and_the_net_that_does_not_accumulate(monkeypatch):
     assert UNet(2, 16, False, B, P, training=False, accumulate_steps=1).flat_gsum is None
     names = []
     real = unet_mod.call
-    monkeypatch.setattr(unet_mod, "call", lambda name, *a: (names.append(name), real(name, *a))[1])
+    for mod in (unet_mod, optim_mod):   # (the passes' calls and the optimizer step's)
+        monkeypatch.setattr(mod, "call", lambda name, *a: (names.append(name), real(name, *a))[1])
     one = UNet(2, 16, False, B, P, seed=43, accumulate_steps=1)
     none = UNet(2, 16, False, B, P, seed=43, accumulate_steps=None)
     plain = UNet(2, 16, False, B, P, seed=43)

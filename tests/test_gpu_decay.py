@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from road_segmentation_unet_amd import optim as optim_mod
 from road_segmentation_unet_amd import unet as unet_mod
 from road_segmentation_unet_amd._lib import RsuError
 from road_segmentation_unet_amd.unet import UNet, ema_decay_at, lr_at
@@ -181,7 +182,8 @@ def test_without_decay_the_net_issues_the_calls_it_always_did(optimizer, monkeyp
     names = {}
     real = unet_mod.call
     who = [None]
-    monkeypatch.setattr(unet_mod, "call", lambda name, *a: (names.setdefault(who[0], []).append(name), real(name, *a))[1])
+    for mod in (unet_mod, optim_mod):   # (the passes' calls and the optimizer step's)
+        monkeypatch.setattr(mod, "call", lambda name, *a: (names.setdefault(who[0], []).append(name), real(name, *a))[1])
     nets = {"none": _net(optimizer, weight_decay=None), "plain": _net(optimizer), "decay": _net(optimizer, weight_decay=LAMBDA)}
     for x, y in _batches(nets["plain"], 2, 77):
         for who[0], m in nets.items():
@@ -228,7 +230,8 @@ def test_the_net_steps_at_the_scheduled_rate(monkeypatch):
     net.set_lr_schedule("cosine", 2, 10, 0.1)
     seen = []
     real = unet_mod.call
-    monkeypatch.setattr(unet_mod, "call", lambda name, *a: (seen.append((name, a)), real(name, *a))[1])
+    for mod in (unet_mod, optim_mod):   # (the passes' calls and the optimizer step's)
+        monkeypatch.setattr(mod, "call", lambda name, *a: (seen.append((name, a)), real(name, *a))[1])
     x, y = _batches(net, 1, 79)[0]
     for t in range(4):
         want = lr_at(t, LR, "cosine", 2, 10, 0.1)
