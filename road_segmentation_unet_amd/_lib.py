@@ -1,4 +1,4 @@
-"""ctypes binding of librsu_hip.so (the C ABI of include/rsu.h and include/rsu_optim.h).
+"""ctypes binding of librsu_hip.so (the C ABI of include/rsu.h, include/rsu_optim.h and include/rsu_loss.h).
 
 The library is REQUIRED: there is no CPU or eager-PyTorch fallback anywhere in this package. If the
 shared object is missing or a symbol cannot be resolved, importing/using the product path raises."""
@@ -158,6 +158,12 @@ SIGNATURES_OPTIM = {
     "rsu_update_table_run_adam_decay": (_i, [_vp, _i, _i, _f, _f, _f, _f, _f, _f, _i, _vp, _vp]),
 }
 
+# and for include/rsu_loss.h, the third (the focal cross-entropy heads)
+SIGNATURES_LOSS = {
+    "rsu_head_fwd_bwd_focal": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _f, _vp]),
+    "rsu_head_eval_focal": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _l, _i, _vp]),
+}
+
 _lib = None
 
 
@@ -173,7 +179,7 @@ def lib():
             raise RsuError("HIP extension missing: %s (build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            "or `make -C road_segmentation_unet_amd/csrc`); there is no fallback path" % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_OPTIM.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_OPTIM.items()) + list(SIGNATURES_LOSS.items()):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

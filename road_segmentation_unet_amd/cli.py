@@ -64,6 +64,9 @@ def main(argv=None):
         decays, live = model.net.decaying_parameters()
         print("Weight decay: {} lambda {:g}, {} of {} live parameters decay (conv kernels; biases, colour adjust and the head do not); "
               "the reported loss excludes the penalty".format(opts.weight_decay_mode, opts.weight_decay, decays, live))
+    if opts.focal_gamma > 0.0:
+        print("Focal loss: gamma {:g}; the logged loss and the validation loss / objective are the focal objective, and the gradient is "
+              "smaller than the cross-entropy's (--lr is not rescaled)".format(opts.focal_gamma))
 
     if opts.restore_model:
         if opts.model_path is not None:

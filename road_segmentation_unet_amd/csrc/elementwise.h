@@ -49,6 +49,10 @@ constexpr int EW_EVAL_SLICES = 8;   // k_head_eval_final: workgroups per 64-bin 
 size_t ew_head_eval_ws_floats(long npix, int C);
 hipError_t ew_head_eval(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w, const float* pixel_w,
                         float* prob, float* sums, unsigned long long* hist, float* ws, long npix, int C, hipStream_t st);
+// the final launches of ew_head_loss (k_head_final_loss over [nblk][2 C + 4] partials) and of ew_head_eval (k_head_eval_final over
+// [nblk][5] partials and the [nblk][2][EW_EVAL_BINS] rows) alone: the focal heads of loss.h end with them
+hipError_t ew_head_final_loss(const float* ws, float* dw, float* db, float* loss_sum, float* weight_sum, int nblk, int C, hipStream_t st);
+hipError_t ew_head_eval_final(const float* ws, const unsigned* hpart, float* sums, unsigned long long* hist, int nblk, hipStream_t st);
 hipError_t ew_color_adjust_bwd(const float* gx, const float* w1, float* dW0, float* db0, int Cout, float scale, int accumulate, hipStream_t st);
 hipError_t ew_pack(const float* src, void* dst, const PackParams& pp, hipStream_t st);
 struct PackJob { PackParams pp; const float* src; bf16_t* dst; int block_start; int pad_; };

@@ -4,19 +4,7 @@
 
 #include <type_traits>
 
-static __device__ __forceinline__ void unpack8(const u32x4 v, float* f) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[2 * i] = bf_lo(v[i]);
-        f[2 * i + 1] = bf_hi(v[i]);
-    }
-}
-static __device__ __forceinline__ u32x4 pack8(const float* f) {
-    u32x4 r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) r[i] = pack_bf2(f[2 * i], f[2 * i + 1]);
-    return r;
-}
+#include "head_stages.h"
 
 // ---------------------------------------------------------------------------------------------
 // unet.py:22-23  color_space_adjust
@@ -421,10 +409,12 @@ __global__ void __launch_bounds__(256) k_reduce_slabs_many(const ReduceJob* __re
 // LP = C/8 lanes per pixel, partial logits reduced with wave shuffles
 // Two sets of kernels. k_head<TRAIN> and k_head_final are PINNED: the unweighted step is on the critical queue, and sharing k_head's body
 // through an inlined function template moved its register allocation (1500 of 1585 ISA lines), so they are written out and nothing
-// below is shared with them. The opt-in heads form one family built from the head_* device helpers below (per-thread setup, the batched
+// below is shared with them. The opt-in heads form one family built from the head_* device helpers of head_stages.h (per-thread setup, the batched
 // load, logits + softmax, the LDS block reduce, the final kernels' sum): k_head_loss<DICE> (weighted training head / pass B of the
 // soft-Dice head) with k_head_final_loss, and the forward-only k_head_sums<EVAL> (pass A of the soft-Dice head / the evaluation head)
 // with k_head_final_dice_sums and k_head_eval_final. Their grid, pixel-to-thread mapping and the order of every sum are k_head<true>'s.
+// The focal members of the family, k_head_focal<DICE> and k_head_sums_focal (rsu_loss.h), are in loss.hip: inside this file they changed
+// 29 lines of address arithmetic in k_head_sums<true>'s block reduce, and every kernel here keeps the ISA it shipped with.
 // ---------------------------------------------------------------------------------------------
 template <bool TRAIN>
 __global__ void __launch_bounds__(256) k_head(const bf16_t* __restrict__ act, const float* __restrict__ w, const float* __restrict__ b,
@@ -558,72 +548,8 @@ __global__ void __launch_bounds__(256) k_head_final(const float* __restrict__ pa
     }
 }
 
-// ---- the opt-in family: stages shared by k_head_loss<DICE> and k_head_sums<EVAL> (see the head of this section) ----
-// per-thread setup: the thread's 8 channels of both weight columns and the two biases
-static __device__ __forceinline__ void head_setup(const float* __restrict__ w, const float* __restrict__ b, int sub, float (&w0)[8], float (&w1)[8],
-                                                  float& b0, float& b1) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        w0[i] = w[(sub * 8 + i) * 2];
-        w1[i] = w[(sub * 8 + i) * 2 + 1];
-    }
-    b0 = b[0];
-    b1 = b[1];
-}
-// HU pixels per thread and trip as in k_head; the pixel's 64-bit label and its weight are requested with its activations, before any is used
-constexpr int HEAD_HU = 4;
-template <typename IT>
-static __device__ __forceinline__ void head_load(const bf16_t* __restrict__ act, const int64_t* __restrict__ labels, const float* __restrict__ pixel_w,
-                                                 IT it0, IT niter, long npix, int C, int LP, int sub, int ppb, long (&pp)[HEAD_HU],
-                                                 bool (&okk)[HEAD_HU], u32x4 (&raw)[HEAD_HU], int64_t (&labv)[HEAD_HU], float (&pwv)[HEAD_HU]) {
-#pragma unroll
-    for (int u = 0; u < HEAD_HU; ++u) {
-        pp[u] = ((long)(it0 + u) * gridDim.x + blockIdx.x) * ppb + threadIdx.x / LP;
-        okk[u] = (it0 + u < niter) && pp[u] < npix;
-        raw[u] = okk[u] ? *(const u32x4*)(act + pp[u] * C + sub * 8) : u32x4{0u, 0u, 0u, 0u};
-        labv[u] = okk[u] ? labels[pp[u]] : 0;
-        pwv[u] = (okk[u] && pixel_w) ? pixel_w[pp[u]] : 1.f;
-    }
-}
-// logits (partial dot products met with wave shuffles) and the two-way softmax: k_head's expressions, so prob gets its bits
-static __device__ __forceinline__ void head_softmax(const u32x4 raw, const float (&w0)[8], const float (&w1)[8], float b0, float b1, int LP,
-                                                    float (&a)[8], float& l0, float& l1, float& m, float& s, float& p0, float& p1) {
-    unpack8(raw, a);
-    l0 = 0.f;
-    l1 = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        l0 = fmaf(a[i], w0[i], l0);
-        l1 = fmaf(a[i], w1[i], l1);
-    }
-    for (int o = 1; o < LP; o <<= 1) {
-        l0 += __shfl_xor(l0, o);
-        l1 += __shfl_xor(l1, o);
-    }
-    l0 += b0;
-    l1 += b1;
-    m = fmaxf(l0, l1);
-    const float e0 = expf(l0 - m), e1 = expf(l1 - m);
-    s = e0 + e1;
-    p1 = e1 / s;
-    p0 = e0 / s;
-}
-// block reduce over rows of NV floats, one row per thread (an odd NV keeps the rows on different LDS banks): value j of the threads that
-// hold channel group sg, in the order of their pixels
-template <int NV>
-static __device__ __forceinline__ float head_block_sum(const float* red, int sg, int j, int ppb, int LP) {
-    float t = 0.f;
-    for (int q = 0; q < ppb; ++q) t += red[(q * LP + sg) * NV + j];
-    return t;
-}
-// k_head_final's sum of output o over the blocks' partials: lane l adds partials l, l + 64, ... (independent loads), then a fixed-order butterfly
-static __device__ __forceinline__ float head_final_sum(const float* __restrict__ partial, int nblk, int nout, int o, int lane) {
-    float t = 0.f;
-    for (int bk = lane; bk < nblk; bk += 64) t += partial[(long)bk * nout + o];
-    for (int m = 32; m > 0; m >>= 1) t += __shfl_xor(t, m);
-    return t;
-}
-
+// (the family's shared stages -- head_setup / head_load / head_softmax / head_block_sum / head_final_sum -- are in head_stages.h: loss.hip
+// builds the focal members from them)
 // The training heads with weights. k_head_loss<false> (rsu.h rsu_head_fwd_bwd_w): k_head<true> with omega = class_w[label] * pixel_w[pixel]
 // in front of the pixel's loss and dlogits. A label that is neither 0 nor 1 (tested on all 64 bits) means omega = 0 BY SELECTION, never by
 // multiplication: the pixel's dact row is stored as +0 and it is left out of every sum, whatever its pixel_w holds. One more per-thread sum
@@ -1302,6 +1228,15 @@ hipError_t ew_head_eval(const void* act, const float* w, const float* b, const i
     unsigned* hpart = (unsigned*)(ws + (size_t)nb * 5);   // [nb][2][EW_EVAL_BINS] behind the [nb][5] partial sums
     hipLaunchKernelGGL(k_head_sums<true>, dim3(nb), dim3(256), 0, st, (const bf16_t*)act, w, b, labels, class_w, pixel_w, prob, ws, hpart, npix, C);
     hipLaunchKernelGGL(k_head_eval_final, dim3(2 + 8 * EW_EVAL_SLICES), dim3(256), 0, st, ws, hpart, sums, hist, nb);
+    return hipGetLastError();
+}
+// the final launches of ew_head_loss and ew_head_eval on their own: loss.hip's focal heads leave the same partials and end with them
+hipError_t ew_head_final_loss(const float* ws, float* dw, float* db, float* loss_sum, float* weight_sum, int nblk, int C, hipStream_t st) {
+    hipLaunchKernelGGL(k_head_final_loss, dim3((2 * C + 4 + 3) / 4), dim3(256), 0, st, ws, dw, db, loss_sum, weight_sum, nblk, C);
+    return hipGetLastError();
+}
+hipError_t ew_head_eval_final(const float* ws, const unsigned* hpart, float* sums, unsigned long long* hist, int nblk, hipStream_t st) {
+    hipLaunchKernelGGL(k_head_eval_final, dim3(2 + 8 * EW_EVAL_SLICES), dim3(256), 0, st, ws, hpart, sums, hist, nblk);
     return hipGetLastError();
 }
 hipError_t ew_color_adjust_bwd(const float* gx, const float* w1, float* dW0, float* db0, int Cout, float scale, int accumulate, hipStream_t st) {

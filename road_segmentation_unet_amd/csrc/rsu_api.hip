@@ -14,10 +14,12 @@
 
 #include "../../include/rsu.h"
 #include "../../include/rsu_optim.h"
+#include "../../include/rsu_loss.h"
 #include "affine_patches.h"
 #include "color_jitter.h"
 #include "border_map.h"
 #include "elementwise.h"
+#include "loss.h"
 #include "optim.h"
 #include "igemm.h"
 
@@ -1528,6 +1530,34 @@ extern "C" int rsu_head_eval(const void* act, const float* w, const float* b, co
                              rsu_stream_t stream) {
     if (!act || !w || !b || !labels || !prob || !sums || !hist || !ws || !head_c_ok(C) || npix < 1) return RSU_EINVAL;
     HIP_CHECK_RET(ew_head_eval(act, w, b, labels, class_w, pixel_w, prob, sums, hist, ws, npix, C, (hipStream_t)stream));
+    return RSU_OK;
+}
+// ---- the focal heads (rsu_loss.h). gamma == 0 is decided here: the call launches what the existing entries launch (0 * log2(0) in the
+// focal kernels would be NaN, and the existing results are then had bit for bit by construction)
+static bool focal_gamma_ok(float gamma) { return std::isfinite(gamma) && gamma >= 0.f; }
+extern "C" int rsu_head_fwd_bwd_focal(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w,
+                                      const float* pixel_w, float gamma, const float* dice_sums, float dice_scale, float smooth, float* prob,
+                                      float* loss_sum, float* weight_sum, void* dact, float* dw, float* db, float* ws, long npix, int C,
+                                      float inv_count, rsu_stream_t stream) {
+    if (!focal_gamma_ok(gamma) || !head_train_args_ok(act, w, b, labels, prob, loss_sum, dact, dw, db, ws, npix, C)) return RSU_EINVAL;
+    if (dice_sums && (!std::isfinite(smooth) || !(smooth > 0.f) || !std::isfinite(dice_scale) || !(dice_scale >= 0.f))) return RSU_EINVAL;
+    if (!dice_sums) dice_scale = smooth = 0.f;   // (not looked at)
+    if (gamma == 0.f)
+        HIP_CHECK_RET(ew_head_loss(act, w, b, labels, class_w, pixel_w, dice_sums, dice_scale, smooth, prob, dact, dw, db, loss_sum, weight_sum,
+                                   ws, npix, C, inv_count, (hipStream_t)stream));
+    else
+        HIP_CHECK_RET(ew_head_focal(act, w, b, labels, class_w, pixel_w, gamma, dice_sums, dice_scale, smooth, prob, dact, dw, db, loss_sum,
+                                    weight_sum, ws, npix, C, inv_count, (hipStream_t)stream));
+    return RSU_OK;
+}
+extern "C" int rsu_head_eval_focal(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w,
+                                   const float* pixel_w, float gamma, float* prob, float* sums, unsigned long long* hist, float* ws, long npix,
+                                   int C, rsu_stream_t stream) {
+    if (!focal_gamma_ok(gamma) || !act || !w || !b || !labels || !prob || !sums || !hist || !ws || !head_c_ok(C) || npix < 1) return RSU_EINVAL;
+    if (gamma == 0.f)
+        HIP_CHECK_RET(ew_head_eval(act, w, b, labels, class_w, pixel_w, prob, sums, hist, ws, npix, C, (hipStream_t)stream));
+    else
+        HIP_CHECK_RET(ew_head_eval_focal(act, w, b, labels, class_w, pixel_w, gamma, prob, sums, hist, ws, npix, C, (hipStream_t)stream));
     return RSU_OK;
 }
 static_assert(RSU_BORDER_MAX_SIDE == BM_MAX_SIDE, "rsu.h and border_map.h must agree on the supported tile size");

@@ -74,6 +74,11 @@ EXTRA_FLAG_DEFS = [
     ("dice_weight", float, 0.0, "lambda >= 0 of a soft-Dice (soft-F1) term: loss = cross-entropy + lambda * (1 - Dice), Dice over each GPU's "
                                 "batch; 0 = off (the reference's loss). Ignored pixels and the weight map enter Dice, class weights do not"),
     ("dice_smooth", float, 1.0, "Smoothing constant s > 0 of Dice = (2 I + s) / (P + Y + s)"),
+    ("focal_gamma", float, 0.0, "gamma >= 0 (finite) of the focal loss (Lin et al. 2017): every pixel's cross-entropy counts (1 - p_t)^gamma "
+                                "times, p_t the probability of its true class; 0 = off (2 is the paper's choice). The logged loss and the "
+                                "validation loss / objective are then the focal objective. The gradient shrinks with gamma (the loss stays "
+                                "normalised by the pixel count), so --lr needs retuning. It multiplies --class_weights, --border_weight and "
+                                "the weight map; --dice_weight adds to it unchanged"),
     ("border_weight", float, 0.0, "w0 >= 0 of a border-distance weight map computed on the GPU from each batch's labels: a pixel counts "
                                   "1 + w0 * exp(-d^2 / (2 border_sigma^2)) times in the loss, d its distance to the other class inside its patch; "
                                   "0 = off (the U-Net paper uses 10). The loss stays normalised by the pixel count and the mean weight is above 1, "
@@ -166,6 +171,45 @@ def parse_dice_weight(value):
     if not (math.isfinite(v) and v >= 0.0):
         raise ValueError("--dice_weight must be a finite float >= 0, not %r" % (value,))
     return v
+
+
+def parse_focal_gamma(value):
+    """The --focal_gamma value as a float: finite and >= 0 (0.0 = the plain cross-entropy). Anything else raises ValueError."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if isinstance(value, bool) or not (math.isfinite(v) and v >= 0.0):
+        raise ValueError("--focal_gamma must be a finite float >= 0, not %r" % (value,))
+    return v
+
+
+def focal_loss_terms(p1, labels, gamma, class_weights=None, pixel_weights=None):
+    """The focal objective of include/rsu_loss.h recomputed on the host, in numpy float64, from road probabilities (a `predict` output or
+    net.prob) and labels of the same shape: (sum omega F CE, sum omega) over the pixels whose label is 0 or 1 -- any other label ignores
+    its pixel BY SELECTION, whatever its weight holds -- with p_t the probability of the pixel's label, F = (1 - p_t)^gamma, CE = -log p_t
+    and omega = class_weights[label] * pixel_weights[pixel] (None: 1). A pixel with p_t == 0 has an infinite CE, as it has without the
+    modulation; one with p_t == 1 adds 0. Divide the first sum by the pixel count for the logged `loss`, by the second for the weighted
+    mean. gamma == 0 is the weighted cross-entropy."""
+    gamma = parse_focal_gamma(gamma)
+    p1, labels = np.asarray(p1, dtype=np.float64).reshape(-1), np.asarray(labels).reshape(-1)
+    if p1.shape != labels.shape:
+        raise ValueError("focal_loss_terms: %d probabilities, %d labels" % (p1.size, labels.size))
+    valid = (labels == 0) | (labels == 1)
+    lab = labels[valid].astype(np.int64)
+    p_t = np.where(lab == 1, p1[valid], 1.0 - p1[valid])
+    p_o = np.where(lab == 1, 1.0 - p1[valid], p1[valid])
+    omega = np.ones(lab.size, np.float64) if class_weights is None else np.asarray(class_weights, np.float64)[lab]
+    if pixel_weights is not None:
+        pw = np.asarray(pixel_weights, dtype=np.float64).reshape(-1)
+        if pw.shape != labels.shape:
+            raise ValueError("focal_loss_terms: %d weights, %d labels" % (pw.size, labels.size))
+        omega = omega * pw[valid]
+    with np.errstate(divide="ignore"):
+        ce = -np.log(p_t)
+    F = np.power(p_o, gamma) if gamma > 0.0 else np.ones_like(p_o)
+    terms = np.where(F == 0.0, 0.0, omega * F * ce)      # (p_t == 1: F = 0 and CE = 0)
+    return float(terms.sum()), float(omega.sum())
 
 
 def parse_dice_smooth(value):
@@ -460,6 +504,7 @@ class Options(object):
             raise ValueError("--optimizer must be momentum or adam, not %r" % (self.optimizer,))
         self.class_weights = parse_class_weights(self.class_weights)   # None, (w0, w1) or "balanced" (cli.main resolves it)
         self.dice_weight, self.dice_smooth = parse_dice_weight(self.dice_weight), parse_dice_smooth(self.dice_smooth)
+        self.focal_gamma = parse_focal_gamma(self.focal_gamma)
         self.border_weight, self.border_sigma = parse_border_weight(self.border_weight), parse_border_sigma(self.border_sigma)
         self.clip_grad_norm = parse_clip_grad_norm(self.clip_grad_norm)
         self.ema_decay, self.ema_warmup = parse_ema_decay(self.ema_decay), bool(self.ema_warmup)
@@ -532,7 +577,7 @@ class ConvolutionalModel:
                         ema_decay=opts.ema_decay if opts.ema_decay > 0.0 else None, ema_warmup=opts.ema_warmup,
                         accumulate_steps=K if K > 1 else None,
                         weight_decay=opts.weight_decay if getattr(opts, "weight_decay", 0.0) > 0.0 else None,
-                        weight_decay_mode=getattr(opts, "weight_decay_mode", "decoupled"))
+                        weight_decay_mode=getattr(opts, "weight_decay_mode", "decoupled"), focal_gamma=getattr(opts, "focal_gamma", 0.0))
         self.net.dropout_seed = int(opts.seed) + 7919 * self.rank  # independent masks on every rank's shard
         # --lr_schedule: cosine | linear with --lr_total_steps=0 wait for resolve_lr_total_steps() (the patches are not known yet)
         self._lr_unresolved = getattr(opts, "lr_schedule", "staircase") in ("cosine", "linear") and getattr(opts, "lr_total_steps", 0) < 1

@@ -99,7 +99,8 @@ class UNet(OptimizerStep):
 
     def __init__(self, num_layers, root_size, dilated_layers, batch_size, patch_size, device="cuda:0", params=None, seed=2017,
                  training=True, optimizer="momentum", class_weights=None, dice_weight=0.0, dice_smooth=1.0, border_weight=0.0, border_sigma=5.0,
-                 clip_grad_norm=None, ema_decay=None, ema_warmup=True, accumulate_steps=None, weight_decay=None, weight_decay_mode="decoupled"):
+                 clip_grad_norm=None, ema_decay=None, ema_warmup=True, accumulate_steps=None, weight_decay=None, weight_decay_mode="decoupled",
+                 focal_gamma=0.0):
         """optimizer: "momentum" (the reference's MomentumOptimizer: apply_momentum) or "adam" (tf.train.AdamOptimizer: apply_adam; a
         second fp32 slot per variable, flat_v).
         class_weights: None or a pair (w0, w1) of finite floats >= 0, not both 0: the weighted cross-entropy of rsu.h
@@ -134,6 +135,11 @@ class UNet(OptimizerStep):
         nothing in state_dict(). The moving average, gradient accumulation and the data-parallel exchange sit in front of or behind
         the update pass and are what they were. Training nets only (ValueError otherwise; bad values raise ValueError too). None: the
         step is what it always was.
+        focal_gamma: gamma >= 0 (finite) of the focal cross-entropy (rsu_loss.h): with gamma > 0 every counted pixel's cross-entropy is
+        scaled by (1 - p_t)^gamma in backward_device (rsu_head_fwd_bwd_focal) and in evaluate_device (rsu_head_eval_focal): loss_sum and
+        eval_sums[0] are then sum omega F CE. It multiplies the class weights, the weight map and the border map; the Dice term is added
+        to it unchanged; inv_count stays 1 / pixel count, so the gradient shrinks. Labels other than 0 / 1 are ignored, as in every
+        weighted pass. 0.0: the passes issue exactly the launches they always did.
         The learning-rate curve is set_lr_schedule()'s; the default is the reference's staircase."""
         self._init_optimizer(training, optimizer, clip_grad_norm, ema_decay, ema_warmup, accumulate_steps, weight_decay, weight_decay_mode)
         assert root_size % 8 == 0 and (root_size // 8) & (root_size // 8 - 1) == 0, "root_size must be 8 * 2^k for the HIP path"
@@ -147,6 +153,7 @@ class UNet(OptimizerStep):
         self.class_weights = class_weights   # (a property: validated, mirrored to the device as f32[2])
         self.pixel_weights = None            # the weight map [B, P, P] float32 on the device, or None (set_pixel_weights)
         self.dice_weight, self.dice_smooth = dice_weight, dice_smooth   # (properties: validated)
+        self.focal_gamma = focal_gamma       # (a property: validated)
         self.border_weight, self.border_sigma = self._border_args(border_weight, border_sigma)
         self.border_map = None               # the generated weight map [B, P, P] float32 (derived from labels per pass), with border_weight > 0
         self.keep = 1.0        # dropout keep probability of the forward pass in flight (set by forward_device)
@@ -193,6 +200,22 @@ class UNet(OptimizerStep):
         if not (math.isfinite(v) and v >= 0.0):
             raise _lib.RsuError("dice_weight must be a finite float >= 0")
         self._dice_weight = v
+
+    @property
+    def focal_gamma(self):
+        """gamma of the focal cross-entropy (rsu_loss.h): > 0 sends backward_device and evaluate_device to the focal heads; 0.0: no
+        modulation, the launches of a net without it"""
+        return self._focal_gamma
+
+    @focal_gamma.setter
+    def focal_gamma(self, v):
+        try:
+            v = float(v)
+        except (TypeError, ValueError):
+            v = float("nan")
+        if not (math.isfinite(v) and v >= 0.0):
+            raise _lib.RsuError("focal_gamma must be a finite float >= 0")
+        self._focal_gamma = v
 
     @property
     def dice_smooth(self):
@@ -650,6 +673,11 @@ class UNet(OptimizerStep):
             raise _lib.RsuError("evaluate_device needs a training net (labels and the head's workspace); a forward-only net has no loss")
         if self.keep != 1.0:
             raise _lib.RsuError("evaluate_device follows forward_device(keep=1.0): the activations in flight were made with dropout")
+        if self._focal_gamma > 0.0:   # the objective the net is trained on: sums[0] += sum omega F CE (rsu_loss.h)
+            call("rsu_head_eval_focal", _ptr(self.act[self.last_name]), _ptr(self.w["weight_output/kernel"]), _ptr(self.w["weight_output/bias"]),
+                 _ptr(self.labels), _ptr(self._class_w_dev), _ptr(self._head_pixel_weights()), self._focal_gamma, _ptr(self.prob),
+                 _ptr(self.eval_sums), _ptr(self.eval_hist), _ptr(self.ws), self.B * self.P * self.P, self.root, self._stream())
+            return
         call("rsu_head_eval", _ptr(self.act[self.last_name]), _ptr(self.w["weight_output/kernel"]), _ptr(self.w["weight_output/bias"]),
              _ptr(self.labels), _ptr(self._class_w_dev), _ptr(self._head_pixel_weights()), _ptr(self.prob), _ptr(self.eval_sums), _ptr(self.eval_hist),
              _ptr(self.ws), self.B * self.P * self.P, self.root, self._stream())
@@ -723,6 +751,8 @@ class UNet(OptimizerStep):
         synchronisation), labels other than 0 / 1 are ignored, the weight map enters D and the class weights do not. loss_sum and weight_sum
         stay the cross-entropy's; the term's value is dice_scale * (1 - D) with D from dice_sums. A data-parallel host passes
         dice_weight / world. With dice_scale == 0 the pass is exactly the one described above.
+        focal_gamma > 0 takes the focal head instead (rsu_loss.h rsu_head_fwd_bwd_focal): omega F CE per counted pixel in loss_sum and its
+        gradient, F = (1 - p_t)^gamma; weight_sum, the Dice term and inv_count as above.
         update = (lr0, momentum): accepted from callers that name the Momentum step they will take; it changes nothing here -- the step
         is apply_momentum's -- but a net built with another optimizer refuses it."""
         self._not_averaged("backward_device")
@@ -753,7 +783,17 @@ class UNet(OptimizerStep):
         last = a[self.last_name]
         self._loss_acc.zero_()
         pixel_w = self._head_pixel_weights()
-        if dice_scale > 0.0:
+        if self._focal_gamma > 0.0:
+            # the focal head (rsu_loss.h): the weighted head's arguments and gamma; with a Dice term pass B behind an unchanged pass A
+            head = (_ptr(last), _ptr(self.w["weight_output/kernel"]), _ptr(self.w["weight_output/bias"]), _ptr(self.labels))
+            npix = B * self.P * self.P
+            if dice_scale > 0.0:
+                call("rsu_head_dice_sums", *head, _ptr(pixel_w), _ptr(self.prob), _ptr(self.dice_sums), _ptr(self.ws), npix, self.root, st)
+            call("rsu_head_fwd_bwd_focal", *head, _ptr(self._class_w_dev), _ptr(pixel_w), self._focal_gamma,
+                 _ptr(self.dice_sums) if dice_scale > 0.0 else None, dice_scale, self._dice_smooth, _ptr(self.prob), _ptr(self.loss_sum),
+                 _ptr(self.weight_sum), _ptr(g[self.last_name]), _ptr(self.g["weight_output/kernel"]), _ptr(self.g["weight_output/bias"]),
+                 _ptr(self.ws), npix, self.root, inv_count, st)
+        elif dice_scale > 0.0:
             head = (_ptr(last), _ptr(self.w["weight_output/kernel"]), _ptr(self.w["weight_output/bias"]), _ptr(self.labels))
             npix = B * self.P * self.P
             call("rsu_head_dice_sums", *head, _ptr(pixel_w), _ptr(self.prob), _ptr(self.dice_sums), _ptr(self.ws), npix, self.root, st)
