@@ -1,4 +1,4 @@
-"""ctypes binding of librsu_hip.so (the C ABI of include/rsu.h, include/rsu_optim.h and include/rsu_loss.h).
+"""ctypes binding of librsu_hip.so (the C ABI of include/rsu.h, include/rsu_optim.h, include/rsu_loss.h and include/rsu_cldice.h).
 
 The library is REQUIRED: there is no CPU or eager-PyTorch fallback anywhere in this package. If the
 shared object is missing or a symbol cannot be resolved, importing/using the product path raises."""
@@ -164,6 +164,14 @@ SIGNATURES_LOSS = {
     "rsu_head_eval_focal": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _l, _i, _vp]),
 }
 
+# and for include/rsu_cldice.h, the fourth (the clDice term: soft-skeleton forward / backward and the head that takes their gradient)
+SIGNATURES_CLDICE = {
+    "rsu_cldice_ws_floats": (_sz, [_i, _i, _i, _i]),
+    "rsu_cldice_fwd": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "rsu_cldice_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _f, _vp, _vp, _i, _i, _i, _vp]),
+    "rsu_head_fwd_bwd_aux": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _f, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -179,7 +187,8 @@ def lib():
             raise RsuError("HIP extension missing: %s (build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            "or `make -C road_segmentation_unet_amd/csrc`); there is no fallback path" % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_OPTIM.items()) + list(SIGNATURES_LOSS.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_OPTIM.items()) + list(SIGNATURES_LOSS.items()) \
+                + list(SIGNATURES_CLDICE.items()):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -196,6 +205,7 @@ DECAY_L2, DECAY_DECOUPLED = 0, 1   # rsu_optim.h RSU_DECAY_*
 AFFINE_MAX_LAUNCH = 32   # rsu.h RSU_AFFINE_MAX_LAUNCH
 ELASTIC_MAX_LAUNCH, ELASTIC_MAX_GRID = 32, 16   # rsu.h RSU_ELASTIC_MAX_LAUNCH, RSU_ELASTIC_MAX_GRID
 JITTER_MAX_LAUNCH = 32   # rsu.h RSU_JITTER_MAX_LAUNCH
+CLDICE_MAX_ITERS = 16   # rsu_cldice.h RSU_CLDICE_MAX_ITERS
 E2BIG = -7
 
 

@@ -68,6 +68,10 @@ def main(argv=None):
         print("Focal loss: gamma {:g}; the logged loss and the validation loss / objective are the focal objective, and the gradient is "
               "smaller than the cross-entropy's (--lr is not rescaled)".format(opts.focal_gamma))
 
+    if opts.cldice_weight > 0.0:
+        print("clDice term: lambda {:g}, {} erosions, smooth {:g}; the logged loss and the validation objective include lambda * (1 - clD)"
+              .format(opts.cldice_weight, opts.cldice_iters, opts.cldice_smooth))
+
     if opts.restore_model:
         if opts.model_path is not None:
             model.restore(file=opts.model_path)

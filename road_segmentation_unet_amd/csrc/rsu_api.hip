@@ -15,11 +15,13 @@
 #include "../../include/rsu.h"
 #include "../../include/rsu_optim.h"
 #include "../../include/rsu_loss.h"
+#include "../../include/rsu_cldice.h"
 #include "affine_patches.h"
 #include "color_jitter.h"
 #include "border_map.h"
 #include "elementwise.h"
 #include "loss.h"
+#include "cldice.h"
 #include "optim.h"
 #include "igemm.h"
 
@@ -1558,6 +1560,36 @@ extern "C" int rsu_head_eval_focal(const void* act, const float* w, const float*
         HIP_CHECK_RET(ew_head_eval(act, w, b, labels, class_w, pixel_w, prob, sums, hist, ws, npix, C, (hipStream_t)stream));
     else
         HIP_CHECK_RET(ew_head_eval_focal(act, w, b, labels, class_w, pixel_w, gamma, prob, sums, hist, ws, npix, C, (hipStream_t)stream));
+    return RSU_OK;
+}
+// ---- the clDice term (rsu_cldice.h): the fused soft-skeleton forward and backward, and the head that takes their gradient wrt prob
+static_assert(RSU_CLDICE_MAX_ITERS == CL_MAX_ITERS, "rsu_cldice.h and cldice.h must agree on the iteration limit");
+static bool cldice_size_ok(int B, int H, int W, int iters) {
+    return B >= 1 && H >= 1 && W >= 1 && (long)B * H * W < (1l << 31) && iters >= 0 && iters <= CL_MAX_ITERS;
+}
+extern "C" size_t rsu_cldice_ws_floats(int B, int H, int W, int iters) { return cldice_size_ok(B, H, W, iters) ? cl_ws_floats(B, H, W, iters) : 0; }
+extern "C" int rsu_cldice_fwd(const float* prob, const int64_t* labels, int iters, float* skel_p, float* skel_y, float* sums, float* ws, int B,
+                              int H, int W, rsu_stream_t stream) {
+    if (!prob || !labels || !skel_p || !skel_y || !sums || !ws || !cldice_size_ok(B, H, W, iters)) return RSU_EINVAL;
+    HIP_CHECK_RET(cl_fwd(prob, labels, iters, skel_p, skel_y, sums, ws, B, H, W, (hipStream_t)stream));
+    return RSU_OK;
+}
+extern "C" int rsu_cldice_bwd(const float* prob, const int64_t* labels, const float* skel_p, const float* skel_y, const float* sums, int iters,
+                              float scale, float smooth, float* gprob, float* ws, int B, int H, int W, rsu_stream_t stream) {
+    if (!prob || !labels || !skel_p || !skel_y || !sums || !gprob || !ws || !cldice_size_ok(B, H, W, iters)) return RSU_EINVAL;
+    if (!std::isfinite(smooth) || !(smooth > 0.f) || !std::isfinite(scale) || !(scale >= 0.f)) return RSU_EINVAL;
+    HIP_CHECK_RET(cl_bwd(prob, labels, skel_y, sums, iters, scale, smooth, gprob, ws, B, H, W, (hipStream_t)stream));
+    return RSU_OK;
+}
+extern "C" int rsu_head_fwd_bwd_aux(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w,
+                                    const float* pixel_w, float gamma, const float* dice_sums, float dice_scale, float smooth, float* prob,
+                                    float* loss_sum, float* weight_sum, void* dact, float* dw, float* db, float* ws, long npix, int C,
+                                    float inv_count, const float* gprob, rsu_stream_t stream) {
+    if (!gprob || !focal_gamma_ok(gamma) || !head_train_args_ok(act, w, b, labels, prob, loss_sum, dact, dw, db, ws, npix, C)) return RSU_EINVAL;
+    if (dice_sums && (!std::isfinite(smooth) || !(smooth > 0.f) || !std::isfinite(dice_scale) || !(dice_scale >= 0.f))) return RSU_EINVAL;
+    if (!dice_sums) dice_scale = smooth = 0.f;   // (not looked at)
+    HIP_CHECK_RET(cl_head_aux(act, w, b, labels, class_w, pixel_w, gamma, dice_sums, dice_scale, smooth, gprob, prob, dact, dw, db, loss_sum,
+                              weight_sum, ws, npix, C, inv_count, (hipStream_t)stream));
     return RSU_OK;
 }
 static_assert(RSU_BORDER_MAX_SIDE == BM_MAX_SIDE, "rsu.h and border_map.h must agree on the supported tile size");

@@ -595,3 +595,110 @@ def elastic_patches(images, labels, recs, S, P):
         lf = labf[n]
         y[k] = _affine_lerp(lf[y0, x0], lf[y0, x1], lf[y1, x0], lf[y1, x1], fy, fx) >= np.float32(0.5)
     return x, y
+
+
+# ---- clDice: the soft skeleton and the centre-line Dice term on the host (include/rsu_cldice.h)
+CLDICE_MAX_ITERS = 16   # rsu_cldice.h RSU_CLDICE_MAX_ITERS
+_CLDICE_CROSS = ((-1, 0), (0, -1), (0, 0), (0, 1), (1, 0))                       # up, left, centre, right, down
+_CLDICE_BOX = tuple((dr, dc) for dr in (-1, 0, 1) for dc in (-1, 0, 1))          # row-major
+
+
+def _cldice_pick(x, offsets, fill, arg):
+    """min (arg = np.argmin) or max (np.argmax) of x [B, H, W] over the window `offsets`; positions outside the image hold `fill`
+    and never win. Returns (values, index of the winner in `offsets`): the FIRST of equal candidates, as the kernels decide."""
+    B, H, W = x.shape
+    pad = np.full((B, H + 2, W + 2), fill, x.dtype)
+    pad[:, 1:-1, 1:-1] = x
+    win = np.stack([pad[:, 1 + dr:1 + dr + H, 1 + dc:1 + dc + W] for dr, dc in offsets])
+    code = arg(win, axis=0)
+    return np.take_along_axis(win, code[None], axis=0)[0], code
+
+
+def _cldice_chain(x, iters):
+    """E_0..E_{k+1}, the erosions' and dilations' winners, d_j, S_j and the second ReLU's masks of skel(x), in x's own precision, every
+    operation rounded once: E_{j+1} = erode(E_j), O_j = dilate(E_{j+1}), d_j = relu(E_j - O_j), S_j = S_{j-1} + relu(d_j - S_{j-1} d_j)."""
+    E, amin, amax, d, S, r = [x], [], [], [], [], []
+    zero = x.dtype.type(0)
+    for j in range(iters + 1):
+        e, c = _cldice_pick(E[j], _CLDICE_CROSS, np.inf, np.argmin)
+        E.append(e)
+        amin.append(c)
+        o, c = _cldice_pick(e, _CLDICE_BOX, -np.inf, np.argmax)
+        amax.append(c)
+        t = E[j] - o
+        d.append(np.where(t > 0, t, zero))
+        if j == 0:
+            S.append(d[0])
+            r.append(None)
+        else:
+            u = d[j] - S[j - 1] * d[j]
+            r.append(u > 0)
+            S.append(S[j - 1] + np.where(u > 0, u, zero))
+    return E, amin, amax, d, S, r
+
+
+def _cldice_check_iters(iters):
+    if isinstance(iters, bool) or int(iters) != iters or not 0 <= int(iters) <= CLDICE_MAX_ITERS:
+        raise ValueError("cldice iterations must be an int in [0, %d], not %r" % (CLDICE_MAX_ITERS, iters))
+    return int(iters)
+
+
+def soft_skeleton(x, iters):
+    """The soft skeleton of include/rsu_cldice.h (Shit et al. 2021, soft_skel) of maps x [B, H, W] in numpy float32, the kernels'
+    operations in their order with one rounding each: equal to rsu_cldice_fwd's skel_p / skel_y bit for bit. Erosion is the min over the
+    cross, dilation the max over the 3 x 3 box; positions outside an image do not exist."""
+    x = np.ascontiguousarray(x, np.float32)
+    if x.ndim != 3:
+        raise ValueError("soft_skeleton: maps [B, H, W], not shape %r" % (x.shape,))
+    return _cldice_chain(x, _cldice_check_iters(iters))[4][-1]
+
+
+def _cldice_route(val, code, offsets):
+    """the transpose of a window pick: out[n + offsets[code[n]]] += val[n]"""
+    B, H, W = val.shape
+    out = np.zeros_like(val)
+    for o, (dr, dc) in enumerate(offsets):
+        v = np.where(code == o, val, 0.0)
+        out[:, max(0, dr):H + min(0, dr), max(0, dc):W + min(0, dc)] += v[:, max(0, -dr):H - max(0, dr), max(0, -dc):W - max(0, dc)]
+    return out
+
+
+def cldice_gradient(prob, labels, iters, scale, smooth, sums=None):
+    """The clDice term scale * (1 - clD) of include/rsu_cldice.h in numpy float64 from float32 probabilities [B, H, W] and int64 labels:
+    returns (skel_p, skel_y, sums, gprob) with sums = {A, Bp, Cc, Dy} and gprob = d term / d prob, the sub-gradient pinned as the
+    kernels pin it: among equal candidates of a window the first in row-major order wins (cross: up, left, centre, right, down),
+    relu'(0) = 0. Pixels whose label is neither 0 nor 1 are constants of the skeleton: they take part in the pooling, add nothing to
+    the sums and get gprob = 0. sums: None, or four numbers the gradient's factors are formed from in place of the maps' own sums, as
+    rsu_cldice_bwd forms them from what it finds in memory (the returned sums stay the maps' own)."""
+    k = _cldice_check_iters(iters)
+    p = np.ascontiguousarray(prob, np.float64)
+    labels = np.asarray(labels)
+    if p.ndim != 3 or labels.shape != p.shape:
+        raise ValueError("cldice_gradient: prob and labels [B, H, W], not %r and %r" % (p.shape, labels.shape))
+    scale, s = float(scale), float(smooth)
+    if not (np.isfinite(s) and s > 0.0 and np.isfinite(scale) and scale >= 0.0):
+        raise ValueError("cldice_gradient: smooth must be finite and > 0, scale finite and >= 0")
+    y = (labels == 1).astype(np.float64)
+    m = (labels == 0) | (labels == 1)
+    E, amin, amax, d, S, r = _cldice_chain(p, k)
+    skel_p, skel_y = S[k], _cldice_chain(y, k)[4][-1]
+    A, Bp = float(np.sum(np.where(m, skel_p * y, 0.0))), float(np.sum(np.where(m, skel_p, 0.0)))
+    Cc, Dy = float(np.sum(np.where(m, skel_y * p, 0.0))), float(np.sum(np.where(m, skel_y, 0.0)))
+    own = np.array([A, Bp, Cc, Dy])
+    if sums is not None:
+        A, Bp, Cc, Dy = (float(v) for v in sums)
+    Tp, Ts = (A + s) / (Bp + s), (Cc + s) / (Dy + s)
+    dTp, dTs = 2.0 * Ts * Ts / (Tp + Ts) ** 2, 2.0 * Tp * Tp / (Tp + Ts) ** 2
+    gS = np.where(m, -scale * dTp * (y * (Bp + s) - (A + s)) / (Bp + s) ** 2, 0.0)
+    a = [None] * (k + 1)              # a_j: the gradient that reaches E_j - O_j through d_j
+    for j in range(k, 0, -1):
+        a[j] = np.where(r[j] & (d[j] > 0), gS * (1.0 - S[j - 1]), 0.0)
+        gS = np.where(r[j], gS * (1.0 - d[j]), gS)
+    a[0] = np.where(d[0] > 0, gS, 0.0)
+    gE = -_cldice_route(a[k], amax[k], _CLDICE_BOX)                    # wrt E_{k+1}
+    for j in range(k, -1, -1):
+        gE = a[j] + _cldice_route(gE, amin[j], _CLDICE_CROSS)
+        if j > 0:
+            gE = gE - _cldice_route(a[j - 1], amax[j - 1], _CLDICE_BOX)
+    gprob = np.where(m, gE - scale * dTs * skel_y / (Dy + s), 0.0)
+    return skel_p, skel_y, own, gprob

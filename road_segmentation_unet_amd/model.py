@@ -79,6 +79,12 @@ EXTRA_FLAG_DEFS = [
                                 "validation loss / objective are then the focal objective. The gradient shrinks with gamma (the loss stays "
                                 "normalised by the pixel count), so --lr needs retuning. It multiplies --class_weights, --border_weight and "
                                 "the weight map; --dice_weight adds to it unchanged"),
+    ("cldice_weight", float, 0.0, "lambda >= 0 of a clDice (centre-line Dice, Shit et al. 2021) term: loss += lambda * (1 - clD), clD over each "
+                                  "GPU's batch from the soft skeletons of the prediction and of the labels; 0 = off. It sees connectivity, "
+                                  "which no per-pixel or overlap term does. Ignored pixels add nothing to it; --class_weights, the weight "
+                                  "maps and --focal_gamma do not enter it"),
+    ("cldice_iters", int, 10, "Erosions k of the soft skeleton, an int in [0, 16]: at least the half-width, in pixels, of the widest road"),
+    ("cldice_smooth", float, 1.0, "Smoothing constant s > 0 of the clDice ratios (A + s) / (Bp + s) and (Cc + s) / (Dy + s)"),
     ("border_weight", float, 0.0, "w0 >= 0 of a border-distance weight map computed on the GPU from each batch's labels: a pixel counts "
                                   "1 + w0 * exp(-d^2 / (2 border_sigma^2)) times in the loss, d its distance to the other class inside its patch; "
                                   "0 = off (the U-Net paper uses 10). The loss stays normalised by the pixel count and the mean weight is above 1, "
@@ -210,6 +216,48 @@ def focal_loss_terms(p1, labels, gamma, class_weights=None, pixel_weights=None):
     F = np.power(p_o, gamma) if gamma > 0.0 else np.ones_like(p_o)
     terms = np.where(F == 0.0, 0.0, omega * F * ce)      # (p_t == 1: F = 0 and CE = 0)
     return float(terms.sum()), float(omega.sum())
+
+
+def parse_cldice_weight(value):
+    """The --cldice_weight value as a float: finite and >= 0 (0.0 = no clDice term). Anything else raises ValueError."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if isinstance(value, bool) or not (math.isfinite(v) and v >= 0.0):
+        raise ValueError("--cldice_weight must be a finite float >= 0, not %r" % (value,))
+    return v
+
+
+def parse_cldice_iters(value):
+    """The --cldice_iters value as an int in [0, 16] (rsu_cldice.h RSU_CLDICE_MAX_ITERS). Anything else raises ValueError."""
+    try:
+        v = int(value)
+        ok = not isinstance(value, bool) and v == (float(value) if not isinstance(value, str) else v) and 0 <= v <= 16
+    except (TypeError, ValueError):
+        v, ok = 0, False
+    if not ok:
+        raise ValueError("--cldice_iters must be an int in [0, 16], not %r" % (value,))
+    return v
+
+
+def parse_cldice_smooth(value):
+    """The --cldice_smooth value as a float: finite and > 0. Anything else raises ValueError."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if isinstance(value, bool) or not (math.isfinite(v) and v > 0.0):
+        raise ValueError("--cldice_smooth must be a finite float > 0, not %r" % (value,))
+    return v
+
+
+def cldice_from_sums(A, Bp, Cc, Dy, smooth):
+    """clD = 2 Tp Ts / (Tp + Ts) with Tp = (A + s) / (Bp + s), Ts = (Cc + s) / (Dy + s), from the sums A = sum m skel(p) y, Bp = sum m skel(p),
+    Cc = sum m skel(y) p, Dy = sum m skel(y) that rsu_cldice_fwd leaves in UNet.cldice_sums (rsu_cldice.h). Plain arithmetic: floats, numpy
+    arrays and tensors alike; empty sums give clD = 1."""
+    Tp, Ts = (A + smooth) / (Bp + smooth), (Cc + smooth) / (Dy + smooth)
+    return 2.0 * Tp * Ts / (Tp + Ts)
 
 
 def parse_dice_smooth(value):
@@ -505,6 +553,8 @@ class Options(object):
         self.class_weights = parse_class_weights(self.class_weights)   # None, (w0, w1) or "balanced" (cli.main resolves it)
         self.dice_weight, self.dice_smooth = parse_dice_weight(self.dice_weight), parse_dice_smooth(self.dice_smooth)
         self.focal_gamma = parse_focal_gamma(self.focal_gamma)
+        self.cldice_weight, self.cldice_iters = parse_cldice_weight(self.cldice_weight), parse_cldice_iters(self.cldice_iters)
+        self.cldice_smooth = parse_cldice_smooth(self.cldice_smooth)
         self.border_weight, self.border_sigma = parse_border_weight(self.border_weight), parse_border_sigma(self.border_sigma)
         self.clip_grad_norm = parse_clip_grad_norm(self.clip_grad_norm)
         self.ema_decay, self.ema_warmup = parse_ema_decay(self.ema_decay), bool(self.ema_warmup)
@@ -577,7 +627,9 @@ class ConvolutionalModel:
                         ema_decay=opts.ema_decay if opts.ema_decay > 0.0 else None, ema_warmup=opts.ema_warmup,
                         accumulate_steps=K if K > 1 else None,
                         weight_decay=opts.weight_decay if getattr(opts, "weight_decay", 0.0) > 0.0 else None,
-                        weight_decay_mode=getattr(opts, "weight_decay_mode", "decoupled"), focal_gamma=getattr(opts, "focal_gamma", 0.0))
+                        weight_decay_mode=getattr(opts, "weight_decay_mode", "decoupled"), focal_gamma=getattr(opts, "focal_gamma", 0.0),
+                        cldice_weight=getattr(opts, "cldice_weight", 0.0), cldice_iters=getattr(opts, "cldice_iters", 10),
+                        cldice_smooth=getattr(opts, "cldice_smooth", 1.0))
         self.net.dropout_seed = int(opts.seed) + 7919 * self.rank  # independent masks on every rank's shard
         # --lr_schedule: cosine | linear with --lr_total_steps=0 wait for resolve_lr_total_steps() (the patches are not known yet)
         self._lr_unresolved = getattr(opts, "lr_schedule", "staircase") in ("cosine", "linear") and getattr(opts, "lr_total_steps", 0) < 1
@@ -636,7 +688,8 @@ class ConvolutionalModel:
         class weights); None: no map, also after a step that had one. With class weights or a map the loss is the weighted sum over the
         GLOBAL pixel count (UNet.backward_device), and a label other than 0 and 1 then ignores its pixel: no loss, no gradient.
         With --dice_weight > 0 the returned loss is that cross-entropy + dice_weight * (1 - D), D the soft Dice of each rank's batch
-        (averaged over the ranks), and labels other than 0 and 1 are ignored as well.
+        (averaged over the ranks), and labels other than 0 and 1 are ignored as well. --cldice_weight > 0 adds
+        cldice_weight * (1 - clD) in the same way, clD the centre-line Dice of each rank's batch (rsu_cldice.h).
         With --accumulate_steps=K > 1 the three arrays hold the rank's whole share of the effective batch, [K*b, ...]: micro-batch j is
         rows [j*b, (j+1)*b), the step is ONE optimizer step, and the predictions come back as a new tensor [K*b,P,P].
         (Synchronous upload: the train() loop stages its batches one step ahead instead, see pool.BatchUploader.)"""
@@ -694,6 +747,7 @@ class ConvolutionalModel:
         # all-reduce of the gradients and of the loss below, and the sum over the micro-batches, then give the mean over all of them,
         # with no collective inside the backward pass
         dice_scale = net.dice_weight / (self.world * K)
+        cldice_scale = net.cldice_weight / (self.world * K)   # the clDice term likewise: each rank's, each micro-batch's own
         loss = None
         for micro in range(K):
             if load is not None and micro > 0:
@@ -702,12 +756,16 @@ class ConvolutionalModel:
             # feed_dict dropout_keep: opts.dropout (tf_aerial_images.py:237); the masks come from a counter-based hash of
             # (seed, rank, dropout site, global step, micro-batch, element) instead of TF's Philox stream
             net.forward_device(keep=float(opts.dropout))
-            net.backward_device(1.0 / (opts.batch_size * opts.patch_size * opts.patch_size), dice_scale=dice_scale)
+            net.backward_device(1.0 / (opts.batch_size * opts.patch_size * opts.patch_size), dice_scale=dice_scale,
+                                cldice_scale=cldice_scale)
             net.accumulate_gradients()   # (K == 1: nothing)
             part = net.loss_sum / (opts.batch_size * opts.patch_size * opts.patch_size)
             if dice_scale > 0.0:   # (device arithmetic on net.dice_sums: no synchronisation)
                 s = net.dice_sums
                 part = part + dice_scale * (1.0 - dice_from_sums(s[0:1], s[1:2], s[2:3], net.dice_smooth))
+            if cldice_scale > 0.0:   # (likewise on net.cldice_sums)
+                s = net.cldice_sums
+                part = part + cldice_scale * (1.0 - cldice_from_sums(s[0:1], s[1:2], s[2:3], s[3:4], net.cldice_smooth))
             loss = part if loss is None else loss + part
             if between is not None and micro < K - 1:
                 between(micro)
@@ -738,7 +796,9 @@ class ConvolutionalModel:
         zero patches whose labels are -1, which the head ignores: the padding adds exactly nothing -- through UNet.forward_device(keep=1)
         and UNet.evaluate_device (one rsu_head_eval launch per chunk). Everything accumulates on the device; the two accumulators are
         SUM-all-reduced (the sums as float64) and read back ONCE. Returns metrics_from_eval(...) of them, with the net's dice_weight /
-        dice_smooth, plus "sums" (float64 [5]) and "hist" (int64 [2, 256]).
+        dice_smooth, plus "sums" (float64 [5]) and "hist" (int64 [2, 256]), and "cldice_sums" (float64 [4]: {A, Bp, Cc, Dy} over the set,
+        all-reduced with the others; zeros with --cldice_weight=0) with "cldice" = cldice_from_sums of them; with --cldice_weight > 0
+        "objective" also includes cldice_weight * (1 - cldice).
         averaged: None scores the averaged weights when the net has them (--ema_decay), True demands them (ValueError on a net without),
         False forces the raw weights; the device work runs inside net.averaged_weights(), and the result carries "averaged" (bool).
         Training is left as it was: weights, the averages and every packed copy (the exchange of averaged_weights() is undone), optimizer
@@ -775,16 +835,24 @@ class ConvolutionalModel:
                     net.forward_device(keep=1.0)
                     net.evaluate_device()
                 sums, hist = net.eval_sums.to(torch.float64), net.eval_hist.clone()
+                with_cl = net.cldice_weight > 0.0
+                if with_cl:   # the four clDice sums ride behind the five of the head: one all-reduce, one read-back
+                    sums = torch.cat([sums, net.eval_cldice_sums.to(torch.float64)])
                 if self.world > 1:
                     dist.all_reduce(sums)
                     dist.all_reduce(hist)
                 sums, hist = sums.cpu().numpy(), hist.cpu().numpy()   # the one synchronisation
+                sums, cl_sums = sums[:5], (sums[5:] if with_cl else np.zeros(4))
         finally:
             net.x.copy_(x0)
             net.labels.copy_(l0)
             net.set_pixel_weights(pw0)
         out = metrics_from_eval(sums, hist, N * int(np.prod(labels.shape[1:])), net.dice_weight, net.dice_smooth, threshold)
         out["sums"], out["hist"], out["averaged"] = sums, hist, averaged
+        out["cldice_sums"] = cl_sums
+        out["cldice"] = float(cldice_from_sums(float(cl_sums[0]), float(cl_sums[1]), float(cl_sums[2]), float(cl_sums[3]), net.cldice_smooth))
+        if with_cl:
+            out["objective"] = out["objective"] + net.cldice_weight * (1.0 - out["cldice"])
         return out
 
     def _validate(self, validation, step):
@@ -799,11 +867,13 @@ class ConvolutionalModel:
             if self._summary is not None:
                 self._summary.add({"val_loss": v["loss"], "val_objective": v["objective"], "val_dice": v["dice"], "val_f1": v["f1"],
                                    "val_iou": v["iou"], "val_best_threshold": v["best_threshold"]}, global_step=step)
+                if opts.cldice_weight > 0.0:
+                    self._summary.add({"val_cldice": v["cldice"]}, global_step=step)
         if self.best_val_f1 is None or v["f1"] > self.best_val_f1:   # (the same numbers on every rank: they come out of the all-reduce)
             self.best_val_f1 = v["f1"]
             if opts.save_best:
                 self.save_as(os.path.abspath(os.path.join(opts.save_path, self.experiment_name + "-best.chkpt")))
-        return {k: v[k] for k in v if k not in ("sums", "hist")}
+        return {k: v[k] for k in v if k not in ("sums", "hist", "cldice_sums")}
 
     def _ensure_summary(self):
         opts = self._options

@@ -100,7 +100,7 @@ class UNet(OptimizerStep):
     def __init__(self, num_layers, root_size, dilated_layers, batch_size, patch_size, device="cuda:0", params=None, seed=2017,
                  training=True, optimizer="momentum", class_weights=None, dice_weight=0.0, dice_smooth=1.0, border_weight=0.0, border_sigma=5.0,
                  clip_grad_norm=None, ema_decay=None, ema_warmup=True, accumulate_steps=None, weight_decay=None, weight_decay_mode="decoupled",
-                 focal_gamma=0.0):
+                 focal_gamma=0.0, cldice_weight=0.0, cldice_iters=10, cldice_smooth=1.0):
         """optimizer: "momentum" (the reference's MomentumOptimizer: apply_momentum) or "adam" (tf.train.AdamOptimizer: apply_adam; a
         second fp32 slot per variable, flat_v).
         class_weights: None or a pair (w0, w1) of finite floats >= 0, not both 0: the weighted cross-entropy of rsu.h
@@ -140,6 +140,12 @@ class UNet(OptimizerStep):
         eval_sums[0] are then sum omega F CE. It multiplies the class weights, the weight map and the border map; the Dice term is added
         to it unchanged; inv_count stays 1 / pixel count, so the gradient shrinks. Labels other than 0 / 1 are ignored, as in every
         weighted pass. 0.0: the passes issue exactly the launches they always did.
+        cldice_weight: lambda >= 0 of the clDice (centre-line Dice) term, objective += lambda (1 - clD) (rsu_cldice.h): the soft skeletons of
+        prob and of the label map by cldice_iters (0 .. 16) erosions, cldice_smooth > 0 the term's smoothing constant. With lambda > 0
+        backward_device runs the head as pass A, rsu_cldice_fwd, rsu_cldice_bwd and rsu_head_fwd_bwd_aux (see there), evaluate_device adds
+        one rsu_cldice_fwd into eval_cldice_sums, and the net owns cldice_sums (f32[4] {A, Bp, Cc, Dy}), eval_cldice_sums, the two
+        skeleton maps, gprob and the term's workspace. Class weights, the weight map, the border map and the focal factor do not enter
+        the term. 0.0: no buffer, no launch, the passes are what they always were. Training nets only.
         The learning-rate curve is set_lr_schedule()'s; the default is the reference's staircase."""
         self._init_optimizer(training, optimizer, clip_grad_norm, ema_decay, ema_warmup, accumulate_steps, weight_decay, weight_decay_mode)
         assert root_size % 8 == 0 and (root_size // 8) & (root_size // 8 - 1) == 0, "root_size must be 8 * 2^k for the HIP path"
@@ -154,6 +160,10 @@ class UNet(OptimizerStep):
         self.pixel_weights = None            # the weight map [B, P, P] float32 on the device, or None (set_pixel_weights)
         self.dice_weight, self.dice_smooth = dice_weight, dice_smooth   # (properties: validated)
         self.focal_gamma = focal_gamma       # (a property: validated)
+        self.cldice_weight, self.cldice_iters, self.cldice_smooth = cldice_weight, cldice_iters, cldice_smooth   # (properties: validated)
+        if self._cldice_weight > 0.0 and not training:
+            raise _lib.RsuError("a forward-only net has no loss to add a clDice term to")
+        self.cldice_sums = self.eval_cldice_sums = self.skel_p = self.skel_y = self.gprob = self._cldice_ws = None
         self.border_weight, self.border_sigma = self._border_args(border_weight, border_sigma)
         self.border_map = None               # the generated weight map [B, P, P] float32 (derived from labels per pass), with border_weight > 0
         self.keep = 1.0        # dropout keep probability of the forward pass in flight (set by forward_device)
@@ -216,6 +226,65 @@ class UNet(OptimizerStep):
         if not (math.isfinite(v) and v >= 0.0):
             raise _lib.RsuError("focal_gamma must be a finite float >= 0")
         self._focal_gamma = v
+
+    @property
+    def cldice_weight(self):
+        """lambda of the clDice term: the default cldice_scale of backward_device (0.0: no such term)"""
+        return self._cldice_weight
+
+    @cldice_weight.setter
+    def cldice_weight(self, v):
+        try:
+            v = float(v)
+        except (TypeError, ValueError):
+            v = float("nan")
+        if not (math.isfinite(v) and v >= 0.0):
+            raise _lib.RsuError("cldice_weight must be a finite float >= 0")
+        self._cldice_weight = v
+
+    @property
+    def cldice_iters(self):
+        """k: the erosions of the soft skeleton (rsu_cldice.h), an int in [0, 16]"""
+        return self._cldice_iters
+
+    @cldice_iters.setter
+    def cldice_iters(self, v):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= _lib.CLDICE_MAX_ITERS:
+            raise _lib.RsuError("cldice_iters must be an int in [0, %d]" % _lib.CLDICE_MAX_ITERS)
+        self._cldice_iters = int(v)
+
+    @property
+    def cldice_smooth(self):
+        """the smoothing constant s of Tp = (A + s) / (Bp + s), Ts = (Cc + s) / (Dy + s)"""
+        return self._cldice_smooth
+
+    @cldice_smooth.setter
+    def cldice_smooth(self, v):
+        try:
+            v = float(v)
+        except (TypeError, ValueError):
+            v = float("nan")
+        if not (math.isfinite(v) and v > 0.0):
+            raise _lib.RsuError("cldice_smooth must be a finite float > 0")
+        self._cldice_smooth = v
+
+    def _cldice_buffers(self):
+        """the term's device buffers, made when a pass first needs them (in __init__ with cldice_weight > 0): the sums of the training
+        and of the evaluation pass, the skeletons of prob and of the labels, gprob = d term / d prob, and the workspace the forward
+        leaves for the backward (rsu_cldice_ws_floats; it grows with cldice_iters)"""
+        need = int(_lib.lib().rsu_cldice_ws_floats(self.B, self.P, self.P, self._cldice_iters))
+        if self.cldice_sums is None:
+            dev = self.device
+            self.cldice_sums = torch.zeros(4, dtype=torch.float32, device=dev)
+            self.eval_cldice_sums = torch.zeros(4, dtype=torch.float32, device=dev)
+            self.skel_p, self.skel_y, self.gprob = (torch.zeros((self.B, self.P, self.P), dtype=torch.float32, device=dev) for _ in range(3))
+        if self._cldice_ws is None or self._cldice_ws.numel() < need:
+            self._cldice_ws = torch.zeros(need, dtype=torch.float32, device=self.device)
+
+    def _cldice_fwd(self, sums):
+        """rsu_cldice_fwd of self.prob / self.labels on the current stream: the skeletons, and sums += {A, Bp, Cc, Dy}"""
+        call("rsu_cldice_fwd", _ptr(self.prob), _ptr(self.labels), self._cldice_iters, _ptr(self.skel_p), _ptr(self.skel_y), _ptr(sums),
+             _ptr(self._cldice_ws), self.B, self.P, self.P, self._stream())
 
     @property
     def dice_smooth(self):
@@ -428,6 +497,8 @@ class UNet(OptimizerStep):
             # (one workspace per stream that launches weight gradients: their slabs are live at the same time)
             self.sched.ws_side = [self.ws] + [torch.zeros_like(self.ws) for _ in self.wstreams[1:]]
             self.gfirst = torch.zeros((2, 9, 12, self.root), dtype=torch.float32, device=dev)  # gx of conv1 / atrous_conv1 (rsu.h)
+            if self._cldice_weight > 0.0:
+                self._cldice_buffers()
             if self.border_weight > 0.0:   # the generated weight map and the column distances between its two launches (rsu.h rsu_border_map)
                 self.border_map = torch.zeros((B, self.P, self.P), dtype=torch.float32, device=dev)
                 self._border_ws = torch.zeros(int(lib.rsu_border_map_ws_bytes(B, self.P, self.P)) // 4, dtype=torch.int32, device=dev)
@@ -659,6 +730,8 @@ class UNet(OptimizerStep):
         """zero the validation accumulators eval_sums / eval_hist (on the current stream)"""
         self.eval_sums.zero_()
         self.eval_hist.zero_()
+        if self.eval_cldice_sums is not None:
+            self.eval_cldice_sums.zero_()
 
     def evaluate_device(self):
         """The forward-only loss and metric counts of self.x / self.labels, for data the optimizer does not see: ONE rsu_head_eval launch
@@ -666,7 +739,8 @@ class UNet(OptimizerStep):
         eval_sums (f32[5]) += {sum omega CE, sum omega, I, P, Y} -- omega and the sums as backward_device defines them, with this net's
         class weights and weight map -- and to eval_hist (int64 [2, 256]): hist[label][min(255, int(p * 256))] += 1 for every pixel whose
         label is 0 or 1; any other label ignores its pixel. No gradient buffer, loss_sum, weight_sum or dice_sums is written, and nothing
-        is read back: a caller sums a whole set on the device (reset_eval first) and synchronises once. ensure_tuned(training=False)
+        is read back: a caller sums a whole set on the device (reset_eval first) and synchronises once. With cldice_weight > 0 one
+        rsu_cldice_fwd (rsu_cldice.h) follows the head: eval_cldice_sums (f32[4]) += {A, Bp, Cc, Dy} of this batch. ensure_tuned(training=False)
         belongs in front of the first such forward pass: at keep == 1 the encoder takes the fused conv + pool launches, whose tuning
         keys differ from a dropout step's."""
         if not self.training:
@@ -677,10 +751,13 @@ class UNet(OptimizerStep):
             call("rsu_head_eval_focal", _ptr(self.act[self.last_name]), _ptr(self.w["weight_output/kernel"]), _ptr(self.w["weight_output/bias"]),
                  _ptr(self.labels), _ptr(self._class_w_dev), _ptr(self._head_pixel_weights()), self._focal_gamma, _ptr(self.prob),
                  _ptr(self.eval_sums), _ptr(self.eval_hist), _ptr(self.ws), self.B * self.P * self.P, self.root, self._stream())
-            return
-        call("rsu_head_eval", _ptr(self.act[self.last_name]), _ptr(self.w["weight_output/kernel"]), _ptr(self.w["weight_output/bias"]),
-             _ptr(self.labels), _ptr(self._class_w_dev), _ptr(self._head_pixel_weights()), _ptr(self.prob), _ptr(self.eval_sums), _ptr(self.eval_hist),
-             _ptr(self.ws), self.B * self.P * self.P, self.root, self._stream())
+        else:
+            call("rsu_head_eval", _ptr(self.act[self.last_name]), _ptr(self.w["weight_output/kernel"]), _ptr(self.w["weight_output/bias"]),
+                 _ptr(self.labels), _ptr(self._class_w_dev), _ptr(self._head_pixel_weights()), _ptr(self.prob), _ptr(self.eval_sums),
+                 _ptr(self.eval_hist), _ptr(self.ws), self.B * self.P * self.P, self.root, self._stream())
+        if self._cldice_weight > 0.0:
+            self._cldice_buffers()
+            self._cldice_fwd(self.eval_cldice_sums)
 
     # ------------------------------------------------------------------ backward
     def _wgrad(self, name, srcs_t, dz, hout, dil=1, block_done=False):
@@ -738,7 +815,7 @@ class UNet(OptimizerStep):
                     _ptr(self.pk[name + "/kernel", "bwd", src_index]), _ptr(dx), _ptr(relu_src), accumulate, self.B, hin, hin, cnt, 0, cnt,
                     cout, dil, self.sched.ncu(), _ptr(kws), kws.numel() if kws is not None else 0, self._stream())
 
-    def backward_device(self, inv_count, update=None, dice_scale=None):
+    def backward_device(self, inv_count, update=None, dice_scale=None, cldice_scale=None):
         """loss + all gradients for self.x / self.labels; forward_device() must have run. inv_count = 1 / (global pixel count).
         The loss is the reference's mean softmax cross-entropy unless class weights other than (1, 1) or a weight map are set
         (class_weights, set_pixel_weights): then pixel p counts omega_p = class_weights[label_p] * pixel_weights[p] times in loss_sum and
@@ -753,6 +830,12 @@ class UNet(OptimizerStep):
         dice_weight / world. With dice_scale == 0 the pass is exactly the one described above.
         focal_gamma > 0 takes the focal head instead (rsu_loss.h rsu_head_fwd_bwd_focal): omega F CE per counted pixel in loss_sum and its
         gradient, F = (1 - p_t)^gamma; weight_sum, the Dice term and inv_count as above.
+        cldice_scale (None: self.cldice_weight) > 0 adds cldice_scale * (1 - clD) of THIS net's batch (rsu_cldice.h). The head then runs as:
+        pass A, which writes prob (rsu_head_dice_sums when the Dice term is on too, otherwise rsu_head_fwd); cldice_sums zeroed on the stream;
+        rsu_cldice_fwd (skel_p, skel_y, cldice_sums); rsu_cldice_bwd (gprob = d term / d prob); rsu_head_fwd_bwd_aux with this net's gamma, Dice
+        term and weights, which carries gprob to the logits. No host synchronisation; loss_sum and weight_sum stay the cross-entropy part,
+        the term's value is cldice_scale * (1 - clD) with clD from cldice_sums. A data-parallel host passes cldice_weight / world. With
+        cldice_scale == 0 the pass issues exactly the launches described above.
         update = (lr0, momentum): accepted from callers that name the Momentum step they will take; it changes nothing here -- the step
         is apply_momentum's -- but a net built with another optimizer refuses it."""
         self._not_averaged("backward_device")
@@ -762,10 +845,13 @@ class UNet(OptimizerStep):
         dice_scale = self._dice_weight if dice_scale is None else float(dice_scale)
         if not (math.isfinite(dice_scale) and dice_scale >= 0.0):
             raise _lib.RsuError("dice_scale must be a finite float >= 0, not %r" % (dice_scale,))
+        cldice_scale = self._cldice_weight if cldice_scale is None else float(cldice_scale)
+        if not (math.isfinite(cldice_scale) and cldice_scale >= 0.0):
+            raise _lib.RsuError("cldice_scale must be a finite float >= 0, not %r" % (cldice_scale,))
         st = self._stream()
         self.sched.begin(self.backward_cu_budget)
         try:
-            self._backward_body(inv_count, dice_scale)
+            self._backward_body(inv_count, dice_scale, cldice_scale)
         finally:
             self.sched.end()   # (an exception inside must not leave later launches planned for a share of the chip)
         # ---- color_space_adjust (unet.py:22-23): its input gradient is never materialised (include/rsu.h, rsu_conv_first_bwd_weight):
@@ -777,13 +863,32 @@ class UNet(OptimizerStep):
             call("rsu_color_adjust_bwd", _ptr(self.gfirst[1]), _ptr(self.w["conv_dilut_0/atrous_conv1/kernel"]), _ptr(gk), _ptr(gb), self.root,
                  inv_keep, 1, st)
 
-    def _backward_body(self, inv_count, dice_scale=0.0):
+    def _backward_body(self, inv_count, dice_scale=0.0, cldice_scale=0.0):
         B, L, st, a, g = self.B, self.L, self._stream(), self.act, self.grad
         keep = self.keep
         last = a[self.last_name]
         self._loss_acc.zero_()
         pixel_w = self._head_pixel_weights()
-        if self._focal_gamma > 0.0:
+        if cldice_scale > 0.0:
+            # the clDice term (rsu_cldice.h): pass A writes prob, the fused skeleton forward and backward turn it into gprob, the aux head
+            # carries gprob to the logits next to the cross-entropy (focal with gamma > 0) and the Dice term
+            head = (_ptr(last), _ptr(self.w["weight_output/kernel"]), _ptr(self.w["weight_output/bias"]))
+            npix = B * self.P * self.P
+            self._cldice_buffers()
+            if dice_scale > 0.0:
+                call("rsu_head_dice_sums", *head, _ptr(self.labels), _ptr(pixel_w), _ptr(self.prob), _ptr(self.dice_sums), _ptr(self.ws), npix,
+                     self.root, st)
+            else:
+                call("rsu_head_fwd", *head, _ptr(self.prob), None, npix, self.root, st)
+            self.cldice_sums.zero_()
+            self._cldice_fwd(self.cldice_sums)
+            call("rsu_cldice_bwd", _ptr(self.prob), _ptr(self.labels), _ptr(self.skel_p), _ptr(self.skel_y), _ptr(self.cldice_sums),
+                 self._cldice_iters, cldice_scale, self._cldice_smooth, _ptr(self.gprob), _ptr(self._cldice_ws), B, self.P, self.P, st)
+            call("rsu_head_fwd_bwd_aux", *head, _ptr(self.labels), _ptr(self._class_w_dev), _ptr(pixel_w), self._focal_gamma,
+                 _ptr(self.dice_sums) if dice_scale > 0.0 else None, dice_scale, self._dice_smooth, _ptr(self.prob), _ptr(self.loss_sum),
+                 _ptr(self.weight_sum), _ptr(g[self.last_name]), _ptr(self.g["weight_output/kernel"]), _ptr(self.g["weight_output/bias"]),
+                 _ptr(self.ws), npix, self.root, inv_count, _ptr(self.gprob), st)
+        elif self._focal_gamma > 0.0:
             # the focal head (rsu_loss.h): the weighted head's arguments and gamma; with a Dice term pass B behind an unchanged pass A
             head = (_ptr(last), _ptr(self.w["weight_output/kernel"]), _ptr(self.w["weight_output/bias"]), _ptr(self.labels))
             npix = B * self.P * self.P
