@@ -1,4 +1,5 @@
-"""ctypes binding of librsu_hip.so (the C ABI of include/rsu.h, include/rsu_optim.h, include/rsu_loss.h and include/rsu_cldice.h).
+"""ctypes binding of librsu_hip.so (the C ABI of include/rsu.h, include/rsu_optim.h, include/rsu_loss.h, include/rsu_cldice.h and
+include/rsu_lovasz.h).
 
 The library is REQUIRED: there is no CPU or eager-PyTorch fallback anywhere in this package. If the
 shared object is missing or a symbol cannot be resolved, importing/using the product path raises."""
@@ -172,6 +173,13 @@ SIGNATURES_CLDICE = {
     "rsu_head_fwd_bwd_aux": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _f, _vp, _vp]),
 }
 
+# and for include/rsu_lovasz.h, the fifth (the Lovasz term: a per-image device-side sort, the loss and its gradient wrt prob)
+SIGNATURES_LOVASZ = {
+    "rsu_lovasz_ws_bytes": (_sz, [_i, _i, _i]),
+    "rsu_lovasz_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "rsu_lovasz_fwd_bwd": (_i, [_vp, _vp, _f, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
+}
+
 _lib = None
 
 
@@ -188,7 +196,7 @@ def lib():
                            "or `make -C road_segmentation_unet_amd/csrc`); there is no fallback path" % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_OPTIM.items()) + list(SIGNATURES_LOSS.items()) \
-                + list(SIGNATURES_CLDICE.items()):
+                + list(SIGNATURES_CLDICE.items()) + list(SIGNATURES_LOVASZ.items()):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

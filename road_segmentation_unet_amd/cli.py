@@ -72,6 +72,10 @@ def main(argv=None):
         print("clDice term: lambda {:g}, {} erosions, smooth {:g}; the logged loss and the validation objective include lambda * (1 - clD)"
               .format(opts.cldice_weight, opts.cldice_iters, opts.cldice_smooth))
 
+    if opts.lovasz_weight > 0.0:
+        print("Lovasz term: lambda {:g}; the logged loss and the validation objective include lambda * the mean per-image Lovasz "
+              "(Jaccard surrogate) loss".format(opts.lovasz_weight))
+
     if opts.restore_model:
         if opts.model_path is not None:
             model.restore(file=opts.model_path)

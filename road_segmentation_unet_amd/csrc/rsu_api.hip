@@ -16,12 +16,14 @@
 #include "../../include/rsu_optim.h"
 #include "../../include/rsu_loss.h"
 #include "../../include/rsu_cldice.h"
+#include "../../include/rsu_lovasz.h"
 #include "affine_patches.h"
 #include "color_jitter.h"
 #include "border_map.h"
 #include "elementwise.h"
 #include "loss.h"
 #include "cldice.h"
+#include "lovasz.h"
 #include "optim.h"
 #include "igemm.h"
 
@@ -1590,6 +1592,23 @@ extern "C" int rsu_head_fwd_bwd_aux(const void* act, const float* w, const float
     if (!dice_sums) dice_scale = smooth = 0.f;   // (not looked at)
     HIP_CHECK_RET(cl_head_aux(act, w, b, labels, class_w, pixel_w, gamma, dice_sums, dice_scale, smooth, gprob, prob, dact, dw, db, loss_sum,
                               weight_sum, ws, npix, C, inv_count, (hipStream_t)stream));
+    return RSU_OK;
+}
+// ---- the Lovasz term (rsu_lovasz.h): a per-image bitonic sort of the errors, the Jaccard differences along the ranks, loss and gradient
+static bool lovasz_size_ok(int B, int H, int W) {
+    return B >= 1 && H >= 1 && W >= 1 && (long)H * W <= LV_MAX_PIXELS && (long)B * H * W < (1l << 31);
+}
+extern "C" size_t rsu_lovasz_ws_bytes(int B, int H, int W) { return lovasz_size_ok(B, H, W) ? lv_ws_bytes(B, H, W) : 0; }
+extern "C" int rsu_lovasz_fwd(const float* prob, const int64_t* labels, float* loss_sum, void* ws, int B, int H, int W, rsu_stream_t stream) {
+    if (!prob || !labels || !loss_sum || !ws || !lovasz_size_ok(B, H, W)) return RSU_EINVAL;
+    HIP_CHECK_RET(lv_run(prob, labels, 0.f, 0, nullptr, loss_sum, ws, B, H, W, (hipStream_t)stream));
+    return RSU_OK;
+}
+extern "C" int rsu_lovasz_fwd_bwd(const float* prob, const int64_t* labels, float scale, int accumulate, float* gprob, float* loss_sum, void* ws,
+                                  int B, int H, int W, rsu_stream_t stream) {
+    if (!prob || !labels || !gprob || !loss_sum || !ws || !lovasz_size_ok(B, H, W)) return RSU_EINVAL;
+    if (!std::isfinite(scale) || !(scale >= 0.f)) return RSU_EINVAL;
+    HIP_CHECK_RET(lv_run(prob, labels, scale / (float)B, accumulate, gprob, loss_sum, ws, B, H, W, (hipStream_t)stream));
     return RSU_OK;
 }
 static_assert(RSU_BORDER_MAX_SIDE == BM_MAX_SIDE, "rsu.h and border_map.h must agree on the supported tile size");

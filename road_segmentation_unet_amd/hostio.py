@@ -702,3 +702,73 @@ def cldice_gradient(prob, labels, iters, scale, smooth, sums=None):
             gE = gE - _cldice_route(a[j - 1], amax[j - 1], _CLDICE_BOX)
     gprob = np.where(m, gE - scale * dTs * skel_y / (Dy + s), 0.0)
     return skel_p, skel_y, own, gprob
+
+
+# ---- Lovasz: the Jaccard surrogate on the host (include/rsu_lovasz.h)
+LOVASZ_MAX_PIXELS = 1 << 24   # rsu_lovasz.h: H * W
+
+
+def _lovasz_image(p, lab):
+    """one image, flat: (loss float32, g float32 per pixel with its sign and 0 at ignored pixels) -- the operations of rsu_lovasz.h, one
+    float32 rounding each"""
+    f32 = np.float32
+    counted = (lab == 0) | (lab == 1)
+    idx = np.nonzero(counted)[0]
+    g_pix = np.zeros(p.shape, f32)
+    n = idx.size
+    if n == 0:
+        return f32(0), g_pix
+    y = lab[idx].astype(np.int64)
+    with np.errstate(invalid="ignore"):
+        e = np.abs(y.astype(f32) - p[idx])
+    # descending by the unsigned pattern, ties by ascending pixel index: a stable ascending sort of the complemented pattern
+    order = np.argsort(~e.view(np.uint32), kind="stable")
+    ys = y[order]
+    G = int(ys.sum())
+    c = np.cumsum(ys)
+    k = np.arange(1, n + 1, dtype=np.int64)
+    J = f32(1) - (G - c).astype(f32) / (G + k - c).astype(f32)
+    g = J - np.concatenate([np.zeros(1, f32), J[:-1]])
+    with np.errstate(invalid="ignore", over="ignore"):
+        loss = np.sum(e[order] * g, dtype=f32)
+    g_pix[idx[order]] = np.where(ys == 1, -g, g)
+    return f32(loss), g_pix
+
+
+def _lovasz_args(prob, labels):
+    p = np.ascontiguousarray(prob, np.float32)
+    labels = np.asarray(labels)
+    if p.ndim != 3 or labels.shape != p.shape:
+        raise ValueError("lovasz: prob and labels [B, H, W], not %r and %r" % (p.shape, labels.shape))
+    if p.shape[1] * p.shape[2] > LOVASZ_MAX_PIXELS or min(p.shape) < 1:
+        raise ValueError("lovasz: 1 <= H * W <= 2^24 and B >= 1, not shape %r" % (p.shape,))
+    return p, labels.astype(np.int64)
+
+
+def lovasz_loss(prob, labels):
+    """The per-image Lovasz losses L_b of include/rsu_lovasz.h, float32 [B], from float32 probabilities [B, H, W] and int64 labels: the
+    errors |y - p| of the pixels whose label is 0 or 1, ranked by their unsigned bit pattern descending (ties: ascending pixel index),
+    times the differences of the Jaccard loss along the ranks. The products are summed by numpy's float32 pairwise sum; the kernels'
+    order differs (rsu_lovasz.h), so the two agree within the bound of a float32 sum, not in bits."""
+    p, labels = _lovasz_args(prob, labels)
+    return np.array([_lovasz_image(p[b].reshape(-1), labels[b].reshape(-1))[0] for b in range(p.shape[0])], np.float32)
+
+
+def lovasz_gradient(prob, labels, scale, into=None):
+    """d (scale / B sum_b L_b) / d prob of include/rsu_lovasz.h in numpy float32, equal to rsu_lovasz_fwd_bwd's gprob bit for bit:
+    c = f32(scale) / f32(B), c * g_{r(i)} negated where y = 1, +0 at pixels whose label is neither 0 nor 1 (their p is not looked at).
+    into: None, or a float32 array [B, H, W] the gradient is added to (one rounding), as accumulate != 0 does; it is not modified."""
+    p, labels = _lovasz_args(prob, labels)
+    scale = np.float32(scale)
+    if not (np.isfinite(scale) and scale >= 0):
+        raise ValueError("lovasz_gradient: scale must be finite and >= 0")
+    c = scale / np.float32(p.shape[0])
+    out = np.empty(p.shape, np.float32)
+    for b in range(p.shape[0]):
+        out[b] = (c * _lovasz_image(p[b].reshape(-1), labels[b].reshape(-1))[1]).reshape(p.shape[1:])
+    if into is not None:
+        into = np.asarray(into, np.float32)
+        if into.shape != p.shape:
+            raise ValueError("lovasz_gradient: into must have prob's shape")
+        out = into + out
+    return out

@@ -85,6 +85,10 @@ EXTRA_FLAG_DEFS = [
                                   "maps and --focal_gamma do not enter it"),
     ("cldice_iters", int, 10, "Erosions k of the soft skeleton, an int in [0, 16]: at least the half-width, in pixels, of the widest road"),
     ("cldice_smooth", float, 1.0, "Smoothing constant s > 0 of the clDice ratios (A + s) / (Bp + s) and (Cc + s) / (Dy + s)"),
+    ("lovasz_weight", float, 0.0, "lambda >= 0 of a Lovasz (Jaccard surrogate, Berman et al. 2018) term: loss += lambda * the mean over the "
+                                  "images of the per-image Lovasz loss of |label - p|, a convex surrogate of 1 - IoU; 0 = off. A mean of "
+                                  "per-image losses: data-parallel and accumulated steps give the objective of one large batch. Ignored "
+                                  "pixels add nothing to it; --class_weights, the weight maps and --focal_gamma do not enter it"),
     ("border_weight", float, 0.0, "w0 >= 0 of a border-distance weight map computed on the GPU from each batch's labels: a pixel counts "
                                   "1 + w0 * exp(-d^2 / (2 border_sigma^2)) times in the loss, d its distance to the other class inside its patch; "
                                   "0 = off (the U-Net paper uses 10). The loss stays normalised by the pixel count and the mean weight is above 1, "
@@ -226,6 +230,17 @@ def parse_cldice_weight(value):
         v = float("nan")
     if isinstance(value, bool) or not (math.isfinite(v) and v >= 0.0):
         raise ValueError("--cldice_weight must be a finite float >= 0, not %r" % (value,))
+    return v
+
+
+def parse_lovasz_weight(value):
+    """The --lovasz_weight value as a float: finite and >= 0 (0.0 = no Lovasz term). Anything else raises ValueError."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if isinstance(value, bool) or not (math.isfinite(v) and v >= 0.0):
+        raise ValueError("--lovasz_weight must be a finite float >= 0, not %r" % (value,))
     return v
 
 
@@ -555,6 +570,7 @@ class Options(object):
         self.focal_gamma = parse_focal_gamma(self.focal_gamma)
         self.cldice_weight, self.cldice_iters = parse_cldice_weight(self.cldice_weight), parse_cldice_iters(self.cldice_iters)
         self.cldice_smooth = parse_cldice_smooth(self.cldice_smooth)
+        self.lovasz_weight = parse_lovasz_weight(self.lovasz_weight)
         self.border_weight, self.border_sigma = parse_border_weight(self.border_weight), parse_border_sigma(self.border_sigma)
         self.clip_grad_norm = parse_clip_grad_norm(self.clip_grad_norm)
         self.ema_decay, self.ema_warmup = parse_ema_decay(self.ema_decay), bool(self.ema_warmup)
@@ -629,7 +645,7 @@ class ConvolutionalModel:
                         weight_decay=opts.weight_decay if getattr(opts, "weight_decay", 0.0) > 0.0 else None,
                         weight_decay_mode=getattr(opts, "weight_decay_mode", "decoupled"), focal_gamma=getattr(opts, "focal_gamma", 0.0),
                         cldice_weight=getattr(opts, "cldice_weight", 0.0), cldice_iters=getattr(opts, "cldice_iters", 10),
-                        cldice_smooth=getattr(opts, "cldice_smooth", 1.0))
+                        cldice_smooth=getattr(opts, "cldice_smooth", 1.0), lovasz_weight=getattr(opts, "lovasz_weight", 0.0))
         self.net.dropout_seed = int(opts.seed) + 7919 * self.rank  # independent masks on every rank's shard
         # --lr_schedule: cosine | linear with --lr_total_steps=0 wait for resolve_lr_total_steps() (the patches are not known yet)
         self._lr_unresolved = getattr(opts, "lr_schedule", "staircase") in ("cosine", "linear") and getattr(opts, "lr_total_steps", 0) < 1
@@ -689,7 +705,8 @@ class ConvolutionalModel:
         GLOBAL pixel count (UNet.backward_device), and a label other than 0 and 1 then ignores its pixel: no loss, no gradient.
         With --dice_weight > 0 the returned loss is that cross-entropy + dice_weight * (1 - D), D the soft Dice of each rank's batch
         (averaged over the ranks), and labels other than 0 and 1 are ignored as well. --cldice_weight > 0 adds
-        cldice_weight * (1 - clD) in the same way, clD the centre-line Dice of each rank's batch (rsu_cldice.h).
+        cldice_weight * (1 - clD) in the same way, clD the centre-line Dice of each rank's batch (rsu_cldice.h). --lovasz_weight > 0 adds
+        lovasz_weight * the mean per-image Lovasz loss (rsu_lovasz.h) over every image of the step.
         With --accumulate_steps=K > 1 the three arrays hold the rank's whole share of the effective batch, [K*b, ...]: micro-batch j is
         rows [j*b, (j+1)*b), the step is ONE optimizer step, and the predictions come back as a new tensor [K*b,P,P].
         (Synchronous upload: the train() loop stages its batches one step ahead instead, see pool.BatchUploader.)"""
@@ -748,6 +765,7 @@ class ConvolutionalModel:
         # with no collective inside the backward pass
         dice_scale = net.dice_weight / (self.world * K)
         cldice_scale = net.cldice_weight / (self.world * K)   # the clDice term likewise: each rank's, each micro-batch's own
+        lovasz_scale = net.lovasz_weight / (self.world * K)   # a mean of per-image losses: with this the step's objective is one large batch's
         loss = None
         for micro in range(K):
             if load is not None and micro > 0:
@@ -757,7 +775,7 @@ class ConvolutionalModel:
             # (seed, rank, dropout site, global step, micro-batch, element) instead of TF's Philox stream
             net.forward_device(keep=float(opts.dropout))
             net.backward_device(1.0 / (opts.batch_size * opts.patch_size * opts.patch_size), dice_scale=dice_scale,
-                                cldice_scale=cldice_scale)
+                                cldice_scale=cldice_scale, lovasz_scale=lovasz_scale)
             net.accumulate_gradients()   # (K == 1: nothing)
             part = net.loss_sum / (opts.batch_size * opts.patch_size * opts.patch_size)
             if dice_scale > 0.0:   # (device arithmetic on net.dice_sums: no synchronisation)
@@ -766,6 +784,9 @@ class ConvolutionalModel:
             if cldice_scale > 0.0:   # (likewise on net.cldice_sums)
                 s = net.cldice_sums
                 part = part + cldice_scale * (1.0 - cldice_from_sums(s[0:1], s[1:2], s[2:3], s[3:4], net.cldice_smooth))
+            if lovasz_scale > 0.0:   # (likewise on net.lovasz_sum = {sum_b L_b, images})
+                s = net.lovasz_sum
+                part = part + lovasz_scale * s[0:1] / s[1:2]
             loss = part if loss is None else loss + part
             if between is not None and micro < K - 1:
                 between(micro)
@@ -798,7 +819,9 @@ class ConvolutionalModel:
         SUM-all-reduced (the sums as float64) and read back ONCE. Returns metrics_from_eval(...) of them, with the net's dice_weight /
         dice_smooth, plus "sums" (float64 [5]) and "hist" (int64 [2, 256]), and "cldice_sums" (float64 [4]: {A, Bp, Cc, Dy} over the set,
         all-reduced with the others; zeros with --cldice_weight=0) with "cldice" = cldice_from_sums of them; with --cldice_weight > 0
-        "objective" also includes cldice_weight * (1 - cldice).
+        "objective" also includes cldice_weight * (1 - cldice). With --lovasz_weight > 0 (only then) also "lovasz", the mean per-image
+        Lovasz loss over the set from the all-reduced {sum_b L_b, images} less the padding images (which add exactly 0), and
+        "objective" includes lovasz_weight * lovasz.
         averaged: None scores the averaged weights when the net has them (--ema_decay), True demands them (ValueError on a net without),
         False forces the raw weights; the device work runs inside net.averaged_weights(), and the result carries "averaged" (bool).
         Training is left as it was: weights, the averages and every packed copy (the exchange of averaged_weights() is undone), optimizer
@@ -838,11 +861,15 @@ class ConvolutionalModel:
                 with_cl = net.cldice_weight > 0.0
                 if with_cl:   # the four clDice sums ride behind the five of the head: one all-reduce, one read-back
                     sums = torch.cat([sums, net.eval_cldice_sums.to(torch.float64)])
+                with_lv = net.lovasz_weight > 0.0
+                if with_lv:   # and the Lovasz pair {sum_b L_b, images} last
+                    sums = torch.cat([sums, net.eval_lovasz_sum.to(torch.float64)])
                 if self.world > 1:
                     dist.all_reduce(sums)
                     dist.all_reduce(hist)
                 sums, hist = sums.cpu().numpy(), hist.cpu().numpy()   # the one synchronisation
-                sums, cl_sums = sums[:5], (sums[5:] if with_cl else np.zeros(4))
+                lv_sums = sums[-2:] if with_lv else None
+                sums, cl_sums = sums[:5], (sums[5:9] if with_cl else np.zeros(4))
         finally:
             net.x.copy_(x0)
             net.labels.copy_(l0)
@@ -853,6 +880,9 @@ class ConvolutionalModel:
         out["cldice"] = float(cldice_from_sums(float(cl_sums[0]), float(cl_sums[1]), float(cl_sums[2]), float(cl_sums[3]), net.cldice_smooth))
         if with_cl:
             out["objective"] = out["objective"] + net.cldice_weight * (1.0 - out["cldice"])
+        if with_lv:   # the mean over the set's N images: the chunks' padding images have no counted pixel, L_b = 0
+            out["lovasz"] = float(lv_sums[0]) / max(N, 1)
+            out["objective"] = out["objective"] + net.lovasz_weight * out["lovasz"]
         return out
 
     def _validate(self, validation, step):
@@ -869,6 +899,8 @@ class ConvolutionalModel:
                                    "val_iou": v["iou"], "val_best_threshold": v["best_threshold"]}, global_step=step)
                 if opts.cldice_weight > 0.0:
                     self._summary.add({"val_cldice": v["cldice"]}, global_step=step)
+                if opts.lovasz_weight > 0.0:
+                    self._summary.add({"val_lovasz": v["lovasz"]}, global_step=step)
         if self.best_val_f1 is None or v["f1"] > self.best_val_f1:   # (the same numbers on every rank: they come out of the all-reduce)
             self.best_val_f1 = v["f1"]
             if opts.save_best:

@@ -100,7 +100,7 @@ class UNet(OptimizerStep):
     def __init__(self, num_layers, root_size, dilated_layers, batch_size, patch_size, device="cuda:0", params=None, seed=2017,
                  training=True, optimizer="momentum", class_weights=None, dice_weight=0.0, dice_smooth=1.0, border_weight=0.0, border_sigma=5.0,
                  clip_grad_norm=None, ema_decay=None, ema_warmup=True, accumulate_steps=None, weight_decay=None, weight_decay_mode="decoupled",
-                 focal_gamma=0.0, cldice_weight=0.0, cldice_iters=10, cldice_smooth=1.0):
+                 focal_gamma=0.0, cldice_weight=0.0, cldice_iters=10, cldice_smooth=1.0, lovasz_weight=0.0):
         """optimizer: "momentum" (the reference's MomentumOptimizer: apply_momentum) or "adam" (tf.train.AdamOptimizer: apply_adam; a
         second fp32 slot per variable, flat_v).
         class_weights: None or a pair (w0, w1) of finite floats >= 0, not both 0: the weighted cross-entropy of rsu.h
@@ -146,6 +146,11 @@ class UNet(OptimizerStep):
         one rsu_cldice_fwd into eval_cldice_sums, and the net owns cldice_sums (f32[4] {A, Bp, Cc, Dy}), eval_cldice_sums, the two
         skeleton maps, gprob and the term's workspace. Class weights, the weight map, the border map and the focal factor do not enter
         the term. 0.0: no buffer, no launch, the passes are what they always were. Training nets only.
+        lovasz_weight: lambda >= 0 of the Lovasz (Jaccard surrogate) term, objective += lambda * the mean over the batch's images of the
+        per-image Lovasz loss (rsu_lovasz.h). With lambda > 0 backward_device runs the head as pass A, rsu_lovasz_fwd_bwd and
+        rsu_head_fwd_bwd_aux (see there), evaluate_device adds one rsu_lovasz_fwd into eval_lovasz_sum, and the net owns lovasz_sum
+        (f32[2] {sum_b L_b, images}), eval_lovasz_sum, gprob (shared with the clDice term) and the sort's workspace. Weights and the focal
+        factor do not enter the term. 0.0: no buffer, no launch. Training nets only.
         The learning-rate curve is set_lr_schedule()'s; the default is the reference's staircase."""
         self._init_optimizer(training, optimizer, clip_grad_norm, ema_decay, ema_warmup, accumulate_steps, weight_decay, weight_decay_mode)
         assert root_size % 8 == 0 and (root_size // 8) & (root_size // 8 - 1) == 0, "root_size must be 8 * 2^k for the HIP path"
@@ -164,6 +169,10 @@ class UNet(OptimizerStep):
         if self._cldice_weight > 0.0 and not training:
             raise _lib.RsuError("a forward-only net has no loss to add a clDice term to")
         self.cldice_sums = self.eval_cldice_sums = self.skel_p = self.skel_y = self.gprob = self._cldice_ws = None
+        self.lovasz_weight = lovasz_weight   # (a property: validated)
+        if self._lovasz_weight > 0.0 and not training:
+            raise _lib.RsuError("a forward-only net has no loss to add a Lovasz term to")
+        self.lovasz_sum = self.eval_lovasz_sum = self._lovasz_ws = None
         self.border_weight, self.border_sigma = self._border_args(border_weight, border_sigma)
         self.border_map = None               # the generated weight map [B, P, P] float32 (derived from labels per pass), with border_weight > 0
         self.keep = 1.0        # dropout keep probability of the forward pass in flight (set by forward_device)
@@ -277,7 +286,9 @@ class UNet(OptimizerStep):
             dev = self.device
             self.cldice_sums = torch.zeros(4, dtype=torch.float32, device=dev)
             self.eval_cldice_sums = torch.zeros(4, dtype=torch.float32, device=dev)
-            self.skel_p, self.skel_y, self.gprob = (torch.zeros((self.B, self.P, self.P), dtype=torch.float32, device=dev) for _ in range(3))
+            self.skel_p, self.skel_y = (torch.zeros((self.B, self.P, self.P), dtype=torch.float32, device=dev) for _ in range(2))
+        if self.gprob is None:
+            self.gprob = torch.zeros((self.B, self.P, self.P), dtype=torch.float32, device=self.device)
         if self._cldice_ws is None or self._cldice_ws.numel() < need:
             self._cldice_ws = torch.zeros(need, dtype=torch.float32, device=self.device)
 
@@ -285,6 +296,35 @@ class UNet(OptimizerStep):
         """rsu_cldice_fwd of self.prob / self.labels on the current stream: the skeletons, and sums += {A, Bp, Cc, Dy}"""
         call("rsu_cldice_fwd", _ptr(self.prob), _ptr(self.labels), self._cldice_iters, _ptr(self.skel_p), _ptr(self.skel_y), _ptr(sums),
              _ptr(self._cldice_ws), self.B, self.P, self.P, self._stream())
+
+    @property
+    def lovasz_weight(self):
+        """lambda of the Lovasz term: the default lovasz_scale of backward_device (0.0: no such term)"""
+        return self._lovasz_weight
+
+    @lovasz_weight.setter
+    def lovasz_weight(self, v):
+        try:
+            v = float(v)
+        except (TypeError, ValueError):
+            v = float("nan")
+        if not (math.isfinite(v) and v >= 0.0):
+            raise _lib.RsuError("lovasz_weight must be a finite float >= 0")
+        self._lovasz_weight = v
+
+    def _lovasz_buffers(self):
+        """the term's device buffers, made when a pass first needs them (in __init__ with lovasz_weight > 0): {sum_b L_b, images} of the
+        training and of the evaluation pass, gprob (the clDice term's, if that made it first) and the sort's workspace"""
+        if self.lovasz_sum is None:
+            dev = self.device
+            self.lovasz_sum = torch.zeros(2, dtype=torch.float32, device=dev)
+            self.eval_lovasz_sum = torch.zeros(2, dtype=torch.float32, device=dev)
+            need = int(_lib.lib().rsu_lovasz_ws_bytes(self.B, self.P, self.P))
+            if need == 0:
+                raise _lib.RsuError("the Lovasz term takes patches of at most 2^24 pixels")
+            self._lovasz_ws = torch.zeros(need // 4, dtype=torch.int32, device=dev)
+        if self.gprob is None:
+            self.gprob = torch.zeros((self.B, self.P, self.P), dtype=torch.float32, device=self.device)
 
     @property
     def dice_smooth(self):
@@ -499,6 +539,8 @@ class UNet(OptimizerStep):
             self.gfirst = torch.zeros((2, 9, 12, self.root), dtype=torch.float32, device=dev)  # gx of conv1 / atrous_conv1 (rsu.h)
             if self._cldice_weight > 0.0:
                 self._cldice_buffers()
+            if self._lovasz_weight > 0.0:
+                self._lovasz_buffers()
             if self.border_weight > 0.0:   # the generated weight map and the column distances between its two launches (rsu.h rsu_border_map)
                 self.border_map = torch.zeros((B, self.P, self.P), dtype=torch.float32, device=dev)
                 self._border_ws = torch.zeros(int(lib.rsu_border_map_ws_bytes(B, self.P, self.P)) // 4, dtype=torch.int32, device=dev)
@@ -732,6 +774,8 @@ class UNet(OptimizerStep):
         self.eval_hist.zero_()
         if self.eval_cldice_sums is not None:
             self.eval_cldice_sums.zero_()
+        if self.eval_lovasz_sum is not None:
+            self.eval_lovasz_sum.zero_()
 
     def evaluate_device(self):
         """The forward-only loss and metric counts of self.x / self.labels, for data the optimizer does not see: ONE rsu_head_eval launch
@@ -740,7 +784,8 @@ class UNet(OptimizerStep):
         class weights and weight map -- and to eval_hist (int64 [2, 256]): hist[label][min(255, int(p * 256))] += 1 for every pixel whose
         label is 0 or 1; any other label ignores its pixel. No gradient buffer, loss_sum, weight_sum or dice_sums is written, and nothing
         is read back: a caller sums a whole set on the device (reset_eval first) and synchronises once. With cldice_weight > 0 one
-        rsu_cldice_fwd (rsu_cldice.h) follows the head: eval_cldice_sums (f32[4]) += {A, Bp, Cc, Dy} of this batch. ensure_tuned(training=False)
+        rsu_cldice_fwd (rsu_cldice.h) follows the head: eval_cldice_sums (f32[4]) += {A, Bp, Cc, Dy} of this batch; with
+        lovasz_weight > 0 one rsu_lovasz_fwd (rsu_lovasz.h): eval_lovasz_sum (f32[2]) += {sum_b L_b, images}. ensure_tuned(training=False)
         belongs in front of the first such forward pass: at keep == 1 the encoder takes the fused conv + pool launches, whose tuning
         keys differ from a dropout step's."""
         if not self.training:
@@ -758,6 +803,10 @@ class UNet(OptimizerStep):
         if self._cldice_weight > 0.0:
             self._cldice_buffers()
             self._cldice_fwd(self.eval_cldice_sums)
+        if self._lovasz_weight > 0.0:
+            self._lovasz_buffers()
+            call("rsu_lovasz_fwd", _ptr(self.prob), _ptr(self.labels), _ptr(self.eval_lovasz_sum), _ptr(self._lovasz_ws), self.B, self.P,
+                 self.P, self._stream())
 
     # ------------------------------------------------------------------ backward
     def _wgrad(self, name, srcs_t, dz, hout, dil=1, block_done=False):
@@ -815,7 +864,7 @@ class UNet(OptimizerStep):
                     _ptr(self.pk[name + "/kernel", "bwd", src_index]), _ptr(dx), _ptr(relu_src), accumulate, self.B, hin, hin, cnt, 0, cnt,
                     cout, dil, self.sched.ncu(), _ptr(kws), kws.numel() if kws is not None else 0, self._stream())
 
-    def backward_device(self, inv_count, update=None, dice_scale=None, cldice_scale=None):
+    def backward_device(self, inv_count, update=None, dice_scale=None, cldice_scale=None, lovasz_scale=None):
         """loss + all gradients for self.x / self.labels; forward_device() must have run. inv_count = 1 / (global pixel count).
         The loss is the reference's mean softmax cross-entropy unless class weights other than (1, 1) or a weight map are set
         (class_weights, set_pixel_weights): then pixel p counts omega_p = class_weights[label_p] * pixel_weights[p] times in loss_sum and
@@ -836,6 +885,12 @@ class UNet(OptimizerStep):
         term and weights, which carries gprob to the logits. No host synchronisation; loss_sum and weight_sum stay the cross-entropy part,
         the term's value is cldice_scale * (1 - clD) with clD from cldice_sums. A data-parallel host passes cldice_weight / world. With
         cldice_scale == 0 the pass issues exactly the launches described above.
+        lovasz_scale (None: self.lovasz_weight) > 0 adds lovasz_scale * (1 / B) sum_b L_b, L_b the Lovasz loss of image b of THIS net's
+        batch (rsu_lovasz.h). The head then runs as: pass A as above; the clDice launches, if that term is on, which write gprob; lovasz_sum
+        zeroed on the stream; rsu_lovasz_fwd_bwd (lovasz_sum += {sum_b L_b, B}; gprob accumulated if clDice wrote it, otherwise
+        overwritten); rsu_head_fwd_bwd_aux. No host synchronisation; the term's value is lovasz_scale * lovasz_sum[0] / lovasz_sum[1]. A
+        mean of per-image losses: a data-parallel or accumulating host passes lovasz_weight / (world * micro-batches) and gets the
+        objective of one large batch. With lovasz_scale == 0 the pass issues exactly the launches described above.
         update = (lr0, momentum): accepted from callers that name the Momentum step they will take; it changes nothing here -- the step
         is apply_momentum's -- but a net built with another optimizer refuses it."""
         self._not_averaged("backward_device")
@@ -848,10 +903,13 @@ class UNet(OptimizerStep):
         cldice_scale = self._cldice_weight if cldice_scale is None else float(cldice_scale)
         if not (math.isfinite(cldice_scale) and cldice_scale >= 0.0):
             raise _lib.RsuError("cldice_scale must be a finite float >= 0, not %r" % (cldice_scale,))
+        lovasz_scale = self._lovasz_weight if lovasz_scale is None else float(lovasz_scale)
+        if not (math.isfinite(lovasz_scale) and lovasz_scale >= 0.0):
+            raise _lib.RsuError("lovasz_scale must be a finite float >= 0, not %r" % (lovasz_scale,))
         st = self._stream()
         self.sched.begin(self.backward_cu_budget)
         try:
-            self._backward_body(inv_count, dice_scale, cldice_scale)
+            self._backward_body(inv_count, dice_scale, cldice_scale, lovasz_scale)
         finally:
             self.sched.end()   # (an exception inside must not leave later launches planned for a share of the chip)
         # ---- color_space_adjust (unet.py:22-23): its input gradient is never materialised (include/rsu.h, rsu_conv_first_bwd_weight):
@@ -863,27 +921,36 @@ class UNet(OptimizerStep):
             call("rsu_color_adjust_bwd", _ptr(self.gfirst[1]), _ptr(self.w["conv_dilut_0/atrous_conv1/kernel"]), _ptr(gk), _ptr(gb), self.root,
                  inv_keep, 1, st)
 
-    def _backward_body(self, inv_count, dice_scale=0.0, cldice_scale=0.0):
+    def _backward_body(self, inv_count, dice_scale=0.0, cldice_scale=0.0, lovasz_scale=0.0):
         B, L, st, a, g = self.B, self.L, self._stream(), self.act, self.grad
         keep = self.keep
         last = a[self.last_name]
         self._loss_acc.zero_()
         pixel_w = self._head_pixel_weights()
-        if cldice_scale > 0.0:
-            # the clDice term (rsu_cldice.h): pass A writes prob, the fused skeleton forward and backward turn it into gprob, the aux head
-            # carries gprob to the logits next to the cross-entropy (focal with gamma > 0) and the Dice term
+        if cldice_scale > 0.0 or lovasz_scale > 0.0:
+            # the terms with a gradient wrt prob: pass A writes prob; the clDice term (rsu_cldice.h: the fused skeleton forward and backward)
+            # and the Lovasz term (rsu_lovasz.h: the sort and the Jaccard differences) turn it into gprob, the second adding to the first;
+            # the aux head carries gprob to the logits next to the cross-entropy (focal with gamma > 0) and the Dice term
             head = (_ptr(last), _ptr(self.w["weight_output/kernel"]), _ptr(self.w["weight_output/bias"]))
             npix = B * self.P * self.P
-            self._cldice_buffers()
+            if cldice_scale > 0.0:
+                self._cldice_buffers()
+            if lovasz_scale > 0.0:
+                self._lovasz_buffers()
             if dice_scale > 0.0:
                 call("rsu_head_dice_sums", *head, _ptr(self.labels), _ptr(pixel_w), _ptr(self.prob), _ptr(self.dice_sums), _ptr(self.ws), npix,
                      self.root, st)
             else:
                 call("rsu_head_fwd", *head, _ptr(self.prob), None, npix, self.root, st)
-            self.cldice_sums.zero_()
-            self._cldice_fwd(self.cldice_sums)
-            call("rsu_cldice_bwd", _ptr(self.prob), _ptr(self.labels), _ptr(self.skel_p), _ptr(self.skel_y), _ptr(self.cldice_sums),
-                 self._cldice_iters, cldice_scale, self._cldice_smooth, _ptr(self.gprob), _ptr(self._cldice_ws), B, self.P, self.P, st)
+            if cldice_scale > 0.0:
+                self.cldice_sums.zero_()
+                self._cldice_fwd(self.cldice_sums)
+                call("rsu_cldice_bwd", _ptr(self.prob), _ptr(self.labels), _ptr(self.skel_p), _ptr(self.skel_y), _ptr(self.cldice_sums),
+                     self._cldice_iters, cldice_scale, self._cldice_smooth, _ptr(self.gprob), _ptr(self._cldice_ws), B, self.P, self.P, st)
+            if lovasz_scale > 0.0:
+                self.lovasz_sum.zero_()
+                call("rsu_lovasz_fwd_bwd", _ptr(self.prob), _ptr(self.labels), lovasz_scale, 1 if cldice_scale > 0.0 else 0, _ptr(self.gprob),
+                     _ptr(self.lovasz_sum), _ptr(self._lovasz_ws), B, self.P, self.P, st)
             call("rsu_head_fwd_bwd_aux", *head, _ptr(self.labels), _ptr(self._class_w_dev), _ptr(pixel_w), self._focal_gamma,
                  _ptr(self.dice_sums) if dice_scale > 0.0 else None, dice_scale, self._dice_smooth, _ptr(self.prob), _ptr(self.loss_sum),
                  _ptr(self.weight_sum), _ptr(g[self.last_name]), _ptr(self.g["weight_output/kernel"]), _ptr(self.g["weight_output/bias"]),
