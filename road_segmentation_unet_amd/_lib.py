@@ -1,5 +1,5 @@
-"""ctypes binding of librsu_hip.so (the C ABI of include/rsu.h, include/rsu_optim.h, include/rsu_loss.h, include/rsu_cldice.h and
-include/rsu_lovasz.h).
+"""ctypes binding of librsu_hip.so (the C ABI of include/rsu.h, include/rsu_optim.h, include/rsu_loss.h, include/rsu_cldice.h,
+include/rsu_lovasz.h and include/rsu_components.h).
 
 The library is REQUIRED: there is no CPU or eager-PyTorch fallback anywhere in this package. If the
 shared object is missing or a symbol cannot be resolved, importing/using the product path raises."""
@@ -180,6 +180,14 @@ SIGNATURES_LOVASZ = {
     "rsu_lovasz_fwd_bwd": (_i, [_vp, _vp, _f, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
 }
 
+# and for include/rsu_components.h, the sixth (connected components: labelling, the mask clean-up, the connectivity count)
+SIGNATURES_COMPONENTS = {
+    "rsu_components_ws_bytes": (_sz, [_i, _i, _i]),
+    "rsu_components_label": (_i, [_vp, _f, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "rsu_components_filter": (_i, [_vp, _f, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "rsu_components_pair_count": (_i, [_vp, _f, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
+}
+
 _lib = None
 
 
@@ -196,7 +204,7 @@ def lib():
                            "or `make -C road_segmentation_unet_amd/csrc`); there is no fallback path" % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_OPTIM.items()) + list(SIGNATURES_LOSS.items()) \
-                + list(SIGNATURES_CLDICE.items()) + list(SIGNATURES_LOVASZ.items()):
+                + list(SIGNATURES_CLDICE.items()) + list(SIGNATURES_LOVASZ.items()) + list(SIGNATURES_COMPONENTS.items()):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

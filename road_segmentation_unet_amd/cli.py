@@ -31,6 +31,15 @@ def parse_options(argv=None):
     return Options(**vars(ns))
 
 
+def _clean_up(model, masks, threshold, rank):
+    """--min_road_area / --max_hole_area between prediction and quantisation: postprocess_masks and one line with the summed stats"""
+    masks = model.postprocess_masks(masks, threshold=threshold)
+    stats = model.last_postprocess_stats
+    if stats is not None and rank == 0:
+        print("Mask clean-up: {} components, {} removed ({} pixels); {} holes, {} filled ({} pixels)".format(*[int(v) for v in stats]))
+    return masks
+
+
 def main(argv=None):
     import torch
     import torch.distributed as dist
@@ -75,6 +84,10 @@ def main(argv=None):
     if opts.lovasz_weight > 0.0:
         print("Lovasz term: lambda {:g}; the logged loss and the validation objective include lambda * the mean per-image Lovasz "
               "(Jaccard surrogate) loss".format(opts.lovasz_weight))
+
+    if opts.min_road_area > 0 or opts.max_hole_area > 0:
+        print("Mask clean-up: road components below {} pixels removed ({}-connected), holes of at most {} pixels filled, before the masks "
+              "are quantised".format(opts.min_road_area, opts.component_connectivity, opts.max_hole_area))
 
     if opts.restore_model:
         if opts.model_path is not None:
@@ -132,7 +145,7 @@ def main(argv=None):
         # reference writes them, its "eval_orror" included, so that its downstream scripts keep finding them)
         print("Evaluate Test")
         eval_images, eval_groundtruth = hostio.load_train_data(opts.train_data_dir)
-        probabilities = model.predict_batchwise(eval_images, opts.pred_batch_size)
+        probabilities = _clean_up(model, model.predict_batchwise(eval_images, opts.pred_batch_size), 0.5, rank)
         if rank == 0:
             binary = ((probabilities > 0.5) * 1).squeeze(-1)
             dumps = (
@@ -151,6 +164,7 @@ def main(argv=None):
         start = time.time()
         masks = model.predict_batchwise(eval_images, opts.pred_batch_size)
         print("Prediction time:{} mins".format((time.time() - start) / 60))
+        masks = _clean_up(model, masks, 0.5, rank)   # (quantize_mask binarises at 0.5 before it averages a block)
         masks = model.quantize_mask(masks, patch_size=hostio.IMG_PATCH_SIZE, threshold=hostio.FOREGROUND_THRESHOLD)
         if rank == 0:
             save_dir = os.path.abspath(os.path.join(opts.save_path, model.experiment_name))

@@ -17,6 +17,7 @@
 #include "../../include/rsu_loss.h"
 #include "../../include/rsu_cldice.h"
 #include "../../include/rsu_lovasz.h"
+#include "../../include/rsu_components.h"
 #include "affine_patches.h"
 #include "color_jitter.h"
 #include "border_map.h"
@@ -24,6 +25,7 @@
 #include "loss.h"
 #include "cldice.h"
 #include "lovasz.h"
+#include "components.h"
 #include "optim.h"
 #include "igemm.h"
 
@@ -1609,6 +1611,31 @@ extern "C" int rsu_lovasz_fwd_bwd(const float* prob, const int64_t* labels, floa
     if (!prob || !labels || !gprob || !loss_sum || !ws || !lovasz_size_ok(B, H, W)) return RSU_EINVAL;
     if (!std::isfinite(scale) || !(scale >= 0.f)) return RSU_EINVAL;
     HIP_CHECK_RET(lv_run(prob, labels, scale / (float)B, accumulate, gprob, loss_sum, ws, B, H, W, (hipStream_t)stream));
+    return RSU_OK;
+}
+// ---- connected components (rsu_components.h): tile union-find in LDS, hierarchical border merges, flatten, gather
+static bool components_size_ok(int N, int H, int W) {
+    return N >= 1 && H >= 1 && W >= 1 && (long)H * W <= CC_MAX_PIXELS && (long)N * H * W < (1l << 31);
+}
+static bool components_args_ok(float threshold, int connectivity) { return std::isfinite(threshold) && (connectivity == 4 || connectivity == 8); }
+extern "C" size_t rsu_components_ws_bytes(int N, int H, int W) { return components_size_ok(N, H, W) ? cc_ws_bytes(N, H, W) : 0; }
+extern "C" int rsu_components_label(const float* prob, float threshold, int connectivity, int invert, int32_t* labels, int32_t* area,
+                                    uint8_t* edge, void* ws, int N, int H, int W, rsu_stream_t stream) {
+    if (!prob || !labels || !ws || !components_size_ok(N, H, W) || !components_args_ok(threshold, connectivity)) return RSU_EINVAL;
+    HIP_CHECK_RET(cc_label(prob, threshold, connectivity, invert, labels, area, edge, ws, N, H, W, (hipStream_t)stream));
+    return RSU_OK;
+}
+extern "C" int rsu_components_filter(const float* prob, float threshold, int connectivity, int min_area, int max_hole, float* out,
+                                     int64_t* stats, void* ws, int N, int H, int W, rsu_stream_t stream) {
+    if (!prob || !out || !ws || !components_size_ok(N, H, W) || !components_args_ok(threshold, connectivity)) return RSU_EINVAL;
+    if (min_area < 0 || max_hole < 0) return RSU_EINVAL;
+    HIP_CHECK_RET(cc_filter(prob, threshold, connectivity, min_area, max_hole, out, stats, ws, N, H, W, (hipStream_t)stream));
+    return RSU_OK;
+}
+extern "C" int rsu_components_pair_count(const float* prob, float threshold, const int64_t* labels64, int connectivity,
+                                         unsigned long long* acc, void* ws, int N, int H, int W, rsu_stream_t stream) {
+    if (!prob || !labels64 || !acc || !ws || !components_size_ok(N, H, W) || !components_args_ok(threshold, connectivity)) return RSU_EINVAL;
+    HIP_CHECK_RET(cc_pair_count(prob, threshold, labels64, connectivity, acc, ws, N, H, W, (hipStream_t)stream));
     return RSU_OK;
 }
 static_assert(RSU_BORDER_MAX_SIDE == BM_MAX_SIDE, "rsu.h and border_map.h must agree on the supported tile size");

@@ -772,3 +772,253 @@ def lovasz_gradient(prob, labels, scale, into=None):
             raise ValueError("lovasz_gradient: into must have prob's shape")
         out = into + out
     return out
+
+
+# ---- connected components on the host (include/rsu_components.h)
+COMPONENTS_MAX_PIXELS = 1 << 24   # rsu_components.h: H * W
+COMPONENTS_TILE = 64              # components.h CC_TILE
+
+
+def _cc_check(prob, threshold, connectivity):
+    p = np.ascontiguousarray(prob, np.float32)
+    if p.ndim != 3 or min(p.shape) < 1 or p.shape[1] * p.shape[2] > COMPONENTS_MAX_PIXELS or p.size >= 1 << 31:
+        raise ValueError("components: prob [N, H, W] with N, H, W >= 1, H * W <= 2^24 and N * H * W < 2^31, not shape %r" % (p.shape,))
+    t = np.float32(threshold)
+    if not np.isfinite(t):
+        raise ValueError("components: threshold must be finite, not %r" % (threshold,))
+    if isinstance(connectivity, bool) or connectivity not in (4, 8):
+        raise ValueError("components: connectivity must be 4 or 8, not %r" % (connectivity,))
+    return p, t
+
+
+def _cc_foreground(p, t):
+    """p >= threshold as one float32 comparison: NaN is background, p == threshold is foreground"""
+    with np.errstate(invalid="ignore"):
+        return p >= t
+
+
+def _cc_offsets(connectivity):
+    return [(0, 1), (1, 0)] + ([(1, 1), (1, -1)] if connectivity == 8 else [])
+
+
+def _cc_labels(fg, connectivity):
+    """labels int32 [H, W] of one mask: 1 + the smallest row-major index of the pixel's component, 0 at background. A union-find on
+    whole arrays: every pixel takes the smallest parent among itself and its neighbours (union), hangs its root under it (link by smaller
+    index, np.minimum.at: the order of the updates is immaterial), then every pixel jumps to its root (find / flatten); parents only
+    decrease, and the loop ends when a round changes nothing -- then neighbours share a root, and a root is the smallest index it can
+    reach."""
+    H, W = fg.shape
+    n = H * W
+    flat = fg.reshape(-1)
+    idx = np.nonzero(flat)[0]
+    par = np.full(n + 1, n, np.int64)       # background, and the sentinel n, point at n
+    par[idx] = idx
+    pad = np.full((H + 2, W + 2), n, np.int64)
+    nb = [(dy, dx) for dy, dx in _cc_offsets(connectivity)] + [(-dy, -dx) for dy, dx in _cc_offsets(connectivity)]
+    while idx.size:
+        pad[1:-1, 1:-1] = par[:n].reshape(H, W)
+        m = pad[1:-1, 1:-1].copy()
+        for dy, dx in nb:
+            np.minimum(m, pad[1 + dy:1 + dy + H, 1 + dx:1 + dx + W], out=m)
+        m = m.reshape(-1)[idx]
+        new = par.copy()
+        np.minimum.at(new, par[idx], m)
+        new[idx] = np.minimum(new[idx], m)
+        while True:
+            jumped = new[new]
+            if np.array_equal(jumped, new):
+                break
+            new = jumped
+        if np.array_equal(new, par):
+            break
+        par = new
+    return np.where(flat, par[:n] + 1, 0).astype(np.int32).reshape(H, W)
+
+
+def _cc_area_edge(labels):
+    """(area int32, edge uint8) per pixel from the labels of one image"""
+    H, W = labels.shape
+    flat = labels.reshape(-1)
+    counts = np.bincount(flat, minlength=H * W + 1)
+    counts[0] = 0
+    touches = np.zeros(H * W + 1, bool)
+    for line in (labels[0], labels[-1], labels[:, 0], labels[:, -1]):
+        touches[line] = True
+    touches[0] = False
+    return counts[flat].astype(np.int32).reshape(H, W), touches[flat].astype(np.uint8).reshape(H, W)
+
+
+def label_components(prob, threshold, connectivity, invert=False):
+    """rsu_components_label on the host: (labels int32, area int32, edge uint8), each [N, H, W], of the mask p >= threshold (invert: of
+    its complement, NaN included) at connectivity 4 or 8; every image on its own."""
+    p, t = _cc_check(prob, threshold, connectivity)
+    fg = _cc_foreground(p, t)
+    if invert:
+        fg = ~fg
+    labels = np.stack([_cc_labels(fg[n], connectivity) for n in range(p.shape[0])])
+    ae = [_cc_area_edge(labels[n]) for n in range(p.shape[0])]
+    return labels, np.stack([a for a, _ in ae]), np.stack([e for _, e in ae])
+
+
+def filter_components(prob, threshold, connectivity, min_area, max_hole):
+    """rsu_components_filter on the host: (out float32 [N, H, W], stats int64 [N, 6]) -- components of fewer than min_area pixels removed
+    (+0), then the holes (components of the complement at the dual connectivity that touch no image edge) of at most max_hole pixels
+    filled (1), every other pixel with the bits it had; stats = {components, components removed, pixels removed, holes, holes filled,
+    pixels filled} per image, a skipped step's three fields 0."""
+    p, t = _cc_check(prob, threshold, connectivity)
+    for name, v in (("min_area", min_area), ("max_hole", max_hole)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise ValueError("components: %s must be an integer >= 0, not %r" % (name, v))
+    N = p.shape[0]
+    f1 = _cc_foreground(p, t)
+    removed, filled = np.zeros(p.shape, bool), np.zeros(p.shape, bool)
+    stats = np.zeros((N, 6), np.int64)
+    for n in range(N):
+        if min_area > 1:
+            lab = _cc_labels(f1[n], connectivity)
+            area, _ = _cc_area_edge(lab)
+            removed[n] = (lab > 0) & (area < min_area)
+            roots = lab.reshape(-1) == np.arange(1, lab.size + 1)
+            stats[n, 0:3] = roots.sum(), (roots & removed[n].reshape(-1)).sum(), removed[n].sum()
+        if max_hole > 0:
+            lab = _cc_labels(~(f1[n] & ~removed[n]), 4 if connectivity == 8 else 8)
+            area, edge = _cc_area_edge(lab)
+            hole = (lab > 0) & (edge == 0)
+            filled[n] = hole & (area <= max_hole)
+            roots = lab.reshape(-1) == np.arange(1, lab.size + 1)
+            stats[n, 3:6] = (roots & hole.reshape(-1)).sum(), (roots & filled[n].reshape(-1)).sum(), filled[n].sum()
+    bits = p.view(np.uint32).copy()
+    bits[removed] = 0
+    bits[filled] = 0x3f800000
+    return bits.view(np.float32), stats
+
+
+def components_pair_count(prob, threshold, labels, connectivity):
+    """rsu_components_pair_count on the host: int64 [4] = {sum cp, sum cy, sum |cp - cy|, images with a counted pixel}; cp the components of
+    {label in {0, 1} and p >= threshold}, cy those of {label == 1}, per image."""
+    p, t = _cc_check(prob, threshold, connectivity)
+    labels = np.asarray(labels).astype(np.int64)
+    if labels.shape != p.shape:
+        raise ValueError("components: labels must have prob's shape")
+    counted = (labels == 0) | (labels == 1)
+    pred = counted & _cc_foreground(p, t)
+    acc = np.zeros(4, np.int64)
+    for n in range(p.shape[0]):
+        cp = len(np.unique(_cc_labels(pred[n], connectivity))) - (0 if pred[n].all() else 1)
+        cy = len(np.unique(_cc_labels(labels[n] == 1, connectivity))) - (0 if (labels[n] == 1).all() else 1)
+        acc += (cp, cy, abs(cp - cy), int(counted[n].any()))
+    return acc
+
+
+def label_components_tiled(mask, connectivity, tile=COMPONENTS_TILE):
+    """The steps of csrc/components.hip on one boolean mask [H, W], serially and in plain Python (slow: for tests): per tile every pixel
+    starts at its horizontal run's first pixel and the runs are united with the row above, leaving out the pairs a neighbour of the same
+    run makes; the tile roots become image indices with a tile area and edge flag each; at level m the pairs across the two new inner
+    borders of every 2^m x 2^m group of tiles are united (link the larger root under the smaller); then every pixel walks to its root
+    and the tile roots add their area and edge flag to it. Returns (labels, area, edge, levels)."""
+    mask = np.asarray(mask, bool)
+    H, W = mask.shape
+    T = int(tile)
+    par = np.zeros(H * W, np.int64)          # parent index + 1, 0 = background
+    ta = np.zeros(H * W, np.int64)
+    tedge = np.zeros(H * W, bool)
+
+    def find(p, i, off):
+        while p[i] - off != i:
+            i = p[i] - off
+        return i
+
+    def union(p, a, b, off):
+        a, b = find(p, a, off), find(p, b, off)
+        if a != b:
+            p[max(a, b)] = min(a, b) + off
+
+    ty_n, tx_n = -(-H // T), -(-W // T)
+    for ty in range(ty_n):
+        for tx in range(tx_n):
+            y0, x0 = ty * T, tx * T
+            f = np.zeros((T, T), bool)
+            sub = mask[y0:y0 + T, x0:x0 + T]
+            f[:sub.shape[0], :sub.shape[1]] = sub
+            lp = np.full(T * T, -1, np.int64)
+            for r in range(T):
+                start = 0
+                for c in range(T):
+                    if not f[r, c]:
+                        start = c + 1
+                    else:
+                        lp[r * T + c] = r * T + start
+            for r in range(1, T):
+                for c in range(T):
+                    if not f[r, c]:
+                        continue
+                    u, l, ul = f[r - 1, c], c > 0 and f[r, c - 1], c > 0 and f[r - 1, c - 1]
+                    rt, ur = c < T - 1 and f[r, c + 1], c < T - 1 and f[r - 1, c + 1]
+                    i = r * T + c
+                    if u:
+                        if not (l and ul):
+                            union(lp, i, i - T, 0)
+                    elif connectivity == 8:
+                        if ul and not l:
+                            union(lp, i, i - T - 1, 0)
+                        if ur and not rt:
+                            union(lp, i, i - T + 1, 0)
+            for r in range(sub.shape[0]):
+                for c in range(sub.shape[1]):
+                    if f[r, c]:
+                        root = find(lp, r * T + c, 0)
+                        g = (y0 + root // T) * W + x0 + root % T
+                        par[(y0 + r) * W + x0 + c] = g + 1
+                        ta[g] += 1
+                        y, x = y0 + r, x0 + c
+                        tedge[g] |= y == 0 or y == H - 1 or x == 0 or x == W - 1
+    levels = 0
+    while (1 << levels) < max(ty_n, tx_n):
+        levels += 1
+    for m in range(1, levels + 1):
+        size = T << m
+        for gy in range(-(-ty_n // (1 << m))):
+            for gx in range(-(-tx_n // (1 << m))):
+                x0, y0 = gx * size, gy * size
+                x1, y1 = min(x0 + size, W), min(y0 + size, H)
+                xb, yb = x0 + size // 2, y0 + size // 2
+                if xb < W:
+                    for y in range(y0, y1):
+                        a = y * W + xb - 1
+                        b = a + 1
+                        if not par[a]:
+                            continue
+                        if par[b]:
+                            union(par, a, b, 1)
+                        if connectivity == 8:
+                            if y + 1 < y1 and par[b + W]:
+                                union(par, a, b + W, 1)
+                            if y - 1 >= y0 and par[b - W]:
+                                union(par, a, b - W, 1)
+                if yb < H:
+                    for x in range(x0, x1):
+                        a = (yb - 1) * W + x
+                        b = a + W
+                        if not par[a]:
+                            continue
+                        if par[b]:
+                            union(par, a, b, 1)
+                        if connectivity == 8:
+                            if x + 1 < x1 and par[b + 1]:
+                                union(par, a, b + 1, 1)
+                            if x - 1 >= x0 and par[b - 1]:
+                                union(par, a, b - 1, 1)
+    labels = np.zeros(H * W, np.int32)
+    tot = np.zeros(H * W, np.int64)
+    tot_edge = np.zeros(H * W, bool)
+    for g in range(H * W):
+        if par[g]:
+            r = find(par, g, 1)
+            labels[g] = r + 1
+            if ta[g]:
+                tot[r] += ta[g]
+                tot_edge[r] |= tedge[g]
+    lab0 = np.maximum(labels.astype(np.int64) - 1, 0)
+    area = np.where(labels > 0, tot[lab0], 0).astype(np.int32)
+    edge = np.where(labels > 0, tot_edge[lab0], False).astype(np.uint8)
+    return labels.reshape(H, W), area.reshape(H, W), edge.reshape(H, W), levels

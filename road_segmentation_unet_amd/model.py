@@ -6,6 +6,7 @@ Data parallelism (new; the reference is single-device): when torch.distributed i
 minibatch, sharded contiguously over ranks; gradients are all-reduced (dist.GradBucketer); predict() shards tiles.
 """
 import contextlib
+import ctypes
 import glob
 import math
 import os
@@ -17,7 +18,7 @@ import torch.distributed as dist
 
 from . import hostio
 from . import images as dimages
-from ._lib import call
+from ._lib import call, lib
 from .dist import GradBucketer, micro_indices, shard_indices, tune_overlap  # noqa: F401  (shard_indices: importable from here as before)
 from .pool import BatchUploader, DevicePatchPool, PatchPool
 from .summary import Summary
@@ -89,6 +90,17 @@ EXTRA_FLAG_DEFS = [
                                   "images of the per-image Lovasz loss of |label - p|, a convex surrogate of 1 - IoU; 0 = off. A mean of "
                                   "per-image losses: data-parallel and accumulated steps give the objective of one large batch. Ignored "
                                   "pixels add nothing to it; --class_weights, the weight maps and --focal_gamma do not enter it"),
+    ("min_road_area", int, 0, "A >= 0: remove predicted road components (pixels with probability >= the threshold, joined at "
+                              "--component_connectivity) of fewer than A pixels before the masks are quantised or binarised, on the GPU "
+                              "(rsu_components.h); 0 = off. Applies to the inference and --eval_train branches and to postprocess_masks, "
+                              "never to training"),
+    ("max_hole_area", int, 0, "A >= 0: fill holes -- background regions of the cleaned mask, joined at the dual connectivity, that touch no "
+                              "image edge -- of at most A pixels; runs after --min_road_area; 0 = off"),
+    ("component_connectivity", int, 8, "4|8: the neighbourhood that joins road pixels into components; holes and background use the dual "
+                                       "(4 for 8, 8 for 4)"),
+    ("validate_components", bool, False, "Count connected components during validation: evaluate() also returns components_pred, "
+                                         "components_true and b0_error, the mean over the validation patches of |predicted - true| "
+                                         "component counts (the error of the zeroth Betti number) at --component_connectivity"),
     ("border_weight", float, 0.0, "w0 >= 0 of a border-distance weight map computed on the GPU from each batch's labels: a pixel counts "
                                   "1 + w0 * exp(-d^2 / (2 border_sigma^2)) times in the loss, d its distance to the other class inside its patch; "
                                   "0 = off (the U-Net paper uses 10). The loss stays normalised by the pixel count and the mean weight is above 1, "
@@ -241,6 +253,31 @@ def parse_lovasz_weight(value):
         v = float("nan")
     if isinstance(value, bool) or not (math.isfinite(v) and v >= 0.0):
         raise ValueError("--lovasz_weight must be a finite float >= 0, not %r" % (value,))
+    return v
+
+
+def parse_component_area(value, name="min_road_area"):
+    """The --min_road_area / --max_hole_area value as an int >= 0 (0 = off; rsu_components.h takes a C int). Anything else raises
+    ValueError."""
+    try:
+        v = int(value)
+        ok = not isinstance(value, bool) and v == (float(value) if not isinstance(value, str) else v) and 0 <= v < (1 << 31)
+    except (TypeError, ValueError, OverflowError):
+        v, ok = 0, False
+    if not ok:
+        raise ValueError("--%s must be an integer >= 0, not %r" % (name, value))
+    return v
+
+
+def parse_component_connectivity(value):
+    """The --component_connectivity value: 4 or 8 as an int. Anything else raises ValueError."""
+    try:
+        v = int(value)
+        ok = not isinstance(value, bool) and v == (float(value) if not isinstance(value, str) else v) and v in (4, 8)
+    except (TypeError, ValueError, OverflowError):
+        v, ok = 0, False
+    if not ok:
+        raise ValueError("--component_connectivity must be 4 or 8, not %r" % (value,))
     return v
 
 
@@ -571,6 +608,10 @@ class Options(object):
         self.cldice_weight, self.cldice_iters = parse_cldice_weight(self.cldice_weight), parse_cldice_iters(self.cldice_iters)
         self.cldice_smooth = parse_cldice_smooth(self.cldice_smooth)
         self.lovasz_weight = parse_lovasz_weight(self.lovasz_weight)
+        self.min_road_area = parse_component_area(self.min_road_area, "min_road_area")
+        self.max_hole_area = parse_component_area(self.max_hole_area, "max_hole_area")
+        self.component_connectivity = parse_component_connectivity(self.component_connectivity)
+        self.validate_components = bool(self.validate_components)
         self.border_weight, self.border_sigma = parse_border_weight(self.border_weight), parse_border_sigma(self.border_sigma)
         self.clip_grad_norm = parse_clip_grad_norm(self.clip_grad_norm)
         self.ema_decay, self.ema_warmup = parse_ema_decay(self.ema_decay), bool(self.ema_warmup)
@@ -660,6 +701,8 @@ class ConvolutionalModel:
         self._summary = None
         self._pending_scalars = []
         self.best_val_f1 = None   # the best validation F1 seen by train() (--save_best keeps that model)
+        self.last_postprocess_stats = None   # postprocess_masks: the summed stats of its last call (int64 [6])
+        self._cc_acc = self._cc_ws = None    # --validate_components: the four counts and the workspace of rsu_components_pair_count
         if self.world > 1:
             self._bucketer = GradBucketer(self.net.flat_g, self.net.n_live)
             self._bucketer.extra_streams = list(self.net.wstreams)
@@ -821,7 +864,11 @@ class ConvolutionalModel:
         all-reduced with the others; zeros with --cldice_weight=0) with "cldice" = cldice_from_sums of them; with --cldice_weight > 0
         "objective" also includes cldice_weight * (1 - cldice). With --lovasz_weight > 0 (only then) also "lovasz", the mean per-image
         Lovasz loss over the set from the all-reduced {sum_b L_b, images} less the padding images (which add exactly 0), and
-        "objective" includes lovasz_weight * lovasz.
+        "objective" includes lovasz_weight * lovasz. With --validate_components (only then) one rsu_components_pair_count
+        (rsu_components.h) per chunk on net.prob and net.labels at `threshold` and --component_connectivity; its four integer counts
+        ride last in the same all-reduce and read-back (exact in float64 below 2^53), and the result gains "components_pred" and
+        "components_true" (the predicted and true components summed over the patches, ignored pixels background in both) and
+        "b0_error" = sum |predicted - true| / max(patches with a counted pixel, 1); the padding patches add exactly nothing.
         averaged: None scores the averaged weights when the net has them (--ema_decay), True demands them (ValueError on a net without),
         False forces the raw weights; the device work runs inside net.averaged_weights(), and the result carries "averaged" (bool).
         Training is left as it was: weights, the averages and every packed copy (the exchange of averaged_weights() is undone), optimizer
@@ -842,6 +889,10 @@ class ConvolutionalModel:
         try:
             with ctx:
                 net.reset_eval()
+                with_cc = bool(getattr(self._options, "validate_components", False))
+                if with_cc:
+                    self._components_buffers()
+                    self._cc_acc.zero_()
                 for t0 in range(lo, hi, B):
                     nb = min(B, hi - t0)
                     if nb < B:
@@ -857,6 +908,11 @@ class ConvolutionalModel:
                         net.set_pixel_weights(None)
                     net.forward_device(keep=1.0)
                     net.evaluate_device()
+                    if with_cc:
+                        call("rsu_components_pair_count", ctypes.c_void_p(net.prob.data_ptr()), float(threshold),
+                             ctypes.c_void_p(net.labels.data_ptr()), int(self._options.component_connectivity),
+                             ctypes.c_void_p(self._cc_acc.data_ptr()), ctypes.c_void_p(self._cc_ws.data_ptr()), B, net.P, net.P,
+                             ctypes.c_void_p(torch.cuda.current_stream(net.device).cuda_stream))
                 sums, hist = net.eval_sums.to(torch.float64), net.eval_hist.clone()
                 with_cl = net.cldice_weight > 0.0
                 if with_cl:   # the four clDice sums ride behind the five of the head: one all-reduce, one read-back
@@ -864,10 +920,15 @@ class ConvolutionalModel:
                 with_lv = net.lovasz_weight > 0.0
                 if with_lv:   # and the Lovasz pair {sum_b L_b, images} last
                     sums = torch.cat([sums, net.eval_lovasz_sum.to(torch.float64)])
+                if with_cc:   # and the four component counts behind everything else
+                    sums = torch.cat([sums, self._cc_acc.to(torch.float64)])
                 if self.world > 1:
                     dist.all_reduce(sums)
                     dist.all_reduce(hist)
                 sums, hist = sums.cpu().numpy(), hist.cpu().numpy()   # the one synchronisation
+                cc_sums = sums[-4:] if with_cc else None
+                if with_cc:
+                    sums = sums[:-4]
                 lv_sums = sums[-2:] if with_lv else None
                 sums, cl_sums = sums[:5], (sums[5:9] if with_cl else np.zeros(4))
         finally:
@@ -883,7 +944,21 @@ class ConvolutionalModel:
         if with_lv:   # the mean over the set's N images: the chunks' padding images have no counted pixel, L_b = 0
             out["lovasz"] = float(lv_sums[0]) / max(N, 1)
             out["objective"] = out["objective"] + net.lovasz_weight * out["lovasz"]
+        if with_cc:
+            out["components_pred"], out["components_true"] = int(cc_sums[0]), int(cc_sums[1])
+            out["b0_error"] = float(cc_sums[2]) / max(float(cc_sums[3]), 1.0)
         return out
+
+    def _components_buffers(self):
+        """the device buffers of --validate_components, made when evaluate() first needs them: the four counts and the workspace"""
+        if self._cc_acc is None:
+            net = self.net
+            need = int(lib().rsu_components_ws_bytes(self.local_batch, net.P, net.P))
+            if need == 0:
+                raise ValueError("--validate_components: a batch of %d patches of %d x %d pixels is outside rsu_components.h's limits"
+                                 % (self.local_batch, net.P, net.P))
+            self._cc_acc = torch.zeros(4, dtype=torch.int64, device=net.device)
+            self._cc_ws = torch.zeros(need // 4, dtype=torch.int32, device=net.device)
 
     def _validate(self, validation, step):
         """one validation pass inside train(): evaluate (the averaged weights with --ema_decay), print and log on rank 0, keep the best model
@@ -894,6 +969,9 @@ class ConvolutionalModel:
             print("\nstep {} validation: loss {:.5f} objective {:.5f} dice {:.4f} f1 {:.4f} iou {:.4f} best threshold {:.4f} (f1 {:.4f}) on {} patches{}"
                   .format(step, v["loss"], v["objective"], v["dice"], v["f1"], v["iou"], v["best_threshold"], v["best_f1"], len(validation[0]),
                           " (averaged weights)" if v["averaged"] else ""))
+            if "b0_error" in v:
+                print("step {} validation components: predicted {} true {} b0_error {:.4f}".format(step, v["components_pred"],
+                                                                                                 v["components_true"], v["b0_error"]))
             if self._summary is not None:
                 self._summary.add({"val_loss": v["loss"], "val_objective": v["objective"], "val_dice": v["dice"], "val_f1": v["f1"],
                                    "val_iou": v["iou"], "val_best_threshold": v["best_threshold"]}, global_step=step)
@@ -901,6 +979,8 @@ class ConvolutionalModel:
                     self._summary.add({"val_cldice": v["cldice"]}, global_step=step)
                 if opts.lovasz_weight > 0.0:
                     self._summary.add({"val_lovasz": v["lovasz"]}, global_step=step)
+                if "b0_error" in v:
+                    self._summary.add({"val_b0_error": v["b0_error"]}, global_step=step)
         if self.best_val_f1 is None or v["f1"] > self.best_val_f1:   # (the same numbers on every rank: they come out of the all-reduce)
             self.best_val_f1 = v["f1"]
             if opts.save_best:
@@ -1212,6 +1292,35 @@ class ConvolutionalModel:
         else:
             call("rsu_quantize_mask_rect", ctypes.c_void_p(t.data_ptr()), ctypes.c_void_p(t.data_ptr()), t.shape[0], t.shape[1], t.shape[2],
                  int(patch_size), float(threshold), st)
+        return t.cpu().numpy()[..., None].astype(a.dtype)
+
+    def postprocess_masks(self, masks, threshold=0.5):
+        """The clean-up of predicted masks on the device (rsu_components_filter): masks [n, H, W, 1] probabilities -> the same shape and
+        dtype, road components (p >= threshold at --component_connectivity) of fewer than --min_road_area pixels set to 0, then holes of
+        at most --max_hole_area pixels set to 1, every other pixel unchanged. The identity -- `masks` itself, no launch -- when both flags
+        are 0. Integer decisions on the same input: every rank computes the same bits. last_postprocess_stats holds the call's summed
+        {components, components removed, pixels removed, holes, holes filled, pixels filled} (int64 [6]; None for the identity)."""
+        opts = self._options
+        min_area, max_hole = int(getattr(opts, "min_road_area", 0)), int(getattr(opts, "max_hole_area", 0))
+        if min_area == 0 and max_hole == 0:
+            self.last_postprocess_stats = None
+            return masks
+        a = np.asarray(masks)
+        if a.ndim != 4 or a.shape[3] != 1:
+            raise ValueError("postprocess_masks: masks must be [n, H, W, 1], not %s" % (a.shape,))
+        n, H, W = (int(v) for v in a.shape[:3])
+        need = int(lib().rsu_components_ws_bytes(n, H, W))
+        if need == 0:
+            raise ValueError("postprocess_masks: %d masks of %d x %d pixels are outside rsu_components.h's limits (H * W <= 2^24, "
+                             "n * H * W < 2^31): clean them in smaller stacks" % (n, H, W))
+        dev = self.net.device
+        t = torch.as_tensor(np.ascontiguousarray(a[..., 0], dtype=np.float32)).to(dev)
+        ws = torch.empty(need // 4, dtype=torch.int32, device=dev)
+        stats = torch.empty((n, 6), dtype=torch.int64, device=dev)
+        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        call("rsu_components_filter", ctypes.c_void_p(t.data_ptr()), float(threshold), int(getattr(opts, "component_connectivity", 8)),
+             min_area, max_hole, ctypes.c_void_p(t.data_ptr()), ctypes.c_void_p(stats.data_ptr()), ctypes.c_void_p(ws.data_ptr()), n, H, W, st)
+        self.last_postprocess_stats = stats.sum(dim=0).cpu().numpy()
         return t.cpu().numpy()[..., None].astype(a.dtype)
 
     # ------------------------------------------------------------------ checkpoints
