@@ -17,6 +17,13 @@
  *   - devices: one process drives one GPU (torch.distributed, one rank per device). The HIP current device must be the device
  *     the stream and the pointers belong to (the Python host calls torch.cuda.set_device); tensors stay below 2 GiB each
  *     (RSU_E2BIG otherwise: split the batch).
+ *   - the 2-GiB rule: EVERY batch-taking entry point -- the MFMA launches and the VALU ones (colour adjust, dropout, pools, gradient
+ *     junction, heads, bias gradient) alike -- returns RSU_E2BIG, before anything is launched or written, when one of the tensors it is
+ *     handed has 0x7ffffff0 bytes or more; below that every entry is exact (tests/test_gpu_large_tensors.py runs each one image short of
+ *     the limit against the oracle, tests/test_large_limits_host.py holds each to its refusal one image past it). Which tensor that is,
+ *     is noted at each entry as "limit:". The decision for the VALU entries is REFUSE, not "exact beyond 2 GiB": their kernels use 64-bit
+ *     addresses, but their dropout counters are 32-bit element indices and k_pool_skip_relu_bwd_code forms its pooled element index and
+ *     its row count N * (H / 2) in int; no caller needs more, since every conv around these launches refuses such tensors.
  *   - activations: NHWC, bfloat16 ("bf16", the storage type of the fast path), raw uint16 bits.
  *     Channel counts of bf16 tensors must be multiples of 8 (16-byte pieces).
  *   - parameters / gradients / optimizer state: float32 in the reference's own layouts: conv
@@ -139,11 +146,13 @@ int rsu_pack_table_run(const void* dev_table, int nentries, int total_blocks, rs
  * out16: bf16 [npix][16] = {dropout(net0)[0..2], 0, m[cj]*(x-0.5)[ci] at 4+3*ci+cj, m[0..2] at 13..15} (m = 0/1 keep
  * mask, all ones without dropout) -- channels 0..2 feed the first 3x3 conv, channels 4..15 are kept for the weight and
  * bias gradients of color_space_adjust (rsu_conv_first_bwd_weight). */
+/* limit: out16, npix * 32 bytes (the dropout counter 3 * npix + c then stays below 2^28). */
 int rsu_color_adjust_fwd(const float* x, const float* w, const float* b, void* out16, long npix, float keep, unsigned key,
                          rsu_stream_t stream);
 /* unet.py:34-35,42-43 first 3x3 conv of level 0 (Cin = 3) + bias + ReLU, dil = 1 or 2 (dilated branch).
  * in16 as above [N][H][W][16]; packed = rsu_pack_conv_first(w f32 HWIO [3][3][3][Cout]) (rows for channels 3..15 are
  * zero, so the (x-0.5) copy in channels 4..6 does not contribute); y bf16 [N][H-2d][W-2d][Cout]. */
+/* limit: max(in16 = N*H*W*32, y = N*(H-2d)*(W-2d)*Cout*2) bytes. */
 size_t rsu_packed_first_bytes(int Cout);
 int rsu_pack_conv_first(const float* w_hwio, void* packed, int Cout, rsu_stream_t stream);
 int rsu_conv_first_fwd(const void* in16, const void* packed, const float* b, void* y, int N, int H, int W, int Cout,
@@ -153,6 +162,7 @@ int rsu_conv_first_fwd(const void* in16, const void* packed, const float* b, voi
  * rsu_conv_first_fwd. The 16-channel tensor of rsu_color_adjust_fwd is neither written nor read (-58 MB and one launch per forward pass at
  * B = 4, 572 px); the results are bit-identical to rsu_color_adjust_fwd(keep = 1) + rsu_conv_first_fwd. A training step still calls
  * rsu_color_adjust_fwd (rsu_conv_first_bwd_weight reads its output), but may do so on another stream, off the forward pass's critical path. */
+/* limit: max(x = N*H*W*12, y = N*(H-2d)*(W-2d)*Cout*2) bytes (y always reaches it first: Cout >= 8). */
 int rsu_color_conv_first_fwd(const float* x, const float* w0, const float* b0, const void* packed, const float* b, void* y, int N, int H,
                              int W, int Cout, int dil, int ncu, rsu_stream_t stream);
 /* weight/bias gradients of that conv and, through it, of color_space_adjust (no input-gradient pass is needed):
@@ -162,7 +172,8 @@ int rsu_color_conv_first_fwd(const float* x, const float* w0, const float* b0, c
  *   d(color_space_adjust/bias)[cj]       = 1/keep * sum_{t,co} W1[t][cj][co] gm[t][cj][co]
  * ws: float workspace of rsu_conv_first_bwd_ws_floats() floats. */
 size_t rsu_conv_first_bwd_ws_floats(int Cout);
-/* db (optional): BiasAddGrad of this conv, computed by the same launch */
+/* db (optional): BiasAddGrad of this conv, computed by the same launch. limit: max(in16 = N*H*W*32, dz = N*(H-2d)*(W-2d)*Cout*2) bytes
+ * (igemm_wg1's own bound of 2^28 output pixels lies beyond it: 2^28 pixels of in16 are 8 GiB). */
 int rsu_conv_first_bwd_weight(const void* in16, const void* dz, float* dw1, float* gx, float* db, float* ws, int N,
                               int H, int W, int Cout, int dil, int ncu, rsu_stream_t stream);
 /* The two sums above in one launch: dW0 f32 [3][3] ([ci][cj]) and db0 f32 [3] from gx [9][12][Cout] and W1 f32 HWIO
@@ -171,6 +182,8 @@ int rsu_color_adjust_bwd(const float* gx, const float* w1, float* dW0, float* db
                          rsu_stream_t stream);
 /* unet.py:95 weight_output 1x1 conv (C -> 2) fused with tf_aerial_images.py:147-148 softmax[...,1].
  * act bf16 [npix][C]; w f32 [C][2]; prob f32 [npix]; logits f32 [npix][2] or NULL (unet.forward's return value). */
+/* limit (this and every rsu_head_* entry below, rsu_loss.h and rsu_cldice.h included): act (and dact), npix * C * 2 bytes -- with C >= 8
+ * the largest tensor of the call (labels and logits are 8 bytes per pixel). */
 int rsu_head_fwd(const void* act, const float* w, const float* b, float* prob, float* logits, long npix, int C,
                  rsu_stream_t stream);
 /* Same plus tf_aerial_images.py:103-110 mean sparse softmax cross-entropy and its backward:
@@ -271,6 +284,8 @@ int rsu_border_map(const int64_t* labels, const float* mul, float* out, int32_t*
 /* ---- 3x3 convolution, MFMA implicit GEMM -------------------------------------------------- */
 /* unet.py:34-39,42-45,88-91: y = relu(conv3x3_valid(concat(srcs), W, dilation) + b).
  * All sources share the window size (Hin, Win); y is bf16 [N][Hin-2d][Win-2d][Cout]. */
+/* limit (rsu_conv2d_fwd, _fwd_pool, _bwd_data and their _k forms): the output, and EVERY source as a whole, N * H * W * C * 2 bytes of the
+ * uncropped tensor (a cropped skip tensor is larger than its window). */
 int rsu_conv2d_fwd(const rsu_src_t* srcs, int nsrc, const void* packed_fwd, const float* bias, void* y, int N,
                    int Hin, int Win, int Cout, int dil, int relu, int ncu, rsu_stream_t stream);
 /* The same three launches (rsu_conv2d_fwd, rsu_conv2d_fwd_pool, rsu_conv2d_bwd_data) with a caller-owned workspace `kws` of `kws_floats`
@@ -312,7 +327,9 @@ int rsu_conv2d_bwd_data(const void* dz, const void* packed_bwd, void* dx, const 
  * ws: rsu_conv2d_bwd_weight_ws_floats() floats of scratch (split-K slabs). */
 size_t rsu_conv2d_bwd_weight_ws_floats(int Cin_total, int src_C, int Cout);
 /* db (optional, f32 [Cout]): BiasAddGrad = sum over pixels of dz, computed by the same launch (one extra MFMA per
- * 32-pixel step); pass it with ONE of the sources of a concatenated input, NULL with the others. */
+ * 32-pixel step); pass it with ONE of the sources of a concatenated input, NULL with the others.
+ * limit: max(src as a whole = N*src.H*src.W*src.C*2, dz = N*Ho*Wo*Cout*2) bytes ("beyond that the offsets wrapped"); rsu_wgrad_group_plan
+ * returns the same RSU_E2BIG for any of its jobs. */
 int rsu_conv2d_bwd_weight(const rsu_src_t* src, const void* dz, float* dw, float* db, float* ws, int N, int Ho, int Wo,
                           int Cin_total, int ci_off, int Cout, int dil, int ncu, rsu_stream_t stream);
 /* Grouped weight gradients (new; TensorFlow's executor runs independent Conv2DBackpropFilter ops side by side, tf_aerial_images.py:120-121).
@@ -345,12 +362,14 @@ size_t rsu_wgrad_group_ws_floats(void);
 int rsu_wgrad_group_plan(const rsu_wgrad_job_t* jobs, int njobs, float* ws, int N, int ncu, void* host_table);
 int rsu_wgrad_group_run(const void* host_table, const void* dev_table, rsu_stream_t stream);
 /* BiasAddGrad: db[c] = sum over npix of dz[pix][c]. ws: rsu_bias_grad_ws_floats(npix, C) floats. */
+/* limit: dz, npix * C * 2 bytes. */
 size_t rsu_bias_grad_ws_floats(long npix, int C);
 int rsu_bias_grad(const void* dz, float* db, float* ws, long npix, int C, rsu_stream_t stream);
 
 /* ---- 2x2 max pool -------------------------------------------------------------------------- */
 /* unet.py:52 max_pooling2d (2,2)/(2,2) VALID, then the next level's dropout (unet.py:29-30; keep = 1: none).
  * x bf16 [N][H][W][C] -> y [N][H/2][W/2][C] */
+/* limit (both forms): x, N*H*W*C*2 bytes (the dropout counter, a pooled element index, then stays below 2^28). */
 int rsu_maxpool2x2_fwd(const void* x, void* y, int N, int H, int W, int C, float keep, unsigned key,
                        rsu_stream_t stream);
 /* ... and, for training, a code tensor for the gradient junction below (H, W even; code [N][H/2][W/2][C] bytes, may be NULL):
@@ -363,7 +382,9 @@ int rsu_maxpool2x2_fwd_code(const void* x, void* y, void* code, int N, int H, in
  *     + zero-pad(dskip)                      (dskip bf16 [N][Hs][Ws][C] centred, may be NULL;
  *                                             adjoint of the centre crop of unet.py:70-83)
  *   dz = g * (y_act > 0)                     (ReluGrad) -> bf16 [N][H][W][C]
- * MaxPoolGrad routes to the first maximum of the window in row-major order. */
+ * MaxPoolGrad routes to the first maximum of the window in row-major order.
+ * limit (both forms): dz (= y_act), N*H*W*C*2 bytes: the int row count N * (H / 2) and pooled element index of the code-byte kernel and the
+ * 32-bit dropout counter of both kernels then stay below 2^28. */
 int rsu_pool_skip_relu_bwd(const void* y_act, const void* dpool, const void* dskip, void* dz, int N, int H, int W,
                            int C, int Hs, int Ws, float keep, unsigned key, rsu_stream_t stream);
 /* The same junction from the code tensor of rsu_maxpool2x2_fwd_code instead of the activation (y_act may then be NULL): one
@@ -372,9 +393,13 @@ int rsu_pool_skip_relu_bwd_code(const void* y_act, const void* code, const void*
                                 int H, int W, int C, int Hs, int Ws, float keep, unsigned key, rsu_stream_t stream);
 /* unet.py:64-65 dropout in front of a transposed conv: y = x / keep * floor(keep + U), bf16 [n] -> bf16 [n] (n % 8 == 0).
  * Its backward is fused into rsu_convT2x2_bwd_data: pass y as relu_src (y > 0 <=> x > 0 and kept) and out_scale = 1/keep. */
+/* limit: n * 2 bytes (the dropout counter is the element index, then below 2^30); an n that is no multiple of 8 is RSU_EINVAL first. */
 int rsu_dropout_fwd(const void* x, void* y, long n, float keep, unsigned key, rsu_stream_t stream);
 
 /* ---- 2x2 stride-2 transposed convolution (unet.py:67-68) ---------------------------------- */
+/* limit (all three): max(x = N*H*W*Cin*2, y / dy = N*4*H*W*Cout*2) bytes. The faster kernels' own bounds (igemm_ct: the 4x tensor below the
+ * limit; igemm_wgt: 2^28 input pixels) select no slower path that could run: the generic launches behind them refuse the same tensors,
+ * and 2^28 pixels of 8 channels are 4 GiB. */
 int rsu_convT2x2_fwd(const void* x, const void* packed_fwd, const float* bias, void* y, int N, int H, int W,
                      int Cin, int Cout, int ncu, rsu_stream_t stream);
 /* dx bf16 [N][H][W][Cin] = out_scale * sum_{a,b,co} dy[2i+a][2j+b][co] K[a][b][co][ci], times (relu_src > 0) if given.

@@ -499,14 +499,20 @@ extern "C" int rsu_grad_accumulate(float* dst, const float* src, long n, int ass
 // VALU head / tail
 // ---------------------------------------------------------------------------------------------
 static bool keep_ok(float keep) { return keep > 0.f && keep <= 1.f; }
+// The 2-GiB rule of the conv entries (run_fwd), held by every batch-taking VALU entry as well: the tensors of a training step pass through
+// both kinds of launch, so nothing is gained by a pool or a head that takes what the convs around it refuse -- and the 32-bit dropout
+// counters and the int products of the pool kernels (elementwise.hip) then stay in range by construction.
+static bool too_big(long bytes) { return bytes >= 0x7ffffff0L; }
 extern "C" int rsu_color_adjust_fwd(const float* x, const float* w, const float* b, void* out16, long npix, float keep, unsigned key,
                                     rsu_stream_t stream) {
-    if (!x || !w || !b || !out16 || npix < 1 || 3 * npix > 0xffffffffL || !keep_ok(keep)) return RSU_EINVAL;
+    if (!x || !w || !b || !out16 || npix < 1 || !keep_ok(keep)) return RSU_EINVAL;
+    if (too_big(npix * 32)) return RSU_E2BIG;   // out16, the larger tensor (the dropout counter 3 * npix + c then stays below 2^28)
     HIP_CHECK_RET(ew_color_adjust(x, w, b, out16, npix, keep, key, (hipStream_t)stream));
     return RSU_OK;
 }
 extern "C" int rsu_dropout_fwd(const void* x, void* y, long n, float keep, unsigned key, rsu_stream_t stream) {
-    if (!x || !y || n < 8 || n % 8 || n > 0xffffffffL || !keep_ok(keep)) return RSU_EINVAL;
+    if (!x || !y || n < 8 || n % 8 || !keep_ok(keep)) return RSU_EINVAL;
+    if (too_big(n * 2)) return RSU_E2BIG;   // (the dropout counter, the element index, then stays below 2^30)
     HIP_CHECK_RET(ew_dropout(x, y, n, keep, key, (hipStream_t)stream));
     return RSU_OK;
 }
@@ -1446,6 +1452,7 @@ extern "C" int rsu_wgrad_group_run(const void* host_table, const void* dev_table
 extern "C" size_t rsu_bias_grad_ws_floats(long npix, int C) { return (size_t)ew_colsum_blocks(npix, C) * C; }
 extern "C" int rsu_bias_grad(const void* dz, float* db, float* ws, long npix, int C, rsu_stream_t stream) {
     if (!dz || !db || !ws || C < 8 || C % 8 || C > 2048 || 256 % (C / 8) || npix < 1) return RSU_EINVAL;
+    if (too_big(npix * C * 2)) return RSU_E2BIG;
     HIP_CHECK_RET(ew_colsum(dz, db, ws, npix, C, (hipStream_t)stream));
     return RSU_OK;
 }
@@ -1457,7 +1464,7 @@ extern "C" int rsu_maxpool2x2_fwd_code(const void* x, void* y, void* code, int N
                                        rsu_stream_t stream) {
     if (!x || !y || C % 8 || H < 2 || W < 2 || !keep_ok(keep)) return RSU_EINVAL;
     if (code && ((H | W) & 1)) return RSU_EINVAL;
-    if (keep < 1.f && (long)N * (H / 2) * (W / 2) * C > 0xffffffffL) return RSU_EINVAL;
+    if (N >= 1 && too_big((long)N * H * W * C * 2)) return RSU_E2BIG;   // x, the largest tensor (the dropout counter, a pooled element index, stays below 2^28)
     HIP_CHECK_RET(ew_maxpool_fwd(x, y, code, N, H, W, C, keep, key, (hipStream_t)stream));
     return RSU_OK;
 }
@@ -1469,6 +1476,9 @@ extern "C" int rsu_pool_skip_relu_bwd_code(const void* y_act, const void* code, 
     if ((!y_act && !code) || !dz || C % 8 || !keep_ok(keep)) return RSU_EINVAL;
     if (code && (((H | W) & 1) || H < 2 || W < 2)) return RSU_EINVAL;   // the code tensor describes whole 2x2 windows
     if (dskip && (Hs > H || Ws > W || Hs < 1 || Ws < 1)) return RSU_EINVAL;
+    // dz, the largest tensor: below the limit the int row count N * (H / 2) and pooled element index of k_pool_skip_relu_bwd_code and
+    // the 32-bit dropout counter of both kernels stay below 2^28
+    if (N >= 1 && H >= 1 && W >= 1 && C >= 8 && too_big((long)N * H * W * C * 2)) return RSU_E2BIG;
     HIP_CHECK_RET(ew_pool_skip_relu_bwd(y_act, code, dpool, dskip, dz, N, H, W, C, dskip ? Hs : 0, dskip ? Ws : 0, keep, key, (hipStream_t)stream));
     return RSU_OK;
 }
@@ -1478,6 +1488,8 @@ extern "C" int rsu_pool_skip_relu_bwd(const void* y_act, const void* dpool, cons
     return rsu_pool_skip_relu_bwd_code(y_act, nullptr, dpool, dskip, dz, N, H, W, C, Hs, Ws, keep, key, stream);
 }
 static bool head_c_ok(int C) { return C >= 8 && C <= 512 && (C % 8) == 0 && ((C / 8) & (C / 8 - 1)) == 0; }
+// act (and dact) [npix][C] bf16: the largest tensor of every head call (C >= 8: 16 bytes per pixel against the 8 of labels or logits)
+static bool head_too_big(long npix, int C) { return too_big(npix * C * 2); }
 // what rsu_head_fwd_bwd, _w and _dice all require
 static bool head_train_args_ok(const void* act, const float* w, const float* b, const int64_t* labels, const float* prob, const float* loss_sum,
                                const void* dact, const float* dw, const float* db, const float* ws, long npix, int C) {
@@ -1493,6 +1505,7 @@ extern "C" int rsu_color_adjust_bwd(const float* gx, const float* w1, float* dW0
 extern "C" int rsu_head_fwd(const void* act, const float* w, const float* b, float* prob, float* logits, long npix, int C,
                             rsu_stream_t stream) {
     if (!act || !w || !b || !prob || !head_c_ok(C) || npix < 1) return RSU_EINVAL;
+    if (head_too_big(npix, C)) return RSU_E2BIG;
     HIP_CHECK_RET(ew_head(false, act, w, b, nullptr, prob, logits, nullptr, nullptr, nullptr, nullptr, nullptr, npix, C, 0.f, (hipStream_t)stream));
     return RSU_OK;
 }
@@ -1500,6 +1513,7 @@ extern "C" size_t rsu_head_ws_floats(long npix, int C) { return (size_t)ew_head_
 extern "C" int rsu_head_fwd_bwd(const void* act, const float* w, const float* b, const int64_t* labels, float* prob, float* loss_sum,
                                 void* dact, float* dw, float* db, float* ws, long npix, int C, float inv_count, rsu_stream_t stream) {
     if (!head_train_args_ok(act, w, b, labels, prob, loss_sum, dact, dw, db, ws, npix, C)) return RSU_EINVAL;
+    if (head_too_big(npix, C)) return RSU_E2BIG;
     HIP_CHECK_RET(ew_head(true, act, w, b, labels, prob, nullptr, dact, dw, db, loss_sum, ws, npix, C, inv_count, (hipStream_t)stream));
     return RSU_OK;
 }
@@ -1508,6 +1522,7 @@ extern "C" int rsu_head_fwd_bwd_w(const void* act, const float* w, const float* 
                                   const float* pixel_w, float* prob, float* loss_sum, float* weight_sum, void* dact, float* dw, float* db,
                                   float* ws, long npix, int C, float inv_count, rsu_stream_t stream) {
     if (!head_train_args_ok(act, w, b, labels, prob, loss_sum, dact, dw, db, ws, npix, C)) return RSU_EINVAL;
+    if (head_too_big(npix, C)) return RSU_E2BIG;
     HIP_CHECK_RET(ew_head_loss(act, w, b, labels, class_w, pixel_w, nullptr, 0.f, 0.f, prob, dact, dw, db, loss_sum, weight_sum, ws, npix, C,
                                inv_count, (hipStream_t)stream));
     return RSU_OK;
@@ -1516,6 +1531,7 @@ extern "C" size_t rsu_head_dice_ws_floats(long npix, int C) { return (size_t)ew_
 extern "C" int rsu_head_dice_sums(const void* act, const float* w, const float* b, const int64_t* labels, const float* pixel_w, float* prob,
                                   float* dice_sums, float* ws, long npix, int C, rsu_stream_t stream) {
     if (!act || !w || !b || !labels || !prob || !dice_sums || !ws || !head_c_ok(C) || npix < 1) return RSU_EINVAL;
+    if (head_too_big(npix, C)) return RSU_E2BIG;
     HIP_CHECK_RET(ew_head_dice_sums(act, w, b, labels, pixel_w, prob, dice_sums, ws, npix, C, (hipStream_t)stream));
     return RSU_OK;
 }
@@ -1524,6 +1540,7 @@ extern "C" int rsu_head_fwd_bwd_dice(const void* act, const float* w, const floa
                                      float* weight_sum, void* dact, float* dw, float* db, float* ws, long npix, int C, float inv_count,
                                      rsu_stream_t stream) {
     if (!head_train_args_ok(act, w, b, labels, prob, loss_sum, dact, dw, db, ws, npix, C)) return RSU_EINVAL;
+    if (head_too_big(npix, C)) return RSU_E2BIG;
     if (!dice_sums || !std::isfinite(smooth) || !(smooth > 0.f) || !std::isfinite(dice_scale) || !(dice_scale >= 0.f)) return RSU_EINVAL;
     HIP_CHECK_RET(ew_head_loss(act, w, b, labels, class_w, pixel_w, dice_sums, dice_scale, smooth, prob, dact, dw, db, loss_sum, weight_sum, ws,
                                npix, C, inv_count, (hipStream_t)stream));
@@ -1535,6 +1552,7 @@ extern "C" int rsu_head_eval(const void* act, const float* w, const float* b, co
                              const float* pixel_w, float* prob, float* sums, unsigned long long* hist, float* ws, long npix, int C,
                              rsu_stream_t stream) {
     if (!act || !w || !b || !labels || !prob || !sums || !hist || !ws || !head_c_ok(C) || npix < 1) return RSU_EINVAL;
+    if (head_too_big(npix, C)) return RSU_E2BIG;
     HIP_CHECK_RET(ew_head_eval(act, w, b, labels, class_w, pixel_w, prob, sums, hist, ws, npix, C, (hipStream_t)stream));
     return RSU_OK;
 }
@@ -1546,6 +1564,7 @@ extern "C" int rsu_head_fwd_bwd_focal(const void* act, const float* w, const flo
                                       float* loss_sum, float* weight_sum, void* dact, float* dw, float* db, float* ws, long npix, int C,
                                       float inv_count, rsu_stream_t stream) {
     if (!focal_gamma_ok(gamma) || !head_train_args_ok(act, w, b, labels, prob, loss_sum, dact, dw, db, ws, npix, C)) return RSU_EINVAL;
+    if (head_too_big(npix, C)) return RSU_E2BIG;
     if (dice_sums && (!std::isfinite(smooth) || !(smooth > 0.f) || !std::isfinite(dice_scale) || !(dice_scale >= 0.f))) return RSU_EINVAL;
     if (!dice_sums) dice_scale = smooth = 0.f;   // (not looked at)
     if (gamma == 0.f)
@@ -1560,6 +1579,7 @@ extern "C" int rsu_head_eval_focal(const void* act, const float* w, const float*
                                    const float* pixel_w, float gamma, float* prob, float* sums, unsigned long long* hist, float* ws, long npix,
                                    int C, rsu_stream_t stream) {
     if (!focal_gamma_ok(gamma) || !act || !w || !b || !labels || !prob || !sums || !hist || !ws || !head_c_ok(C) || npix < 1) return RSU_EINVAL;
+    if (head_too_big(npix, C)) return RSU_E2BIG;
     if (gamma == 0.f)
         HIP_CHECK_RET(ew_head_eval(act, w, b, labels, class_w, pixel_w, prob, sums, hist, ws, npix, C, (hipStream_t)stream));
     else
@@ -1590,6 +1610,7 @@ extern "C" int rsu_head_fwd_bwd_aux(const void* act, const float* w, const float
                                     float* loss_sum, float* weight_sum, void* dact, float* dw, float* db, float* ws, long npix, int C,
                                     float inv_count, const float* gprob, rsu_stream_t stream) {
     if (!gprob || !focal_gamma_ok(gamma) || !head_train_args_ok(act, w, b, labels, prob, loss_sum, dact, dw, db, ws, npix, C)) return RSU_EINVAL;
+    if (head_too_big(npix, C)) return RSU_E2BIG;
     if (dice_sums && (!std::isfinite(smooth) || !(smooth > 0.f) || !std::isfinite(dice_scale) || !(dice_scale >= 0.f))) return RSU_EINVAL;
     if (!dice_sums) dice_scale = smooth = 0.f;   // (not looked at)
     HIP_CHECK_RET(cl_head_aux(act, w, b, labels, class_w, pixel_w, gamma, dice_sums, dice_scale, smooth, gprob, prob, dact, dw, db, loss_sum,
