@@ -1,5 +1,5 @@
 """ctypes binding of librsu_hip.so (the C ABI of include/rsu.h, include/rsu_optim.h, include/rsu_loss.h, include/rsu_cldice.h,
-include/rsu_lovasz.h and include/rsu_components.h).
+include/rsu_lovasz.h, include/rsu_components.h and include/rsu_distance.h).
 
 The library is REQUIRED: there is no CPU or eager-PyTorch fallback anywhere in this package. If the
 shared object is missing or a symbol cannot be resolved, importing/using the product path raises."""
@@ -188,6 +188,13 @@ SIGNATURES_COMPONENTS = {
     "rsu_components_pair_count": (_i, [_vp, _f, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
 }
 
+# and for include/rsu_distance.h, the seventh (mask distances: the exact distance transform of both masks and its histogram)
+SIGNATURES_DISTANCE = {
+    "rsu_distance_ws_bytes": (_sz, [_i, _i, _i]),
+    "rsu_mask_distance": (_i, [_vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "rsu_distance_hist": (_i, [_vp, _f, _vp, _vp, _vp, _i, _i, _i, _vp]),
+}
+
 _lib = None
 
 
@@ -204,7 +211,8 @@ def lib():
                            "or `make -C road_segmentation_unet_amd/csrc`); there is no fallback path" % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_OPTIM.items()) + list(SIGNATURES_LOSS.items()) \
-                + list(SIGNATURES_CLDICE.items()) + list(SIGNATURES_LOVASZ.items()) + list(SIGNATURES_COMPONENTS.items()):
+                + list(SIGNATURES_CLDICE.items()) + list(SIGNATURES_LOVASZ.items()) + list(SIGNATURES_COMPONENTS.items()) \
+                + list(SIGNATURES_DISTANCE.items()):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -222,6 +230,7 @@ AFFINE_MAX_LAUNCH = 32   # rsu.h RSU_AFFINE_MAX_LAUNCH
 ELASTIC_MAX_LAUNCH, ELASTIC_MAX_GRID = 32, 16   # rsu.h RSU_ELASTIC_MAX_LAUNCH, RSU_ELASTIC_MAX_GRID
 JITTER_MAX_LAUNCH = 32   # rsu.h RSU_JITTER_MAX_LAUNCH
 CLDICE_MAX_ITERS = 16   # rsu_cldice.h RSU_CLDICE_MAX_ITERS
+DIST_BINS, DIST_NONE, DIST_MAX_SIDE = 64, 0x7fffffff, 1024   # rsu_distance.h RSU_DIST_BINS, RSU_DIST_NONE, RSU_DIST_MAX_SIDE
 E2BIG = -7
 
 

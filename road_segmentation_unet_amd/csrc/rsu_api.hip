@@ -18,6 +18,7 @@
 #include "../../include/rsu_cldice.h"
 #include "../../include/rsu_lovasz.h"
 #include "../../include/rsu_components.h"
+#include "../../include/rsu_distance.h"
 #include "affine_patches.h"
 #include "color_jitter.h"
 #include "border_map.h"
@@ -26,6 +27,7 @@
 #include "cldice.h"
 #include "lovasz.h"
 #include "components.h"
+#include "distance.h"
 #include "optim.h"
 #include "igemm.h"
 
@@ -1657,6 +1659,28 @@ extern "C" int rsu_components_pair_count(const float* prob, float threshold, con
                                          unsigned long long* acc, void* ws, int N, int H, int W, rsu_stream_t stream) {
     if (!prob || !labels64 || !acc || !ws || !components_size_ok(N, H, W) || !components_args_ok(threshold, connectivity)) return RSU_EINVAL;
     HIP_CHECK_RET(cc_pair_count(prob, threshold, labels64, connectivity, acc, ws, N, H, W, (hipStream_t)stream));
+    return RSU_OK;
+}
+// ---- mask distances (rsu_distance.h): the separable exact distance transform of the predicted and the truth mask, and its histogram
+static_assert(RSU_DIST_MAX_SIDE == DT_MAX_SIDE && RSU_DIST_BINS == DT_BINS, "rsu_distance.h and distance.h must agree on the limits");
+static bool distance_size_ok(int N, int H, int W) { return N >= 1 && H >= 1 && W >= 1 && H <= DT_MAX_SIDE && W <= DT_MAX_SIDE; }
+static bool distance_too_big(int N, int H, int W, int bytes) { return (long)N * H * W * bytes >= 0x7ffffff0L; }
+extern "C" size_t rsu_distance_ws_bytes(int N, int H, int W) {
+    return distance_size_ok(N, H, W) && !distance_too_big(N, H, W, 4) ? dt_ws_bytes(N, H, W) : 0;
+}
+extern "C" int rsu_mask_distance(const float* prob, float threshold, const int64_t* labels64, int32_t* d2_pred, int32_t* d2_true, void* ws,
+                                 int N, int H, int W, rsu_stream_t stream) {
+    if (!prob || !ws || (!d2_pred && !d2_true) || (d2_true && !labels64) || !distance_size_ok(N, H, W) || !std::isfinite(threshold))
+        return RSU_EINVAL;
+    if (distance_too_big(N, H, W, labels64 ? 8 : 4)) return RSU_E2BIG;
+    HIP_CHECK_RET(dt_mask_distance(prob, threshold, labels64, d2_pred, d2_true, ws, N, H, W, (hipStream_t)stream));
+    return RSU_OK;
+}
+extern "C" int rsu_distance_hist(const float* prob, float threshold, const int64_t* labels64, unsigned long long* acc, void* ws, int N, int H,
+                                 int W, rsu_stream_t stream) {
+    if (!prob || !labels64 || !acc || !ws || !distance_size_ok(N, H, W) || !std::isfinite(threshold)) return RSU_EINVAL;
+    if (distance_too_big(N, H, W, 8)) return RSU_E2BIG;
+    HIP_CHECK_RET(dt_distance_hist(prob, threshold, labels64, acc, ws, N, H, W, (hipStream_t)stream));
     return RSU_OK;
 }
 static_assert(RSU_BORDER_MAX_SIDE == BM_MAX_SIDE, "rsu.h and border_map.h must agree on the supported tile size");

@@ -1022,3 +1022,117 @@ def label_components_tiled(mask, connectivity, tile=COMPONENTS_TILE):
     area = np.where(labels > 0, tot[lab0], 0).astype(np.int32)
     edge = np.where(labels > 0, tot_edge[lab0], False).astype(np.uint8)
     return labels.reshape(H, W), area.reshape(H, W), edge.reshape(H, W), levels
+
+
+# ---- mask distances on the host (include/rsu_distance.h)
+DIST_BINS, DIST_NONE, DIST_MAX_SIDE = 64, 0x7fffffff, 1024   # rsu_distance.h RSU_DIST_BINS, RSU_DIST_NONE, RSU_DIST_MAX_SIDE
+
+
+def _dist_check(prob, threshold, labels, need_labels):
+    p = np.ascontiguousarray(prob, np.float32)
+    if p.ndim != 3 or min(p.shape) < 1 or max(p.shape[1:]) > DIST_MAX_SIDE:
+        raise ValueError("distance: prob [N, H, W] with N, H, W >= 1 and H, W <= %d, not shape %r" % (DIST_MAX_SIDE, p.shape))
+    t = np.float32(threshold)
+    if not np.isfinite(t):
+        raise ValueError("distance: threshold must be finite, not %r" % (threshold,))
+    if labels is None:
+        if need_labels:
+            raise ValueError("distance: labels are required")
+        return p, t, None
+    lab = np.asarray(labels)
+    if lab.shape != p.shape or lab.dtype.kind not in "iu":
+        raise ValueError("distance: labels must be an integer array of prob's shape %r, not %s %r" % (p.shape, lab.dtype, lab.shape))
+    return p, t, lab.astype(np.int64)
+
+
+def _dist_masks(p, t, lab):
+    """(P, T): P = {counted and p >= threshold} (one float32 comparison: NaN outside, p == threshold inside), T = {label == 1}; without
+    labels every pixel is counted and T is empty"""
+    with np.errstate(invalid="ignore"):
+        pred = p >= t
+    if lab is None:
+        return pred, np.zeros(p.shape, bool)
+    return pred & ((lab == 0) | (lab == 1)), lab == 1
+
+
+def _dist_transform(mask):
+    """int32 [N, H, W]: the exact squared Euclidean distance of every pixel to the nearest True pixel of its own image, DIST_NONE in an
+    image without one. Separable, in integers: the nearest mask pixel per column (running maxima down and up), then per row the min
+    over x' of (x - x')^2 + g(x')^2, taken offset by offset until the offset's square alone reaches the largest minimum so far."""
+    N, H, W = mask.shape
+    out = np.full((N, H, W), DIST_NONE, np.int64)
+    live = np.nonzero(mask.reshape(N, -1).any(axis=1))[0]
+    if live.size == 0:
+        return out.astype(np.int32)
+    m = mask[live]
+    big = np.int64(1) << 40
+    ys = np.arange(H, dtype=np.int64)[None, :, None]
+    above = np.maximum.accumulate(np.where(m, ys, -big), axis=1)
+    below = np.minimum.accumulate(np.where(m, ys, big)[:, ::-1], axis=1)[:, ::-1]
+    g = np.minimum(ys - above, below - ys)
+    sq = np.where(g < big // 2, g * g, big)
+    best = sq.copy()
+    d = 1
+    while d < W and d * d < int(best.max()):
+        np.minimum(best[:, :, d:], sq[:, :, :-d] + d * d, out=best[:, :, d:])
+        np.minimum(best[:, :, :-d], sq[:, :, d:] + d * d, out=best[:, :, :-d])
+        d += 1
+    out[live] = best
+    return out.astype(np.int32)
+
+
+def mask_distance(prob, threshold, labels=None):
+    """rsu_mask_distance on the host: (d2_pred, d2_true), int32 [N, H, W] each -- the exact squared Euclidean distance of EVERY pixel to
+    P = {label in {0, 1} and p >= threshold} and to T = {label == 1} of its own image, DIST_NONE where the image has no such pixel.
+    Ignored pixels are plain geometry. labels=None: every pixel is counted and T is empty (d2_true is DIST_NONE everywhere)."""
+    p, t, lab = _dist_check(prob, threshold, labels, False)
+    pred, true = _dist_masks(p, t, lab)
+    return _dist_transform(pred), _dist_transform(true)
+
+
+_DIST_SQUARES = np.arange(DIST_BINS, dtype=np.int64) ** 2
+
+
+def distance_bin(d2):
+    """bin(d2) of rsu_distance.h: min(r, DIST_BINS - 1) with r the smallest integer such that r * r >= d2, in integers (a search in the
+    table of squares); DIST_NONE lands in the last bin"""
+    return np.minimum(np.searchsorted(_DIST_SQUARES, np.asarray(d2, np.int64), side="left"), DIST_BINS - 1).astype(np.int64)
+
+
+def distance_hist(prob, threshold, labels):
+    """rsu_distance_hist on the host: int64 [2, DIST_BINS]; hist[0][b] = the pixels of P whose distance to T falls into bin b, hist[1][b] =
+    the pixels of T by their distance to P, summed over the images. An image without a counted pixel adds nothing."""
+    p, t, lab = _dist_check(prob, threshold, labels, True)
+    pred, true = _dist_masks(p, t, lab)
+    d2_pred, d2_true = _dist_transform(pred), _dist_transform(true)
+    hist = np.zeros((2, DIST_BINS), np.int64)
+    hist[0] = np.bincount(distance_bin(d2_true[pred]), minlength=DIST_BINS)
+    hist[1] = np.bincount(distance_bin(d2_pred[true]), minlength=DIST_BINS)
+    return hist
+
+
+def relaxed_metrics(hist, slack):
+    """The buffer-relaxed scores of Mnih & Hinton from a distance histogram (int [2, DIST_BINS], distance_hist / rsu_distance_hist) at
+    `slack` = rho pixels, an int in [0, DIST_BINS - 2]:
+      relaxed_precision = the share of predicted road pixels with a true road pixel within rho (sum(hist[0][:rho + 1]) / max(sum(hist[0]), 1)),
+      relaxed_recall    = the share of true road pixels with a predicted one within rho, likewise from hist[1],
+      relaxed_f1        = their harmonic mean, 0 when both are 0,
+      mean_dist_pred / mean_dist_true = the mean BIN INDEX of the predicted / true pixels: the distance rounded up to whole pixels and
+                          SATURATING at DIST_BINS - 1 = 63 (a pixel farther than 62 pixels away, or without any pixel of the other mask in
+                          its image, counts as 63), 0 without pixels,
+      far_pred / far_true = the share of them in that last bin.
+    At slack 0 the first two are the plain pixel precision and recall. Distances are per image: a road just outside a patch is not seen."""
+    h = np.asarray(hist)
+    if h.shape != (2, DIST_BINS) or h.dtype.kind not in "iu":
+        raise ValueError("relaxed_metrics: hist must be an integer array [2, %d], not %s %r" % (DIST_BINS, h.dtype, h.shape))
+    if isinstance(slack, bool) or not isinstance(slack, (int, np.integer)) or not 0 <= slack <= DIST_BINS - 2:
+        raise ValueError("relaxed_metrics: slack must be an integer in [0, %d], not %r" % (DIST_BINS - 2, slack))
+    h = h.astype(np.int64)
+    tot = [int(h[0].sum()), int(h[1].sum())]
+    precision, recall = [float(int(h[s][:int(slack) + 1].sum())) / max(tot[s], 1) for s in (0, 1)]
+    idx = np.arange(DIST_BINS, dtype=np.int64)
+    mean = [float(int((h[s] * idx).sum())) / max(tot[s], 1) for s in (0, 1)]
+    far = [float(int(h[s][-1])) / max(tot[s], 1) for s in (0, 1)]
+    f1 = 2.0 * precision * recall / (precision + recall) if precision + recall > 0.0 else 0.0
+    return {"relaxed_precision": precision, "relaxed_recall": recall, "relaxed_f1": f1, "mean_dist_pred": mean[0], "mean_dist_true": mean[1],
+            "far_pred": far[0], "far_true": far[1]}

@@ -19,6 +19,7 @@ import torch.distributed as dist
 from . import hostio
 from . import images as dimages
 from ._lib import call, lib
+from .hostio import DIST_BINS, DIST_MAX_SIDE, relaxed_metrics
 from .dist import GradBucketer, micro_indices, shard_indices, tune_overlap  # noqa: F401  (shard_indices: importable from here as before)
 from .pool import BatchUploader, DevicePatchPool, PatchPool
 from .summary import Summary
@@ -101,6 +102,15 @@ EXTRA_FLAG_DEFS = [
     ("validate_components", bool, False, "Count connected components during validation: evaluate() also returns components_pred, "
                                          "components_true and b0_error, the mean over the validation patches of |predicted - true| "
                                          "component counts (the error of the zeroth Betti number) at --component_connectivity"),
+    ("validate_distances", bool, False, "Measure distances during validation: evaluate() also returns dist_hist (the predicted road pixels "
+                                        "by their distance to the nearest true road pixel and the other way round, on the GPU: "
+                                        "rsu_distance.h) and from it the buffer-relaxed relaxed_precision, relaxed_recall and relaxed_f1 "
+                                        "of Mnih & Hinton at --relaxed_slack, mean_dist_pred / mean_dist_true and far_pred / far_true. "
+                                        "Distances are per validation patch: a true road just outside the patch is not seen"),
+    ("relaxed_slack", int, 3, "RHO, an int in [0, 62]: a predicted road pixel counts as correct when a true road pixel lies within RHO "
+                              "pixels, and a true one as found when a predicted one does (3 on the Massachusetts roads set; 0 = the plain "
+                              "pixel precision and recall). Used with --validate_distances"),
+    ("save_best_metric", str, "f1", "f1|relaxed_f1: the validation figure --save_best compares; relaxed_f1 requires --validate_distances"),
     ("border_weight", float, 0.0, "w0 >= 0 of a border-distance weight map computed on the GPU from each batch's labels: a pixel counts "
                                   "1 + w0 * exp(-d^2 / (2 border_sigma^2)) times in the loss, d its distance to the other class inside its patch; "
                                   "0 = off (the U-Net paper uses 10). The loss stays normalised by the pixel count and the mean weight is above 1, "
@@ -113,7 +123,7 @@ EXTRA_FLAG_DEFS = [
     ("validation_images", int, 0, "Hold out the last K training images, whole, as a validation set (0 = off); K must leave at least one "
                                   "training image, and --class_weights=balanced counts the remaining images only"),
     ("validate_every", int, 0, "Number of steps between validations on the held-out images; 0 = once at the end of each epoch"),
-    ("save_best", bool, False, "Keep <save_path>/<experiment>-best.chkpt, rewritten whenever the validation F1 improves"),
+    ("save_best", bool, False, "Keep <save_path>/<experiment>-best.chkpt, rewritten whenever the validation F1 (--save_best_metric) improves"),
     ("ema_decay", float, 0.0, "Decay d (0 <= d < 1) of an exponential moving average of the weights, tf.train.ExponentialMovingAverage, "
                               "updated on the GPU after every optimizer step; 0 = off. Validation, --save_best, prediction and the final "
                               "inference then use the averaged weights; checkpoints hold both the raw weights and the averages"),
@@ -279,6 +289,26 @@ def parse_component_connectivity(value):
     if not ok:
         raise ValueError("--component_connectivity must be 4 or 8, not %r" % (value,))
     return v
+
+
+def parse_relaxed_slack(value):
+    """The --relaxed_slack value as an int in [0, 62] (rsu_distance.h: bins 0 .. RSU_DIST_BINS - 2 are exact). Anything else raises
+    ValueError."""
+    try:
+        v = int(value)
+        ok = not isinstance(value, bool) and v == (float(value) if not isinstance(value, str) else v) and 0 <= v <= 62
+    except (TypeError, ValueError, OverflowError):
+        v, ok = 0, False
+    if not ok:
+        raise ValueError("--relaxed_slack must be an integer in [0, 62], not %r" % (value,))
+    return v
+
+
+def parse_save_best_metric(value):
+    """The --save_best_metric value: "f1" or "relaxed_f1". Anything else raises ValueError."""
+    if not isinstance(value, str) or value not in ("f1", "relaxed_f1"):
+        raise ValueError("--save_best_metric must be f1 or relaxed_f1, not %r" % (value,))
+    return value
 
 
 def parse_cldice_iters(value):
@@ -612,6 +642,11 @@ class Options(object):
         self.max_hole_area = parse_component_area(self.max_hole_area, "max_hole_area")
         self.component_connectivity = parse_component_connectivity(self.component_connectivity)
         self.validate_components = bool(self.validate_components)
+        self.validate_distances = bool(self.validate_distances)
+        self.relaxed_slack = parse_relaxed_slack(self.relaxed_slack)
+        self.save_best_metric = parse_save_best_metric(self.save_best_metric)
+        if self.save_best_metric == "relaxed_f1" and not self.validate_distances:
+            raise ValueError("--save_best_metric=relaxed_f1 requires --validate_distances: without it validation measures no distances")
         self.border_weight, self.border_sigma = parse_border_weight(self.border_weight), parse_border_sigma(self.border_sigma)
         self.clip_grad_norm = parse_clip_grad_norm(self.clip_grad_norm)
         self.ema_decay, self.ema_warmup = parse_ema_decay(self.ema_decay), bool(self.ema_warmup)
@@ -701,8 +736,10 @@ class ConvolutionalModel:
         self._summary = None
         self._pending_scalars = []
         self.best_val_f1 = None   # the best validation F1 seen by train() (--save_best keeps that model)
+        self.best_val_score = None   # the best validation --save_best_metric (the same figure unless it is relaxed_f1)
         self.last_postprocess_stats = None   # postprocess_masks: the summed stats of its last call (int64 [6])
         self._cc_acc = self._cc_ws = None    # --validate_components: the four counts and the workspace of rsu_components_pair_count
+        self._dt_acc = self._dt_ws = None    # --validate_distances: the 2 x 64 counters and the workspace of rsu_distance_hist
         if self.world > 1:
             self._bucketer = GradBucketer(self.net.flat_g, self.net.n_live)
             self._bucketer.extra_streams = list(self.net.wstreams)
@@ -869,6 +906,11 @@ class ConvolutionalModel:
         ride last in the same all-reduce and read-back (exact in float64 below 2^53), and the result gains "components_pred" and
         "components_true" (the predicted and true components summed over the patches, ignored pixels background in both) and
         "b0_error" = sum |predicted - true| / max(patches with a counted pixel, 1); the padding patches add exactly nothing.
+        With --validate_distances (only then) one rsu_distance_hist (rsu_distance.h) per chunk on net.prob and net.labels at `threshold`,
+        behind the head and the component count; its 128 integer counters ride last in the same all-reduce and read-back (exact in float64
+        below 2^53), and the result gains "dist_hist" (int64 [2, 64]: the predicted road pixels by their distance to the truth, the true
+        ones by theirs to the prediction) and the keys of hostio.relaxed_metrics of it at --relaxed_slack. Distances are per patch: a
+        true road just outside a patch is not seen. The padding patches add exactly nothing.
         averaged: None scores the averaged weights when the net has them (--ema_decay), True demands them (ValueError on a net without),
         False forces the raw weights; the device work runs inside net.averaged_weights(), and the result carries "averaged" (bool).
         Training is left as it was: weights, the averages and every packed copy (the exchange of averaged_weights() is undone), optimizer
@@ -893,6 +935,10 @@ class ConvolutionalModel:
                 if with_cc:
                     self._components_buffers()
                     self._cc_acc.zero_()
+                with_dt = bool(getattr(self._options, "validate_distances", False))
+                if with_dt:
+                    self._distance_buffers()
+                    self._dt_acc.zero_()
                 for t0 in range(lo, hi, B):
                     nb = min(B, hi - t0)
                     if nb < B:
@@ -913,6 +959,11 @@ class ConvolutionalModel:
                              ctypes.c_void_p(net.labels.data_ptr()), int(self._options.component_connectivity),
                              ctypes.c_void_p(self._cc_acc.data_ptr()), ctypes.c_void_p(self._cc_ws.data_ptr()), B, net.P, net.P,
                              ctypes.c_void_p(torch.cuda.current_stream(net.device).cuda_stream))
+                    if with_dt:
+                        call("rsu_distance_hist", ctypes.c_void_p(net.prob.data_ptr()), float(threshold),
+                             ctypes.c_void_p(net.labels.data_ptr()), ctypes.c_void_p(self._dt_acc.data_ptr()),
+                             ctypes.c_void_p(self._dt_ws.data_ptr()), B, net.P, net.P,
+                             ctypes.c_void_p(torch.cuda.current_stream(net.device).cuda_stream))
                 sums, hist = net.eval_sums.to(torch.float64), net.eval_hist.clone()
                 with_cl = net.cldice_weight > 0.0
                 if with_cl:   # the four clDice sums ride behind the five of the head: one all-reduce, one read-back
@@ -922,10 +973,15 @@ class ConvolutionalModel:
                     sums = torch.cat([sums, net.eval_lovasz_sum.to(torch.float64)])
                 if with_cc:   # and the four component counts behind everything else
                     sums = torch.cat([sums, self._cc_acc.to(torch.float64)])
+                if with_dt:   # and the 2 x 64 distance counters last of all
+                    sums = torch.cat([sums, self._dt_acc.to(torch.float64)])
                 if self.world > 1:
                     dist.all_reduce(sums)
                     dist.all_reduce(hist)
                 sums, hist = sums.cpu().numpy(), hist.cpu().numpy()   # the one synchronisation
+                dt_sums = sums[-2 * DIST_BINS:] if with_dt else None
+                if with_dt:
+                    sums = sums[:-2 * DIST_BINS]
                 cc_sums = sums[-4:] if with_cc else None
                 if with_cc:
                     sums = sums[:-4]
@@ -947,7 +1003,21 @@ class ConvolutionalModel:
         if with_cc:
             out["components_pred"], out["components_true"] = int(cc_sums[0]), int(cc_sums[1])
             out["b0_error"] = float(cc_sums[2]) / max(float(cc_sums[3]), 1.0)
+        if with_dt:
+            out["dist_hist"] = np.rint(dt_sums).astype(np.int64).reshape(2, DIST_BINS)
+            out.update(relaxed_metrics(out["dist_hist"], int(self._options.relaxed_slack)))
         return out
+
+    def _distance_buffers(self):
+        """the device buffers of --validate_distances, made when evaluate() first needs them: the 2 x 64 counters and the workspace"""
+        if self._dt_acc is None:
+            net = self.net
+            need = int(lib().rsu_distance_ws_bytes(self.local_batch, net.P, net.P))
+            if need == 0 or self.local_batch * net.P * net.P * 8 >= 0x7ffffff0:
+                raise ValueError("--validate_distances: a batch of %d patches of %d x %d pixels is outside rsu_distance.h's limits (sides "
+                                 "up to %d, the labels below 2 GiB)" % (self.local_batch, net.P, net.P, DIST_MAX_SIDE))
+            self._dt_acc = torch.zeros(2 * DIST_BINS, dtype=torch.int64, device=net.device)
+            self._dt_ws = torch.zeros(need // 4, dtype=torch.int32, device=net.device)
 
     def _components_buffers(self):
         """the device buffers of --validate_components, made when evaluate() first needs them: the four counts and the workspace"""
@@ -972,6 +1042,11 @@ class ConvolutionalModel:
             if "b0_error" in v:
                 print("step {} validation components: predicted {} true {} b0_error {:.4f}".format(step, v["components_pred"],
                                                                                                  v["components_true"], v["b0_error"]))
+            if "relaxed_f1" in v:
+                print("step {} validation distances: relaxed f1 {:.4f} precision {:.4f} recall {:.4f} at slack {}; mean distance predicted "
+                      "{:.3f} true {:.3f}; beyond 62 pixels: predicted {:.4f} true {:.4f}"
+                      .format(step, v["relaxed_f1"], v["relaxed_precision"], v["relaxed_recall"], opts.relaxed_slack, v["mean_dist_pred"],
+                              v["mean_dist_true"], v["far_pred"], v["far_true"]))
             if self._summary is not None:
                 self._summary.add({"val_loss": v["loss"], "val_objective": v["objective"], "val_dice": v["dice"], "val_f1": v["f1"],
                                    "val_iou": v["iou"], "val_best_threshold": v["best_threshold"]}, global_step=step)
@@ -981,11 +1056,19 @@ class ConvolutionalModel:
                     self._summary.add({"val_lovasz": v["lovasz"]}, global_step=step)
                 if "b0_error" in v:
                     self._summary.add({"val_b0_error": v["b0_error"]}, global_step=step)
-        if self.best_val_f1 is None or v["f1"] > self.best_val_f1:   # (the same numbers on every rank: they come out of the all-reduce)
+                if "relaxed_f1" in v:
+                    self._summary.add({"val_relaxed_f1": v["relaxed_f1"], "val_relaxed_precision": v["relaxed_precision"],
+                                       "val_relaxed_recall": v["relaxed_recall"], "val_mean_dist_pred": v["mean_dist_pred"],
+                                       "val_mean_dist_true": v["mean_dist_true"]}, global_step=step)
+        # (the same numbers on every rank: they come out of the all-reduce)
+        if self.best_val_f1 is None or v["f1"] > self.best_val_f1:
             self.best_val_f1 = v["f1"]
+        score = v[getattr(opts, "save_best_metric", "f1")]   # what --save_best compares: with the default v["f1"], and best_val_score is best_val_f1
+        if self.best_val_score is None or score > self.best_val_score:
+            self.best_val_score = score
             if opts.save_best:
                 self.save_as(os.path.abspath(os.path.join(opts.save_path, self.experiment_name + "-best.chkpt")))
-        return {k: v[k] for k in v if k not in ("sums", "hist", "cldice_sums")}
+        return {k: v[k] for k in v if k not in ("sums", "hist", "cldice_sums", "dist_hist")}
 
     def _ensure_summary(self):
         opts = self._options
