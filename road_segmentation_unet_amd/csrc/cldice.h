@@ -1,6 +1,7 @@
-// cldice.hip: the clDice term (include/rsu_cldice.h): the fused soft-skeleton forward and backward and the head that takes d objective / d prob
+// cldice.hip: the clDice term (include/rsu_cldice.h): the fused soft-skeleton forward and backward. (The head that takes their
+// d objective / d prob, rsu_head_fwd_bwd_aux, is head.hip's hd_train.)
 #pragma once
-#include "elementwise.h"
+#include "head.h"   // head_final_sum: k_cldice_final sums the tiles' partials as the heads' final kernels do
 
 constexpr int CL_MAX_ITERS = 16;   // rsu_cldice.h RSU_CLDICE_MAX_ITERS
 constexpr int CL_FWD_TILE = 32;    // the forward's tile side: one workgroup per tile, one row of four partial sums per workgroup
@@ -13,8 +14,3 @@ hipError_t cl_fwd(const float* prob, const int64_t* labels, int iters, float* sk
                   hipStream_t st);
 hipError_t cl_bwd(const float* prob, const int64_t* labels, const float* skel_y, const float* sums, int iters, float scale, float smooth,
                   float* gprob, const float* ws, int B, int H, int W, hipStream_t st);
-// the training head with a given d objective / d prob (rsu_head_fwd_bwd_aux): ew_head_loss's / ew_head_focal's grid, workspace and final
-// kernel; gamma == 0 takes the cross-entropy lines of k_head_loss
-hipError_t cl_head_aux(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w, const float* pixel_w,
-                       float gamma, const float* dice_sums, float dice_scale, float smooth, const float* gprob, float* prob, void* dact, float* dw,
-                       float* db, float* loss_sum, float* weight_sum, float* ws, long npix, int C, float inv_count, hipStream_t st);

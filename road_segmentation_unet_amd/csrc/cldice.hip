@@ -1,7 +1,5 @@
 #include "cldice.h"
 
-#include "head_stages.h"
-
 // The clDice term (include/rsu_cldice.h; Shit et al., CVPR 2021): scale * (1 - clD) from the soft skeletons of the prob map and of the label
 // map. Per map x [H][W] (an image on its own: no window crosses into another), float32, one rounding per operation (nothing here is
 // contracted into a fused multiply-add: hostio.soft_skeleton restates the maps bit for bit):
@@ -302,138 +300,6 @@ __global__ void __launch_bounds__(256) k_cldice_bwd(const float* __restrict__ pr
     }
 }
 
-// ---- the training head that takes d objective / d prob (rsu_head_fwd_bwd_aux): k_head_focal<DICE> (loss.hip) and, with FOCAL == false, the
-// cross-entropy lines of k_head_loss<DICE> (elementwise.hip), with one more line: through p1 = softmax(z)[1], d p1 / d z1 = p0 p1 = -d p1 / d z0,
-// a counted pixel's gprob reaches its logits in front of dact, dw and db. An ignored pixel's gprob is never loaded. loss_sum and weight_sum stay
-// the cross-entropy part; grid, pixel-to-thread mapping, load batching, block reduce and the 2 C + 4 partials are the family's, so
-// k_head_final_loss finishes it. gprob is loaded where it is used, not with the batch: the batch's registers are the family's.
-// The cross-entropy instantiations keep two independent dlogits where the focal ones keep +-g: at 4 waves per SIMD (128 VGPRs) they spilled
-// 4 and 8 registers to scratch, so they ask for 3 (the kernel is HBM-bound); the focal ones fit 128 as k_head_focal does.
-static __device__ __forceinline__ void head_focal_aux(bool lab, float l0, float l1, float m, float s, float p0, float p1, float gamma, float& fce,
-                                                      float& fg) {
-#pragma clang fp contract(off)
-    const float pt = lab ? p1 : p0, po = lab ? p0 : p1;
-    const float ce = -((lab ? l1 : l0) - m - logf(s));
-    const float F = exp2f(gamma * log2f(po));
-    fce = F * ce;
-    fg = F * fmaf(gamma * pt, ce, po);
-}
-template <bool FOCAL, bool DICE>
-__global__ void __launch_bounds__(256, FOCAL ? 4 : 3) k_head_aux(const bf16_t* __restrict__ act, const float* __restrict__ w, const float* __restrict__ b,
-                                                  const int64_t* __restrict__ labels, const float* __restrict__ class_w,
-                                                  const float* __restrict__ pixel_w, float gamma, const float* __restrict__ dice_sums,
-                                                  float dice_scale, float smooth, const float* __restrict__ gprob, float* __restrict__ prob,
-                                                  bf16_t* __restrict__ dact, float* __restrict__ partial, long npix, int C, float inv_count) {
-    const int LP = C >> 3;
-    const int sub = threadIdx.x % LP;
-    const int ppb = 256 / LP;  // pixels per block iteration
-    float w0[8], w1[8], b0, b1;
-    head_setup(w, b, sub, w0, w1, b0, b1);
-    const float cw0 = class_w ? class_w[0] : 1.f, cw1 = class_w ? class_w[1] : 1.f;
-    float gq0 = 0.f, gq1 = 0.f;
-    if constexpr (DICE) {   // k_head_loss<true>'s two uniform factors
-        const float dU = dice_sums[1] + dice_sums[2] + smooth;
-        const float dD = (2.f * dice_sums[0] + smooth) / dU;
-        gq0 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(dice_scale * dD / dU)));
-        gq1 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(dice_scale * (dD - 2.f) / dU)));
-    }
-    float gw0[8], gw1[8], gb0 = 0.f, gb1 = 0.f, lsum = 0.f, osum = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) gw0[i] = gw1[i] = 0.f;
-    const int niter = (int)((npix + (long)gridDim.x * ppb - 1) / ((long)gridDim.x * ppb));
-    for (int it0 = 0; it0 < niter; it0 += HEAD_HU) {
-        long pp[HEAD_HU];
-        bool okk[HEAD_HU];
-        u32x4 raw[HEAD_HU];
-        int64_t labv[HEAD_HU];
-        float pwv[HEAD_HU];
-        head_load<int>(act, labels, pixel_w, it0, niter, npix, C, LP, sub, ppb, pp, okk, raw, labv, pwv);
-#pragma unroll
-        for (int u = 0; u < HEAD_HU; ++u) {
-            const long p = pp[u];
-            const bool ok = okk[u];
-            float a[8], l0, l1, m, s, p0, p1;
-            head_softmax(raw[u], w0, w1, b0, b1, LP, a, l0, l1, m, s, p0, p1);
-            if (ok && sub == 0) prob[p] = p1;
-            if (!ok) continue;
-            const int64_t lab = labv[u];
-            if (lab != 0 && lab != 1) {   // ignored
-                *(u32x4*)(dact + p * C + sub * 8) = u32x4{0u, 0u, 0u, 0u};
-                continue;
-            }
-            const float ga = gprob[p] * (p0 * p1);
-            const float omega = (lab ? cw1 : cw0) * pwv[u];
-            float d0, d1, fce = 0.f;
-            if constexpr (FOCAL) {
-                float fg;
-                head_focal_aux(lab != 0, l0, l1, m, s, p0, p1, gamma, fce, fg);
-                const float g = (omega * inv_count) * fg;
-                d0 = lab ? g : -g;
-                d1 = lab ? -g : g;
-            } else {
-                d0 = (p0 - (lab == 0 ? 1.f : 0.f)) * inv_count * omega;
-                d1 = (p1 - (lab == 1 ? 1.f : 0.f)) * inv_count * omega;
-                fce = -((lab ? l1 : l0) - m - logf(s));   // (formed here: l0, l1, m and s need not live through the pixel's backward)
-            }
-            if constexpr (DICE) {
-                const float gt = pwv[u] * (p0 * p1);
-                if constexpr (FOCAL) {
-                    // k_head_focal<true> compiles its `d0 -= gd; d1 += gd` into one fused multiply-add each; behind the lines below the
-                    // compiler rounded the product first. Written out, so that a zero gprob leaves that kernel's numbers
-                    const float gq = lab ? gq1 : gq0;
-                    d0 = fmaf(-gt, gq, d0);
-                    d1 = fmaf(gt, gq, d1);
-                } else {
-                    const float gd = lab ? gt * gq1 : gt * gq0;
-                    d0 -= gd;
-                    d1 += gd;
-                }
-            }
-            d0 -= ga;
-            d1 += ga;
-            // the pixel's backward: weight gradients, and dact through the ReLU in front of the head
-            float da[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                gw0[i] = fmaf(a[i], d0, gw0[i]);
-                gw1[i] = fmaf(a[i], d1, gw1[i]);
-                da[i] = a[i] > 0.f ? fmaf(d0, w0[i], d1 * w1[i]) : 0.f;
-            }
-            *(u32x4*)(dact + p * C + sub * 8) = pack8(da);
-            if (sub == 0) {
-                if constexpr (FOCAL) {
-#pragma clang fp contract(off)
-                    gb0 += d0;
-                    gb1 += d1;
-                    lsum = fmaf(fce, omega, lsum);
-                    osum += omega;
-                } else {
-                    gb0 += d0;
-                    gb1 += d1;
-                    lsum += omega * fce;
-                    osum += omega;
-                }
-            }
-        }
-    }
-    constexpr int NV = 21;
-    __shared__ float red[256 * NV];
-    float* my = red + threadIdx.x * NV;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        my[i] = gw0[i];
-        my[8 + i] = gw1[i];
-    }
-    my[16] = gb0; my[17] = gb1; my[18] = lsum; my[19] = osum;
-    __syncthreads();
-    const int nout = 2 * C + 4;  // [C][2] dw, db[2], loss, weight sum
-    for (int o = threadIdx.x; o < nout; o += 256) {
-        const int c = o >> 1;
-        partial[(long)blockIdx.x * nout + o] = o < 2 * C ? head_block_sum<NV>(red, c >> 3, (o & 1) * 8 + (c & 7), ppb, LP)
-                                                         : head_block_sum<NV>(red, 0, 16 + (o - 2 * C), ppb, LP);
-    }
-}
-
 // ---- host-side launchers
 static inline int cl_cdiv(int a, int b) { return (a + b - 1) / b; }
 long cl_fwd_tiles(int B, int H, int W) { return (long)B * cl_cdiv(H, CL_FWD_TILE) * cl_cdiv(W, CL_FWD_TILE); }
@@ -456,15 +322,4 @@ hipError_t cl_bwd(const float* prob, const int64_t* labels, const float* skel_y,
     hipLaunchKernelGGL(k_cldice_bwd, dim3((unsigned)((long)B * tiles_x * tiles_y)), dim3(256), 0, st, prob, labels, skel_y, sums, ws, iters, scale,
                        smooth, gprob, H, W, tiles_x, tiles_y, N);
     return hipGetLastError();
-}
-hipError_t cl_head_aux(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w, const float* pixel_w,
-                       float gamma, const float* dice_sums, float dice_scale, float smooth, const float* gprob, float* prob, void* dact, float* dw,
-                       float* db, float* loss_sum, float* weight_sum, float* ws, long npix, int C, float inv_count, hipStream_t st) {
-    const int nb = ew_head_blocks(npix, C);
-    auto kern = gamma > 0.f ? (dice_sums ? k_head_aux<true, true> : k_head_aux<true, false>)
-                            : (dice_sums ? k_head_aux<false, true> : k_head_aux<false, false>);
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(256), 0, st, (const bf16_t*)act, w, b, labels, class_w, pixel_w, gamma, dice_sums, dice_scale, smooth,
-                       gprob, prob, (bf16_t*)dact, ws, npix, C, inv_count);
-    const hipError_t e = hipGetLastError();
-    return e != hipSuccess ? e : ew_head_final_loss(ws, dw, db, loss_sum, weight_sum, nb, C, st);
 }

@@ -31,28 +31,6 @@ struct ReduceJob {
 };
 int ew_reduce_job_blocks(ReduceJob& j);   // sets j.wide, returns the workgroups the job needs
 hipError_t ew_reduce_slabs_many(const ReduceJob* jobs_dev, int njobs, int total_blocks, hipStream_t st);
-int ew_head_blocks(long npix, int C);
-hipError_t ew_head(bool train, const void* act, const float* w, const float* b, const int64_t* labels, float* prob, float* logits, void* dact, float* dw,
-                   float* db, float* loss_sum, float* ws, long npix, int C, float inv_count, hipStream_t st);
-// the weighted training head and pass B of the soft-Dice head (rsu.h rsu_head_fwd_bwd_w, rsu_head_fwd_bwd_dice): same grid, ws of
-// ew_head_blocks() * (2 C + 4) floats; dice_sums == nullptr: no Dice term (dice_scale and smooth are not read)
-hipError_t ew_head_loss(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w, const float* pixel_w,
-                        const float* dice_sums, float dice_scale, float smooth, float* prob, void* dact, float* dw, float* db, float* loss_sum,
-                        float* weight_sum, float* ws, long npix, int C, float inv_count, hipStream_t st);
-// pass A of the soft-Dice head (rsu.h rsu_head_dice_sums): same grid, ws of ew_head_blocks() * 3 floats
-hipError_t ew_head_dice_sums(const void* act, const float* w, const float* b, const int64_t* labels, const float* pixel_w, float* prob,
-                             float* dice_sums, float* ws, long npix, int C, hipStream_t st);
-// the evaluation head (rsu.h rsu_head_eval): same grid, forward only; ws of ew_head_eval_ws_floats() floats (5 partial sums and one
-// 2 x EW_EVAL_BINS row of u32 counters per workgroup). EW_EVAL_BINS is rsu.h's RSU_EVAL_BINS.
-constexpr int EW_EVAL_BINS = 256;
-constexpr int EW_EVAL_SLICES = 8;   // k_head_eval_final: workgroups per 64-bin group (= adds per address of hist per call)
-size_t ew_head_eval_ws_floats(long npix, int C);
-hipError_t ew_head_eval(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w, const float* pixel_w,
-                        float* prob, float* sums, unsigned long long* hist, float* ws, long npix, int C, hipStream_t st);
-// the final launches of ew_head_loss (k_head_final_loss over [nblk][2 C + 4] partials) and of ew_head_eval (k_head_eval_final over
-// [nblk][5] partials and the [nblk][2][EW_EVAL_BINS] rows) alone: the focal heads of loss.h end with them
-hipError_t ew_head_final_loss(const float* ws, float* dw, float* db, float* loss_sum, float* weight_sum, int nblk, int C, hipStream_t st);
-hipError_t ew_head_eval_final(const float* ws, const unsigned* hpart, float* sums, unsigned long long* hist, int nblk, hipStream_t st);
 hipError_t ew_color_adjust_bwd(const float* gx, const float* w1, float* dW0, float* db0, int Cout, float scale, int accumulate, hipStream_t st);
 hipError_t ew_pack(const float* src, void* dst, const PackParams& pp, hipStream_t st);
 struct PackJob { PackParams pp; const float* src; bf16_t* dst; int block_start; int pad_; };

@@ -1,10 +1,6 @@
 // HBM-bound kernels of the U-Net path: 16-byte (8 x bf16) accesses per lane everywhere, coalesced along
-// the channel axis of NHWC; wave-level shuffles for the per-pixel reductions of the head.
+// the channel axis of NHWC. (The head of the net is head.hip.)
 #include "elementwise.h"
-
-#include <type_traits>
-
-#include "head_stages.h"
 
 // ---------------------------------------------------------------------------------------------
 // unet.py:22-23  color_space_adjust
@@ -404,397 +400,6 @@ __global__ void __launch_bounds__(256) k_reduce_slabs_many(const ReduceJob* __re
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// head: 1x1 conv (C -> 2) + softmax[...,1] (+ mean CE loss and its backward)
-// LP = C/8 lanes per pixel, partial logits reduced with wave shuffles
-// Two sets of kernels. k_head<TRAIN> and k_head_final are PINNED: the unweighted step is on the critical queue, and sharing k_head's body
-// through an inlined function template moved its register allocation (1500 of 1585 ISA lines), so they are written out and nothing
-// below is shared with them. The opt-in heads form one family built from the head_* device helpers of head_stages.h (per-thread setup, the batched
-// load, logits + softmax, the LDS block reduce, the final kernels' sum): k_head_loss<DICE> (weighted training head / pass B of the
-// soft-Dice head) with k_head_final_loss, and the forward-only k_head_sums<EVAL> (pass A of the soft-Dice head / the evaluation head)
-// with k_head_final_dice_sums and k_head_eval_final. Their grid, pixel-to-thread mapping and the order of every sum are k_head<true>'s.
-// The focal members of the family, k_head_focal<DICE> and k_head_sums_focal (rsu_loss.h), are in loss.hip: inside this file they changed
-// 29 lines of address arithmetic in k_head_sums<true>'s block reduce, and every kernel here keeps the ISA it shipped with.
-// ---------------------------------------------------------------------------------------------
-template <bool TRAIN>
-__global__ void __launch_bounds__(256) k_head(const bf16_t* __restrict__ act, const float* __restrict__ w, const float* __restrict__ b,
-                                              const int64_t* __restrict__ labels, float* __restrict__ prob, float* __restrict__ logits,
-                                              bf16_t* __restrict__ dact, float* __restrict__ partial, long npix, int C, float inv_count) {
-    const int LP = C >> 3;
-    const int sub = threadIdx.x % LP;
-    const int ppb = 256 / LP;  // pixels per block iteration
-    float w0[8], w1[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        w0[i] = w[(sub * 8 + i) * 2];
-        w1[i] = w[(sub * 8 + i) * 2 + 1];
-    }
-    const float b0 = b[0], b1 = b[1];
-    float gw0[8], gw1[8], gb0 = 0.f, gb1 = 0.f, lsum = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) gw0[i] = gw1[i] = 0.f;
-    const long niter = (npix + (long)gridDim.x * ppb - 1) / ((long)gridDim.x * ppb);
-    // HU pixels per thread and trip, all loads requested before any is used: the HBM latency (~2 us x 6 TB/s = 47 KB per CU in flight) wants more
-    // than the 16-32 KB that one or two 16-byte loads per lane of 16-20 resident waves give (round 5: two, 3.87 TB/s; round 6: four). The sums keep
-    // the order of the pixels: same bits.
-    constexpr int HU = 4;
-    for (long it0 = 0; it0 < niter; it0 += HU) {
-        long pp[HU];
-        bool okk[HU];
-        u32x4 raw[HU];
-        int labv[HU];
-#pragma unroll
-        for (int u = 0; u < HU; ++u) {
-            labv[u] = 0;
-            pp[u] = ((it0 + u) * gridDim.x + blockIdx.x) * ppb + threadIdx.x / LP;
-            okk[u] = (it0 + u < niter) && pp[u] < npix;
-            raw[u] = okk[u] ? *(const u32x4*)(act + pp[u] * C + sub * 8) : u32x4{0u, 0u, 0u, 0u};
-            if (TRAIN) labv[u] = okk[u] ? (int)labels[pp[u]] : 0;
-        }
-#pragma unroll
-        for (int u = 0; u < HU; ++u) {
-            const long p = pp[u];
-            const bool ok = okk[u];
-            float a[8];
-            unpack8(raw[u], a);
-            float l0 = 0.f, l1 = 0.f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                l0 = fmaf(a[i], w0[i], l0);
-                l1 = fmaf(a[i], w1[i], l1);
-            }
-            for (int o = 1; o < LP; o <<= 1) {
-                l0 += __shfl_xor(l0, o);
-                l1 += __shfl_xor(l1, o);
-            }
-            l0 += b0;
-            l1 += b1;
-            const float m = fmaxf(l0, l1);
-            const float e0 = expf(l0 - m), e1 = expf(l1 - m);
-            const float s = e0 + e1;
-            const float p1 = e1 / s, p0 = e0 / s;
-            if (ok && sub == 0) {
-                prob[p] = p1;
-                if (logits) {
-                    logits[2 * p] = l0;
-                    logits[2 * p + 1] = l1;
-                }
-            }
-            if (TRAIN) {
-                if (ok) {
-                    const int lab = labv[u];
-                    const float d0 = (p0 - (lab == 0 ? 1.f : 0.f)) * inv_count;
-                    const float d1 = (p1 - (lab == 1 ? 1.f : 0.f)) * inv_count;
-                    float da[8];
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        gw0[i] = fmaf(a[i], d0, gw0[i]);
-                        gw1[i] = fmaf(a[i], d1, gw1[i]);
-                        da[i] = a[i] > 0.f ? fmaf(d0, w0[i], d1 * w1[i]) : 0.f;
-                    }
-                    *(u32x4*)(dact + p * C + sub * 8) = pack8(da);
-                    if (sub == 0) {
-                        gb0 += d0;
-                        gb1 += d1;
-                        lsum += -((lab ? l1 : l0) - m - logf(s));
-                    }
-                }
-            }
-        }
-    }
-    if (TRAIN) {
-        // block reduce: threads with equal `sub` hold partials for the same 8 channels
-        __shared__ float red[256 * 19];
-        float* my = red + threadIdx.x * 19;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            my[i] = gw0[i];
-            my[8 + i] = gw1[i];
-        }
-        my[16] = gb0; my[17] = gb1; my[18] = lsum;
-        __syncthreads();
-        const int nout = 2 * C + 3;  // [C][2] dw, db[2], loss
-        for (int o = threadIdx.x; o < nout; o += 256) {
-            float t = 0.f;
-            if (o < 2 * C) {
-                const int c = o >> 1, k = o & 1, sg = c >> 3, i = c & 7;
-                for (int q = 0; q < ppb; ++q) t += red[(q * LP + sg) * 19 + k * 8 + i];
-            } else {
-                const int j = 16 + (o - 2 * C);
-                for (int q = 0; q < ppb; ++q) t += red[(q * LP) * 19 + j];
-            }
-            partial[(long)blockIdx.x * nout + o] = t;
-        }
-    }
-}
-template __global__ void k_head<true>(const bf16_t*, const float*, const float*, const int64_t*, float*, float*, bf16_t*, float*, long, int, float);
-template __global__ void k_head<false>(const bf16_t*, const float*, const float*, const int64_t*, float*, float*, bf16_t*, float*, long, int, float);
-
-__global__ void __launch_bounds__(256) k_head_final(const float* __restrict__ partial, float* __restrict__ dw, float* __restrict__ db,
-                                                    float* __restrict__ loss_sum, int nblk, int C) {
-    // one wave per output (four per workgroup): lane l sums partials l, l + 64, ... (independent loads), then a fixed-order butterfly;
-    // 2 C + 3 outputs of ~1000 partials each -- with 32 lanes per output in 17 workgroups the kernel was a chain of ~32 dependent
-    // L2 round trips (11 us)
-    const int nout = 2 * C + 3;
-    const int o = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (o >= nout) return;
-    float t = 0.f;
-    for (int bk = lane; bk < nblk; bk += 64) t += partial[(long)bk * nout + o];
-    for (int m = 32; m > 0; m >>= 1) t += __shfl_xor(t, m);
-    if (lane == 0) {
-        if (o < 2 * C) dw[o] = t;
-        else if (o < 2 * C + 2) db[o - 2 * C] = t;
-        else loss_sum[0] += t;
-    }
-}
-
-// (the family's shared stages -- head_setup / head_load / head_softmax / head_block_sum / head_final_sum -- are in head_stages.h: loss.hip
-// builds the focal members from them)
-// The training heads with weights. k_head_loss<false> (rsu.h rsu_head_fwd_bwd_w): k_head<true> with omega = class_w[label] * pixel_w[pixel]
-// in front of the pixel's loss and dlogits. A label that is neither 0 nor 1 (tested on all 64 bits) means omega = 0 BY SELECTION, never by
-// multiplication: the pixel's dact row is stored as +0 and it is left out of every sum, whatever its pixel_w holds. One more per-thread sum
-// (omega -> weight_sum) rides through the block reduce: 2 C + 4 partials per block. Grid, pixel-to-thread mapping and the order of every sum
-// are k_head<true>'s, and x * 1.0f is exact: with every omega == 1 the outputs have its bits (tests/test_gpu_weighted_loss.py).
-// k_head_loss<true> (rsu.h rsu_head_fwd_bwd_dice, pass B of the soft-Dice head) adds, for every counted pixel, the gradient of
-// dice_scale * (1 - D) wrt its logits,
-//   g = dice_scale * m (D - 2 y) / U * p0 p1   added to dlogit 1 and taken from dlogit 0,   U = P + Y + smooth, D = (2 I + smooth) / U,
-// in front of the weight / bias gradients and dact. {I, P, Y} are READ from dice_sums (three uniform loads per thread; what pass A left
-// there, or what a host made of it): nothing is recomputed here. The class weights do not enter g; loss_sum and weight_sum keep their
-// cross-entropy meaning. <false> never touches dice_sums, dice_scale or smooth.
-// 4 waves per SIMD asked for (<= 128 VGPRs, k_head<true>'s occupancy): the 64-bit labels and the weights in flight cost 131 without.
-template <bool DICE>
-__global__ void __launch_bounds__(256, 4) k_head_loss(const bf16_t* __restrict__ act, const float* __restrict__ w, const float* __restrict__ b,
-                                                   const int64_t* __restrict__ labels, const float* __restrict__ class_w,
-                                                   const float* __restrict__ pixel_w, const float* __restrict__ dice_sums, float dice_scale,
-                                                   float smooth, float* __restrict__ prob, bf16_t* __restrict__ dact,
-                                                   float* __restrict__ partial, long npix, int C, float inv_count) {
-    const int LP = C >> 3;
-    const int sub = threadIdx.x % LP;
-    const int ppb = 256 / LP;  // pixels per block iteration
-    float w0[8], w1[8], b0, b1;
-    head_setup(w, b, sub, w0, w1, b0, b1);
-    const float cw0 = class_w ? class_w[0] : 1.f, cw1 = class_w ? class_w[1] : 1.f;
-    float gq0 = 0.f, gq1 = 0.f;
-    if constexpr (DICE) {
-        const float dU = dice_sums[1] + dice_sums[2] + smooth;
-        const float dD = (2.f * dice_sums[0] + smooth) / dU;
-        // dice_scale (D - 2 y) / U for y = 0 and y = 1: the same in every lane, so kept in scalar registers and multiplied in before the
-        // label selects (a select between the two would copy one into a vector register). <false> sits at 128 VGPRs, <true> has none to
-        // spare at 4 waves per SIMD: with the two factors as plain floats and a 64-bit trip count it spilled 7 registers to scratch.
-        gq0 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(dice_scale * dD / dU)));
-        gq1 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(dice_scale * (dD - 2.f) / dU)));
-    }
-    float gw0[8], gw1[8], gb0 = 0.f, gb1 = 0.f, lsum = 0.f, osum = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) gw0[i] = gw1[i] = 0.f;
-    // (<true>: a 32-bit trip count: at most 8 below 1024 blocks, npix / (1024 ppb) above; two vector registers less than the 64-bit one,
-    // which <false> keeps: its code is the one that shipped)
-    using IT = std::conditional_t<DICE, int, long>;
-    const IT niter = (IT)((npix + (long)gridDim.x * ppb - 1) / ((long)gridDim.x * ppb));
-    for (IT it0 = 0; it0 < niter; it0 += HEAD_HU) {
-        long pp[HEAD_HU];
-        bool okk[HEAD_HU];
-        u32x4 raw[HEAD_HU];
-        int64_t labv[HEAD_HU];
-        float pwv[HEAD_HU];
-        head_load<IT>(act, labels, pixel_w, it0, niter, npix, C, LP, sub, ppb, pp, okk, raw, labv, pwv);
-#pragma unroll
-        for (int u = 0; u < HEAD_HU; ++u) {
-            const long p = pp[u];
-            const bool ok = okk[u];
-            float a[8], l0, l1, m, s, p0, p1;
-            head_softmax(raw[u], w0, w1, b0, b1, LP, a, l0, l1, m, s, p0, p1);
-            if (ok && sub == 0) prob[p] = p1;
-            if (!ok) continue;
-            const int64_t lab = labv[u];
-            if (lab != 0 && lab != 1) {   // ignored
-                *(u32x4*)(dact + p * C + sub * 8) = u32x4{0u, 0u, 0u, 0u};
-                continue;
-            }
-            const float omega = (lab ? cw1 : cw0) * pwv[u];
-            float d0 = (p0 - (lab == 0 ? 1.f : 0.f)) * inv_count * omega;
-            float d1 = (p1 - (lab == 1 ? 1.f : 0.f)) * inv_count * omega;
-            if constexpr (DICE) {
-                const float gt = pwv[u] * (p0 * p1);
-                const float g = lab ? gt * gq1 : gt * gq0;
-                d0 -= g;
-                d1 += g;
-            }
-            // the pixel's backward: weight gradients, and dact through the ReLU in front of the head
-            float da[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                gw0[i] = fmaf(a[i], d0, gw0[i]);
-                gw1[i] = fmaf(a[i], d1, gw1[i]);
-                da[i] = a[i] > 0.f ? fmaf(d0, w0[i], d1 * w1[i]) : 0.f;
-            }
-            *(u32x4*)(dact + p * C + sub * 8) = pack8(da);
-            if (sub == 0) {
-                gb0 += d0;
-                gb1 += d1;
-                lsum += omega * -((lab ? l1 : l0) - m - logf(s));
-                osum += omega;
-            }
-        }
-    }
-    // block reduce as in k_head, one more value per thread: threads with equal `sub` hold partials for the same 8 channels
-    constexpr int NV = 21;
-    __shared__ float red[256 * NV];
-    float* my = red + threadIdx.x * NV;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        my[i] = gw0[i];
-        my[8 + i] = gw1[i];
-    }
-    my[16] = gb0; my[17] = gb1; my[18] = lsum; my[19] = osum;
-    __syncthreads();
-    const int nout = 2 * C + 4;  // [C][2] dw, db[2], loss, weight sum
-    for (int o = threadIdx.x; o < nout; o += 256) {
-        const int c = o >> 1;
-        partial[(long)blockIdx.x * nout + o] = o < 2 * C ? head_block_sum<NV>(red, c >> 3, (o & 1) * 8 + (c & 7), ppb, LP)
-                                                         : head_block_sum<NV>(red, 0, 16 + (o - 2 * C), ppb, LP);
-    }
-}
-// k_head_final over 2 C + 4 outputs: the last one is the sum of the weights (weight_sum may be NULL: not wanted). Same lanes, same order.
-__global__ void __launch_bounds__(256) k_head_final_loss(const float* __restrict__ partial, float* __restrict__ dw, float* __restrict__ db,
-                                                         float* __restrict__ loss_sum, float* __restrict__ weight_sum, int nblk, int C) {
-    const int nout = 2 * C + 4;
-    const int o = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (o >= nout) return;
-    const float t = head_final_sum(partial, nblk, nout, o, lane);
-    if (lane == 0) {
-        if (o < 2 * C) dw[o] = t;
-        else if (o < 2 * C + 2) db[o - 2 * C] = t;
-        else if (o == 2 * C + 2) loss_sum[0] += t;
-        else if (weight_sum) weight_sum[0] += t;
-    }
-}
-
-// The forward-only heads: k_head_loss's grid, pixel-to-thread mapping, load batching and logit / softmax expressions (prob gets the same
-// bits); no dact, no dw, no db. Per thread (the sub == 0 lane of a pixel) the sums
-//   I = sum m p y, P = sum m p, Y = sum m y   with the pixel's mass m = pixel_w (1 without a map),
-// and with EVAL in front of them {omega CE, omega} in k_head_loss's expressions and order; everything 0 BY SELECTION for a label that is
-// neither 0 nor 1 (all 64 bits). NS = 3 or 5 partials per block, in the order of k_head_loss's scalar outputs.
-// k_head_sums<false> (rsu.h rsu_head_dice_sums) is pass A of the soft-Dice head: the Dice gradient of a pixel needs {I, P, Y} over the
-// whole batch, so the head runs twice. class_w and hpart are not touched.
-// k_head_sums<true> (rsu.h rsu_head_eval) is the evaluation head for held-out data: it also keeps, for every counted pixel, one count in the
-// block's LDS histogram hist[label][min(255, (int)(p * 256))].
-// The histogram: one LDS counter array per block (2 x 256 u32), bumped by the pixel's sub == 0 lane only -- at most 64 / LP lanes of a
-// wave, so a trained network that sends every pixel to bin 0 or bin 255 costs a wave at most that many serialised LDS adds per pixel
-// trip, next to 64 16-byte HBM loads. Blocks never meet on a global address: each stores its 512 counters as a plain row of the
-// workspace (2 KB per block, 2 MB at 1024 blocks against 77 MB of activations read), and k_head_eval_final sums the rows. 1024 blocks
-// adding to the two hot addresses of a saturated histogram at the same moment is exactly what this avoids.
-template <bool EVAL>
-__global__ void __launch_bounds__(256, 4) k_head_sums(const bf16_t* __restrict__ act, const float* __restrict__ w, const float* __restrict__ b,
-                                                   const int64_t* __restrict__ labels, const float* __restrict__ class_w,
-                                                   const float* __restrict__ pixel_w, float* __restrict__ prob, float* __restrict__ partial,
-                                                   unsigned* __restrict__ hpart, long npix, int C) {
-    constexpr int NS = EVAL ? 5 : 3;
-    const int LP = C >> 3;
-    const int sub = threadIdx.x % LP;
-    const int ppb = 256 / LP;  // pixels per block iteration
-    __shared__ unsigned hist[EVAL ? 2 * EW_EVAL_BINS : 1];   // (<false> never names it: no LDS is set aside)
-    if constexpr (EVAL)
-        for (int i = threadIdx.x; i < 2 * EW_EVAL_BINS; i += 256) hist[i] = 0u;
-    float w0[8], w1[8], b0, b1;
-    head_setup(w, b, sub, w0, w1, b0, b1);
-    float cw0 = 1.f, cw1 = 1.f;
-    if constexpr (EVAL) {
-        cw0 = class_w ? class_w[0] : 1.f;
-        cw1 = class_w ? class_w[1] : 1.f;
-    }
-    float lsum = 0.f, osum = 0.f, si = 0.f, sp = 0.f, sy = 0.f;
-    if constexpr (EVAL) __syncthreads();
-    const long niter = (npix + (long)gridDim.x * ppb - 1) / ((long)gridDim.x * ppb);
-    for (long it0 = 0; it0 < niter; it0 += HEAD_HU) {
-        long pp[HEAD_HU];
-        bool okk[HEAD_HU];
-        u32x4 raw[HEAD_HU];
-        int64_t labv[HEAD_HU];
-        float pwv[HEAD_HU];
-        head_load<long>(act, labels, pixel_w, it0, niter, npix, C, LP, sub, ppb, pp, okk, raw, labv, pwv);
-#pragma unroll
-        for (int u = 0; u < HEAD_HU; ++u) {
-            float a[8], l0, l1, m, s, p0, p1;
-            head_softmax(raw[u], w0, w1, b0, b1, LP, a, l0, l1, m, s, p0, p1);
-            if (!okk[u] || sub != 0) continue;
-            prob[pp[u]] = p1;
-            const int64_t lab = labv[u];
-            if (lab != 0 && lab != 1) continue;   // ignored: no loss, no weight, no mass, no count, whatever its pixel_w holds
-            {
-                // Left to itself the compiler contracts k_head_loss's `lsum += omega * -(...)` and, with three sums, `sp += m p`, `si += m p`
-                // into one fused multiply-add each and adds a ROUNDED omega to osum; with five sums side by side it chose otherwise (lsum
-                // and osum as a packed add behind a rounded product, or omega's product fused into osum): one ulp apart on a block's sum.
-                // So nothing in this block is contracted and the fused forms are written out: both instantiations give the same bits, and
-                // <true>'s first two sums are k_head_loss's.
-#pragma clang fp contract(off)
-                if constexpr (EVAL) {
-                    const float omega = (lab ? cw1 : cw0) * pwv[u];
-                    lsum = fmaf(-((lab ? l1 : l0) - m - logf(s)), omega, lsum);
-                    osum += omega;
-                }
-                sp = fmaf(pwv[u], p1, sp);
-                if (lab) {
-                    si = fmaf(pwv[u], p1, si);
-                    sy += pwv[u];
-                }
-            }
-            if constexpr (EVAL) {
-                // p1 is in [0, 1] (or NaN from non-finite logits, which converts to 0): the clamp keeps the index inside the array regardless
-                const int bin = max(0, min(EW_EVAL_BINS - 1, (int)(p1 * (float)EW_EVAL_BINS)));
-                atomicAdd(&hist[(int)lab * EW_EVAL_BINS + bin], 1u);
-            }
-        }
-    }
-    // block reduce: the threads with sub == 0 hold the sums
-    __shared__ float red[256 * NS];
-    float* my = red + threadIdx.x * NS;
-    if constexpr (EVAL) {
-        my[0] = lsum;
-        my[1] = osum;
-    }
-    my[NS - 3] = si;
-    my[NS - 2] = sp;
-    my[NS - 1] = sy;
-    __syncthreads();
-    if (threadIdx.x < NS) partial[(long)blockIdx.x * NS + threadIdx.x] = head_block_sum<NS>(red, 0, threadIdx.x, ppb, LP);
-    if constexpr (EVAL)
-        for (int i = threadIdx.x; i < 2 * EW_EVAL_BINS; i += 256) hpart[(long)blockIdx.x * (2 * EW_EVAL_BINS) + i] = hist[i];
-}
-// one wave per sum, k_head_final's lanes and order; dice_sums[0..2] = {I, P, Y} is OVERWRITTEN (the caller zeroes nothing)
-__global__ void __launch_bounds__(256) k_head_final_dice_sums(const float* __restrict__ partial, float* __restrict__ dice_sums, int nblk) {
-    const int o = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (o >= 3) return;
-    const float t = head_final_sum(partial, nblk, 3, o, lane);
-    if (lane == 0) dice_sums[o] = t;
-}
-// Workgroups 0 and 1: one wave per sum, k_head_final's lanes and order; sums[0..4] ACCUMULATE (+=: a validation set sums on the device).
-// Workgroups 2 .. 2 + 8 * EW_EVAL_SLICES - 1: the histogram rows. Workgroup (g, s) owns the 64 bins of group g and the rows
-// bk = 4 s + wave (mod 4 * EW_EVAL_SLICES): a wave reads 256 contiguous bytes per row, the four waves meet in LDS, and 64 lanes add the
-// slice's 64 totals to hist with one vector 64-bit atomic each (512 contiguous bytes; EW_EVAL_SLICES adds per address per call, whatever
-// the input). Integer adds: the result does not depend on their order.
-__global__ void __launch_bounds__(256) k_head_eval_final(const float* __restrict__ partial, const unsigned* __restrict__ hpart,
-                                                         float* __restrict__ sums, unsigned long long* __restrict__ hist, int nblk) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (blockIdx.x < 2) {
-        const int o = blockIdx.x * 4 + wave;
-        if (o >= 5) return;
-        const float t = head_final_sum(partial, nblk, 5, o, lane);
-        if (lane == 0) sums[o] += t;
-        return;
-    }
-    const int hb = blockIdx.x - 2, g = hb & 7, s = hb >> 3;
-    unsigned long long t = 0ull;
-    for (int bk = 4 * s + wave; bk < nblk; bk += 4 * EW_EVAL_SLICES) t += hpart[(long)bk * (2 * EW_EVAL_BINS) + g * 64 + lane];
-    __shared__ unsigned long long acc[4 * 64];
-    acc[threadIdx.x] = t;
-    __syncthreads();
-    if (wave == 0) {
-        t = acc[lane] + acc[64 + lane] + acc[128 + lane] + acc[192 + lane];
-        if (t) atomicAdd(&hist[g * 64 + lane], t);
-    }
-}
-
 // color_space_adjust gradients from the first conv's scatter buffer (include/rsu.h, rsu_color_adjust_bwd): 12 outputs, each a
 // 9 x Cout sum in a fixed order (lane-strided partials, then an LDS tree): one block of 12 x 64 threads
 __global__ void __launch_bounds__(768) k_color_adjust_bwd(const float* __restrict__ gx, const float* __restrict__ w1, float* __restrict__ dW0,
@@ -1183,60 +788,6 @@ int ew_reduce_job_blocks(ReduceJob& j) {
 }
 hipError_t ew_reduce_slabs_many(const ReduceJob* jobs_dev, int njobs, int total_blocks, hipStream_t st) {
     hipLaunchKernelGGL(k_reduce_slabs_many, dim3(total_blocks), dim3(256), 0, st, jobs_dev, njobs);
-    return hipGetLastError();
-}
-int ew_head_blocks(long npix, int C) {
-    const int ppb = 256 / (C / 8);
-    long nb = (npix + (long)ppb * 8 - 1) / ((long)ppb * 8);
-    if (nb > 1024) nb = 1024;
-    if (nb < 1) nb = 1;
-    return (int)nb;
-}
-hipError_t ew_head(bool train, const void* act, const float* w, const float* b, const int64_t* labels, float* prob, float* logits, void* dact,
-                   float* dw, float* db, float* loss_sum, float* ws, long npix, int C, float inv_count, hipStream_t st) {
-    const int nb = ew_head_blocks(npix, C);
-    if (train) {
-        hipLaunchKernelGGL(k_head<true>, dim3(nb), dim3(256), 0, st, (const bf16_t*)act, w, b, labels, prob, logits, (bf16_t*)dact, ws, npix, C, inv_count);
-        hipLaunchKernelGGL(k_head_final, dim3((2 * C + 3 + 3) / 4), dim3(256), 0, st, ws, dw, db, loss_sum, nb, C);
-    } else {
-        hipLaunchKernelGGL(k_head<false>, dim3(nb), dim3(256), 0, st, (const bf16_t*)act, w, b, nullptr, prob, logits, nullptr, nullptr, npix, C, 0.f);
-    }
-    return hipGetLastError();
-}
-// dice_sums == nullptr: the weighted head alone (k_head_loss<false>); else pass B of the soft-Dice head
-hipError_t ew_head_loss(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w, const float* pixel_w,
-                        const float* dice_sums, float dice_scale, float smooth, float* prob, void* dact, float* dw, float* db, float* loss_sum,
-                        float* weight_sum, float* ws, long npix, int C, float inv_count, hipStream_t st) {
-    const int nb = ew_head_blocks(npix, C);
-    hipLaunchKernelGGL(dice_sums ? k_head_loss<true> : k_head_loss<false>, dim3(nb), dim3(256), 0, st, (const bf16_t*)act, w, b, labels, class_w,
-                       pixel_w, dice_sums, dice_scale, smooth, prob, (bf16_t*)dact, ws, npix, C, inv_count);
-    hipLaunchKernelGGL(k_head_final_loss, dim3((2 * C + 4 + 3) / 4), dim3(256), 0, st, ws, dw, db, loss_sum, weight_sum, nb, C);
-    return hipGetLastError();
-}
-hipError_t ew_head_dice_sums(const void* act, const float* w, const float* b, const int64_t* labels, const float* pixel_w, float* prob,
-                             float* dice_sums, float* ws, long npix, int C, hipStream_t st) {
-    const int nb = ew_head_blocks(npix, C);
-    hipLaunchKernelGGL(k_head_sums<false>, dim3(nb), dim3(256), 0, st, (const bf16_t*)act, w, b, labels, nullptr, pixel_w, prob, ws, nullptr, npix, C);
-    hipLaunchKernelGGL(k_head_final_dice_sums, dim3(1), dim3(256), 0, st, ws, dice_sums, nb);
-    return hipGetLastError();
-}
-size_t ew_head_eval_ws_floats(long npix, int C) { return (size_t)ew_head_blocks(npix, C) * (5 + 2 * EW_EVAL_BINS); }
-hipError_t ew_head_eval(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w, const float* pixel_w,
-                        float* prob, float* sums, unsigned long long* hist, float* ws, long npix, int C, hipStream_t st) {
-    static_assert(2 * EW_EVAL_BINS == 8 * 64, "k_head_eval_final cuts the histogram into 8 groups of 64 bins");
-    const int nb = ew_head_blocks(npix, C);
-    unsigned* hpart = (unsigned*)(ws + (size_t)nb * 5);   // [nb][2][EW_EVAL_BINS] behind the [nb][5] partial sums
-    hipLaunchKernelGGL(k_head_sums<true>, dim3(nb), dim3(256), 0, st, (const bf16_t*)act, w, b, labels, class_w, pixel_w, prob, ws, hpart, npix, C);
-    hipLaunchKernelGGL(k_head_eval_final, dim3(2 + 8 * EW_EVAL_SLICES), dim3(256), 0, st, ws, hpart, sums, hist, nb);
-    return hipGetLastError();
-}
-// the final launches of ew_head_loss and ew_head_eval on their own: loss.hip's focal heads leave the same partials and end with them
-hipError_t ew_head_final_loss(const float* ws, float* dw, float* db, float* loss_sum, float* weight_sum, int nblk, int C, hipStream_t st) {
-    hipLaunchKernelGGL(k_head_final_loss, dim3((2 * C + 4 + 3) / 4), dim3(256), 0, st, ws, dw, db, loss_sum, weight_sum, nblk, C);
-    return hipGetLastError();
-}
-hipError_t ew_head_eval_final(const float* ws, const unsigned* hpart, float* sums, unsigned long long* hist, int nblk, hipStream_t st) {
-    hipLaunchKernelGGL(k_head_eval_final, dim3(2 + 8 * EW_EVAL_SLICES), dim3(256), 0, st, ws, hpart, sums, hist, nblk);
     return hipGetLastError();
 }
 hipError_t ew_color_adjust_bwd(const float* gx, const float* w1, float* dW0, float* db0, int Cout, float scale, int accumulate, hipStream_t st) {

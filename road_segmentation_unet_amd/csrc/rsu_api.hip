@@ -23,7 +23,7 @@
 #include "color_jitter.h"
 #include "border_map.h"
 #include "elementwise.h"
-#include "loss.h"
+#include "head.h"
 #include "cldice.h"
 #include "lovasz.h"
 #include "components.h"
@@ -1497,6 +1497,10 @@ static bool head_train_args_ok(const void* act, const float* w, const float* b, 
                                const void* dact, const float* dw, const float* db, const float* ws, long npix, int C) {
     return act && w && b && labels && prob && loss_sum && dact && dw && db && ws && head_c_ok(C) && npix >= 1;
 }
+// the Dice term's two scalars, wherever dice_sums is given
+static bool dice_args_ok(float dice_scale, float smooth) {
+    return std::isfinite(smooth) && smooth > 0.f && std::isfinite(dice_scale) && dice_scale >= 0.f;
+}
 extern "C" int rsu_color_adjust_bwd(const float* gx, const float* w1, float* dW0, float* db0, int Cout, float scale, int accumulate,
                                     rsu_stream_t stream) {
     if (!gx || !w1 || !dW0 || !db0 || Cout < 1 || !(scale > 0.f)) return RSU_EINVAL;
@@ -1525,8 +1529,8 @@ extern "C" int rsu_head_fwd_bwd_w(const void* act, const float* w, const float* 
                                   float* ws, long npix, int C, float inv_count, rsu_stream_t stream) {
     if (!head_train_args_ok(act, w, b, labels, prob, loss_sum, dact, dw, db, ws, npix, C)) return RSU_EINVAL;
     if (head_too_big(npix, C)) return RSU_E2BIG;
-    HIP_CHECK_RET(ew_head_loss(act, w, b, labels, class_w, pixel_w, nullptr, 0.f, 0.f, prob, dact, dw, db, loss_sum, weight_sum, ws, npix, C,
-                               inv_count, (hipStream_t)stream));
+    HIP_CHECK_RET(hd_train(act, w, b, labels, class_w, pixel_w, 0.f, nullptr, 0.f, 0.f, nullptr, prob, dact, dw, db, loss_sum, weight_sum, ws, npix,
+                           C, inv_count, (hipStream_t)stream));
     return RSU_OK;
 }
 extern "C" size_t rsu_head_dice_ws_floats(long npix, int C) { return (size_t)ew_head_blocks(npix, C) * (2 * C + 4); }
@@ -1543,23 +1547,23 @@ extern "C" int rsu_head_fwd_bwd_dice(const void* act, const float* w, const floa
                                      rsu_stream_t stream) {
     if (!head_train_args_ok(act, w, b, labels, prob, loss_sum, dact, dw, db, ws, npix, C)) return RSU_EINVAL;
     if (head_too_big(npix, C)) return RSU_E2BIG;
-    if (!dice_sums || !std::isfinite(smooth) || !(smooth > 0.f) || !std::isfinite(dice_scale) || !(dice_scale >= 0.f)) return RSU_EINVAL;
-    HIP_CHECK_RET(ew_head_loss(act, w, b, labels, class_w, pixel_w, dice_sums, dice_scale, smooth, prob, dact, dw, db, loss_sum, weight_sum, ws,
-                               npix, C, inv_count, (hipStream_t)stream));
+    if (!dice_sums || !dice_args_ok(dice_scale, smooth)) return RSU_EINVAL;
+    HIP_CHECK_RET(hd_train(act, w, b, labels, class_w, pixel_w, 0.f, dice_sums, dice_scale, smooth, nullptr, prob, dact, dw, db, loss_sum, weight_sum,
+                           ws, npix, C, inv_count, (hipStream_t)stream));
     return RSU_OK;
 }
-static_assert(RSU_EVAL_BINS == EW_EVAL_BINS, "rsu.h and elementwise.h must agree on the histogram's size");
+static_assert(RSU_EVAL_BINS == EW_EVAL_BINS, "rsu.h and head.h must agree on the histogram's size");
 extern "C" size_t rsu_head_eval_ws_floats(long npix, int C) { return (head_c_ok(C) && npix >= 1) ? ew_head_eval_ws_floats(npix, C) : 0; }
 extern "C" int rsu_head_eval(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w,
                              const float* pixel_w, float* prob, float* sums, unsigned long long* hist, float* ws, long npix, int C,
                              rsu_stream_t stream) {
     if (!act || !w || !b || !labels || !prob || !sums || !hist || !ws || !head_c_ok(C) || npix < 1) return RSU_EINVAL;
     if (head_too_big(npix, C)) return RSU_E2BIG;
-    HIP_CHECK_RET(ew_head_eval(act, w, b, labels, class_w, pixel_w, prob, sums, hist, ws, npix, C, (hipStream_t)stream));
+    HIP_CHECK_RET(hd_eval(act, w, b, labels, class_w, pixel_w, 0.f, prob, sums, hist, ws, npix, C, (hipStream_t)stream));
     return RSU_OK;
 }
-// ---- the focal heads (rsu_loss.h). gamma == 0 is decided here: the call launches what the existing entries launch (0 * log2(0) in the
-// focal kernels would be NaN, and the existing results are then had bit for bit by construction)
+// ---- the focal heads (rsu_loss.h). gamma == 0 launches what the entries above launch: hd_train and hd_eval take the focal instantiations
+// for gamma > 0 only (0 * log2(0) in them would be NaN), so the existing results are then had bit for bit by construction
 static bool focal_gamma_ok(float gamma) { return std::isfinite(gamma) && gamma >= 0.f; }
 extern "C" int rsu_head_fwd_bwd_focal(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w,
                                       const float* pixel_w, float gamma, const float* dice_sums, float dice_scale, float smooth, float* prob,
@@ -1567,14 +1571,9 @@ extern "C" int rsu_head_fwd_bwd_focal(const void* act, const float* w, const flo
                                       float inv_count, rsu_stream_t stream) {
     if (!focal_gamma_ok(gamma) || !head_train_args_ok(act, w, b, labels, prob, loss_sum, dact, dw, db, ws, npix, C)) return RSU_EINVAL;
     if (head_too_big(npix, C)) return RSU_E2BIG;
-    if (dice_sums && (!std::isfinite(smooth) || !(smooth > 0.f) || !std::isfinite(dice_scale) || !(dice_scale >= 0.f))) return RSU_EINVAL;
-    if (!dice_sums) dice_scale = smooth = 0.f;   // (not looked at)
-    if (gamma == 0.f)
-        HIP_CHECK_RET(ew_head_loss(act, w, b, labels, class_w, pixel_w, dice_sums, dice_scale, smooth, prob, dact, dw, db, loss_sum, weight_sum,
-                                   ws, npix, C, inv_count, (hipStream_t)stream));
-    else
-        HIP_CHECK_RET(ew_head_focal(act, w, b, labels, class_w, pixel_w, gamma, dice_sums, dice_scale, smooth, prob, dact, dw, db, loss_sum,
-                                    weight_sum, ws, npix, C, inv_count, (hipStream_t)stream));
+    if (dice_sums && !dice_args_ok(dice_scale, smooth)) return RSU_EINVAL;
+    HIP_CHECK_RET(hd_train(act, w, b, labels, class_w, pixel_w, gamma, dice_sums, dice_scale, smooth, nullptr, prob, dact, dw, db, loss_sum,
+                           weight_sum, ws, npix, C, inv_count, (hipStream_t)stream));
     return RSU_OK;
 }
 extern "C" int rsu_head_eval_focal(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w,
@@ -1582,10 +1581,7 @@ extern "C" int rsu_head_eval_focal(const void* act, const float* w, const float*
                                    int C, rsu_stream_t stream) {
     if (!focal_gamma_ok(gamma) || !act || !w || !b || !labels || !prob || !sums || !hist || !ws || !head_c_ok(C) || npix < 1) return RSU_EINVAL;
     if (head_too_big(npix, C)) return RSU_E2BIG;
-    if (gamma == 0.f)
-        HIP_CHECK_RET(ew_head_eval(act, w, b, labels, class_w, pixel_w, prob, sums, hist, ws, npix, C, (hipStream_t)stream));
-    else
-        HIP_CHECK_RET(ew_head_eval_focal(act, w, b, labels, class_w, pixel_w, gamma, prob, sums, hist, ws, npix, C, (hipStream_t)stream));
+    HIP_CHECK_RET(hd_eval(act, w, b, labels, class_w, pixel_w, gamma, prob, sums, hist, ws, npix, C, (hipStream_t)stream));
     return RSU_OK;
 }
 // ---- the clDice term (rsu_cldice.h): the fused soft-skeleton forward and backward, and the head that takes their gradient wrt prob
@@ -1613,10 +1609,9 @@ extern "C" int rsu_head_fwd_bwd_aux(const void* act, const float* w, const float
                                     float inv_count, const float* gprob, rsu_stream_t stream) {
     if (!gprob || !focal_gamma_ok(gamma) || !head_train_args_ok(act, w, b, labels, prob, loss_sum, dact, dw, db, ws, npix, C)) return RSU_EINVAL;
     if (head_too_big(npix, C)) return RSU_E2BIG;
-    if (dice_sums && (!std::isfinite(smooth) || !(smooth > 0.f) || !std::isfinite(dice_scale) || !(dice_scale >= 0.f))) return RSU_EINVAL;
-    if (!dice_sums) dice_scale = smooth = 0.f;   // (not looked at)
-    HIP_CHECK_RET(cl_head_aux(act, w, b, labels, class_w, pixel_w, gamma, dice_sums, dice_scale, smooth, gprob, prob, dact, dw, db, loss_sum,
-                              weight_sum, ws, npix, C, inv_count, (hipStream_t)stream));
+    if (dice_sums && !dice_args_ok(dice_scale, smooth)) return RSU_EINVAL;
+    HIP_CHECK_RET(hd_train(act, w, b, labels, class_w, pixel_w, gamma, dice_sums, dice_scale, smooth, gprob, prob, dact, dw, db, loss_sum, weight_sum,
+                           ws, npix, C, inv_count, (hipStream_t)stream));
     return RSU_OK;
 }
 // ---- the Lovasz term (rsu_lovasz.h): a per-image bitonic sort of the errors, the Jaccard differences along the ranks, loss and gradient

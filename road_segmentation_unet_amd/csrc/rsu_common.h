@@ -29,6 +29,20 @@ __device__ __forceinline__ bf16_t f2bf(float f) {
     __bf16 r = (__bf16)f;
     return __builtin_bit_cast(bf16_t, r);
 }
+// the 8 x bf16 of one 16-byte access <-> 8 floats
+__device__ __forceinline__ void unpack8(const u32x4 v, float* f) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        f[2 * i] = bf_lo(v[i]);
+        f[2 * i + 1] = bf_hi(v[i]);
+    }
+}
+__device__ __forceinline__ u32x4 pack8(const float* f) {
+    u32x4 r;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] = pack_bf2(f[2 * i], f[2 * i + 1]);
+    return r;
+}
 
 // ---- packed ReLU mask: 0xffff in each half of the result where the bf16 half of m is > 0 (sign clear, not zero), else 0:
 // 0 - m with saturation (so that m = 0x8000, minus zero, becomes +32767), then an arithmetic shift by 15 spreads the sign: negative

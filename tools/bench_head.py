@@ -13,7 +13,8 @@ the first succeeded:
                   and the derived ratios next to the byte ratios they are expected to follow. Exit status 1 if the evaluation head is
                   slower than the weighted training head (it reads the same bytes and does not write dact).
 
-The name table knows the kernels before and after the opt-in heads became one family, so a trace of either library (RSU_LIB_PATH) parses."""
+The name table knows every name these kernels have had (kernels of their own; k_head_loss<DICE> / k_head_sums<EVAL>; now
+k_head_train<FOCAL, DICE, AUX> / k_head_sums<EVAL, FOCAL>), so a trace of either library (RSU_LIB_PATH) parses."""
 import argparse
 import csv
 import glob
@@ -25,10 +26,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 # kernel name (demangled or mangled; first match wins) -> kind. A final kernel belongs to the main kernel issued just before it.
 NAMES = [("k_head_final", "final"), ("k_head_eval_final", "final"),
-         ("k_head_dice_sums", "A"), ("k_head_sums<false>", "A"), ("k_head_sumsILb0", "A"),
-         ("k_head_dice", "B"), ("k_head_loss<true>", "B"), ("k_head_lossILb1", "B"),
-         ("k_head_w", "W"), ("k_head_loss<false>", "W"), ("k_head_lossILb0", "W"),
-         ("k_head_eval", "E"), ("k_head_sums<true>", "E"), ("k_head_sumsILb1", "E"),
+         ("k_head_dice_sums", "A"), ("k_head_sums<false", "A"), ("k_head_sumsILb0", "A"),
+         ("k_head_dice", "B"), ("k_head_loss<true>", "B"), ("k_head_lossILb1", "B"), ("k_head_train<false, true, false>", "B"),
+         ("k_head_trainILb0ELb1ELb0", "B"),
+         ("k_head_w", "W"), ("k_head_loss<false>", "W"), ("k_head_lossILb0", "W"), ("k_head_train<false, false, false>", "W"),
+         ("k_head_trainILb0ELb0ELb0", "W"),
+         ("k_head_eval", "E"), ("k_head_sums<true", "E"), ("k_head_sumsILb1", "E"),
          ("k_head<true>", "U"), ("k_headILb1", "U")]
 ROUND = {"U": ["U"], "W": ["Wc", "Wm"], "A": ["A"], "B": ["B"], "E": ["E", "Es"]}   # the dispatches of one kind within a round, in issue order
 WHAT = {"U": "unweighted", "Wc": "weighted, class weights", "Wm": "weighted, class weights + map", "A": "Dice pass A (sums)",

@@ -1,7 +1,9 @@
-"""SHA-256 of every output buffer of the five training / evaluation head entries (rsu.h rsu_head_fwd_bwd, rsu_head_fwd_bwd_w,
-rsu_head_dice_sums, rsu_head_fwd_bwd_dice, rsu_head_eval) on fixed, seeded inputs: C in {16, 64}; npix not a multiple of the block's
-pixel count, once below and once above the 1024-block grid limit; without weights, with class weights, with a weight map, with ignored
-labels. For a change that must keep the bits: run it once per library (RSU_LIB_PATH), each in a fresh process, and compare the files:
+"""SHA-256 of every output buffer of every training / evaluation head entry (rsu.h rsu_head_fwd_bwd, rsu_head_fwd_bwd_w,
+rsu_head_dice_sums, rsu_head_fwd_bwd_dice, rsu_head_eval; rsu_loss.h rsu_head_fwd_bwd_focal, rsu_head_eval_focal; rsu_cldice.h
+rsu_head_fwd_bwd_aux) on fixed, seeded inputs: C in {16, 64}; npix not a multiple of the block's pixel count, once below and once above
+the 1024-block grid limit; without weights, with class weights, with a weight map, with ignored labels; the focal entries at gamma 0 and
+2, the training ones with and without the Dice sums; the aux entry with a seeded d objective / d prob and with a zero one.
+For a change that must keep the bits: run it once per library (RSU_LIB_PATH), each in a fresh process, and compare the files:
 
     timeout -k 10 300 python tools/head_hashes.py --out a.txt
     RSU_LIB_PATH=ab_libs/librsu_parent.so timeout -k 10 300 python tools/head_hashes.py --out b.txt && cmp a.txt b.txt
@@ -45,6 +47,7 @@ def main():
         labels, ignored = labels.to(dev), ignored.to(dev)
         class_w = torch.tensor([0.6, 2.5], device=dev)
         pixel_w = (0.25 + torch.rand(npix, generator=gen)).to(dev)
+        gprobs = {"g": (torch.randn(npix, generator=gen) * (3.0 / npix)).to(dev), "g0": torch.zeros(npix, device=dev)}
         inv = 1.0 / npix
         n_ws = max(int(lib().rsu_head_eval_ws_floats(npix, C)), int(lib().rsu_head_dice_ws_floats(npix, C)),
                    int(lib().rsu_head_w_ws_floats(npix, C)), int(lib().rsu_head_ws_floats(npix, C)))
@@ -82,6 +85,24 @@ def main():
             for _ in range(2):   # the sums and the histogram accumulate over calls
                 call("rsu_head_eval", *head, p(cw), p(pw), p(o["prob"]), p(eval_sums), p(eval_hist), p(o["ws"]), npix, C, st)
             digest(case, "eval", prob=o["prob"], eval_sums=eval_sums, eval_hist=eval_hist)
+            for gamma in (0.0, 2.0):
+                for dtag, ds in (("", None), ("_dice", dice_sums)):
+                    outs = lambda o: (p(o["prob"]), p(o["loss_sum"]), p(o["weight_sum"]), p(o["dact"]), p(o["dw"]), p(o["db"]),  # noqa: E731
+                                      p(o["ws"]), npix, C, inv)
+                    o = fresh()
+                    call("rsu_head_fwd_bwd_focal", *head, p(cw), p(pw), gamma, p(ds), 0.7, 1.0, *outs(o), st)
+                    del o["ws"]
+                    digest(case, "fwd_bwd_focal_gamma%.0f%s" % (gamma, dtag), **o)
+                    for gtag, gprob in gprobs.items():
+                        o = fresh()
+                        call("rsu_head_fwd_bwd_aux", *head, p(cw), p(pw), gamma, p(ds), 0.7, 1.0, *outs(o), p(gprob), st)
+                        del o["ws"]
+                        digest(case, "fwd_bwd_aux_gamma%.0f%s_%s" % (gamma, dtag, gtag), **o)
+                o = fresh()
+                eval_sums, eval_hist = torch.zeros(5, device=dev), torch.zeros((2, EVAL_BINS), dtype=torch.int64, device=dev)
+                for _ in range(2):
+                    call("rsu_head_eval_focal", *head, p(cw), p(pw), gamma, p(o["prob"]), p(eval_sums), p(eval_hist), p(o["ws"]), npix, C, st)
+                digest(case, "eval_focal_gamma%.0f" % gamma, prob=o["prob"], eval_sums=eval_sums, eval_hist=eval_hist)
     with open(a.out, "w") as f:
         f.write("\n".join(lines) + "\n")
     print("%d buffers hashed with %s -> %s" % (len(lines), os.environ.get("RSU_LIB_PATH", "the product library"), a.out))
