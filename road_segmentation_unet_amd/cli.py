@@ -165,11 +165,15 @@ def main(argv=None):
         masks = model.predict_batchwise(eval_images, opts.pred_batch_size)
         print("Prediction time:{} mins".format((time.time() - start) / 60))
         masks = _clean_up(model, masks, 0.5, rank)   # (quantize_mask binarises at 0.5 before it averages a block)
+        lines = model.centerlines(masks, threshold=0.5) if opts.save_centerlines else None   # (of the cleaned masks, before they are quantised)
         masks = model.quantize_mask(masks, patch_size=hostio.IMG_PATCH_SIZE, threshold=hostio.FOREGROUND_THRESHOLD)
         if rank == 0:
             save_dir = os.path.abspath(os.path.join(opts.save_path, model.experiment_name))
             overlays = hostio.overlays(eval_images, masks, fade=0.4)
             hostio.save_all(overlays, save_dir)
+            if lines is not None:
+                hostio.save_all(lines, save_dir, "centerlines_{:03d}.png", greyscale=True)
+                print("Centre-lines: {} skeleton pixels in {} images".format(int(lines.sum()), len(lines)))
             if masks.shape[1] % hostio.IMG_PATCH_SIZE or masks.shape[2] % hostio.IMG_PATCH_SIZE:
                 print("No submission.csv: {} x {} images are not made of whole {}-pixel patches".format(
                     masks.shape[1], masks.shape[2], hostio.IMG_PATCH_SIZE))

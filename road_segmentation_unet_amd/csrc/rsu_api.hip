@@ -19,6 +19,7 @@
 #include "../../include/rsu_lovasz.h"
 #include "../../include/rsu_components.h"
 #include "../../include/rsu_distance.h"
+#include "../../include/rsu_thin.h"
 #include "affine_patches.h"
 #include "color_jitter.h"
 #include "border_map.h"
@@ -28,6 +29,7 @@
 #include "lovasz.h"
 #include "components.h"
 #include "distance.h"
+#include "thin.h"
 #include "optim.h"
 #include "igemm.h"
 
@@ -1676,6 +1678,24 @@ extern "C" int rsu_distance_hist(const float* prob, float threshold, const int64
     if (!prob || !labels64 || !acc || !ws || !distance_size_ok(N, H, W) || !std::isfinite(threshold)) return RSU_EINVAL;
     if (distance_too_big(N, H, W, 8)) return RSU_E2BIG;
     HIP_CHECK_RET(dt_distance_hist(prob, threshold, labels64, acc, ws, N, H, W, (hipStream_t)stream));
+    return RSU_OK;
+}
+// ---- centre-lines (rsu_thin.h): Guo & Hall's parallel thinning of the predicted and the truth mask on bit rows
+static_assert(RSU_THIN_MAX_SIDE == TH_MAX_SIDE && RSU_THIN_MAX_ITERS == TH_MAX_ITERS, "rsu_thin.h and thin.h must agree on the limits");
+static bool thin_size_ok(int N, int H, int W, int max_iters) {
+    return N >= 1 && H >= 1 && W >= 1 && H <= TH_MAX_SIDE && W <= TH_MAX_SIDE && max_iters >= 1 && max_iters <= TH_MAX_ITERS;
+}
+static bool thin_too_big(int N, int H, int W, int bytes) { return (long)N * H * W * bytes >= 0x7ffffff0L; }
+extern "C" size_t rsu_thin_ws_bytes(int N, int H, int W, int max_iters) {
+    return thin_size_ok(N, H, W, max_iters) && !thin_too_big(N, H, W, 4) ? th_ws_bytes(N, H, W, max_iters) : 0;
+}
+extern "C" int rsu_mask_thin(const float* prob, float threshold, const int64_t* labels64, int max_iters, float* skel_pred, int64_t* skel_true,
+                             unsigned long long* acc, uint32_t* info, void* ws, int N, int H, int W, rsu_stream_t stream) {
+    if (!prob || !ws || (!skel_pred && !skel_true) || (skel_true && !labels64) || (acc && !(skel_pred && skel_true)) ||
+        !thin_size_ok(N, H, W, max_iters) || !std::isfinite(threshold))
+        return RSU_EINVAL;
+    if (thin_too_big(N, H, W, labels64 ? 8 : 4)) return RSU_E2BIG;
+    HIP_CHECK_RET(th_mask_thin(prob, threshold, labels64, max_iters, skel_pred, skel_true, acc, info, ws, N, H, W, (hipStream_t)stream));
     return RSU_OK;
 }
 static_assert(RSU_BORDER_MAX_SIDE == BM_MAX_SIDE, "rsu.h and border_map.h must agree on the supported tile size");

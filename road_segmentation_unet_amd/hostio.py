@@ -1136,3 +1136,96 @@ def relaxed_metrics(hist, slack):
     f1 = 2.0 * precision * recall / (precision + recall) if precision + recall > 0.0 else 0.0
     return {"relaxed_precision": precision, "relaxed_recall": recall, "relaxed_f1": f1, "mean_dist_pred": mean[0], "mean_dist_true": mean[1],
             "far_pred": far[0], "far_true": far[1]}
+
+
+# ---- centre-lines on the host (include/rsu_thin.h)
+THIN_MAX_SIDE, THIN_MAX_ITERS = 1024, 512   # rsu_thin.h RSU_THIN_MAX_SIDE, RSU_THIN_MAX_ITERS
+
+
+def _thin_iters(max_iters):
+    if isinstance(max_iters, bool) or not isinstance(max_iters, (int, np.integer)) or not 1 <= max_iters <= THIN_MAX_ITERS:
+        raise ValueError("thin: max_iters must be an integer in [1, %d], not %r" % (THIN_MAX_ITERS, max_iters))
+    return int(max_iters)
+
+
+def _thin_deleted(m, sub):
+    """the pixels of bool [N, H, W] that sub-iteration `sub` of Guo & Hall's rule deletes (everything outside an image is background)"""
+    q = np.pad(m, ((0, 0), (1, 1), (1, 1)))
+    H, W = m.shape[1:]
+
+    def at(dy, dx):
+        return q[:, 1 + dy:1 + dy + H, 1 + dx:1 + dx + W]
+    p2, p3, p4, p5, p6, p7, p8, p9 = at(-1, 0), at(-1, 1), at(0, 1), at(1, 1), at(1, 0), at(1, -1), at(0, -1), at(-1, -1)
+    i8 = np.int8
+    C = (~p2 & (p3 | p4)).astype(i8) + (~p4 & (p5 | p6)).astype(i8) + (~p6 & (p7 | p8)).astype(i8) + (~p8 & (p9 | p2)).astype(i8)
+    N1 = (p9 | p2).astype(i8) + (p3 | p4).astype(i8) + (p5 | p6).astype(i8) + (p7 | p8).astype(i8)
+    N2 = (p2 | p3).astype(i8) + (p4 | p5).astype(i8) + (p6 | p7).astype(i8) + (p8 | p9).astype(i8)
+    Nn = np.minimum(N1, N2)
+    mm = ((p6 | p7 | ~p9) & p8) if sub == 0 else ((p2 | p3 | ~p5) & p4)
+    return m & (C == 1) & (Nn >= 2) & (Nn <= 3) & ~mm
+
+
+def thin_mask(mask, max_iters):
+    """Guo & Hall's two-sub-iteration parallel thinning (CACM 1989, algorithm A1; the rule of include/rsu_thin.h) of a bool [N, H, W],
+    image by image: (skeleton bool [N, H, W], deleted int64 [N]). An iteration is sub-iteration 0 then 1, each deleting all its pixels at
+    once from the state before it; the loop ends after max_iters iterations or with the first iteration that deletes nothing anywhere.
+    deleted[n] = the pixels the LAST executed iteration took from image n: 0 means image n reached its fixed point within max_iters."""
+    m = np.asarray(mask)
+    if m.ndim != 3 or m.dtype != np.bool_ or min(m.shape) < 1:
+        raise ValueError("thin_mask: mask must be a bool array [N, H, W] with N, H, W >= 1, not %s %r" % (m.dtype, m.shape))
+    m = m.copy()
+    deleted = np.zeros(m.shape[0], np.int64)
+    for _ in range(_thin_iters(max_iters)):
+        deleted[:] = 0
+        for sub in (0, 1):
+            d = _thin_deleted(m, sub)
+            deleted += d.reshape(d.shape[0], -1).sum(axis=1)
+            m &= ~d
+        if not deleted.any():
+            break
+    return m, deleted
+
+
+def mask_thin(prob, threshold, labels, max_iters):
+    """rsu_mask_thin on the host, in its output formats: (skel_pred float32 [N, H, W] with 1.0 on the skeleton of P = {label in {0, 1} and
+    p >= threshold}, skel_true int64 [N, H, W] with 1 on the skeleton of T = {label == 1}, 0 on every other counted pixel and the label
+    itself on an ignored one, counts int64 [4] = {|S_P|, |S_P and T|, |S_T|, |S_T and P|}, info uint32 [N, 2] = the pixels the last
+    executed iteration deleted from P / from T per image). labels=None: every pixel is counted, T is empty and skel_true is None."""
+    p, t, lab = _dist_check(prob, threshold, labels, False)
+    if max(p.shape[1:]) > THIN_MAX_SIDE:
+        raise ValueError("thin: H, W <= %d, not shape %r" % (THIN_MAX_SIDE, p.shape))
+    pred, true = _dist_masks(p, t, lab)
+    sp, dp = thin_mask(pred, max_iters)
+    st, dt = thin_mask(true, max_iters)
+    counts = np.array([sp.sum(), (sp & true).sum(), st.sum(), (st & pred).sum()], np.int64)
+    skel_true = None if lab is None else np.where((lab == 0) | (lab == 1), st.astype(np.int64), lab)
+    return sp.astype(np.float32), skel_true, counts, np.stack([dp, dt], axis=1).astype(np.uint32)
+
+
+def centerline_metrics(cl_hist, counts, slack):
+    """The centre-line scores of the road-extraction literature (Wiedemann 1998, Heipke 1997) and the clDice METRIC on hard skeletons
+    (Shit et al. 2021) from cl_hist = the distance histogram of the two SKELETONS (int [2, DIST_BINS]: distance_hist / rsu_distance_hist
+    of mask_thin's two outputs at threshold 0.5) and counts = mask_thin's four integers {|S_P|, |S_P and T|, |S_T|, |S_T and P|}, at
+    `slack` = the buffer width in pixels, an int in [0, DIST_BINS - 2]:
+      cl_correctness  = the share of the predicted centre-line within slack of the true one (sum(cl_hist[0][:slack + 1]) / max(sum(cl_hist[0]), 1)),
+      cl_completeness = the share of the true centre-line within slack of the predicted one, likewise from cl_hist[1],
+      cl_quality      = comp * corr / (comp - comp * corr + corr), 0 when both are 0,
+      cldice_hard     = the harmonic mean of tprec = |S_P and T| / max(|S_P|, 1) and tsens = |S_T and P| / max(|S_T|, 1), 0 when both are 0,
+      cl_len_pred / cl_len_true = |S_P| / |S_T|: the skeletons' PIXEL COUNTS, a proxy of the centre-line length (a diagonal step counts
+                        like a straight one), not a length in pixels."""
+    h = np.asarray(cl_hist)
+    if h.shape != (2, DIST_BINS) or h.dtype.kind not in "iu":
+        raise ValueError("centerline_metrics: cl_hist must be an integer array [2, %d], not %s %r" % (DIST_BINS, h.dtype, h.shape))
+    c = np.asarray(counts)
+    if c.shape != (4,) or c.dtype.kind not in "iu" or (c < 0).any():
+        raise ValueError("centerline_metrics: counts must be four integers >= 0, not %s %r" % (c.dtype, counts))
+    if isinstance(slack, bool) or not isinstance(slack, (int, np.integer)) or not 0 <= slack <= DIST_BINS - 2:
+        raise ValueError("centerline_metrics: slack must be an integer in [0, %d], not %r" % (DIST_BINS - 2, slack))
+    h = h.astype(np.int64)
+    tot = [int(h[0].sum()), int(h[1].sum())]
+    corr, comp = [float(int(h[s][:int(slack) + 1].sum())) / max(tot[s], 1) for s in (0, 1)]
+    quality = comp * corr / (comp - comp * corr + corr) if comp + corr > 0.0 else 0.0
+    sp, spt, st, stp = (int(v) for v in c)
+    tprec, tsens = float(spt) / max(sp, 1), float(stp) / max(st, 1)
+    hard = 2.0 * tprec * tsens / (tprec + tsens) if tprec + tsens > 0.0 else 0.0
+    return {"cl_correctness": corr, "cl_completeness": comp, "cl_quality": quality, "cldice_hard": hard, "cl_len_pred": sp, "cl_len_true": st}

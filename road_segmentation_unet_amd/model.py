@@ -19,7 +19,7 @@ import torch.distributed as dist
 from . import hostio
 from . import images as dimages
 from ._lib import call, lib
-from .hostio import DIST_BINS, DIST_MAX_SIDE, relaxed_metrics
+from .hostio import DIST_BINS, DIST_MAX_SIDE, THIN_MAX_ITERS, THIN_MAX_SIDE, centerline_metrics, relaxed_metrics
 from .dist import GradBucketer, micro_indices, shard_indices, tune_overlap  # noqa: F401  (shard_indices: importable from here as before)
 from .pool import BatchUploader, DevicePatchPool, PatchPool
 from .summary import Summary
@@ -110,7 +110,20 @@ EXTRA_FLAG_DEFS = [
     ("relaxed_slack", int, 3, "RHO, an int in [0, 62]: a predicted road pixel counts as correct when a true road pixel lies within RHO "
                               "pixels, and a true one as found when a predicted one does (3 on the Massachusetts roads set; 0 = the plain "
                               "pixel precision and recall). Used with --validate_distances"),
-    ("save_best_metric", str, "f1", "f1|relaxed_f1: the validation figure --save_best compares; relaxed_f1 requires --validate_distances"),
+    ("save_best_metric", str, "f1", "f1|relaxed_f1|cl_quality: the validation figure --save_best compares; relaxed_f1 requires "
+                                    "--validate_distances, cl_quality requires --validate_centerlines"),
+    ("validate_centerlines", bool, False, "Extract centre-lines during validation: evaluate() thins the predicted and the true road mask "
+                                          "of every patch to one-pixel skeletons on the GPU (Guo & Hall's parallel thinning: "
+                                          "rsu_thin.h) and also returns cl_hist (the distance histogram of the two skeletons) and from "
+                                          "it cl_correctness, cl_completeness and cl_quality (Wiedemann, Heipke) at --relaxed_slack, "
+                                          "cldice_hard (the clDice metric on hard skeletons), cl_len_pred / cl_len_true (skeleton pixel "
+                                          "counts) and thin_unconverged. Skeletons are per validation patch. Does not need "
+                                          "--validate_distances"),
+    ("centerline_max_iters", int, 64, "Thinning iterations at most, an int in [1, 512]: a road of half-width w needs about w + 6; image "
+                                      "sides still changing after them are counted in thin_unconverged. Used by --validate_centerlines "
+                                      "and --save_centerlines"),
+    ("save_centerlines", bool, False, "Inference: also write the centre-line of every predicted mask (after --min_road_area / "
+                                      "--max_hole_area, at threshold 0.5) as a greyscale PNG beside the overlays"),
     ("border_weight", float, 0.0, "w0 >= 0 of a border-distance weight map computed on the GPU from each batch's labels: a pixel counts "
                                   "1 + w0 * exp(-d^2 / (2 border_sigma^2)) times in the loss, d its distance to the other class inside its patch; "
                                   "0 = off (the U-Net paper uses 10). The loss stays normalised by the pixel count and the mean weight is above 1, "
@@ -305,10 +318,22 @@ def parse_relaxed_slack(value):
 
 
 def parse_save_best_metric(value):
-    """The --save_best_metric value: "f1" or "relaxed_f1". Anything else raises ValueError."""
-    if not isinstance(value, str) or value not in ("f1", "relaxed_f1"):
-        raise ValueError("--save_best_metric must be f1 or relaxed_f1, not %r" % (value,))
+    """The --save_best_metric value: "f1", "relaxed_f1" or "cl_quality". Anything else raises ValueError."""
+    if not isinstance(value, str) or value not in ("f1", "relaxed_f1", "cl_quality"):
+        raise ValueError("--save_best_metric must be f1, relaxed_f1 or cl_quality, not %r" % (value,))
     return value
+
+
+def parse_centerline_max_iters(value):
+    """The --centerline_max_iters value as an int in [1, 512] (rsu_thin.h RSU_THIN_MAX_ITERS). Anything else raises ValueError."""
+    try:
+        v = int(value)
+        ok = not isinstance(value, bool) and v == (float(value) if not isinstance(value, str) else v) and 1 <= v <= THIN_MAX_ITERS
+    except (TypeError, ValueError, OverflowError):
+        v, ok = 0, False
+    if not ok:
+        raise ValueError("--centerline_max_iters must be an integer in [1, %d], not %r" % (THIN_MAX_ITERS, value))
+    return v
 
 
 def parse_cldice_iters(value):
@@ -647,6 +672,10 @@ class Options(object):
         self.save_best_metric = parse_save_best_metric(self.save_best_metric)
         if self.save_best_metric == "relaxed_f1" and not self.validate_distances:
             raise ValueError("--save_best_metric=relaxed_f1 requires --validate_distances: without it validation measures no distances")
+        self.validate_centerlines, self.save_centerlines = bool(self.validate_centerlines), bool(self.save_centerlines)
+        self.centerline_max_iters = parse_centerline_max_iters(self.centerline_max_iters)
+        if self.save_best_metric == "cl_quality" and not self.validate_centerlines:
+            raise ValueError("--save_best_metric=cl_quality requires --validate_centerlines: without it validation extracts no centre-lines")
         self.border_weight, self.border_sigma = parse_border_weight(self.border_weight), parse_border_sigma(self.border_sigma)
         self.clip_grad_norm = parse_clip_grad_norm(self.clip_grad_norm)
         self.ema_decay, self.ema_warmup = parse_ema_decay(self.ema_decay), bool(self.ema_warmup)
@@ -740,6 +769,7 @@ class ConvolutionalModel:
         self.last_postprocess_stats = None   # postprocess_masks: the summed stats of its last call (int64 [6])
         self._cc_acc = self._cc_ws = None    # --validate_components: the four counts and the workspace of rsu_components_pair_count
         self._dt_acc = self._dt_ws = None    # --validate_distances: the 2 x 64 counters and the workspace of rsu_distance_hist
+        self._cl_acc = self._cl_ws = None    # --validate_centerlines: the 2 x 64 + 4 + 1 counters; the workspaces, skeletons and info
         if self.world > 1:
             self._bucketer = GradBucketer(self.net.flat_g, self.net.n_live)
             self._bucketer.extra_streams = list(self.net.wstreams)
@@ -939,6 +969,10 @@ class ConvolutionalModel:
                 if with_dt:
                     self._distance_buffers()
                     self._dt_acc.zero_()
+                with_th = bool(getattr(self._options, "validate_centerlines", False))
+                if with_th:
+                    self._centerline_buffers()
+                    self._cl_acc.zero_()
                 for t0 in range(lo, hi, B):
                     nb = min(B, hi - t0)
                     if nb < B:
@@ -964,6 +998,16 @@ class ConvolutionalModel:
                              ctypes.c_void_p(net.labels.data_ptr()), ctypes.c_void_p(self._dt_acc.data_ptr()),
                              ctypes.c_void_p(self._dt_ws.data_ptr()), B, net.P, net.P,
                              ctypes.c_void_p(torch.cuda.current_stream(net.device).cuda_stream))
+                    if with_th:   # both skeletons and the four counts, then the distance histogram of the skeletons
+                        cl = self._cl_ws
+                        st = ctypes.c_void_p(torch.cuda.current_stream(net.device).cuda_stream)
+                        call("rsu_mask_thin", ctypes.c_void_p(net.prob.data_ptr()), float(threshold), ctypes.c_void_p(net.labels.data_ptr()),
+                             int(self._options.centerline_max_iters), ctypes.c_void_p(cl["skel_pred"].data_ptr()),
+                             ctypes.c_void_p(cl["skel_true"].data_ptr()), ctypes.c_void_p(self._cl_acc[2 * DIST_BINS:].data_ptr()),
+                             ctypes.c_void_p(cl["info"].data_ptr()), ctypes.c_void_p(cl["thin"].data_ptr()), B, net.P, net.P, st)
+                        call("rsu_distance_hist", ctypes.c_void_p(cl["skel_pred"].data_ptr()), 0.5, ctypes.c_void_p(cl["skel_true"].data_ptr()),
+                             ctypes.c_void_p(self._cl_acc.data_ptr()), ctypes.c_void_p(cl["dist"].data_ptr()), B, net.P, net.P, st)
+                        self._cl_acc[-1] += (cl["info"] != 0).sum()   # (on the device: no read-back)
                 sums, hist = net.eval_sums.to(torch.float64), net.eval_hist.clone()
                 with_cl = net.cldice_weight > 0.0
                 if with_cl:   # the four clDice sums ride behind the five of the head: one all-reduce, one read-back
@@ -975,10 +1019,15 @@ class ConvolutionalModel:
                     sums = torch.cat([sums, self._cc_acc.to(torch.float64)])
                 if with_dt:   # and the 2 x 64 distance counters last of all
                     sums = torch.cat([sums, self._dt_acc.to(torch.float64)])
+                if with_th:   # and behind them the centre-line counters: 2 x 64 bins, the four counts, the unconverged image sides
+                    sums = torch.cat([sums, self._cl_acc.to(torch.float64)])
                 if self.world > 1:
                     dist.all_reduce(sums)
                     dist.all_reduce(hist)
                 sums, hist = sums.cpu().numpy(), hist.cpu().numpy()   # the one synchronisation
+                th_sums = sums[-(2 * DIST_BINS + 5):] if with_th else None
+                if with_th:
+                    sums = sums[:-(2 * DIST_BINS + 5)]
                 dt_sums = sums[-2 * DIST_BINS:] if with_dt else None
                 if with_dt:
                     sums = sums[:-2 * DIST_BINS]
@@ -1006,7 +1055,31 @@ class ConvolutionalModel:
         if with_dt:
             out["dist_hist"] = np.rint(dt_sums).astype(np.int64).reshape(2, DIST_BINS)
             out.update(relaxed_metrics(out["dist_hist"], int(self._options.relaxed_slack)))
+        if with_th:
+            th = np.rint(th_sums).astype(np.int64)
+            out["cl_hist"] = th[:2 * DIST_BINS].reshape(2, DIST_BINS)
+            out.update(centerline_metrics(out["cl_hist"], th[2 * DIST_BINS:2 * DIST_BINS + 4], int(self._options.relaxed_slack)))
+            out["thin_unconverged"] = int(th[-1])
         return out
+
+    def _centerline_buffers(self):
+        """the device buffers of --validate_centerlines, made when evaluate() first needs them: the counters (the 2 x 64 bins of the
+        skeletons' distance histogram, rsu_mask_thin's four counts, the unconverged image sides), the two skeletons, info and the
+        workspaces of rsu_mask_thin and rsu_distance_hist"""
+        if self._cl_acc is None:
+            net, B = self.net, self.local_batch
+            iters = int(self._options.centerline_max_iters)
+            need, need_dt = int(lib().rsu_thin_ws_bytes(B, net.P, net.P, iters)), int(lib().rsu_distance_ws_bytes(B, net.P, net.P))
+            if need == 0 or need_dt == 0 or B * net.P * net.P * 8 >= 0x7ffffff0:
+                raise ValueError("--validate_centerlines: a batch of %d patches of %d x %d pixels is outside rsu_thin.h's limits (sides "
+                                 "up to %d, the labels below 2 GiB)" % (B, net.P, net.P, THIN_MAX_SIDE))
+            dev = net.device
+            self._cl_ws = {"skel_pred": torch.zeros((B, net.P, net.P), dtype=torch.float32, device=dev),
+                           "skel_true": torch.zeros((B, net.P, net.P), dtype=torch.int64, device=dev),
+                           "info": torch.zeros((B, 2), dtype=torch.int32, device=dev),
+                           "thin": torch.zeros(need // 8, dtype=torch.int64, device=dev),
+                           "dist": torch.zeros(need_dt // 4, dtype=torch.int32, device=dev)}
+            self._cl_acc = torch.zeros(2 * DIST_BINS + 5, dtype=torch.int64, device=dev)
 
     def _distance_buffers(self):
         """the device buffers of --validate_distances, made when evaluate() first needs them: the 2 x 64 counters and the workspace"""
@@ -1047,6 +1120,11 @@ class ConvolutionalModel:
                       "{:.3f} true {:.3f}; beyond 62 pixels: predicted {:.4f} true {:.4f}"
                       .format(step, v["relaxed_f1"], v["relaxed_precision"], v["relaxed_recall"], opts.relaxed_slack, v["mean_dist_pred"],
                               v["mean_dist_true"], v["far_pred"], v["far_true"]))
+            if "cl_quality" in v:
+                print("step {} validation centre-lines: quality {:.4f} completeness {:.4f} correctness {:.4f} at slack {}; hard clDice {:.4f}; "
+                      "skeleton pixels predicted {} true {}; unconverged image sides {}"
+                      .format(step, v["cl_quality"], v["cl_completeness"], v["cl_correctness"], opts.relaxed_slack, v["cldice_hard"],
+                              v["cl_len_pred"], v["cl_len_true"], v["thin_unconverged"]))
             if self._summary is not None:
                 self._summary.add({"val_loss": v["loss"], "val_objective": v["objective"], "val_dice": v["dice"], "val_f1": v["f1"],
                                    "val_iou": v["iou"], "val_best_threshold": v["best_threshold"]}, global_step=step)
@@ -1060,6 +1138,9 @@ class ConvolutionalModel:
                     self._summary.add({"val_relaxed_f1": v["relaxed_f1"], "val_relaxed_precision": v["relaxed_precision"],
                                        "val_relaxed_recall": v["relaxed_recall"], "val_mean_dist_pred": v["mean_dist_pred"],
                                        "val_mean_dist_true": v["mean_dist_true"]}, global_step=step)
+                if "cl_quality" in v:
+                    self._summary.add({"val_cl_quality": v["cl_quality"], "val_cl_completeness": v["cl_completeness"],
+                                       "val_cl_correctness": v["cl_correctness"], "val_cldice_hard": v["cldice_hard"]}, global_step=step)
         # (the same numbers on every rank: they come out of the all-reduce)
         if self.best_val_f1 is None or v["f1"] > self.best_val_f1:
             self.best_val_f1 = v["f1"]
@@ -1068,7 +1149,7 @@ class ConvolutionalModel:
             self.best_val_score = score
             if opts.save_best:
                 self.save_as(os.path.abspath(os.path.join(opts.save_path, self.experiment_name + "-best.chkpt")))
-        return {k: v[k] for k in v if k not in ("sums", "hist", "cldice_sums", "dist_hist")}
+        return {k: v[k] for k in v if k not in ("sums", "hist", "cldice_sums", "dist_hist", "cl_hist")}
 
     def _ensure_summary(self):
         opts = self._options
@@ -1405,6 +1486,30 @@ class ConvolutionalModel:
              min_area, max_hole, ctypes.c_void_p(t.data_ptr()), ctypes.c_void_p(stats.data_ptr()), ctypes.c_void_p(ws.data_ptr()), n, H, W, st)
         self.last_postprocess_stats = stats.sum(dim=0).cpu().numpy()
         return t.cpu().numpy()[..., None].astype(a.dtype)
+
+    def centerlines(self, masks, threshold=0.5):
+        """The centre-lines of predicted masks on the device (rsu_mask_thin with labels64 = NULL: every pixel counted): masks [n, H, W] or
+        [n, H, W, 1] probabilities (what postprocess_masks returns) -> float32 [n, H, W], 1.0 on the one-pixel-wide, topology-preserving
+        skeleton of {p >= threshold} and 0.0 elsewhere, after at most --centerline_max_iters iterations of Guo & Hall's thinning.
+        Integer decisions on the same input: every rank computes the same bits."""
+        a = np.asarray(masks)
+        if a.ndim == 4 and a.shape[3] == 1:
+            a = a[..., 0]
+        if a.ndim != 3:
+            raise ValueError("centerlines: masks must be [n, H, W] or [n, H, W, 1], not %s" % (a.shape,))
+        n, H, W = (int(v) for v in a.shape)
+        iters = int(getattr(self._options, "centerline_max_iters", 64))
+        need = int(lib().rsu_thin_ws_bytes(n, H, W, iters)) if min(n, H, W) >= 1 else 0
+        if need == 0:
+            raise ValueError("centerlines (--save_centerlines): %d masks of %d x %d pixels are outside rsu_thin.h's limits (sides up to %d, "
+                             "n * H * W * 4 below 2 GiB): thin them in smaller stacks" % (n, H, W, THIN_MAX_SIDE))
+        dev = self.net.device
+        t = torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+        out = torch.empty_like(t)
+        ws = torch.empty(need // 8, dtype=torch.int64, device=dev)
+        call("rsu_mask_thin", ctypes.c_void_p(t.data_ptr()), float(threshold), None, iters, ctypes.c_void_p(out.data_ptr()), None, None, None,
+             ctypes.c_void_p(ws.data_ptr()), n, H, W, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        return out.cpu().numpy()
 
     # ------------------------------------------------------------------ checkpoints
     def save_as(self, path):
