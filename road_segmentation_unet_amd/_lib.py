@@ -1,5 +1,5 @@
 """ctypes binding of librsu_hip.so (the C ABI of include/rsu.h, include/rsu_optim.h, include/rsu_loss.h, include/rsu_cldice.h,
-include/rsu_lovasz.h, include/rsu_components.h, include/rsu_distance.h and include/rsu_thin.h).
+include/rsu_lovasz.h, include/rsu_components.h, include/rsu_distance.h, include/rsu_thin.h and include/rsu_graph.h).
 
 The library is REQUIRED: there is no CPU or eager-PyTorch fallback anywhere in this package. If the
 shared object is missing or a symbol cannot be resolved, importing/using the product path raises."""
@@ -201,6 +201,12 @@ SIGNATURES_THIN = {
     "rsu_mask_thin": (_i, [_vp, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
 }
 
+# and for include/rsu_graph.h, the ninth (centre-line graph: spur pruning of both masks, their ends, isolated pixels and junction pixels)
+SIGNATURES_GRAPH = {
+    "rsu_graph_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "rsu_skeleton_graph": (_i, [_vp, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+}
+
 _lib = None
 
 
@@ -218,7 +224,7 @@ def lib():
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_OPTIM.items()) + list(SIGNATURES_LOSS.items()) \
                 + list(SIGNATURES_CLDICE.items()) + list(SIGNATURES_LOVASZ.items()) + list(SIGNATURES_COMPONENTS.items()) \
-                + list(SIGNATURES_DISTANCE.items()) + list(SIGNATURES_THIN.items()):
+                + list(SIGNATURES_DISTANCE.items()) + list(SIGNATURES_THIN.items()) + list(SIGNATURES_GRAPH.items()):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -238,6 +244,7 @@ JITTER_MAX_LAUNCH = 32   # rsu.h RSU_JITTER_MAX_LAUNCH
 CLDICE_MAX_ITERS = 16   # rsu_cldice.h RSU_CLDICE_MAX_ITERS
 DIST_BINS, DIST_NONE, DIST_MAX_SIDE = 64, 0x7fffffff, 1024   # rsu_distance.h RSU_DIST_BINS, RSU_DIST_NONE, RSU_DIST_MAX_SIDE
 THIN_MAX_SIDE, THIN_MAX_ITERS = 1024, 512   # rsu_thin.h RSU_THIN_MAX_SIDE, RSU_THIN_MAX_ITERS
+GRAPH_MAX_SIDE, GRAPH_MAX_BRANCH = 1024, 64   # rsu_graph.h RSU_GRAPH_MAX_SIDE, RSU_GRAPH_MAX_BRANCH
 E2BIG = -7
 
 

@@ -20,6 +20,7 @@
 #include "../../include/rsu_components.h"
 #include "../../include/rsu_distance.h"
 #include "../../include/rsu_thin.h"
+#include "../../include/rsu_graph.h"
 #include "affine_patches.h"
 #include "color_jitter.h"
 #include "border_map.h"
@@ -30,6 +31,7 @@
 #include "components.h"
 #include "distance.h"
 #include "thin.h"
+#include "graph.h"
 #include "optim.h"
 #include "igemm.h"
 
@@ -1696,6 +1698,26 @@ extern "C" int rsu_mask_thin(const float* prob, float threshold, const int64_t* 
         return RSU_EINVAL;
     if (thin_too_big(N, H, W, labels64 ? 8 : 4)) return RSU_E2BIG;
     HIP_CHECK_RET(th_mask_thin(prob, threshold, labels64, max_iters, skel_pred, skel_true, acc, info, ws, N, H, W, (hipStream_t)stream));
+    return RSU_OK;
+}
+// ---- centre-line graph (rsu_graph.h): morphological pruning of both masks and the ends, isolated pixels and junction pixels of the result
+static_assert(RSU_GRAPH_MAX_SIDE == GR_MAX_SIDE && RSU_GRAPH_MAX_BRANCH == GR_MAX_BRANCH, "rsu_graph.h and graph.h must agree on the limits");
+static bool graph_size_ok(int N, int H, int W, int min_branch) {
+    return N >= 1 && H >= 1 && W >= 1 && H <= GR_MAX_SIDE && W <= GR_MAX_SIDE && min_branch >= 0 && min_branch <= GR_MAX_BRANCH;
+}
+static bool graph_too_big(int N, int H, int W, int bytes) { return (long)N * H * W * bytes >= 0x7ffffff0L; }
+extern "C" size_t rsu_graph_ws_bytes(int N, int H, int W, int min_branch) {
+    return graph_size_ok(N, H, W, min_branch) && !graph_too_big(N, H, W, 4) ? gr_ws_bytes(N, H, W, min_branch) : 0;
+}
+extern "C" int rsu_skeleton_graph(const float* prob, float threshold, const int64_t* labels64, int min_branch, float* out_pred, int64_t* out_true,
+                                  float* junc_pred, int64_t* junc_true, unsigned long long* acc, void* ws, int N, int H, int W,
+                                  rsu_stream_t stream) {
+    if (!prob || !ws || (!out_pred && !out_true && !junc_pred && !junc_true) || ((out_true || junc_true) && !labels64) ||
+        !graph_size_ok(N, H, W, min_branch) || !std::isfinite(threshold))
+        return RSU_EINVAL;
+    if (graph_too_big(N, H, W, labels64 ? 8 : 4)) return RSU_E2BIG;
+    HIP_CHECK_RET(gr_skeleton_graph(prob, threshold, labels64, min_branch, out_pred, out_true, junc_pred, junc_true, acc, ws, N, H, W,
+                                    (hipStream_t)stream));
     return RSU_OK;
 }
 static_assert(RSU_BORDER_MAX_SIDE == BM_MAX_SIDE, "rsu.h and border_map.h must agree on the supported tile size");

@@ -1229,3 +1229,129 @@ def centerline_metrics(cl_hist, counts, slack):
     tprec, tsens = float(spt) / max(sp, 1), float(stp) / max(st, 1)
     hard = 2.0 * tprec * tsens / (tprec + tsens) if tprec + tsens > 0.0 else 0.0
     return {"cl_correctness": corr, "cl_completeness": comp, "cl_quality": quality, "cldice_hard": hard, "cl_len_pred": sp, "cl_len_true": st}
+
+
+# ---- centre-line pruning and nodes on the host (include/rsu_graph.h)
+GRAPH_MAX_SIDE, GRAPH_MAX_BRANCH = 1024, 64   # rsu_graph.h RSU_GRAPH_MAX_SIDE, RSU_GRAPH_MAX_BRANCH
+
+
+def _graph_branch(min_branch):
+    if isinstance(min_branch, bool) or not isinstance(min_branch, (int, np.integer)) or not 0 <= min_branch <= GRAPH_MAX_BRANCH:
+        raise ValueError("graph: min_branch must be an integer in [0, %d], not %r" % (GRAPH_MAX_BRANCH, min_branch))
+    return int(min_branch)
+
+
+def _graph_mask(mask, what):
+    m = np.asarray(mask)
+    if m.ndim != 3 or m.dtype != np.bool_ or min(m.shape) < 1:
+        raise ValueError("%s: mask must be a bool array [N, H, W] with N, H, W >= 1, not %s %r" % (what, m.dtype, m.shape))
+    return m
+
+
+def _graph_counts(m):
+    """(n8, X) of bool [N, H, W], int8 each: the number of set neighbours and the number of 0 -> 1 steps around the eight neighbours
+    p2 .. p9, clockwise from north and cyclic (everything outside an image is background)"""
+    q = np.pad(m, ((0, 0), (1, 1), (1, 1)))
+    H, W = m.shape[1:]
+    ring = [q[:, 1 + dy:1 + dy + H, 1 + dx:1 + dx + W] for dy, dx in ((-1, 0), (-1, 1), (0, 1), (1, 1), (1, 0), (1, -1), (0, -1), (-1, -1))]
+    n8 = np.zeros(m.shape, np.int8)
+    X = np.zeros(m.shape, np.int8)
+    for i in range(8):
+        n8 += ring[i]
+        X += ~ring[i] & ring[(i + 1) % 8]
+    return n8, X
+
+
+def _graph_end(m):
+    n8, X = _graph_counts(m)
+    return m & (X <= 1) & (n8 <= 3)
+
+
+def prune_mask(mask, min_branch):
+    """Morphological pruning (Gonzalez & Woods; the rule of include/rsu_graph.h) of a bool [N, H, W], image by image, L = min_branch:
+    X1 = A, L times X1 &= ~END(X1); E = END(X1), L times E = A & dilate8(E); B = X1 | E, with END(A) = A and X <= 1 and n8 <= 3. A
+    branch of at most L pixels goes, a longer one stays whole; a free curve of at most 2 L pixels vanishes; a loop is untouched. Known
+    artefact: a spur within L pixels (geodesic) of a true line end grows back with that end."""
+    a = _graph_mask(mask, "prune_mask")
+    L = _graph_branch(min_branch)
+    x1 = a.copy()
+    for _ in range(L):
+        x1 &= ~_graph_end(x1)
+    e = _graph_end(x1)
+    H, W = a.shape[1:]
+    for _ in range(L):
+        q = np.pad(e, ((0, 0), (1, 1), (1, 1)))
+        d = np.zeros_like(e)
+        for dy in (0, 1, 2):
+            for dx in (0, 1, 2):
+                d |= q[:, dy:dy + H, dx:dx + W]
+        e = a & d
+    return x1 | e if L else x1
+
+
+def skeleton_nodes(mask):
+    """(ends, isolated, junctions), bool [N, H, W] each, of a bool [N, H, W]: an end is a pixel of END(mask) with a neighbour, an
+    isolated pixel one without, a junction pixel a pixel of the mask whose crossing number X is 3 or more (include/rsu_graph.h).
+    Adjacent junction pixels are one junction."""
+    m = _graph_mask(mask, "skeleton_nodes")
+    n8, X = _graph_counts(m)
+    end = m & (X <= 1) & (n8 <= 3)
+    return end & (n8 >= 1), end & (n8 == 0), m & (X >= 3)
+
+
+def skeleton_graph(prob, threshold, labels, min_branch):
+    """rsu_skeleton_graph on the host, in its output formats: (out_pred float32, out_true int64, junc_pred float32, junc_true int64,
+    counts int64 [8]). out_* hold the pruned B of P = {label in {0, 1} and p >= threshold} and of T = {label == 1}, junc_* the junction
+    pixels of the two B; on the truth side an ignored pixel keeps its label. counts = {|B|, ends, isolated, junction pixels} of P, then
+    of T. labels=None: every pixel is counted, T is empty and the two *_true outputs are None."""
+    p, t, lab = _dist_check(prob, threshold, labels, False)
+    if max(p.shape[1:]) > GRAPH_MAX_SIDE:
+        raise ValueError("graph: H, W <= %d, not shape %r" % (GRAPH_MAX_SIDE, p.shape))
+    L = _graph_branch(min_branch)
+    pred, true = _dist_masks(p, t, lab)
+    counts = np.zeros(8, np.int64)
+    outs = []
+    for side, a in enumerate((pred, true)):
+        b = prune_mask(a, L)
+        ends, iso, junc = skeleton_nodes(b)
+        counts[4 * side:4 * side + 4] = (b.sum(), ends.sum(), iso.sum(), junc.sum())
+        outs.append((b, junc))
+    if lab is None:
+        out_true = junc_true = None
+    else:
+        counted = (lab == 0) | (lab == 1)
+        out_true, junc_true = (np.where(counted, m.astype(np.int64), lab) for m in outs[1])
+    return outs[0][0].astype(np.float32), out_true, outs[0][1].astype(np.float32), junc_true, counts
+
+
+def graph_metrics(jn_hist, jn_counts, counts, slack):
+    """The junction and end scores of a validation pass from jn_hist = the distance histogram of the two JUNCTION-PIXEL masks (int
+    [2, DIST_BINS]: distance_hist / rsu_distance_hist of skeleton_graph's junc_pred at threshold 0.5 and junc_true), jn_counts = four
+    integers {junction clusters of the prediction, of the truth (8-connected components of the junction pixels), the sum over the
+    patches of |pred - true| clusters, the patches with a counted pixel}, counts = skeleton_graph's eight integers, at `slack` pixels:
+      jn_precision   = the share of predicted junction pixels within slack of a true one (read as relaxed_metrics reads its histogram),
+      jn_recall      = the share of true junction pixels within slack of a predicted one,
+      jn_f1          = their harmonic mean, 0 when both are 0,
+      junctions_pred / junctions_true = the cluster counts,
+      junction_error = the mean |pred - true| clusters per patch that has a counted pixel, 0 without one,
+      ends_pred / ends_true / isolated_pred / isolated_true = pixel counts.
+    A road that leaves its patch ends there and counts as an end, on both sides alike: the comparison is the figure, not the count."""
+    h = np.asarray(jn_hist)
+    if h.shape != (2, DIST_BINS) or h.dtype.kind not in "iu":
+        raise ValueError("graph_metrics: jn_hist must be an integer array [2, %d], not %s %r" % (DIST_BINS, h.dtype, h.shape))
+    j = np.asarray(jn_counts)
+    if j.shape != (4,) or j.dtype.kind not in "iu" or (j < 0).any():
+        raise ValueError("graph_metrics: jn_counts must be four integers >= 0, not %s %r" % (j.dtype, jn_counts))
+    c = np.asarray(counts)
+    if c.shape != (8,) or c.dtype.kind not in "iu" or (c < 0).any():
+        raise ValueError("graph_metrics: counts must be eight integers >= 0, not %s %r" % (c.dtype, counts))
+    if isinstance(slack, bool) or not isinstance(slack, (int, np.integer)) or not 0 <= slack <= DIST_BINS - 2:
+        raise ValueError("graph_metrics: slack must be an integer in [0, %d], not %r" % (DIST_BINS - 2, slack))
+    h = h.astype(np.int64)
+    tot = [int(h[0].sum()), int(h[1].sum())]
+    prec, rec = [float(int(h[s][:int(slack) + 1].sum())) / max(tot[s], 1) for s in (0, 1)]
+    f1 = 2.0 * prec * rec / (prec + rec) if prec + rec > 0.0 else 0.0
+    jp, jt, err, patches = (int(v) for v in j)
+    return {"jn_precision": prec, "jn_recall": rec, "jn_f1": f1, "junctions_pred": jp, "junctions_true": jt,
+            "junction_error": float(err) / patches if patches else 0.0, "ends_pred": int(c[1]), "ends_true": int(c[5]),
+            "isolated_pred": int(c[2]), "isolated_true": int(c[6])}

@@ -19,7 +19,7 @@ import torch.distributed as dist
 from . import hostio
 from . import images as dimages
 from ._lib import call, lib
-from .hostio import DIST_BINS, DIST_MAX_SIDE, THIN_MAX_ITERS, THIN_MAX_SIDE, centerline_metrics, relaxed_metrics
+from .hostio import DIST_BINS, DIST_MAX_SIDE, GRAPH_MAX_BRANCH, GRAPH_MAX_SIDE, THIN_MAX_ITERS, THIN_MAX_SIDE, centerline_metrics, graph_metrics, relaxed_metrics
 from .dist import GradBucketer, micro_indices, shard_indices, tune_overlap  # noqa: F401  (shard_indices: importable from here as before)
 from .pool import BatchUploader, DevicePatchPool, PatchPool
 from .summary import Summary
@@ -124,6 +124,19 @@ EXTRA_FLAG_DEFS = [
                                       "and --save_centerlines"),
     ("save_centerlines", bool, False, "Inference: also write the centre-line of every predicted mask (after --min_road_area / "
                                       "--max_hole_area, at threshold 0.5) as a greyscale PNG beside the overlays"),
+    ("centerline_min_branch", int, 0, "L, an int in [0, 64]: prune the centre-lines on the GPU (morphological pruning: rsu_graph.h); a "
+                                      "branch of at most L pixels is removed, a longer one kept whole; 0 = off. Used by "
+                                      "--validate_centerlines (cl_hist, cl_correctness, cl_completeness, cl_quality, cl_len_pred and "
+                                      "cl_len_true then describe the pruned centre-lines; cldice_hard stays on the unpruned skeletons, its "
+                                      "counts need the full masks, which only the thinning sees) and --save_centerlines. A spur within L "
+                                      "pixels of a true line end returns with that end"),
+    ("validate_junctions", bool, False, "Requires --validate_centerlines: evaluate() also marks the junction pixels, ends and isolated "
+                                        "pixels of both (pruned) centre-lines on the GPU and returns jn_hist (the distance histogram of "
+                                        "the two junction-pixel masks), jn_precision, jn_recall and jn_f1 at --relaxed_slack, "
+                                        "junctions_pred / junctions_true (8-connected clusters of junction pixels), junction_error (the "
+                                        "mean |predicted - true| clusters per patch), ends_pred / ends_true and isolated_pred / "
+                                        "isolated_true. A road that leaves its patch ends there and counts as an end on both sides "
+                                        "alike: the comparison is the figure, not the count"),
     ("border_weight", float, 0.0, "w0 >= 0 of a border-distance weight map computed on the GPU from each batch's labels: a pixel counts "
                                   "1 + w0 * exp(-d^2 / (2 border_sigma^2)) times in the loss, d its distance to the other class inside its patch; "
                                   "0 = off (the U-Net paper uses 10). The loss stays normalised by the pixel count and the mean weight is above 1, "
@@ -333,6 +346,19 @@ def parse_centerline_max_iters(value):
         v, ok = 0, False
     if not ok:
         raise ValueError("--centerline_max_iters must be an integer in [1, %d], not %r" % (THIN_MAX_ITERS, value))
+    return v
+
+
+def parse_centerline_min_branch(value):
+    """The --centerline_min_branch value as an int in [0, 64] (rsu_graph.h RSU_GRAPH_MAX_BRANCH; 0 = off). Anything else raises
+    ValueError."""
+    try:
+        v = int(value)
+        ok = not isinstance(value, bool) and v == (float(value) if not isinstance(value, str) else v) and 0 <= v <= GRAPH_MAX_BRANCH
+    except (TypeError, ValueError, OverflowError):
+        v, ok = 0, False
+    if not ok:
+        raise ValueError("--centerline_min_branch must be an integer in [0, %d], not %r" % (GRAPH_MAX_BRANCH, value))
     return v
 
 
@@ -676,6 +702,10 @@ class Options(object):
         self.centerline_max_iters = parse_centerline_max_iters(self.centerline_max_iters)
         if self.save_best_metric == "cl_quality" and not self.validate_centerlines:
             raise ValueError("--save_best_metric=cl_quality requires --validate_centerlines: without it validation extracts no centre-lines")
+        self.centerline_min_branch = parse_centerline_min_branch(self.centerline_min_branch)
+        self.validate_junctions = bool(self.validate_junctions)
+        if self.validate_junctions and not self.validate_centerlines:
+            raise ValueError("--validate_junctions requires --validate_centerlines: without it validation extracts no centre-lines")
         self.border_weight, self.border_sigma = parse_border_weight(self.border_weight), parse_border_sigma(self.border_sigma)
         self.clip_grad_norm = parse_clip_grad_norm(self.clip_grad_norm)
         self.ema_decay, self.ema_warmup = parse_ema_decay(self.ema_decay), bool(self.ema_warmup)
@@ -770,6 +800,7 @@ class ConvolutionalModel:
         self._cc_acc = self._cc_ws = None    # --validate_components: the four counts and the workspace of rsu_components_pair_count
         self._dt_acc = self._dt_ws = None    # --validate_distances: the 2 x 64 counters and the workspace of rsu_distance_hist
         self._cl_acc = self._cl_ws = None    # --validate_centerlines: the 2 x 64 + 4 + 1 counters; the workspaces, skeletons and info
+        self._gr_acc = self._gr_ws = None    # --centerline_min_branch / --validate_junctions: the 8 + 2 x 64 + 4 counters; workspaces, junction masks
         if self.world > 1:
             self._bucketer = GradBucketer(self.net.flat_g, self.net.n_live)
             self._bucketer.extra_streams = list(self.net.wstreams)
@@ -941,6 +972,11 @@ class ConvolutionalModel:
         below 2^53), and the result gains "dist_hist" (int64 [2, 64]: the predicted road pixels by their distance to the truth, the true
         ones by theirs to the prediction) and the keys of hostio.relaxed_metrics of it at --relaxed_slack. Distances are per patch: a
         true road just outside a patch is not seen. The padding patches add exactly nothing.
+        With --validate_centerlines and --centerline_min_branch > 0 or --validate_junctions (only then) one rsu_skeleton_graph
+        (rsu_graph.h) per chunk behind rsu_mask_thin, in place on the two skeletons and before their rsu_distance_hist: the cl_* keys but
+        cldice_hard then describe the pruned centre-lines; with --validate_junctions also one rsu_distance_hist and one
+        rsu_components_pair_count (connectivity 8) on the two junction-pixel masks, and the result gains "jn_hist" (int64 [2, 64]) and
+        the keys of hostio.graph_metrics at --relaxed_slack. Their 8 + 128 + 4 counters ride last in the same read-back.
         averaged: None scores the averaged weights when the net has them (--ema_decay), True demands them (ValueError on a net without),
         False forces the raw weights; the device work runs inside net.averaged_weights(), and the result carries "averaged" (bool).
         Training is left as it was: weights, the averages and every packed copy (the exchange of averaged_weights() is undone), optimizer
@@ -973,6 +1009,12 @@ class ConvolutionalModel:
                 if with_th:
                     self._centerline_buffers()
                     self._cl_acc.zero_()
+                min_branch = int(getattr(self._options, "centerline_min_branch", 0)) if with_th else 0
+                with_jn = with_th and bool(getattr(self._options, "validate_junctions", False))
+                with_gr = min_branch > 0 or with_jn
+                if with_gr:
+                    self._graph_buffers()
+                    self._gr_acc.zero_()
                 for t0 in range(lo, hi, B):
                     nb = min(B, hi - t0)
                     if nb < B:
@@ -1005,9 +1047,20 @@ class ConvolutionalModel:
                              int(self._options.centerline_max_iters), ctypes.c_void_p(cl["skel_pred"].data_ptr()),
                              ctypes.c_void_p(cl["skel_true"].data_ptr()), ctypes.c_void_p(self._cl_acc[2 * DIST_BINS:].data_ptr()),
                              ctypes.c_void_p(cl["info"].data_ptr()), ctypes.c_void_p(cl["thin"].data_ptr()), B, net.P, net.P, st)
+                        if with_gr:   # prune the two skeletons in place and / or mark their junction pixels; the eight node counts
+                            gr, sp, sl = self._gr_ws, ctypes.c_void_p(cl["skel_pred"].data_ptr()), ctypes.c_void_p(cl["skel_true"].data_ptr())
+                            jp = ctypes.c_void_p(gr["junc_pred"].data_ptr()) if with_jn else None
+                            jt = ctypes.c_void_p(gr["junc_true"].data_ptr()) if with_jn else None
+                            call("rsu_skeleton_graph", sp, 0.5, sl, min_branch, sp if min_branch else None, sl if min_branch else None, jp, jt,
+                                 ctypes.c_void_p(self._gr_acc.data_ptr()), ctypes.c_void_p(gr["graph"].data_ptr()), B, net.P, net.P, st)
                         call("rsu_distance_hist", ctypes.c_void_p(cl["skel_pred"].data_ptr()), 0.5, ctypes.c_void_p(cl["skel_true"].data_ptr()),
                              ctypes.c_void_p(self._cl_acc.data_ptr()), ctypes.c_void_p(cl["dist"].data_ptr()), B, net.P, net.P, st)
                         self._cl_acc[-1] += (cl["info"] != 0).sum()   # (on the device: no read-back)
+                        if with_jn:   # how far the junction pixels of one side lie from the other's, and the junctions as clusters
+                            call("rsu_distance_hist", jp, 0.5, jt, ctypes.c_void_p(self._gr_acc[8:].data_ptr()),
+                                 ctypes.c_void_p(cl["dist"].data_ptr()), B, net.P, net.P, st)
+                            call("rsu_components_pair_count", jp, 0.5, jt, 8, ctypes.c_void_p(self._gr_acc[8 + 2 * DIST_BINS:].data_ptr()),
+                                 ctypes.c_void_p(gr["comp"].data_ptr()), B, net.P, net.P, st)
                 sums, hist = net.eval_sums.to(torch.float64), net.eval_hist.clone()
                 with_cl = net.cldice_weight > 0.0
                 if with_cl:   # the four clDice sums ride behind the five of the head: one all-reduce, one read-back
@@ -1021,10 +1074,15 @@ class ConvolutionalModel:
                     sums = torch.cat([sums, self._dt_acc.to(torch.float64)])
                 if with_th:   # and behind them the centre-line counters: 2 x 64 bins, the four counts, the unconverged image sides
                     sums = torch.cat([sums, self._cl_acc.to(torch.float64)])
+                if with_gr:   # and behind the centre-line counters the graph's: eight node counts, 2 x 64 junction bins, four cluster counts
+                    sums = torch.cat([sums, self._gr_acc.to(torch.float64)])
                 if self.world > 1:
                     dist.all_reduce(sums)
                     dist.all_reduce(hist)
                 sums, hist = sums.cpu().numpy(), hist.cpu().numpy()   # the one synchronisation
+                gr_sums = sums[-(2 * DIST_BINS + 12):] if with_gr else None
+                if with_gr:
+                    sums = sums[:-(2 * DIST_BINS + 12)]
                 th_sums = sums[-(2 * DIST_BINS + 5):] if with_th else None
                 if with_th:
                     sums = sums[:-(2 * DIST_BINS + 5)]
@@ -1060,7 +1118,36 @@ class ConvolutionalModel:
             out["cl_hist"] = th[:2 * DIST_BINS].reshape(2, DIST_BINS)
             out.update(centerline_metrics(out["cl_hist"], th[2 * DIST_BINS:2 * DIST_BINS + 4], int(self._options.relaxed_slack)))
             out["thin_unconverged"] = int(th[-1])
+        if with_gr:
+            gr = np.rint(gr_sums).astype(np.int64)
+            if min_branch > 0:   # the pruned centre-lines' pixel counts (cldice_hard stays on the unpruned skeletons)
+                out["cl_len_pred"], out["cl_len_true"] = int(gr[0]), int(gr[4])
+            if with_jn:
+                out["jn_hist"] = gr[8:8 + 2 * DIST_BINS].reshape(2, DIST_BINS)
+                out.update(graph_metrics(out["jn_hist"], gr[8 + 2 * DIST_BINS:], gr[:8], int(self._options.relaxed_slack)))
         return out
+
+    def _graph_buffers(self):
+        """the device buffers of --centerline_min_branch / --validate_junctions, made when evaluate() first needs them: the counters
+        (rsu_skeleton_graph's eight counts, the 2 x 64 bins of the junction pixels' distance histogram, the four cluster counts), the
+        workspace of rsu_skeleton_graph and, for the junctions, the two junction-pixel masks and the workspace of
+        rsu_components_pair_count (rsu_distance_hist re-uses the centre-lines' workspace)"""
+        if self._gr_acc is None:
+            net, B, dev = self.net, self.local_batch, self.net.device
+            need = int(lib().rsu_graph_ws_bytes(B, net.P, net.P, int(self._options.centerline_min_branch)))
+            if need == 0 or B * net.P * net.P * 8 >= 0x7ffffff0:
+                raise ValueError("--centerline_min_branch / --validate_junctions: a batch of %d patches of %d x %d pixels is outside "
+                                 "rsu_graph.h's limits (sides up to %d, the labels below 2 GiB)" % (B, net.P, net.P, GRAPH_MAX_SIDE))
+            self._gr_ws = {"graph": torch.zeros(need // 8, dtype=torch.int64, device=dev)}
+            if bool(self._options.validate_junctions):
+                need_cc = int(lib().rsu_components_ws_bytes(B, net.P, net.P))
+                if need_cc == 0:
+                    raise ValueError("--validate_junctions: a batch of %d patches of %d x %d pixels is outside rsu_components.h's limits"
+                                     % (B, net.P, net.P))
+                self._gr_ws.update({"junc_pred": torch.zeros((B, net.P, net.P), dtype=torch.float32, device=dev),
+                                    "junc_true": torch.zeros((B, net.P, net.P), dtype=torch.int64, device=dev),
+                                    "comp": torch.zeros(need_cc // 4, dtype=torch.int32, device=dev)})
+            self._gr_acc = torch.zeros(2 * DIST_BINS + 12, dtype=torch.int64, device=dev)
 
     def _centerline_buffers(self):
         """the device buffers of --validate_centerlines, made when evaluate() first needs them: the counters (the 2 x 64 bins of the
@@ -1125,6 +1212,12 @@ class ConvolutionalModel:
                       "skeleton pixels predicted {} true {}; unconverged image sides {}"
                       .format(step, v["cl_quality"], v["cl_completeness"], v["cl_correctness"], opts.relaxed_slack, v["cldice_hard"],
                               v["cl_len_pred"], v["cl_len_true"], v["thin_unconverged"]))
+            if "jn_f1" in v:
+                print("step {} validation junctions: f1 {:.4f} precision {:.4f} recall {:.4f} at slack {}; junctions predicted {} true {} "
+                      "error {:.4f}; ends predicted {} true {}; isolated pixels predicted {} true {}"
+                      .format(step, v["jn_f1"], v["jn_precision"], v["jn_recall"], opts.relaxed_slack, v["junctions_pred"],
+                              v["junctions_true"], v["junction_error"], v["ends_pred"], v["ends_true"], v["isolated_pred"],
+                              v["isolated_true"]))
             if self._summary is not None:
                 self._summary.add({"val_loss": v["loss"], "val_objective": v["objective"], "val_dice": v["dice"], "val_f1": v["f1"],
                                    "val_iou": v["iou"], "val_best_threshold": v["best_threshold"]}, global_step=step)
@@ -1141,6 +1234,9 @@ class ConvolutionalModel:
                 if "cl_quality" in v:
                     self._summary.add({"val_cl_quality": v["cl_quality"], "val_cl_completeness": v["cl_completeness"],
                                        "val_cl_correctness": v["cl_correctness"], "val_cldice_hard": v["cldice_hard"]}, global_step=step)
+                if "jn_f1" in v:
+                    self._summary.add({"val_jn_f1": v["jn_f1"], "val_jn_precision": v["jn_precision"], "val_jn_recall": v["jn_recall"],
+                                       "val_junction_error": v["junction_error"]}, global_step=step)
         # (the same numbers on every rank: they come out of the all-reduce)
         if self.best_val_f1 is None or v["f1"] > self.best_val_f1:
             self.best_val_f1 = v["f1"]
@@ -1149,7 +1245,7 @@ class ConvolutionalModel:
             self.best_val_score = score
             if opts.save_best:
                 self.save_as(os.path.abspath(os.path.join(opts.save_path, self.experiment_name + "-best.chkpt")))
-        return {k: v[k] for k in v if k not in ("sums", "hist", "cldice_sums", "dist_hist", "cl_hist")}
+        return {k: v[k] for k in v if k not in ("sums", "hist", "cldice_sums", "dist_hist", "cl_hist", "jn_hist")}
 
     def _ensure_summary(self):
         opts = self._options
@@ -1490,7 +1586,8 @@ class ConvolutionalModel:
     def centerlines(self, masks, threshold=0.5):
         """The centre-lines of predicted masks on the device (rsu_mask_thin with labels64 = NULL: every pixel counted): masks [n, H, W] or
         [n, H, W, 1] probabilities (what postprocess_masks returns) -> float32 [n, H, W], 1.0 on the one-pixel-wide, topology-preserving
-        skeleton of {p >= threshold} and 0.0 elsewhere, after at most --centerline_max_iters iterations of Guo & Hall's thinning.
+        skeleton of {p >= threshold} and 0.0 elsewhere, after at most --centerline_max_iters iterations of Guo & Hall's thinning, and with
+        --centerline_min_branch = L > 0 pruned of its branches of at most L pixels (rsu_skeleton_graph, in place on the skeletons).
         Integer decisions on the same input: every rank computes the same bits."""
         a = np.asarray(masks)
         if a.ndim == 4 and a.shape[3] == 1:
@@ -1509,6 +1606,11 @@ class ConvolutionalModel:
         ws = torch.empty(need // 8, dtype=torch.int64, device=dev)
         call("rsu_mask_thin", ctypes.c_void_p(t.data_ptr()), float(threshold), None, iters, ctypes.c_void_p(out.data_ptr()), None, None, None,
              ctypes.c_void_p(ws.data_ptr()), n, H, W, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        min_branch = int(getattr(self._options, "centerline_min_branch", 0))
+        if min_branch > 0:   # prune the skeletons in place (the sizes rsu_thin.h takes are the ones rsu_graph.h takes)
+            gws = torch.empty(int(lib().rsu_graph_ws_bytes(n, H, W, min_branch)) // 8, dtype=torch.int64, device=dev)
+            call("rsu_skeleton_graph", ctypes.c_void_p(out.data_ptr()), 0.5, None, min_branch, ctypes.c_void_p(out.data_ptr()), None, None, None,
+                 None, ctypes.c_void_p(gws.data_ptr()), n, H, W, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
         return out.cpu().numpy()
 
     # ------------------------------------------------------------------ checkpoints

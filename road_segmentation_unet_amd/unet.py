@@ -9,6 +9,7 @@ arithmetic kernel on the path is a hand-written HIP kernel reached through librs
 import ctypes
 import math
 import os
+import weakref
 
 import numpy as np
 import torch
@@ -180,7 +181,10 @@ class UNet(OptimizerStep):
         self.backward_cu_budget = None   # CUs the backward launches may plan for in total (None: the library's default)
         self._tuned = set()    # (training?, backward_cu_budget, dropout?) combinations the tuning pass has run for (tune / ensure_tuned)
         # which stream, CU share, weight-gradient group and workspace every launch gets; its side streams are `wstreams`
-        self.sched = BackwardSchedule(self.device, batch_size, training, self._timed)
+        # (the schedule reaches _timed through a weak reference: net -> sched -> bound method -> net would be a cycle, and a dropped net would
+        # hold its device buffers until Python's next FULL collection, which a long-running process with many objects rarely runs)
+        me = weakref.ref(self)
+        self.sched = BackwardSchedule(self.device, batch_size, training, lambda *args: me()._timed(*args))
         self.wstream = self.wstreams[0] if self.wstreams else None   # the first side stream
         self.pool_code = {}
         self.prof = None       # list collecting (tag, algorithmic flops, start event, end event, CU share) when profiling
