@@ -1,5 +1,6 @@
 """ctypes binding of librsu_hip.so (the C ABI of include/rsu.h, include/rsu_optim.h, include/rsu_loss.h, include/rsu_cldice.h,
-include/rsu_lovasz.h, include/rsu_components.h, include/rsu_distance.h, include/rsu_thin.h and include/rsu_graph.h).
+include/rsu_lovasz.h, include/rsu_components.h, include/rsu_distance.h, include/rsu_thin.h, include/rsu_graph.h and
+include/rsu_segments.h).
 
 The library is REQUIRED: there is no CPU or eager-PyTorch fallback anywhere in this package. If the
 shared object is missing or a symbol cannot be resolved, importing/using the product path raises."""
@@ -207,6 +208,12 @@ SIGNATURES_GRAPH = {
     "rsu_skeleton_graph": (_i, [_vp, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
 }
 
+# and for include/rsu_segments.h, the tenth (road segments: the centre-line cut at its node zones, one measured row per segment)
+SIGNATURES_SEGMENTS = {
+    "rsu_segments_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "rsu_line_segments": (_i, [_vp, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+}
+
 _lib = None
 
 
@@ -224,7 +231,8 @@ def lib():
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_OPTIM.items()) + list(SIGNATURES_LOSS.items()) \
                 + list(SIGNATURES_CLDICE.items()) + list(SIGNATURES_LOVASZ.items()) + list(SIGNATURES_COMPONENTS.items()) \
-                + list(SIGNATURES_DISTANCE.items()) + list(SIGNATURES_THIN.items()) + list(SIGNATURES_GRAPH.items()):
+                + list(SIGNATURES_DISTANCE.items()) + list(SIGNATURES_THIN.items()) + list(SIGNATURES_GRAPH.items()) \
+                + list(SIGNATURES_SEGMENTS.items()):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -245,6 +253,7 @@ CLDICE_MAX_ITERS = 16   # rsu_cldice.h RSU_CLDICE_MAX_ITERS
 DIST_BINS, DIST_NONE, DIST_MAX_SIDE = 64, 0x7fffffff, 1024   # rsu_distance.h RSU_DIST_BINS, RSU_DIST_NONE, RSU_DIST_MAX_SIDE
 THIN_MAX_SIDE, THIN_MAX_ITERS = 1024, 512   # rsu_thin.h RSU_THIN_MAX_SIDE, RSU_THIN_MAX_ITERS
 GRAPH_MAX_SIDE, GRAPH_MAX_BRANCH = 1024, 64   # rsu_graph.h RSU_GRAPH_MAX_SIDE, RSU_GRAPH_MAX_BRANCH
+SEGMENTS_MAX_SIDE, SEGMENTS_MAX_EDGES = 1024, 65536   # rsu_segments.h RSU_SEGMENTS_MAX_SIDE, RSU_SEGMENTS_MAX_EDGES
 E2BIG = -7
 
 

@@ -166,6 +166,7 @@ def main(argv=None):
         print("Prediction time:{} mins".format((time.time() - start) / 60))
         masks = _clean_up(model, masks, 0.5, rank)   # (quantize_mask binarises at 0.5 before it averages a block)
         lines = model.centerlines(masks, threshold=0.5) if opts.save_centerlines else None   # (of the cleaned masks, before they are quantised)
+        graphs = model.road_graph(masks, threshold=0.5) if opts.save_road_graph else None   # (of the cleaned masks too)
         masks = model.quantize_mask(masks, patch_size=hostio.IMG_PATCH_SIZE, threshold=hostio.FOREGROUND_THRESHOLD)
         if rank == 0:
             save_dir = os.path.abspath(os.path.join(opts.save_path, model.experiment_name))
@@ -174,6 +175,13 @@ def main(argv=None):
             if lines is not None:
                 hostio.save_all(lines, save_dir, "centerlines_{:03d}.png", greyscale=True)
                 print("Centre-lines: {} skeleton pixels in {} images".format(int(lines.sum()), len(lines)))
+            if graphs is not None:
+                import json
+                for i, g in enumerate(graphs):   # (numbered as save_all numbers the overlays)
+                    with open(os.path.join(save_dir, "graph_{:03d}.json".format(i + 1)), "w") as f:
+                        json.dump(g, f)
+                print("Road graphs: {} nodes and {} edges in {} images".format(sum(len(g["nodes"]) for g in graphs),
+                                                                               sum(len(g["edges"]) for g in graphs), len(graphs)))
             if masks.shape[1] % hostio.IMG_PATCH_SIZE or masks.shape[2] % hostio.IMG_PATCH_SIZE:
                 print("No submission.csv: {} x {} images are not made of whole {}-pixel patches".format(
                     masks.shape[1], masks.shape[2], hostio.IMG_PATCH_SIZE))

@@ -8,6 +8,10 @@
 
 constexpr int CC_TILE = 64;             // the tile's side: a row of a tile is one wave's ballot
 constexpr int CC_MAX_PIXELS = 1 << 24;  // H * W: an area fits the 25 low bits of a total, the edge flag sits at bit 30
+// a per-root total (cc_label leaves them behind the parents in ws): the area in the low bits, the edge flag above (segments.hip reads the area)
+constexpr int CC_EDGE = 1 << 30;
+constexpr int CC_AREA = (1 << 25) - 1;
+static_assert(CC_MAX_PIXELS <= CC_AREA, "an area fits below the edge flag");
 // the merge launches of one labelling: ceil(log2(max(tiles_y, tiles_x)))
 int cc_levels(int H, int W);
 // ws: five int32 arrays of N * H * W elements and four int32 counters per image

@@ -19,10 +19,7 @@
 constexpr int CC_THREADS = 256;
 constexpr int CC_ROWS = CC_TILE / (CC_THREADS / 64);   // rows of a tile per wave
 constexpr int CC_PIX = CC_TILE * CC_TILE;
-constexpr int CC_EDGE = 1 << 30;
-constexpr int CC_AREA = (1 << 25) - 1;
 static_assert(CC_TILE == 64 && CC_THREADS == 256, "a tile row is one 64-lane ballot, four waves share the 64 rows");
-static_assert(CC_MAX_PIXELS <= CC_AREA, "an area fits below the edge flag");
 
 enum { CC_FG = 0, CC_INV = 1, CC_HOLES = 2, CC_PRED = 3, CC_TRUTH = 4 };
 // what a labelling labels. A launch covers `planes` = N or 2 N masks: plane q is image q % N in mode `mode + q / N` (the pair count labels

@@ -21,6 +21,7 @@
 #include "../../include/rsu_distance.h"
 #include "../../include/rsu_thin.h"
 #include "../../include/rsu_graph.h"
+#include "../../include/rsu_segments.h"
 #include "affine_patches.h"
 #include "color_jitter.h"
 #include "border_map.h"
@@ -32,6 +33,7 @@
 #include "distance.h"
 #include "thin.h"
 #include "graph.h"
+#include "segments.h"
 #include "optim.h"
 #include "igemm.h"
 
@@ -1718,6 +1720,27 @@ extern "C" int rsu_skeleton_graph(const float* prob, float threshold, const int6
     if (graph_too_big(N, H, W, labels64 ? 8 : 4)) return RSU_E2BIG;
     HIP_CHECK_RET(gr_skeleton_graph(prob, threshold, labels64, min_branch, out_pred, out_true, junc_pred, junc_true, acc, ws, N, H, W,
                                     (hipStream_t)stream));
+    return RSU_OK;
+}
+// ---- road segments (rsu_segments.h): the centre-line cut at its node zones, labelled, ordered and measured segment by segment
+static_assert(RSU_SEGMENTS_MAX_SIDE == SG_MAX_SIDE && RSU_SEGMENTS_MAX_EDGES == SG_MAX_EDGES, "rsu_segments.h and segments.h must agree on the limits");
+static bool segments_size_ok(int N, int H, int W, int max_edges) {
+    return N >= 1 && H >= 1 && W >= 1 && H <= SG_MAX_SIDE && W <= SG_MAX_SIDE && max_edges >= 1 && max_edges <= SG_MAX_EDGES;
+}
+// the four int32 planes of one internal array, 16 bytes per pixel; labels64 has 8
+static bool segments_too_big(int N, int H, int W) { return (long)N * H * W * 16 >= 0x7ffffff0L; }
+extern "C" size_t rsu_segments_ws_bytes(int N, int H, int W, int max_edges) {
+    return segments_size_ok(N, H, W, max_edges) && !segments_too_big(N, H, W) ? sg_ws_bytes(N, H, W) : 0;
+}
+extern "C" int rsu_line_segments(const float* prob, float threshold, const int64_t* labels64, int max_edges, int32_t* edges_pred,
+                                 int32_t* edges_true, int32_t* counts, int32_t* seg_pred, int32_t* seg_true, int32_t* node_pred,
+                                 int32_t* node_true, unsigned long long* acc, void* ws, int N, int H, int W, rsu_stream_t stream) {
+    if (!prob || !ws || !counts || !edges_pred || (labels64 && !edges_true) || (!labels64 && (edges_true || seg_true || node_true)) ||
+        !segments_size_ok(N, H, W, max_edges) || !std::isfinite(threshold))
+        return RSU_EINVAL;
+    if (segments_too_big(N, H, W)) return RSU_E2BIG;
+    HIP_CHECK_RET(sg_line_segments(prob, threshold, labels64, max_edges, edges_pred, edges_true, counts, seg_pred, seg_true, node_pred, node_true,
+                                   acc, ws, N, H, W, (hipStream_t)stream));
     return RSU_OK;
 }
 static_assert(RSU_BORDER_MAX_SIDE == BM_MAX_SIDE, "rsu.h and border_map.h must agree on the supported tile size");

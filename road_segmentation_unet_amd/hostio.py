@@ -1355,3 +1355,181 @@ def graph_metrics(jn_hist, jn_counts, counts, slack):
     return {"jn_precision": prec, "jn_recall": rec, "jn_f1": f1, "junctions_pred": jp, "junctions_true": jt,
             "junction_error": float(err) / patches if patches else 0.0, "ends_pred": int(c[1]), "ends_true": int(c[5]),
             "isolated_pred": int(c[2]), "isolated_true": int(c[6])}
+
+
+# ---- road segments on the host (include/rsu_segments.h)
+SEGMENTS_MAX_SIDE, SEGMENTS_MAX_EDGES = 1024, 65536   # rsu_segments.h RSU_SEGMENTS_MAX_SIDE, RSU_SEGMENTS_MAX_EDGES
+SEGMENTS_BLOCK, SEGMENTS_TILE = 256, (64, 16)         # csrc/segments.hip SG_BLOCK; SG_TW, SG_TH
+_SEG_RING = ((-1, 0), (-1, 1), (0, 1), (1, 1), (1, 0), (1, -1), (0, -1), (-1, -1))   # p2 .. p9: clockwise from north
+
+
+def _segments_edges(max_edges):
+    if isinstance(max_edges, bool) or not isinstance(max_edges, (int, np.integer)) or not 1 <= max_edges <= SEGMENTS_MAX_EDGES:
+        raise ValueError("segments: max_edges must be an integer in [1, %d], not %r" % (SEGMENTS_MAX_EDGES, max_edges))
+    return int(max_edges)
+
+
+def segment_zones(mask):
+    """(S, Z), bool [N, H, W] each, of a bool [N, H, W]: J = the pixels with crossing number X >= 3, the node zones Z = mask and
+    dilate8(J), the segment pixels S = mask and not Z (include/rsu_segments.h)"""
+    a = _graph_mask(mask, "segment_zones")
+    junc = skeleton_nodes(a)[2]
+    H, W = a.shape[1:]
+    q = np.pad(junc, ((0, 0), (1, 1), (1, 1)))
+    d = np.zeros_like(a)
+    for dy in (0, 1, 2):
+        for dx in (0, 1, 2):
+            d |= q[:, dy:dy + H, dx:dx + W]
+    z = a & d
+    return a & ~z, z
+
+
+def _segments_image(a, max_edges, fill):
+    """(rows int32 [max_edges, 8], segments, nodes, seg int32 [H, W], node int32 [H, W]) of one bool [H, W]"""
+    H, W = a.shape
+    s, z = (m[0] for m in segment_zones(a[None]))
+    ends, iso, _ = skeleton_nodes(a[None])
+    end = (ends[0] | iso[0]) & s
+    seg, zone = _cc_labels(s, 8), _cc_labels(z, 8)
+    index = np.arange(H * W, dtype=np.int64).reshape(H, W)
+    node = np.where(end, -(index + 1), zone).astype(np.int32)
+    pad = lambda m: np.pad(m, 1)   # noqa: E731
+    at = lambda m, k: m[1 + _SEG_RING[k][0]:1 + _SEG_RING[k][0] + H, 1 + _SEG_RING[k][1]:1 + _SEG_RING[k][1] + W]   # noqa: E731
+    sq, zq, aq = pad(s), pad(zone), pad(a)
+    sn = [at(sq, k) for k in range(8)]
+    zn = [at(zq, k).astype(np.int64) for k in range(8)]
+    an = [at(aq, k) for k in range(8)]
+    # links towards E (2), SE (3), S (4), SW (5): every pair once; a diagonal one only if neither pixel 4-adjacent to both is in A
+    ortho = sn[2].astype(np.int64) + sn[4]
+    diag = (sn[3] & ~an[2] & ~an[4]).astype(np.int64) + (sn[5] & ~an[6] & ~an[4])
+    # contacts: the distinct zone labels among the eight neighbours; orthogonal if the label is among N, E, S, W
+    contacts = np.zeros((H, W), np.int64)
+    big = np.int64(1) << 40
+    lo, hi = np.full((H, W), big), np.full((H, W), -big)
+    for k in range(8):
+        first = zn[k] != 0
+        for m in range(k):
+            first &= zn[m] != zn[k]
+        edge = (zn[0] == zn[k]) | (zn[2] == zn[k]) | (zn[4] == zn[k]) | (zn[6] == zn[k])
+        contacts += first
+        ortho += first & edge
+        diag += first & ~edge
+        lo = np.where(first, np.minimum(lo, zn[k]), lo)
+        hi = np.where(first, np.maximum(hi, zn[k]), hi)
+    lo = np.where(end, np.minimum(lo, -(index + 1)), lo)
+    hi = np.where(end, np.maximum(hi, -(index + 1)), hi)
+    where = np.nonzero(s.reshape(-1))[0]
+    owner = seg.reshape(-1)[where].astype(np.int64)
+    labels = np.unique(owner)                          # ascending: the row order
+    row_of = np.searchsorted(labels, owner)
+    k = labels.size
+    table = np.zeros((k, 8), np.int64)
+    table[:, 0] = labels
+    table[:, 4], table[:, 5] = big, -big
+    for col, src in ((1, np.ones((H, W), np.int64)), (2, ortho), (3, diag), (6, contacts), (7, end.astype(np.int64))):
+        np.add.at(table[:, col], row_of, src.reshape(-1)[where])
+    np.minimum.at(table[:, 4], row_of, lo.reshape(-1)[where])
+    np.maximum.at(table[:, 5], row_of, hi.reshape(-1)[where])
+    none = table[:, 4] == big
+    table[none, 4] = table[none, 5] = 0
+    rows = np.full((max_edges, 8), fill, np.int32)
+    rows[:min(k, max_edges)] = table[:max_edges]
+    return rows, k, int(np.unique(zone[z]).size), seg, node
+
+
+def segments_acc(rows, stored):
+    """the eight integers rsu_line_segments adds to acc[side] for the first `stored` rows of one image: {rows stored, pixels, ortho,
+    diag, dangling, free, rings, multi}"""
+    r = np.asarray(rows)[:stored].astype(np.int64)
+    c, e = r[:, 6], r[:, 7]
+    return np.array([stored, r[:, 1].sum(), r[:, 2].sum(), r[:, 3].sum(), ((c == 1) & (e == 1)).sum(), ((c == 0) & (e >= 1)).sum(),
+                     (c + e == 0).sum(), (c + e > 2).sum()], np.int64)
+
+
+def line_segments(prob, threshold, labels, max_edges, fill=0):
+    """rsu_line_segments on the host, in its output formats: (edges_pred, edges_true int32 [N, max_edges, 8], counts int32 [N, 4],
+    seg_pred, seg_true, node_pred, node_true int32 [N, H, W], acc int64 [2, 8]) of P = {label in {0, 1} and p >= threshold} and of
+    T = {label == 1}. A row is {label, pixels, ortho, diag, node_a, node_b, contacts, ends}, in ascending label order; rows at and past
+    min(count, max_edges) keep `fill`; counts = {segments of P, nodes of P, segments of T, nodes of T}, the true numbers. labels=None:
+    every pixel is counted, T is empty and the three *_true outputs are None."""
+    p, t, lab = _dist_check(prob, threshold, labels, False)
+    if max(p.shape[1:]) > SEGMENTS_MAX_SIDE:
+        raise ValueError("segments: H, W <= %d, not shape %r" % (SEGMENTS_MAX_SIDE, p.shape))
+    cap = _segments_edges(max_edges)
+    N = p.shape[0]
+    counts = np.zeros((N, 4), np.int32)
+    acc = np.zeros((2, 8), np.int64)
+    outs = []
+    for side, a in enumerate(_dist_masks(p, t, lab)):
+        if side == 1 and lab is None:
+            outs.append((None, None, None))
+            continue
+        per = [_segments_image(a[n], cap, fill) for n in range(N)]
+        for n, (rows, k, nodes, _, _) in enumerate(per):
+            counts[n, 2 * side:2 * side + 2] = (k, nodes)
+            acc[side] += segments_acc(rows, min(k, cap))
+        outs.append((np.stack([r[0] for r in per]), np.stack([r[3] for r in per]), np.stack([r[4] for r in per])))
+    return outs[0][0], outs[1][0], counts, outs[0][1], outs[1][1], outs[0][2], outs[1][2], acc
+
+
+def segment_metrics(acc, counts_sum):
+    """The road-network figures of a validation pass from acc = rsu_line_segments' sixteen integers ([2, 8]: {rows stored, pixels, ortho,
+    diag, dangling, free, rings, multi} of the prediction, then of the truth) and counts_sum = the sum of its counts over the patches
+    ({segments of P, nodes of P, segments of T, nodes of T}), per side * in (pred, true):
+      segments_*          = the stored rows,
+      road_length_*       = ortho + sqrt(2) diag over them (float64),
+      seg_len_mean_*      = road_length / segments, 0 without one,
+      dangling_*, free_*, rings_*, multi_* = the rows of each kind,
+      segments_dropped_*  = the true segment count minus the stored rows (rows past --max_segments),
+      nodes_*             = the node zones,
+    and length_ratio = road_length_pred / road_length_true, 0 without truth."""
+    a = np.asarray(acc)
+    if a.shape != (2, 8) or a.dtype.kind not in "iu" or (a.astype(np.int64) < 0).any():
+        raise ValueError("segment_metrics: acc must be sixteen integers >= 0 as [2, 8], not %s %r" % (a.dtype, a.shape))
+    c = np.asarray(counts_sum)
+    if c.shape != (4,) or c.dtype.kind not in "iu" or (c.astype(np.int64) < 0).any():
+        raise ValueError("segment_metrics: counts_sum must be four integers >= 0, not %s %r" % (c.dtype, counts_sum))
+    out, length = {}, []
+    for side, name in enumerate(("pred", "true")):
+        rows, _, ortho, diag, dangling, free, rings, multi = (int(v) for v in a[side])
+        total = float(ortho) + float(np.sqrt(np.float64(2.0))) * float(diag)
+        length.append(total)
+        if int(c[2 * side]) < rows:
+            raise ValueError("segment_metrics: more stored rows (%d) than segments (%d)" % (rows, int(c[2 * side])))
+        out.update({"segments_" + name: rows, "road_length_" + name: total, "seg_len_mean_" + name: total / rows if rows else 0.0,
+                    "dangling_" + name: dangling, "free_" + name: free, "rings_" + name: rings, "multi_" + name: multi,
+                    "segments_dropped_" + name: int(c[2 * side]) - rows, "nodes_" + name: int(c[2 * side + 1])})
+    out["length_ratio"] = length[0] / length[1] if length[1] > 0.0 else 0.0
+    return out
+
+
+def road_graph(edges, count, node_map, H, W):
+    """One image's network as a plain dict from rsu_line_segments' outputs: edges int32 [max_edges, 8], count = its segment count (the
+    first min(count, max_edges) rows are read), node_map = node_* of the image, int32 [H, W] (sparse: node ids at zone pixels, negative
+    ids at line ends).
+      nodes: [{id, kind: junction | end | isolated, y, x}]: a junction's position is the centroid of its zone, an end's its pixel; an
+             isolated pixel is an end whose segment has one pixel. Ascending id.
+      edges: [{id, a, b, pixels, length, contacts, ends}], length = ortho + sqrt(2) diag, in row order."""
+    e = np.asarray(edges)
+    m = np.asarray(node_map)
+    if e.ndim != 2 or e.shape[1] != 8 or e.dtype.kind not in "iu":
+        raise ValueError("road_graph: edges must be an integer array [max_edges, 8], not %s %r" % (e.dtype, e.shape))
+    if m.shape != (H, W) or m.dtype.kind not in "iu":
+        raise ValueError("road_graph: node_map must be an integer array [%d, %d], not %s %r" % (H, W, m.dtype, m.shape))
+    if isinstance(count, bool) or not isinstance(count, (int, np.integer)) or count < 0:
+        raise ValueError("road_graph: count must be an integer >= 0, not %r" % (count,))
+    rows = e[:min(int(count), e.shape[0])].astype(np.int64)
+    lone = set(int(-r[4]) for r in rows if r[1] == 1 and r[6] == 0 and r[7] == 1)   # one-pixel segments without a contact
+    nodes = []
+    ys, xs = np.nonzero(m)
+    ids = m[ys, xs].astype(np.int64)
+    for i in np.unique(ids):
+        sel = ids == i
+        if i > 0:
+            nodes.append({"id": int(i), "kind": "junction", "y": float(ys[sel].mean()), "x": float(xs[sel].mean())})
+        else:
+            nodes.append({"id": int(i), "kind": "isolated" if int(-i) in lone else "end", "y": float(ys[sel][0]), "x": float(xs[sel][0])})
+    root2 = float(np.sqrt(np.float64(2.0)))
+    out = [{"id": int(r[0]), "a": int(r[4]), "b": int(r[5]), "pixels": int(r[1]), "length": float(r[2]) + root2 * float(r[3]),
+            "contacts": int(r[6]), "ends": int(r[7])} for r in rows]
+    return {"nodes": nodes, "edges": out}

@@ -20,6 +20,8 @@ from . import hostio
 from . import images as dimages
 from ._lib import call, lib
 from .hostio import DIST_BINS, DIST_MAX_SIDE, GRAPH_MAX_BRANCH, GRAPH_MAX_SIDE, THIN_MAX_ITERS, THIN_MAX_SIDE, centerline_metrics, graph_metrics, relaxed_metrics
+from .hostio import SEGMENTS_MAX_EDGES, SEGMENTS_MAX_SIDE, segment_metrics
+from .hostio import road_graph as hostio_road_graph
 from .dist import GradBucketer, micro_indices, shard_indices, tune_overlap  # noqa: F401  (shard_indices: importable from here as before)
 from .pool import BatchUploader, DevicePatchPool, PatchPool
 from .summary import Summary
@@ -137,6 +139,18 @@ EXTRA_FLAG_DEFS = [
                                         "mean |predicted - true| clusters per patch), ends_pred / ends_true and isolated_pred / "
                                         "isolated_true. A road that leaves its patch ends there and counts as an end on both sides "
                                         "alike: the comparison is the figure, not the count"),
+    ("validate_segments", bool, False, "Requires --validate_centerlines: evaluate() also cuts both (pruned) centre-lines at their "
+                                       "junctions into road segments on the GPU (rsu_segments.h) and returns segments_pred / segments_true, "
+                                       "road_length_pred / road_length_true (orthogonal links + sqrt(2) diagonal links, from node zone to "
+                                       "node zone), seg_len_mean_*, dangling_*, free_*, rings_*, multi_*, segments_dropped_* (segments "
+                                       "past --max_segments in a patch), nodes_* and length_ratio. Segments are per validation patch: a "
+                                       "road that leaves its patch ends there"),
+    ("max_segments", int, 4096, "An int in [1, 65536]: the rows of the segment table per image and side. Segments past it are counted "
+                                "(segments_dropped_*) but not measured. Used by --validate_segments and --save_road_graph"),
+    ("save_road_graph", bool, False, "Inference: also write the road network of every predicted mask (after --min_road_area / "
+                                     "--max_hole_area, at threshold 0.5; thinned, pruned by --centerline_min_branch, cut into segments) "
+                                     "as graph_%03d.json beside the overlays: nodes (junctions, ends, isolated pixels) and edges with "
+                                     "their lengths"),
     ("border_weight", float, 0.0, "w0 >= 0 of a border-distance weight map computed on the GPU from each batch's labels: a pixel counts "
                                   "1 + w0 * exp(-d^2 / (2 border_sigma^2)) times in the loss, d its distance to the other class inside its patch; "
                                   "0 = off (the U-Net paper uses 10). The loss stays normalised by the pixel count and the mean weight is above 1, "
@@ -359,6 +373,18 @@ def parse_centerline_min_branch(value):
         v, ok = 0, False
     if not ok:
         raise ValueError("--centerline_min_branch must be an integer in [0, %d], not %r" % (GRAPH_MAX_BRANCH, value))
+    return v
+
+
+def parse_max_segments(value):
+    """The --max_segments value as an int in [1, 65536] (rsu_segments.h RSU_SEGMENTS_MAX_EDGES). Anything else raises ValueError."""
+    try:
+        v = int(value)
+        ok = not isinstance(value, bool) and v == (float(value) if not isinstance(value, str) else v) and 1 <= v <= SEGMENTS_MAX_EDGES
+    except (TypeError, ValueError, OverflowError):
+        v, ok = 0, False
+    if not ok:
+        raise ValueError("--max_segments must be an integer in [1, %d], not %r" % (SEGMENTS_MAX_EDGES, value))
     return v
 
 
@@ -706,6 +732,10 @@ class Options(object):
         self.validate_junctions = bool(self.validate_junctions)
         if self.validate_junctions and not self.validate_centerlines:
             raise ValueError("--validate_junctions requires --validate_centerlines: without it validation extracts no centre-lines")
+        self.validate_segments, self.save_road_graph = bool(self.validate_segments), bool(self.save_road_graph)
+        self.max_segments = parse_max_segments(self.max_segments)
+        if self.validate_segments and not self.validate_centerlines:
+            raise ValueError("--validate_segments requires --validate_centerlines: without it validation extracts no centre-lines")
         self.border_weight, self.border_sigma = parse_border_weight(self.border_weight), parse_border_sigma(self.border_sigma)
         self.clip_grad_norm = parse_clip_grad_norm(self.clip_grad_norm)
         self.ema_decay, self.ema_warmup = parse_ema_decay(self.ema_decay), bool(self.ema_warmup)
@@ -801,6 +831,7 @@ class ConvolutionalModel:
         self._dt_acc = self._dt_ws = None    # --validate_distances: the 2 x 64 counters and the workspace of rsu_distance_hist
         self._cl_acc = self._cl_ws = None    # --validate_centerlines: the 2 x 64 + 4 + 1 counters; the workspaces, skeletons and info
         self._gr_acc = self._gr_ws = None    # --centerline_min_branch / --validate_junctions: the 8 + 2 x 64 + 4 counters; workspaces, junction masks
+        self._sg_acc = self._sg_ws = None    # --validate_segments: the 16 + 4 counters; the workspace, the two segment tables, the counts
         if self.world > 1:
             self._bucketer = GradBucketer(self.net.flat_g, self.net.n_live)
             self._bucketer.extra_streams = list(self.net.wstreams)
@@ -977,6 +1008,9 @@ class ConvolutionalModel:
         cldice_hard then describe the pruned centre-lines; with --validate_junctions also one rsu_distance_hist and one
         rsu_components_pair_count (connectivity 8) on the two junction-pixel masks, and the result gains "jn_hist" (int64 [2, 64]) and
         the keys of hostio.graph_metrics at --relaxed_slack. Their 8 + 128 + 4 counters ride last in the same read-back.
+        With --validate_centerlines and --validate_segments (only then) one rsu_line_segments (rsu_segments.h) per chunk on the two
+        (pruned) skeletons, --max_segments rows per patch and side; its sixteen counters and the patches' summed counts are kept on the
+        device, ride last of all in the same read-back, and the result gains the keys of hostio.segment_metrics.
         averaged: None scores the averaged weights when the net has them (--ema_decay), True demands them (ValueError on a net without),
         False forces the raw weights; the device work runs inside net.averaged_weights(), and the result carries "averaged" (bool).
         Training is left as it was: weights, the averages and every packed copy (the exchange of averaged_weights() is undone), optimizer
@@ -1015,6 +1049,10 @@ class ConvolutionalModel:
                 if with_gr:
                     self._graph_buffers()
                     self._gr_acc.zero_()
+                with_sg = with_th and bool(getattr(self._options, "validate_segments", False))
+                if with_sg:
+                    self._segment_buffers()
+                    self._sg_acc.zero_()
                 for t0 in range(lo, hi, B):
                     nb = min(B, hi - t0)
                     if nb < B:
@@ -1055,6 +1093,13 @@ class ConvolutionalModel:
                                  ctypes.c_void_p(self._gr_acc.data_ptr()), ctypes.c_void_p(gr["graph"].data_ptr()), B, net.P, net.P, st)
                         call("rsu_distance_hist", ctypes.c_void_p(cl["skel_pred"].data_ptr()), 0.5, ctypes.c_void_p(cl["skel_true"].data_ptr()),
                              ctypes.c_void_p(self._cl_acc.data_ptr()), ctypes.c_void_p(cl["dist"].data_ptr()), B, net.P, net.P, st)
+                        if with_sg:   # the segments of the two (pruned) skeletons; the patches' counts are summed on the device
+                            sg = self._sg_ws
+                            call("rsu_line_segments", ctypes.c_void_p(cl["skel_pred"].data_ptr()), 0.5, ctypes.c_void_p(cl["skel_true"].data_ptr()),
+                                 int(self._options.max_segments), ctypes.c_void_p(sg["edges_pred"].data_ptr()),
+                                 ctypes.c_void_p(sg["edges_true"].data_ptr()), ctypes.c_void_p(sg["counts"].data_ptr()), None, None, None, None,
+                                 ctypes.c_void_p(self._sg_acc.data_ptr()), ctypes.c_void_p(sg["segments"].data_ptr()), B, net.P, net.P, st)
+                            self._sg_acc[16:] += sg["counts"].sum(dim=0)
                         self._cl_acc[-1] += (cl["info"] != 0).sum()   # (on the device: no read-back)
                         if with_jn:   # how far the junction pixels of one side lie from the other's, and the junctions as clusters
                             call("rsu_distance_hist", jp, 0.5, jt, ctypes.c_void_p(self._gr_acc[8:].data_ptr()),
@@ -1076,10 +1121,15 @@ class ConvolutionalModel:
                     sums = torch.cat([sums, self._cl_acc.to(torch.float64)])
                 if with_gr:   # and behind the centre-line counters the graph's: eight node counts, 2 x 64 junction bins, four cluster counts
                     sums = torch.cat([sums, self._gr_acc.to(torch.float64)])
+                if with_sg:   # and last of all the segments': sixteen counters and the four summed counts
+                    sums = torch.cat([sums, self._sg_acc.to(torch.float64)])
                 if self.world > 1:
                     dist.all_reduce(sums)
                     dist.all_reduce(hist)
                 sums, hist = sums.cpu().numpy(), hist.cpu().numpy()   # the one synchronisation
+                sg_sums = sums[-20:] if with_sg else None
+                if with_sg:
+                    sums = sums[:-20]
                 gr_sums = sums[-(2 * DIST_BINS + 12):] if with_gr else None
                 if with_gr:
                     sums = sums[:-(2 * DIST_BINS + 12)]
@@ -1125,7 +1175,26 @@ class ConvolutionalModel:
             if with_jn:
                 out["jn_hist"] = gr[8:8 + 2 * DIST_BINS].reshape(2, DIST_BINS)
                 out.update(graph_metrics(out["jn_hist"], gr[8 + 2 * DIST_BINS:], gr[:8], int(self._options.relaxed_slack)))
+        if with_sg:
+            sg = np.rint(sg_sums).astype(np.int64)
+            out.update(segment_metrics(sg[:16].reshape(2, 8), sg[16:]))
         return out
+
+    def _segment_buffers(self):
+        """the device buffers of --validate_segments, made when evaluate() first needs them: the counters (rsu_line_segments' sixteen
+        and the four summed counts), its workspace, the two segment tables of --max_segments rows per patch and the per-patch counts"""
+        if self._sg_acc is None:
+            net, B, dev = self.net, self.local_batch, self.net.device
+            cap = int(self._options.max_segments)
+            need = int(lib().rsu_segments_ws_bytes(B, net.P, net.P, cap))
+            if need == 0:
+                raise ValueError("--validate_segments: a batch of %d patches of %d x %d pixels is outside rsu_segments.h's limits (sides up "
+                                 "to %d, 16 bytes per pixel below 2 GiB)" % (B, net.P, net.P, SEGMENTS_MAX_SIDE))
+            self._sg_ws = {"segments": torch.zeros(need // 8, dtype=torch.int64, device=dev),
+                           "edges_pred": torch.zeros((B, cap, 8), dtype=torch.int32, device=dev),
+                           "edges_true": torch.zeros((B, cap, 8), dtype=torch.int32, device=dev),
+                           "counts": torch.zeros((B, 4), dtype=torch.int32, device=dev)}
+            self._sg_acc = torch.zeros(20, dtype=torch.int64, device=dev)
 
     def _graph_buffers(self):
         """the device buffers of --centerline_min_branch / --validate_junctions, made when evaluate() first needs them: the counters
@@ -1218,6 +1287,12 @@ class ConvolutionalModel:
                       .format(step, v["jn_f1"], v["jn_precision"], v["jn_recall"], opts.relaxed_slack, v["junctions_pred"],
                               v["junctions_true"], v["junction_error"], v["ends_pred"], v["ends_true"], v["isolated_pred"],
                               v["isolated_true"]))
+            if "length_ratio" in v:
+                print("step {} validation road segments: predicted {} true {}; road length predicted {:.1f} true {:.1f} (ratio {:.4f}); "
+                      "nodes predicted {} true {}; dangling predicted {} true {}; multi predicted {} true {}; dropped predicted {} true {}"
+                      .format(step, v["segments_pred"], v["segments_true"], v["road_length_pred"], v["road_length_true"], v["length_ratio"],
+                              v["nodes_pred"], v["nodes_true"], v["dangling_pred"], v["dangling_true"], v["multi_pred"], v["multi_true"],
+                              v["segments_dropped_pred"], v["segments_dropped_true"]))
             if self._summary is not None:
                 self._summary.add({"val_loss": v["loss"], "val_objective": v["objective"], "val_dice": v["dice"], "val_f1": v["f1"],
                                    "val_iou": v["iou"], "val_best_threshold": v["best_threshold"]}, global_step=step)
@@ -1237,6 +1312,9 @@ class ConvolutionalModel:
                 if "jn_f1" in v:
                     self._summary.add({"val_jn_f1": v["jn_f1"], "val_jn_precision": v["jn_precision"], "val_jn_recall": v["jn_recall"],
                                        "val_junction_error": v["junction_error"]}, global_step=step)
+                if "length_ratio" in v:
+                    self._summary.add({"val_length_ratio": v["length_ratio"], "val_road_length_pred": v["road_length_pred"],
+                                       "val_road_length_true": v["road_length_true"]}, global_step=step)
         # (the same numbers on every rank: they come out of the all-reduce)
         if self.best_val_f1 is None or v["f1"] > self.best_val_f1:
             self.best_val_f1 = v["f1"]
@@ -1612,6 +1690,36 @@ class ConvolutionalModel:
             call("rsu_skeleton_graph", ctypes.c_void_p(out.data_ptr()), 0.5, None, min_branch, ctypes.c_void_p(out.data_ptr()), None, None, None,
                  None, ctypes.c_void_p(gws.data_ptr()), n, H, W, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
         return out.cpu().numpy()
+
+    def road_graph(self, masks, threshold=0.5):
+        """The road network of predicted masks, one plain dict per image (hostio.road_graph: nodes and edges with their lengths): masks
+        [n, H, W] or [n, H, W, 1] probabilities -> the centre-lines of {p >= threshold} (rsu_mask_thin, pruned by --centerline_min_branch:
+        centerlines()), cut at their junctions into segments and measured on the device (rsu_line_segments, --max_segments rows per
+        image; a dict carries "segments" = the true segment count, which may exceed its edges). Integer decisions on the same input:
+        every rank computes the same network."""
+        lines = self.centerlines(masks, threshold)
+        n, H, W = (int(v) for v in lines.shape)
+        cap = int(getattr(self._options, "max_segments", 4096))
+        need = int(lib().rsu_segments_ws_bytes(n, H, W, cap))
+        if need == 0:
+            raise ValueError("road_graph (--save_road_graph): %d masks of %d x %d pixels are outside rsu_segments.h's limits (sides up to %d, "
+                             "n * H * W * 16 below 2 GiB): use smaller stacks" % (n, H, W, SEGMENTS_MAX_SIDE))
+        dev = self.net.device
+        t = torch.as_tensor(lines).to(dev)
+        edges = torch.zeros((n, cap, 8), dtype=torch.int32, device=dev)
+        counts = torch.zeros((n, 4), dtype=torch.int32, device=dev)
+        node = torch.zeros((n, H, W), dtype=torch.int32, device=dev)
+        ws = torch.empty(need // 8, dtype=torch.int64, device=dev)
+        call("rsu_line_segments", ctypes.c_void_p(t.data_ptr()), 0.5, None, cap, ctypes.c_void_p(edges.data_ptr()), None,
+             ctypes.c_void_p(counts.data_ptr()), None, None, ctypes.c_void_p(node.data_ptr()), None, None, ctypes.c_void_p(ws.data_ptr()),
+             n, H, W, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        edges, counts, node = edges.cpu().numpy(), counts.cpu().numpy(), node.cpu().numpy()
+        out = []
+        for i in range(n):
+            g = hostio_road_graph(edges[i], int(counts[i, 0]), node[i], H, W)
+            g["segments"] = int(counts[i, 0])
+            out.append(g)
+        return out
 
     # ------------------------------------------------------------------ checkpoints
     def save_as(self, path):
