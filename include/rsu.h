@@ -40,8 +40,16 @@
  *   rsu_packed_first_bytes bytes. It writes nothing to its inputs, and its results do not depend on whatever lies around any of these
  *   ranges: a caller may place its buffers back to back. The kernels' buffer descriptors do not bound anything: the
  *   contract rests on the kernels' own predicates, and tests/test_gpu_fenced.py holds every launching entry point to it inside an arena
- *   whose every byte outside the payloads is a NaN pattern. Base pointers are 256-byte aligned there; the 16-byte (4-byte, 8-byte)
- *   alignment notes at the entries below are what the ABI requires.
+ *   whose every byte outside the payloads is a NaN pattern.
+ *   Alignment: every launching entry point (and every call that stores a device pointer in a table for a later launch) states at its
+ *   prototype, as "align (entry): argument bytes, ...", the alignment of each pointer argument: the widest single access or atomic the
+ *   kernels make through it (16 for the 16-byte pieces of a bf16 tensor or of packed weights and for float4 passes, 8 for 64-bit labels,
+ *   keys, plane words and counters, 4 for tensors read float by float), for a workspace the largest need of anything carved out of it;
+ *   "host" marks host memory that is read before the call returns, "byte" a tensor of bytes. A key "p.field" or "p[]" is a device pointer
+ *   inside the host struct or array p. A non-NULL pointer that is no multiple of its number is RSU_EINVAL, before anything is launched or
+ *   written; NULL keeps the meaning it has at the entry; at the stated alignment -- and at no larger one -- every entry is exact:
+ *   tests/test_align_limits_host.py holds each entry to its refusal, tests/test_gpu_aligned_min.py runs each inside the arena with every
+ *   buffer at 256 k + its number. Nothing else is assumed: a buffer that follows another back to back needs only its own alignment.
  */
 #ifndef RSU_H_
 #define RSU_H_
@@ -111,15 +119,19 @@ int rsu_input_size_needed(int output_size, int num_layers, int* input_size);
  * every byte of it, the zero padding of the fragment order included: the buffer needs no initialisation. */
 size_t rsu_packed_bytes(int taps, int rows, const int* seg_c, int nseg);
 /* conv forward (unet.py:34-45,88-91): A[tap][co][ci]; seg_c = channel count of each concat source */
+/* align (rsu_pack_conv_fwd): w_hwio 4, packed 2, seg_c host. */
 int rsu_pack_conv_fwd(const float* w_hwio, void* packed, int k, int Cin, int Cout, const int* seg_c, int nseg,
                       rsu_stream_t stream);
 /* conv backward-data (Conv2DBackpropInput): A[flipped tap][ci][co] for the input channels
  * [ci_off, ci_off+ci_cnt) of a kernel with Cin_total inputs (one pack per concat source) */
+/* align (rsu_pack_conv_bwd): w_hwio 4, packed 2. */
 int rsu_pack_conv_bwd(const float* w_hwio, void* packed, int k, int Cin_total, int ci_off, int ci_cnt, int Cout,
                       rsu_stream_t stream);
 /* transposed conv forward (unet.py:67-68): four 1x1 matrices A[a*2+b][co][ci] */
+/* align (rsu_pack_convT_fwd): k_hwoi 4, packed 2. */
 int rsu_pack_convT_fwd(const float* k_hwoi, void* packed, int Cin, int Cout, rsu_stream_t stream);
 /* transposed conv backward-data: A[a*2+b][ci][co] */
+/* align (rsu_pack_convT_bwd): k_hwoi 4, packed 2. */
 int rsu_pack_convT_bwd(const float* k_hwoi, void* packed, int Cin, int Cout, rsu_stream_t stream);
 
 /* Batched packing: every weight tensor of the network re-packed by ONE kernel launch (the per-tensor calls above cost a
@@ -132,9 +144,11 @@ int rsu_pack_convT_bwd(const float* k_hwoi, void* packed, int Cin, int Cout, rsu
 #define RSU_PACK_CONVT_BWD 3
 #define RSU_PACK_CONV_FIRST 4
 size_t rsu_pack_table_entry_bytes(void);
+/* align (rsu_pack_table_add): host_table host, w 4, packed 16, seg_c host. */
 int rsu_pack_table_add(void* host_table, int index, int kind, const float* w, void* packed, int k, int Cin_total, int ci_off,
                        int ci_cnt, int Cout, const int* seg_c, int nseg);
 int rsu_pack_table_finish(void* host_table, int nentries, int* total_blocks);
+/* align (rsu_pack_table_run): dev_table 8. */
 int rsu_pack_table_run(const void* dev_table, int nentries, int total_blocks, rsu_stream_t stream);
 
 /* ---- network head / tail (VALU kernels) -------------------------------------------------- */
@@ -147,6 +161,7 @@ int rsu_pack_table_run(const void* dev_table, int nentries, int total_blocks, rs
  * mask, all ones without dropout) -- channels 0..2 feed the first 3x3 conv, channels 4..15 are kept for the weight and
  * bias gradients of color_space_adjust (rsu_conv_first_bwd_weight). */
 /* limit: out16, npix * 32 bytes (the dropout counter 3 * npix + c then stays below 2^28). */
+/* align (rsu_color_adjust_fwd): x 4, w 4, b 4, out16 16. */
 int rsu_color_adjust_fwd(const float* x, const float* w, const float* b, void* out16, long npix, float keep, unsigned key,
                          rsu_stream_t stream);
 /* unet.py:34-35,42-43 first 3x3 conv of level 0 (Cin = 3) + bias + ReLU, dil = 1 or 2 (dilated branch).
@@ -154,7 +169,9 @@ int rsu_color_adjust_fwd(const float* x, const float* w, const float* b, void* o
  * zero, so the (x-0.5) copy in channels 4..6 does not contribute); y bf16 [N][H-2d][W-2d][Cout]. */
 /* limit: max(in16 = N*H*W*32, y = N*(H-2d)*(W-2d)*Cout*2) bytes. */
 size_t rsu_packed_first_bytes(int Cout);
+/* align (rsu_pack_conv_first): w_hwio 4, packed 2. */
 int rsu_pack_conv_first(const float* w_hwio, void* packed, int Cout, rsu_stream_t stream);
+/* align (rsu_conv_first_fwd): in16 16, packed 16, b 4, y 16. */
 int rsu_conv_first_fwd(const void* in16, const void* packed, const float* b, void* y, int N, int H, int W, int Cout,
                        int dil, int ncu, rsu_stream_t stream);
 /* unet.py:22-23 AND unet.py:34-35,42-43 in one launch (no dropout: keep == 1): y = relu(conv3x3(conv1x1(x - 0.5, w0) + b0, W1, dilation) + b) straight from
@@ -163,6 +180,7 @@ int rsu_conv_first_fwd(const void* in16, const void* packed, const float* b, voi
  * B = 4, 572 px); the results are bit-identical to rsu_color_adjust_fwd(keep = 1) + rsu_conv_first_fwd. A training step still calls
  * rsu_color_adjust_fwd (rsu_conv_first_bwd_weight reads its output), but may do so on another stream, off the forward pass's critical path. */
 /* limit: max(x = N*H*W*12, y = N*(H-2d)*(W-2d)*Cout*2) bytes (y always reaches it first: Cout >= 8). */
+/* align (rsu_color_conv_first_fwd): x 4, w0 4, b0 4, packed 16, b 4, y 16. */
 int rsu_color_conv_first_fwd(const float* x, const float* w0, const float* b0, const void* packed, const float* b, void* y, int N, int H,
                              int W, int Cout, int dil, int ncu, rsu_stream_t stream);
 /* weight/bias gradients of that conv and, through it, of color_space_adjust (no input-gradient pass is needed):
@@ -174,16 +192,19 @@ int rsu_color_conv_first_fwd(const float* x, const float* w0, const float* b0, c
 size_t rsu_conv_first_bwd_ws_floats(int Cout);
 /* db (optional): BiasAddGrad of this conv, computed by the same launch. limit: max(in16 = N*H*W*32, dz = N*(H-2d)*(W-2d)*Cout*2) bytes
  * (igemm_wg1's own bound of 2^28 output pixels lies beyond it: 2^28 pixels of in16 are 8 GiB). */
+/* align (rsu_conv_first_bwd_weight): in16 16, dz 16, dw1 4, gx 4, db 16, ws 16. */
 int rsu_conv_first_bwd_weight(const void* in16, const void* dz, float* dw1, float* gx, float* db, float* ws, int N,
                               int H, int W, int Cout, int dil, int ncu, rsu_stream_t stream);
 /* The two sums above in one launch: dW0 f32 [3][3] ([ci][cj]) and db0 f32 [3] from gx [9][12][Cout] and W1 f32 HWIO
  * [3][3][3][Cout]; scale = 1/keep. accumulate != 0 adds to dW0/db0 (the dilated twin conv_dilut_0 shares color_space_adjust). */
+/* align (rsu_color_adjust_bwd): gx 4, w1 4, dW0 4, db0 4. */
 int rsu_color_adjust_bwd(const float* gx, const float* w1, float* dW0, float* db0, int Cout, float scale, int accumulate,
                          rsu_stream_t stream);
 /* unet.py:95 weight_output 1x1 conv (C -> 2) fused with tf_aerial_images.py:147-148 softmax[...,1].
  * act bf16 [npix][C]; w f32 [C][2]; prob f32 [npix]; logits f32 [npix][2] or NULL (unet.forward's return value). */
 /* limit (this and every rsu_head_* entry below, rsu_loss.h and rsu_cldice.h included): act (and dact), npix * C * 2 bytes -- with C >= 8
  * the largest tensor of the call (labels and logits are 8 bytes per pixel). */
+/* align (rsu_head_fwd): act 16, w 4, b 4, prob 4, logits 4. */
 int rsu_head_fwd(const void* act, const float* w, const float* b, float* prob, float* logits, long npix, int C,
                  rsu_stream_t stream);
 /* Same plus tf_aerial_images.py:103-110 mean sparse softmax cross-entropy and its backward:
@@ -192,6 +213,7 @@ int rsu_head_fwd(const void* act, const float* w, const float* b, float* prob, f
  * scaled by inv_count (1 / global pixel count); dw f32 [C][2], db f32 [2] (overwritten).
  * ws: rsu_head_ws_floats(npix, C) floats. */
 size_t rsu_head_ws_floats(long npix, int C);
+/* align (rsu_head_fwd_bwd): act 16, w 4, b 4, labels 8, prob 4, loss_sum 4, dact 16, dw 4, db 4, ws 4. */
 int rsu_head_fwd_bwd(const void* act, const float* w, const float* b, const int64_t* labels, float* prob,
                      float* loss_sum, void* dact, float* dw, float* db, float* ws, long npix, int C,
                      float inv_count, rsu_stream_t stream);
@@ -208,6 +230,7 @@ int rsu_head_fwd_bwd(const void* act, const float* w, const float* b, const int6
  * omega_p == 1 (class_w {1, 1} or NULL, pixel_w all ones or NULL, labels in {0,1}) they equal rsu_head_fwd_bwd's bit for bit.
  * ws: rsu_head_w_ws_floats(npix, C) floats (one more partial per workgroup than rsu_head_ws_floats). */
 size_t rsu_head_w_ws_floats(long npix, int C);
+/* align (rsu_head_fwd_bwd_w): act 16, w 4, b 4, labels 8, class_w 4, pixel_w 4, prob 4, loss_sum 4, weight_sum 4, dact 16, dw 4, db 4, ws 4. */
 int rsu_head_fwd_bwd_w(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w,
                        const float* pixel_w, float* prob, float* loss_sum, float* weight_sum, void* dact, float* dw, float* db,
                        float* ws, long npix, int C, float inv_count, rsu_stream_t stream);
@@ -231,8 +254,11 @@ int rsu_head_fwd_bwd_w(const void* act, const float* w, const float* b, const in
  * RSU_EINVAL for dice_sums == NULL, a smooth that is not finite and > 0, a dice_scale that is not finite and >= 0 -- returned before
  * anything is launched or written. ws: rsu_head_dice_ws_floats(npix, C) floats, enough for either call. */
 size_t rsu_head_dice_ws_floats(long npix, int C);
+/* align (rsu_head_dice_sums): act 16, w 4, b 4, labels 8, pixel_w 4, prob 4, dice_sums 4, ws 4. */
 int rsu_head_dice_sums(const void* act, const float* w, const float* b, const int64_t* labels, const float* pixel_w, float* prob,
                        float* dice_sums, float* ws, long npix, int C, rsu_stream_t stream);
+/* align (rsu_head_fwd_bwd_dice): act 16, w 4, b 4, labels 8, class_w 4, pixel_w 4, dice_sums 4, prob 4, loss_sum 4, weight_sum 4, dact 16, dw 4,
+ * db 4, ws 4. */
 int rsu_head_fwd_bwd_dice(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w,
                           const float* pixel_w, const float* dice_sums, float dice_scale, float smooth, float* prob, float* loss_sum,
                           float* weight_sum, void* dact, float* dw, float* db, float* ws, long npix, int C, float inv_count,
@@ -253,6 +279,7 @@ int rsu_head_fwd_bwd_dice(const void* act, const float* w, const float* b, const
  * ws: rsu_head_eval_ws_floats(npix, C) floats (0 for a refused C or npix). */
 #define RSU_EVAL_BINS 256
 size_t rsu_head_eval_ws_floats(long npix, int C);
+/* align (rsu_head_eval): act 16, w 4, b 4, labels 8, class_w 4, pixel_w 4, prob 4, sums 4, hist 8, ws 4. */
 int rsu_head_eval(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w, const float* pixel_w,
                   float* prob, float* sums, unsigned long long* hist, float* ws, long npix, int C, rsu_stream_t stream);
 
@@ -278,6 +305,7 @@ int rsu_head_eval(const void* act, const float* w, const float* b, const int64_t
 #define RSU_BORDER_D2_INF 0x7fffffff
 #define RSU_BORDER_MAX_SIDE 1024
 size_t rsu_border_map_ws_bytes(int N, int H, int W);
+/* align (rsu_border_map): labels 8, mul 4, out 4, d2 4, ws 4. */
 int rsu_border_map(const int64_t* labels, const float* mul, float* out, int32_t* d2 /* may be NULL */, void* ws,
                    int N, int H, int W, float w0, float sigma, rsu_stream_t stream);
 
@@ -286,6 +314,7 @@ int rsu_border_map(const int64_t* labels, const float* mul, float* out, int32_t*
  * All sources share the window size (Hin, Win); y is bf16 [N][Hin-2d][Win-2d][Cout]. */
 /* limit (rsu_conv2d_fwd, _fwd_pool, _bwd_data and their _k forms): the output, and EVERY source as a whole, N * H * W * C * 2 bytes of the
  * uncropped tensor (a cropped skip tensor is larger than its window). */
+/* align (rsu_conv2d_fwd): srcs host, srcs.ptr 16, packed_fwd 16, bias 4, y 16. */
 int rsu_conv2d_fwd(const rsu_src_t* srcs, int nsrc, const void* packed_fwd, const float* bias, void* y, int N,
                    int Hin, int Win, int Cout, int dil, int relu, int ncu, rsu_stream_t stream);
 /* The same three launches (rsu_conv2d_fwd, rsu_conv2d_fwd_pool, rsu_conv2d_bwd_data) with a caller-owned workspace `kws` of `kws_floats`
@@ -301,10 +330,13 @@ int rsu_conv2d_fwd(const rsu_src_t* srcs, int nsrc, const void* packed_fwd, cons
  * the rule batch-independent cost the N = 4 step 12-14 %, profiles/r05/abenv_perimg_*.txt). The workspace must not be shared with a launch
  * running concurrently on another stream: the host keeps one per stream that issues conv launches. */
 size_t rsu_conv_splitk_ws_floats(void);
+/* align (rsu_conv2d_fwd_k): srcs host, srcs.ptr 16, packed_fwd 16, bias 4, y 16, kws 16. */
 int rsu_conv2d_fwd_k(const rsu_src_t* srcs, int nsrc, const void* packed_fwd, const float* bias, void* y, int N,
                      int Hin, int Win, int Cout, int dil, int relu, int ncu, float* kws, size_t kws_floats, rsu_stream_t stream);
+/* align (rsu_conv2d_fwd_pool_k): srcs host, srcs.ptr 16, packed_fwd 16, bias 4, y 16, pooled 16, code 8, kws 16. */
 int rsu_conv2d_fwd_pool_k(const rsu_src_t* srcs, int nsrc, const void* packed_fwd, const float* bias, void* y, void* pooled, void* code,
                           int N, int Hin, int Win, int Cout, float keep, unsigned key, int ncu, float* kws, size_t kws_floats, rsu_stream_t stream);
+/* align (rsu_conv2d_bwd_data_k): dz 16, packed_bwd 16, dx 16, relu_src 16, kws 16. */
 int rsu_conv2d_bwd_data_k(const void* dz, const void* packed_bwd, void* dx, const void* relu_src, int accumulate, int N, int H, int W,
                           int Cin_total, int ci_off, int ci_cnt, int Cout, int dil, int ncu, float* kws, size_t kws_floats, rsu_stream_t stream);
 /* unet.py:44-52 in one launch: y = relu(conv3x3_valid(concat(srcs), W) + b) (dilation 1), pooled = max_pooling2d(y, 2, 2) followed by
@@ -313,12 +345,14 @@ int rsu_conv2d_bwd_data_k(const void* dz, const void* packed_bwd, void* dx, cons
  * sizes pool with floor semantics, as max_pooling2d does. Where a tile shape with whole 2x2 windows per wavefront fits the layer, the
  * size is even and keep == 1 the pool is part of the conv kernel's epilogue (lane shuffles on the packed results; the activation is not
  * read back from HBM); otherwise the call issues the two launches itself. Same bits either way. */
+/* align (rsu_conv2d_fwd_pool): srcs host, srcs.ptr 16, packed_fwd 16, bias 4, y 16, pooled 16, code 8. */
 int rsu_conv2d_fwd_pool(const rsu_src_t* srcs, int nsrc, const void* packed_fwd, const float* bias, void* y, void* pooled, void* code,
                         int N, int Hin, int Win, int Cout, float keep, unsigned key, int ncu, rsu_stream_t stream);
 /* Conv2DBackpropInput for input channels [ci_off, ci_off+ci_cnt) of a conv with Cin_total inputs:
  * dx bf16 [N][H][W][ci_cnt] (H, W = conv input size), dz bf16 [N][H-2d][W-2d][Cout].
  * relu_src (optional, same shape as dx): dx *= (relu_src > 0)  -- ReluGrad of the producing layer.
  * accumulate != 0: dx += result (two consumers of one tensor, unet.py:32-45). */
+/* align (rsu_conv2d_bwd_data): dz 16, packed_bwd 16, dx 16, relu_src 16. */
 int rsu_conv2d_bwd_data(const void* dz, const void* packed_bwd, void* dx, const void* relu_src, int accumulate,
                         int N, int H, int W, int Cin_total, int ci_off, int ci_cnt, int Cout, int dil, int ncu,
                         rsu_stream_t stream);
@@ -330,6 +364,7 @@ size_t rsu_conv2d_bwd_weight_ws_floats(int Cin_total, int src_C, int Cout);
  * 32-pixel step); pass it with ONE of the sources of a concatenated input, NULL with the others.
  * limit: max(src as a whole = N*src.H*src.W*src.C*2, dz = N*Ho*Wo*Cout*2) bytes ("beyond that the offsets wrapped"); rsu_wgrad_group_plan
  * returns the same RSU_E2BIG for any of its jobs. */
+/* align (rsu_conv2d_bwd_weight): src host, src.ptr 16, dz 16, dw 16, db 16, ws 16. */
 int rsu_conv2d_bwd_weight(const rsu_src_t* src, const void* dz, float* dw, float* db, float* ws, int N, int Ho, int Wo,
                           int Cin_total, int ci_off, int Cout, int dil, int ncu, rsu_stream_t stream);
 /* Grouped weight gradients (new; TensorFlow's executor runs independent Conv2DBackpropFilter ops side by side, tf_aerial_images.py:120-121).
@@ -359,21 +394,26 @@ typedef struct {
 } rsu_wgrad_job_t;
 size_t rsu_wgrad_group_table_bytes(void);
 size_t rsu_wgrad_group_ws_floats(void);
+/* align (rsu_wgrad_group_plan): jobs host, jobs.db 16, jobs.dw 16, jobs.dz 16, jobs.src.ptr 16, ws 16, host_table host. */
 int rsu_wgrad_group_plan(const rsu_wgrad_job_t* jobs, int njobs, float* ws, int N, int ncu, void* host_table);
+/* align (rsu_wgrad_group_run): host_table host, dev_table 8. */
 int rsu_wgrad_group_run(const void* host_table, const void* dev_table, rsu_stream_t stream);
 /* BiasAddGrad: db[c] = sum over npix of dz[pix][c]. ws: rsu_bias_grad_ws_floats(npix, C) floats. */
 /* limit: dz, npix * C * 2 bytes. */
 size_t rsu_bias_grad_ws_floats(long npix, int C);
+/* align (rsu_bias_grad): dz 16, db 4, ws 4. */
 int rsu_bias_grad(const void* dz, float* db, float* ws, long npix, int C, rsu_stream_t stream);
 
 /* ---- 2x2 max pool -------------------------------------------------------------------------- */
 /* unet.py:52 max_pooling2d (2,2)/(2,2) VALID, then the next level's dropout (unet.py:29-30; keep = 1: none).
  * x bf16 [N][H][W][C] -> y [N][H/2][W/2][C] */
 /* limit (both forms): x, N*H*W*C*2 bytes (the dropout counter, a pooled element index, then stays below 2^28). */
+/* align (rsu_maxpool2x2_fwd): x 16, y 16. */
 int rsu_maxpool2x2_fwd(const void* x, void* y, int N, int H, int W, int C, float keep, unsigned key,
                        rsu_stream_t stream);
 /* ... and, for training, a code tensor for the gradient junction below (H, W even; code [N][H/2][W/2][C] bytes, may be NULL):
  * per pooled element bits 0-3 = (window element 2*dy+dx > 0), bits 4-5 = the window's first maximum in row-major order. */
+/* align (rsu_maxpool2x2_fwd_code): x 16, y 16, code 8. */
 int rsu_maxpool2x2_fwd_code(const void* x, void* y, void* code, int N, int H, int W, int C, float keep, unsigned key,
                             rsu_stream_t stream);
 /* Gradient junction at an encoder output y_act (ReLU output, bf16 [N][H][W][C]):
@@ -385,36 +425,43 @@ int rsu_maxpool2x2_fwd_code(const void* x, void* y, void* code, int N, int H, in
  * MaxPoolGrad routes to the first maximum of the window in row-major order.
  * limit (both forms): dz (= y_act), N*H*W*C*2 bytes: the int row count N * (H / 2) and pooled element index of the code-byte kernel and the
  * 32-bit dropout counter of both kernels then stay below 2^28. */
+/* align (rsu_pool_skip_relu_bwd): y_act 16, dpool 16, dskip 16, dz 16. */
 int rsu_pool_skip_relu_bwd(const void* y_act, const void* dpool, const void* dskip, void* dz, int N, int H, int W,
                            int C, int Hs, int Ws, float keep, unsigned key, rsu_stream_t stream);
 /* The same junction from the code tensor of rsu_maxpool2x2_fwd_code instead of the activation (y_act may then be NULL): one
  * byte per pooled element instead of four bf16 activations, the same bits. */
+/* align (rsu_pool_skip_relu_bwd_code): y_act 16, code 8, dpool 16, dskip 16, dz 16. */
 int rsu_pool_skip_relu_bwd_code(const void* y_act, const void* code, const void* dpool, const void* dskip, void* dz, int N,
                                 int H, int W, int C, int Hs, int Ws, float keep, unsigned key, rsu_stream_t stream);
 /* unet.py:64-65 dropout in front of a transposed conv: y = x / keep * floor(keep + U), bf16 [n] -> bf16 [n] (n % 8 == 0).
  * Its backward is fused into rsu_convT2x2_bwd_data: pass y as relu_src (y > 0 <=> x > 0 and kept) and out_scale = 1/keep. */
 /* limit: n * 2 bytes (the dropout counter is the element index, then below 2^30); an n that is no multiple of 8 is RSU_EINVAL first. */
+/* align (rsu_dropout_fwd): x 16, y 16. */
 int rsu_dropout_fwd(const void* x, void* y, long n, float keep, unsigned key, rsu_stream_t stream);
 
 /* ---- 2x2 stride-2 transposed convolution (unet.py:67-68) ---------------------------------- */
 /* limit (all three): max(x = N*H*W*Cin*2, y / dy = N*4*H*W*Cout*2) bytes. The faster kernels' own bounds (igemm_ct: the 4x tensor below the
  * limit; igemm_wgt: 2^28 input pixels) select no slower path that could run: the generic launches behind them refuse the same tensors,
  * and 2^28 pixels of 8 channels are 4 GiB. */
+/* align (rsu_convT2x2_fwd): x 16, packed_fwd 16, bias 4, y 16. */
 int rsu_convT2x2_fwd(const void* x, const void* packed_fwd, const float* bias, void* y, int N, int H, int W,
                      int Cin, int Cout, int ncu, rsu_stream_t stream);
 /* dx bf16 [N][H][W][Cin] = out_scale * sum_{a,b,co} dy[2i+a][2j+b][co] K[a][b][co][ci], times (relu_src > 0) if given.
  * out_scale != 1 is applied by a second pass over the stored tensor: dx = bf16(out_scale * bf16(sum)), two roundings by design
  * (tests/test_gpu_rounding.py holds it to exactly these two). */
+/* align (rsu_convT2x2_bwd_data): dy 16, packed_bwd 16, dx 16, relu_src 16. */
 int rsu_convT2x2_bwd_data(const void* dy, const void* packed_bwd, void* dx, const void* relu_src, float out_scale,
                           int N, int H, int W, int Cin, int Cout, int ncu, rsu_stream_t stream);
 /* dK f32 [2][2][Cout][Cin] and, when db != NULL, db f32 [Cout] = sum over all pixels of dy (BiasAddGrad of the transposed
  * conv, unet.py:72) from the same launch; ws: rsu_convT2x2_bwd_weight_ws_floats() floats */
 size_t rsu_convT2x2_bwd_weight_ws_floats(int Cin, int Cout);
+/* align (rsu_convT2x2_bwd_weight): x 16, dy 16, dK 16, db 16, ws 16. */
 int rsu_convT2x2_bwd_weight(const void* x, const void* dy, float* dK, float* db, float* ws, int N, int H, int W,
                             int Cin, int Cout, int ncu, rsu_stream_t stream);
 
 /* ---- optimizer (tf_aerial_images.py:116-121, MomentumOptimizer, use_nesterov=False) ------- */
 /* acc = mu*acc + gscale*g ; w -= lr*acc. gscale folds the 1/world_size of data-parallel averaging. */
+/* align (rsu_momentum_step): w 16, acc 16, g 16. */
 int rsu_momentum_step(float* w, float* acc, const float* g, float lr, float mu, float gscale, long n,
                       rsu_stream_t stream);
 
@@ -430,10 +477,13 @@ int rsu_momentum_step(float* w, float* acc, const float* g, float lr, float mu, 
  * written again (rewriting it every step would cost the pass bandwidth for bytes that never change): every packed buffer of a table must
  * have been packed ONCE by rsu_pack_* / rsu_pack_table_run (from the initial weights) before the first run. */
 size_t rsu_update_table_entry_bytes(void);
+/* align (rsu_update_table_add_plain): host_table host, w 16, acc 16, g 16. */
 int rsu_update_table_add_plain(void* host_table, int index, float* w, float* acc, const float* g, long n);
+/* align (rsu_update_table_add): host_table host, w 16, acc 16, g 16, packed_fwd 16, packed_bwd host, packed_bwd[] 16, seg_c host. */
 int rsu_update_table_add(void* host_table, int index, int kind, float* w, float* acc, const float* g, void* packed_fwd,
                          void* const* packed_bwd, int Cin_total, int Cout, const int* seg_c, int nseg);
 int rsu_update_table_finish(void* host_table, int nentries, int* total_blocks);
+/* align (rsu_update_table_run): dev_table 8. */
 int rsu_update_table_run(const void* dev_table, int nentries, int total_blocks, float lr, float mu, float gscale,
                          rsu_stream_t stream);
 
@@ -443,6 +493,7 @@ int rsu_update_table_run(const void* dev_table, int nentries, int total_blocks, 
  * with alpha = lr_t * sqrt(1 - beta2^t) / (1 - beta1^t) computed by the caller in float32 (AdamOptimizer._apply_dense; beta1^t and
  * beta2^t are the float32 `beta1_power` / `beta2_power` accumulators, multiplied by beta1 / beta2 after every step as
  * AdamOptimizer._finish does). gscale folds the 1/world_size of data-parallel averaging. w, m, v, g 16-byte aligned. */
+/* align (rsu_adam_step): w 16, m 16, v 16, g 16. */
 int rsu_adam_step(float* w, float* m, float* v, const float* g, float alpha, float beta1, float beta2, float epsilon, float gscale,
                   long n, rsu_stream_t stream);
 /* The Adam step of every live variable and the re-pack of the MFMA copies in ONE launch: the table of rsu_update_table_add[_plain]
@@ -450,7 +501,9 @@ int rsu_adam_step(float* w, float* m, float* v, const float* g, float alpha, flo
  * same extent as acc) before rsu_update_table_finish. Reads w, m, v, g once, writes w, m, v and the packed layouts: 32 B per weight of
  * a packed conv kernel, 28 B per plain-range float (Momentum: 24 B and 20 B). Same arithmetic per element as rsu_adam_step, same
  * packed bits as rsu_pack_*. */
+/* align (rsu_update_table_set_second_slot): host_table host, v 16. */
 int rsu_update_table_set_second_slot(void* host_table, int index, float* v);
+/* align (rsu_update_table_run_adam): dev_table 8. */
 int rsu_update_table_run_adam(const void* dev_table, int nentries, int total_blocks, float alpha, float beta1, float beta2,
                               float epsilon, float gscale, rsu_stream_t stream);
 
@@ -483,14 +536,17 @@ int rsu_update_table_run_adam(const void* dev_table, int nentries, int total_blo
 #define RSU_GRAD_NORM_BLOCK_FLOATS 16384
 size_t rsu_clip_state_bytes(void);
 size_t rsu_grad_norm_ws_floats(long n);
+/* align (rsu_grad_norm): g 16, ws 4, state 4. */
 int rsu_grad_norm(const float* g, long n, float max_norm, float* ws, void* state, rsu_stream_t stream);
 /* rsu_update_table_run / rsu_update_table_run_adam with gscale * state->scale for gscale (one float32 multiply, made once per
  * workgroup; everything behind it is the arithmetic of the plain pass, so a _clip run whose record holds scale s gives the bits of the
  * plain run with gscale * s). `state` is a record rsu_grad_norm wrote earlier on the same stream. With RSU_CLIP_NONFINITE set in it
  * every workgroup returns before its first load: weights, optimizer slots and packed copies stay as they are, consistent with each
  * other. RSU_EINVAL for a NULL or misaligned state (and what the plain run rejects), before anything is launched. */
+/* align (rsu_update_table_run_clip): dev_table 8, state 4. */
 int rsu_update_table_run_clip(const void* dev_table, int nentries, int total_blocks, float lr, float mu, float gscale,
                               const void* state, rsu_stream_t stream);
+/* align (rsu_update_table_run_adam_clip): dev_table 8, state 4. */
 int rsu_update_table_run_adam_clip(const void* dev_table, int nentries, int total_blocks, float alpha, float beta1, float beta2,
                                    float epsilon, float gscale, const void* state, rsu_stream_t stream);
 
@@ -507,6 +563,7 @@ int rsu_update_table_run_adam_clip(const void* dev_table, int nentries, int tota
  * averages as they were. Any other record behaves as NULL (the scale is the gradient's business, not the average's).
  * Errors, returned before anything is launched: RSU_EINVAL for a NULL ema or w, n < 1, a one_minus_decay that is not in (0, 1] (nan
  * included), an ema or w that is not 16-byte aligned, overlapping ema and w ranges, a clip_state that is not 4-byte aligned. */
+/* align (rsu_ema_step): ema 16, w 16, clip_state 4. */
 int rsu_ema_step(float* ema, const float* w, long n, float one_minus_decay, const void* clip_state /* may be NULL */,
                  rsu_stream_t stream);
 
@@ -525,6 +582,7 @@ int rsu_ema_step(float* ema, const float* w, long n, float one_minus_decay, cons
  * Errors, returned before anything is launched: RSU_EINVAL for a NULL dst or src, n < 1, a dst or src that is not 16-byte aligned,
  * overlapping [dst, dst + n) and [src, src + n); RSU_E2BIG for an n whose grid would not fit 31 bits. */
 #define RSU_GRAD_ACCUMULATE_BLOCK_FLOATS 8192
+/* align (rsu_grad_accumulate): dst 16, src 16. */
 int rsu_grad_accumulate(float* dst, const float* src, long n, int assign, rsu_stream_t stream);
 
 /* ---- patch / stride tiler (src/images.py) -------------------------------------------------- */
@@ -532,12 +590,15 @@ int rsu_grad_accumulate(float* dst, const float* src, long n, int assign, rsu_st
  * y-inner order, images.py:76-77) of image n is the [S][S] window of the symmetric-padded image at
  * origin (x0, y0) = ((t / pps) * stride, (t % pps) * stride). imgs f32 [nimg][H][H][3];
  * tiles f32 [ntiles][S][S][3] for tile indices [t0, t0+ntiles) of the flattened (img, t) list. */
+/* align (rsu_extract_tiles): imgs 4, tiles 4. */
 int rsu_extract_tiles(const float* imgs, float* tiles, int nimg, int H, int S, int P, int stride, long t0,
                       long ntiles, rsu_stream_t stream);
 /* images.py:131-164 images_from_patches, accumulation half: acc[n][y0+i][x0+j] += prob[t][i][j],
  * hits += 1 (f32 accumulators [nimg][H][H]; the division is rsu_overlap_finish). */
+/* align (rsu_overlap_add): prob 4, acc 4, hits 4. */
 int rsu_overlap_add(const float* prob, float* acc, float* hits, int nimg, int H, int P, int stride, long t0,
                     long ntiles, rsu_stream_t stream);
+/* align (rsu_overlap_finish): acc 4, hits 4, out 4. */
 int rsu_overlap_finish(const float* acc, const float* hits, float* out, long n, rsu_stream_t stream);
 
 /* ---- the tiler for images of any size: rectangular, any stride, clamped last tile (new) ----- */
@@ -553,12 +614,14 @@ int rsu_tile_grid(int H, int W, int P, int stride, int* ny, int* nx);
  * reflects repeatedly. Pure data movement; every index is 64-bit. On an input rsu_extract_tiles accepts the tiles are its tiles.
  * Errors, returned before anything is launched: RSU_EINVAL for a NULL imgs or tiles, nimg < 1, P > H, P > W, P > S, an odd S - P,
  * stride < 1, t0 < 0, ntiles < 1, t0 + ntiles > nimg * nx * ny. */
+/* align (rsu_extract_tiles_rect): imgs 4, tiles 4. */
 int rsu_extract_tiles_rect(const float* imgs, float* tiles, int nimg, int H, int W, int S, int P, int stride, long t0,
                            long ntiles, rsu_stream_t stream);
 /* rsu_overlap_add on that grid: acc and hits f32 [nimg][H][W]. Gather form, one thread per output pixel, no atomics: the pixel's
  * covering tiles of [t0, t0 + ntiles) are summed in increasing tile index (per axis the regular tiles, then the clamped one, each
  * counted once) in double and added to acc once per call; hits += their number. On an input rsu_overlap_add accepts acc and hits get
  * its bits. The division is rsu_overlap_finish. Errors as rsu_extract_tiles_rect (without S), for a NULL prob, acc or hits. */
+/* align (rsu_overlap_add_rect): prob 4, acc 4, hits 4. */
 int rsu_overlap_add_rect(const float* prob, float* acc, float* hits, int nimg, int H, int W, int P, int stride, long t0,
                          long ntiles, rsu_stream_t stream);
 
@@ -595,6 +658,7 @@ typedef struct {
     int pad_;
 } rsu_affine_t; /* 32 bytes */
 #define RSU_AFFINE_MAX_LAUNCH 32
+/* align (rsu_affine_patches): images 4, labels byte, recs host, x_out 4, labels_out 8. */
 int rsu_affine_patches(const float* images, const uint8_t* labels, const rsu_affine_t* recs /* HOST pointer */, int nrec, int nimg, int He,
                        int Hl, int S, int P, float* x_out, int64_t* labels_out, rsu_stream_t stream);
 
@@ -648,6 +712,7 @@ typedef struct {
 } rsu_elastic_t; /* 48 bytes */
 #define RSU_ELASTIC_MAX_LAUNCH 32
 #define RSU_ELASTIC_MAX_GRID 16
+/* align (rsu_elastic_patches): images 4, labels byte, recs host, x_out 4, labels_out 8. */
 int rsu_elastic_patches(const float* images, const uint8_t* labels, const rsu_elastic_t* recs /* HOST pointer */, int nrec, int nimg, int He,
                         int Hl, int S, int P, float* x_out, int64_t* labels_out, rsu_stream_t stream);
 
@@ -690,6 +755,7 @@ typedef struct {
 } rsu_jitter_t;    /* 80 bytes */
 #define RSU_JITTER_MAX_LAUNCH 32
 size_t rsu_color_jitter_ws_bytes(int nrec, int S);
+/* align (rsu_color_jitter): x 4, recs host, ws 8. */
 int rsu_color_jitter(float* x /* f32 [nrec][S][S][3], in place */, const rsu_jitter_t* recs /* HOST pointer */,
                      int nrec, int S, void* ws /* may be NULL when every k[] is zero */, rsu_stream_t stream);
 
@@ -697,18 +763,22 @@ int rsu_color_jitter(float* x /* f32 [nrec][S][S][3], in place */, const rsu_jit
 /* images.py:256-266 quantize_mask: per patch_size block of masks f32 [nimg][S][S] (channel axis squeezed), label =
  * mean(mask >= 0.5) > threshold, written over the block of `out` (out == masks is allowed: a block is read completely before it
  * is written). patch_size <= 64. */
+/* align (rsu_quantize_mask): masks 4, out 4. */
 int rsu_quantize_mask(const float* masks, float* out, int nimg, int S, int patch_size, float threshold, rsu_stream_t stream);
 /* rsu_quantize_mask on masks f32 [nimg][H][W]: the same rule per patch_size block; a block cut by the image's edge takes the mean over
  * the pixels it holds. out == masks is allowed; patch_size <= 64. RSU_EINVAL for a NULL masks or out, nimg, H, W or patch_size below 1,
  * patch_size above 64; RSU_E2BIG for more than 2^31 - 1 blocks. */
+/* align (rsu_quantize_mask_rect): masks 4, out 4. */
 int rsu_quantize_mask_rect(const float* masks, float* out, int nimg, int H, int W, int patch_size, float threshold,
                            rsu_stream_t stream);
 /* images.py:88-99 labels_for_patches over images.py:35-85 extract_patches(masks, patch_size): labels int64
  * [nimg][S/ps][S/ps] in the reference's patch order (x outer, y inner), label = mean(patch) > threshold. */
+/* align (rsu_labels_for_patches): masks 4, labels 8. */
 int rsu_labels_for_patches(const float* masks, int64_t* labels, int nimg, int S, int patch_size, float threshold,
                            rsu_stream_t stream);
 /* summary.py:141-147 tf.metrics.accuracy / recall / precision keep running counts: counts[0..3] += TP, FP, FN, TN of n
  * int64 {0,1} labels (caller zeroes `counts` where the reference runs tf.local_variables_initializer()). */
+/* align (rsu_confusion_counts): predictions 8, labels 8, counts 8. */
 int rsu_confusion_counts(const int64_t* predictions, const int64_t* labels, long n, unsigned long long* counts,
                          rsu_stream_t stream);
 

@@ -41,8 +41,10 @@ extern "C" {
  * B * H * W >= 2^31, iters outside [0, RSU_CLDICE_MAX_ITERS], a smooth that is not finite and > 0, a scale that is not finite and >= 0. */
 #define RSU_CLDICE_MAX_ITERS 16
 size_t rsu_cldice_ws_floats(int B, int H, int W, int iters);   /* 0 for refused arguments */
+/* align (rsu_cldice_fwd): prob 4, labels 8, skel_p 4, skel_y 4, sums 4, ws 4. */
 int rsu_cldice_fwd(const float* prob, const int64_t* labels, int iters, float* skel_p, float* skel_y, float* sums, float* ws, int B, int H,
                    int W, rsu_stream_t stream);
+/* align (rsu_cldice_bwd): prob 4, labels 8, skel_p 4, skel_y 4, sums 4, gprob 4, ws 4. */
 int rsu_cldice_bwd(const float* prob, const int64_t* labels, const float* skel_p, const float* skel_y, const float* sums, int iters,
                    float scale, float smooth, float* gprob, float* ws, int B, int H, int W, rsu_stream_t stream);
 
@@ -52,6 +54,8 @@ int rsu_cldice_bwd(const float* prob, const int64_t* labels, const float* skel_p
  * allowed and gives the cross-entropy lines of rsu_head_fwd_bwd_w / rsu_head_fwd_bwd_dice; every other argument, the workspace
  * (rsu_head_dice_ws_floats) and every other error are rsu_head_fwd_bwd_focal's; a NULL gprob is RSU_EINVAL. With gprob all zero every
  * output equals that entry's as numbers. */
+/* align (rsu_head_fwd_bwd_aux): act 16, w 4, b 4, labels 8, class_w 4, pixel_w 4, dice_sums 4, prob 4, loss_sum 4, weight_sum 4, dact 16, dw 4,
+ * db 4, ws 4, gprob 4. */
 int rsu_head_fwd_bwd_aux(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w /* may be NULL */,
                          const float* pixel_w /* may be NULL */, float gamma, const float* dice_sums /* may be NULL */, float dice_scale,
                          float smooth, float* prob, float* loss_sum, float* weight_sum /* may be NULL */, void* dact, float* dw, float* db,

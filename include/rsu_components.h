@@ -46,6 +46,7 @@ size_t rsu_components_ws_bytes(int N, int H, int W);   /* 0 for refused sizes */
  * labels int32 [N][H][W] as defined above. area int32 [N][H][W] (may be NULL): at every labelled pixel the pixel count of its component,
  * 0 elsewhere. edge uint8 [N][H][W] (may be NULL): 1 at every labelled pixel whose component has a pixel in row 0, row H - 1, column 0 or
  * column W - 1, 0 elsewhere. Launches: 2 + M, and one more when area or edge is given. Nothing is written outside labels, area, edge, ws. */
+/* align (rsu_components_label): prob 4, labels 4, area 4, edge byte, ws 4. */
 int rsu_components_label(const float* prob, float threshold, int connectivity, int invert, int32_t* labels, int32_t* area, uint8_t* edge,
                          void* ws, int N, int H, int W, rsu_stream_t stream);
 
@@ -59,6 +60,7 @@ int rsu_components_label(const float* prob, float threshold, int connectivity, i
  *   4. stats int64 [N][6] (may be NULL), written, not accumulated: {components of F0, components removed, pixels removed, holes, holes
  *      filled, pixels filled} of image n. A skipped labelling writes its three fields as 0.
  * Launches: (2 + M) * (labellings not skipped) + 1. Nothing is written outside out, stats and ws. */
+/* align (rsu_components_filter): prob 4, out 4, stats 8, ws 4. */
 int rsu_components_filter(const float* prob, float threshold, int connectivity, int min_area, int max_hole, float* out, int64_t* stats,
                           void* ws, int N, int H, int W, rsu_stream_t stream);
 
@@ -68,6 +70,7 @@ int rsu_components_filter(const float* prob, float threshold, int connectivity, 
  * zeroes them): acc[0] += sum cp, acc[1] += sum cy, acc[2] += sum |cp - cy|, acc[3] += the images with at least one counted pixel. An
  * image without a counted pixel (the padding of an evaluation chunk: labels -1) adds exactly nothing. Both masks of every image are
  * labelled by the same launches: 3 + M in all. Nothing is written outside acc[0..3] and ws. */
+/* align (rsu_components_pair_count): prob 4, labels64 8, acc 8, ws 4. */
 int rsu_components_pair_count(const float* prob, float threshold, const int64_t* labels64, int connectivity, unsigned long long* acc, void* ws,
                               int N, int H, int W, rsu_stream_t stream);
 

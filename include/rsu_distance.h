@@ -48,6 +48,7 @@ size_t rsu_distance_ws_bytes(int N, int H, int W);          /* 0 for refused siz
 /* exact squared distances. d2_pred[q] = D2_P(q), d2_true[q] = D2_T(q), int32 [N][H][W], at EVERY pixel (ignored ones included).
  * Either output may be NULL, not both. labels64 may be NULL iff d2_true is NULL: every pixel is then counted.
  * Nothing is written outside d2_pred, d2_true and ws. */
+/* align (rsu_mask_distance): prob 4, labels64 8, d2_pred 4, d2_true 4, ws 4. */
 int rsu_mask_distance(const float* prob, float threshold, const int64_t* labels64, int32_t* d2_pred, int32_t* d2_true,
                       void* ws, int N, int H, int W, rsu_stream_t stream);
 
@@ -57,6 +58,7 @@ int rsu_mask_distance(const float* prob, float threshold, const int64_t* labels6
  * An image without a counted pixel (the padding of an evaluation chunk: labels -1) has P and T empty and adds exactly nothing. The row
  * scan stops at d = RSU_DIST_BINS - 2: nothing past the last bin is needed, which bounds its cost whatever the data.
  * Nothing is written outside acc[0 .. 2 * RSU_DIST_BINS - 1] and ws. */
+/* align (rsu_distance_hist): prob 4, labels64 8, acc 8, ws 4. */
 int rsu_distance_hist(const float* prob, float threshold, const int64_t* labels64, unsigned long long* acc,
                       void* ws, int N, int H, int W, rsu_stream_t stream);
 

@@ -81,6 +81,7 @@ size_t rsu_graph_ws_bytes(int N, int H, int W, int min_branch);      /* 0 for re
  *        acc[0 .. 3] += {|B|, ends, isolated pixels, junction pixels} of P,   acc[4 .. 7] += the same of T,
  *      with one integer atomic add per non-zero counter per workgroup. An image without a counted pixel adds exactly nothing.
  * Nothing is written outside the four outputs, acc[0 .. 7] and ws. */
+/* align (rsu_skeleton_graph): prob 4, labels64 8, out_pred 4, out_true 8, junc_pred 4, junc_true 8, acc 8, ws 8. */
 int rsu_skeleton_graph(const float* prob, float threshold, const int64_t* labels64, int min_branch, float* out_pred, int64_t* out_true,
                        float* junc_pred, int64_t* junc_true, unsigned long long* acc, void* ws, int N, int H, int W, rsu_stream_t stream);
 

@@ -45,10 +45,13 @@ extern "C" {
  * the corresponding entry of rsu.h refuses (a NULL among act, w, b, labels, prob, loss_sum / sums, hist, dact, dw, db, ws; a C that is
  * not 8 * 2^k in [8, 512]; npix < 1; with dice_sums != NULL a smooth that is not finite and > 0 or a dice_scale that is not finite
  * and >= 0). */
+/* align (rsu_head_fwd_bwd_focal): act 16, w 4, b 4, labels 8, class_w 4, pixel_w 4, dice_sums 4, prob 4, loss_sum 4, weight_sum 4, dact 16, dw 4,
+ * db 4, ws 4. */
 int rsu_head_fwd_bwd_focal(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w /* may be NULL */,
                            const float* pixel_w /* may be NULL */, float gamma, const float* dice_sums /* may be NULL */, float dice_scale,
                            float smooth, float* prob, float* loss_sum, float* weight_sum /* may be NULL */, void* dact, float* dw, float* db,
                            float* ws, long npix, int C, float inv_count, rsu_stream_t stream);
+/* align (rsu_head_eval_focal): act 16, w 4, b 4, labels 8, class_w 4, pixel_w 4, prob 4, sums 4, hist 8, ws 4. */
 int rsu_head_eval_focal(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w /* may be NULL */,
                         const float* pixel_w /* may be NULL */, float gamma, float* prob, float* sums, unsigned long long* hist, float* ws,
                         long npix, int C, rsu_stream_t stream);

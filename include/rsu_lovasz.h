@@ -48,7 +48,9 @@ extern "C" {
  * No host synchronisation; nothing is written outside gprob, loss_sum[0..1] and ws. Errors, returned before anything is launched or
  * written: RSU_EINVAL for a NULL pointer, B, H, W < 1, H * W > 2^24, B * H * W >= 2^31, a scale that is not finite and >= 0. */
 size_t rsu_lovasz_ws_bytes(int B, int H, int W);   /* 0 for refused arguments */
+/* align (rsu_lovasz_fwd): prob 4, labels 8, loss_sum 4, ws 8. */
 int rsu_lovasz_fwd(const float* prob, const int64_t* labels, float* loss_sum, void* ws, int B, int H, int W, rsu_stream_t stream);
+/* align (rsu_lovasz_fwd_bwd): prob 4, labels 8, gprob 4, loss_sum 4, ws 8. */
 int rsu_lovasz_fwd_bwd(const float* prob, const int64_t* labels, float scale, int accumulate, float* gprob, float* loss_sum, void* ws, int B,
                        int H, int W, rsu_stream_t stream);
 

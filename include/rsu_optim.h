@@ -37,8 +37,10 @@ extern "C" {
  * mode other than the two constants, a clip_state that is not 4-byte aligned. */
 #define RSU_DECAY_L2 0
 #define RSU_DECAY_DECOUPLED 1
+/* align (rsu_update_table_run_decay): dev_table 8, clip_state 4. */
 int rsu_update_table_run_decay(const void* dev_table, int nentries, int total_blocks, float lr, float mu, float gscale, float decay,
                                int mode, const void* clip_state /* may be NULL */, rsu_stream_t stream);
+/* align (rsu_update_table_run_adam_decay): dev_table 8, clip_state 4. */
 int rsu_update_table_run_adam_decay(const void* dev_table, int nentries, int total_blocks, float alpha, float beta1, float beta2,
                                     float epsilon, float gscale, float decay, int mode, const void* clip_state /* may be NULL */,
                                     rsu_stream_t stream);

@@ -105,6 +105,8 @@ size_t rsu_segments_ws_bytes(int N, int H, int W, int max_edges);   /* 0 for ref
  * RSU_E2BIG: labels64 (N H W 8 bytes) or the entry's largest internal array (16 N H W bytes, the four int32 planes) reaches 0x7ffffff0.
  *      Without labels64 the second rule alone holds. At 1024 x 1024 the last admitted batch is 127 images, and 128 is refused.
  * An argument error is reported before the size. Nothing is written outside the outputs, acc[0 .. 15] and ws. */
+/* align (rsu_line_segments): prob 4, labels64 8, edges_pred 4, edges_true 4, counts 4, seg_pred 4, seg_true 4, node_pred 4, node_true 4, acc 8,
+ * ws 8. */
 int rsu_line_segments(const float* prob, float threshold, const int64_t* labels64, int max_edges, int32_t* edges_pred, int32_t* edges_true,
                       int32_t* counts, int32_t* seg_pred, int32_t* seg_true, int32_t* node_pred, int32_t* node_true, unsigned long long* acc,
                       void* ws, int N, int H, int W, rsu_stream_t stream);

@@ -61,6 +61,7 @@ size_t rsu_thin_ws_bytes(int N, int H, int W, int max_iters);   /* 0 for refused
  * info: may be NULL; otherwise uint32 [N][2], WRITTEN: per image, for P ([n][0]) and T ([n][1]), the number of pixels the LAST executed
  *       iteration deleted. 0: converged within max_iters. Without labels64 [n][1] is 0.
  * Nothing is written outside skel_pred, skel_true, acc[0 .. 3], info and ws. */
+/* align (rsu_mask_thin): prob 4, labels64 8, skel_pred 4, skel_true 8, acc 8, info 4, ws 8. */
 int rsu_mask_thin(const float* prob, float threshold, const int64_t* labels64, int max_iters, float* skel_pred, int64_t* skel_true,
                   unsigned long long* acc, uint32_t* info, void* ws, int N, int H, int W, rsu_stream_t stream);
 

@@ -56,6 +56,11 @@ static const void* zero_page() {
     return ptr[dev];
 }
 
+// The "align:" notes of the public headers: an entry returns RSU_EINVAL, before anything is launched or written, for a non-NULL pointer that is
+// no multiple of the bytes its note states (NULL keeps whatever meaning it has at the entry). misaligned(a, p, q, ...): one of p, q, ... is not
+// a multiple of a (a power of two); tests/align_util.py holds the same numbers, tests/test_align_limits_host.py holds every entry to them.
+template <typename... P>
+static inline bool misaligned(uintptr_t a, P... p) { return ((... | (uintptr_t)p) & (a - 1)) != 0; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int rup(int a, int b) { return cdiv(a, b) * b; }
 static inline unsigned magic32(int d) { return (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }
@@ -213,6 +218,7 @@ static int make_pack(PackParams& pp, int ntap, int rows, const int* seg_c, int n
 static int do_pack(const float* src, void* dst, int ntap, int rows, const int* seg_c, int nseg, long s_tap, long s_row, long s_k,
                    int flip, hipStream_t st) {
     if (!src || !dst || nseg < 1 || nseg > 3) return RSU_EINVAL;
+    if (misaligned(4, src) || misaligned(2, dst)) return RSU_EINVAL;   // (k_pack: scalar f32 loads, bf16 stores one by one)
     PackParams pp;
     pp.nchunks = kpad_total(seg_c, nseg) / 32;
     pp.ntap = ntap;
@@ -264,6 +270,7 @@ extern "C" size_t rsu_pack_table_entry_bytes(void) { return sizeof(PackJob); }
 extern "C" int rsu_pack_table_add(void* host_table, int index, int kind, const float* w, void* packed, int k, int Cin_total, int ci_off,
                                   int ci_cnt, int Cout, const int* seg_c, int nseg) {
     if (!host_table || !w || !packed || index < 0) return RSU_EINVAL;
+    if (misaligned(4, w) || misaligned(16, packed)) return RSU_EINVAL;   // (k_pack_many stores 16-byte groups)
     PackJob* t = (PackJob*)host_table + index;
     int one[1];
     int rc = RSU_EINVAL, used = 1;
@@ -316,7 +323,7 @@ extern "C" int rsu_pack_table_finish(void* host_table, int nentries, int* total_
     return RSU_OK;
 }
 extern "C" int rsu_pack_table_run(const void* dev_table, int nentries, int total_blocks, rsu_stream_t stream) {
-    if (!dev_table || nentries < 1 || total_blocks < 1) return RSU_EINVAL;
+    if (!dev_table || nentries < 1 || total_blocks < 1 || misaligned(8, dev_table)) return RSU_EINVAL;
     HIP_CHECK_RET(ew_pack_many((const PackJob*)dev_table, nentries, total_blocks, (hipStream_t)stream));
     return RSU_OK;
 }
@@ -335,6 +342,11 @@ extern "C" int rsu_update_table_add(void* host_table, int index, int kind, float
                                     void* const* packed_bwd, int Cin_total, int Cout, const int* seg_c, int nseg) {
     if (!host_table || index < 0 || !w || !acc || !g || !packed_fwd || Cout % 8 || Cout < 8) return RSU_EINVAL;
     if (((uintptr_t)w | (uintptr_t)acc | (uintptr_t)g) & 15) return RSU_EINVAL;
+    if (misaligned(16, packed_fwd)) return RSU_EINVAL;   // (the pass stores 16-byte pieces of both packed layouts)
+    // (the backward-data packs the kind reads: packed_bwd[0..nseg) of a conv kernel, packed_bwd[0] of a transposed conv's, none otherwise)
+    const int nbwd = !packed_bwd ? 0 : kind == RSU_PACK_CONV_FWD ? (seg_c ? (nseg < 3 ? nseg : 3) : 1) : kind == RSU_PACK_CONVT_FWD ? 1 : 0;
+    for (int i = 0; i < nbwd; ++i)
+        if (misaligned(16, packed_bwd[i])) return RSU_EINVAL;
     UpJob* t = (UpJob*)host_table + index;
     memset(t, 0, sizeof(UpJob));
     t->w = w; t->acc = acc; t->g = g; t->kind = 1;
@@ -418,7 +430,7 @@ extern "C" int rsu_update_table_finish(void* host_table, int nentries, int* tota
 // the six rsu_update_table_run* entries: each checks what its rule adds and launches the pass with that rule through update_table_run
 template <typename Rule>
 static int update_table_run(const void* dev_table, int nentries, int total_blocks, const Rule& h, rsu_stream_t stream) {
-    if (!dev_table || nentries < 1 || total_blocks < 1) return RSU_EINVAL;
+    if (!dev_table || nentries < 1 || total_blocks < 1 || misaligned(8, dev_table)) return RSU_EINVAL;
     HIP_CHECK_RET(ew_update_pack_many((const UpJob*)dev_table, nentries, total_blocks, h, (hipStream_t)stream));
     return RSU_OK;
 }
@@ -514,12 +526,13 @@ static bool too_big(long bytes) { return bytes >= 0x7ffffff0L; }
 extern "C" int rsu_color_adjust_fwd(const float* x, const float* w, const float* b, void* out16, long npix, float keep, unsigned key,
                                     rsu_stream_t stream) {
     if (!x || !w || !b || !out16 || npix < 1 || !keep_ok(keep)) return RSU_EINVAL;
+    if (misaligned(4, x, w, b) || misaligned(16, out16)) return RSU_EINVAL;
     if (too_big(npix * 32)) return RSU_E2BIG;   // out16, the larger tensor (the dropout counter 3 * npix + c then stays below 2^28)
     HIP_CHECK_RET(ew_color_adjust(x, w, b, out16, npix, keep, key, (hipStream_t)stream));
     return RSU_OK;
 }
 extern "C" int rsu_dropout_fwd(const void* x, void* y, long n, float keep, unsigned key, rsu_stream_t stream) {
-    if (!x || !y || n < 8 || n % 8 || !keep_ok(keep)) return RSU_EINVAL;
+    if (!x || !y || n < 8 || n % 8 || !keep_ok(keep) || misaligned(16, x, y)) return RSU_EINVAL;
     if (too_big(n * 2)) return RSU_E2BIG;   // (the dropout counter, the element index, then stays below 2^30)
     HIP_CHECK_RET(ew_dropout(x, y, n, keep, key, (hipStream_t)stream));
     return RSU_OK;
@@ -687,6 +700,11 @@ static int run_fwd(const rsu_src_t* srcs, int nsrc, const void* wp, long wp_y_st
     const bool pool = pool_out != nullptr;
     const int ncu = launch_ncu(ncu_arg);
     if (ncu < 0) return RSU_EINVAL;
+    // 16-byte pieces of every bf16 tensor and of the packed weights (LDS-DMA loads, 128-bit buffer loads and stores), 16-byte stores of the
+    // split-K partial sums, 8 code bytes per store; the bias is read float by float
+    if (misaligned(16, wp, out, mask_src, pool_out, kws) || misaligned(8, pool_code) || misaligned(4, bias)) return RSU_EINVAL;
+    for (int i = 0; i < nsrc; ++i)
+        if (misaligned(16, srcs[i].ptr)) return RSU_EINVAL;
     const long out_bytes = (long)N * oH * oW * outC * 2;
     const int gen = env_int("RSU_FWD_GEN", 3);
     // the kernels address every tensor through 32-bit byte offsets of a buffer descriptor: a tensor must stay below 2 GiB (split
@@ -886,6 +904,9 @@ extern "C" int rsu_conv2d_fwd_pool_k(const rsu_src_t* srcs, int nsrc, const void
     const int Ho = Hin - 2, Wo = Win - 2;
     if (Ho < 2 || Wo < 2) return RSU_EINVAL;
     if (code && ((Ho | Wo) & 1)) return RSU_EINVAL;   // (the code bytes describe whole 2x2 windows: refused before anything is launched)
+    if (misaligned(16, packed_fwd, y, pooled, kws) || misaligned(8, code) || misaligned(4, bias)) return RSU_EINVAL;   // (as run_fwd: the two-launch form must refuse before its first launch)
+    for (int i = 0; i < nsrc; ++i)
+        if (misaligned(16, srcs[i].ptr)) return RSU_EINVAL;
     const bool even = ((Ho | Wo) & 1) == 0;   // the folded epilogue pools whole 2x2 windows; odd sizes take the two launches (floor semantics, no code bytes)
     // the pool folds into the conv's epilogue where a ping-pong tile shape with whole window rows per wave fits the layer and no dropout
     // follows (its mask is a function of the pooled element index: the separate kernel applies it); otherwise: the two launches
@@ -925,6 +946,7 @@ extern "C" int rsu_pack_conv_first(const float* w, void* packed, int Cout, rsu_s
 extern "C" int rsu_conv_first_fwd(const void* in16, const void* packed, const float* b, void* y, int N, int H, int W, int Cout, int dil,
                                   int ncu, rsu_stream_t stream) {
     if (!in16 || !packed || !y || Cout % 8 || H <= 2 * dil || W <= 2 * dil + 1 || (dil != 1 && dil != 2)) return RSU_EINVAL;
+    if (misaligned(16, in16, packed, y) || misaligned(4, b)) return RSU_EINVAL;
     rsu_src_t s;
     s.ptr = in16; s.H = H; s.W = W; s.C = 16; s.oy = 0; s.ox = 0;
     const int Ho = H - 2 * dil, Wo = W - 2 * dil;
@@ -942,6 +964,7 @@ extern "C" int rsu_conv_first_fwd(const void* in16, const void* packed, const fl
 extern "C" int rsu_color_conv_first_fwd(const float* x, const float* w0, const float* b0, const void* packed, const float* b, void* y, int N, int H,
                                         int W, int Cout, int dil, int ncu, rsu_stream_t stream) {
     if (!x || !w0 || !b0 || !packed || !y || Cout % 8 || H <= 2 * dil || W <= 2 * dil + 1 || (dil != 1 && dil != 2)) return RSU_EINVAL;
+    if (misaligned(16, packed, y) || misaligned(4, x, w0, b0, b)) return RSU_EINVAL;   // (x: 12-byte pixels, read as three dwords)
     const int Ho = H - 2 * dil, Wo = W - 2 * dil;
     const int n = launch_ncu(ncu);
     if (n < 0) return RSU_EINVAL;
@@ -974,6 +997,7 @@ static int run_ct(int mode, const void* a, int Ca, int N, int H, int W, const vo
                   void* out, int outC, int Cn, const void* mask_src, int ncu_arg, hipStream_t st) {
     const int ncu = launch_ncu(ncu_arg);
     if (ncu < 0) return RSU_EINVAL;
+    if (misaligned(16, a, wp, out, mask_src) || misaligned(4, bias)) return RSU_EINVAL;
     IgCtParams p;
     memset(&p, 0, sizeof(p));
     p.a = (const bf16_t*)a;
@@ -1089,6 +1113,8 @@ static int prep_wgrad(WgPrep& w, int cfg, const void* F, int Hf, int Wf, int Cf,
                       int cs_off, int N, int ntap, int kw, int dil, int stride, int ncu, float* db, float* dbs) {
     // 32-bit byte offsets inside the kernel: both operand tensors must stay below 2 GiB (beyond that the offsets wrapped
     // silently and only the weight gradients came out wrong)
+    // 16-byte pieces of both bf16 operands; the gradient, the bias sums and the slabs are stored and reduced as float4
+    if (misaligned(16, F, S->ptr, out, db, dbs)) return RSU_EINVAL;
     if ((long)N * Hf * Wf * Cf * 2 >= 0x7ffffff0L || (long)N * S->H * S->W * S->C * 2 >= 0x7ffffff0L) return RSU_E2BIG;
     WgPlan pl;
     const int wide = wgrad_pick_cfg(cfg, Cf);
@@ -1163,6 +1189,7 @@ extern "C" int rsu_conv2d_bwd_weight(const rsu_src_t* src, const void* dz, float
     if (!src || !src->ptr || !dz || !dw || !ws || src->C % 8 || Cout % 8 || ci_off + src->C > Cin_total || (dil != 1 && dil != 2))
         return RSU_EINVAL;
     if (src->oy < 0 || src->ox < 0 || src->oy + Ho + 2 * dil > src->H || src->ox + Wo + 2 * dil > src->W || Wo < 2) return RSU_EINVAL;
+    if (misaligned(16, ws)) return RSU_EINVAL;   // (src->ptr, dz, dw, db: prep_wgrad)
     // F = dz (cf = co), S = layer input (cs = ci): slab[tap][ci][co] = HWIO
     return run_wgrad(IGW_CFG_64x64, dz, Ho, Wo, Cout, src, dw, ws, Cin_total, Cout, ci_off, N, 9, 3, dil, 1, ncu, (hipStream_t)stream, db);
 }
@@ -1178,6 +1205,7 @@ extern "C" size_t rsu_convT2x2_bwd_weight_ws_floats(int Cin, int Cout) {
 extern "C" int rsu_convT2x2_bwd_weight(const void* x, const void* dy, float* dK, float* db, float* ws, int N, int H, int W, int Cin,
                                        int Cout, int ncu, rsu_stream_t stream) {
     if (!x || !dy || !dK || !ws || Cin % 8 || Cout % 8 || W < 2) return RSU_EINVAL;
+    if (misaligned(16, x, dy, dK, db, ws)) return RSU_EINVAL;
     // RSU_WGT_GEN=1: the generic igemm_wgrad launch (4 taps, stride 2) of rounds 1-3a; 3 (default since round 6): the ping-pong kernel of
     // igemm_wgt.hip at every CU budget; 2 (rounds 3-5): the ping-pong kernel only where the launch has (most of) the chip to itself. In round 3
     // the faster kernel beside a backward-data kernel made the STEP slower (945 -> 938 patches/s, profiles/r03/lib_ab_wgt.txt); with round 4's
@@ -1208,6 +1236,7 @@ extern "C" size_t rsu_conv_first_bwd_ws_floats(int Cout) {
 extern "C" int rsu_conv_first_bwd_weight(const void* in16, const void* dz, float* dw1, float* gxc, float* db, float* ws, int N, int H, int W,
                                          int Cout, int dil, int ncu, rsu_stream_t stream) {
     if (!in16 || !dz || !dw1 || !ws || Cout % 8 || (dil != 1 && dil != 2) || W - 2 * dil < 2) return RSU_EINVAL;
+    if (misaligned(16, in16, dz, db, ws) || misaligned(4, dw1, gxc)) return RSU_EINVAL;   // (dw1, gx: the scatter kernel stores float by float)
     rsu_src_t s;
     s.ptr = in16; s.H = H; s.W = W; s.C = 16; s.oy = 0; s.ox = 0;
     float* tmp = ws;                          // [9][16][Cout]
@@ -1282,6 +1311,7 @@ static double wg_family_cost(int family) {
 }
 extern "C" int rsu_wgrad_group_plan(const rsu_wgrad_job_t* jobs, int njobs, float* ws, int N, int ncu_arg, void* host_table) {
     if (!jobs || njobs < 1 || njobs > IGW_GROUP_MAX || !ws || !host_table || N < 1) return RSU_EINVAL;
+    if (misaligned(16, ws)) return RSU_EINVAL;   // (the pointers of the jobs: prep_wgrad)
     const int ncu = launch_ncu(ncu_arg);
     if (ncu < 0) return RSU_EINVAL;
     WgGroupTable& T = *(WgGroupTable*)host_table;
@@ -1436,7 +1466,7 @@ extern "C" int rsu_wgrad_group_plan(const rsu_wgrad_job_t* jobs, int njobs, floa
     return RSU_OK;
 }
 extern "C" int rsu_wgrad_group_run(const void* host_table, const void* dev_table, rsu_stream_t stream) {
-    if (!host_table || !dev_table) return RSU_EINVAL;
+    if (!host_table || !dev_table || misaligned(8, dev_table)) return RSU_EINVAL;
     const WgGroupTable& T = *(const WgGroupTable*)host_table;
     if (T.magic != WG_TABLE_MAGIC) return RSU_EINVAL;
     hipStream_t st = (hipStream_t)stream;
@@ -1460,6 +1490,7 @@ extern "C" int rsu_wgrad_group_run(const void* host_table, const void* dev_table
 extern "C" size_t rsu_bias_grad_ws_floats(long npix, int C) { return (size_t)ew_colsum_blocks(npix, C) * C; }
 extern "C" int rsu_bias_grad(const void* dz, float* db, float* ws, long npix, int C, rsu_stream_t stream) {
     if (!dz || !db || !ws || C < 8 || C % 8 || C > 2048 || 256 % (C / 8) || npix < 1) return RSU_EINVAL;
+    if (misaligned(16, dz) || misaligned(4, db, ws)) return RSU_EINVAL;
     if (too_big(npix * C * 2)) return RSU_E2BIG;
     HIP_CHECK_RET(ew_colsum(dz, db, ws, npix, C, (hipStream_t)stream));
     return RSU_OK;
@@ -1472,6 +1503,7 @@ extern "C" int rsu_maxpool2x2_fwd_code(const void* x, void* y, void* code, int N
                                        rsu_stream_t stream) {
     if (!x || !y || C % 8 || H < 2 || W < 2 || !keep_ok(keep)) return RSU_EINVAL;
     if (code && ((H | W) & 1)) return RSU_EINVAL;
+    if (misaligned(16, x, y) || misaligned(8, code)) return RSU_EINVAL;   // (8 code bytes per store)
     if (N >= 1 && too_big((long)N * H * W * C * 2)) return RSU_E2BIG;   // x, the largest tensor (the dropout counter, a pooled element index, stays below 2^28)
     HIP_CHECK_RET(ew_maxpool_fwd(x, y, code, N, H, W, C, keep, key, (hipStream_t)stream));
     return RSU_OK;
@@ -1484,6 +1516,7 @@ extern "C" int rsu_pool_skip_relu_bwd_code(const void* y_act, const void* code, 
     if ((!y_act && !code) || !dz || C % 8 || !keep_ok(keep)) return RSU_EINVAL;
     if (code && (((H | W) & 1) || H < 2 || W < 2)) return RSU_EINVAL;   // the code tensor describes whole 2x2 windows
     if (dskip && (Hs > H || Ws > W || Hs < 1 || Ws < 1)) return RSU_EINVAL;
+    if (misaligned(16, y_act, dpool, dskip, dz) || misaligned(8, code)) return RSU_EINVAL;
     // dz, the largest tensor: below the limit the int row count N * (H / 2) and pooled element index of k_pool_skip_relu_bwd_code and
     // the 32-bit dropout counter of both kernels stay below 2^28
     if (N >= 1 && H >= 1 && W >= 1 && C >= 8 && too_big((long)N * H * W * C * 2)) return RSU_E2BIG;
@@ -1498,6 +1531,11 @@ extern "C" int rsu_pool_skip_relu_bwd(const void* y_act, const void* dpool, cons
 static bool head_c_ok(int C) { return C >= 8 && C <= 512 && (C % 8) == 0 && ((C / 8) & (C / 8 - 1)) == 0; }
 // act (and dact) [npix][C] bf16: the largest tensor of every head call (C >= 8: 16 bytes per pixel against the 8 of labels or logits)
 static bool head_too_big(long npix, int C) { return too_big(npix * C * 2); }
+// the alignments of the head family: 16-byte pieces of act and dact, 64-bit labels, a 64-bit atomic per histogram bin; every other tensor
+// (weights, maps, sums, gradients, the workspace) is read and written float by float
+static bool head_misaligned(const void* act, const void* dact, const void* labels, const void* hist) {
+    return misaligned(16, act, dact) || misaligned(8, labels, hist);
+}
 // what rsu_head_fwd_bwd, _w and _dice all require
 static bool head_train_args_ok(const void* act, const float* w, const float* b, const int64_t* labels, const float* prob, const float* loss_sum,
                                const void* dact, const float* dw, const float* db, const float* ws, long npix, int C) {
@@ -1509,7 +1547,7 @@ static bool dice_args_ok(float dice_scale, float smooth) {
 }
 extern "C" int rsu_color_adjust_bwd(const float* gx, const float* w1, float* dW0, float* db0, int Cout, float scale, int accumulate,
                                     rsu_stream_t stream) {
-    if (!gx || !w1 || !dW0 || !db0 || Cout < 1 || !(scale > 0.f)) return RSU_EINVAL;
+    if (!gx || !w1 || !dW0 || !db0 || Cout < 1 || !(scale > 0.f) || misaligned(4, gx, w1, dW0, db0)) return RSU_EINVAL;
     HIP_CHECK_RET(ew_color_adjust_bwd(gx, w1, dW0, db0, Cout, scale, accumulate, (hipStream_t)stream));
     return RSU_OK;
 }
@@ -1517,6 +1555,7 @@ extern "C" int rsu_color_adjust_bwd(const float* gx, const float* w1, float* dW0
 extern "C" int rsu_head_fwd(const void* act, const float* w, const float* b, float* prob, float* logits, long npix, int C,
                             rsu_stream_t stream) {
     if (!act || !w || !b || !prob || !head_c_ok(C) || npix < 1) return RSU_EINVAL;
+    if (head_misaligned(act, nullptr, nullptr, nullptr) || misaligned(4, w, b, prob, logits)) return RSU_EINVAL;
     if (head_too_big(npix, C)) return RSU_E2BIG;
     HIP_CHECK_RET(ew_head(false, act, w, b, nullptr, prob, logits, nullptr, nullptr, nullptr, nullptr, nullptr, npix, C, 0.f, (hipStream_t)stream));
     return RSU_OK;
@@ -1525,6 +1564,7 @@ extern "C" size_t rsu_head_ws_floats(long npix, int C) { return (size_t)ew_head_
 extern "C" int rsu_head_fwd_bwd(const void* act, const float* w, const float* b, const int64_t* labels, float* prob, float* loss_sum,
                                 void* dact, float* dw, float* db, float* ws, long npix, int C, float inv_count, rsu_stream_t stream) {
     if (!head_train_args_ok(act, w, b, labels, prob, loss_sum, dact, dw, db, ws, npix, C)) return RSU_EINVAL;
+    if (head_misaligned(act, dact, labels, nullptr) || misaligned(4, w, b, prob, loss_sum, dw, db, ws)) return RSU_EINVAL;
     if (head_too_big(npix, C)) return RSU_E2BIG;
     HIP_CHECK_RET(ew_head(true, act, w, b, labels, prob, nullptr, dact, dw, db, loss_sum, ws, npix, C, inv_count, (hipStream_t)stream));
     return RSU_OK;
@@ -1534,6 +1574,7 @@ extern "C" int rsu_head_fwd_bwd_w(const void* act, const float* w, const float* 
                                   const float* pixel_w, float* prob, float* loss_sum, float* weight_sum, void* dact, float* dw, float* db,
                                   float* ws, long npix, int C, float inv_count, rsu_stream_t stream) {
     if (!head_train_args_ok(act, w, b, labels, prob, loss_sum, dact, dw, db, ws, npix, C)) return RSU_EINVAL;
+    if (head_misaligned(act, dact, labels, nullptr) || misaligned(4, w, b, class_w, pixel_w, prob, loss_sum, weight_sum, dw, db, ws)) return RSU_EINVAL;
     if (head_too_big(npix, C)) return RSU_E2BIG;
     HIP_CHECK_RET(hd_train(act, w, b, labels, class_w, pixel_w, 0.f, nullptr, 0.f, 0.f, nullptr, prob, dact, dw, db, loss_sum, weight_sum, ws, npix,
                            C, inv_count, (hipStream_t)stream));
@@ -1543,6 +1584,7 @@ extern "C" size_t rsu_head_dice_ws_floats(long npix, int C) { return (size_t)ew_
 extern "C" int rsu_head_dice_sums(const void* act, const float* w, const float* b, const int64_t* labels, const float* pixel_w, float* prob,
                                   float* dice_sums, float* ws, long npix, int C, rsu_stream_t stream) {
     if (!act || !w || !b || !labels || !prob || !dice_sums || !ws || !head_c_ok(C) || npix < 1) return RSU_EINVAL;
+    if (head_misaligned(act, nullptr, labels, nullptr) || misaligned(4, w, b, pixel_w, prob, dice_sums, ws)) return RSU_EINVAL;
     if (head_too_big(npix, C)) return RSU_E2BIG;
     HIP_CHECK_RET(ew_head_dice_sums(act, w, b, labels, pixel_w, prob, dice_sums, ws, npix, C, (hipStream_t)stream));
     return RSU_OK;
@@ -1552,6 +1594,8 @@ extern "C" int rsu_head_fwd_bwd_dice(const void* act, const float* w, const floa
                                      float* weight_sum, void* dact, float* dw, float* db, float* ws, long npix, int C, float inv_count,
                                      rsu_stream_t stream) {
     if (!head_train_args_ok(act, w, b, labels, prob, loss_sum, dact, dw, db, ws, npix, C)) return RSU_EINVAL;
+    if (head_misaligned(act, dact, labels, nullptr) || misaligned(4, w, b, class_w, pixel_w, dice_sums, prob, loss_sum, weight_sum, dw, db, ws))
+        return RSU_EINVAL;
     if (head_too_big(npix, C)) return RSU_E2BIG;
     if (!dice_sums || !dice_args_ok(dice_scale, smooth)) return RSU_EINVAL;
     HIP_CHECK_RET(hd_train(act, w, b, labels, class_w, pixel_w, 0.f, dice_sums, dice_scale, smooth, nullptr, prob, dact, dw, db, loss_sum, weight_sum,
@@ -1564,6 +1608,7 @@ extern "C" int rsu_head_eval(const void* act, const float* w, const float* b, co
                              const float* pixel_w, float* prob, float* sums, unsigned long long* hist, float* ws, long npix, int C,
                              rsu_stream_t stream) {
     if (!act || !w || !b || !labels || !prob || !sums || !hist || !ws || !head_c_ok(C) || npix < 1) return RSU_EINVAL;
+    if (head_misaligned(act, nullptr, labels, hist) || misaligned(4, w, b, class_w, pixel_w, prob, sums, ws)) return RSU_EINVAL;
     if (head_too_big(npix, C)) return RSU_E2BIG;
     HIP_CHECK_RET(hd_eval(act, w, b, labels, class_w, pixel_w, 0.f, prob, sums, hist, ws, npix, C, (hipStream_t)stream));
     return RSU_OK;
@@ -1576,6 +1621,8 @@ extern "C" int rsu_head_fwd_bwd_focal(const void* act, const float* w, const flo
                                       float* loss_sum, float* weight_sum, void* dact, float* dw, float* db, float* ws, long npix, int C,
                                       float inv_count, rsu_stream_t stream) {
     if (!focal_gamma_ok(gamma) || !head_train_args_ok(act, w, b, labels, prob, loss_sum, dact, dw, db, ws, npix, C)) return RSU_EINVAL;
+    if (head_misaligned(act, dact, labels, nullptr) || misaligned(4, w, b, class_w, pixel_w, dice_sums, prob, loss_sum, weight_sum, dw, db, ws))
+        return RSU_EINVAL;
     if (head_too_big(npix, C)) return RSU_E2BIG;
     if (dice_sums && !dice_args_ok(dice_scale, smooth)) return RSU_EINVAL;
     HIP_CHECK_RET(hd_train(act, w, b, labels, class_w, pixel_w, gamma, dice_sums, dice_scale, smooth, nullptr, prob, dact, dw, db, loss_sum,
@@ -1586,6 +1633,7 @@ extern "C" int rsu_head_eval_focal(const void* act, const float* w, const float*
                                    const float* pixel_w, float gamma, float* prob, float* sums, unsigned long long* hist, float* ws, long npix,
                                    int C, rsu_stream_t stream) {
     if (!focal_gamma_ok(gamma) || !act || !w || !b || !labels || !prob || !sums || !hist || !ws || !head_c_ok(C) || npix < 1) return RSU_EINVAL;
+    if (head_misaligned(act, nullptr, labels, hist) || misaligned(4, w, b, class_w, pixel_w, prob, sums, ws)) return RSU_EINVAL;
     if (head_too_big(npix, C)) return RSU_E2BIG;
     HIP_CHECK_RET(hd_eval(act, w, b, labels, class_w, pixel_w, gamma, prob, sums, hist, ws, npix, C, (hipStream_t)stream));
     return RSU_OK;
@@ -1599,12 +1647,14 @@ extern "C" size_t rsu_cldice_ws_floats(int B, int H, int W, int iters) { return 
 extern "C" int rsu_cldice_fwd(const float* prob, const int64_t* labels, int iters, float* skel_p, float* skel_y, float* sums, float* ws, int B,
                               int H, int W, rsu_stream_t stream) {
     if (!prob || !labels || !skel_p || !skel_y || !sums || !ws || !cldice_size_ok(B, H, W, iters)) return RSU_EINVAL;
+    if (misaligned(4, prob, skel_p, skel_y, sums, ws) || misaligned(8, labels)) return RSU_EINVAL;
     HIP_CHECK_RET(cl_fwd(prob, labels, iters, skel_p, skel_y, sums, ws, B, H, W, (hipStream_t)stream));
     return RSU_OK;
 }
 extern "C" int rsu_cldice_bwd(const float* prob, const int64_t* labels, const float* skel_p, const float* skel_y, const float* sums, int iters,
                               float scale, float smooth, float* gprob, float* ws, int B, int H, int W, rsu_stream_t stream) {
     if (!prob || !labels || !skel_p || !skel_y || !sums || !gprob || !ws || !cldice_size_ok(B, H, W, iters)) return RSU_EINVAL;
+    if (misaligned(4, prob, skel_p, skel_y, sums, gprob, ws) || misaligned(8, labels)) return RSU_EINVAL;
     if (!std::isfinite(smooth) || !(smooth > 0.f) || !std::isfinite(scale) || !(scale >= 0.f)) return RSU_EINVAL;
     HIP_CHECK_RET(cl_bwd(prob, labels, skel_y, sums, iters, scale, smooth, gprob, ws, B, H, W, (hipStream_t)stream));
     return RSU_OK;
@@ -1614,6 +1664,8 @@ extern "C" int rsu_head_fwd_bwd_aux(const void* act, const float* w, const float
                                     float* loss_sum, float* weight_sum, void* dact, float* dw, float* db, float* ws, long npix, int C,
                                     float inv_count, const float* gprob, rsu_stream_t stream) {
     if (!gprob || !focal_gamma_ok(gamma) || !head_train_args_ok(act, w, b, labels, prob, loss_sum, dact, dw, db, ws, npix, C)) return RSU_EINVAL;
+    if (head_misaligned(act, dact, labels, nullptr) || misaligned(4, w, b, class_w, pixel_w, dice_sums, prob, loss_sum, weight_sum, dw, db, ws, gprob))
+        return RSU_EINVAL;
     if (head_too_big(npix, C)) return RSU_E2BIG;
     if (dice_sums && !dice_args_ok(dice_scale, smooth)) return RSU_EINVAL;
     HIP_CHECK_RET(hd_train(act, w, b, labels, class_w, pixel_w, gamma, dice_sums, dice_scale, smooth, gprob, prob, dact, dw, db, loss_sum, weight_sum,
@@ -1627,12 +1679,14 @@ static bool lovasz_size_ok(int B, int H, int W) {
 extern "C" size_t rsu_lovasz_ws_bytes(int B, int H, int W) { return lovasz_size_ok(B, H, W) ? lv_ws_bytes(B, H, W) : 0; }
 extern "C" int rsu_lovasz_fwd(const float* prob, const int64_t* labels, float* loss_sum, void* ws, int B, int H, int W, rsu_stream_t stream) {
     if (!prob || !labels || !loss_sum || !ws || !lovasz_size_ok(B, H, W)) return RSU_EINVAL;
+    if (misaligned(4, prob, loss_sum) || misaligned(8, labels, ws)) return RSU_EINVAL;   // (ws: the 64-bit sort keys come first)
     HIP_CHECK_RET(lv_run(prob, labels, 0.f, 0, nullptr, loss_sum, ws, B, H, W, (hipStream_t)stream));
     return RSU_OK;
 }
 extern "C" int rsu_lovasz_fwd_bwd(const float* prob, const int64_t* labels, float scale, int accumulate, float* gprob, float* loss_sum, void* ws,
                                   int B, int H, int W, rsu_stream_t stream) {
     if (!prob || !labels || !gprob || !loss_sum || !ws || !lovasz_size_ok(B, H, W)) return RSU_EINVAL;
+    if (misaligned(4, prob, gprob, loss_sum) || misaligned(8, labels, ws)) return RSU_EINVAL;
     if (!std::isfinite(scale) || !(scale >= 0.f)) return RSU_EINVAL;
     HIP_CHECK_RET(lv_run(prob, labels, scale / (float)B, accumulate, gprob, loss_sum, ws, B, H, W, (hipStream_t)stream));
     return RSU_OK;
@@ -1646,6 +1700,7 @@ extern "C" size_t rsu_components_ws_bytes(int N, int H, int W) { return componen
 extern "C" int rsu_components_label(const float* prob, float threshold, int connectivity, int invert, int32_t* labels, int32_t* area,
                                     uint8_t* edge, void* ws, int N, int H, int W, rsu_stream_t stream) {
     if (!prob || !labels || !ws || !components_size_ok(N, H, W) || !components_args_ok(threshold, connectivity)) return RSU_EINVAL;
+    if (misaligned(4, prob, labels, area, ws)) return RSU_EINVAL;   // (edge: bytes)
     HIP_CHECK_RET(cc_label(prob, threshold, connectivity, invert, labels, area, edge, ws, N, H, W, (hipStream_t)stream));
     return RSU_OK;
 }
@@ -1653,12 +1708,14 @@ extern "C" int rsu_components_filter(const float* prob, float threshold, int con
                                      int64_t* stats, void* ws, int N, int H, int W, rsu_stream_t stream) {
     if (!prob || !out || !ws || !components_size_ok(N, H, W) || !components_args_ok(threshold, connectivity)) return RSU_EINVAL;
     if (min_area < 0 || max_hole < 0) return RSU_EINVAL;
+    if (misaligned(4, prob, out, ws) || misaligned(8, stats)) return RSU_EINVAL;   // (stats: 64-bit atomics)
     HIP_CHECK_RET(cc_filter(prob, threshold, connectivity, min_area, max_hole, out, stats, ws, N, H, W, (hipStream_t)stream));
     return RSU_OK;
 }
 extern "C" int rsu_components_pair_count(const float* prob, float threshold, const int64_t* labels64, int connectivity,
                                          unsigned long long* acc, void* ws, int N, int H, int W, rsu_stream_t stream) {
     if (!prob || !labels64 || !acc || !ws || !components_size_ok(N, H, W) || !components_args_ok(threshold, connectivity)) return RSU_EINVAL;
+    if (misaligned(4, prob, ws) || misaligned(8, labels64, acc)) return RSU_EINVAL;
     HIP_CHECK_RET(cc_pair_count(prob, threshold, labels64, connectivity, acc, ws, N, H, W, (hipStream_t)stream));
     return RSU_OK;
 }
@@ -1673,6 +1730,7 @@ extern "C" int rsu_mask_distance(const float* prob, float threshold, const int64
                                  int N, int H, int W, rsu_stream_t stream) {
     if (!prob || !ws || (!d2_pred && !d2_true) || (d2_true && !labels64) || !distance_size_ok(N, H, W) || !std::isfinite(threshold))
         return RSU_EINVAL;
+    if (misaligned(4, prob, d2_pred, d2_true, ws) || misaligned(8, labels64)) return RSU_EINVAL;
     if (distance_too_big(N, H, W, labels64 ? 8 : 4)) return RSU_E2BIG;
     HIP_CHECK_RET(dt_mask_distance(prob, threshold, labels64, d2_pred, d2_true, ws, N, H, W, (hipStream_t)stream));
     return RSU_OK;
@@ -1680,6 +1738,7 @@ extern "C" int rsu_mask_distance(const float* prob, float threshold, const int64
 extern "C" int rsu_distance_hist(const float* prob, float threshold, const int64_t* labels64, unsigned long long* acc, void* ws, int N, int H,
                                  int W, rsu_stream_t stream) {
     if (!prob || !labels64 || !acc || !ws || !distance_size_ok(N, H, W) || !std::isfinite(threshold)) return RSU_EINVAL;
+    if (misaligned(4, prob, ws) || misaligned(8, labels64, acc)) return RSU_EINVAL;   // (acc: 64-bit atomics)
     if (distance_too_big(N, H, W, 8)) return RSU_E2BIG;
     HIP_CHECK_RET(dt_distance_hist(prob, threshold, labels64, acc, ws, N, H, W, (hipStream_t)stream));
     return RSU_OK;
@@ -1698,6 +1757,8 @@ extern "C" int rsu_mask_thin(const float* prob, float threshold, const int64_t* 
     if (!prob || !ws || (!skel_pred && !skel_true) || (skel_true && !labels64) || (acc && !(skel_pred && skel_true)) ||
         !thin_size_ok(N, H, W, max_iters) || !std::isfinite(threshold))
         return RSU_EINVAL;
+    // (ws: 64-bit plane words first; acc: 64-bit atomics; skel_true: 64-bit stores)
+    if (misaligned(4, prob, skel_pred, info) || misaligned(8, labels64, skel_true, acc, ws)) return RSU_EINVAL;
     if (thin_too_big(N, H, W, labels64 ? 8 : 4)) return RSU_E2BIG;
     HIP_CHECK_RET(th_mask_thin(prob, threshold, labels64, max_iters, skel_pred, skel_true, acc, info, ws, N, H, W, (hipStream_t)stream));
     return RSU_OK;
@@ -1717,6 +1778,7 @@ extern "C" int rsu_skeleton_graph(const float* prob, float threshold, const int6
     if (!prob || !ws || (!out_pred && !out_true && !junc_pred && !junc_true) || ((out_true || junc_true) && !labels64) ||
         !graph_size_ok(N, H, W, min_branch) || !std::isfinite(threshold))
         return RSU_EINVAL;
+    if (misaligned(4, prob, out_pred, junc_pred) || misaligned(8, labels64, out_true, junc_true, acc, ws)) return RSU_EINVAL;
     if (graph_too_big(N, H, W, labels64 ? 8 : 4)) return RSU_E2BIG;
     HIP_CHECK_RET(gr_skeleton_graph(prob, threshold, labels64, min_branch, out_pred, out_true, junc_pred, junc_true, acc, ws, N, H, W,
                                     (hipStream_t)stream));
@@ -1738,6 +1800,7 @@ extern "C" int rsu_line_segments(const float* prob, float threshold, const int64
     if (!prob || !ws || !counts || !edges_pred || (labels64 && !edges_true) || (!labels64 && (edges_true || seg_true || node_true)) ||
         !segments_size_ok(N, H, W, max_edges) || !std::isfinite(threshold))
         return RSU_EINVAL;
+    if (misaligned(4, prob, edges_pred, edges_true, counts, seg_pred, seg_true, node_pred, node_true) || misaligned(8, labels64, acc, ws)) return RSU_EINVAL;
     if (segments_too_big(N, H, W)) return RSU_E2BIG;
     HIP_CHECK_RET(sg_line_segments(prob, threshold, labels64, max_edges, edges_pred, edges_true, counts, seg_pred, seg_true, node_pred, node_true,
                                    acc, ws, N, H, W, (hipStream_t)stream));
@@ -1750,6 +1813,7 @@ extern "C" int rsu_border_map(const int64_t* labels, const float* mul, float* ou
                               float sigma, rsu_stream_t stream) {
     if (!labels || !out || !ws || !border_size_ok(N, H, W)) return RSU_EINVAL;
     if (!std::isfinite(w0) || !(w0 >= 0.f) || !std::isfinite(sigma) || !(sigma > 0.f)) return RSU_EINVAL;
+    if (misaligned(8, labels) || misaligned(4, mul, out, d2, ws)) return RSU_EINVAL;
     if ((long)N * H * W * 8 >= 0x7ffffff0L) return RSU_E2BIG;
     // -1 / (2 sigma^2), in double and rounded once: the host mirror forms the same float
     const float neg_inv_2s2 = (float)(-1.0 / (2.0 * (double)sigma * (double)sigma));
@@ -1762,6 +1826,7 @@ extern "C" int rsu_affine_patches(const float* images, const uint8_t* labels, co
                                   int P, float* x_out, int64_t* labels_out, rsu_stream_t stream) {
     if (!images || !labels || !recs || !x_out || !labels_out || nrec < 1 || nimg < 1 || Hl < 1 || P < 1 || S < P) return RSU_EINVAL;
     if (He < Hl || ((He - Hl) & 1) || ((S - P) & 1) || He - Hl != S - P) return RSU_EINVAL;
+    if (misaligned(4, images, x_out) || misaligned(8, labels_out)) return RSU_EINVAL;   // (12-byte pixels as three floats; labels: bytes)
     for (int r = 0; r < nrec; ++r) {
         const rsu_affine_t& a = recs[r];
         if (a.image < 0 || a.image >= nimg) return RSU_EINVAL;
@@ -1780,6 +1845,7 @@ extern "C" int rsu_elastic_patches(const float* images, const uint8_t* labels, c
                                    int P, float* x_out, int64_t* labels_out, rsu_stream_t stream) {
     if (!images || !labels || !recs || !x_out || !labels_out || nrec < 1 || nimg < 1 || Hl < 1 || P < 1 || S < P) return RSU_EINVAL;
     if (He < Hl || ((He - Hl) & 1) || ((S - P) & 1) || He - Hl != S - P) return RSU_EINVAL;
+    if (misaligned(4, images, x_out) || misaligned(8, labels_out)) return RSU_EINVAL;   // (12-byte pixels as three floats; labels: bytes)
     for (int r = 0; r < nrec; ++r) {
         const rsu_elastic_t& a = recs[r];
         if (a.image < 0 || a.image >= nimg) return RSU_EINVAL;
@@ -1808,7 +1874,7 @@ extern "C" int rsu_color_jitter(float* x, const rsu_jitter_t* recs, int nrec, in
         }
         if (!std::isfinite(j.sigma) || !(j.sigma >= 0.f) || !(j.sigma <= 1.f)) return RSU_EINVAL;
     }
-    if ((any_k && !ws) || ((uintptr_t)ws & 7)) return RSU_EINVAL;
+    if ((any_k && !ws) || ((uintptr_t)ws & 7) || misaligned(4, x)) return RSU_EINVAL;
     if ((long)nrec * S * S * 12 >= 0x7ffffff0L) return RSU_E2BIG;
     HIP_CHECK_RET(cj_color_jitter(x, (const CjRec*)recs, nrec, S, ws, (hipStream_t)stream));
     return RSU_OK;
@@ -1831,7 +1897,7 @@ extern "C" int rsu_extract_tiles(const float* imgs, float* tiles, int nimg, int 
     // images.py:60-61 asserts + tf_aerial_images.py:288-293 geometry
     if (!imgs || !tiles || P > S || (S - P) % 2 || P > H || stride < 1 || (H - P) % stride || (S - P) / 2 > H) return RSU_EINVAL;
     const int pps = (H - P) / stride + 1;
-    if (t0 < 0 || ntiles < 1 || t0 + ntiles > (long)nimg * pps * pps) return RSU_EINVAL;
+    if (t0 < 0 || ntiles < 1 || t0 + ntiles > (long)nimg * pps * pps || misaligned(4, imgs, tiles)) return RSU_EINVAL;
     HIP_CHECK_RET(ew_extract_tiles(imgs, tiles, H, S, P, stride, pps, t0, ntiles, (hipStream_t)stream));
     return RSU_OK;
 }
@@ -1839,7 +1905,7 @@ extern "C" int rsu_overlap_add(const float* prob, float* acc, float* hits, int n
                                rsu_stream_t stream) {
     if (!prob || !acc || !hits || P > H || stride < 1 || (H - P) % stride) return RSU_EINVAL;
     const int pps = (H - P) / stride + 1;
-    if (t0 < 0 || ntiles < 1 || t0 + ntiles > (long)nimg * pps * pps) return RSU_EINVAL;
+    if (t0 < 0 || ntiles < 1 || t0 + ntiles > (long)nimg * pps * pps || misaligned(4, prob, acc, hits)) return RSU_EINVAL;
     HIP_CHECK_RET(ew_overlap_add(prob, acc, hits, nimg, H, P, stride, pps, t0, ntiles, (hipStream_t)stream));
     return RSU_OK;
 }
@@ -1859,18 +1925,19 @@ static int rect_tile_range_ok(int nimg, int H, int W, int P, int stride, long t0
 extern "C" int rsu_extract_tiles_rect(const float* imgs, float* tiles, int nimg, int H, int W, int S, int P, int stride, long t0, long ntiles,
                                       rsu_stream_t stream) {
     if (!imgs || !tiles || P > S || (S - P) % 2 || !rect_tile_range_ok(nimg, H, W, P, stride, t0, ntiles)) return RSU_EINVAL;
+    if (misaligned(4, imgs, tiles)) return RSU_EINVAL;
     if (ntiles > 0x7fffffffffffffffL / 3 / S / S) return RSU_E2BIG;
     HIP_CHECK_RET(ew_extract_tiles_rect(imgs, tiles, H, W, S, P, stride, t0, ntiles, (hipStream_t)stream));
     return RSU_OK;
 }
 extern "C" int rsu_overlap_add_rect(const float* prob, float* acc, float* hits, int nimg, int H, int W, int P, int stride, long t0, long ntiles,
                                     rsu_stream_t stream) {
-    if (!prob || !acc || !hits || !rect_tile_range_ok(nimg, H, W, P, stride, t0, ntiles)) return RSU_EINVAL;
+    if (!prob || !acc || !hits || !rect_tile_range_ok(nimg, H, W, P, stride, t0, ntiles) || misaligned(4, prob, acc, hits)) return RSU_EINVAL;
     HIP_CHECK_RET(ew_overlap_add_rect(prob, acc, hits, nimg, H, W, P, stride, t0, ntiles, (hipStream_t)stream));
     return RSU_OK;
 }
 extern "C" int rsu_overlap_finish(const float* acc, const float* hits, float* out, long n, rsu_stream_t stream) {
-    if (!acc || !hits || !out || n < 1) return RSU_EINVAL;
+    if (!acc || !hits || !out || n < 1 || misaligned(4, acc, hits, out)) return RSU_EINVAL;
     HIP_CHECK_RET(ew_overlap_finish(acc, hits, out, n, (hipStream_t)stream));
     return RSU_OK;
 }
@@ -1879,13 +1946,13 @@ extern "C" int rsu_overlap_finish(const float* acc, const float* hits, float* ou
 // post-processing wire format + metrics counters
 // ---------------------------------------------------------------------------------------------
 extern "C" int rsu_quantize_mask(const float* masks, float* out, int nimg, int S, int patch_size, float threshold, rsu_stream_t stream) {
-    if (!masks || !out || nimg < 1 || S < 1 || patch_size < 1 || patch_size > 64) return RSU_EINVAL;
+    if (!masks || !out || nimg < 1 || S < 1 || patch_size < 1 || patch_size > 64 || misaligned(4, masks, out)) return RSU_EINVAL;
     HIP_CHECK_RET(ew_block_label(masks, out, nullptr, nimg, S, patch_size, threshold, 0, (hipStream_t)stream));
     return RSU_OK;
 }
 extern "C" int rsu_quantize_mask_rect(const float* masks, float* out, int nimg, int H, int W, int patch_size, float threshold,
                                       rsu_stream_t stream) {
-    if (!masks || !out || nimg < 1 || H < 1 || W < 1 || patch_size < 1 || patch_size > 64) return RSU_EINVAL;
+    if (!masks || !out || nimg < 1 || H < 1 || W < 1 || patch_size < 1 || patch_size > 64 || misaligned(4, masks, out)) return RSU_EINVAL;
     const long blocks = (long)nimg * ((H + patch_size - 1) / patch_size) * ((W + patch_size - 1) / patch_size);
     if (blocks > 0x7fffffffL) return RSU_E2BIG;
     HIP_CHECK_RET(ew_block_label_rect(masks, out, nimg, H, W, patch_size, threshold, (hipStream_t)stream));
@@ -1894,12 +1961,13 @@ extern "C" int rsu_quantize_mask_rect(const float* masks, float* out, int nimg, 
 extern "C" int rsu_labels_for_patches(const float* masks, int64_t* labels, int nimg, int S, int patch_size, float threshold,
                                       rsu_stream_t stream) {
     if (!masks || !labels || nimg < 1 || S < 1 || patch_size < 1 || patch_size > 64 || S % patch_size) return RSU_EINVAL;
+    if (misaligned(4, masks) || misaligned(8, labels)) return RSU_EINVAL;
     HIP_CHECK_RET(ew_block_label(masks, nullptr, labels, nimg, S, patch_size, threshold, 1, (hipStream_t)stream));
     return RSU_OK;
 }
 extern "C" int rsu_confusion_counts(const int64_t* predictions, const int64_t* labels, long n, unsigned long long* counts,
                                     rsu_stream_t stream) {
-    if (!predictions || !labels || !counts || n < 1) return RSU_EINVAL;
+    if (!predictions || !labels || !counts || n < 1 || misaligned(8, predictions, labels, counts)) return RSU_EINVAL;   // (counts: 64-bit atomics)
     HIP_CHECK_RET(ew_confusion(predictions, labels, n, counts, (hipStream_t)stream));
     return RSU_OK;
 }

@@ -3,7 +3,9 @@ of the 16-bit word 0x7FA5 -- a NaN as bf16, a NaN as float32 (0x7FA57FA5), an ab
 MFMA kernels are built with num_records = 0x7fffffff: the hardware checks no bound, every tile edge is a hand-written
 predicate, and the exact-size torch tensors of the op tests sit in 512-byte allocator blocks that swallow a short overrun.
 
-Layout. A payload starts on a 256-byte boundary and ends exactly at its last byte. In front of and behind every payload lie at least
+Layout. A payload starts on a 256-byte boundary -- under Placement("minimum") at a 256-byte boundary plus its own minimum alignment, an
+address aligned to exactly that and to nothing larger (the arena itself starts on a 256-byte boundary) -- and ends exactly at its last
+byte. Every claim below holds under both placements. In front of and behind every payload lie at least
 BAND = 1 MiB of pattern; behind a workspace at least the workspace's own size (a size function that is wrong by a factor of two still
 lands inside the arena). The gap between two neighbours is the band behind the first PLUS the band in front of the second, so every
 byte of a gap belongs to exactly one (tensor, side). Outputs start as pattern too: an element a kernel never wrote reads as NaN.
@@ -39,7 +41,30 @@ class _Spec:
     def __init__(self, name, kind, dtype, shape, data=None, band=None):
         self.name, self.kind, self.dtype, self.shape, self.data, self.band = name, kind, dtype, tuple(int(s) for s in shape), data, band
         self.nbytes = int(np.prod(self.shape, dtype=np.int64)) * torch.empty(0, dtype=dtype).element_size()
+        self.minimum = torch.empty(0, dtype=dtype).element_size()    # its minimum alignment: the element size unless a Placement says more
         assert self.nbytes > 0, name
+
+
+class Placement:
+    """Where the payloads of the arenas of ONE case start. "aligned" (the default of Arena): every payload on a 256-byte boundary.
+    "minimum": a payload starts at a 256-byte boundary PLUS its own minimum alignment m (a power of two below 256), so its address is a
+    multiple of m and of nothing larger -- what a caller who places buffers back to back may hand a kernel. A spec's minimum is its element
+    size; minima[i] = {spec name: bytes} raises it for the specs of the i-th arena the case builds (tests/align_util.ALIGN by (entry,
+    argument): tests/test_gpu_aligned_min.py). Bands, the attribution of gap bytes, check() and poison_outside() are the same under both.
+    The placement keeps the arenas built with it (.arenas), in order."""
+
+    def __init__(self, mode="aligned", minima=()):
+        assert mode in ("aligned", "minimum"), mode
+        self.mode, self.minima, self.arenas = mode, list(minima), []
+
+    def shift(self, spec):
+        """bytes between the 256-byte boundary and the start of `spec` in the arena that is being built"""
+        if self.mode == "aligned":
+            return 0
+        over = self.minima[len(self.arenas)] if len(self.arenas) < len(self.minima) else {}
+        m = max(spec.minimum, int(over.get(spec.name, 0)))
+        assert 0 < m < ALIGN and m & (m - 1) == 0 and m % spec.minimum == 0, (spec.name, m)
+        return m
 
 
 def _cpu(a, dtype):
@@ -94,18 +119,21 @@ def _up(n, a=ALIGN):
 
 
 class Arena:
-    def __init__(self, device, specs, band=BAND):
+    def __init__(self, device, specs, band=BAND, placement="aligned"):
         self.device, self.specs, self.band = device, list(specs), band
         assert len({s.name for s in self.specs}) == len(self.specs), "duplicate names"
+        self.placement = placement if isinstance(placement, Placement) else Placement(placement)
         cur = 0
         self.place = {}          # name -> (start, end, band behind)
         for s in self.specs:
-            start = _up(cur + band)
+            start = _up(cur + band) + self.placement.shift(s)
             behind = _up(max(band, s.nbytes) if s.kind == "ws" and s.band is None else max(band, s.band or 0))
             self.place[s.name] = (start, start + s.nbytes, behind)
             cur = start + s.nbytes + behind
         self.total = _up(cur)
-        self.mem = torch.empty(self.total, dtype=torch.uint8, device=device)
+        raw = torch.empty(self.total + ALIGN, dtype=torch.uint8, device=device)    # (the arena itself starts on a 256-byte boundary on any device)
+        self.mem = raw[(-raw.data_ptr()) % ALIGN:][:self.total]
+        assert self.mem.data_ptr() % ALIGN == 0
         self.mem.view(torch.int16).fill_(PATTERN)
         # the regions: every byte that is no payload, attributed to (tensor, side); offsets are formed from `origin`
         self.regions = []        # (name, side, start, end, origin)
@@ -128,6 +156,7 @@ class Arena:
                 self.mem[start:end].copy_(s.data.view(torch.uint8).reshape(-1).to(device))
             if s.kind == "in":
                 self.given[s.name] = self.mem[start:end].clone()
+        self.placement.arenas.append(self)
 
     def __getitem__(self, name):
         return self.t[name]

@@ -37,13 +37,13 @@ def _launch_cldice(A, iters, st):
 
 @pytest.mark.parametrize("kind", ["tied4", "saturated"])
 @pytest.mark.parametrize("iters", [3, 16])
-def test_cldice_fwd_bwd(iters, kind):
+def test_cldice_fwd_bwd(iters, kind, placement="aligned"):
     p, labels = CU.INPUTS[kind](SHAPE)
     assert ((labels != 0) & (labels != 1)).sum() > labels.size // 20
     o32 = lambda name, *s: F.out(name, s, torch.float32)  # noqa: E731
     specs = [F.f32("prob", p), F.raw("labels", labels), o32("skel_p", *SHAPE), o32("skel_y", *SHAPE), o32("gprob", *SHAPE),
              F.state("sums", np.zeros(4, np.float32)), F.ws("ws", lib().rsu_cldice_ws_floats(*SHAPE, iters))]
-    A = F.Arena(hu.DEV, specs)
+    A = F.Arena(hu.DEV, specs, placement=placement)
     _launch_cldice(A, iters, hu.stream())
     what = "clDice fenced k=%d %s" % (iters, kind)
     A.check(what)
@@ -70,7 +70,7 @@ def _launch_aux(A, C, inv, st):
 
 
 @pytest.mark.parametrize("C", HEAD_C)
-def test_aux_head(C):
+def test_aux_head(C, placement="aligned"):
     rng, act, w, b, labels = _inputs(C)
     pixel_w = _weight_map(rng)
     labels, ign = _with_ignored(rng, labels)
@@ -84,7 +84,7 @@ def test_aux_head(C):
     for k in ("f", "d"):
         specs += [o32("prob_" + k, NPIX), F.out("dact_" + k, (NPIX, C)), o32("dw_" + k, C, 2), o32("db_" + k, 2), z("loss_" + k, 1), z("wsum_" + k, 1)]
     specs += [o32("prob_s", NPIX), o32("dsums", 3), F.ws("ws_f", L.rsu_head_dice_ws_floats(NPIX, C)), F.ws("ws_d", L.rsu_head_dice_ws_floats(NPIX, C))]
-    A = F.Arena(hu.DEV, specs)
+    A = F.Arena(hu.DEV, specs, placement=placement)
     _launch_aux(A, C, inv, hu.stream())
     what = "aux head fenced C=%d" % C
     A.check(what)

@@ -33,7 +33,7 @@ def _launch(A, shape, connectivity, st):
 
 @pytest.mark.parametrize("connectivity", CU.CONNECTIVITIES)
 @pytest.mark.parametrize("shape", SHAPES, ids=[CU.shape_id(s) for s in SHAPES])
-def test_components_entries(shape, connectivity):
+def test_components_entries(shape, connectivity, placement="aligned"):
     prob = CU.float_bank(shape)
     labels64 = CU.pair_labels(shape)
     nbytes = int(lib().rsu_components_ws_bytes(*shape))
@@ -42,7 +42,7 @@ def test_components_entries(shape, connectivity):
              F.out("edge", shape, torch.uint8), F.out("labels_inv", shape, torch.int32), F.out("out", shape, torch.float32),
              F.out("stats", (shape[0], 6), torch.int64), F.state("inplace", prob), F.state("acc", np.zeros(4, np.int64)),
              F.ws("ws", nbytes // 4, dtype=torch.int32)]
-    A = F.Arena(hu.DEV, specs)
+    A = F.Arena(hu.DEV, specs, placement=placement)
     _launch(A, shape, connectivity, hu.stream())
     what = "components fenced %s %d" % (shape, connectivity)
     A.check(what)

@@ -32,7 +32,7 @@ def _launch(A, shape, st):
 
 
 @pytest.mark.parametrize("shape", SHAPES, ids=[DU.shape_id(s) for s in SHAPES])
-def test_distance_entries(shape):
+def test_distance_entries(shape, placement="aligned"):
     prob = CU.float_bank(shape)
     labels64 = DU.mixed_labels(shape)
     nbytes = int(lib().rsu_distance_ws_bytes(*shape))
@@ -40,7 +40,7 @@ def test_distance_entries(shape):
     specs = [F.f32("prob", prob), F.raw("labels64", labels64)]
     specs += [F.out(n, shape, torch.int32) for n in ("d2_pred", "d2_true", "pred_only", "true_only", "no_labels")]
     specs += [F.state("acc", np.zeros((2, DU.BINS), np.int64)), F.ws("ws", nbytes // 4, dtype=torch.int32)]
-    A = F.Arena(hu.DEV, specs)
+    A = F.Arena(hu.DEV, specs, placement=placement)
     _launch(A, shape, hu.stream())
     what = "distance fenced %s" % (shape,)
     A.check(what)

@@ -64,7 +64,7 @@ CONV = [(2, 13, 19, 24, 40, 1, True), (1, 17, 15, 72, 136, 2, False), (2, 37, 41
 CONV_MULTI = (2, 37, 41, 72, 136, 1, True)    # the awkward shape with several tiles per workgroup: the forced tile shapes, ncu = 32
 
 
-def _conv_fwd(shape, relu, ncu=0, y_rows_short=0, x_rows_short=0, compare=True, capfd=None):
+def _conv_fwd(shape, relu, ncu=0, y_rows_short=0, x_rows_short=0, compare=True, capfd=None, placement="aligned"):
     """test_gpu_ops.test_conv2d_fwd's launch, the weights packed by rsu_pack_conv_fwd into a buffer of exactly rsu_packed_bytes.
     y_rows_short / x_rows_short: the positive controls -- the output / the input carved that many image rows shorter than the call says"""
     N, H, W, Cin, Cout, dil, awkward = shape
@@ -74,7 +74,7 @@ def _conv_fwd(shape, relu, ncu=0, y_rows_short=0, x_rows_short=0, compare=True, 
     b = _rand(rng, Cout, scale=0.1)
     Ho, Wo = H - 2 * dil, W - 2 * dil
     A = F.Arena(hu.DEV, [F.bf16("x", x.reshape(-1)[:(N * H - x_rows_short) * W * Cin]), F.f32("w", w), _packed("wp", 9, Cout, [Cin]), F.f32("b", b),
-                         F.out("y", ((N * Ho - y_rows_short) * Wo * Cout,))])
+                         F.out("y", ((N * Ho - y_rows_short) * Wo * Cout,))], placement=placement)
     if awkward:
         _awkward(N, N * Ho * Wo, Cin, Cout, A["x"], A["y"], A["b"])
     seg = (ctypes.c_int * 1)(Cin)
@@ -132,12 +132,12 @@ def _crop_case(sizes, chans, h, w, Cout, seed):
 @pytest.mark.parametrize("sizes,chans,h,w,Cout", [([(34, 38), (28, 30), (22, 26)], [32, 32, 32], 22, 26, 64), ([(25, 29), (19, 23)], [16, 16], 19, 23, 16),
                                                   ([(29, 33), (23, 27), (21, 23)], [24, 40, 8], 21, 23, 40)], ids=["32+32+32", "16+16", "24+40+8"])
 @pytest.mark.parametrize("relu", [0, 1])
-def test_conv2d_fwd_cropped_sources(sizes, chans, h, w, Cout, relu):
+def test_conv2d_fwd_cropped_sources(sizes, chans, h, w, Cout, relu, placement="aligned"):
     """test_gpu_ops.test_conv2d_fwd_three_cropped_sources / _odd_channel_segments, the margins of every source poisoned; 24+40+8 -> 40 is
     the awkward one"""
     N, srcs, Cin, Wt, bias, cat = _crop_case(sizes, chans, h, w, Cout, 5)
     A = F.Arena(hu.DEV, [F.bf16("src%d" % i, a) for i, a in enumerate(srcs)] + [F.f32("w", Wt), _packed("wp", 9, Cout, chans), F.f32("b", bias),
-                                                                                F.out("y", (N, h - 2, w - 2, Cout))])
+                                                                                F.out("y", (N, h - 2, w - 2, Cout))], placement=placement)
     if chans[0] % 32:
         _awkward(N, N * (h - 2) * (w - 2), chans[0], Cout, A["y"], *[A["src%d" % i] for i in range(len(srcs))])
     for i, (H, W) in enumerate(sizes):
@@ -151,7 +151,7 @@ def test_conv2d_fwd_cropped_sources(sizes, chans, h, w, Cout, relu):
 
 
 @pytest.mark.parametrize("relu", [0, 1])
-def test_conv2d_fwd_k_split(relu, capfd, monkeypatch):
+def test_conv2d_fwd_k_split(relu, capfd, monkeypatch, placement="aligned"):
     """test_gpu_ops.test_conv2d_fwd_split_k at (1, 20, 20, [200, 120] -> 128): the split asserted on the plan line, the workspace exactly
     rsu_conv_splitk_ws_floats"""
     monkeypatch.setenv("RSU_PLAN_DEBUG", "1")
@@ -163,7 +163,7 @@ def test_conv2d_fwd_k_split(relu, capfd, monkeypatch):
     b = _rand(rng, Cout, scale=0.1)
     nk = int(lib().rsu_conv_splitk_ws_floats())
     A = F.Arena(hu.DEV, [F.bf16("x0", xs[0]), F.bf16("x1", xs[1]), F.f32("w", w), _packed("wp", 9, Cout, segs), F.f32("b", b),
-                         F.out("y", (N, H - 2, W - 2, Cout)), F.ws("kws", nk)])
+                         F.out("y", (N, H - 2, W - 2, Cout)), F.ws("kws", nk)], placement=placement)
     seg = (ctypes.c_int * 2)(*segs)
     call("rsu_pack_conv_fwd", hu.ptr(A["w"]), hu.ptr(A["wp"]), 3, Cin, Cout, seg, 2, hu.stream())
     s = (RsuSrc * 2)(hu.src_of(A["x0"], H, W), hu.src_of(A["x1"], H, W))
@@ -175,7 +175,7 @@ def test_conv2d_fwd_k_split(relu, capfd, monkeypatch):
     hu.assert_bf16_close(_host(A["y"]), U.conv2d_fwd(np.concatenate(xs, axis=3), hu.q(w), b, relu=bool(relu)), "conv2d_fwd_k split-K relu %d" % relu)
 
 
-def _bwd_data(shape, mode, ncu=0, k=False, capfd=None):
+def _bwd_data(shape, mode, ncu=0, k=False, capfd=None, placement="aligned"):
     """test_gpu_ops.test_conv2d_bwd_data's launches: mode "mask" (ReLU mask), "plain", "accumulate" (onto a stored bf16 tensor)"""
     N, H, W, Cin, Cout, dil, awkward = shape
     rng = np.random.RandomState(Cin + Cout * 3 + W)
@@ -189,7 +189,7 @@ def _bwd_data(shape, mode, ncu=0, k=False, capfd=None):
     nk = int(lib().rsu_conv_splitk_ws_floats())
     if k:
         specs.append(F.ws("kws", nk))
-    A = F.Arena(hu.DEV, specs)
+    A = F.Arena(hu.DEV, specs, placement=placement)
     if awkward:
         _awkward(N, N * H * W, Cout, Cin, A["dz"], A["dx"])     # (the GEMM's input channels are Cout, its output channels Cin)
     call("rsu_pack_conv_bwd", hu.ptr(A["w"]), hu.ptr(A["wp"]), 3, Cin, 0, Cin, Cout, hu.stream())
@@ -239,7 +239,7 @@ def test_conv2d_bwd_data_k_split(mode, capfd, monkeypatch):
     _bwd_data((1, 20, 20, 512, 512, 1, False), mode, k=True, capfd=capfd)
 
 
-def test_conv2d_bwd_data_source_slice():
+def test_conv2d_bwd_data_source_slice(placement="aligned"):
     """test_gpu_ops.test_conv2d_bwd_data_source_slice, N = 2, 24 -> 40 + 24 + 8 channels: one pack and one launch per concat source"""
     rng = np.random.RandomState(9)
     N, H, W, Cin, Cout = 2, 13, 19, 72, 24
@@ -248,7 +248,7 @@ def test_conv2d_bwd_data_source_slice():
     full = U.conv2d_bwd_data(dz, hu.q(w), (H, W))
     slices = [(0, 40), (40, 24), (64, 8)]
     A = F.Arena(hu.DEV, [F.bf16("dz", dz), F.f32("w", w)] + [_packed("wp%d" % off, 9, cnt, [Cout]) for off, cnt in slices]
-                + [F.out("dx%d" % off, (N, H, W, cnt)) for off, cnt in slices])
+                + [F.out("dx%d" % off, (N, H, W, cnt)) for off, cnt in slices], placement=placement)
     _awkward(N, N * H * W, Cout, 40, A["dz"], A["dx0"])
     for off, cnt in slices:
         call("rsu_pack_conv_bwd", hu.ptr(A["w"]), hu.ptr(A["wp%d" % off]), 3, Cin, off, cnt, Cout, hu.stream())
@@ -264,7 +264,7 @@ POOL = [(2, 12, 14, 24, 40, True), (2, 70, 70, 64, 64, False)]     # N, H, W, Ci
 @pytest.mark.parametrize("shape", POOL, ids=str)
 @pytest.mark.parametrize("with_code", [1, 0])
 @pytest.mark.parametrize("k", [0, 1], ids=["plain", "k"])
-def test_conv2d_fwd_pool(shape, with_code, k, monkeypatch, capfd):
+def test_conv2d_fwd_pool(shape, with_code, k, monkeypatch, capfd, placement="aligned"):
     """test_gpu_ops.test_conv2d_fwd_pool_equals_conv_then_pool's launch with RSU_POOL_FUSED=2 (fold wherever a tile shape can), with and
     without code bytes, through rsu_conv2d_fwd_pool and rsu_conv2d_fwd_pool_k (workspace exactly rsu_conv_splitk_ws_floats). At
     both shapes the folded kernel is asserted on the plan line (pool1, one conv launch: cfg3, strip width 16). Activation against the
@@ -284,7 +284,7 @@ def test_conv2d_fwd_pool(shape, with_code, k, monkeypatch, capfd):
         specs.append(F.out("code", (N, Ho // 2, Wo // 2, Cout), torch.uint8))
     if k:
         specs.append(F.ws("kws", nk))
-    A = F.Arena(hu.DEV, specs)
+    A = F.Arena(hu.DEV, specs, placement=placement)
     if awkward:
         _awkward(N, N * Ho * Wo, Cin, Cout, A["x"], A["y"], A["pool"])
     seg = (ctypes.c_int * 1)(Cin)
@@ -317,7 +317,7 @@ def _pool_code(x):
 
 
 # ------------------------------------------------------------------------------------------- 3x3 weight gradients, bias gradient
-def _wgrad(shape, ncu=0, crop=None):
+def _wgrad(shape, ncu=0, crop=None, placement="aligned"):
     """test_gpu_ops.test_conv2d_bwd_weight_and_bias's launches: the workspace exactly rsu_conv2d_bwd_weight_ws_floats; rsu_bias_grad
     with exactly rsu_bias_grad_ws_floats where it admits the channel count. crop = (H0, W0): the source is a larger tensor, its margins
     poisoned"""
@@ -333,7 +333,7 @@ def _wgrad(shape, ncu=0, crop=None):
              F.ws("ws", lib().rsu_conv2d_bwd_weight_ws_floats(Cin, Cin, Cout))]
     if bias_ok:
         specs += [F.out("db2", (Cout,), torch.float32), F.ws("bws", lib().rsu_bias_grad_ws_floats(N * Ho * Wo, Cout))]
-    A = F.Arena(hu.DEV, specs)
+    A = F.Arena(hu.DEV, specs, placement=placement)
     if awkward:
         _awkward(N, N * Ho * Wo, Cin, Cout, A["x"], A["dz"], A["db"])
     if crop:
@@ -357,7 +357,7 @@ def test_conv2d_bwd_weight_and_bias_grad(shape):
 
 
 @pytest.mark.parametrize("npix,C", [(3 * 37 * 41, 8), (3 * 37 * 41, 16), (2 * 11 * 17, 64), (7, 8), (1003, 2048)])
-def test_bias_grad(npix, C):
+def test_bias_grad(npix, C, placement="aligned"):
     """rsu_bias_grad admits C with 256 % (C / 8) == 0 only, which none of the awkward conv shapes has: here alone, at odd pixel counts
     (more than one block, and fewer pixels than a block has rows), the smallest and the largest admitted C, the workspace exactly
     rsu_bias_grad_ws_floats"""
@@ -365,7 +365,7 @@ def test_bias_grad(npix, C):
     assert 256 % (C // 8) == 0 and (C == 2048 or (npix * C * 2) % 512 != 0)
     rng = np.random.RandomState(npix % 1000 + C)
     dz = hu.q(_rand(rng, npix, C, scale=0.1))
-    A = F.Arena(hu.DEV, [F.bf16("dz", dz), F.out("db", (C,), torch.float32), F.ws("ws", lib().rsu_bias_grad_ws_floats(npix, C))])
+    A = F.Arena(hu.DEV, [F.bf16("dz", dz), F.out("db", (C,), torch.float32), F.ws("ws", lib().rsu_bias_grad_ws_floats(npix, C))], placement=placement)
     call("rsu_bias_grad", hu.ptr(A["dz"]), hu.ptr(A["db"]), hu.ptr(A["ws"]), npix, C, hu.stream())
     A.check("bias_grad npix %d C %d" % (npix, C))
     hu.assert_f32_close(_host(A["db"]), dz.astype(np.float64).sum(0), "bias_grad npix %d C %d" % (npix, C))
@@ -395,7 +395,7 @@ def test_conv2d_bwd_weight_cropped_source():
     _wgrad((2, 13, 19, 24, 40, 1, True), crop=(25, 29))
 
 
-def test_wgrad_group(monkeypatch):
+def test_wgrad_group(monkeypatch, placement="aligned"):
     """test_gpu_ops.test_wgrad_group_equals_single_launches' job set (ncu = 64) with the workspace exactly rsu_wgrad_group_ws_floats (a 4 MiB
     band behind it: the planner checks its own need on the host) and the device table exactly rsu_wgrad_group_table_bytes"""
     ncu = 64
@@ -420,7 +420,7 @@ def test_wgrad_group(monkeypatch):
             refs.append(U.convT_bwd(x, np.zeros((2, 2, cout, cin_t), np.float32), dy, need_dx=False)[1:])
     nb = lib().rsu_wgrad_group_table_bytes()
     specs += [F.ws("ws", lib().rsu_wgrad_group_ws_floats(), band=4 * MiB), F.out("table", (nb,), torch.uint8)]
-    A = F.Arena(hu.DEV, specs)
+    A = F.Arena(hu.DEV, specs, placement=placement)
     jobs = []
     for i, (kind, H, W, cin_t, off, csrc, cout, dil) in enumerate(jobspecs):
         if kind == 0:
@@ -451,7 +451,7 @@ def test_wgrad_group(monkeypatch):
 CONVT = [(2, 7, 9, 72, 40, True), (3, 33, 31, 72, 64, False), (2, 52, 50, 96, 96, False), (1, 9, 11, 24, 16, False)]   # N, H, W, Cin, Cout, awkward
 
 
-def _convT(shape, ncu=0, ws_slabs_short=0, compare=True):
+def _convT(shape, ncu=0, ws_slabs_short=0, compare=True, placement="aligned"):
     """test_gpu_ops.test_convT's launches: forward, backward-data with the ReLU mask, rsu_dropout_fwd and the backward-data behind it
     (out_scale = 1 / keep), the weight gradient with a workspace of exactly rsu_convT2x2_bwd_weight_ws_floats; both packs into buffers of
     exactly rsu_packed_bytes"""
@@ -466,7 +466,7 @@ def _convT(shape, ncu=0, ws_slabs_short=0, compare=True):
         nws -= ws_slabs_short * (4 * Cout * Cin + Cout)
     A = F.Arena(hu.DEV, [F.bf16("x", x), F.f32("K", K), _packed("pf", 1, Cout, [Cin], mult=4), _packed("pb", 4, Cin, [Cout]), F.f32("b", b), F.bf16("dy", dy),
                          F.out("y", (N, 2 * H, 2 * W, Cout)), F.out("dx", (N, H, W, Cin)), F.out("xdrop", (N, H, W, Cin)), F.out("dx2", (N, H, W, Cin)),
-                         F.out("dK", (2, 2, Cout, Cin), torch.float32), F.out("db", (Cout,), torch.float32), F.ws("ws", nws)])
+                         F.out("dK", (2, 2, Cout, Cin), torch.float32), F.out("db", (Cout,), torch.float32), F.ws("ws", nws)], placement=placement)
     if awkward:
         _awkward(N, N * H * W, Cin, Cout, A["x"], A["y"], A["dy"], A["db"])
     st = hu.stream()
@@ -517,7 +517,7 @@ def test_convT_ncu32():
 FIRST = [(1, 5, 19, 8, 1, False), (3, 21, 50, 72, 1, True), (1, 40, 37, 16, 2, False)]     # N, H, W, Cout, dil, awkward
 
 
-def _first(shape, ncu=0):
+def _first(shape, ncu=0, placement="aligned"):
     """test_gpu_ops.test_color_adjust_and_first_conv's launches (keep = 0.8 at dilation 1) plus rsu_color_conv_first_fwd and
     rsu_color_adjust_bwd: the packed buffer exactly rsu_packed_first_bytes, the workspace exactly rsu_conv_first_bwd_ws_floats. The
     first layer's input channels are 3 (16 stored): the awkward property "a multiple of 8 but not of 32" holds for the stored tensor."""
@@ -533,7 +533,7 @@ def _first(shape, ncu=0):
                          F.out("in16", (N, H, W, 16)), F.out("in16k", (N, H, W, 16)), F.out("pk1", (lib().rsu_packed_first_bytes(Cout) // 2,)),
                          F.out("y", (N, Ho, Wo, Cout)), F.out("yb", (N, Ho, Wo, Cout)),
                          F.out("dw1", (3, 3, 3, Cout), torch.float32), F.out("gx", (9, 12, Cout), torch.float32), F.out("db", (Cout,), torch.float32),
-                         F.ws("ws", lib().rsu_conv_first_bwd_ws_floats(Cout)), F.out("dW0", (3, 3), torch.float32), F.out("db0", (3,), torch.float32)])
+                         F.ws("ws", lib().rsu_conv_first_bwd_ws_floats(Cout)), F.out("dW0", (3, 3), torch.float32), F.out("db0", (3,), torch.float32)], placement=placement)
     if awkward:
         _awkward(N, N * Ho * Wo, 16, Cout, A["x"], A["y"], A["dz"], A["db"])
     st = hu.stream()
@@ -588,7 +588,7 @@ def _up2(a):
     return np.repeat(np.repeat(a, 2, axis=1), 2, axis=2)
 
 
-def _pool_junction(shape, dskip_rows_short=0):
+def _pool_junction(shape, dskip_rows_short=0, placement="aligned"):
     """test_gpu_ops.test_maxpool_fwd_and_junction_bwd's launches: the pool with and without dropout, with code bytes where the size is
     even, the gradient junction from the activation and from the code bytes. (1, 9, 11, 8) pools an odd size with floor semantics."""
     N, H, W, C = shape
@@ -606,7 +606,7 @@ def _pool_junction(shape, dskip_rows_short=0):
              F.out("yd", (N, Hp, Wp, C)), F.out("dz", (N, H, W, C)), F.out("dzd", (N, H, W, C))]
     if even:
         specs += [F.out("y2", (N, Hp, Wp, C)), F.out("code", (N, Hp, Wp, C), torch.uint8), F.out("dz2", (N, H, W, C))]
-    A = F.Arena(hu.DEV, specs)
+    A = F.Arena(hu.DEV, specs, placement=placement)
     st = hu.stream()
     call("rsu_maxpool2x2_fwd", hu.ptr(A["x"]), hu.ptr(A["y"]), N, H, W, C, 1.0, 0, st)
     call("rsu_maxpool2x2_fwd", hu.ptr(A["x"]), hu.ptr(A["yd"]), N, H, W, C, keep, key, st)
@@ -641,24 +641,24 @@ def test_pool_and_junction(shape):
 
 
 @pytest.mark.parametrize("n", [8, 2 * 7 * 9 * 72, 1003 * 8])
-def test_dropout_fwd(n):
+def test_dropout_fwd(n, placement="aligned"):
     """rsu_dropout_fwd takes n % 8 == 0 only (rsu.h): 8 (one vector), an awkward tensor's count, and 8024 = 8 * 1003 elements, whose byte
     size is no multiple of 512 and whose vector count is odd"""
     assert n % 8 == 0 and (n == 8 or (2 * n) % 512 != 0)
     rng = np.random.RandomState(n % 1000)
     x = hu.q(_rand(rng, n))
     keep, key = 0.8, 0x5EED0001
-    A = F.Arena(hu.DEV, [F.bf16("x", x), F.out("y", (n,))])
+    A = F.Arena(hu.DEV, [F.bf16("x", x), F.out("y", (n,))], placement=placement)
     call("rsu_dropout_fwd", hu.ptr(A["x"]), hu.ptr(A["y"]), n, keep, key, hu.stream())
     A.check("dropout_fwd n %d" % n)
     m = U.dropout_mask((n,), keep, key)
     np.testing.assert_array_equal(_host(A["y"]), hu.q(x * m * (np.float32(1) / np.float32(keep))))
 
 
-def test_dropout_fwd_refuses_a_count_that_is_no_multiple_of_8():
+def test_dropout_fwd_refuses_a_count_that_is_no_multiple_of_8(placement="aligned"):
     """the precondition n % 8 == 0 of rsu.h is held, not assumed: RSU_EINVAL before anything is launched or written"""
     x = hu.q(_rand(np.random.RandomState(1), 1003))
-    A = F.Arena(hu.DEV, [F.bf16("x", x), F.out("y", (1003,))])
+    A = F.Arena(hu.DEV, [F.bf16("x", x), F.out("y", (1003,))], placement=placement)
     for n in (1003, 1001, 7):
         assert lib().rsu_dropout_fwd(hu.ptr(A["x"]), hu.ptr(A["y"]), n, 0.8, 1, hu.stream()) == -22, n
     A.check("refused dropout_fwd")
@@ -678,7 +678,7 @@ def _hist_from_prob(prob, labels):
 
 
 @pytest.mark.parametrize("C", HEAD_C)
-def test_heads(C):
+def test_heads(C, placement="aligned"):
     """npix = 3 * 37 * 41 (odd: no multiple of any block) at every admitted C: rsu_head_fwd, _fwd_bwd, _fwd_bwd_w (class weights, a weight
     map, ignored labels), rsu_head_dice_sums + _fwd_bwd_dice, rsu_head_eval -- the launches of test_gpu_ops.test_head,
     test_gpu_weighted_loss, test_gpu_dice_loss and test_gpu_validation, each workspace exactly its own size function's"""
@@ -699,7 +699,7 @@ def test_heads(C):
     specs += [o32("prob_s", NPIX), o32("dsums", 3), z("esums", 5), F.state("hist", np.zeros((2, 256), np.int64)),
               F.ws("ws_a", L.rsu_head_ws_floats(NPIX, C)), F.ws("ws_w", L.rsu_head_w_ws_floats(NPIX, C)), F.ws("ws_d", L.rsu_head_dice_ws_floats(NPIX, C)),
               F.ws("ws_e", L.rsu_head_eval_ws_floats(NPIX, C))]
-    A = F.Arena(hu.DEV, specs)
+    A = F.Arena(hu.DEV, specs, placement=placement)
     p = lambda n: hu.ptr(A[n])  # noqa: E731
     st = hu.stream()
     call("rsu_head_fwd", p("act"), p("w"), p("b"), p("prob0"), p("logits"), NPIX, C, st)
@@ -732,7 +732,7 @@ def test_heads(C):
     np.testing.assert_array_equal(A["hist"].cpu().numpy(), _hist_from_prob(A["prob_e"].cpu().numpy(), lab_i))
 
 
-def test_border_map():
+def test_border_map(placement="aligned"):
     """test_gpu_border_map's launch at its smallest geometries as one batch of every case tile, with a caller map and d2; the workspace
     exactly rsu_border_map_ws_bytes"""
     from road_segmentation_unet_amd import hostio
@@ -745,7 +745,7 @@ def test_border_map():
         mul = bu.mul_map(rng, labels)
         nws = int(lib().rsu_border_map_ws_bytes(N, H, W))
         A = F.Arena(hu.DEV, [F.raw("labels", labels), F.f32("mul", mul), F.out("out", (N, H, W), torch.float32), F.out("d2", (N, H, W), torch.int32),
-                             F.ws("ws", nws, torch.uint8)])
+                             F.ws("ws", nws, torch.uint8)], placement=placement)
         call("rsu_border_map", hu.ptr(A["labels"]), hu.ptr(A["mul"]), hu.ptr(A["out"]), hu.ptr(A["d2"]), hu.ptr(A["ws"]), N, H, W, 10.0, 5.0, hu.stream())
         A.check("border_map %dx%dx%d" % (N, H, W))
         torch.cuda.synchronize()
@@ -772,7 +772,7 @@ OPT_N = [1003, 3, 5]     # 1003: float4s and a tail of three; 3: below a vector 
 
 
 @pytest.mark.parametrize("n", OPT_N)
-def test_momentum_adam_ema_accumulate_norm(n):
+def test_momentum_adam_ema_accumulate_norm(n, placement="aligned"):
     """rsu_momentum_step, rsu_adam_step, rsu_grad_norm (workspace exactly rsu_grad_norm_ws_floats, the 32-byte record exactly
     rsu_clip_state_bytes), rsu_ema_step (with and without the record), rsu_grad_accumulate (assign and add) on vectors of n floats that end
     at their last byte: the launches of test_gpu_ops.test_momentum_step, test_gpu_adam.test_adam_step_op, test_gpu_clip, test_gpu_ema,
@@ -786,7 +786,7 @@ def test_momentum_adam_ema_accumulate_norm(n):
     assert L.rsu_clip_state_bytes() == 32
     A = F.Arena(hu.DEV, [F.f32("g", g), F.state("w", w), F.state("acc", a), F.state("w2", w), F.state("m", m), F.state("v", v), F.f32("wconst", w),
                          F.state("ema", ema), F.state("ema2", ema), F.state("dst", dst), F.out("dst2", (n,), torch.float32),
-                         F.ws("nws", L.rsu_grad_norm_ws_floats(n)), F.state("state", np.zeros(L.rsu_clip_state_bytes() // 4, np.int32))])
+                         F.ws("nws", L.rsu_grad_norm_ws_floats(n)), F.state("state", np.zeros(L.rsu_clip_state_bytes() // 4, np.int32))], placement=placement)
     p = lambda k: hu.ptr(A[k])  # noqa: E731
     st = hu.stream()
     alpha, b1, b2, eps, omd = 1.234e-3, 0.9, 0.999, 1e-8, 0.25
@@ -816,7 +816,7 @@ def test_momentum_adam_ema_accumulate_norm(n):
 
 
 @pytest.mark.parametrize("mode", ["momentum", "adam", "momentum_clip", "adam_clip"])
-def test_update_and_pack_tables(mode):
+def test_update_and_pack_tables(mode, placement="aligned"):
     """rsu_update_table_run and its Adam and clip variants over a table with one entry of every kind -- a 3x3 conv kernel of two concat
     sources (24 + 16 -> 40), a transposed-conv kernel (72 -> 40), the first conv (3 -> 72) and a plain range of 1003 floats -- against the
     numpy restatement of the step; then rsu_pack_table_run and the per-tensor rsu_pack_* calls from the NEW weights into buffers of
@@ -846,7 +846,7 @@ def test_update_and_pack_tables(mode):
     specs += [F.out("utable", (esz * 4,), torch.uint8), F.out("ptable", (psz * 9,), torch.uint8), F.ws("nws", L.rsu_grad_norm_ws_floats(1003)),
               F.state("state", np.zeros(8, np.int32))]
     x = hu.q(_rand(rng, 2, 9, 11, 40))
-    A = F.Arena(hu.DEV, specs)
+    A = F.Arena(hu.DEV, specs, placement=placement)
     p = lambda k: hu.ptr(A[k])  # noqa: E731
     st = hu.stream()
     # ---- the update table
@@ -932,7 +932,7 @@ def test_update_and_pack_tables(mode):
         assert torch.equal(t, s), "rsu_pack_table_run against rsu_pack_*: " + k
     # ---- one conv on the copy the update pass wrote (its two sources and its output in an arena of their own)
     xa, xb = np.ascontiguousarray(x[..., :24]), np.ascontiguousarray(x[..., 24:])
-    B = F.Arena(hu.DEV, [F.bf16("xa", xa), F.bf16("xb", xb), F.out("y", (2, 7, 9, Cc))])
+    B = F.Arena(hu.DEV, [F.bf16("xa", xa), F.bf16("xb", xb), F.out("y", (2, 7, 9, Cc))], placement=placement)
     s2 = (RsuSrc * 2)(hu.src_of(B["xa"], 9, 11), hu.src_of(B["xb"], 9, 11))
     call("rsu_conv2d_fwd", s2, 2, p("u_conv_fwd"), None, hu.ptr(B["y"]), 2, 9, 11, Cc, 1, 1, 0, st)
     B.check(what + ": conv on the re-packed copy")
@@ -941,7 +941,7 @@ def test_update_and_pack_tables(mode):
 
 
 # =========================================================================================== host-path kernels
-def test_tilers_square_and_rect():
+def test_tilers_square_and_rect(placement="aligned"):
     """test_gpu_ops.test_tiler_extract_and_overlap at (20, 8, 12, 4, 2) and test_gpu_tiler_rect.test_rect_tiler_against_the_rule at
     (2, 23, 31, 8, 12, 5), its smallest geometry with a clamped last tile; both in two calls split at nt // 2, then rsu_overlap_finish"""
     from tests import rect_util as R
@@ -961,7 +961,7 @@ def test_tilers_square_and_rect():
     A = F.Arena(hu.DEV, [F.f32("imgs", imgs), F.f32("prob", prob), F.out("tiles", (nt, S, S, 3), torch.float32), zeros("acc", nimg, H, H), zeros("hits", nimg, H, H),
                          F.out("mean", (nimg, H, H), torch.float32),
                          F.f32("imgs2", imgs2), F.f32("prob2", prob2), F.out("tiles2", (nt2, S2, S2, 3), torch.float32), zeros("acc2", nimg2, H2, W2),
-                         zeros("hits2", nimg2, H2, W2), F.out("mean2", (nimg2, H2, W2), torch.float32)])
+                         zeros("hits2", nimg2, H2, W2), F.out("mean2", (nimg2, H2, W2), torch.float32)], placement=placement)
     p = lambda k: hu.ptr(A[k])  # noqa: E731
     st = hu.stream()
     half = nt // 2
@@ -987,7 +987,7 @@ def test_tilers_square_and_rect():
     np.testing.assert_allclose(_host(A["mean2"]), refm2, rtol=2e-6, atol=1e-7)
 
 
-def test_quantize_labels_confusion():
+def test_quantize_labels_confusion(placement="aligned"):
     """rsu_quantize_mask (40 px masks, 16 px blocks: edge blocks hold 8 of 16 pixels; out of place and in place), rsu_quantize_mask_rect
     (2, 40, 56), rsu_labels_for_patches (48 px, 16 px patches) and rsu_confusion_counts (n = 5003) against hostio's numpy statements"""
     from road_segmentation_unet_amd import hostio
@@ -1000,7 +1000,7 @@ def test_quantize_labels_confusion():
     A = F.Arena(hu.DEV, [F.f32("m", m[..., 0]), F.out("q", (2, 40, 40), torch.float32), F.state("m_inplace", m[..., 0]),
                          F.f32("m2", m2[..., 0]), F.out("q2", (2, 40, 56), torch.float32), F.state("m2_inplace", m2[..., 0]),
                          F.f32("m3", m3), F.out("lab", (2, 3, 3), torch.int64), F.raw("pred", pred), F.raw("truth", truth),
-                         F.state("counts", np.zeros(4, np.int64))])
+                         F.state("counts", np.zeros(4, np.int64))], placement=placement)
     p = lambda k: hu.ptr(A[k])  # noqa: E731
     st = hu.stream()
     call("rsu_quantize_mask", p("m"), p("q"), 2, 40, 16, 0.25, st)
@@ -1024,7 +1024,7 @@ def test_quantize_labels_confusion():
     np.testing.assert_array_equal(A["counts"].cpu().numpy(), [tp, fp, fn, tn])
 
 
-def test_affine_and_elastic_patches():
+def test_affine_and_elastic_patches(placement="aligned"):
     """rsu_affine_patches and rsu_elastic_patches at their own tests' smallest geometries, the bank's first 38 records (crosses the
     32-record cut): bit for bit against the host mirrors (tests/affine_util.py, tests/elastic_util.py)"""
     from road_segmentation_unet_amd import _lib, hostio
@@ -1037,7 +1037,7 @@ def test_affine_and_elastic_patches():
     _, _, erecs, ehx, ehy = eu.case(Hl, offset, S, P)
     erecs = np.ascontiguousarray(erecs[200:200 + n])
     A = F.Arena(hu.DEV, [F.f32("img", ext), F.raw("lab", np.ascontiguousarray(lab, dtype=np.uint8)), F.out("x", (n, S, S, 3), torch.float32),
-                         F.out("y", (n, P, P), torch.int64), F.out("ex", (n, S, S, 3), torch.float32), F.out("ey", (n, P, P), torch.int64)])
+                         F.out("y", (n, P, P), torch.int64), F.out("ex", (n, S, S, 3), torch.float32), F.out("ey", (n, P, P), torch.int64)], placement=placement)
     p = lambda k: hu.ptr(A[k])  # noqa: E731
     call("rsu_affine_patches", p("img"), p("lab"), recs.ctypes.data_as(ctypes.POINTER(_lib.RsuAffine)), n, ext.shape[0], ext.shape[1], lab.shape[1], S, P,
          p("x"), p("y"), hu.stream())
@@ -1053,7 +1053,7 @@ def test_affine_and_elastic_patches():
 
 
 @pytest.mark.parametrize("S,nrec", [(11, 3), (37, 33)])
-def test_color_jitter(S, nrec):
+def test_color_jitter(S, nrec, placement="aligned"):
     """test_gpu_jitter.test_kernels_equal_the_host_mirror's launch: x in place, the workspace exactly rsu_color_jitter_ws_bytes"""
     from road_segmentation_unet_amd import _lib, hostio
     from tests import jitter_util as ju
@@ -1062,7 +1062,7 @@ def test_color_jitter(S, nrec):
     want = hostio.color_jitter(x, recs)
     nws = lib().rsu_color_jitter_ws_bytes(nrec, S)
     assert nws % 8 == 0 and (x.size * 4) % 512 != 0
-    A = F.Arena(hu.DEV, [F.state("x", x), F.ws("ws", nws // 8, torch.int64)])
+    A = F.Arena(hu.DEV, [F.state("x", x), F.ws("ws", nws // 8, torch.int64)], placement=placement)
     call("rsu_color_jitter", hu.ptr(A["x"]), recs.ctypes.data_as(ctypes.POINTER(_lib.RsuJitter)), nrec, S, hu.ptr(A["ws"]), hu.stream())
     A.check("color_jitter S %d nrec %d" % (S, nrec))
     np.testing.assert_array_equal(_host(A["x"]), want)

@@ -37,7 +37,7 @@ def _launch(A, shape, b, st):
 
 
 @pytest.mark.parametrize("shape,b", CASES, ids=["%s-%d" % (GU.shape_id(s), b) for s, b in CASES])
-def test_graph_entry(shape, b):
+def test_graph_entry(shape, b, placement="aligned"):
     prob = CU.float_bank(shape)
     labels64 = TU.mixed_labels(shape)
     nbytes = int(lib().rsu_graph_ws_bytes(*shape, b))
@@ -46,7 +46,7 @@ def test_graph_entry(shape, b):
     specs += [F.out(n, shape, torch.float32) for n in ("out_pred", "junc_pred", "pred_only", "jpred_only", "no_labels", "jno_labels")]
     specs += [F.out(n, shape, torch.int64) for n in ("out_true", "junc_true", "true_only", "jtrue_only")]
     specs += [F.state("acc", np.zeros(8, np.int64)), F.state("acc_free", np.zeros(8, np.int64)), F.ws("ws", nbytes // 8, dtype=torch.int64)]
-    A = F.Arena(hu.DEV, specs)
+    A = F.Arena(hu.DEV, specs, placement=placement)
     _launch(A, shape, b, hu.stream())
     what = "graph fenced %s, min_branch %d" % (shape, b)
     A.check(what)

@@ -38,7 +38,7 @@ def _launch(A, C, inv, st):
 
 
 @pytest.mark.parametrize("C", HEAD_C)
-def test_focal_heads(C):
+def test_focal_heads(C, placement="aligned"):
     assert NPIX == 3 * 37 * 41 and NPIX % 2 == 1
     rng, act, w, b, labels = _inputs(C)
     pixel_w = _weight_map(rng)
@@ -54,7 +54,7 @@ def test_focal_heads(C):
     specs += [o32("prob_s", NPIX), o32("dsums", 3), o32("prob_e", NPIX), z("esums", 5), F.state("hist", np.zeros((2, 256), np.int64)),
               F.ws("ws_f", L.rsu_head_dice_ws_floats(NPIX, C)), F.ws("ws_d", L.rsu_head_dice_ws_floats(NPIX, C)),
               F.ws("ws_e", L.rsu_head_eval_ws_floats(NPIX, C))]
-    A = F.Arena(hu.DEV, specs)
+    A = F.Arena(hu.DEV, specs, placement=placement)
     _launch(A, C, inv, hu.stream())
     what = "focal heads C=%d" % C
     A.check(what)

@@ -30,7 +30,7 @@ def _launch(A, shape, st):
 
 @pytest.mark.parametrize("kind", ["quant4", "scattered_ignored"])
 @pytest.mark.parametrize("shape", SHAPES, ids=["%dx%dx%d" % s for s in SHAPES])
-def test_lovasz_fwd_and_fwd_bwd(shape, kind):
+def test_lovasz_fwd_and_fwd_bwd(shape, kind, placement="aligned"):
     p, labels = LU.INPUTS[kind](shape)
     if kind == "quant4":
         labels = LU.scattered_ignored(shape)[1]
@@ -41,7 +41,7 @@ def test_lovasz_fwd_and_fwd_bwd(shape, kind):
     z2 = lambda name: F.state(name, np.zeros(2, np.float32))  # noqa: E731
     specs = [F.f32("prob", p), F.raw("labels", labels), F.out("gprob", shape, torch.float32), F.state("gacc", g0), z2("loss_f"), z2("loss_b"),
              z2("loss_a"), F.ws("ws", nbytes // 4, dtype=torch.int32)]
-    A = F.Arena(hu.DEV, specs)
+    A = F.Arena(hu.DEV, specs, placement=placement)
     _launch(A, shape, hu.stream())
     what = "Lovasz fenced %s %s" % (shape, kind)
     A.check(what)

@@ -66,7 +66,7 @@ class _Table:
     """one arena with the four variables, their slots and gradients, the packed copies an update table points at (`u_`: packed once from
     the initial weights), a second set for rsu_pack_* of the new weights (`s_`), the table, and the record of rsu_grad_norm"""
 
-    def __init__(self, adam, var, grads, clip):
+    def __init__(self, adam, var, grads, clip, placement="aligned"):
         _, _, accs, vs, bad = _inputs()
         L = lib()
         self.adam = adam
@@ -81,7 +81,7 @@ class _Table:
         esz = L.rsu_update_table_entry_bytes()
         specs += [F.out("utable", (esz * 4,), torch.uint8), F.f32("g_norm", bad if clip == "nonfinite" else _inputs()[1]["plain"]),
                   F.ws("nws", L.rsu_grad_norm_ws_floats(1003)), F.state("state", np.zeros(8, np.int32))]
-        self.A = A = F.Arena(hu.DEV, specs)
+        self.A = A = F.Arena(hu.DEV, specs, placement=placement)
         self.p = p = lambda k: hu.ptr(A[k])  # noqa: E731
         self.st = st = hu.stream()
         host = ctypes.create_string_buffer(esz * 4)
@@ -162,13 +162,13 @@ def _same_bits(X, Y, names, what):
 @pytest.mark.parametrize("clip", [None, "clip", "nonfinite"], ids=["null", "clip", "nonfinite"])
 @pytest.mark.parametrize("mode", ["l2", "decoupled"])
 @pytest.mark.parametrize("rule", ["momentum", "adam"])
-def test_update_table_decay(rule, mode, clip):
+def test_update_table_decay(rule, mode, clip, placement="aligned"):
     """rsu_update_table_run_decay / rsu_update_table_run_adam_decay (module docstring)"""
     adam, m = rule == "adam", D.L2 if mode == "l2" else D.DECOUPLED
     var, grads, accs, vs, _ = _inputs()
     decay = float(f32(LAMBDA)) if m == D.L2 else float(f32(LR) * f32(LAMBDA))
     what = "update table decay, %s %s %s" % (rule, mode, clip)
-    T = _Table(adam, var, grads, clip)
+    T = _Table(adam, var, grads, clip, placement)
     A = T.A
     state_before = A["state"].clone()
     assert T.decay_entry(decay, m, T.state_ptr(clip)) == 0, what
@@ -193,7 +193,7 @@ def test_update_table_decay(rule, mode, clip):
         lo, hi, _ = A.place["u_" + k]
         assert not torch.equal(A.mem[lo:hi], T.before[lo:hi]), what + ": the update pass left the old copy: " + k
     # 3. the plain range: the bits of the existing entry on the same inputs (U: the undecayed run, also the yardstick of 7.)
-    U = _Table(adam, var, grads, clip)
+    U = _Table(adam, var, grads, clip, placement)
     U.run_existing(clip)
     U.A.check(what + ": undecayed run")
     _same_bits(T, U, [s + "plain" for s in T.slots()], what + ": plain range against the existing entry")
@@ -202,14 +202,14 @@ def test_update_table_decay(rule, mode, clip):
     if m == D.DECOUPLED:
         # 4. the existing entry on weights pre-decayed on the host: w - f32(d) * w, two float32 roundings
         pre = {k: (D.decayed_weights(var[k], decay) if k in DECAYS else var[k]) for k in KEYS}
-        R = _Table(adam, pre, grads, clip)
+        R = _Table(adam, pre, grads, clip, placement)
         R.run_existing(clip)
         R.A.check(what + ": reference run")
         _same_bits(T, R, [s + k for k in KEYS for s in T.slots()] + ["u_" + k for k in PACK_KEYS], what + ": against the pre-decayed run")
     elif adam:
         # 5. the existing Adam entry with gscale = 1 on the gradient f32(f32(gscale' g) + f32(lambda w)); the plain range: f32(gscale' g)
         g1 = {k: D.l2_gradient(var[k], grads[k], gs, decay, decays=k in DECAYS) for k in KEYS}
-        R = _Table(adam, var, g1, None)
+        R = _Table(adam, var, g1, None, placement)
         R.run_existing(None, gscale=1.0)
         R.A.check(what + ": reference run")
         _same_bits(T, R, [s + k for k in KEYS for s in T.slots()] + ["u_" + k for k in PACK_KEYS], what + ": against the transformed gradient")

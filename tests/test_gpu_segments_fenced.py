@@ -40,7 +40,7 @@ def _launch(A, shape, st):
 
 
 @pytest.mark.parametrize("shape,kind", CASES, ids=["%s-%s" % (SU.shape_id(s), k) for s, k in CASES])
-def test_segments_entry(shape, kind):
+def test_segments_entry(shape, kind, placement="aligned"):
     if kind == "floats":
         prob, labels64 = CU.float_bank(shape), TU.mixed_labels(shape)
     else:
@@ -52,7 +52,7 @@ def test_segments_entry(shape, kind):
     specs += [F.out(n, shape, torch.int32) for n in MAPS]
     specs += [F.out(n, (shape[0], 4), torch.int32) for n in ("counts", "counts2", "counts_free")]
     specs += [F.state("acc", np.zeros((2, 8), np.int64)), F.state("acc_free", np.zeros((2, 8), np.int64)), F.ws("ws", nbytes // 8, dtype=torch.int64)]
-    A = F.Arena(hu.DEV, specs)
+    A = F.Arena(hu.DEV, specs, placement=placement)
     fill = {n: A[n].cpu().numpy().copy() for n in TABLES}
     _launch(A, shape, hu.stream())
     what = "segments fenced %s, %s" % (shape, kind)

@@ -32,7 +32,7 @@ def _launch(A, shape, iters, st):
 
 
 @pytest.mark.parametrize("shape,iters", CASES, ids=["%s-%d" % (TU.shape_id(s), i) for s, i in CASES])
-def test_thin_entry(shape, iters):
+def test_thin_entry(shape, iters, placement="aligned"):
     prob = CU.float_bank(shape)
     labels64 = TU.mixed_labels(shape)
     nbytes = int(lib().rsu_thin_ws_bytes(*shape, iters))
@@ -42,7 +42,7 @@ def test_thin_entry(shape, iters):
     specs += [F.out(n, shape, torch.int64) for n in ("skel_true", "true_only")]
     specs += [F.out(n, (shape[0], 2), torch.int32) for n in ("info", "info_pred", "info_free")]
     specs += [F.state("acc", np.zeros(4, np.int64)), F.ws("ws", nbytes // 8, dtype=torch.int64)]
-    A = F.Arena(hu.DEV, specs)
+    A = F.Arena(hu.DEV, specs, placement=placement)
     _launch(A, shape, iters, hu.stream())
     what = "thin fenced %s, %d iterations" % (shape, iters)
     A.check(what)
