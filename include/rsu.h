@@ -50,6 +50,14 @@
  *   written; NULL keeps the meaning it has at the entry; at the stated alignment -- and at no larger one -- every entry is exact:
  *   tests/test_align_limits_host.py holds each entry to its refusal, tests/test_gpu_aligned_min.py runs each inside the arena with every
  *   buffer at 256 k + its number. Nothing else is assumed: a buffer that follows another back to back needs only its own alignment.
+ *   Workspaces: a `ws` or `kws` argument, in this header and in the family headers, need not be cleared and holds nothing between
+ *   calls -- the launches of ONE call initialise every word of it that they read, and no result depends on what it held before, be it
+ *   zeros, ones, or what another entry, another layer or another batch left there (one buffer may serve them all in turn, as UNet.ws
+ *   does). The exceptions are named where they occur: rsu_cldice_bwd reads what rsu_cldice_fwd wrote (rsu_cldice.h), and a group's ws
+ *   belongs to the group from rsu_wgrad_group_run to the end of its stream work. Sums that travel between two calls do so in arguments
+ *   of their own (dice_sums, sums, state), never in a workspace; an accumulator the caller zeroes (loss_sum, acc, sums, hist) is no
+ *   workspace. tests/test_gpu_ws_history.py runs every entry that takes a workspace with it zeroed, filled with 0xFF and filled with the
+ *   rolled leftover of an earlier call, and asks for the same bytes in every output each time.
  */
 #ifndef RSU_H_
 #define RSU_H_
@@ -188,7 +196,7 @@ int rsu_color_conv_first_fwd(const float* x, const float* w0, const float* b0, c
  * rows 9..11 gm[t][cj][co] = sum_pix m[pix+t][cj] dz[pix][co]. With W1 = this conv's kernel:
  *   d(color_space_adjust/kernel)[ci][cj] = 1/keep * sum_{t,co} W1[t][cj][co] gxc[t][3*ci+cj][co]
  *   d(color_space_adjust/bias)[cj]       = 1/keep * sum_{t,co} W1[t][cj][co] gm[t][cj][co]
- * ws: float workspace of rsu_conv_first_bwd_ws_floats() floats. */
+ * ws: float workspace of rsu_conv_first_bwd_ws_floats() floats. It need not be cleared and holds nothing between calls. */
 size_t rsu_conv_first_bwd_ws_floats(int Cout);
 /* db (optional): BiasAddGrad of this conv, computed by the same launch. limit: max(in16 = N*H*W*32, dz = N*(H-2d)*(W-2d)*Cout*2) bytes
  * (igemm_wg1's own bound of 2^28 output pixels lies beyond it: 2^28 pixels of in16 are 8 GiB). */
@@ -211,7 +219,7 @@ int rsu_head_fwd(const void* act, const float* w, const float* b, float* prob, f
  * labels int64 [npix] in {0,1}; loss_sum f32[1] (+= sum of per-pixel losses; caller zeroes it);
  * dact bf16 [npix][C] = gradient wrt the PRE-activation of the last conv2 (ReLU mask applied),
  * scaled by inv_count (1 / global pixel count); dw f32 [C][2], db f32 [2] (overwritten).
- * ws: rsu_head_ws_floats(npix, C) floats. */
+ * ws: rsu_head_ws_floats(npix, C) floats. It need not be cleared and holds nothing between calls. */
 size_t rsu_head_ws_floats(long npix, int C);
 /* align (rsu_head_fwd_bwd): act 16, w 4, b 4, labels 8, prob 4, loss_sum 4, dact 16, dw 4, db 4, ws 4. */
 int rsu_head_fwd_bwd(const void* act, const float* w, const float* b, const int64_t* labels, float* prob,
@@ -228,7 +236,7 @@ int rsu_head_fwd_bwd(const void* act, const float* w, const float* b, const int6
  * weight_sum, whatever its pixel_w holds (it is never multiplied). dact, dw, db, prob, inv_count, C and the error codes are
  * rsu_head_fwd_bwd's. Same grid, pixel-to-thread mapping and fixed summation orders: results are deterministic, and with every
  * omega_p == 1 (class_w {1, 1} or NULL, pixel_w all ones or NULL, labels in {0,1}) they equal rsu_head_fwd_bwd's bit for bit.
- * ws: rsu_head_w_ws_floats(npix, C) floats (one more partial per workgroup than rsu_head_ws_floats). */
+ * ws: rsu_head_w_ws_floats(npix, C) floats (one more partial per workgroup than rsu_head_ws_floats). It need not be cleared and holds nothing between calls. */
 size_t rsu_head_w_ws_floats(long npix, int C);
 /* align (rsu_head_fwd_bwd_w): act 16, w 4, b 4, labels 8, class_w 4, pixel_w 4, prob 4, loss_sum 4, weight_sum 4, dact 16, dw 4, db 4, ws 4. */
 int rsu_head_fwd_bwd_w(const void* act, const float* w, const float* b, const int64_t* labels, const float* class_w,
@@ -252,7 +260,9 @@ int rsu_head_fwd_bwd_w(const void* act, const float* w, const float* b, const in
  * own batch's Dice, and dice_scale = lambda / world keeps the SUM all-reduce of gradients the gradient of the mean of the ranks' terms).
  * An ignored pixel's dact row is +0 and it adds nothing to any sum, whatever its pixel_w holds. Errors: rsu_head_fwd_bwd_w's, plus
  * RSU_EINVAL for dice_sums == NULL, a smooth that is not finite and > 0, a dice_scale that is not finite and >= 0 -- returned before
- * anything is launched or written. ws: rsu_head_dice_ws_floats(npix, C) floats, enough for either call. */
+ * anything is launched or written. ws: rsu_head_dice_ws_floats(npix, C) floats, enough for either call.
+ * It need not be cleared and holds nothing between calls, not between these two either: rsu_head_dice_sums writes dice_sums = {I, P, Y},
+ * rsu_head_fwd_bwd_dice reads them from there; each call's partial sums live in ws from its first launch to its second. */
 size_t rsu_head_dice_ws_floats(long npix, int C);
 /* align (rsu_head_dice_sums): act 16, w 4, b 4, labels 8, pixel_w 4, prob 4, dice_sums 4, ws 4. */
 int rsu_head_dice_sums(const void* act, const float* w, const float* b, const int64_t* labels, const float* pixel_w, float* prob,
@@ -276,7 +286,7 @@ int rsu_head_fwd_bwd_dice(const void* act, const float* w, const float* b, const
  * so every output is deterministic. With a threshold t = k / RSU_EVAL_BINS, "p >= t" is "bin >= k" exactly: the confusion counts at
  * every such threshold follow from hist on the host. Errors: RSU_EINVAL for a NULL act, w, b, labels, prob, sums, hist or ws, a C
  * the other heads refuse, npix < 1 -- returned before anything is launched or written.
- * ws: rsu_head_eval_ws_floats(npix, C) floats (0 for a refused C or npix). */
+ * ws: rsu_head_eval_ws_floats(npix, C) floats (0 for a refused C or npix). It need not be cleared and holds nothing between calls. */
 #define RSU_EVAL_BINS 256
 size_t rsu_head_eval_ws_floats(long npix, int C);
 /* align (rsu_head_eval): act 16, w 4, b 4, labels 8, class_w 4, pixel_w 4, prob 4, sums 4, hist 8, ws 4. */
@@ -295,6 +305,7 @@ int rsu_head_eval(const void* act, const float* w, const float* b, const int64_t
  *   an IGNORED pixel (any other label): out = +0, d2 = RSU_BORDER_D2_INF; it is never anyone's "other class" and its mul is never read
  *   (selection, not multiplication, as everywhere in the head family).
  * out f32 [N][H][W]; d2 int32 [N][H][W] or NULL; ws: rsu_border_map_ws_bytes(N, H, W) bytes (0 for a refused size).
+ * It need not be cleared and holds nothing between calls (the column pass writes every word the row pass reads).
  * Exact separable transform in integer arithmetic (a column pass into ws, a row pass from LDS): d2 is exact and no output depends on the
  * grid, the wave order or the box; exp is a fixed sequence of float32 operations (no library call), which hostio.border_weight_map
  * restates: out is reproducible bit for bit on the host. Two launches on `stream`, no host synchronisation, no allocation, no atomics.
@@ -328,7 +339,8 @@ int rsu_conv2d_fwd(const rsu_src_t* srcs, int nsrc, const void* packed_fwd, cons
  * never split). The geometry includes the batch: a layer splits into more slices at N = 1 than at N = 4, so the deep layers of one image
  * associate their fp32 sums differently in batches of different size (the distance is pinned per layer in tests/test_gpu_ops.py; making
  * the rule batch-independent cost the N = 4 step 12-14 %, profiles/r05/abenv_perimg_*.txt). The workspace must not be shared with a launch
- * running concurrently on another stream: the host keeps one per stream that issues conv launches. */
+ * running concurrently on another stream: the host keeps one per stream that issues conv launches. kws need not be cleared and holds
+ * nothing between calls: the first launch writes every partial sum the second reads, and one buffer serves every layer in turn. */
 size_t rsu_conv_splitk_ws_floats(void);
 /* align (rsu_conv2d_fwd_k): srcs host, srcs.ptr 16, packed_fwd 16, bias 4, y 16, kws 16. */
 int rsu_conv2d_fwd_k(const rsu_src_t* srcs, int nsrc, const void* packed_fwd, const float* bias, void* y, int N,
@@ -358,7 +370,7 @@ int rsu_conv2d_bwd_data(const void* dz, const void* packed_bwd, void* dx, const 
                         rsu_stream_t stream);
 /* Conv2DBackpropFilter for the input channels held by `src` (rows [ci_off, ci_off+src.C) of dw):
  * dw f32 HWIO [3][3][Cin_total][Cout] (only those rows are written). (Ho, Wo) = size of dz.
- * ws: rsu_conv2d_bwd_weight_ws_floats() floats of scratch (split-K slabs). */
+ * ws: rsu_conv2d_bwd_weight_ws_floats() floats of scratch (split-K slabs). It need not be cleared and holds nothing between calls. */
 size_t rsu_conv2d_bwd_weight_ws_floats(int Cin_total, int src_C, int Cout);
 /* db (optional, f32 [Cout]): BiasAddGrad = sum over pixels of dz, computed by the same launch (one extra MFMA per
  * 32-pixel step); pass it with ONE of the sources of a concatenated input, NULL with the others.
@@ -379,7 +391,9 @@ int rsu_conv2d_bwd_weight(const rsu_src_t* src, const void* dz, float* dw, float
  * rsu_wgrad_group_run after every backward pass. job.kind selects the fields' meaning:
  *   RSU_WGRAD_CONV3X3  as rsu_conv2d_bwd_weight: src = the input window, dz [N][Ho][Wo][Cout], dw HWIO rows [ci_off, ci_off+src.C), db optional
  *   RSU_WGRAD_CONVT2X2 as rsu_convT2x2_bwd_weight: src = {x, H, W, Cin, 0, 0}, dz = dy [N][2H][2W][Cout], dw = dK, db optional
- * ws: rsu_wgrad_group_ws_floats() floats of scratch, owned by the group between a run and the end of its stream work. */
+ * ws: rsu_wgrad_group_ws_floats() floats of scratch, owned by the group between a run and the end of its stream work. rsu_wgrad_group_plan
+ * only stores the address; every run writes the slabs its reduce launch reads. It need not be cleared and holds nothing between runs:
+ * other launches may use it in between. */
 #define RSU_WGRAD_CONV3X3 0
 #define RSU_WGRAD_CONVT2X2 1
 #define RSU_WGRAD_GROUP_MAX 16
@@ -398,7 +412,7 @@ size_t rsu_wgrad_group_ws_floats(void);
 int rsu_wgrad_group_plan(const rsu_wgrad_job_t* jobs, int njobs, float* ws, int N, int ncu, void* host_table);
 /* align (rsu_wgrad_group_run): host_table host, dev_table 8. */
 int rsu_wgrad_group_run(const void* host_table, const void* dev_table, rsu_stream_t stream);
-/* BiasAddGrad: db[c] = sum over npix of dz[pix][c]. ws: rsu_bias_grad_ws_floats(npix, C) floats. */
+/* BiasAddGrad: db[c] = sum over npix of dz[pix][c]. ws: rsu_bias_grad_ws_floats(npix, C) floats. It need not be cleared and holds nothing between calls. */
 /* limit: dz, npix * C * 2 bytes. */
 size_t rsu_bias_grad_ws_floats(long npix, int C);
 /* align (rsu_bias_grad): dz 16, db 4, ws 4. */
@@ -453,7 +467,7 @@ int rsu_convT2x2_fwd(const void* x, const void* packed_fwd, const float* bias, v
 int rsu_convT2x2_bwd_data(const void* dy, const void* packed_bwd, void* dx, const void* relu_src, float out_scale,
                           int N, int H, int W, int Cin, int Cout, int ncu, rsu_stream_t stream);
 /* dK f32 [2][2][Cout][Cin] and, when db != NULL, db f32 [Cout] = sum over all pixels of dy (BiasAddGrad of the transposed
- * conv, unet.py:72) from the same launch; ws: rsu_convT2x2_bwd_weight_ws_floats() floats */
+ * conv, unet.py:72) from the same launch; ws: rsu_convT2x2_bwd_weight_ws_floats() floats. It need not be cleared and holds nothing between calls. */
 size_t rsu_convT2x2_bwd_weight_ws_floats(int Cin, int Cout);
 /* align (rsu_convT2x2_bwd_weight): x 16, dy 16, dK 16, db 16, ws 16. */
 int rsu_convT2x2_bwd_weight(const void* x, const void* dy, float* dK, float* db, float* ws, int N, int H, int W,
@@ -527,7 +541,8 @@ int rsu_update_table_run_adam(const void* dev_table, int nentries, int total_blo
  * fixed order, a fixed tree adds the lanes, and the workgroup writes one partial sum and one "saw inf or nan" word. Pass 2, one
  * workgroup, adds the partials in double in a fixed order and one thread writes the record. The same g, n and max_norm therefore
  * give the same bits on every call, device and rank. Only g[0, n) is read (the n & 3 scalars behind the last float4 singly).
- * ws: rsu_grad_norm_ws_floats(n) floats (2 per workgroup; 0 for n < 1), written in full, nothing behind them.
+ * ws: rsu_grad_norm_ws_floats(n) floats (2 per workgroup; 0 for n < 1), written in full, nothing behind them. It need not be
+ * cleared and holds nothing between calls: what the calls share is `state`.
  * Errors, returned before anything is launched: RSU_EINVAL for a NULL g, ws or state, n < 1, a max_norm that is not > 0 (nan included;
  * +inf is allowed: the call then only measures and guards), a g that is not 16-byte aligned, a ws or state that is not 4-byte aligned. */
 #define RSU_CLIP_STATE_BYTES 32
@@ -742,7 +757,8 @@ int rsu_elastic_patches(const float* images, const uint8_t* labels, const rsu_el
  * Launches on `stream`, per RSU_JITTER_MAX_LAUNCH records (they travel as kernel arguments): one that sums (only when a record of the
  * launch has a non-zero k[]) and one that applies; no memset, copy, allocation, atomics or synchronisation. ws: rsu_color_jitter_ws_bytes(nrec,
  * S) bytes (0 for nrec or S below 1), 8-byte aligned: three int64 partial sums per 4096-pixel share of a sample, for the records of one
- * launch -- every launch of a call re-uses it, stream order keeps them apart -- written before they are read, nothing to zero. A
+ * launch -- every launch of a call re-uses it, stream order keeps them apart -- written before they are read, nothing to zero: it need not be
+ * cleared and holds nothing between calls. A
  * sample's output depends on its own record alone, not on its neighbours or on where the record list is cut.
  * Errors, returned before anything is launched or written: RSU_EINVAL for a NULL x or recs, nrec or S below 1, a record field that is
  * not finite, |a| or |k| above 64, sigma outside [0, 1], a NULL ws while some record has a non-zero k[], a ws that is not 8-byte aligned;

@@ -33,9 +33,14 @@ extern "C" {
  *
  * rsu_cldice_fwd: skel_p, skel_y [B][H][W] are overwritten; sums[0..3] += {A, Bp, Cc, Dy} (the caller zeroes). Two launches whatever
  *   iters: the tiled skeleton kernel and a final kernel that adds the tiles' partial sums in a fixed order. ws: rsu_cldice_ws_floats floats.
+ *   ws need not be cleared and the forward reads nothing it did not write itself. It WRITES, for the backward: the erosion levels
+ *   E_1 .. E_{iters+1} and the skeleton states S_0 .. S_{iters-1} of the prob map, [2 iters + 1][B H W] floats, and behind them the
+ *   tiles' partial sums, which only its own final kernel reads.
  * rsu_cldice_bwd: gprob [B][H][W] is overwritten with d (scale (1 - clD)) / d p, with the sums READ from `sums` as they stand (what the
  *   forward left, or what a host made of it: nothing is recomputed). One launch whatever iters; no atomics, a fixed order of every sum.
- *   It reads what rsu_cldice_fwd left in ws for the same prob, labels and iters: the caller leaves ws untouched between the two.
+ *   It reads what rsu_cldice_fwd left in ws for the same prob, labels and iters -- those [2 iters + 1] maps, nothing else -- and writes
+ *   nothing to it: the caller leaves ws untouched between the two. This is the one workspace that carries data from one entry to another;
+ *   behind the backward, and in front of the next forward, it holds nothing.
  *   skel_p is part of the signature for symmetry and is not read.
  * No host synchronisation anywhere. Errors, returned before anything is launched or written: RSU_EINVAL for a NULL pointer, B, H, W < 1,
  * B * H * W >= 2^31, iters outside [0, RSU_CLDICE_MAX_ITERS], a smooth that is not finite and > 0, a scale that is not finite and >= 0. */
@@ -52,7 +57,7 @@ int rsu_cldice_bwd(const float* prob, const int64_t* labels, const float* skel_p
  * gprob[p] * p0 p1 is added to dlogit 1 and taken from dlogit 0 (p1 = softmax(z)[1]) in front of dact, dw and db. An ignored pixel's
  * gprob is not looked at (its dact row is +0). loss_sum and weight_sum keep their meaning: the cross-entropy part only. gamma == 0 is
  * allowed and gives the cross-entropy lines of rsu_head_fwd_bwd_w / rsu_head_fwd_bwd_dice; every other argument, the workspace
- * (rsu_head_dice_ws_floats) and every other error are rsu_head_fwd_bwd_focal's; a NULL gprob is RSU_EINVAL. With gprob all zero every
+ * (rsu_head_dice_ws_floats; it need not be cleared and holds nothing between calls) and every other error are rsu_head_fwd_bwd_focal's; a NULL gprob is RSU_EINVAL. With gprob all zero every
  * output equals that entry's as numbers. */
 /* align (rsu_head_fwd_bwd_aux): act 16, w 4, b 4, labels 8, class_w 4, pixel_w 4, dice_sums 4, prob 4, loss_sum 4, weight_sum 4, dact 16, dw 4,
  * db 4, ws 4, gprob 4. */

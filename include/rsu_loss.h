@@ -33,13 +33,14 @@ extern "C" {
  *
  * rsu_head_fwd_bwd_focal: the training head. += loss_sum[0] receives sum omega F CE and weight_sum[0] (may be NULL) sum omega -- the
  * caller zeroes both, as for rsu_head_fwd_bwd_w; prob [npix], dact [npix][C] bf16 (through the ReLU in front of the head), dw [C][2] and
- * db [2] are overwritten. ws: rsu_head_dice_ws_floats(npix, C) floats.
+ * db [2] are overwritten. ws: rsu_head_dice_ws_floats(npix, C) floats. It need not be cleared and holds nothing between calls (the Dice
+ * sums of pass A arrive in dice_sums, not in ws).
  *   dice_sums == NULL: the focal head alone; dice_scale and smooth are not looked at.
  *   dice_sums != NULL: pass B of the soft-Dice head behind an unchanged rsu_head_dice_sums: the Dice gradient of rsu_head_fwd_bwd_dice is
  *   added to dlogit exactly as there (neither the class weights nor F enter it); dice_sums is read only.
  * rsu_head_eval_focal: the evaluation head, rsu_head_eval with sums[0] += sum omega F CE: sums[1..4] += {sum omega, I, P, Y} and hist
  * [2][RSU_EVAL_BINS] receive what rsu_head_eval adds, bit for bit; the caller zeroes the accumulators before the first batch.
- * ws: rsu_head_eval_ws_floats(npix, C) floats. From zeroed accumulators sums[0] has the bits of the training entry's loss_sum.
+ * ws: rsu_head_eval_ws_floats(npix, C) floats. It need not be cleared and holds nothing between calls. From zeroed accumulators sums[0] has the bits of the training entry's loss_sum.
  * gamma == 0 is decided on the host: the call launches exactly what rsu_head_fwd_bwd_w / rsu_head_fwd_bwd_dice / rsu_head_eval launch.
  * Errors, returned before anything is launched or written: RSU_EINVAL for a gamma that is not finite or is negative, and for whatever
  * the corresponding entry of rsu.h refuses (a NULL among act, w, b, labels, prob, loss_sum / sums, hist, dact, dw, db, ws; a C that is

@@ -45,6 +45,7 @@ extern "C" {
  * rsu_lovasz_fwd: loss_sum[0] += sum_b L_b, loss_sum[1] += B (the caller zeroes them). The evaluation's entry.
  * rsu_lovasz_fwd_bwd: the same, and gprob [B][H][W] written or accumulated as above.
  * ws: rsu_lovasz_ws_bytes bytes, 8-byte aligned: B * Pn keys of 8 bytes and, per tile of 4096 keys, two int32 counts and one float sum.
+ * It need not be cleared and holds nothing between calls.
  * No host synchronisation; nothing is written outside gprob, loss_sum[0..1] and ws. Errors, returned before anything is launched or
  * written: RSU_EINVAL for a NULL pointer, B, H, W < 1, H * W > 2^24, B * H * W >= 2^31, a scale that is not finite and >= 0. */
 size_t rsu_lovasz_ws_bytes(int B, int H, int W);   /* 0 for refused arguments */

@@ -9,6 +9,8 @@ byte. Every claim below holds under both placements. In front of and behind ever
 BAND = 1 MiB of pattern; behind a workspace at least the workspace's own size (a size function that is wrong by a factor of two still
 lands inside the arena). The gap between two neighbours is the band behind the first PLUS the band in front of the second, so every
 byte of a gap belongs to exactly one (tensor, side). Outputs start as pattern too: an element a kernel never wrote reads as NaN.
+A workspace starts as pattern unless the case's Placement carries another fill (zeros, ones, or the rolled leftover of an earlier run:
+tests/ws_util.py runs every case under each and asks for byte-identical results).
 
 Arena.check(what), called after the launches of a case, makes one synchronisation and asserts that every band byte still holds the
 pattern (compared as raw integers on the device, reduced to one flag) and that every tensor registered as an input still holds the bytes
@@ -24,6 +26,7 @@ import torch
 PATTERN = 0x7FA5
 BAND = 1 << 20
 ALIGN = 256
+FILLS = ("pattern", "zeros", "ones", "rolled")
 
 _BF16, _F32 = torch.bfloat16, torch.float32
 
@@ -51,11 +54,38 @@ class Placement:
     multiple of m and of nothing larger -- what a caller who places buffers back to back may hand a kernel. A spec's minimum is its element
     size; minima[i] = {spec name: bytes} raises it for the specs of the i-th arena the case builds (tests/align_util.ALIGN by (entry,
     argument): tests/test_gpu_aligned_min.py). Bands, the attribution of gap bytes, check() and poison_outside() are the same under both.
-    The placement keeps the arenas built with it (.arenas), in order."""
+    The placement keeps the arenas built with it (.arenas), in order.
 
-    def __init__(self, mode="aligned", minima=()):
+    fill: what a WORKSPACE payload (kind "ws", nothing else) holds when the case starts. "pattern" (the default: as the bands), "zeros"
+    (every byte 0x00), "ones" (every byte 0xFF: -1 as a signed integer, the maximum as an unsigned one, a NaN with another payload as a
+    float) or "rolled": the bytes snapshots[(arena index, spec name)] -- what the same workspace held after an earlier run of the case
+    (workspaces()) -- rolled by (count // 3) | 1 elements of the spec's element type: real counters, in-range parents, real bit planes
+    and real partial sums, all in the wrong places. Bands, inputs, outputs, states and check() are the same under every fill.
+    Arena.refill(name) puts the fill back into a workspace later on (tests/ws_util.py: in front of every call that receives it)."""
+
+    def __init__(self, mode="aligned", minima=(), fill="pattern", snapshots=None):
         assert mode in ("aligned", "minimum"), mode
+        assert fill in FILLS, fill
         self.mode, self.minima, self.arenas = mode, list(minima), []
+        self.fill, self.snapshots = fill, dict(snapshots or {})
+
+    def workspaces(self):
+        """{(arena index, spec name): the bytes every workspace of the arenas built so far holds now}: the snapshots of a "rolled" run"""
+        return {(i, s.name): A.payload_bytes(s.name).clone() for i, A in enumerate(self.arenas) for s in A.specs if s.kind == "ws"}
+
+    def fill_workspace(self, spec, payload, index):
+        """`payload`: the bytes of workspace `spec` of arena `index` (a uint8 view); "pattern" is Arena.refill's own"""
+        if self.fill == "zeros":
+            payload.zero_()
+        elif self.fill == "ones":
+            payload.fill_(0xFF)
+        elif self.fill == "rolled":
+            key = (index, spec.name)
+            assert key in self.snapshots, "no snapshot of workspace %s of arena %d" % (spec.name, key[0])
+            snap = self.snapshots[key].to(payload.device)
+            assert snap.dtype == torch.uint8 and snap.numel() == payload.numel(), key
+            esz = spec.nbytes // spec.shape[0]
+            payload.copy_(torch.roll(snap.view(-1, esz), roll_shift(spec.shape[0]), 0).reshape(-1))
 
     def shift(self, spec):
         """bytes between the 256-byte boundary and the start of `spec` in the arena that is being built"""
@@ -65,6 +95,11 @@ class Placement:
         m = max(spec.minimum, int(over.get(spec.name, 0)))
         assert 0 < m < ALIGN and m & (m - 1) == 0 and m % spec.minimum == 0, (spec.name, m)
         return m
+
+
+def roll_shift(count):
+    """how far a "rolled" workspace of `count` elements is rolled: odd, about a third of it"""
+    return (count // 3) | 1
 
 
 def _cpu(a, dtype):
@@ -109,8 +144,8 @@ def state(name, a, dtype=None):
 
 
 def ws(name, count, dtype=_F32, band=None):
-    """a WORKSPACE of exactly `count` elements (the advertised size): starts as pattern; the band behind it is at least its own size
-    (`band`: another minimum, for a workspace whose planner checks its need on the host)"""
+    """a WORKSPACE of exactly `count` elements (the advertised size): starts as the placement's fill (pattern by default); the band
+    behind it is at least its own size (`band`: another minimum, for a workspace whose planner checks its need on the host)"""
     return _Spec(name, "ws", dtype, (count,), band=band)
 
 
@@ -156,10 +191,38 @@ class Arena:
                 self.mem[start:end].copy_(s.data.view(torch.uint8).reshape(-1).to(device))
             if s.kind == "in":
                 self.given[s.name] = self.mem[start:end].clone()
+        self.index = len(self.placement.arenas)      # which arena of its placement this is
+        if self.placement.fill != "pattern":
+            for s in self.specs:
+                if s.kind == "ws":
+                    self.refill(s.name)
         self.placement.arenas.append(self)
+
+    def refill(self, name):
+        """workspace `name` as it was when the arena was built: the placement's fill again, whatever the launches since left there
+        (tests/ws_util.py does this in front of every library call that receives the workspace)"""
+        spec = next(s for s in self.specs if s.name == name)
+        assert spec.kind == "ws", name
+        start, end, _ = self.place[name]
+        if self.placement.fill == "pattern":
+            v = self.mem[start:end]         # (the arena's words lie on even offsets: low byte first)
+            if start & 1:
+                v[0] = PATTERN >> 8
+                v = v[1:]
+            even = v.numel() // 2 * 2
+            v[:even].view(torch.int16).fill_(PATTERN)
+            if v.numel() > even:
+                v[even] = PATTERN & 0xFF
+        else:
+            self.placement.fill_workspace(spec, self.mem[start:end], self.index)
 
     def __getitem__(self, name):
         return self.t[name]
+
+    def payload_bytes(self, name):
+        """the payload as the bytes of the arena (a view)"""
+        start, end, _ = self.place[name]
+        return self.mem[start:end]
 
     def nbytes(self, name):
         start, end, _ = self.place[name]

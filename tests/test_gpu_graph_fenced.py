@@ -36,10 +36,7 @@ def _launch(A, shape, b, st):
     call("rsu_skeleton_graph", p("prob"), T, None, b, p("no_labels"), None, p("jno_labels"), None, p("acc_free"), p("ws"), *shape, st)
 
 
-@pytest.mark.parametrize("shape,b", CASES, ids=["%s-%d" % (GU.shape_id(s), b) for s, b in CASES])
-def test_graph_entry(shape, b, placement="aligned"):
-    prob = CU.float_bank(shape)
-    labels64 = TU.mixed_labels(shape)
+def _case(prob, labels64, shape, b, placement):
     nbytes = int(lib().rsu_graph_ws_bytes(*shape, b))
     assert nbytes > 0 and nbytes % 8 == 0
     specs = [F.f32("prob", prob), F.raw("labels64", labels64)]
@@ -63,7 +60,50 @@ def test_graph_entry(shape, b, placement="aligned"):
     assert np.array_equal(got["acc_free"], free[4]) and not free[4][4:].any(), what
 
 
+@pytest.mark.parametrize("shape,b", CASES, ids=["%s-%d" % (GU.shape_id(s), b) for s, b in CASES])
+def test_graph_entry(shape, b, placement="aligned"):
+    _case(CU.float_bank(shape), TU.mixed_labels(shape), shape, b, placement)
+
+
+EARLY_SHAPE = (2, 230, 97)
+
+
+def _theta(m, y0, y1, x0, x1):
+    """a one-pixel rectangle outline with a bar across it: four junctions, no end"""
+    m[y0, x0:x1 + 1] = m[y1, x0:x1 + 1] = m[(y0 + y1) // 2, x0:x1 + 1] = True
+    m[y0:y1 + 1, x0] = m[y0:y1 + 1, x1] = True
+
+
+def early_inputs():
+    """(prob, labels64) at EARLY_SHAPE, for min_branch = MAX_BRANCH (four delete and five regrow launches), whose images and sides end
+    their delete phase at different launches. Image 0, prediction: an outline with a bar across it and a spur of five pixels -- the first
+    delete launch removes the spur, the second finds nothing and leaves a count of 0, the other launches of both phases return at once.
+    Image 0, truth: the same without a spur and a lone line of nine pixels, gone in the first five rounds; the second launch counts 0.
+    Image 1, prediction: a line of 200 pixels, shortened by every round of every delete launch and regrown to its full length. Image 1,
+    truth: an outline with a spur of 40 pixels, deleted by the first three launches; the fourth counts 0 and nothing is regrown. A few
+    labels of image 1 are ignored. tests/test_ws_history_host.py proves this on the host."""
+    pred, true = np.zeros(EARLY_SHAPE, bool), np.zeros(EARLY_SHAPE, bool)
+    _theta(pred[0], 20, 80, 10, 70)
+    pred[0, 81:86, 40] = True
+    _theta(true[0], 100, 180, 20, 90)
+    true[0, 200, 30:39] = True
+    pred[1, 15:215, 50] = True
+    _theta(true[1], 60, 120, 10, 50)
+    true[1, 90, 51:91] = True
+    labels64 = true.astype(np.int64)
+    labels64[1, 200:204, 0:6] = -1
+    labels64[1, 0:3, 90:97] = 2
+    return CU.prob_of(pred), labels64
+
+
+def test_graph_converges_per_image(placement="aligned"):
+    """every image side ends its delete phase at another launch, one regrows and three do not: the counters differ per image, side and
+    launch, so a workspace that holds another call's counters holds a 0 where a launch ran and a count where one returned at once"""
+    prob, labels64 = early_inputs()
+    _case(prob, labels64, EARLY_SHAPE, GU.MAX_BRANCH, placement)
+
+
 # ------------------------------------------------------------------------------------------- the registry (tests/test_graph_host.py)
 # launching entry of include/rsu_graph.h -> the cases that launch it inside an arena (HELPERS: what a case calls it through)
-FENCED = {"rsu_skeleton_graph": ["test_graph_entry"]}
-HELPERS = {"test_graph_entry": (_launch,)}
+FENCED = {"rsu_skeleton_graph": ["test_graph_entry", "test_graph_converges_per_image"]}
+HELPERS = {"test_graph_entry": (_case, _launch), "test_graph_converges_per_image": (_case, _launch)}
