@@ -6,7 +6,6 @@ Data parallelism (new; the reference is single-device): when torch.distributed i
 minibatch, sharded contiguously over ranks; gradients are all-reduced (dist.GradBucketer); predict() shards tiles.
 """
 import contextlib
-import ctypes
 import glob
 import math
 import os
@@ -18,9 +17,9 @@ import torch.distributed as dist
 
 from . import hostio
 from . import images as dimages
-from ._lib import call, lib
-from .hostio import DIST_BINS, DIST_MAX_SIDE, GRAPH_MAX_BRANCH, GRAPH_MAX_SIDE, THIN_MAX_ITERS, THIN_MAX_SIDE, centerline_metrics, graph_metrics, relaxed_metrics
-from .hostio import SEGMENTS_MAX_EDGES, SEGMENTS_MAX_SIDE, segment_metrics
+from . import mask_metrics
+from ._lib import call
+from .hostio import GRAPH_MAX_BRANCH, SEGMENTS_MAX_EDGES, SEGMENTS_MAX_SIDE, THIN_MAX_ITERS, THIN_MAX_SIDE
 from .hostio import road_graph as hostio_road_graph
 from .dist import GradBucketer, micro_indices, shard_indices, tune_overlap  # noqa: F401  (shard_indices: importable from here as before)
 from .pool import BatchUploader, DevicePatchPool, PatchPool
@@ -827,11 +826,7 @@ class ConvolutionalModel:
         self.best_val_f1 = None   # the best validation F1 seen by train() (--save_best keeps that model)
         self.best_val_score = None   # the best validation --save_best_metric (the same figure unless it is relaxed_f1)
         self.last_postprocess_stats = None   # postprocess_masks: the summed stats of its last call (int64 [6])
-        self._cc_acc = self._cc_ws = None    # --validate_components: the four counts and the workspace of rsu_components_pair_count
-        self._dt_acc = self._dt_ws = None    # --validate_distances: the 2 x 64 counters and the workspace of rsu_distance_hist
-        self._cl_acc = self._cl_ws = None    # --validate_centerlines: the 2 x 64 + 4 + 1 counters; the workspaces, skeletons and info
-        self._gr_acc = self._gr_ws = None    # --centerline_min_branch / --validate_junctions: the 8 + 2 x 64 + 4 counters; workspaces, junction masks
-        self._sg_acc = self._sg_ws = None    # --validate_segments: the 16 + 4 counters; the workspace, the two segment tables, the counts
+        self._mask_metrics = None   # evaluate() with a --validate_* mask stage on: their one accumulator and device buffers (mask_metrics.py)
         if self.world > 1:
             self._bucketer = GradBucketer(self.net.flat_g, self.net.n_live)
             self._bucketer.extra_streams = list(self.net.wstreams)
@@ -993,24 +988,10 @@ class ConvolutionalModel:
         all-reduced with the others; zeros with --cldice_weight=0) with "cldice" = cldice_from_sums of them; with --cldice_weight > 0
         "objective" also includes cldice_weight * (1 - cldice). With --lovasz_weight > 0 (only then) also "lovasz", the mean per-image
         Lovasz loss over the set from the all-reduced {sum_b L_b, images} less the padding images (which add exactly 0), and
-        "objective" includes lovasz_weight * lovasz. With --validate_components (only then) one rsu_components_pair_count
-        (rsu_components.h) per chunk on net.prob and net.labels at `threshold` and --component_connectivity; its four integer counts
-        ride last in the same all-reduce and read-back (exact in float64 below 2^53), and the result gains "components_pred" and
-        "components_true" (the predicted and true components summed over the patches, ignored pixels background in both) and
-        "b0_error" = sum |predicted - true| / max(patches with a counted pixel, 1); the padding patches add exactly nothing.
-        With --validate_distances (only then) one rsu_distance_hist (rsu_distance.h) per chunk on net.prob and net.labels at `threshold`,
-        behind the head and the component count; its 128 integer counters ride last in the same all-reduce and read-back (exact in float64
-        below 2^53), and the result gains "dist_hist" (int64 [2, 64]: the predicted road pixels by their distance to the truth, the true
-        ones by theirs to the prediction) and the keys of hostio.relaxed_metrics of it at --relaxed_slack. Distances are per patch: a
-        true road just outside a patch is not seen. The padding patches add exactly nothing.
-        With --validate_centerlines and --centerline_min_branch > 0 or --validate_junctions (only then) one rsu_skeleton_graph
-        (rsu_graph.h) per chunk behind rsu_mask_thin, in place on the two skeletons and before their rsu_distance_hist: the cl_* keys but
-        cldice_hard then describe the pruned centre-lines; with --validate_junctions also one rsu_distance_hist and one
-        rsu_components_pair_count (connectivity 8) on the two junction-pixel masks, and the result gains "jn_hist" (int64 [2, 64]) and
-        the keys of hostio.graph_metrics at --relaxed_slack. Their 8 + 128 + 4 counters ride last in the same read-back.
-        With --validate_centerlines and --validate_segments (only then) one rsu_line_segments (rsu_segments.h) per chunk on the two
-        (pruned) skeletons, --max_segments rows per patch and side; its sixteen counters and the patches' summed counts are kept on the
-        device, ride last of all in the same read-back, and the result gains the keys of hostio.segment_metrics.
+        "objective" includes lovasz_weight * lovasz. With any of --validate_components, --validate_distances and --validate_centerlines
+        (with it --centerline_min_branch, --validate_junctions, --validate_segments), and only then, the integer mask metrics of
+        mask_metrics.MaskMetrics: its launches per chunk behind the head on net.prob and net.labels at `threshold`, its counters last in
+        the same all-reduce and read-back (exact in float64 below 2^53), and the result gains the keys of mask_metrics.decode.
         averaged: None scores the averaged weights when the net has them (--ema_decay), True demands them (ValueError on a net without),
         False forces the raw weights; the device work runs inside net.averaged_weights(), and the result carries "averaged" (bool).
         Training is left as it was: weights, the averages and every packed copy (the exchange of averaged_weights() is undone), optimizer
@@ -1031,28 +1012,9 @@ class ConvolutionalModel:
         try:
             with ctx:
                 net.reset_eval()
-                with_cc = bool(getattr(self._options, "validate_components", False))
-                if with_cc:
-                    self._components_buffers()
-                    self._cc_acc.zero_()
-                with_dt = bool(getattr(self._options, "validate_distances", False))
-                if with_dt:
-                    self._distance_buffers()
-                    self._dt_acc.zero_()
-                with_th = bool(getattr(self._options, "validate_centerlines", False))
-                if with_th:
-                    self._centerline_buffers()
-                    self._cl_acc.zero_()
-                min_branch = int(getattr(self._options, "centerline_min_branch", 0)) if with_th else 0
-                with_jn = with_th and bool(getattr(self._options, "validate_junctions", False))
-                with_gr = min_branch > 0 or with_jn
-                if with_gr:
-                    self._graph_buffers()
-                    self._gr_acc.zero_()
-                with_sg = with_th and bool(getattr(self._options, "validate_segments", False))
-                if with_sg:
-                    self._segment_buffers()
-                    self._sg_acc.zero_()
+                mm = self._ensure_mask_metrics()
+                if mm is not None:
+                    mm.reset()
                 for t0 in range(lo, hi, B):
                     nb = min(B, hi - t0)
                     if nb < B:
@@ -1068,44 +1030,8 @@ class ConvolutionalModel:
                         net.set_pixel_weights(None)
                     net.forward_device(keep=1.0)
                     net.evaluate_device()
-                    if with_cc:
-                        call("rsu_components_pair_count", ctypes.c_void_p(net.prob.data_ptr()), float(threshold),
-                             ctypes.c_void_p(net.labels.data_ptr()), int(self._options.component_connectivity),
-                             ctypes.c_void_p(self._cc_acc.data_ptr()), ctypes.c_void_p(self._cc_ws.data_ptr()), B, net.P, net.P,
-                             ctypes.c_void_p(torch.cuda.current_stream(net.device).cuda_stream))
-                    if with_dt:
-                        call("rsu_distance_hist", ctypes.c_void_p(net.prob.data_ptr()), float(threshold),
-                             ctypes.c_void_p(net.labels.data_ptr()), ctypes.c_void_p(self._dt_acc.data_ptr()),
-                             ctypes.c_void_p(self._dt_ws.data_ptr()), B, net.P, net.P,
-                             ctypes.c_void_p(torch.cuda.current_stream(net.device).cuda_stream))
-                    if with_th:   # both skeletons and the four counts, then the distance histogram of the skeletons
-                        cl = self._cl_ws
-                        st = ctypes.c_void_p(torch.cuda.current_stream(net.device).cuda_stream)
-                        call("rsu_mask_thin", ctypes.c_void_p(net.prob.data_ptr()), float(threshold), ctypes.c_void_p(net.labels.data_ptr()),
-                             int(self._options.centerline_max_iters), ctypes.c_void_p(cl["skel_pred"].data_ptr()),
-                             ctypes.c_void_p(cl["skel_true"].data_ptr()), ctypes.c_void_p(self._cl_acc[2 * DIST_BINS:].data_ptr()),
-                             ctypes.c_void_p(cl["info"].data_ptr()), ctypes.c_void_p(cl["thin"].data_ptr()), B, net.P, net.P, st)
-                        if with_gr:   # prune the two skeletons in place and / or mark their junction pixels; the eight node counts
-                            gr, sp, sl = self._gr_ws, ctypes.c_void_p(cl["skel_pred"].data_ptr()), ctypes.c_void_p(cl["skel_true"].data_ptr())
-                            jp = ctypes.c_void_p(gr["junc_pred"].data_ptr()) if with_jn else None
-                            jt = ctypes.c_void_p(gr["junc_true"].data_ptr()) if with_jn else None
-                            call("rsu_skeleton_graph", sp, 0.5, sl, min_branch, sp if min_branch else None, sl if min_branch else None, jp, jt,
-                                 ctypes.c_void_p(self._gr_acc.data_ptr()), ctypes.c_void_p(gr["graph"].data_ptr()), B, net.P, net.P, st)
-                        call("rsu_distance_hist", ctypes.c_void_p(cl["skel_pred"].data_ptr()), 0.5, ctypes.c_void_p(cl["skel_true"].data_ptr()),
-                             ctypes.c_void_p(self._cl_acc.data_ptr()), ctypes.c_void_p(cl["dist"].data_ptr()), B, net.P, net.P, st)
-                        if with_sg:   # the segments of the two (pruned) skeletons; the patches' counts are summed on the device
-                            sg = self._sg_ws
-                            call("rsu_line_segments", ctypes.c_void_p(cl["skel_pred"].data_ptr()), 0.5, ctypes.c_void_p(cl["skel_true"].data_ptr()),
-                                 int(self._options.max_segments), ctypes.c_void_p(sg["edges_pred"].data_ptr()),
-                                 ctypes.c_void_p(sg["edges_true"].data_ptr()), ctypes.c_void_p(sg["counts"].data_ptr()), None, None, None, None,
-                                 ctypes.c_void_p(self._sg_acc.data_ptr()), ctypes.c_void_p(sg["segments"].data_ptr()), B, net.P, net.P, st)
-                            self._sg_acc[16:] += sg["counts"].sum(dim=0)
-                        self._cl_acc[-1] += (cl["info"] != 0).sum()   # (on the device: no read-back)
-                        if with_jn:   # how far the junction pixels of one side lie from the other's, and the junctions as clusters
-                            call("rsu_distance_hist", jp, 0.5, jt, ctypes.c_void_p(self._gr_acc[8:].data_ptr()),
-                                 ctypes.c_void_p(cl["dist"].data_ptr()), B, net.P, net.P, st)
-                            call("rsu_components_pair_count", jp, 0.5, jt, 8, ctypes.c_void_p(self._gr_acc[8 + 2 * DIST_BINS:].data_ptr()),
-                                 ctypes.c_void_p(gr["comp"].data_ptr()), B, net.P, net.P, st)
+                    if mm is not None:
+                        mm.run(net.prob, net.labels, threshold)
                 sums, hist = net.eval_sums.to(torch.float64), net.eval_hist.clone()
                 with_cl = net.cldice_weight > 0.0
                 if with_cl:   # the four clDice sums ride behind the five of the head: one all-reduce, one read-back
@@ -1113,35 +1039,14 @@ class ConvolutionalModel:
                 with_lv = net.lovasz_weight > 0.0
                 if with_lv:   # and the Lovasz pair {sum_b L_b, images} last
                     sums = torch.cat([sums, net.eval_lovasz_sum.to(torch.float64)])
-                if with_cc:   # and the four component counts behind everything else
-                    sums = torch.cat([sums, self._cc_acc.to(torch.float64)])
-                if with_dt:   # and the 2 x 64 distance counters last of all
-                    sums = torch.cat([sums, self._dt_acc.to(torch.float64)])
-                if with_th:   # and behind them the centre-line counters: 2 x 64 bins, the four counts, the unconverged image sides
-                    sums = torch.cat([sums, self._cl_acc.to(torch.float64)])
-                if with_gr:   # and behind the centre-line counters the graph's: eight node counts, 2 x 64 junction bins, four cluster counts
-                    sums = torch.cat([sums, self._gr_acc.to(torch.float64)])
-                if with_sg:   # and last of all the segments': sixteen counters and the four summed counts
-                    sums = torch.cat([sums, self._sg_acc.to(torch.float64)])
+                if mm is not None:   # and the mask stages' integer counters behind everything else
+                    sums = torch.cat([sums, mm.acc.to(torch.float64)])
                 if self.world > 1:
                     dist.all_reduce(sums)
                     dist.all_reduce(hist)
                 sums, hist = sums.cpu().numpy(), hist.cpu().numpy()   # the one synchronisation
-                sg_sums = sums[-20:] if with_sg else None
-                if with_sg:
-                    sums = sums[:-20]
-                gr_sums = sums[-(2 * DIST_BINS + 12):] if with_gr else None
-                if with_gr:
-                    sums = sums[:-(2 * DIST_BINS + 12)]
-                th_sums = sums[-(2 * DIST_BINS + 5):] if with_th else None
-                if with_th:
-                    sums = sums[:-(2 * DIST_BINS + 5)]
-                dt_sums = sums[-2 * DIST_BINS:] if with_dt else None
-                if with_dt:
-                    sums = sums[:-2 * DIST_BINS]
-                cc_sums = sums[-4:] if with_cc else None
-                if with_cc:
-                    sums = sums[:-4]
+                if mm is not None:
+                    sums, mask_counts = sums[:-mm.acc.numel()], sums[-mm.acc.numel():]
                 lv_sums = sums[-2:] if with_lv else None
                 sums, cl_sums = sums[:5], (sums[5:9] if with_cl else np.zeros(4))
         finally:
@@ -1157,107 +1062,23 @@ class ConvolutionalModel:
         if with_lv:   # the mean over the set's N images: the chunks' padding images have no counted pixel, L_b = 0
             out["lovasz"] = float(lv_sums[0]) / max(N, 1)
             out["objective"] = out["objective"] + net.lovasz_weight * out["lovasz"]
-        if with_cc:
-            out["components_pred"], out["components_true"] = int(cc_sums[0]), int(cc_sums[1])
-            out["b0_error"] = float(cc_sums[2]) / max(float(cc_sums[3]), 1.0)
-        if with_dt:
-            out["dist_hist"] = np.rint(dt_sums).astype(np.int64).reshape(2, DIST_BINS)
-            out.update(relaxed_metrics(out["dist_hist"], int(self._options.relaxed_slack)))
-        if with_th:
-            th = np.rint(th_sums).astype(np.int64)
-            out["cl_hist"] = th[:2 * DIST_BINS].reshape(2, DIST_BINS)
-            out.update(centerline_metrics(out["cl_hist"], th[2 * DIST_BINS:2 * DIST_BINS + 4], int(self._options.relaxed_slack)))
-            out["thin_unconverged"] = int(th[-1])
-        if with_gr:
-            gr = np.rint(gr_sums).astype(np.int64)
-            if min_branch > 0:   # the pruned centre-lines' pixel counts (cldice_hard stays on the unpruned skeletons)
-                out["cl_len_pred"], out["cl_len_true"] = int(gr[0]), int(gr[4])
-            if with_jn:
-                out["jn_hist"] = gr[8:8 + 2 * DIST_BINS].reshape(2, DIST_BINS)
-                out.update(graph_metrics(out["jn_hist"], gr[8 + 2 * DIST_BINS:], gr[:8], int(self._options.relaxed_slack)))
-        if with_sg:
-            sg = np.rint(sg_sums).astype(np.int64)
-            out.update(segment_metrics(sg[:16].reshape(2, 8), sg[16:]))
+        if mm is not None:
+            out.update(mm.decode(mask_counts))
         return out
 
-    def _segment_buffers(self):
-        """the device buffers of --validate_segments, made when evaluate() first needs them: the counters (rsu_line_segments' sixteen
-        and the four summed counts), its workspace, the two segment tables of --max_segments rows per patch and the per-patch counts"""
-        if self._sg_acc is None:
-            net, B, dev = self.net, self.local_batch, self.net.device
-            cap = int(self._options.max_segments)
-            need = int(lib().rsu_segments_ws_bytes(B, net.P, net.P, cap))
-            if need == 0:
-                raise ValueError("--validate_segments: a batch of %d patches of %d x %d pixels is outside rsu_segments.h's limits (sides up "
-                                 "to %d, 16 bytes per pixel below 2 GiB)" % (B, net.P, net.P, SEGMENTS_MAX_SIDE))
-            self._sg_ws = {"segments": torch.zeros(need // 8, dtype=torch.int64, device=dev),
-                           "edges_pred": torch.zeros((B, cap, 8), dtype=torch.int32, device=dev),
-                           "edges_true": torch.zeros((B, cap, 8), dtype=torch.int32, device=dev),
-                           "counts": torch.zeros((B, 4), dtype=torch.int32, device=dev)}
-            self._sg_acc = torch.zeros(20, dtype=torch.int64, device=dev)
-
-    def _graph_buffers(self):
-        """the device buffers of --centerline_min_branch / --validate_junctions, made when evaluate() first needs them: the counters
-        (rsu_skeleton_graph's eight counts, the 2 x 64 bins of the junction pixels' distance histogram, the four cluster counts), the
-        workspace of rsu_skeleton_graph and, for the junctions, the two junction-pixel masks and the workspace of
-        rsu_components_pair_count (rsu_distance_hist re-uses the centre-lines' workspace)"""
-        if self._gr_acc is None:
-            net, B, dev = self.net, self.local_batch, self.net.device
-            need = int(lib().rsu_graph_ws_bytes(B, net.P, net.P, int(self._options.centerline_min_branch)))
-            if need == 0 or B * net.P * net.P * 8 >= 0x7ffffff0:
-                raise ValueError("--centerline_min_branch / --validate_junctions: a batch of %d patches of %d x %d pixels is outside "
-                                 "rsu_graph.h's limits (sides up to %d, the labels below 2 GiB)" % (B, net.P, net.P, GRAPH_MAX_SIDE))
-            self._gr_ws = {"graph": torch.zeros(need // 8, dtype=torch.int64, device=dev)}
-            if bool(self._options.validate_junctions):
-                need_cc = int(lib().rsu_components_ws_bytes(B, net.P, net.P))
-                if need_cc == 0:
-                    raise ValueError("--validate_junctions: a batch of %d patches of %d x %d pixels is outside rsu_components.h's limits"
-                                     % (B, net.P, net.P))
-                self._gr_ws.update({"junc_pred": torch.zeros((B, net.P, net.P), dtype=torch.float32, device=dev),
-                                    "junc_true": torch.zeros((B, net.P, net.P), dtype=torch.int64, device=dev),
-                                    "comp": torch.zeros(need_cc // 4, dtype=torch.int32, device=dev)})
-            self._gr_acc = torch.zeros(2 * DIST_BINS + 12, dtype=torch.int64, device=dev)
-
-    def _centerline_buffers(self):
-        """the device buffers of --validate_centerlines, made when evaluate() first needs them: the counters (the 2 x 64 bins of the
-        skeletons' distance histogram, rsu_mask_thin's four counts, the unconverged image sides), the two skeletons, info and the
-        workspaces of rsu_mask_thin and rsu_distance_hist"""
-        if self._cl_acc is None:
-            net, B = self.net, self.local_batch
-            iters = int(self._options.centerline_max_iters)
-            need, need_dt = int(lib().rsu_thin_ws_bytes(B, net.P, net.P, iters)), int(lib().rsu_distance_ws_bytes(B, net.P, net.P))
-            if need == 0 or need_dt == 0 or B * net.P * net.P * 8 >= 0x7ffffff0:
-                raise ValueError("--validate_centerlines: a batch of %d patches of %d x %d pixels is outside rsu_thin.h's limits (sides "
-                                 "up to %d, the labels below 2 GiB)" % (B, net.P, net.P, THIN_MAX_SIDE))
-            dev = net.device
-            self._cl_ws = {"skel_pred": torch.zeros((B, net.P, net.P), dtype=torch.float32, device=dev),
-                           "skel_true": torch.zeros((B, net.P, net.P), dtype=torch.int64, device=dev),
-                           "info": torch.zeros((B, 2), dtype=torch.int32, device=dev),
-                           "thin": torch.zeros(need // 8, dtype=torch.int64, device=dev),
-                           "dist": torch.zeros(need_dt // 4, dtype=torch.int32, device=dev)}
-            self._cl_acc = torch.zeros(2 * DIST_BINS + 5, dtype=torch.int64, device=dev)
-
-    def _distance_buffers(self):
-        """the device buffers of --validate_distances, made when evaluate() first needs them: the 2 x 64 counters and the workspace"""
-        if self._dt_acc is None:
-            net = self.net
-            need = int(lib().rsu_distance_ws_bytes(self.local_batch, net.P, net.P))
-            if need == 0 or self.local_batch * net.P * net.P * 8 >= 0x7ffffff0:
-                raise ValueError("--validate_distances: a batch of %d patches of %d x %d pixels is outside rsu_distance.h's limits (sides "
-                                 "up to %d, the labels below 2 GiB)" % (self.local_batch, net.P, net.P, DIST_MAX_SIDE))
-            self._dt_acc = torch.zeros(2 * DIST_BINS, dtype=torch.int64, device=net.device)
-            self._dt_ws = torch.zeros(need // 4, dtype=torch.int32, device=net.device)
-
-    def _components_buffers(self):
-        """the device buffers of --validate_components, made when evaluate() first needs them: the four counts and the workspace"""
-        if self._cc_acc is None:
-            net = self.net
-            need = int(lib().rsu_components_ws_bytes(self.local_batch, net.P, net.P))
-            if need == 0:
-                raise ValueError("--validate_components: a batch of %d patches of %d x %d pixels is outside rsu_components.h's limits"
-                                 % (self.local_batch, net.P, net.P))
-            self._cc_acc = torch.zeros(4, dtype=torch.int64, device=net.device)
-            self._cc_ws = torch.zeros(need // 4, dtype=torch.int32, device=net.device)
+    def _ensure_mask_metrics(self):
+        """the owner of the mask stages' device buffers (mask_metrics.MaskMetrics), made when evaluate() first needs it; None while no
+        --validate_* flag of its stages is on: no call, no buffer, no key"""
+        opts = self._options
+        flags = mask_metrics.Flags.of(opts)
+        if not flags.any:
+            return None
+        if self._mask_metrics is None or self._mask_metrics.flags != flags:
+            self._mask_metrics = mask_metrics.MaskMetrics(
+                flags, self.net.device, self.local_batch, self.net.P, connectivity=getattr(opts, "component_connectivity", 8),
+                max_iters=getattr(opts, "centerline_max_iters", 64), max_segments=getattr(opts, "max_segments", 4096),
+                relaxed_slack=getattr(opts, "relaxed_slack", 0))
+        return self._mask_metrics
 
     def _validate(self, validation, step):
         """one validation pass inside train(): evaluate (the averaged weights with --ema_decay), print and log on rank 0, keep the best model
@@ -1620,16 +1441,13 @@ class ConvolutionalModel:
     def quantize_mask(self, masks, threshold, patch_size):
         """images.quantize_mask (images.py:256-266) on the device: masks [n, H, W, 1] float -> same shape, every patch_size block
         overwritten with its label mean(mask >= 0.5) > threshold (a block cut by the image's edge: over the pixels it holds)"""
-        import ctypes
         a = np.asarray(masks)
         t = torch.as_tensor(np.ascontiguousarray(a[..., 0], dtype=np.float32)).to(self.net.device)
-        st = ctypes.c_void_p(torch.cuda.current_stream(self.net.device).cuda_stream)
+        p, st = mask_metrics.ptr(t), mask_metrics.stream(self.net.device)
         if t.shape[1] == t.shape[2]:
-            call("rsu_quantize_mask", ctypes.c_void_p(t.data_ptr()), ctypes.c_void_p(t.data_ptr()), t.shape[0], t.shape[1], int(patch_size),
-                 float(threshold), st)
+            call("rsu_quantize_mask", p, p, t.shape[0], t.shape[1], int(patch_size), float(threshold), st)
         else:
-            call("rsu_quantize_mask_rect", ctypes.c_void_p(t.data_ptr()), ctypes.c_void_p(t.data_ptr()), t.shape[0], t.shape[1], t.shape[2],
-                 int(patch_size), float(threshold), st)
+            call("rsu_quantize_mask_rect", p, p, t.shape[0], t.shape[1], t.shape[2], int(patch_size), float(threshold), st)
         return t.cpu().numpy()[..., None].astype(a.dtype)
 
     def postprocess_masks(self, masks, threshold=0.5):
@@ -1647,17 +1465,13 @@ class ConvolutionalModel:
         if a.ndim != 4 or a.shape[3] != 1:
             raise ValueError("postprocess_masks: masks must be [n, H, W, 1], not %s" % (a.shape,))
         n, H, W = (int(v) for v in a.shape[:3])
-        need = int(lib().rsu_components_ws_bytes(n, H, W))
-        if need == 0:
-            raise ValueError("postprocess_masks: %d masks of %d x %d pixels are outside rsu_components.h's limits (H * W <= 2^24, "
-                             "n * H * W < 2^31): clean them in smaller stacks" % (n, H, W))
         dev = self.net.device
+        ws = mask_metrics.workspace("components", (n, H, W), (), dev, "postprocess_masks: %d masks of %d x %d pixels are outside "
+                                    "rsu_components.h's limits (H * W <= 2^24, n * H * W < 2^31): clean them in smaller stacks" % (n, H, W))
         t = torch.as_tensor(np.ascontiguousarray(a[..., 0], dtype=np.float32)).to(dev)
-        ws = torch.empty(need // 4, dtype=torch.int32, device=dev)
         stats = torch.empty((n, 6), dtype=torch.int64, device=dev)
-        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        call("rsu_components_filter", ctypes.c_void_p(t.data_ptr()), float(threshold), int(getattr(opts, "component_connectivity", 8)),
-             min_area, max_hole, ctypes.c_void_p(t.data_ptr()), ctypes.c_void_p(stats.data_ptr()), ctypes.c_void_p(ws.data_ptr()), n, H, W, st)
+        mask_metrics.components_filter(t, threshold, getattr(opts, "component_connectivity", 8), min_area, max_hole, t, stats, ws,
+                                       mask_metrics.stream(dev))
         self.last_postprocess_stats = stats.sum(dim=0).cpu().numpy()
         return t.cpu().numpy()[..., None].astype(a.dtype)
 
@@ -1667,29 +1481,19 @@ class ConvolutionalModel:
         skeleton of {p >= threshold} and 0.0 elsewhere, after at most --centerline_max_iters iterations of Guo & Hall's thinning, and with
         --centerline_min_branch = L > 0 pruned of its branches of at most L pixels (rsu_skeleton_graph, in place on the skeletons).
         Integer decisions on the same input: every rank computes the same bits."""
+        return self._centerlines_device(masks, threshold).cpu().numpy()
+
+    def _centerlines_device(self, masks, threshold):
+        """centerlines(), its result still on the device (mask_metrics.thin_stack)"""
         a = np.asarray(masks)
         if a.ndim == 4 and a.shape[3] == 1:
             a = a[..., 0]
         if a.ndim != 3:
             raise ValueError("centerlines: masks must be [n, H, W] or [n, H, W, 1], not %s" % (a.shape,))
-        n, H, W = (int(v) for v in a.shape)
-        iters = int(getattr(self._options, "centerline_max_iters", 64))
-        need = int(lib().rsu_thin_ws_bytes(n, H, W, iters)) if min(n, H, W) >= 1 else 0
-        if need == 0:
-            raise ValueError("centerlines (--save_centerlines): %d masks of %d x %d pixels are outside rsu_thin.h's limits (sides up to %d, "
-                             "n * H * W * 4 below 2 GiB): thin them in smaller stacks" % (n, H, W, THIN_MAX_SIDE))
-        dev = self.net.device
-        t = torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-        out = torch.empty_like(t)
-        ws = torch.empty(need // 8, dtype=torch.int64, device=dev)
-        call("rsu_mask_thin", ctypes.c_void_p(t.data_ptr()), float(threshold), None, iters, ctypes.c_void_p(out.data_ptr()), None, None, None,
-             ctypes.c_void_p(ws.data_ptr()), n, H, W, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        min_branch = int(getattr(self._options, "centerline_min_branch", 0))
-        if min_branch > 0:   # prune the skeletons in place (the sizes rsu_thin.h takes are the ones rsu_graph.h takes)
-            gws = torch.empty(int(lib().rsu_graph_ws_bytes(n, H, W, min_branch)) // 8, dtype=torch.int64, device=dev)
-            call("rsu_skeleton_graph", ctypes.c_void_p(out.data_ptr()), 0.5, None, min_branch, ctypes.c_void_p(out.data_ptr()), None, None, None,
-                 None, ctypes.c_void_p(gws.data_ptr()), n, H, W, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        return out.cpu().numpy()
+        return mask_metrics.thin_stack(
+            torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)), self.net.device, threshold, int(getattr(self._options, "centerline_max_iters", 64)), int(getattr(self._options, "centerline_min_branch", 0)),
+            "centerlines (--save_centerlines): %d masks of %d x %d pixels are outside rsu_thin.h's limits (sides up to %d, n * H * W * 4 below "
+            "2 GiB): thin them in smaller stacks" % (tuple(a.shape) + (THIN_MAX_SIDE,)))
 
     def road_graph(self, masks, threshold=0.5):
         """The road network of predicted masks, one plain dict per image (hostio.road_graph: nodes and edges with their lengths): masks
@@ -1697,22 +1501,16 @@ class ConvolutionalModel:
         centerlines()), cut at their junctions into segments and measured on the device (rsu_line_segments, --max_segments rows per
         image; a dict carries "segments" = the true segment count, which may exceed its edges). Integer decisions on the same input:
         every rank computes the same network."""
-        lines = self.centerlines(masks, threshold)
+        lines = self._centerlines_device(masks, threshold)   # (exactly 0.0 / 1.0, and they stay on the device)
         n, H, W = (int(v) for v in lines.shape)
-        cap = int(getattr(self._options, "max_segments", 4096))
-        need = int(lib().rsu_segments_ws_bytes(n, H, W, cap))
-        if need == 0:
-            raise ValueError("road_graph (--save_road_graph): %d masks of %d x %d pixels are outside rsu_segments.h's limits (sides up to %d, "
-                             "n * H * W * 16 below 2 GiB): use smaller stacks" % (n, H, W, SEGMENTS_MAX_SIDE))
-        dev = self.net.device
-        t = torch.as_tensor(lines).to(dev)
+        cap, dev = int(getattr(self._options, "max_segments", 4096)), lines.device
+        ws = mask_metrics.workspace("segments", (n, H, W), (cap,), dev, "road_graph (--save_road_graph): %d masks of %d x %d pixels are outside "
+                                    "rsu_segments.h's limits (sides up to %d, n * H * W * 16 below 2 GiB): use smaller stacks"
+                                    % (n, H, W, SEGMENTS_MAX_SIDE))
         edges = torch.zeros((n, cap, 8), dtype=torch.int32, device=dev)
         counts = torch.zeros((n, 4), dtype=torch.int32, device=dev)
         node = torch.zeros((n, H, W), dtype=torch.int32, device=dev)
-        ws = torch.empty(need // 8, dtype=torch.int64, device=dev)
-        call("rsu_line_segments", ctypes.c_void_p(t.data_ptr()), 0.5, None, cap, ctypes.c_void_p(edges.data_ptr()), None,
-             ctypes.c_void_p(counts.data_ptr()), None, None, ctypes.c_void_p(node.data_ptr()), None, None, ctypes.c_void_p(ws.data_ptr()),
-             n, H, W, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        mask_metrics.line_segments(lines, 0.5, None, cap, edges, None, counts, None, None, node, None, None, ws, mask_metrics.stream(dev))
         edges, counts, node = edges.cpu().numpy(), counts.cpu().numpy(), node.cpu().numpy()
         out = []
         for i in range(n):

@@ -145,9 +145,11 @@ def test_flags_defaults_parsers_and_refusals():
 
 
 def test_postprocess_masks_is_the_identity_without_a_launch(monkeypatch):
+    from road_segmentation_unet_amd import mask_metrics      # (it issues the tool's calls and asks the library for its workspace)
     calls = []
-    monkeypatch.setattr(M, "call", lambda *a: calls.append(a))
-    monkeypatch.setattr(M, "lib", lambda: calls.append("lib"))
+    for mod in (M, mask_metrics):
+        monkeypatch.setattr(mod, "call", lambda *a: calls.append(a))
+    monkeypatch.setattr(mask_metrics, "lib", lambda: calls.append("lib"))
     m = object.__new__(M.ConvolutionalModel)
     m._options = M.Options()
     masks = np.random.RandomState(0).rand(2, 9, 7, 1)

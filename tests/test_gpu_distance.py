@@ -161,7 +161,7 @@ def _chunks(m, X, y):
 def test_evaluate_with_validate_distances(monkeypatch):
     """dist_hist equals the sum over the chunks of hostio.distance_hist on the probabilities evaluate produced; the relaxed keys are
     relaxed_metrics of it at --relaxed_slack; without the flag the keys are absent and no rsu_distance_* call is made"""
-    from road_segmentation_unet_amd import model as M
+    from road_segmentation_unet_amd import mask_metrics as M      # (it issues the calls)
     N = 5
     X, y = _patches(N)
     y[1, :3] = -1
@@ -190,7 +190,7 @@ def test_evaluate_with_validate_distances(monkeypatch):
     plain_model = _model()
     plain = plain_model.evaluate(X, y, threshold=thr)
     assert not KEYS & set(plain) and not [c for c in calls if c.startswith("rsu_distance") or c.startswith("rsu_mask_distance")]
-    assert plain_model._dt_acc is None and plain_model._dt_ws is None
+    assert plain_model._mask_metrics is None
     assert plain["f1"] == out["f1"] and np.array_equal(plain["sums"], out["sums"])
 
 

@@ -248,7 +248,7 @@ def _check(out, want):
 
 
 def test_evaluate_with_pruning_and_junctions(monkeypatch):
-    from road_segmentation_unet_amd import model as M
+    from road_segmentation_unet_amd import mask_metrics as M      # (it issues the calls)
     N = 5
     X, y = _patches(N)
     y[1, :3] = -1
@@ -282,7 +282,7 @@ def test_evaluate_with_pruning_and_junctions(monkeypatch):
     pruned = _model(validate_centerlines=True, centerline_min_branch=2, relaxed_slack=2)
     got = pruned.evaluate(X, y, threshold=thr)
     assert calls.count("rsu_skeleton_graph") == 3 and calls.count("rsu_distance_hist") == 3 and "rsu_components_pair_count" not in calls
-    assert set(got) == set(unpruned) and "junc_pred" not in pruned._gr_ws
+    assert set(got) == set(unpruned) and "junc_pred" not in pruned._mask_metrics.ws
     _check(got, {k: v for k, v in want.items() if k in CL_KEYS})
     del calls[:]
     junc = _model(validate_centerlines=True, validate_junctions=True, relaxed_slack=2)
@@ -301,9 +301,10 @@ def test_evaluate_with_pruning_and_junctions(monkeypatch):
     plain_model = _model(validate_centerlines=True, relaxed_slack=2)
     plain = plain_model.evaluate(X, y, threshold=thr)
     assert "rsu_skeleton_graph" not in calls and "rsu_components_pair_count" not in calls and calls.count("rsu_distance_hist") == 3
-    assert plain_model._gr_acc is None and plain_model._gr_ws is None and set(plain) == set(unpruned)
+    mm = plain_model._mask_metrics
+    assert "graph" not in mm.lay and not {"graph", "junc_pred", "junc_true", "comp"} & set(mm.ws) and set(plain) == set(unpruned)
     bare = _model()
-    assert not (CL_KEYS | JN_KEYS) & set(bare.evaluate(X, y, threshold=thr)) and bare._gr_acc is None and bare._cl_acc is None
+    assert not (CL_KEYS | JN_KEYS) & set(bare.evaluate(X, y, threshold=thr)) and bare._mask_metrics is None
 
 
 def test_centerlines_of_predicted_masks_pruned():
@@ -325,7 +326,7 @@ def test_cli_save_centerlines_pruned(tmp_path, monkeypatch):
     from PIL import Image
     from road_segmentation_unet_amd.cli import main
     from road_segmentation_unet_amd.model import ConvolutionalModel
-    from road_segmentation_unet_amd import model as M
+    from road_segmentation_unet_amd import mask_metrics as M      # (it issues the calls)
     rng = np.random.RandomState(4)
     ev = tmp_path / "eval"
     ev.mkdir()

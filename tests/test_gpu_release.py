@@ -70,7 +70,7 @@ def test_a_dropped_model_frees_its_buffers_without_a_collection(no_collector):
                            device="cuda:0", params=U.init_params(L, ROOT, True, seed=13, bias_scale=0.05))
     m.train_step(X[:B], y[:B])
     out = m.evaluate(X, y)
-    assert "jn_f1" in out and m._gr_ws is not None and torch.cuda.memory_allocated() > base
+    assert "jn_f1" in out and "graph" in m._mask_metrics.ws and torch.cuda.memory_allocated() > base
     del out
     ref, net = weakref.ref(m), weakref.ref(m.net)
     del m

@@ -174,7 +174,7 @@ def _host_metrics(chunks, thr, max_iters, min_branch, cap):
 
 
 def test_evaluate_with_segments_and_road_graph(monkeypatch):
-    from road_segmentation_unet_amd import model as M
+    from road_segmentation_unet_amd import mask_metrics as M      # (it issues the calls)
     from tests import test_gpu_graph as TG
     N = 5
     X, y = TG._patches(N)
@@ -205,7 +205,9 @@ def test_evaluate_with_segments_and_road_graph(monkeypatch):
     del calls[:]
     plain_model = TG._model(validate_centerlines=True, relaxed_slack=2)
     plain = plain_model.evaluate(X, y, threshold=thr)
-    assert "rsu_line_segments" not in calls and plain_model._sg_acc is None and plain_model._sg_ws is None and not SG_KEYS & set(plain)
+    mm = plain_model._mask_metrics
+    assert "rsu_line_segments" not in calls and "segments" not in mm.lay and not SG_KEYS & set(plain)
+    assert not {"segments", "edges_pred", "edges_true", "counts"} & set(mm.ws)
     assert set(out) - set(plain) == SG_KEYS
     # road_graph(): thin, prune, segments; one dict per image, equal to the host chain
     shape = (2, 230, 97)

@@ -195,7 +195,7 @@ def _host_composition(chunks, thr, max_iters):
 
 
 def test_evaluate_with_validate_centerlines(monkeypatch):
-    from road_segmentation_unet_amd import model as M
+    from road_segmentation_unet_amd import mask_metrics as M      # (it issues the calls)
     N = 5
     X, y = _patches(N)
     y[1, :3] = -1
@@ -231,7 +231,7 @@ def test_evaluate_with_validate_centerlines(monkeypatch):
     plain_model = _model()
     plain = plain_model.evaluate(X, y, threshold=thr)
     assert not KEYS & set(plain) and not [c for c in calls if "thin" in c or "distance" in c]
-    assert plain_model._cl_acc is None and plain_model._cl_ws is None
+    assert plain_model._mask_metrics is None
     assert plain["f1"] == out["f1"] and np.array_equal(plain["sums"], out["sums"])
     assert set(out) - set(plain) == KEYS
 

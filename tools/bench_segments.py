@@ -16,9 +16,15 @@
       VARIANT=parent` in a checkout of the parent, loaded through RSU_LIB_PATH), alternating fresh processes on one box; the order of the
       arms rotates from round to round. Every process runs under its own time limit and the series stops at the first one that fails.
       Medians per arm; the spread of the parent arm's runs is the noise the difference is read against.
-  bench_segments.py arm [--validate] [--steps N]
+  bench_segments.py step --all-flags --parent-tree PARENT_CHECKOUT [--lib LIBRARY] [--reps N]
+      a validation pass with ALL FIVE mask stages on (--validate_components, --validate_distances, --validate_centerlines with
+      --centerline_min_branch=8, --validate_junctions and --validate_segments: evaluate() over the same 8 patches of 388 x 388 in chunks
+      of 4), and the default pass again, with this tree's Python against a checkout of the parent commit's, both on ONE library (--lib,
+      default this tree's): the same rotation of fresh processes. The verdict: this arm's median inside the parent arm's own min .. max,
+      or below it.
+  bench_segments.py arm [--validate [--all-flags] [--tree ROOT]] [--steps N]
       one arm of the above in this process. --parent-lib: the library is the parent commit's, which has no entry of rsu_segments.h --
-      the table is left unbound (the default step and validation call none of them).
+      the table is left unbound (the default step and validation call none of them). --tree: the checkout whose package is imported.
 The record goes to standard output: keep it under profiles/rNN/.
 """
 import argparse
@@ -39,6 +45,9 @@ ap.add_argument("--calls", type=int, default=50)
 ap.add_argument("--side", type=int, default=608)
 ap.add_argument("--validate", action="store_true")
 ap.add_argument("--parent-lib", action="store_true")
+ap.add_argument("--all-flags", action="store_true")
+ap.add_argument("--parent-tree", default=None)
+ap.add_argument("--tree", default=None)
 a = ap.parse_args()
 
 
@@ -47,11 +56,19 @@ def median(v):
 
 
 if a.mode_ == "step":
-    if not a.lib or not os.path.exists(a.lib):
-        sys.exit("step needs --lib: the parent commit's library")
-    parent = {"RSU_LIB_PATH": os.path.abspath(a.lib)}
-    arms = [("parent step", parent, ["--parent-lib"]), ("this step", {}, []), ("parent validate", parent, ["--parent-lib", "--validate"]),
-            ("this validate", {}, ["--validate"])]
+    if a.all_flags:
+        one_lib = os.path.abspath(a.lib or os.path.join(HERE, "road_segmentation_unet_amd", "librsu_hip.so"))
+        if not a.parent_tree or not os.path.isdir(os.path.join(a.parent_tree, "road_segmentation_unet_amd")) or not os.path.exists(one_lib):
+            sys.exit("step --all-flags needs --parent-tree: a checkout of the parent commit, and a built library")
+        both, tree = {"RSU_LIB_PATH": one_lib}, ["--tree", os.path.abspath(a.parent_tree)]
+        arms = [("parent all-flags", both, ["--validate", "--all-flags"] + tree), ("this all-flags", both, ["--validate", "--all-flags"]),
+                ("parent default", both, ["--validate"] + tree), ("this default", both, ["--validate"])]
+    else:
+        if not a.lib or not os.path.exists(a.lib):
+            sys.exit("step needs --lib: the parent commit's library")
+        parent = {"RSU_LIB_PATH": os.path.abspath(a.lib)}
+        arms = [("parent step", parent, ["--parent-lib"]), ("this step", {}, []), ("parent validate", parent, ["--parent-lib", "--validate"]),
+                ("this validate", {}, ["--validate"])]
     ms = {k: [] for k, _, _ in arms}
     for rep in range(a.reps):
         for name, env, extra in arms[rep % len(arms):] + arms[:rep % len(arms)]:   # (no arm is always the first of its round)
@@ -68,6 +85,13 @@ if a.mode_ == "step":
     med = {k: median(v) for k, v in ms.items()}
     for k, _, _ in arms:
         print("%-15s ms: %s | median %.4f min %.4f max %.4f" % (k, " ".join("%.4f" % v for v in ms[k]), med[k], min(ms[k]), max(ms[k])))
+    if a.all_flags:
+        for what, title in (("all-flags", "all five mask stages on"), ("default", "no flag set")):
+            lo, hi, this, par = min(ms["parent " + what]), max(ms["parent " + what]), med["this " + what], med["parent " + what]
+            print("validation pass, %s, this tree's Python against the parent's on one library: median %.4f ms against %.4f ms (%+.2f %%); "
+                  "the parent arm's own runs span %.4f .. %.4f ms: this median is %s"
+                  % (title, this, par, 100 * (this - par) / par, lo, hi, "BELOW that range" if this < lo else "inside it" if this <= hi else "ABOVE it"))
+        sys.exit(0)
     for what in ("step", "validate"):
         spread, own = max(ms["parent " + what]) - min(ms["parent " + what]), max(ms["this " + what]) - min(ms["this " + what])
         d = med["this " + what] - med["parent " + what]
@@ -76,7 +100,7 @@ if a.mode_ == "step":
                                                      "inside" if abs(d) <= spread else "OUTSIDE"))
     sys.exit(0)
 
-sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.abspath(a.tree) if a.tree else HERE)
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -113,10 +137,14 @@ if a.mode_ == "arm" and not a.validate:
     print("default step lib %s: %.4f ms/step = %.1f patches/s (%d steps)" % (sha, ms, B / ms * 1e3, a.steps))
     sys.exit(0)
 
+BRANCH_ALL = 8   # --centerline_min_branch of the all-flags arm
+
 if a.mode_ == "arm":
     from road_segmentation_unet_amd.model import ConvolutionalModel, Options
     from road_segmentation_unet_amd.unet import input_size_needed
-    opts = Options(num_layers=5, root_size=64, patch_size=388, batch_size=4, dropout=1.0, logdir=None)
+    stages = dict(validate_components=True, validate_distances=True, validate_centerlines=True, centerline_min_branch=BRANCH_ALL,
+                  validate_junctions=True, validate_segments=True) if a.all_flags else {}
+    opts = Options(num_layers=5, root_size=64, patch_size=388, batch_size=4, dropout=1.0, logdir=None, **stages)
     model = ConvolutionalModel(opts)
     rng = np.random.RandomState(0)
     S = input_size_needed(388, 5)
@@ -128,9 +156,12 @@ if a.mode_ == "arm":
         torch.cuda.synchronize(); t0 = time.perf_counter()
         v = model.evaluate(X, y)
         torch.cuda.synchronize(); t.append((time.perf_counter() - t0) * 1e3)
-    assert "cl_hist" not in v and "segments_pred" not in v
-    print("default validate lib %s, 8 patches of 388 x 388 in chunks of 4, 7 calls %s: %.4f ms/pass (median)"
-          % (sha, " ".join("%.1f" % x for x in t), median(t)))
+    assert all((k in v) == a.all_flags for k in ("components_pred", "dist_hist", "cl_hist", "jn_hist", "segments_pred"))
+    pkg = os.path.dirname(os.path.abspath(sys.modules[ConvolutionalModel.__module__].__file__))
+    assert pkg == os.path.join(os.path.abspath(a.tree) if a.tree else HERE, "road_segmentation_unet_amd"), pkg
+    print("%s validate lib %s, the package of %s, 8 patches of 388 x 388 in chunks of 4, 7 calls %s: %.4f ms/pass (median)"
+          % ("all-flags" if a.all_flags else "default", sha, "the --tree checkout" if a.tree else "this tree", " ".join("%.1f" % x for x in t),
+             median(t)))
     sys.exit(0)
 
 # ---- kernels, split
