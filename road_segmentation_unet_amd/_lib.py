@@ -1,6 +1,6 @@
 """ctypes binding of librsu_hip.so (the C ABI of include/rsu.h, include/rsu_optim.h, include/rsu_loss.h, include/rsu_cldice.h,
-include/rsu_lovasz.h, include/rsu_components.h, include/rsu_distance.h, include/rsu_thin.h, include/rsu_graph.h and
-include/rsu_segments.h).
+include/rsu_lovasz.h, include/rsu_components.h, include/rsu_distance.h, include/rsu_thin.h, include/rsu_graph.h,
+include/rsu_segments.h and include/rsu_paths.h).
 
 The library is REQUIRED: there is no CPU or eager-PyTorch fallback anywhere in this package. If the
 shared object is missing or a symbol cannot be resolved, importing/using the product path raises."""
@@ -214,6 +214,12 @@ SIGNATURES_SEGMENTS = {
     "rsu_line_segments": (_i, [_vp, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
 }
 
+# and for include/rsu_paths.h, the eleventh (ordered polylines: the pixels of every stored segment ranked along it)
+SIGNATURES_PATHS = {
+    "rsu_paths_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "rsu_segment_paths": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+}
+
 _lib = None
 
 
@@ -232,7 +238,7 @@ def lib():
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_OPTIM.items()) + list(SIGNATURES_LOSS.items()) \
                 + list(SIGNATURES_CLDICE.items()) + list(SIGNATURES_LOVASZ.items()) + list(SIGNATURES_COMPONENTS.items()) \
                 + list(SIGNATURES_DISTANCE.items()) + list(SIGNATURES_THIN.items()) + list(SIGNATURES_GRAPH.items()) \
-                + list(SIGNATURES_SEGMENTS.items()):
+                + list(SIGNATURES_SEGMENTS.items()) + list(SIGNATURES_PATHS.items()):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -254,6 +260,7 @@ DIST_BINS, DIST_NONE, DIST_MAX_SIDE = 64, 0x7fffffff, 1024   # rsu_distance.h RS
 THIN_MAX_SIDE, THIN_MAX_ITERS = 1024, 512   # rsu_thin.h RSU_THIN_MAX_SIDE, RSU_THIN_MAX_ITERS
 GRAPH_MAX_SIDE, GRAPH_MAX_BRANCH = 1024, 64   # rsu_graph.h RSU_GRAPH_MAX_SIDE, RSU_GRAPH_MAX_BRANCH
 SEGMENTS_MAX_SIDE, SEGMENTS_MAX_EDGES = 1024, 65536   # rsu_segments.h RSU_SEGMENTS_MAX_SIDE, RSU_SEGMENTS_MAX_EDGES
+PATHS_MAX_SIDE, PATHS_MAX_EDGES, PATHS_MAX_LEN = 1024, 65536, 1 << 20   # rsu_paths.h RSU_PATHS_MAX_SIDE, RSU_PATHS_MAX_EDGES, RSU_PATHS_MAX_LEN
 E2BIG = -7
 
 

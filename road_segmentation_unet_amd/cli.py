@@ -182,6 +182,9 @@ def main(argv=None):
                         json.dump(g, f)
                 print("Road graphs: {} nodes and {} edges in {} images".format(sum(len(g["nodes"]) for g in graphs),
                                                                                sum(len(g["edges"]) for g in graphs), len(graphs)))
+                if opts.road_graph_paths:
+                    print("Road paths: {} points, {} segments not ordered (branched or longer than {} pixels)".format(
+                        sum(len(e["path"]) for g in graphs for e in g["edges"]), sum(g["unordered"] for g in graphs), opts.max_path_length))
             if masks.shape[1] % hostio.IMG_PATCH_SIZE or masks.shape[2] % hostio.IMG_PATCH_SIZE:
                 print("No submission.csv: {} x {} images are not made of whole {}-pixel patches".format(
                     masks.shape[1], masks.shape[2], hostio.IMG_PATCH_SIZE))

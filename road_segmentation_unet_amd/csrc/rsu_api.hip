@@ -22,6 +22,7 @@
 #include "../../include/rsu_thin.h"
 #include "../../include/rsu_graph.h"
 #include "../../include/rsu_segments.h"
+#include "../../include/rsu_paths.h"
 #include "affine_patches.h"
 #include "color_jitter.h"
 #include "border_map.h"
@@ -34,6 +35,7 @@
 #include "thin.h"
 #include "graph.h"
 #include "segments.h"
+#include "paths.h"
 #include "optim.h"
 #include "igemm.h"
 
@@ -1804,6 +1806,30 @@ extern "C" int rsu_line_segments(const float* prob, float threshold, const int64
     if (segments_too_big(N, H, W)) return RSU_E2BIG;
     HIP_CHECK_RET(sg_line_segments(prob, threshold, labels64, max_edges, edges_pred, edges_true, counts, seg_pred, seg_true, node_pred, node_true,
                                    acc, ws, N, H, W, (hipStream_t)stream));
+    return RSU_OK;
+}
+// ---- ordered polylines (rsu_paths.h): the pixels of every stored segment ranked along it by pointer jumping over arcs
+static_assert(RSU_PATHS_MAX_SIDE == PT_MAX_SIDE && RSU_PATHS_MAX_EDGES == PT_MAX_EDGES && RSU_PATHS_MAX_LEN == PT_MAX_LEN,
+              "rsu_paths.h and paths.h must agree on the limits");
+static bool paths_size_ok(int N, int H, int W, int max_edges, int max_len) {
+    return N >= 1 && H >= 1 && W >= 1 && H <= PT_MAX_SIDE && W <= PT_MAX_SIDE && max_edges >= 1 && max_edges <= PT_MAX_EDGES && max_len >= 1 &&
+           max_len <= PT_MAX_LEN;
+}
+// one arc buffer: two 64-bit words per pixel
+static bool paths_too_big(int N, int H, int W) { return (long)N * H * W * 16 >= 0x7ffffff0L; }
+extern "C" size_t rsu_paths_ws_bytes(int N, int H, int W, int max_edges, int max_len) {
+    return paths_size_ok(N, H, W, max_edges, max_len) && !paths_too_big(N, H, W) ? pt_ws_bytes(N, H, W, max_edges, max_len) : 0;
+}
+extern "C" int rsu_segment_paths(const int32_t* seg, const int32_t* edges, const int32_t* counts, int side, int max_edges, int max_len,
+                                 int max_points, int32_t* paths, int32_t* offsets, int32_t* kind, int32_t* pos, int32_t* info, void* ws, int N,
+                                 int H, int W, rsu_stream_t stream) {
+    if (!seg || !edges || !counts || !paths || !offsets || !kind || !info || !ws || !paths_size_ok(N, H, W, max_edges, max_len) ||
+        (side != 0 && side != 1) || max_points < 1 || max_points > H * W)
+        return RSU_EINVAL;
+    if (misaligned(4, seg, edges, counts, paths, offsets, kind, pos, info) || misaligned(8, ws)) return RSU_EINVAL;
+    if (paths_too_big(N, H, W)) return RSU_E2BIG;
+    HIP_CHECK_RET(pt_segment_paths(seg, edges, counts, side, max_edges, max_len, max_points, paths, offsets, kind, pos, info, ws, N, H, W,
+                                   (hipStream_t)stream));
     return RSU_OK;
 }
 static_assert(RSU_BORDER_MAX_SIDE == BM_MAX_SIDE, "rsu.h and border_map.h must agree on the supported tile size");

@@ -1503,13 +1503,183 @@ def segment_metrics(acc, counts_sum):
     return out
 
 
-def road_graph(edges, count, node_map, H, W):
+# ---- ordered polylines on the host (include/rsu_paths.h)
+PATHS_MAX_SIDE, PATHS_MAX_EDGES, PATHS_MAX_LEN = 1024, 65536, 1 << 20   # rsu_paths.h RSU_PATHS_MAX_SIDE, RSU_PATHS_MAX_EDGES, RSU_PATHS_MAX_LEN
+PATHS_BLOCK, PATHS_TILE = 256, (64, 16)                                 # csrc/paths.hip PT_BLOCK; PT_TW, PT_TH
+PATH_KINDS = ("open", "ring", "branched", "long")                       # the kind of a stored row: 0, 1, 2, 3
+_PATH_DIRS = ((-1, -1), (-1, 0), (-1, 1), (0, -1), (0, 1), (1, -1), (1, 0), (1, 1))   # ascending row-major offset: NW N NE W E SW S SE
+
+
+def path_rounds(max_len):
+    """R = ceil(log2(max_len)): the doublings (jump launches) of one rsu_segment_paths call"""
+    return (int(max_len) - 1).bit_length()
+
+
+def path_link_mask(s):
+    """int32 [H, W] of a bool [H, W]: bit d set where the pixel and its neighbour in direction d (_PATH_DIRS) are path-linked: both in S
+    and 4-adjacent, or diagonal neighbours with neither of the two pixels 4-adjacent to both in S (include/rsu_paths.h); 0 outside S"""
+    H, W = s.shape
+    q = np.pad(s, 1)
+    at = [q[1 + dy:1 + dy + H, 1 + dx:1 + dx + W] for dy, dx in _PATH_DIRS]
+    n, w, e, so = at[1], at[3], at[4], at[6]
+    link = [at[0] & ~n & ~w, n, at[2] & ~n & ~e, w, e, at[5] & ~so & ~w, so, at[7] & ~so & ~e]
+    mask = np.zeros((H, W), np.int32)
+    for d in range(8):
+        mask |= (s & link[d]).astype(np.int32) << d
+    return mask
+
+
+def _paths_check(seg, edges, counts, side, max_len, max_points):
+    sg, e, c = np.asarray(seg), np.asarray(edges), np.asarray(counts)
+    if sg.ndim != 3 or sg.dtype.kind not in "iu" or min(sg.shape) < 1:
+        raise ValueError("segment_paths: seg must be an integer array [N, H, W] with N, H, W >= 1, not %s %r" % (sg.dtype, sg.shape))
+    N, H, W = sg.shape
+    if max(H, W) > PATHS_MAX_SIDE:
+        raise ValueError("segment_paths: H, W <= %d, not shape %r" % (PATHS_MAX_SIDE, sg.shape))
+    if isinstance(side, bool) or not isinstance(side, (int, np.integer)) or side not in (0, 1):
+        raise ValueError("segment_paths: side must be 0 or 1, not %r" % (side,))
+    if e.ndim != 3 or e.shape[0] != N or e.shape[2] != 8 or e.dtype.kind not in "iu" or not 1 <= e.shape[1] <= PATHS_MAX_EDGES:
+        raise ValueError("segment_paths: edges must be an integer array [%d, max_edges, 8] with max_edges in [1, %d], not %s %r"
+                         % (N, PATHS_MAX_EDGES, e.dtype, e.shape))
+    if c.shape != (N, 4) or c.dtype.kind not in "iu":
+        raise ValueError("segment_paths: counts must be an integer array [%d, 4], not %s %r" % (N, c.dtype, c.shape))
+    if isinstance(max_len, bool) or not isinstance(max_len, (int, np.integer)) or not 1 <= max_len <= PATHS_MAX_LEN:
+        raise ValueError("segment_paths: max_len must be an integer in [1, %d], not %r" % (PATHS_MAX_LEN, max_len))
+    if isinstance(max_points, bool) or not isinstance(max_points, (int, np.integer)) or not 1 <= max_points <= H * W:
+        raise ValueError("segment_paths: max_points must be an integer in [1, H W = %d], not %r" % (H * W, max_points))
+    if N * H * W * 16 >= 0x7ffffff0:
+        raise ValueError("segment_paths: an arc buffer of %d x %d x %d pixels (16 bytes each) reaches 2 GiB" % (N, H, W))
+    return sg, e, c
+
+
+def _paths_walk(mask, start, ring, limit):
+    """the pixels of one segment from `start` along the links: mask = the flat link masks, ring: leave the start towards its smaller
+    neighbour and stop in front of it again; at most `limit` pixels"""
+    W = mask[1]
+    m = mask[0]
+    out, prev, cur = [start], -1, start
+    while len(out) < limit:
+        nxt = -1
+        for d in range(8):
+            if m[cur] >> d & 1:
+                w = cur + _PATH_DIRS[d][0] * W + _PATH_DIRS[d][1]
+                if w != prev:
+                    nxt = w
+                    break
+        if nxt < 0 or nxt == start:
+            break
+        out.append(nxt)
+        prev, cur = cur, nxt
+    return out
+
+
+def segment_paths(seg, edges, counts, side, max_len, max_points, fill=0):
+    """rsu_segment_paths on the host, by a sequential walk, in its output formats: (paths int32 [N, max_points], offsets int32
+    [N, max_edges + 1], kind int32 [N, max_edges], pos int32 [N, H, W], info int32 [N, 4]) of seg int32 [N, H, W], edges int32
+    [N, max_edges, 8] and counts int32 [N, 4] of one rsu_line_segments call, for side 0 (counts[:, 0]) or 1 (counts[:, 2]). The first
+    stored = min(count, max_edges) rows are read; a stored row is open (kind 0), a ring (1), branched (2: a pixel of link degree >= 3) or
+    too long (3: pixels > max_len, tested first); the pixels of an open row run from its smaller-indexed terminal, those of a ring from
+    its smallest pixel towards the smaller-indexed of that pixel's two neighbours; offsets = the exclusive sums of the ordered rows'
+    pixel counts (the true numbers, also past max_points), paths[n, offsets[n, r] + p] = the row-major index of position p of row r,
+    pos = 1 + position at ordered pixels and 0 elsewhere, info = {points, open rows, ring rows, rows of kind 2 or 3}. Elements the entry
+    does not touch keep `fill`: rows at and past stored, offsets past stored, path elements no ordered row owns. Bad arguments raise
+    ValueError by the header's rules."""
+    sg, e, c = _paths_check(seg, edges, counts, side, max_len, max_points)
+    N, H, W = sg.shape
+    cap = e.shape[1]
+    paths = np.full((N, int(max_points)), fill, np.int32)
+    offsets = np.full((N, cap + 1), fill, np.int32)
+    kind = np.full((N, cap), fill, np.int32)
+    pos = np.zeros((N, H, W), np.int32)
+    info = np.zeros((N, 4), np.int32)
+    for n in range(N):
+        stored = min(max(int(c[n, 2 * side]), 0), cap)
+        rows = e[n, :stored].astype(np.int64)
+        flat = sg[n].reshape(-1).astype(np.int64)
+        mask = path_link_mask(sg[n] != 0).reshape(-1)
+        where = np.nonzero(flat)[0]
+        row_of = np.searchsorted(rows[:, 0], flat[where])
+        hit = row_of < stored
+        hit[hit] = rows[row_of[hit], 0] == flat[where[hit]]
+        where, row_of = where[hit], row_of[hit]                     # the pixels of stored rows, ascending index; their rows
+        deg = np.array([bin(int(v)).count("1") for v in mask[where]], np.int64) if where.size else np.zeros(0, np.int64)
+        branched = np.zeros(stored, bool)
+        np.logical_or.at(branched, row_of, deg >= 3)
+        big = np.int64(1) << 40
+        minterm = np.full(stored, big)
+        np.minimum.at(minterm, row_of[deg <= 1], where[deg <= 1])
+        found = np.bincount(row_of, minlength=stored) if stored else np.zeros(0, np.int64)
+        k = np.where(rows[:, 1] > max_len, 3, np.where(branched, 2, np.where(minterm != big, 0, 1)))
+        length = np.where(k <= 1, rows[:, 1], 0)
+        off = np.concatenate([[0], np.cumsum(length)])
+        kind[n, :stored] = k
+        offsets[n, :stored + 1] = off.astype(np.int32)
+        info[n] = (off[-1], (k == 0).sum(), (k == 1).sum(), (k >= 2).sum())
+        m = (mask.tolist(), W)
+        for r in range(stored):
+            if k[r] > 1 or not found[r]:
+                continue
+            ring = k[r] == 1
+            start = int(rows[r, 0]) - 1 if ring else int(minterm[r])
+            if not 0 <= start < H * W or not mask[start] and ring:
+                continue
+            for p, v in enumerate(_paths_walk(m, start, ring, int(found[r]))):
+                pos[n].reshape(-1)[v] = p + 1
+                if 0 <= off[r] + p < max_points:
+                    paths[n, off[r] + p] = v
+    return paths, offsets, kind, pos, info
+
+
+def simplify_path(points, eps):
+    """Ramer-Douglas-Peucker on a chain of points, integer [n, 2]: the first and the last point stay, and between two kept points every
+    point within eps of the straight line between them goes (the distance to the line through them; to the point where the two
+    coincide). eps = 0 returns the input. A ring is a chain that is cut at its first point: it is treated as open, from position 0 to
+    its last pixel. Host only."""
+    pts = np.asarray(points)
+    if pts.ndim != 2 or pts.shape[1] != 2 or pts.dtype.kind not in "iu":
+        raise ValueError("simplify_path: points must be an integer array [n, 2], not %s %r" % (pts.dtype, pts.shape))
+    if isinstance(eps, bool) or not isinstance(eps, (int, float, np.integer, np.floating)) or not eps >= 0 or not np.isfinite(eps):
+        raise ValueError("simplify_path: eps must be a finite number >= 0, not %r" % (eps,))
+    n = pts.shape[0]
+    if eps == 0 or n <= 2:
+        return pts.copy()
+    p = pts.astype(np.float64)
+    keep = np.zeros(n, bool)
+    keep[0] = keep[-1] = True
+    stack = [(0, n - 1)]
+    while stack:
+        a, b = stack.pop()
+        if b - a < 2:
+            continue
+        d, q = p[b] - p[a], p[a + 1:b] - p[a]
+        norm = float(np.hypot(d[0], d[1]))
+        dist = np.abs(d[0] * q[:, 1] - d[1] * q[:, 0]) / norm if norm > 0.0 else np.hypot(q[:, 0], q[:, 1])
+        i = int(np.argmax(dist))
+        if dist[i] > eps:
+            keep[a + 1 + i] = True
+            stack += [(a, a + 1 + i), (a + 1 + i, b)]
+    return pts[keep]
+
+
+def _node_touches(m, node, y, x):
+    """node id `node` touches pixel (y, x) of node map m: the pixel's own negative id, or a positive zone id among its eight neighbours"""
+    if node < 0:
+        return int(m[y, x]) == node
+    return node > 0 and bool((m[max(y - 1, 0):y + 2, max(x - 1, 0):x + 2] == node).any())
+
+
+def road_graph(edges, count, node_map, H, W, paths=None):
     """One image's network as a plain dict from rsu_line_segments' outputs: edges int32 [max_edges, 8], count = its segment count (the
     first min(count, max_edges) rows are read), node_map = node_* of the image, int32 [H, W] (sparse: node ids at zone pixels, negative
     ids at line ends).
       nodes: [{id, kind: junction | end | isolated, y, x}]: a junction's position is the centroid of its zone, an end's its pixel; an
              isolated pixel is an end whose segment has one pixel. Ascending id.
-      edges: [{id, a, b, pixels, length, contacts, ends}], length = ortho + sqrt(2) diag, in row order."""
+      edges: [{id, a, b, pixels, length, contacts, ends}], length = ortho + sqrt(2) diag, in row order.
+    paths = (paths int32 [max_points], offsets int32 [max_edges + 1], kind int32 [max_edges]) of the image from rsu_segment_paths: every
+    edge also gets "kind" (open | ring | branched | long) and "path", a list of [y, x] (empty for the unordered kinds; cut where the
+    points passed max_points). An open path is reversed when node a touches its last pixel and not its first (the pixel's own negative id
+    in node_map, or a positive zone id among its eight neighbours), so it runs from a to b where that is decidable; otherwise the
+    device order stays."""
     e = np.asarray(edges)
     m = np.asarray(node_map)
     if e.ndim != 2 or e.shape[1] != 8 or e.dtype.kind not in "iu":
@@ -1532,4 +1702,21 @@ def road_graph(edges, count, node_map, H, W):
     root2 = float(np.sqrt(np.float64(2.0)))
     out = [{"id": int(r[0]), "a": int(r[4]), "b": int(r[5]), "pixels": int(r[1]), "length": float(r[2]) + root2 * float(r[3]),
             "contacts": int(r[6]), "ends": int(r[7])} for r in rows]
+    if paths is not None:
+        pts, off, kind = (np.asarray(a) for a in paths)
+        if pts.ndim != 1 or off.shape != (e.shape[0] + 1,) or kind.shape != (e.shape[0],) or any(a.dtype.kind not in "iu" for a in (pts, off, kind)):
+            raise ValueError("road_graph: paths must be integer arrays ([max_points], [%d], [%d]), not %r, %r, %r"
+                             % (e.shape[0] + 1, e.shape[0], pts.shape, off.shape, kind.shape))
+        for i, (r, edge) in enumerate(zip(rows, out)):
+            k = int(kind[i])
+            if not 0 <= k <= 3:
+                raise ValueError("road_graph: kind[%d] = %d is none of 0 .. 3" % (i, k))
+            chain = []
+            if k <= 1:
+                lo = min(max(int(off[i]), 0), pts.shape[0])
+                hi = min(max(int(off[i]) + int(r[1]), lo), pts.shape[0])
+                chain = [[int(v) // W, int(v) % W] for v in pts[lo:hi]]
+                if k == 0 and len(chain) > 1 and _node_touches(m, int(r[4]), *chain[-1]) and not _node_touches(m, int(r[4]), *chain[0]):
+                    chain.reverse()
+            edge["kind"], edge["path"] = PATH_KINDS[k], chain
     return {"nodes": nodes, "edges": out}

@@ -1,5 +1,5 @@
-"""The chain from a mask to a road graph, in one place: the entry points of rsu_components.h, rsu_distance.h, rsu_thin.h, rsu_graph.h and
-rsu_segments.h as functions of tensors, their workspaces, and the integer mask metrics of a validation pass -- the layout of their one
+"""The chain from a mask to a road graph, in one place: the entry points of rsu_components.h, rsu_distance.h, rsu_thin.h, rsu_graph.h,
+rsu_segments.h and rsu_paths.h as functions of tensors, their workspaces, and the integer mask metrics of a validation pass -- the layout of their one
 accumulator (layout), the launches of a chunk (MaskMetrics.run) and the reading of the all-reduced counters (decode).
 ConvolutionalModel.evaluate() and the mask tools (postprocess_masks, centerlines, road_graph) drive it; nothing here knows a model."""
 import ctypes
@@ -59,16 +59,23 @@ def line_segments(prob, threshold, labels, max_edges, edges_pred, edges_true, co
          ptr(seg_pred), ptr(seg_true), ptr(node_pred), ptr(node_true), ptr(acc), ptr(ws), *prob.shape, st)
 
 
+def segment_paths(seg, edges, counts, side, max_len, max_points, paths, offsets, kind, pos, info, ws, st):
+    """rsu_paths.h: the pixels of every stored segment of one side of line_segments in their order along it; paths int32 [N, max_points],
+    offsets int32 [N, max_edges + 1], kind int32 [N, max_edges], pos int32 [N, H, W] or None, info int32 [N, 4]"""
+    call("rsu_segment_paths", ptr(seg), ptr(edges), ptr(counts), int(side), int(edges.shape[1]), int(max_len), int(max_points), ptr(paths),
+         ptr(offsets), ptr(kind), ptr(pos), ptr(info), ptr(ws), *seg.shape, st)
+
+
 # ------------------------------------------------------------------ workspaces
 # header -> (its size function, the element type of the width its `align` note asks of ws)
 _WS = {"components": ("rsu_components_ws_bytes", torch.int32), "distance": ("rsu_distance_ws_bytes", torch.int32),
        "thin": ("rsu_thin_ws_bytes", torch.int64), "graph": ("rsu_graph_ws_bytes", torch.int64),
-       "segments": ("rsu_segments_ws_bytes", torch.int64)}
+       "segments": ("rsu_segments_ws_bytes", torch.int64), "paths": ("rsu_paths_ws_bytes", torch.int64)}
 
 
 def workspace(entry, shape, extra, device, message, ok=True, zero=False):
     """The workspace of rsu_<entry>.h's launches on `shape` = (n, H, W) and the header's `extra` size arguments (thin: max_iters; graph:
-    min_branch; segments: max_edges). ValueError(message) where the header takes no such sizes (its size function returns 0) or the caller's
+    min_branch; segments: max_edges; paths: max_edges, max_len). ValueError(message) where the header takes no such sizes (its size function returns 0) or the caller's
     own guard `ok` fails. No entry reads what its workspace held: torch.empty, or zeros for a buffer that is kept."""
     fn, dtype = _WS[entry]
     need = int(getattr(lib(), fn)(*(int(v) for v in tuple(shape) + tuple(extra)))) if ok else 0

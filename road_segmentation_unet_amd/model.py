@@ -21,6 +21,7 @@ from . import mask_metrics
 from ._lib import call
 from .hostio import GRAPH_MAX_BRANCH, SEGMENTS_MAX_EDGES, SEGMENTS_MAX_SIDE, THIN_MAX_ITERS, THIN_MAX_SIDE
 from .hostio import road_graph as hostio_road_graph
+from .hostio import PATHS_MAX_LEN, PATHS_MAX_SIDE, simplify_path
 from .dist import GradBucketer, micro_indices, shard_indices, tune_overlap  # noqa: F401  (shard_indices: importable from here as before)
 from .pool import BatchUploader, DevicePatchPool, PatchPool
 from .summary import Summary
@@ -150,6 +151,14 @@ EXTRA_FLAG_DEFS = [
                                      "--max_hole_area, at threshold 0.5; thinned, pruned by --centerline_min_branch, cut into segments) "
                                      "as graph_%03d.json beside the overlays: nodes (junctions, ends, isolated pixels) and edges with "
                                      "their lengths"),
+    ("road_graph_paths", bool, False, "With --save_road_graph (and road_graph()): also order the pixels of every segment along it on the "
+                                      "GPU (rsu_paths.h) and give every edge its \"kind\" (open | ring | branched | long) and its \"path\", a "
+                                      "list of [y, x] from node a to node b where that is decidable; branched and long segments get an "
+                                      "empty path, and every graph their number as \"unordered\""),
+    ("max_path_length", int, 4096, "An int in [1, 1048576]: segments of more pixels are not ordered (kind \"long\"). Used by "
+                                   "--road_graph_paths"),
+    ("road_graph_simplify", float, 0.0, "EPS >= 0: simplify every path of --road_graph_paths with Ramer-Douglas-Peucker at EPS pixels (the "
+                                        "first and last point stay); 0 = every pixel"),
     ("border_weight", float, 0.0, "w0 >= 0 of a border-distance weight map computed on the GPU from each batch's labels: a pixel counts "
                                   "1 + w0 * exp(-d^2 / (2 border_sigma^2)) times in the loss, d its distance to the other class inside its patch; "
                                   "0 = off (the U-Net paper uses 10). The loss stays normalised by the pixel count and the mean weight is above 1, "
@@ -384,6 +393,30 @@ def parse_max_segments(value):
         v, ok = 0, False
     if not ok:
         raise ValueError("--max_segments must be an integer in [1, %d], not %r" % (SEGMENTS_MAX_EDGES, value))
+    return v
+
+
+def parse_max_path_length(value):
+    """The --max_path_length value as an int in [1, 1048576] (rsu_paths.h RSU_PATHS_MAX_LEN). Anything else raises ValueError."""
+    try:
+        v = int(value)
+        ok = not isinstance(value, bool) and v == (float(value) if not isinstance(value, str) else v) and 1 <= v <= PATHS_MAX_LEN
+    except (TypeError, ValueError, OverflowError):
+        v, ok = 0, False
+    if not ok:
+        raise ValueError("--max_path_length must be an integer in [1, %d], not %r" % (PATHS_MAX_LEN, value))
+    return v
+
+
+def parse_road_graph_simplify(value):
+    """The --road_graph_simplify value as a finite float >= 0 (0 = every pixel). Anything else raises ValueError."""
+    try:
+        v = float(value)
+        ok = not isinstance(value, bool) and np.isfinite(v) and v >= 0.0
+    except (TypeError, ValueError, OverflowError):
+        v, ok = 0.0, False
+    if not ok:
+        raise ValueError("--road_graph_simplify must be a finite number >= 0, not %r" % (value,))
     return v
 
 
@@ -733,6 +766,9 @@ class Options(object):
             raise ValueError("--validate_junctions requires --validate_centerlines: without it validation extracts no centre-lines")
         self.validate_segments, self.save_road_graph = bool(self.validate_segments), bool(self.save_road_graph)
         self.max_segments = parse_max_segments(self.max_segments)
+        self.road_graph_paths = bool(self.road_graph_paths)
+        self.max_path_length = parse_max_path_length(self.max_path_length)
+        self.road_graph_simplify = parse_road_graph_simplify(self.road_graph_simplify)
         if self.validate_segments and not self.validate_centerlines:
             raise ValueError("--validate_segments requires --validate_centerlines: without it validation extracts no centre-lines")
         self.border_weight, self.border_sigma = parse_border_weight(self.border_weight), parse_border_sigma(self.border_sigma)
@@ -1500,22 +1536,42 @@ class ConvolutionalModel:
         [n, H, W] or [n, H, W, 1] probabilities -> the centre-lines of {p >= threshold} (rsu_mask_thin, pruned by --centerline_min_branch:
         centerlines()), cut at their junctions into segments and measured on the device (rsu_line_segments, --max_segments rows per
         image; a dict carries "segments" = the true segment count, which may exceed its edges). Integer decisions on the same input:
-        every rank computes the same network."""
+        every rank computes the same network. With --road_graph_paths the segment labels are asked for too, rsu_segment_paths orders the
+        pixels of every stored segment of at most --max_path_length pixels along it, every edge gains "kind" and "path" (hostio.road_graph,
+        simplified at --road_graph_simplify) and every dict "unordered" = its branched and too long segments."""
         lines = self._centerlines_device(masks, threshold)   # (exactly 0.0 / 1.0, and they stay on the device)
         n, H, W = (int(v) for v in lines.shape)
-        cap, dev = int(getattr(self._options, "max_segments", 4096)), lines.device
+        opts = self._options
+        cap, dev, st = int(getattr(opts, "max_segments", 4096)), lines.device, mask_metrics.stream(lines.device)
         ws = mask_metrics.workspace("segments", (n, H, W), (cap,), dev, "road_graph (--save_road_graph): %d masks of %d x %d pixels are outside "
                                     "rsu_segments.h's limits (sides up to %d, n * H * W * 16 below 2 GiB): use smaller stacks"
                                     % (n, H, W, SEGMENTS_MAX_SIDE))
-        edges = torch.zeros((n, cap, 8), dtype=torch.int32, device=dev)
-        counts = torch.zeros((n, 4), dtype=torch.int32, device=dev)
-        node = torch.zeros((n, H, W), dtype=torch.int32, device=dev)
-        mask_metrics.line_segments(lines, 0.5, None, cap, edges, None, counts, None, None, node, None, None, ws, mask_metrics.stream(dev))
+
+        def zeros(*shape):
+            return torch.zeros(shape, dtype=torch.int32, device=dev)
+
+        edges, counts, node = zeros(n, cap, 8), zeros(n, 4), zeros(n, H, W)
+        ordered = bool(getattr(opts, "road_graph_paths", False))
+        seg = zeros(n, H, W) if ordered else None
+        mask_metrics.line_segments(lines, 0.5, None, cap, edges, None, counts, seg, None, node, None, None, ws, st)
+        if ordered:
+            max_len, eps = int(getattr(opts, "max_path_length", 4096)), float(getattr(opts, "road_graph_simplify", 0.0))
+            pws = mask_metrics.workspace("paths", (n, H, W), (cap, max_len), dev, "road_graph (--road_graph_paths): %d masks of %d x %d pixels "
+                                         "are outside rsu_paths.h's limits (sides up to %d, n * H * W * 16 below 2 GiB): use smaller stacks"
+                                         % (n, H, W, PATHS_MAX_SIDE))
+            paths, offsets, kind, info = zeros(n, H * W), zeros(n, cap + 1), zeros(n, cap), zeros(n, 4)
+            mask_metrics.segment_paths(seg, edges, counts, 0, max_len, H * W, paths, offsets, kind, None, info, pws, st)
+            paths, offsets, kind, info = (t.cpu().numpy() for t in (paths, offsets, kind, info))
         edges, counts, node = edges.cpu().numpy(), counts.cpu().numpy(), node.cpu().numpy()
         out = []
         for i in range(n):
-            g = hostio_road_graph(edges[i], int(counts[i, 0]), node[i], H, W)
+            g = hostio_road_graph(edges[i], int(counts[i, 0]), node[i], H, W, paths=(paths[i], offsets[i], kind[i]) if ordered else None)
             g["segments"] = int(counts[i, 0])
+            if ordered:
+                g["unordered"] = int(info[i, 3])
+                for e in g["edges"] if eps > 0.0 else ():
+                    if len(e["path"]) > 2:
+                        e["path"] = simplify_path(np.asarray(e["path"], np.int64), eps).tolist()
             out.append(g)
         return out
 
