@@ -2,16 +2,12 @@
 // pixel to the nearest valid pixel of the other class, by the separable transform in integer arithmetic, and the U-Net paper's weight
 // 1 + w0 exp(-D2 / (2 sigma^2)) from it. Two launches, no atomics, no floating-point reduction: every output is a pure function of the tile.
 //
-//   k_border_cols  threads across x (coalesced 8-byte label loads and 4-byte stores), one wave per 64 rows of a 64-column strip. A thread
-//                  keeps the two class masks of its 64 rows in registers; the down sweep (nearest valid pixel of each class at or above)
-//                  and the up sweep (at or below) of a column are then bit scans inside the chunk plus one carry per direction from the
-//                  other chunks of the column, handed over through LDS. Writes one word per pixel: g0 | g1 << 16, the vertical
-//                  distances to class 0 / class 1 (0 = the pixel itself has that class; 0xffff = the column has none).
-//   k_border_rows  one workgroup per row: the row's squared column distances of both classes staged in LDS, then every thread takes
-//                  min over x' of (x - x')^2 + g_other(x')^2, scanning outwards from its own column and stopping once (x - x')^2 alone
-//                  reaches the minimum found so far -- no later candidate can be smaller. A row without any finite distance to a class
-//                  (an all-background tile, the padding tiles of a validation pass) skips the scans for that class altogether.
+//   k_border_cols  edt.h's column pass over the two class masks (coalesced 8-byte label loads): g0 | g1 << 16, the vertical distances to
+//                  class 0 / class 1.
+//   k_border_rows  edt.h's row pass, every pixel against the OTHER class. A row without any finite distance to a class (an
+//                  all-background tile, the padding tiles of a validation pass) skips the scans for that class altogether.
 #include "border_map.h"
+#include "edt.h"
 
 // Every float32 operation below must be rounded on its own: the host mirror restates them one by one. hipcc contracts a * b + c into one
 // fma, also through __fmul_rn / __fadd_rn and under `#pragma clang fp contract(off)`: the Makefile compiles this file with
@@ -20,9 +16,6 @@
 namespace {
 
 constexpr int BM_INF = 0x7fffffff;      // rsu.h RSU_BORDER_D2_INF
-constexpr int BM_BIG = 0x40000000;      // "no pixel of that class in the column", as a square: BM_BIG + 1023^2 stays below 2^31
-constexpr unsigned BM_NONE = 0xffffu;   // the same in a packed word
-constexpr int BM_ABOVE = -0x20000, BM_BELOW = 0x40000;   // row numbers of "none above" / "none below": any distance to them is > 0xffff
 
 // exp(t) for t <= 0 in float32 with a FIXED sequence of IEEE operations (no contraction, no library call), so that the host mirror
 // (hostio.border_weight_map) reproduces every bit: k = rint(t log2 e), r = t - k ln2 (two steps), the degree-7 Taylor polynomial of
@@ -46,7 +39,7 @@ __device__ __forceinline__ float bm_exp(float t) {
 // grid N * nstrips (nstrips = ceil(W / 64)), block (64, ceil(H / 64)); LDS int [4][blockDim.y][64]
 __global__ void __launch_bounds__(1024) k_border_cols(const int64_t* __restrict__ labels, uint32_t* __restrict__ ws, int H, int W, int nstrips) {
     extern __shared__ int bm_lds[];
-    const int tx = threadIdx.x, k = threadIdx.y, CH = blockDim.y;
+    const int tx = threadIdx.x, k = threadIdx.y;
     const int n = blockIdx.x / nstrips;
     const int x = (blockIdx.x - n * nstrips) * 64 + tx, y0 = k * 64;
     const bool xin = x < W;
@@ -68,37 +61,7 @@ __global__ void __launch_bounds__(1024) k_border_cols(const int64_t* __restrict_
             m1 |= (unsigned long long)(in && l[j] == 1) << (i0 + j);
         }
     }
-    int* last0 = bm_lds;
-    int* last1 = last0 + CH * 64;
-    int* first0 = last1 + CH * 64;
-    int* first1 = first0 + CH * 64;
-    const int slot = k * 64 + tx;
-    last0[slot] = m0 ? y0 + 63 - __clzll((long long)m0) : BM_ABOVE;
-    last1[slot] = m1 ? y0 + 63 - __clzll((long long)m1) : BM_ABOVE;
-    first0[slot] = m0 ? y0 + __ffsll((long long)m0) - 1 : BM_BELOW;
-    first1[slot] = m1 ? y0 + __ffsll((long long)m1) - 1 : BM_BELOW;
-    __syncthreads();
-    int up0 = BM_ABOVE, up1 = BM_ABOVE, dn0 = BM_BELOW, dn1 = BM_BELOW;
-    for (int kk = 0; kk < k; ++kk) {
-        up0 = max(up0, last0[kk * 64 + tx]);
-        up1 = max(up1, last1[kk * 64 + tx]);
-    }
-    for (int kk = k + 1; kk < CH; ++kk) {
-        dn0 = min(dn0, first0[kk * 64 + tx]);
-        dn1 = min(dn1, first1[kk * 64 + tx]);
-    }
-    if (!xin) return;
-    const int rows = min(64, H - y0);
-    for (int i = 0; i < rows; ++i) {
-        const int y = y0 + i;
-        const unsigned long long upto = ~0ull >> (63 - i);
-        const unsigned long long lo0 = m0 & upto, lo1 = m1 & upto, hi0 = m0 >> i, hi1 = m1 >> i;
-        const int a0 = lo0 ? y0 + 63 - __clzll((long long)lo0) : up0, b0 = hi0 ? y + __ffsll((long long)hi0) - 1 : dn0;
-        const int a1 = lo1 ? y0 + 63 - __clzll((long long)lo1) : up1, b1 = hi1 ? y + __ffsll((long long)hi1) - 1 : dn1;
-        const unsigned g0 = (unsigned)min(min(y - a0, b0 - y), (int)BM_NONE);
-        const unsigned g1 = (unsigned)min(min(y - a1, b1 - y), (int)BM_NONE);
-        ws[img + (size_t)y * W + x] = g0 | (g1 << 16);
-    }
+    edt_cols_store(m0, m1, bm_lds, ws, img, x, H, W);
 }
 
 // grid N * H (one workgroup per row), block a multiple of 64; LDS int [2][Wp], Wp = W rounded up to 32 (lanes that read different classes then never share a bank)
@@ -106,30 +69,15 @@ __global__ void __launch_bounds__(512) k_border_rows(const uint32_t* __restrict_
                                                      int32_t* __restrict__ d2out, int W, int Wp, float w0, float neg_inv_2s2) {
     extern __shared__ int bm_lds[];
     const size_t row = (size_t)blockIdx.x * W;
-    int any = 0;   // bit c: some column of this row has a pixel of class c
-    for (int x = threadIdx.x; x < W; x += blockDim.x) {
-        const unsigned u = ws[row + x];
-        const int g0 = (int)(u & 0xffffu), g1 = (int)(u >> 16);
-        bm_lds[x] = g0 == (int)BM_NONE ? BM_BIG : g0 * g0;
-        bm_lds[Wp + x] = g1 == (int)BM_NONE ? BM_BIG : g1 * g1;
-        any |= (g0 != (int)BM_NONE ? 1 : 0) | (g1 != (int)BM_NONE ? 2 : 0);
-    }
-    any = (__syncthreads_or(any & 1) ? 1 : 0) | (__syncthreads_or(any & 2) ? 2 : 0);   // (also the barrier behind the staging)
+    const int any = edt_stage(ws, row, bm_lds, W, Wp, blockDim.x);   // bit c: some column of this row has a pixel of class c
     for (int x = threadIdx.x; x < W; x += blockDim.x) {
         const int cls = bm_lds[x] == 0 ? 0 : (bm_lds[Wp + x] == 0 ? 1 : 2);   // distance 0 to a class: the pixel has it; neither: ignored
         int d2 = BM_INF;
         float o = 0.0f;
         if (cls < 2) {
-            const int* other = bm_lds + (cls ? 0 : Wp);
-            int best = other[x];
-            if ((any >> (1 - cls)) & 1) {
-                const int dmax = max(x, W - 1 - x);
-                // (a clamped index re-reads the edge column with a larger d: never below what that column already gave)
-                for (int d = 1; d <= dmax && d * d < best; ++d)
-                    best = min(best, min(other[max(x - d, 0)], other[min(x + d, W - 1)]) + d * d);
-            }
+            const int best = edt_scan(bm_lds + (cls ? 0 : Wp), x, W, (any >> (1 - cls)) & 1);
             float border = 1.0f;
-            if (best < BM_BIG) {
+            if (best < EDT_BIG) {
                 d2 = best;
                 border = __fadd_rn(1.0f, __fmul_rn(w0, bm_exp(__fmul_rn((float)d2, neg_inv_2s2))));
             }

@@ -1,19 +1,17 @@
 // Mask distances (include/rsu_distance.h): the exact squared Euclidean distance of every pixel to the predicted mask P = {counted and
 // prob >= threshold} and to the truth mask T = {label == 1}, by the separable transform in integer arithmetic, and the histogram of
-// those distances over the pixels of the other mask. The shape is border_map.hip's; the masks are built from prob and labels64 directly.
+// those distances over the pixels of the other mask. The transform itself is edt.h's, shared with border_map.hip; the masks are
+// built from prob and labels64 directly.
 //
-//   k_dist_cols   threads across x (coalesced label and probability loads, 4-byte stores), one wave per 64 rows of a 64-column strip. A
-//                 thread keeps both masks of its 64 rows in registers; the nearest mask pixel at or above and at or below every row is a
-//                 bit scan inside the chunk plus one carry per direction from the other chunks of the column, handed over through LDS.
-//                 Writes one word per pixel: gT | gP << 16, the vertical distances to T / P (0 = the pixel itself; 0xffff = none).
-//   k_dist_rows   one workgroup per row: the row's squared column distances staged in LDS, every thread takes min over x' of
-//                 (x - x')^2 + g(x')^2, scanning outwards and stopping once (x - x')^2 alone reaches the minimum so far. Exact int32 out.
+//   k_dist_cols   edt.h's column pass (coalesced label and probability loads, 4-byte stores): gT | gP << 16.
+//   k_dist_rows   edt.h's row pass. Exact int32 out.
 //   k_dist_hist   DT_HIST_ROWS rows per workgroup. Nothing past the last bin is needed: the staged squares are those of min(g, 63), as
 //                 16-bit words, and the scan ends by d = 62 whatever the data. Only pixels of P look up T and only pixels of T look up P;
 //                 bins are counted with LDS integer atomics (the first and the last bin in registers first: most pixels land there),
 //                 and one 64-bit integer atomic add per non-zero bin per workgroup goes to acc. Integer adds commute: acc is a function
 //                 of the inputs alone.
 #include "distance.h"
+#include "edt.h"
 
 // rows of an image per workgroup of k_dist_hist: more rows, fewer flush atomics and fewer, longer workgroups (tools/bench_distance.py
 // times 1, 2, 4 and 8 from A/B builds: make VARIANT=rowsK EXTRA=-DDT_HIST_ROWS=K)
@@ -24,9 +22,6 @@
 namespace {
 
 constexpr int DT_NONE = 0x7fffffff;     // rsu_distance.h RSU_DIST_NONE
-constexpr int DT_BIG = 0x40000000;      // "no mask pixel in the column", as a square: DT_BIG + 1023^2 stays below 2^31
-constexpr unsigned DT_GNONE = 0xffffu;  // the same in a packed word
-constexpr int DT_ABOVE = -0x20000, DT_BELOW = 0x40000;   // row numbers of "none above" / "none below": any distance to them is > 0xffff
 constexpr int DT_LAST = DT_BINS - 1;    // the saturating bin
 constexpr int DT_HIST_THREADS = 256;
 
@@ -35,7 +30,7 @@ template <bool LAB>
 __global__ void __launch_bounds__(1024) k_dist_cols(const float* __restrict__ prob, float threshold, const int64_t* __restrict__ labels,
                                                     uint32_t* __restrict__ ws, int H, int W, int nstrips) {
     extern __shared__ int dt_lds[];
-    const int tx = threadIdx.x, k = threadIdx.y, CH = blockDim.y;
+    const int tx = threadIdx.x, k = threadIdx.y;
     const int n = blockIdx.x / nstrips;
     const int x = (blockIdx.x - n * nstrips) * 64 + tx, y0 = k * 64;
     const bool xin = x < W;
@@ -61,37 +56,7 @@ __global__ void __launch_bounds__(1024) k_dist_cols(const float* __restrict__ pr
             mp |= (unsigned long long)(in && counted && p[j] >= threshold) << (i0 + j);   // (NaN compares false)
         }
     }
-    int* lastt = dt_lds;
-    int* lastp = lastt + CH * 64;
-    int* firstt = lastp + CH * 64;
-    int* firstp = firstt + CH * 64;
-    const int slot = k * 64 + tx;
-    lastt[slot] = mt ? y0 + 63 - __clzll((long long)mt) : DT_ABOVE;
-    lastp[slot] = mp ? y0 + 63 - __clzll((long long)mp) : DT_ABOVE;
-    firstt[slot] = mt ? y0 + __ffsll((long long)mt) - 1 : DT_BELOW;
-    firstp[slot] = mp ? y0 + __ffsll((long long)mp) - 1 : DT_BELOW;
-    __syncthreads();
-    int upt = DT_ABOVE, upp = DT_ABOVE, dnt = DT_BELOW, dnp = DT_BELOW;
-    for (int kk = 0; kk < k; ++kk) {
-        upt = max(upt, lastt[kk * 64 + tx]);
-        upp = max(upp, lastp[kk * 64 + tx]);
-    }
-    for (int kk = k + 1; kk < CH; ++kk) {
-        dnt = min(dnt, firstt[kk * 64 + tx]);
-        dnp = min(dnp, firstp[kk * 64 + tx]);
-    }
-    if (!xin) return;
-    const int rows = min(64, H - y0);
-    for (int i = 0; i < rows; ++i) {
-        const int y = y0 + i;
-        const unsigned long long upto = ~0ull >> (63 - i);
-        const unsigned long long lot = mt & upto, lop = mp & upto, hit = mt >> i, hip_ = mp >> i;
-        const int at = lot ? y0 + 63 - __clzll((long long)lot) : upt, bt = hit ? y + __ffsll((long long)hit) - 1 : dnt;
-        const int ap = lop ? y0 + 63 - __clzll((long long)lop) : upp, bp = hip_ ? y + __ffsll((long long)hip_) - 1 : dnp;
-        const unsigned gt = (unsigned)min(min(y - at, bt - y), (int)DT_GNONE);
-        const unsigned gp = (unsigned)min(min(y - ap, bp - y), (int)DT_GNONE);
-        ws[img + (size_t)y * W + x] = gt | (gp << 16);
-    }
+    edt_cols_store(mt, mp, dt_lds, ws, img, x, H, W);
 }
 
 // grid N * H (one workgroup per row), block a multiple of 64; LDS int [2][Wp], Wp = W rounded up to 32
@@ -99,28 +64,14 @@ __global__ void __launch_bounds__(512) k_dist_rows(const uint32_t* __restrict__ 
                                                    int W, int Wp) {
     extern __shared__ int dt_lds[];
     const size_t row = (size_t)blockIdx.x * W;
-    int any = 0;   // bit 0: some column of this row has a pixel of T; bit 1: of P
+    const int any = edt_stage(ws, row, dt_lds, W, Wp, blockDim.x);   // bit 0: some column of this row has a pixel of T; bit 1: of P
     for (int x = threadIdx.x; x < W; x += blockDim.x) {
-        const unsigned u = ws[row + x];
-        const int gt = (int)(u & 0xffffu), gp = (int)(u >> 16);
-        dt_lds[x] = gt == (int)DT_GNONE ? DT_BIG : gt * gt;
-        dt_lds[Wp + x] = gp == (int)DT_GNONE ? DT_BIG : gp * gp;
-        any |= (gt != (int)DT_GNONE ? 1 : 0) | (gp != (int)DT_GNONE ? 2 : 0);
-    }
-    any = (__syncthreads_or(any & 1) ? 1 : 0) | (__syncthreads_or(any & 2) ? 2 : 0);   // (also the barrier behind the staging)
-    for (int x = threadIdx.x; x < W; x += blockDim.x) {
-        const int dmax = max(x, W - 1 - x);
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
             int32_t* out = c ? d2_pred : d2_true;
             if (!out) continue;
-            const int* g2 = dt_lds + c * Wp;
-            int best = g2[x];
-            if ((any >> c) & 1) {
-                // (a clamped index re-reads the edge column with a larger d: never below what that column already gave)
-                for (int d = 1; d <= dmax && d * d < best; ++d) best = min(best, min(g2[max(x - d, 0)], g2[min(x + d, W - 1)]) + d * d);
-            }
-            out[row + x] = best < DT_BIG ? best : DT_NONE;
+            const int best = edt_scan(dt_lds + c * Wp, x, W, (any >> c) & 1);
+            out[row + x] = best < EDT_BIG ? best : DT_NONE;
         }
     }
 }
@@ -166,10 +117,7 @@ __global__ void __launch_bounds__(DT_HIST_THREADS) k_dist_hist(const uint32_t* _
         }
         const unsigned short* other = in_p ? rowt : rowp;
         const int side = in_p ? 0 : 1;
-        int best = other[x];
-        const int dmax = max(x, W - 1 - x);
-        for (int d = 1; d <= dmax && d * d < best; ++d)   // (best <= 63^2: ends by d = 62)
-            best = min(best, min((int)other[max(x - d, 0)], (int)other[min(x + d, W - 1)]) + d * d);
+        const int best = edt_scan(other, x, W);   // (best <= 63^2: ends by d = 62)
         if (best > (DT_LAST - 1) * (DT_LAST - 1)) {
             last_p += in_p ? 1u : 0u;
             last_t += in_p ? 0u : 1u;
@@ -189,10 +137,8 @@ __global__ void __launch_bounds__(DT_HIST_THREADS) k_dist_hist(const uint32_t* _
 hipError_t dt_cols(const float* prob, float threshold, const int64_t* labels, void* ws, int N, int H, int W, hipStream_t st) {
     const int CH = (H + 63) / 64, nstrips = (W + 63) / 64;
     const size_t lds = (size_t)4 * CH * 64 * sizeof(int);
-    if (labels)
-        hipLaunchKernelGGL(k_dist_cols<true>, dim3(N * nstrips), dim3(64, CH), lds, st, prob, threshold, labels, (uint32_t*)ws, H, W, nstrips);
-    else
-        hipLaunchKernelGGL(k_dist_cols<false>, dim3(N * nstrips), dim3(64, CH), lds, st, prob, threshold, labels, (uint32_t*)ws, H, W, nstrips);
+    hipLaunchKernelGGL(labels ? k_dist_cols<true> : k_dist_cols<false>, dim3(N * nstrips), dim3(64, CH), lds, st, prob, threshold, labels,
+                       (uint32_t*)ws, H, W, nstrips);
     return hipGetLastError();
 }
 

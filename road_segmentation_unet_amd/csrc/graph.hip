@@ -1,24 +1,18 @@
 // Centre-line pruning and node classification (include/rsu_graph.h): Gonzalez & Woods' morphological pruning of the predicted mask
 // P = {counted and prob >= threshold} and of the truth mask T = {label == 1} -- L rounds that delete every END pixel, the END pixels of
 // what is left, L rounds of a dilation of those inside the mask -- and the ends, isolated pixels and junction pixels of the result,
-// evaluated bit-sliced on bit rows. The layout is thin.hip's (copied, not shared: thin.o stays what it was).
+// evaluated bit-sliced on bit rows: the layout, the init launch and the step tile are those of bitrows.h, which thin.hip shares.
 //
-// ws holds bit planes of [N][2][H][Wq] 64-bit words (side 0 = P, side 1 = T), Wq = ceil(W / GR_CORE): a word keeps GR_CORE pixels of a
-// row in its low bits (bit i = pixel xw * GR_CORE + i), the bits above and the pixels past W stay 0. Plane O keeps the masks A; with
-// L > 0 planes X0 and X1 are the working copies of the delete phase (step s reads X[s & 1] and writes the other) and planes E0 and E1
-// those of the regrow phase (launch g writes E[g & 1]). Behind them sit the counters, [D + G][N][2], D = ceil(L / GR_R) delete and
-// G = ceil((L + 1) / GR_R) regrow launches.
+// ws holds bit planes in the layout of bitrows.h (CORE = GR_CORE). Plane O keeps the masks A; with L > 0 planes X0 and X1 are the working
+// copies of the delete phase (step s reads X[s & 1] and writes the other) and planes E0 and E1 those of the regrow phase (launch g
+// writes E[g & 1]). Behind them sit the counters, [D + G][N][2], D = ceil(L / GR_R) delete and G = ceil((L + 1) / GR_R) regrow launches.
 //
-//   k_graph_init    one workgroup per image row: coalesced label and probability loads, one ballot per wave and mask into LDS as plain
-//                   64-pixel words, then one thread per plane word cuts its GR_CORE pixels out. Writes plane O (and X0); clears the counters.
-//   k_graph_delete  one workgroup of GR_ROWS threads per image side, row tile and word column: a thread holds ONE 64-bit window of one
-//                   row -- GR_HALO pixels of the word to the left, the word's GR_CORE pixels, GR_HALO pixels of the word to the right --
-//                   so east and west are shifts of its own register and north and south are its neighbours' registers, handed over
-//                   through LDS (two buffers: one barrier per round). What is shifted in at the window's rim is wrong; the error walks
-//                   one pixel per round and after GR_R of them has not left the halo. Core rows store their core bits. Deleted core
-//                   pixels are counted per thread, summed in LDS and added to the launch's own counter with one integer atomic per
-//                   workgroup; the launch behind reads it and returns where it is 0: that image side was at its fixed point and both
-//                   planes hold it.
+//   k_graph_init    bitrows.h's init launch. Writes plane O (and X0); clears the counters.
+//   k_graph_delete  bitrows.h's step tile: east and west are shifts of a thread's own window and north and south are its neighbours'
+//                   registers, handed over through LDS (two buffers: one barrier per round). What is shifted in at the window's rim is
+//                   wrong; the error walks one pixel per round and after GR_R of them has not left the halo. Deleted core pixels are
+//                   counted per thread and added to the launch's own counter; the launch behind reads it and returns where it is 0:
+//                   that image side was at its fixed point and both planes hold it.
 //   k_graph_regrow  the same tile. A thread holds its window of E and the fixed window of A. The FIRST launch forms E = END(X1) from
 //                   the delete phase's plane, which costs one pixel of halo, and carries GR_R - 1 rounds; the others carry GR_R. A
 //                   launch counts the core pixels it added to E; where the count before it is 0 (for the first: the last delete
@@ -27,6 +21,7 @@
 //                   any, follows from the counters), one thread per word classifies its GR_CORE pixels, then every thread writes pixels.
 //                   The eight counts go to acc through LDS integer atomics, one 64-bit atomic add per non-zero count per workgroup.
 #include "graph.h"
+#include "bitrows.h"
 
 #ifndef GR_ROWS
 #define GR_ROWS 128   // rows of a step tile, halo included: GR_ROWS - 2 * GR_HALO core rows
@@ -34,7 +29,8 @@
 
 namespace {
 
-typedef unsigned long long u64;
+namespace br = bitrows;
+using br::u64;
 constexpr int GR_INIT_THREADS = 256;
 constexpr int GR_FIN_THREADS = 256, GR_FIN_ROWS = 4;
 constexpr int GR_CROWS = GR_ROWS - 2 * GR_HALO;
@@ -42,44 +38,13 @@ constexpr u64 GR_COREBITS = (1ull << GR_CORE) - 1;
 constexpr int GR_MAX_WQ = (GR_MAX_SIDE + GR_CORE - 1) / GR_CORE;
 static_assert(GR_CROWS >= 1 && GR_ROWS % 64 == 0, "tile geometry");
 
-// grid N * H, block GR_INIT_THREADS. LAB: labels given (else every pixel counted, T empty). plane_x: nullptr without a prune phase
+// grid N * H, block GR_INIT_THREADS: bitrows.h init_row. plane_x: nullptr without a prune phase
 template <bool LAB>
 __global__ void __launch_bounds__(GR_INIT_THREADS) k_graph_init(const float* __restrict__ prob, float threshold,
                                                                 const int64_t* __restrict__ labels, u64* __restrict__ plane_o,
                                                                 u64* __restrict__ plane_x, uint32_t* __restrict__ counters, int nlaunch,
                                                                 int N, int H, int W, int Wq) {
-    __shared__ u64 bits[2][GR_MAX_SIDE / 64 + GR_INIT_THREADS / 64 + 1];   // (a wave past W still stores its empty ballot)
-    const int n = blockIdx.x / H, y = blockIdx.x - n * H, tid = threadIdx.x;
-    if (y == 0)   // the image's own counters, two per step launch
-        for (int i = tid; i < 2 * nlaunch; i += GR_INIT_THREADS) counters[((size_t)(i >> 1) * N + n) * 2 + (i & 1)] = 0;
-    for (int i = tid; i < 2 * (int)(sizeof(bits[0]) / sizeof(u64)); i += GR_INIT_THREADS) (&bits[0][0])[i] = 0;
-    __syncthreads();
-    const size_t row = ((size_t)n * H + y) * W;
-    for (int x0 = 0; x0 < W; x0 += GR_INIT_THREADS) {
-        const int x = x0 + tid;
-        const bool in = x < W;
-        const size_t at = row + (in ? x : W - 1);   // (lanes past the row load a valid address and drop the value)
-        const int64_t l = LAB ? labels[at] : 0;
-        const float p = prob[at];
-        const bool counted = l == 0 || l == 1;
-        const u64 mp = __ballot(in && counted && p >= threshold);   // (NaN compares false)
-        const u64 mt = __ballot(LAB && in && l == 1);
-        if ((tid & 63) == 0) {
-            bits[0][x >> 6] = mp;
-            bits[1][x >> 6] = mt;
-        }
-    }
-    __syncthreads();
-    for (int i = tid; i < 2 * Wq; i += GR_INIT_THREADS) {
-        const int side = i >= Wq ? 1 : 0, xw = i - side * Wq;
-        const int b = xw * GR_CORE, w0 = b >> 6, sh = b & 63;
-        u64 v = bits[side][w0] >> sh;
-        if (sh) v |= bits[side][w0 + 1] << (64 - sh);
-        v &= GR_COREBITS;
-        const size_t o = (((size_t)n * 2 + side) * H + y) * Wq + xw;
-        plane_o[o] = v;
-        if (plane_x) plane_x[o] = v;
-    }
+    br::init_row<LAB, GR_CORE, GR_INIT_THREADS, GR_MAX_SIDE>(prob, threshold, labels, plane_o, plane_x, counters, nlaunch, N, H, W, Wq);
 }
 
 // the sum of eight one-bit planes, bit-sliced: bit 0, bit 1 and "4 or more" of the count (full and half adders)
@@ -94,13 +59,12 @@ __device__ __forceinline__ GrCount gr_sum8(u64 a1, u64 a2, u64 a3, u64 a4, u64 a
     const u64 x5 = c1 ^ c2, s5 = x5 ^ c3, c5 = (c1 & c2) | (x5 & c3);
     return {b0, s5 ^ c4, c5 | (s5 & c4)};
 }
-// the neighbours of window c clockwise from north; u and d are the windows of the rows above and below. Bit i + 1 is the pixel to the
-// east of bit i. n8: the number of set neighbours; X: the number of 0 -> 1 steps around the cycle
+// of the neighbours of window c (bitrows.h ring): n8, the number set; X, the number of 0 -> 1 steps around the cycle
 struct GrNodes {
     GrCount n8, X;
 };
 __device__ __forceinline__ GrNodes gr_nodes(u64 u, u64 c, u64 d) {
-    const u64 p2 = u, p3 = u >> 1, p4 = c >> 1, p5 = d >> 1, p6 = d, p7 = d << 1, p8 = c << 1, p9 = u << 1;
+    const auto [p2, p3, p4, p5, p6, p7, p8, p9] = br::ring(u, c, d);
     GrNodes r;
     r.n8 = gr_sum8(p2, p3, p4, p5, p6, p7, p8, p9);
     r.X = gr_sum8(~p2 & p3, ~p3 & p4, ~p4 & p5, ~p5 & p6, ~p6 & p7, ~p7 & p8, ~p8 & p9, ~p9 & p2);
@@ -112,31 +76,16 @@ __device__ __forceinline__ u64 gr_end(u64 u, u64 c, u64 d) {
     return c & ~(k.X.b1 | k.X.hi) & ~k.n8.hi;
 }
 
-// the window of row r (a row of a plane, Wq words) around word xw
-__device__ __forceinline__ u64 gr_window(const u64* __restrict__ r, int xw, int Wq) {
-    const u64 lw = xw > 0 ? r[xw - 1] : 0, rw = xw + 1 < Wq ? r[xw + 1] : 0;
-    return (lw >> (GR_CORE - GR_HALO)) | (r[xw] << GR_HALO) | (rw << (GR_HALO + GR_CORE));
-}
-
 // grid N * nsides * ntiles * Wq (ntiles = ceil(H / GR_CROWS)), block GR_ROWS. prev: the counters of the launch before (nullptr for the
 // first step); cnt: this launch's. rounds in [1, GR_R].
 __global__ void __launch_bounds__(GR_ROWS) k_graph_delete(const u64* __restrict__ in, u64* __restrict__ out, const uint32_t* __restrict__ prev,
                                                           uint32_t* __restrict__ cnt, int H, int Wq, int rounds, int nsides, int ntiles) {
     __shared__ u64 rows[2][GR_ROWS + 2];
-    __shared__ unsigned red;
-    const int per = ntiles * Wq, z = blockIdx.x / per, rest = blockIdx.x - z * per;
-    const int n = z / nsides, slot = n * 2 + (z - n * nsides);
-    if (prev && prev[slot] == 0) return;   // (the same for the whole workgroup) a fixed point: out already holds it
-    const int tid = threadIdx.x, ty = rest / Wq, xw = rest - ty * Wq;
-    const int y = ty * GR_CROWS - GR_HALO + tid;
-    const size_t base = (size_t)slot * H * Wq;
-    u64 c = 0;
-    if (y >= 0 && y < H) c = gr_window(in + base + (size_t)y * Wq, xw, Wq);
-    if (tid == 0) {
-        rows[0][0] = rows[1][0] = rows[0][GR_ROWS + 1] = rows[1][GR_ROWS + 1] = 0;
-        red = 0;
-    }
-    const bool core_row = tid >= GR_HALO && tid < GR_ROWS - GR_HALO && y < H;
+    __shared__ unsigned red[1];
+    const br::Tile t = br::tile_open<GR_HALO, GR_ROWS>(rows, red, prev, H, Wq, nsides, ntiles);
+    if (t.skip) return;
+    const int tid = threadIdx.x;
+    u64 c = t.in_image ? br::window<GR_CORE, GR_HALO>(in + t.row, t.xw, Wq) : 0;
     const u64 core = GR_COREBITS << GR_HALO;
     unsigned total = 0;
     for (int it = 0; it < rounds; ++it) {
@@ -147,12 +96,7 @@ __global__ void __launch_bounds__(GR_ROWS) k_graph_delete(const u64* __restrict_
         c &= ~del;
         total += __popcll(del & core);
     }
-    if (core_row) {
-        out[base + (size_t)y * Wq + xw] = (c >> GR_HALO) & GR_COREBITS;
-        if (total) atomicAdd(&red, total);
-    }
-    __syncthreads();
-    if (tid == 0 && red) atomicAdd(&cnt[slot], red);
+    br::tile_close<GR_CORE, GR_HALO>(t, out, c, red, total, cnt);
 }
 
 // grid and block as k_graph_delete. FIRST: `in` is the delete phase's plane X1 and E starts as END(X1); else `in` is the E plane of the
@@ -162,23 +106,15 @@ __global__ void __launch_bounds__(GR_ROWS) k_graph_regrow(const u64* __restrict_
                                                           const uint32_t* __restrict__ prev, uint32_t* __restrict__ cnt, int H, int Wq,
                                                           int rounds, int nsides, int ntiles) {
     __shared__ u64 rows[2][GR_ROWS + 2];
-    __shared__ unsigned red;
-    const int per = ntiles * Wq, z = blockIdx.x / per, rest = blockIdx.x - z * per;
-    const int n = z / nsides, slot = n * 2 + (z - n * nsides);
-    if (prev[slot] == 0) return;   // (the same for the whole workgroup) nothing to grow, or E at its fixed point: see k_graph_final
-    const int tid = threadIdx.x, ty = rest / Wq, xw = rest - ty * Wq;
-    const int y = ty * GR_CROWS - GR_HALO + tid;
-    const size_t base = (size_t)slot * H * Wq;
+    __shared__ unsigned red[1];
+    const br::Tile t = br::tile_open<GR_HALO, GR_ROWS>(rows, red, prev, H, Wq, nsides, ntiles);
+    if (t.skip) return;   // nothing to grow, or E at its fixed point: see k_graph_final
+    const int tid = threadIdx.x;
     u64 e = 0, a = 0;
-    if (y >= 0 && y < H) {
-        e = gr_window(in + base + (size_t)y * Wq, xw, Wq);
-        a = gr_window(mask + base + (size_t)y * Wq, xw, Wq);
+    if (t.in_image) {
+        e = br::window<GR_CORE, GR_HALO>(in + t.row, t.xw, Wq);
+        a = br::window<GR_CORE, GR_HALO>(mask + t.row, t.xw, Wq);
     }
-    if (tid == 0) {
-        rows[0][0] = rows[1][0] = rows[0][GR_ROWS + 1] = rows[1][GR_ROWS + 1] = 0;
-        red = 0;
-    }
-    const bool core_row = tid >= GR_HALO && tid < GR_ROWS - GR_HALO && y < H;
     const u64 core = GR_COREBITS << GR_HALO;
     unsigned before = 0;
     if (FIRST) {
@@ -195,13 +131,7 @@ __global__ void __launch_bounds__(GR_ROWS) k_graph_regrow(const u64* __restrict_
         const u64 v = buf[tid] | e | buf[tid + 2];
         e = a & (v | (v << 1) | (v >> 1));
     }
-    if (core_row) {
-        out[base + (size_t)y * Wq + xw] = (e >> GR_HALO) & GR_COREBITS;
-        const unsigned grown = __popcll(e & core) - before;
-        if (grown) atomicAdd(&red, grown);
-    }
-    __syncthreads();
-    if (tid == 0 && red) atomicAdd(&cnt[slot], red);
+    br::tile_close<GR_CORE, GR_HALO>(t, out, e, red, t.core_row ? __popcll(e & core) - before : 0u, cnt);
 }
 
 // grid N * nblk (nblk = ceil(H / GR_FIN_ROWS)), block GR_FIN_THREADS. x1: the plane behind the delete phase (plane O without one);
@@ -269,46 +199,38 @@ __global__ void __launch_bounds__(GR_FIN_THREADS) k_graph_final(const u64* __res
     for (int r = 0; r < rows; ++r) {
         const size_t row = ((size_t)n * H + y0 + r) * W;
         for (int x = tid; x < W; x += GR_FIN_THREADS) {
-            const int xw = x / GR_CORE, b = x - xw * GR_CORE;
-            if (out_pred) out_pred[row + x] = ((ow[0][0][r][xw] >> b) & 1) ? 1.0f : 0.0f;
-            if (junc_pred) junc_pred[row + x] = ((ow[0][1][r][xw] >> b) & 1) ? 1.0f : 0.0f;
+            if (out_pred) out_pred[row + x] = br::pixel<GR_CORE>(ow[0][0][r], x) ? 1.0f : 0.0f;
+            if (junc_pred) junc_pred[row + x] = br::pixel<GR_CORE>(ow[0][1][r], x) ? 1.0f : 0.0f;
             if (LAB && (out_true || junc_true)) {
                 const int64_t l = labels[row + x];   // (read before the same thread writes it: out_true may be labels)
                 const bool counted = l == 0 || l == 1;
-                if (junc_true) junc_true[row + x] = counted ? (int64_t)((ow[1][1][r][xw] >> b) & 1) : l;
-                if (out_true) out_true[row + x] = counted ? (int64_t)((ow[1][0][r][xw] >> b) & 1) : l;
+                if (junc_true) junc_true[row + x] = counted ? (int64_t)br::pixel<GR_CORE>(ow[1][1][r], x) : l;
+                if (out_true) out_true[row + x] = counted ? (int64_t)br::pixel<GR_CORE>(ow[1][0][r], x) : l;
             }
         }
     }
     if (acc && tid < 8 && sums[tid]) atomicAdd(&acc[tid], (u64)sums[tid]);
 }
 
-inline int gr_wq(int W) { return (W + GR_CORE - 1) / GR_CORE; }
 inline int gr_delete_launches(int L) { return (L + GR_R - 1) / GR_R; }
 inline int gr_regrow_launches(int L) { return L ? (L + 1 + GR_R - 1) / GR_R : 0; }
-inline size_t gr_plane_words(int N, int H, int W) { return (size_t)N * 2 * H * gr_wq(W); }
-inline size_t gr_counters(int N, int L) { return (size_t)(gr_delete_launches(L) + gr_regrow_launches(L)) * N * 2; }
-
 }  // namespace
 
 size_t gr_ws_bytes(int N, int H, int W, int min_branch) {
-    return (min_branch ? 5 : 1) * gr_plane_words(N, H, W) * sizeof(u64) + (gr_counters(N, min_branch) * sizeof(uint32_t) + 7) / 8 * 8;
+    return (min_branch ? 5 : 1) * br::plane_words<GR_CORE>(N, H, W) * sizeof(u64) +
+           br::counter_bytes((size_t)(gr_delete_launches(min_branch) + gr_regrow_launches(min_branch)) * N * 2);
 }
 
 hipError_t gr_skeleton_graph(const float* prob, float threshold, const int64_t* labels, int min_branch, float* out_pred, int64_t* out_true,
                              float* junc_pred, int64_t* junc_true, unsigned long long* acc, void* ws, int N, int H, int W, hipStream_t st) {
-    const int Wq = gr_wq(W), L = min_branch, D = gr_delete_launches(L), G = gr_regrow_launches(L), nsides = labels ? 2 : 1;
-    const size_t words = gr_plane_words(N, H, W);
+    const int Wq = br::wq<GR_CORE>(W), L = min_branch, D = gr_delete_launches(L), G = gr_regrow_launches(L), nsides = labels ? 2 : 1;
+    const size_t words = br::plane_words<GR_CORE>(N, H, W);
     u64* plane_o = (u64*)ws;
     u64* px[2] = {plane_o + words, plane_o + 2 * words};
     u64* pe[2] = {plane_o + 3 * words, plane_o + 4 * words};
     uint32_t* counters = (uint32_t*)(plane_o + 5 * words);   // (used with L > 0 only)
-    if (labels)
-        hipLaunchKernelGGL(k_graph_init<true>, dim3(N * H), dim3(GR_INIT_THREADS), 0, st, prob, threshold, labels, plane_o,
-                           L ? px[0] : (u64*)nullptr, counters, D + G, N, H, W, Wq);
-    else
-        hipLaunchKernelGGL(k_graph_init<false>, dim3(N * H), dim3(GR_INIT_THREADS), 0, st, prob, threshold, labels, plane_o,
-                           L ? px[0] : (u64*)nullptr, counters, D + G, N, H, W, Wq);
+    hipLaunchKernelGGL(labels ? k_graph_init<true> : k_graph_init<false>, dim3(N * H), dim3(GR_INIT_THREADS), 0, st, prob, threshold, labels,
+                       plane_o, L ? px[0] : (u64*)nullptr, counters, D + G, N, H, W, Wq);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const int ntiles = (H + GR_CROWS - 1) / GR_CROWS;
@@ -340,11 +262,7 @@ hipError_t gr_skeleton_graph(const float* prob, float threshold, const int64_t* 
     const dim3 fgrid(N * nblk);
     const u64* x1 = L ? px[D & 1] : plane_o;
     const uint32_t* cn = L ? counters : nullptr;
-    if (labels)
-        hipLaunchKernelGGL(k_graph_final<true>, fgrid, dim3(GR_FIN_THREADS), 0, st, x1, (const u64*)pe[0], (const u64*)pe[1], cn, D, G, labels,
-                           out_pred, out_true, junc_pred, junc_true, (u64*)acc, N, H, W, Wq, nblk);
-    else
-        hipLaunchKernelGGL(k_graph_final<false>, fgrid, dim3(GR_FIN_THREADS), 0, st, x1, (const u64*)pe[0], (const u64*)pe[1], cn, D, G, labels,
-                           out_pred, out_true, junc_pred, junc_true, (u64*)acc, N, H, W, Wq, nblk);
+    hipLaunchKernelGGL(labels ? k_graph_final<true> : k_graph_final<false>, fgrid, dim3(GR_FIN_THREADS), 0, st, x1, (const u64*)pe[0],
+                       (const u64*)pe[1], cn, D, G, labels, out_pred, out_true, junc_pred, junc_true, (u64*)acc, N, H, W, Wq, nblk);
     return hipGetLastError();
 }

@@ -525,6 +525,8 @@ static bool keep_ok(float keep) { return keep > 0.f && keep <= 1.f; }
 // both kinds of launch, so nothing is gained by a pool or a head that takes what the convs around it refuse -- and the 32-bit dropout
 // counters and the int products of the pool kernels (elementwise.hip) then stay in range by construction.
 static bool too_big(long bytes) { return bytes >= 0x7ffffff0L; }
+// the batch and the image sides of a mask tool: at least 1, the sides at most max_side
+static bool dims_ok(int N, int H, int W, int max_side) { return N >= 1 && H >= 1 && W >= 1 && H <= max_side && W <= max_side; }
 extern "C" int rsu_color_adjust_fwd(const float* x, const float* w, const float* b, void* out16, long npix, float keep, unsigned key,
                                     rsu_stream_t stream) {
     if (!x || !w || !b || !out16 || npix < 1 || !keep_ok(keep)) return RSU_EINVAL;
@@ -1723,36 +1725,33 @@ extern "C" int rsu_components_pair_count(const float* prob, float threshold, con
 }
 // ---- mask distances (rsu_distance.h): the separable exact distance transform of the predicted and the truth mask, and its histogram
 static_assert(RSU_DIST_MAX_SIDE == DT_MAX_SIDE && RSU_DIST_BINS == DT_BINS, "rsu_distance.h and distance.h must agree on the limits");
-static bool distance_size_ok(int N, int H, int W) { return N >= 1 && H >= 1 && W >= 1 && H <= DT_MAX_SIDE && W <= DT_MAX_SIDE; }
-static bool distance_too_big(int N, int H, int W, int bytes) { return (long)N * H * W * bytes >= 0x7ffffff0L; }
 extern "C" size_t rsu_distance_ws_bytes(int N, int H, int W) {
-    return distance_size_ok(N, H, W) && !distance_too_big(N, H, W, 4) ? dt_ws_bytes(N, H, W) : 0;
+    return dims_ok(N, H, W, DT_MAX_SIDE) && !too_big((long)N * H * W * 4) ? dt_ws_bytes(N, H, W) : 0;
 }
 extern "C" int rsu_mask_distance(const float* prob, float threshold, const int64_t* labels64, int32_t* d2_pred, int32_t* d2_true, void* ws,
                                  int N, int H, int W, rsu_stream_t stream) {
-    if (!prob || !ws || (!d2_pred && !d2_true) || (d2_true && !labels64) || !distance_size_ok(N, H, W) || !std::isfinite(threshold))
+    if (!prob || !ws || (!d2_pred && !d2_true) || (d2_true && !labels64) || !dims_ok(N, H, W, DT_MAX_SIDE) || !std::isfinite(threshold))
         return RSU_EINVAL;
     if (misaligned(4, prob, d2_pred, d2_true, ws) || misaligned(8, labels64)) return RSU_EINVAL;
-    if (distance_too_big(N, H, W, labels64 ? 8 : 4)) return RSU_E2BIG;
+    if (too_big((long)N * H * W * (labels64 ? 8 : 4))) return RSU_E2BIG;
     HIP_CHECK_RET(dt_mask_distance(prob, threshold, labels64, d2_pred, d2_true, ws, N, H, W, (hipStream_t)stream));
     return RSU_OK;
 }
 extern "C" int rsu_distance_hist(const float* prob, float threshold, const int64_t* labels64, unsigned long long* acc, void* ws, int N, int H,
                                  int W, rsu_stream_t stream) {
-    if (!prob || !labels64 || !acc || !ws || !distance_size_ok(N, H, W) || !std::isfinite(threshold)) return RSU_EINVAL;
+    if (!prob || !labels64 || !acc || !ws || !dims_ok(N, H, W, DT_MAX_SIDE) || !std::isfinite(threshold)) return RSU_EINVAL;
     if (misaligned(4, prob, ws) || misaligned(8, labels64, acc)) return RSU_EINVAL;   // (acc: 64-bit atomics)
-    if (distance_too_big(N, H, W, 8)) return RSU_E2BIG;
+    if (too_big((long)N * H * W * 8)) return RSU_E2BIG;
     HIP_CHECK_RET(dt_distance_hist(prob, threshold, labels64, acc, ws, N, H, W, (hipStream_t)stream));
     return RSU_OK;
 }
 // ---- centre-lines (rsu_thin.h): Guo & Hall's parallel thinning of the predicted and the truth mask on bit rows
 static_assert(RSU_THIN_MAX_SIDE == TH_MAX_SIDE && RSU_THIN_MAX_ITERS == TH_MAX_ITERS, "rsu_thin.h and thin.h must agree on the limits");
 static bool thin_size_ok(int N, int H, int W, int max_iters) {
-    return N >= 1 && H >= 1 && W >= 1 && H <= TH_MAX_SIDE && W <= TH_MAX_SIDE && max_iters >= 1 && max_iters <= TH_MAX_ITERS;
+    return dims_ok(N, H, W, TH_MAX_SIDE) && max_iters >= 1 && max_iters <= TH_MAX_ITERS;
 }
-static bool thin_too_big(int N, int H, int W, int bytes) { return (long)N * H * W * bytes >= 0x7ffffff0L; }
 extern "C" size_t rsu_thin_ws_bytes(int N, int H, int W, int max_iters) {
-    return thin_size_ok(N, H, W, max_iters) && !thin_too_big(N, H, W, 4) ? th_ws_bytes(N, H, W, max_iters) : 0;
+    return thin_size_ok(N, H, W, max_iters) && !too_big((long)N * H * W * 4) ? th_ws_bytes(N, H, W, max_iters) : 0;
 }
 extern "C" int rsu_mask_thin(const float* prob, float threshold, const int64_t* labels64, int max_iters, float* skel_pred, int64_t* skel_true,
                              unsigned long long* acc, uint32_t* info, void* ws, int N, int H, int W, rsu_stream_t stream) {
@@ -1761,18 +1760,17 @@ extern "C" int rsu_mask_thin(const float* prob, float threshold, const int64_t* 
         return RSU_EINVAL;
     // (ws: 64-bit plane words first; acc: 64-bit atomics; skel_true: 64-bit stores)
     if (misaligned(4, prob, skel_pred, info) || misaligned(8, labels64, skel_true, acc, ws)) return RSU_EINVAL;
-    if (thin_too_big(N, H, W, labels64 ? 8 : 4)) return RSU_E2BIG;
+    if (too_big((long)N * H * W * (labels64 ? 8 : 4))) return RSU_E2BIG;
     HIP_CHECK_RET(th_mask_thin(prob, threshold, labels64, max_iters, skel_pred, skel_true, acc, info, ws, N, H, W, (hipStream_t)stream));
     return RSU_OK;
 }
 // ---- centre-line graph (rsu_graph.h): morphological pruning of both masks and the ends, isolated pixels and junction pixels of the result
 static_assert(RSU_GRAPH_MAX_SIDE == GR_MAX_SIDE && RSU_GRAPH_MAX_BRANCH == GR_MAX_BRANCH, "rsu_graph.h and graph.h must agree on the limits");
 static bool graph_size_ok(int N, int H, int W, int min_branch) {
-    return N >= 1 && H >= 1 && W >= 1 && H <= GR_MAX_SIDE && W <= GR_MAX_SIDE && min_branch >= 0 && min_branch <= GR_MAX_BRANCH;
+    return dims_ok(N, H, W, GR_MAX_SIDE) && min_branch >= 0 && min_branch <= GR_MAX_BRANCH;
 }
-static bool graph_too_big(int N, int H, int W, int bytes) { return (long)N * H * W * bytes >= 0x7ffffff0L; }
 extern "C" size_t rsu_graph_ws_bytes(int N, int H, int W, int min_branch) {
-    return graph_size_ok(N, H, W, min_branch) && !graph_too_big(N, H, W, 4) ? gr_ws_bytes(N, H, W, min_branch) : 0;
+    return graph_size_ok(N, H, W, min_branch) && !too_big((long)N * H * W * 4) ? gr_ws_bytes(N, H, W, min_branch) : 0;
 }
 extern "C" int rsu_skeleton_graph(const float* prob, float threshold, const int64_t* labels64, int min_branch, float* out_pred, int64_t* out_true,
                                   float* junc_pred, int64_t* junc_true, unsigned long long* acc, void* ws, int N, int H, int W,
@@ -1781,7 +1779,7 @@ extern "C" int rsu_skeleton_graph(const float* prob, float threshold, const int6
         !graph_size_ok(N, H, W, min_branch) || !std::isfinite(threshold))
         return RSU_EINVAL;
     if (misaligned(4, prob, out_pred, junc_pred) || misaligned(8, labels64, out_true, junc_true, acc, ws)) return RSU_EINVAL;
-    if (graph_too_big(N, H, W, labels64 ? 8 : 4)) return RSU_E2BIG;
+    if (too_big((long)N * H * W * (labels64 ? 8 : 4))) return RSU_E2BIG;
     HIP_CHECK_RET(gr_skeleton_graph(prob, threshold, labels64, min_branch, out_pred, out_true, junc_pred, junc_true, acc, ws, N, H, W,
                                     (hipStream_t)stream));
     return RSU_OK;
@@ -1789,12 +1787,11 @@ extern "C" int rsu_skeleton_graph(const float* prob, float threshold, const int6
 // ---- road segments (rsu_segments.h): the centre-line cut at its node zones, labelled, ordered and measured segment by segment
 static_assert(RSU_SEGMENTS_MAX_SIDE == SG_MAX_SIDE && RSU_SEGMENTS_MAX_EDGES == SG_MAX_EDGES, "rsu_segments.h and segments.h must agree on the limits");
 static bool segments_size_ok(int N, int H, int W, int max_edges) {
-    return N >= 1 && H >= 1 && W >= 1 && H <= SG_MAX_SIDE && W <= SG_MAX_SIDE && max_edges >= 1 && max_edges <= SG_MAX_EDGES;
+    return dims_ok(N, H, W, SG_MAX_SIDE) && max_edges >= 1 && max_edges <= SG_MAX_EDGES;
 }
-// the four int32 planes of one internal array, 16 bytes per pixel; labels64 has 8
-static bool segments_too_big(int N, int H, int W) { return (long)N * H * W * 16 >= 0x7ffffff0L; }
+// (too_big: the four int32 planes of one internal array, 16 bytes per pixel; labels64 has 8)
 extern "C" size_t rsu_segments_ws_bytes(int N, int H, int W, int max_edges) {
-    return segments_size_ok(N, H, W, max_edges) && !segments_too_big(N, H, W) ? sg_ws_bytes(N, H, W) : 0;
+    return segments_size_ok(N, H, W, max_edges) && !too_big((long)N * H * W * 16) ? sg_ws_bytes(N, H, W) : 0;
 }
 extern "C" int rsu_line_segments(const float* prob, float threshold, const int64_t* labels64, int max_edges, int32_t* edges_pred,
                                  int32_t* edges_true, int32_t* counts, int32_t* seg_pred, int32_t* seg_true, int32_t* node_pred,
@@ -1803,7 +1800,7 @@ extern "C" int rsu_line_segments(const float* prob, float threshold, const int64
         !segments_size_ok(N, H, W, max_edges) || !std::isfinite(threshold))
         return RSU_EINVAL;
     if (misaligned(4, prob, edges_pred, edges_true, counts, seg_pred, seg_true, node_pred, node_true) || misaligned(8, labels64, acc, ws)) return RSU_EINVAL;
-    if (segments_too_big(N, H, W)) return RSU_E2BIG;
+    if (too_big((long)N * H * W * 16)) return RSU_E2BIG;
     HIP_CHECK_RET(sg_line_segments(prob, threshold, labels64, max_edges, edges_pred, edges_true, counts, seg_pred, seg_true, node_pred, node_true,
                                    acc, ws, N, H, W, (hipStream_t)stream));
     return RSU_OK;
@@ -1812,13 +1809,11 @@ extern "C" int rsu_line_segments(const float* prob, float threshold, const int64
 static_assert(RSU_PATHS_MAX_SIDE == PT_MAX_SIDE && RSU_PATHS_MAX_EDGES == PT_MAX_EDGES && RSU_PATHS_MAX_LEN == PT_MAX_LEN,
               "rsu_paths.h and paths.h must agree on the limits");
 static bool paths_size_ok(int N, int H, int W, int max_edges, int max_len) {
-    return N >= 1 && H >= 1 && W >= 1 && H <= PT_MAX_SIDE && W <= PT_MAX_SIDE && max_edges >= 1 && max_edges <= PT_MAX_EDGES && max_len >= 1 &&
-           max_len <= PT_MAX_LEN;
+    return dims_ok(N, H, W, PT_MAX_SIDE) && max_edges >= 1 && max_edges <= PT_MAX_EDGES && max_len >= 1 && max_len <= PT_MAX_LEN;
 }
-// one arc buffer: two 64-bit words per pixel
-static bool paths_too_big(int N, int H, int W) { return (long)N * H * W * 16 >= 0x7ffffff0L; }
+// (too_big: one arc buffer, two 64-bit words per pixel)
 extern "C" size_t rsu_paths_ws_bytes(int N, int H, int W, int max_edges, int max_len) {
-    return paths_size_ok(N, H, W, max_edges, max_len) && !paths_too_big(N, H, W) ? pt_ws_bytes(N, H, W, max_edges, max_len) : 0;
+    return paths_size_ok(N, H, W, max_edges, max_len) && !too_big((long)N * H * W * 16) ? pt_ws_bytes(N, H, W, max_edges, max_len) : 0;
 }
 extern "C" int rsu_segment_paths(const int32_t* seg, const int32_t* edges, const int32_t* counts, int side, int max_edges, int max_len,
                                  int max_points, int32_t* paths, int32_t* offsets, int32_t* kind, int32_t* pos, int32_t* info, void* ws, int N,
@@ -1827,20 +1822,19 @@ extern "C" int rsu_segment_paths(const int32_t* seg, const int32_t* edges, const
         (side != 0 && side != 1) || max_points < 1 || max_points > H * W)
         return RSU_EINVAL;
     if (misaligned(4, seg, edges, counts, paths, offsets, kind, pos, info) || misaligned(8, ws)) return RSU_EINVAL;
-    if (paths_too_big(N, H, W)) return RSU_E2BIG;
+    if (too_big((long)N * H * W * 16)) return RSU_E2BIG;
     HIP_CHECK_RET(pt_segment_paths(seg, edges, counts, side, max_edges, max_len, max_points, paths, offsets, kind, pos, info, ws, N, H, W,
                                    (hipStream_t)stream));
     return RSU_OK;
 }
 static_assert(RSU_BORDER_MAX_SIDE == BM_MAX_SIDE, "rsu.h and border_map.h must agree on the supported tile size");
-static bool border_size_ok(int N, int H, int W) { return N >= 1 && H >= 1 && W >= 1 && H <= BM_MAX_SIDE && W <= BM_MAX_SIDE; }
-extern "C" size_t rsu_border_map_ws_bytes(int N, int H, int W) { return border_size_ok(N, H, W) ? bm_ws_bytes(N, H, W) : 0; }
+extern "C" size_t rsu_border_map_ws_bytes(int N, int H, int W) { return dims_ok(N, H, W, BM_MAX_SIDE) ? bm_ws_bytes(N, H, W) : 0; }
 extern "C" int rsu_border_map(const int64_t* labels, const float* mul, float* out, int32_t* d2, void* ws, int N, int H, int W, float w0,
                               float sigma, rsu_stream_t stream) {
-    if (!labels || !out || !ws || !border_size_ok(N, H, W)) return RSU_EINVAL;
+    if (!labels || !out || !ws || !dims_ok(N, H, W, BM_MAX_SIDE)) return RSU_EINVAL;
     if (!std::isfinite(w0) || !(w0 >= 0.f) || !std::isfinite(sigma) || !(sigma > 0.f)) return RSU_EINVAL;
     if (misaligned(8, labels) || misaligned(4, mul, out, d2, ws)) return RSU_EINVAL;
-    if ((long)N * H * W * 8 >= 0x7ffffff0L) return RSU_E2BIG;
+    if (too_big((long)N * H * W * 8)) return RSU_E2BIG;
     // -1 / (2 sigma^2), in double and rounded once: the host mirror forms the same float
     const float neg_inv_2s2 = (float)(-1.0 / (2.0 * (double)sigma * (double)sigma));
     HIP_CHECK_RET(bm_border_map(labels, mul, out, d2, ws, N, H, W, w0, neg_inv_2s2, (hipStream_t)stream));

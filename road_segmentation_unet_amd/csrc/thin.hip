@@ -1,23 +1,20 @@
 // Mask thinning (include/rsu_thin.h): the centre-lines of the predicted mask P = {counted and prob >= threshold} and of the truth mask
 // T = {label == 1} by Guo & Hall's two-sub-iteration parallel thinning, evaluated bit-sliced on bit rows.
 //
-// ws holds three bit planes of [N][2][H][Wq] 64-bit words (side 0 = P, side 1 = T), Wq = ceil(W / TH_CORE): a word keeps TH_CORE pixels
-// of a row in its low bits (bit i = pixel xw * TH_CORE + i), the bits above and the pixels past W stay 0. Plane O keeps the masks for
-// the counts, planes A and B are the working copies: step s reads one and writes the other. Behind them sit the counters.
+// ws holds three bit planes in the layout of bitrows.h (CORE = TH_CORE). Plane O keeps the masks for the counts, planes A and B are the
+// working copies: step s reads one and writes the other. Behind them sit the counters.
 //
-//   k_thin_init   one workgroup per image row: coalesced label and probability loads, one ballot per wave and mask into LDS as plain
-//                 64-pixel words, then one thread per plane word cuts its TH_CORE pixels out. Writes planes O and A; clears the counters.
-//   k_thin_step   one workgroup of TH_ROWS threads per image side, row tile and word column: a thread holds ONE 64-bit window of one row -- TH_HALO pixels of the
-//                 word to the left, the word's TH_CORE pixels, TH_HALO pixels of the word to the right -- so east and west are shifts of
-//                 its own register and north and south are its neighbours' registers, handed over through LDS (two buffers: one barrier
-//                 per sub-iteration). What is shifted in at the window's rim is wrong; the error walks one pixel per sub-iteration and
-//                 after 2 * TH_K of them has not left the halo. Core rows store their core bits. Deletions of core pixels are counted
-//                 per thread, summed in LDS and added to the launch's own counter with one integer atomic per workgroup; the launch
-//                 behind reads it and returns where it is 0: that image side was at its fixed point and both planes hold it.
+//   k_thin_init   bitrows.h's init launch. Writes planes O and A; clears the counters.
+//   k_thin_step   bitrows.h's step tile: east and west are shifts of a thread's own window and north and south are its neighbours'
+//                 registers, handed over through LDS (two buffers: one barrier per sub-iteration). What is shifted in at the window's
+//                 rim is wrong; the error walks one pixel per sub-iteration and after 2 * TH_K of them has not left the halo. Deletions
+//                 of core pixels are counted per thread and added to the launch's own counter; the launch behind reads it and returns
+//                 where it is 0: that image side was at its fixed point and both planes hold it.
 //   k_thin_final  TH_FIN_ROWS rows per workgroup: the bits of the last plane and of plane O to skel_pred / skel_true, the four counts to
 //                 acc (LDS integer atomics, one 64-bit atomic add per non-zero count per workgroup), the last launch's count of its last
 //                 iteration to info.
 #include "thin.h"
+#include "bitrows.h"
 
 #ifndef TH_ROWS
 #define TH_ROWS 128   // rows of a step tile, halo included: TH_ROWS - 2 * TH_HALO core rows
@@ -25,7 +22,8 @@
 
 namespace {
 
-typedef unsigned long long u64;
+namespace br = bitrows;
+using br::u64;
 constexpr int TH_INIT_THREADS = 256;
 constexpr int TH_FIN_THREADS = 256, TH_FIN_ROWS = 4;
 constexpr int TH_CROWS = TH_ROWS - 2 * TH_HALO;
@@ -33,51 +31,19 @@ constexpr u64 TH_COREBITS = (1ull << TH_CORE) - 1;
 constexpr int TH_MAX_WQ = (TH_MAX_SIDE + TH_CORE - 1) / TH_CORE;
 static_assert(TH_CROWS >= 1 && TH_ROWS % 64 == 0 && 4 * TH_MAX_WQ <= TH_FIN_THREADS, "tile geometry");
 
-// grid N * H, block TH_INIT_THREADS. LAB: labels given (else every pixel counted, T empty)
+// grid N * H, block TH_INIT_THREADS: bitrows.h init_row. Plane A starts as a copy of plane O
 template <bool LAB>
 __global__ void __launch_bounds__(TH_INIT_THREADS) k_thin_init(const float* __restrict__ prob, float threshold,
                                                                const int64_t* __restrict__ labels, u64* __restrict__ plane_o,
                                                                u64* __restrict__ plane_a, uint32_t* __restrict__ counters, int nlaunch,
                                                                int N, int H, int W, int Wq) {
-    __shared__ u64 bits[2][TH_MAX_SIDE / 64 + TH_INIT_THREADS / 64 + 1];   // (a wave past W still stores its empty ballot)
-    const int n = blockIdx.x / H, y = blockIdx.x - n * H, tid = threadIdx.x;
-    if (y == 0)   // the image's own counters, two per launch that has some
-        for (int i = tid; i < 2 * nlaunch; i += TH_INIT_THREADS) counters[((size_t)(i >> 1) * N + n) * 2 + (i & 1)] = 0;
-    for (int i = tid; i < 2 * (int)(sizeof(bits[0]) / sizeof(u64)); i += TH_INIT_THREADS) (&bits[0][0])[i] = 0;
-    __syncthreads();
-    const size_t row = ((size_t)n * H + y) * W;
-    for (int x0 = 0; x0 < W; x0 += TH_INIT_THREADS) {
-        const int x = x0 + tid;
-        const bool in = x < W;
-        const size_t at = row + (in ? x : W - 1);   // (lanes past the row load a valid address and drop the value)
-        const int64_t l = LAB ? labels[at] : 0;
-        const float p = prob[at];
-        const bool counted = l == 0 || l == 1;
-        const u64 mp = __ballot(in && counted && p >= threshold);   // (NaN compares false)
-        const u64 mt = __ballot(LAB && in && l == 1);
-        if ((tid & 63) == 0) {
-            bits[0][x >> 6] = mp;
-            bits[1][x >> 6] = mt;
-        }
-    }
-    __syncthreads();
-    if (tid < 2 * Wq) {
-        const int side = tid >= Wq ? 1 : 0, xw = tid - side * Wq;
-        const int b = xw * TH_CORE, w0 = b >> 6, sh = b & 63;
-        u64 v = bits[side][w0] >> sh;
-        if (sh) v |= bits[side][w0 + 1] << (64 - sh);
-        v &= TH_COREBITS;
-        const size_t o = (((size_t)n * 2 + side) * H + y) * Wq + xw;
-        plane_o[o] = v;
-        plane_a[o] = v;
-    }
+    br::init_row<LAB, TH_CORE, TH_INIT_THREADS, TH_MAX_SIDE>(prob, threshold, labels, plane_o, plane_a, counters, nlaunch, N, H, W, Wq);
 }
 
-// the pixels of window c that a sub-iteration deletes; u and d are the windows of the rows above and below. Bit i + 1 is the pixel to
-// the east of bit i.
+// the pixels of window c that a sub-iteration deletes; u and d are the windows of the rows above and below
 template <int SUB>
 __device__ __forceinline__ u64 th_deleted(u64 u, u64 c, u64 d) {
-    const u64 p2 = u, p3 = u >> 1, p4 = c >> 1, p5 = d >> 1, p6 = d, p7 = d << 1, p8 = c << 1, p9 = u << 1;
+    const auto [p2, p3, p4, p5, p6, p7, p8, p9] = br::ring(u, c, d);
     // C == 1: exactly one of the four terms (a two-bit adder: the pair sums are a, b and e, f)
     const u64 t1 = ~p2 & (p3 | p4), t2 = ~p4 & (p5 | p6), t3 = ~p6 & (p7 | p8), t4 = ~p8 & (p9 | p2);
     const u64 c_one = ((t1 ^ t2) ^ (t3 ^ t4)) & ~((t1 & t2) | (t3 & t4));
@@ -98,23 +64,10 @@ __global__ void __launch_bounds__(TH_ROWS) k_thin_step(const u64* __restrict__ i
                                                        int nsides, int ntiles) {
     __shared__ u64 rows[2][TH_ROWS + 2];
     __shared__ unsigned red[2];
-    const int per = ntiles * Wq, z = blockIdx.x / per, rest = blockIdx.x - z * per;
-    const int n = z / nsides, slot = n * 2 + (z - n * nsides);
-    if (prev && prev[slot] == 0) return;   // (the same for the whole workgroup) a fixed point: out already holds it
-    const int tid = threadIdx.x, ty = rest / Wq, xw = rest - ty * Wq;
-    const int y = ty * TH_CROWS - TH_HALO + tid;
-    const size_t base = (size_t)slot * H * Wq;
-    u64 c = 0;
-    if (y >= 0 && y < H) {
-        const u64* r = in + base + (size_t)y * Wq;
-        const u64 lw = xw > 0 ? r[xw - 1] : 0, rw = xw + 1 < Wq ? r[xw + 1] : 0;
-        c = (lw >> (TH_CORE - TH_HALO)) | (r[xw] << TH_HALO) | (rw << (TH_HALO + TH_CORE));
-    }
-    if (tid == 0) {
-        rows[0][0] = rows[1][0] = rows[0][TH_ROWS + 1] = rows[1][TH_ROWS + 1] = 0;
-        red[0] = red[1] = 0;
-    }
-    const bool core_row = tid >= TH_HALO && tid < TH_ROWS - TH_HALO && y < H;
+    const br::Tile t = br::tile_open<TH_HALO, TH_ROWS>(rows, red, prev, H, Wq, nsides, ntiles);
+    if (t.skip) return;
+    const int tid = threadIdx.x;
+    u64 c = t.in_image ? br::window<TH_CORE, TH_HALO>(in + t.row, t.xw, Wq) : 0;
     const u64 core = TH_COREBITS << TH_HALO;
     unsigned total = 0, final_it = 0;
     for (int it = 0; it < iters; ++it) {
@@ -136,16 +89,7 @@ __global__ void __launch_bounds__(TH_ROWS) k_thin_step(const u64* __restrict__ i
         total += here;
         if (it == iters - 1) final_it = here;
     }
-    if (core_row) {
-        out[base + (size_t)y * Wq + xw] = (c >> TH_HALO) & TH_COREBITS;
-        if (total) atomicAdd(&red[0], total);
-        if (final_it) atomicAdd(&red[1], final_it);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        if (red[0]) atomicAdd(&cnt[slot], red[0]);
-        if (last && red[1]) atomicAdd(&last[slot], red[1]);
-    }
+    br::tile_close<TH_CORE, TH_HALO>(t, out, c, red, total, cnt, final_it, last);
 }
 
 // grid N * nblk (nblk = ceil(H / TH_FIN_ROWS)), block TH_FIN_THREADS. fin: the plane behind the last step; last: [N][2] (see k_thin_step)
@@ -172,9 +116,8 @@ __global__ void __launch_bounds__(TH_FIN_THREADS) k_thin_final(const u64* __rest
         __syncthreads();
         const size_t row = ((size_t)n * H + y) * W;
         for (int x = tid; x < W; x += TH_FIN_THREADS) {
-            const int xw = x / TH_CORE, b = x - xw * TH_CORE;
-            const unsigned sp = (unsigned)(w[0][xw] >> b) & 1u, st = (unsigned)(w[1][xw] >> b) & 1u;
-            const unsigned p = (unsigned)(w[2][xw] >> b) & 1u, t = (unsigned)(w[3][xw] >> b) & 1u;
+            const unsigned sp = br::pixel<TH_CORE>(w[0], x), st = br::pixel<TH_CORE>(w[1], x);
+            const unsigned p = br::pixel<TH_CORE>(w[2], x), t = br::pixel<TH_CORE>(w[3], x);
             if (skel_pred) skel_pred[row + x] = sp ? 1.0f : 0.0f;
             if (skel_true) {
                 const int64_t l = labels[row + x];
@@ -195,32 +138,25 @@ __global__ void __launch_bounds__(TH_FIN_THREADS) k_thin_final(const u64* __rest
     if (tid < 4 && sums[tid]) atomicAdd(&acc[tid], (u64)sums[tid]);
 }
 
-inline int th_wq(int W) { return (W + TH_CORE - 1) / TH_CORE; }
 inline int th_steps(int max_iters) { return (max_iters + TH_K - 1) / TH_K; }
-inline size_t th_plane_words(int N, int H, int W) { return (size_t)N * 2 * H * th_wq(W); }
-// counters: one [N][2] per step launch, then the [N][2] of the last step's last iteration
-inline size_t th_counters(int N, int max_iters) { return (size_t)(th_steps(max_iters) + 1) * N * 2; }
 
 }  // namespace
 
+// counters: one [N][2] per step launch, then the [N][2] of the last step's last iteration
 size_t th_ws_bytes(int N, int H, int W, int max_iters) {
-    return 3 * th_plane_words(N, H, W) * sizeof(u64) + (th_counters(N, max_iters) * sizeof(uint32_t) + 7) / 8 * 8;
+    return 3 * br::plane_words<TH_CORE>(N, H, W) * sizeof(u64) + br::counter_bytes((size_t)(th_steps(max_iters) + 1) * N * 2);
 }
 
 hipError_t th_mask_thin(const float* prob, float threshold, const int64_t* labels, int max_iters, float* skel_pred, int64_t* skel_true,
                         unsigned long long* acc, uint32_t* info, void* ws, int N, int H, int W, hipStream_t st) {
-    const int Wq = th_wq(W), S = th_steps(max_iters), nsides = labels ? 2 : 1;
-    const size_t words = th_plane_words(N, H, W);
+    const int Wq = br::wq<TH_CORE>(W), S = th_steps(max_iters), nsides = labels ? 2 : 1;
+    const size_t words = br::plane_words<TH_CORE>(N, H, W);
     u64* plane_o = (u64*)ws;
     u64* plane[2] = {plane_o + words, plane_o + 2 * words};
     uint32_t* counters = (uint32_t*)(plane_o + 3 * words);
     uint32_t* last = counters + (size_t)S * N * 2;
-    if (labels)
-        hipLaunchKernelGGL(k_thin_init<true>, dim3(N * H), dim3(TH_INIT_THREADS), 0, st, prob, threshold, labels, plane_o, plane[0], counters,
-                           S + 1, N, H, W, Wq);
-    else
-        hipLaunchKernelGGL(k_thin_init<false>, dim3(N * H), dim3(TH_INIT_THREADS), 0, st, prob, threshold, labels, plane_o, plane[0], counters,
-                           S + 1, N, H, W, Wq);
+    hipLaunchKernelGGL(labels ? k_thin_init<true> : k_thin_init<false>, dim3(N * H), dim3(TH_INIT_THREADS), 0, st, prob, threshold, labels,
+                       plane_o, plane[0], counters, S + 1, N, H, W, Wq);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const int ntiles = (H + TH_CROWS - 1) / TH_CROWS;
@@ -234,12 +170,7 @@ hipError_t th_mask_thin(const float* prob, float threshold, const int64_t* label
         if (e != hipSuccess) return e;
     }
     const int nblk = (H + TH_FIN_ROWS - 1) / TH_FIN_ROWS;
-    const dim3 fgrid(N * nblk);
-    if (labels)
-        hipLaunchKernelGGL(k_thin_final<true>, fgrid, dim3(TH_FIN_THREADS), 0, st, (const u64*)plane[S & 1], (const u64*)plane_o, labels,
-                           (const uint32_t*)last, skel_pred, skel_true, (u64*)acc, info, H, W, Wq, nblk);
-    else
-        hipLaunchKernelGGL(k_thin_final<false>, fgrid, dim3(TH_FIN_THREADS), 0, st, (const u64*)plane[S & 1], (const u64*)plane_o, labels,
-                           (const uint32_t*)last, skel_pred, skel_true, (u64*)acc, info, H, W, Wq, nblk);
+    hipLaunchKernelGGL(labels ? k_thin_final<true> : k_thin_final<false>, dim3(N * nblk), dim3(TH_FIN_THREADS), 0, st, (const u64*)plane[S & 1],
+                       (const u64*)plane_o, labels, (const uint32_t*)last, skel_pred, skel_true, (u64*)acc, info, H, W, Wq, nblk);
     return hipGetLastError();
 }

@@ -17,8 +17,8 @@ R, CORE, CROWS = 16, 32, 96         # csrc/graph.h GR_R; the tile of a step laun
 BRANCHES = (0, 1, R - 1, R, R + 1, 2 * R + 1, MAX_BRANCH)
 # (N, H, W): one pixel; less than a ballot word; one ballot word; exactly one tile, a pixel less / more on either axis; three row tiles by
 # four word columns, all partial; two by seven; the widest row (32 words) and the tallest column (11 row tiles)
-SHAPES = [(1, 1, 1), (1, 3, 5), (2, 64, 64), (2, CROWS, CORE), (1, CROWS + 1, CORE - 1), (3, CROWS - 1, CORE + 1), (2, 230, 97), (1, 129, 200),
-          (1, 3, 1024), (1, 1024, 3)]
+SHAPES = [(1, 1, 1), (1, 3, 5), (2, 64, 64), (1, 65, 63), (3, 63, 65), (2, CROWS, CORE), (1, CROWS + 1, CORE - 1), (3, CROWS - 1, CORE + 1),
+          (2, 230, 97), (1, 129, 200), (1, 3, 1024), (1, 1024, 3)]
 CORNER_SHAPE = (1, 2 * CROWS - 20, 4 * CORE - 10)   # the corner of four tiles at row CROWS, column CORE, and three more down the row
 
 

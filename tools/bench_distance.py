@@ -8,9 +8,9 @@
       (blurred noise through a sigmoid; the truth is the same map at a higher level, so the prediction is the truth grown by a few
       pixels) and the test bank's random pair (rand0.55 against rand0.41: every distance is 0, 1 or 2 pixels). One process, the arms
       alternated call by call; every call is timed on the host between two synchronisations (the scipy arm is host work): us per call,
-      median of 20 rounds with min and max. --row-libs: A/B builds of the library that differ in the rows a workgroup of the histogram's
-      row launch takes (make -C road_segmentation_unet_amd/csrc VARIANT=rowsK EXTRA=-DDT_HIST_ROWS=K); rsu_distance_hist of each is
-      timed in the same alternation, and every arm's histogram must equal the first's.
+      median of 20 rounds with min and max (the scipy arm: 3 rounds). --row-libs: A/B builds of the library that differ in the rows a workgroup of the histogram's
+      row launch takes (make -C road_segmentation_unet_amd/csrc VARIANT=rowsK EXTRA=-DDT_HIST_ROWS=K); rsu_distance_hist and
+      rsu_mask_distance of each are timed in the same alternation, and every arm's outputs must equal the first's.
   bench_distance.py step --lib PARENT_LIBRARY [--reps N]
       the DEFAULT config-2 training step and a DEFAULT validation pass (evaluate() over 8 patches of 388 x 388, no flag of this change
       set) with this tree's library against the parent commit's library (built as `make -C road_segmentation_unet_amd/csrc
@@ -144,7 +144,8 @@ row_libs = []
 for item in [s for s in a.row_libs.split(",") if s]:
     rows, path = item.split("=", 1)
     L = ctypes.CDLL(os.path.abspath(path))
-    L.rsu_distance_hist.restype, L.rsu_distance_hist.argtypes = _lib.SIGNATURES_DISTANCE["rsu_distance_hist"]
+    for entry in ("rsu_distance_hist", "rsu_mask_distance"):
+        getattr(L, entry).restype, getattr(L, entry).argtypes = _lib.SIGNATURES_DISTANCE[entry]
     row_libs.append((int(rows), L, hashlib.sha256(open(path, "rb").read()).hexdigest()[:16]))
 for rows, _L, h in row_libs:
     print("row-block variant: %d row(s) per workgroup, lib %s" % (rows, h))
@@ -171,6 +172,7 @@ class Case:
         self.d2t = torch.zeros(prob.shape, dtype=torch.int32, device=dev)
         self.acc = torch.zeros((2, BINS), dtype=torch.int64, device=dev)
         self.row_acc = {rows: torch.zeros((2, BINS), dtype=torch.int64, device=dev) for rows, _L, _h in row_libs}
+        self.row_d2 = {rows: torch.zeros((2,) + tuple(prob.shape), dtype=torch.int32, device=dev) for rows, _L, _h in row_libs}
         self.ws = torch.zeros(lib.rsu_distance_ws_bytes(self.N, self.H, self.W) // 4, dtype=torch.int32, device=dev)
         self.scipy_hist = self.scipy_d2 = None
 
@@ -182,6 +184,13 @@ class Case:
         def run():
             self.row_acc[rows].zero_()
             rc = L.rsu_distance_hist(_ptr(self.prob), THR, _ptr(self.lab64), _ptr(self.row_acc[rows]), _ptr(self.ws), self.N, self.H, self.W, st())
+            assert rc == 0, rc
+        return run
+
+    def distance_of(self, rows, L):
+        def run():
+            d2 = self.row_d2[rows]
+            rc = L.rsu_mask_distance(_ptr(self.prob), THR, _ptr(self.lab64), _ptr(d2[0]), _ptr(d2[1]), _ptr(self.ws), self.N, self.H, self.W, st())
             assert rc == 0, rc
         return run
 
@@ -205,14 +214,17 @@ class Case:
         self.scipy_hist, self.scipy_d2 = hist, d2
 
 
-def timed(arms, rounds=20):
+def timed(arms, rounds=20, slow="copy + 2 scipy edt + bincount", slow_rounds=3):
+    """the host route is timed in the first rounds only: the arm behind it starts on a device that has idled for tens of milliseconds"""
     for _ in range(3):
         for _n, fn in arms:
             fn()
     torch.cuda.synchronize()
     us = {k: [] for k, _ in arms}
-    for _ in range(rounds):
+    for r in range(rounds):
         for name, fn in arms:
+            if name == slow and r >= slow_rounds:
+                continue
             torch.cuda.synchronize(); t0 = time.perf_counter()
             fn()
             torch.cuda.synchronize(); us[name].append((time.perf_counter() - t0) * 1e6)
@@ -225,13 +237,15 @@ for S in (388, 608):
         print("N x H x W = 2 x %d x %d, %s; us per call between two synchronisations, median of 20 (min .. max)" % (S, S, name))
         arms = [("rsu_distance_hist", c.hist), ("rsu_mask_distance", c.distance), ("copy + 2 scipy edt + bincount", c.scipy_route)]
         arms += [("rsu_distance_hist, %d row(s)/workgroup" % rows, c.hist_of(rows, L)) for rows, L, _h in row_libs]
+        arms += [("rsu_mask_distance, the %d-row library" % rows, c.distance_of(rows, L)) for rows, L, _h in row_libs]
         us = timed(arms)
         for arm, u in us.items():
             print("  %-38s %9.1f us (%.1f .. %.1f)" % (arm, median(u), min(u), max(u)))
         acc = c.acc.cpu().numpy()
         same_h = bool(np.array_equal(acc, c.scipy_hist))
         same_d = bool(np.array_equal(c.d2p.cpu().numpy(), c.scipy_d2[0]) and np.array_equal(c.d2t.cpu().numpy(), c.scipy_d2[1]))
-        same_r = all(bool(np.array_equal(t.cpu().numpy(), acc)) for t in c.row_acc.values())
+        same_r = all(bool(np.array_equal(t.cpu().numpy(), acc)) for t in c.row_acc.values()) and \
+            all(bool(torch.equal(t[0], c.d2p) and torch.equal(t[1], c.d2t)) for t in c.row_d2.values())
         hm, sm = median(us["rsu_distance_hist"]), median(us["copy + 2 scipy edt + bincount"])
         print("  histogram equals scipy's: %s; distances equal scipy's: %s; row-block variants agree: %s; hist %.1f us against %.1f us: x %.1f"
               % (same_h, same_d, same_r, hm, sm, sm / hm))

@@ -16,6 +16,9 @@
       VARIANT=parent` in a checkout of the parent, loaded through RSU_LIB_PATH), alternating fresh processes on one box; the order of the
       arms rotates from round to round. Every process runs under its own time limit and the series stops at the first one that fails.
       Medians per arm; the spread of the parent arm's runs is the noise the difference is read against.
+  bench_segments.py step --all-flags --lib PARENT_LIBRARY [--reps N]
+      the same two arms per library, the validation pass with ALL FIVE mask stages on (below): for a change of the mask tools' kernels.
+      The parent's library must then have every entry this tree's Python binds.
   bench_segments.py step --all-flags --parent-tree PARENT_CHECKOUT [--lib LIBRARY] [--reps N]
       a validation pass with ALL FIVE mask stages on (--validate_components, --validate_distances, --validate_centerlines with
       --centerline_min_branch=8, --validate_junctions and --validate_segments: evaluate() over the same 8 patches of 388 x 388 in chunks
@@ -56,7 +59,7 @@ def median(v):
 
 
 if a.mode_ == "step":
-    if a.all_flags:
+    if a.all_flags and (a.parent_tree or not a.lib):
         one_lib = os.path.abspath(a.lib or os.path.join(HERE, "road_segmentation_unet_amd", "librsu_hip.so"))
         if not a.parent_tree or not os.path.isdir(os.path.join(a.parent_tree, "road_segmentation_unet_amd")) or not os.path.exists(one_lib):
             sys.exit("step --all-flags needs --parent-tree: a checkout of the parent commit, and a built library")
@@ -67,8 +70,8 @@ if a.mode_ == "step":
         if not a.lib or not os.path.exists(a.lib):
             sys.exit("step needs --lib: the parent commit's library")
         parent = {"RSU_LIB_PATH": os.path.abspath(a.lib)}
-        arms = [("parent step", parent, ["--parent-lib"]), ("this step", {}, []), ("parent validate", parent, ["--parent-lib", "--validate"]),
-                ("this validate", {}, ["--validate"])]
+        old, val = ([], ["--validate", "--all-flags"]) if a.all_flags else (["--parent-lib"], ["--validate"])
+        arms = [("parent step", parent, old), ("this step", {}, []), ("parent validate", parent, old + val), ("this validate", {}, val)]
     ms = {k: [] for k, _, _ in arms}
     for rep in range(a.reps):
         for name, env, extra in arms[rep % len(arms):] + arms[:rep % len(arms)]:   # (no arm is always the first of its round)
@@ -85,7 +88,7 @@ if a.mode_ == "step":
     med = {k: median(v) for k, v in ms.items()}
     for k, _, _ in arms:
         print("%-15s ms: %s | median %.4f min %.4f max %.4f" % (k, " ".join("%.4f" % v for v in ms[k]), med[k], min(ms[k]), max(ms[k])))
-    if a.all_flags:
+    if a.all_flags and a.parent_tree:
         for what, title in (("all-flags", "all five mask stages on"), ("default", "no flag set")):
             lo, hi, this, par = min(ms["parent " + what]), max(ms["parent " + what]), med["this " + what], med["parent " + what]
             print("validation pass, %s, this tree's Python against the parent's on one library: median %.4f ms against %.4f ms (%+.2f %%); "
@@ -95,8 +98,9 @@ if a.mode_ == "step":
     for what in ("step", "validate"):
         spread, own = max(ms["parent " + what]) - min(ms["parent " + what]), max(ms["this " + what]) - min(ms["this " + what])
         d = med["this " + what] - med["parent " + what]
-        print("default %s, this library - parent's (medians): %+.4f ms (%+.2f %%); run-to-run spread (max - min) of the parent arm %.4f ms, of "
-              "this arm %.4f ms: %s the parent's" % (what, d, 100 * d / med["parent " + what], spread, own,
+        print("%s %s, this library - parent's (medians): %+.4f ms (%+.2f %%); run-to-run spread (max - min) of the parent arm %.4f ms, of "
+              "this arm %.4f ms: %s the parent's" % ("all-flags" if a.all_flags and what == "validate" else "default", what, d,
+                                                     100 * d / med["parent " + what], spread, own,
                                                      "inside" if abs(d) <= spread else "OUTSIDE"))
     sys.exit(0)
 
