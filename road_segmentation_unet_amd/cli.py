@@ -185,6 +185,9 @@ def main(argv=None):
                 if opts.road_graph_paths:
                     print("Road paths: {} points, {} segments not ordered (branched or longer than {} pixels)".format(
                         sum(len(e["path"]) for g in graphs for e in g["edges"]), sum(g["unordered"] for g in graphs), opts.max_path_length))
+                if opts.road_graph_distances:
+                    print("Road distances: {} nodes in the tables, {} past --max_graph_nodes={}".format(
+                        sum(len(g["node_index"]) for g in graphs), sum(g["nodes_dropped"] for g in graphs), opts.max_graph_nodes))
             if masks.shape[1] % hostio.IMG_PATCH_SIZE or masks.shape[2] % hostio.IMG_PATCH_SIZE:
                 print("No submission.csv: {} x {} images are not made of whole {}-pixel patches".format(
                     masks.shape[1], masks.shape[2], hostio.IMG_PATCH_SIZE))

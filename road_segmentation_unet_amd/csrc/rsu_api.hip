@@ -23,6 +23,7 @@
 #include "../../include/rsu_graph.h"
 #include "../../include/rsu_segments.h"
 #include "../../include/rsu_paths.h"
+#include "../../include/rsu_routes.h"
 #include "affine_patches.h"
 #include "color_jitter.h"
 #include "border_map.h"
@@ -36,6 +37,7 @@
 #include "graph.h"
 #include "segments.h"
 #include "paths.h"
+#include "routes.h"
 #include "optim.h"
 #include "igemm.h"
 
@@ -1825,6 +1827,38 @@ extern "C" int rsu_segment_paths(const int32_t* seg, const int32_t* edges, const
     if (too_big((long)N * H * W * 16)) return RSU_E2BIG;
     HIP_CHECK_RET(pt_segment_paths(seg, edges, counts, side, max_edges, max_len, max_points, paths, offsets, kind, pos, info, ws, N, H, W,
                                    (hipStream_t)stream));
+    return RSU_OK;
+}
+// ---- network distances and the path-length score (rsu_routes.h): the node table, a blocked Floyd-Warshall in integer min-plus, one direction of the score
+static_assert(RSU_ROUTES_MAX_SIDE == RT_MAX_SIDE && RSU_ROUTES_MAX_NODES == RT_MAX_NODES && RSU_ROUTES_INF == RT_INF && RSU_ROUTES_Q == RT_Q,
+              "rsu_routes.h and routes.h must agree on the limits");
+static bool routes_nodes_ok(int max_nodes) { return max_nodes >= 1 && max_nodes <= RT_MAX_NODES; }
+// (too_big: node_map, 4 bytes per pixel; dist, 4 bytes per pair of nodes)
+static bool routes_too_big(int N, int H, int W, int max_nodes) {
+    return too_big((long)N * H * W * 4) || too_big((long)N * max_nodes * max_nodes * 4);
+}
+extern "C" size_t rsu_routes_ws_bytes(int N, int H, int W, int max_nodes) {
+    return dims_ok(N, H, W, RT_MAX_SIDE) && routes_nodes_ok(max_nodes) && !routes_too_big(N, H, W, max_nodes) ? rt_ws_bytes(N, H, W, max_nodes) : 0;
+}
+extern "C" int rsu_graph_routes(const int32_t* node_map, const int32_t* edges, const int32_t* counts, int side, int max_edges, int max_nodes,
+                                int32_t* nodes, int32_t* dist, int32_t* info, void* ws, int N, int H, int W, rsu_stream_t stream) {
+    if (!node_map || !edges || !counts || !nodes || !dist || !info || !ws || !dims_ok(N, H, W, RT_MAX_SIDE) || (side != 0 && side != 1) ||
+        max_edges < 1 || max_edges > RT_MAX_EDGES || !routes_nodes_ok(max_nodes))
+        return RSU_EINVAL;
+    if (misaligned(4, node_map, edges, counts, nodes, dist, info, ws)) return RSU_EINVAL;
+    if (routes_too_big(N, H, W, max_nodes)) return RSU_E2BIG;
+    HIP_CHECK_RET(rt_graph_routes(node_map, edges, counts, side, max_edges, max_nodes, nodes, dist, info, ws, N, H, W, (hipStream_t)stream));
+    return RSU_OK;
+}
+extern "C" int rsu_route_score(const int32_t* nodes_a, const int32_t* dist_a, const int32_t* info_a, const int32_t* nodes_b, const int32_t* dist_b,
+                               const int32_t* info_b, int max_nodes, int slack, int32_t* match, unsigned long long* acc, int N,
+                               rsu_stream_t stream) {
+    if (!nodes_a || !dist_a || !info_a || !nodes_b || !dist_b || !info_b || !match || !acc || N < 1 || !routes_nodes_ok(max_nodes) || slack < 0 ||
+        slack > 1023)
+        return RSU_EINVAL;
+    if (misaligned(4, nodes_a, dist_a, info_a, nodes_b, dist_b, info_b, match) || misaligned(8, acc)) return RSU_EINVAL;   // (acc: 64-bit atomics)
+    if (too_big((long)N * max_nodes * max_nodes * 4)) return RSU_E2BIG;
+    HIP_CHECK_RET(rt_route_score(nodes_a, dist_a, info_a, nodes_b, dist_b, info_b, max_nodes, slack, match, acc, N, (hipStream_t)stream));
     return RSU_OK;
 }
 static_assert(RSU_BORDER_MAX_SIDE == BM_MAX_SIDE, "rsu.h and border_map.h must agree on the supported tile size");

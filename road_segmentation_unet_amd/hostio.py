@@ -1720,3 +1720,179 @@ def road_graph(edges, count, node_map, H, W, paths=None):
                     chain.reverse()
             edge["kind"], edge["path"] = PATH_KINDS[k], chain
     return {"nodes": nodes, "edges": out}
+
+
+# ---- network distances and the path-length score on the host (include/rsu_routes.h)
+ROUTES_MAX_SIDE, ROUTES_MAX_NODES, ROUTES_MAX_EDGES = 1024, 1024, 65536   # rsu_routes.h RSU_ROUTES_MAX_SIDE, RSU_ROUTES_MAX_NODES; max_edges
+ROUTES_INF, ROUTES_Q = 0x3fffffff, 65536                                  # rsu_routes.h RSU_ROUTES_INF (no path), RSU_ROUTES_Q (the unit of q)
+ROUTES_ORTHO, ROUTES_DIAG = 70, 99                                        # a weight is 70 ortho + 99 diag: 99 / 70 is a convergent of sqrt(2)
+ROUTES_BLOCK, ROUTES_TILE = 256, 64                                       # csrc/routes.hip RT_BLOCK, RT_TILE
+
+
+def _routes_int(what, name, v, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+        raise ValueError("%s: %s must be an integer in [%d, %d], not %r" % (what, name, lo, hi, v))
+    return int(v)
+
+
+def _routes_check(node_map, edges, counts, side, max_nodes):
+    m, e, c = np.asarray(node_map), np.asarray(edges), np.asarray(counts)
+    if m.ndim != 3 or m.dtype.kind not in "iu" or min(m.shape) < 1:
+        raise ValueError("graph_routes: node_map must be an integer array [N, H, W] with N, H, W >= 1, not %s %r" % (m.dtype, m.shape))
+    N, H, W = m.shape
+    if max(H, W) > ROUTES_MAX_SIDE:
+        raise ValueError("graph_routes: H, W <= %d, not shape %r" % (ROUTES_MAX_SIDE, m.shape))
+    if isinstance(side, bool) or not isinstance(side, (int, np.integer)) or side not in (0, 1):
+        raise ValueError("graph_routes: side must be 0 or 1, not %r" % (side,))
+    if e.ndim != 3 or e.shape[0] != N or e.shape[2] != 8 or e.dtype.kind not in "iu" or not 1 <= e.shape[1] <= ROUTES_MAX_EDGES:
+        raise ValueError("graph_routes: edges must be an integer array [%d, max_edges, 8] with max_edges in [1, %d], not %s %r"
+                         % (N, ROUTES_MAX_EDGES, e.dtype, e.shape))
+    if c.shape != (N, 4) or c.dtype.kind not in "iu":
+        raise ValueError("graph_routes: counts must be an integer array [%d, 4], not %s %r" % (N, c.dtype, c.shape))
+    cap = _routes_int("graph_routes", "max_nodes", max_nodes, 1, ROUTES_MAX_NODES)
+    if N * H * W * 4 >= 0x7ffffff0 or N * cap * cap * 4 >= 0x7ffffff0:
+        raise ValueError("graph_routes: node_map (%d x %d x %d) or dist (%d x %d x %d) reaches 2 GiB" % (N, H, W, N, cap, cap))
+    return m, e, c, cap
+
+
+def _routes_find(ids, v):
+    """the rows of the node ids `v` in a table whose ids ascend in absolute value: the first row whose |id| is not below |v|, taken where
+    its id is v; -1 elsewhere"""
+    v = np.asarray(v, np.int64)
+    r = np.searchsorted(np.abs(ids), np.abs(v))
+    hit = r < ids.size
+    hit[hit] = ids[r[hit]] == v[hit]
+    return np.where(hit, r, -1)
+
+
+def graph_routes(node_map, edges, counts, side, max_nodes, fill=0, solver=None):
+    """rsu_graph_routes on the host, in its output formats: (nodes int32 [N, max_nodes, 4], dist int32 [N, max_nodes, max_nodes], info int32
+    [N, 4]) of node_map int32 [N, H, W], edges int32 [N, max_edges, 8] and counts int32 [N, 4] of one side of rsu_line_segments (side 0
+    reads counts[:, 0], side 1 counts[:, 2]). A node is a root pixel p of node_map (node_map[p] == p + 1: a zone's smallest pixel, or
+    node_map[p] < 0: a line end), numbered in ascending p; its row is {id, y, x, pixels}: an end's pixel and 1, a zone's rounded centroid
+    (2 sum + pixels) // (2 pixels) and its pixel count. A stored row of edges with node_a != node_b is an edge of weight
+    min(70 ortho + 99 diag, ROUTES_INF) between its two nodes; parallel edges keep the minimum; a row with a negative ortho or diag or a
+    node that is not in the stored table is skipped and counted. dist[n, i, j] is the length of the shortest path (Floyd-Warshall in
+    integer min-plus, sums cut at ROUTES_INF), ROUTES_INF without one, 0 on the diagonal. info = {nodes, nodes stored, edges used, rows
+    skipped}. Rows and columns at and past the stored nodes keep `fill`. Bad arguments raise ValueError by the header's rules.
+    solver: a function that takes the int32 matrix of the direct edges' weights (ROUTES_INF: none, 0 on the diagonal) and returns the
+    distances in its place, instead of the Floyd-Warshall loop here (tools/bench_routes.py times scipy's this way)."""
+    m, e, c, cap = _routes_check(node_map, edges, counts, side, max_nodes)
+    N, H, W = m.shape
+    nodes = np.full((N, cap, 4), fill, np.int32)
+    dist = np.full((N, cap, cap), fill, np.int32)
+    info = np.zeros((N, 4), np.int32)
+    index = np.arange(H * W, dtype=np.int64)
+    for n in range(N):
+        flat = m[n].reshape(-1).astype(np.int64)
+        roots = np.nonzero((flat == index + 1) | (flat < 0))[0]
+        total, stored = roots.size, min(roots.size, cap)
+        roots = roots[:stored]
+        ids = flat[roots]
+        table = np.stack([ids, roots // W, roots % W, np.ones(stored, np.int64)], axis=1)
+        zone = np.nonzero(flat > 0)[0]                      # the zones' pixels add to their node's sums
+        row = _routes_find(ids, flat[zone])
+        zone, row = zone[row >= 0], row[row >= 0]
+        pixels, sy, sx = (np.zeros(stored, np.int64) for _ in range(3))
+        np.add.at(pixels, row, 1)
+        np.add.at(sy, row, zone // W)
+        np.add.at(sx, row, zone % W)
+        z = (ids > 0) & (pixels > 0)
+        table[z, 1] = (2 * sy[z] + pixels[z]) // (2 * pixels[z])
+        table[z, 2] = (2 * sx[z] + pixels[z]) // (2 * pixels[z])
+        table[z, 3] = pixels[z]
+        nodes[n, :stored] = table
+        rows = e[n, :min(max(int(c[n, 2 * side]), 0), e.shape[1])].astype(np.int64)
+        rows = rows[rows[:, 4] != rows[:, 5]]               # rings and loops through one node are no edges
+        ia, ib = _routes_find(ids, rows[:, 4]), _routes_find(ids, rows[:, 5])
+        good = (rows[:, 2] >= 0) & (rows[:, 3] >= 0) & (ia >= 0) & (ib >= 0)
+        w = np.minimum(ROUTES_ORTHO * rows[good, 2] + ROUTES_DIAG * rows[good, 3], ROUTES_INF).astype(np.int32)
+        D = np.full((stored, stored), ROUTES_INF, np.int32)
+        D[np.arange(stored), np.arange(stored)] = 0
+        np.minimum.at(D, (ia[good], ib[good]), w)
+        np.minimum.at(D, (ib[good], ia[good]), w)
+        for k in range(stored if solver is None else 0):    # (the sum of two entries stays inside int32)
+            D = np.minimum(D, np.minimum(D[:, k, None] + D[None, k, :], ROUTES_INF))
+        if solver is not None:
+            D = solver(D)
+        dist[n, :stored, :stored] = D
+        info[n] = (total, stored, int(good.sum()), int((~good).sum()))
+    return nodes, dist, info
+
+
+def _score_check(nodes_a, dist_a, info_a, nodes_b, dist_b, info_b, slack):
+    arrays = [np.asarray(a) for a in (nodes_a, dist_a, info_a, nodes_b, dist_b, info_b)]
+    na = arrays[0]
+    if na.ndim != 3 or na.shape[2] != 4 or not 1 <= na.shape[1] <= ROUTES_MAX_NODES or na.shape[0] < 1:
+        raise ValueError("route_score: nodes_a must be an integer array [N, max_nodes, 4] with max_nodes in [1, %d], not %r"
+                         % (ROUTES_MAX_NODES, na.shape))
+    N, cap = na.shape[:2]
+    for name, a, shape in zip(("nodes_a", "dist_a", "info_a", "nodes_b", "dist_b", "info_b"), arrays,
+                              ((N, cap, 4), (N, cap, cap), (N, 4)) * 2):
+        if a.shape != shape or a.dtype.kind not in "iu":
+            raise ValueError("route_score: %s must be an integer array %r, not %s %r" % (name, shape, a.dtype, a.shape))
+    _routes_int("route_score", "slack", slack, 0, 1023)
+    return arrays, N, cap
+
+
+def route_score(nodes_a, dist_a, info_a, nodes_b, dist_b, info_b, slack, fill=0):
+    """rsu_route_score on the host: (match int32 [N, max_nodes], acc int64 [4]) of two graphs in graph_routes' formats with one
+    max_nodes. match[n, i], for every stored node i of a, is the stored node j of b with the smallest (dy)^2 + (dx)^2 (ties: the smaller
+    j) where that is at most slack^2, else -1; rows at and past the stored count keep `fill`. Every pair i < k of a with
+    0 < d = dist_a[i, k] < ROUTES_INF adds to acc = {pairs, sum q, unmatched, broken}: q = ROUTES_Q where either node is unmatched
+    (unmatched) or e = dist_b[match i, match k] is ROUTES_INF (broken), else min(ROUTES_Q, ROUTES_Q |d - e| // d). The direction's score is
+    1 - sum q / (ROUTES_Q pairs) (route_metrics)."""
+    (na, da, fa, nb, db, fb), N, cap = _score_check(nodes_a, dist_a, info_a, nodes_b, dist_b, info_b, slack)
+    match = np.full((N, cap), fill, np.int32)
+    acc = np.zeros(4, np.int64)
+    for n in range(N):
+        sa, sb = (min(max(int(f[n, 1]), 0), cap) for f in (fa, fb))
+        pa, pb = na[n, :sa, 1:3].astype(np.int64), nb[n, :sb, 1:3].astype(np.int64)
+        if sb:
+            d2 = ((pa[:, None, :] - pb[None, :, :]) ** 2).sum(axis=2)
+            best = np.argmin(d2, axis=1)                     # (the first of equal minima: the smaller j)
+            m = np.where(d2[np.arange(sa), best] <= int(slack) ** 2, best, -1)
+        else:
+            m = np.full(sa, -1, np.int64)
+        match[n, :sa] = m
+        i, k = np.triu_indices(sa, 1)
+        d = da[n, i, k].astype(np.int64)
+        pair = (d > 0) & (d < ROUTES_INF)
+        i, k, d = i[pair], k[pair], d[pair]
+        lost = (m[i] < 0) | (m[k] < 0)
+        e = np.where(lost, ROUTES_INF, db[n, np.maximum(m[i], 0), np.maximum(m[k], 0)].astype(np.int64)) if sb else np.full(d.size, ROUTES_INF, np.int64)
+        broken = ~lost & (e >= ROUTES_INF)
+        q = np.where(lost | broken, ROUTES_Q, np.minimum(ROUTES_Q, ROUTES_Q * np.abs(d - e) // np.maximum(d, 1)))
+        acc += np.array([d.size, q.sum(), lost.sum(), broken.sum()], np.int64)
+    return match, acc
+
+
+def route_metrics(acc_true_to_pred, acc_pred_to_true, info_sums):
+    """The path-length figures of a validation pass from the two directions' rsu_route_score counters ({pairs, sum q, unmatched, broken}
+    each) and info_sums = rsu_graph_routes' info summed over the patches, of the prediction then of the truth ({nodes, nodes stored, edges
+    used, rows skipped} each), per direction * in (true_to_pred, pred_to_true) and side + in (pred, true):
+      apls_*               = 1 - sum q / (ROUTES_Q pairs), 0 without a pair,
+      route_pairs_*, route_unmatched_*, route_broken_* = the pairs, those with an unmatched node, those whose counterparts no path joins,
+      graph_nodes_+        = the nodes, graph_nodes_dropped_+ = those past --max_graph_nodes,
+    and apls = the harmonic mean of the two directions, 0 where either has no pairs. The control points are the graphs' own nodes: no
+    points are injected along the edges (include/rsu_routes.h)."""
+    out, score = {}, []
+    s = np.asarray(info_sums)
+    if s.shape != (8,) or s.dtype.kind not in "iu" or (s.astype(np.int64) < 0).any():
+        raise ValueError("route_metrics: info_sums must be eight integers >= 0, not %s %r" % (s.dtype, s.shape))
+    for name, acc in (("true_to_pred", acc_true_to_pred), ("pred_to_true", acc_pred_to_true)):
+        a = np.asarray(acc)
+        if a.shape != (4,) or a.dtype.kind not in "iu" or (a.astype(np.int64) < 0).any():
+            raise ValueError("route_metrics: acc_%s must be four integers >= 0, not %s %r" % (name, a.dtype, a.shape))
+        pairs, q, unmatched, broken = (int(v) for v in a)
+        if q > ROUTES_Q * pairs or unmatched + broken > pairs:
+            raise ValueError("route_metrics: acc_%s = %r is no sum over %d pairs" % (name, a.tolist(), pairs))
+        score.append(1.0 - q / float(ROUTES_Q * pairs) if pairs else 0.0)
+        out.update({"apls_" + name: score[-1], "route_pairs_" + name: pairs, "route_unmatched_" + name: unmatched, "route_broken_" + name: broken})
+    t, p = score
+    out["apls"] = 2.0 * t * p / (t + p) if int(np.asarray(acc_true_to_pred)[0]) and int(np.asarray(acc_pred_to_true)[0]) and t + p > 0.0 else 0.0
+    for side, name in enumerate(("pred", "true")):
+        if int(s[4 * side + 1]) > int(s[4 * side]):
+            raise ValueError("route_metrics: more stored nodes (%d) than nodes (%d)" % (int(s[4 * side + 1]), int(s[4 * side])))
+        out["graph_nodes_" + name], out["graph_nodes_dropped_" + name] = int(s[4 * side]), int(s[4 * side]) - int(s[4 * side + 1])
+    return out

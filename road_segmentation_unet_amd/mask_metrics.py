@@ -1,5 +1,5 @@
 """The chain from a mask to a road graph, in one place: the entry points of rsu_components.h, rsu_distance.h, rsu_thin.h, rsu_graph.h,
-rsu_segments.h and rsu_paths.h as functions of tensors, their workspaces, and the integer mask metrics of a validation pass -- the layout of their one
+rsu_segments.h, rsu_paths.h and rsu_routes.h as functions of tensors, their workspaces, and the integer mask metrics of a validation pass -- the layout of their one
 accumulator (layout), the launches of a chunk (MaskMetrics.run) and the reading of the all-reduced counters (decode).
 ConvolutionalModel.evaluate() and the mask tools (postprocess_masks, centerlines, road_graph) drive it; nothing here knows a model."""
 import ctypes
@@ -66,16 +66,32 @@ def segment_paths(seg, edges, counts, side, max_len, max_points, paths, offsets,
          ptr(offsets), ptr(kind), ptr(pos), ptr(info), ptr(ws), *seg.shape, st)
 
 
+def graph_routes(node_map, edges, counts, side, nodes, dist, info, ws, st):
+    """rsu_routes.h: the node table of one side of line_segments and the length of the shortest path between every two nodes; nodes int32
+    [N, max_nodes, 4], dist int32 [N, max_nodes, max_nodes] (70 per orthogonal link, 99 per diagonal one; hostio.ROUTES_INF: no path),
+    info int32 [N, 4] = {nodes, nodes stored, edges used, rows skipped}"""
+    call("rsu_graph_routes", ptr(node_map), ptr(edges), ptr(counts), int(side), int(edges.shape[1]), int(nodes.shape[1]), ptr(nodes), ptr(dist),
+         ptr(info), ptr(ws), *node_map.shape, st)
+
+
+def route_score(a, b, slack, match, acc, st):
+    """rsu_routes.h: one direction of the path-length score between two graphs (nodes, dist, info) of graph_routes with one max_nodes;
+    match int32 [N, max_nodes]; acc[4] += {pairs, sum q, unmatched, broken}"""
+    call("rsu_route_score", ptr(a[0]), ptr(a[1]), ptr(a[2]), ptr(b[0]), ptr(b[1]), ptr(b[2]), int(a[0].shape[1]), int(slack), ptr(match),
+         ptr(acc), int(a[0].shape[0]), st)
+
+
 # ------------------------------------------------------------------ workspaces
 # header -> (its size function, the element type of the width its `align` note asks of ws)
 _WS = {"components": ("rsu_components_ws_bytes", torch.int32), "distance": ("rsu_distance_ws_bytes", torch.int32),
        "thin": ("rsu_thin_ws_bytes", torch.int64), "graph": ("rsu_graph_ws_bytes", torch.int64),
-       "segments": ("rsu_segments_ws_bytes", torch.int64), "paths": ("rsu_paths_ws_bytes", torch.int64)}
+       "segments": ("rsu_segments_ws_bytes", torch.int64), "paths": ("rsu_paths_ws_bytes", torch.int64),
+       "routes": ("rsu_routes_ws_bytes", torch.int32)}
 
 
 def workspace(entry, shape, extra, device, message, ok=True, zero=False):
     """The workspace of rsu_<entry>.h's launches on `shape` = (n, H, W) and the header's `extra` size arguments (thin: max_iters; graph:
-    min_branch; segments: max_edges; paths: max_edges, max_len). ValueError(message) where the header takes no such sizes (its size function returns 0) or the caller's
+    min_branch; segments: max_edges; paths: max_edges, max_len; routes: max_nodes). ValueError(message) where the header takes no such sizes (its size function returns 0) or the caller's
     own guard `ok` fails. No entry reads what its workspace held: torch.empty, or zeros for a buffer that is kept."""
     fn, dtype = _WS[entry]
     need = int(getattr(lib(), fn)(*(int(v) for v in tuple(shape) + tuple(extra)))) if ok else 0
@@ -100,21 +116,22 @@ def thin_stack(t, device, threshold, max_iters, min_branch, message):
 
 
 # ------------------------------------------------------------------ the accumulator of a validation pass
-class Flags(namedtuple("Flags", "components distances centerlines min_branch junctions segments")):
-    """The resolved --validate_components, --validate_distances, --validate_centerlines, --centerline_min_branch, --validate_junctions and
-    --validate_segments: junctions, segments and min_branch count only with centre-lines; the graph stage is on iff one of
-    min_branch > 0 and junctions is."""
+class Flags(namedtuple("Flags", "components distances centerlines min_branch junctions segments routes")):
+    """The resolved --validate_components, --validate_distances, --validate_centerlines, --centerline_min_branch, --validate_junctions,
+    --validate_segments and --validate_routes: junctions, segments and min_branch count only with centre-lines, routes only with
+    segments; the graph stage is on iff one of min_branch > 0 and junctions is."""
     __slots__ = ()
 
-    def __new__(cls, components=False, distances=False, centerlines=False, min_branch=0, junctions=False, segments=False):
+    def __new__(cls, components=False, distances=False, centerlines=False, min_branch=0, junctions=False, segments=False, routes=False):
         cl = bool(centerlines)
-        return super().__new__(cls, bool(components), bool(distances), cl, int(min_branch) if cl else 0, cl and bool(junctions),
-                               cl and bool(segments))
+        sg = cl and bool(segments)
+        return super().__new__(cls, bool(components), bool(distances), cl, int(min_branch) if cl else 0, cl and bool(junctions), sg,
+                               sg and bool(routes))
 
     @classmethod
     def of(cls, options):
         return cls(*(getattr(options, k, 0) for k in ("validate_components", "validate_distances", "validate_centerlines",
-                                                      "centerline_min_branch", "validate_junctions", "validate_segments")))
+                                                      "centerline_min_branch", "validate_junctions", "validate_segments", "validate_routes")))
 
     @property
     def graph(self):
@@ -132,6 +149,7 @@ STAGES = OrderedDict([
     ("centerlines", (("hist", 2 * DIST_BINS), ("counts", 4), ("unconverged", 1))),           # ... of the two skeletons; rsu_mask_thin's four; info != 0
     ("graph", (("nodes", 8), ("jn_hist", 2 * DIST_BINS), ("jn_counts", 4))),                 # rsu_skeleton_graph's eight; the junction pixels' histogram and clusters
     ("segments", (("acc", 16), ("counts_sum", 4))),                                          # rsu_line_segments' sixteen; the patches' summed counts
+    ("routes", (("acc", 8), ("info", 8))),                                                   # rsu_route_score's four, truth -> prediction then back; the patches' summed info of both sides
 ])
 
 
@@ -163,7 +181,8 @@ def decode(flags, counts, relaxed_slack):
       centerlines: "cl_hist", the keys of hostio.centerline_metrics and "thin_unconverged" (image sides still moving at the last iteration);
       graph:       with min_branch > 0 cl_len_pred / cl_len_true are the PRUNED centre-lines' pixel counts (cldice_hard stays on the
                    unpruned skeletons); with junctions "jn_hist" and the keys of hostio.graph_metrics;
-      segments:    the keys of hostio.segment_metrics."""
+      segments:    the keys of hostio.segment_metrics;
+      routes:      the keys of hostio.route_metrics."""
     lay, c, slack = layout(flags), np.rint(np.asarray(counts)).astype(np.int64), int(relaxed_slack)
     if c.shape != (total(flags),):
         raise ValueError("decode: %s counters for a layout of %d" % (c.shape, total(flags)))
@@ -188,6 +207,9 @@ def decode(flags, counts, relaxed_slack):
             out.update(hostio.graph_metrics(out["jn_hist"], c[lay["graph.jn_counts"]], nodes, slack))
     if flags.segments:
         out.update(hostio.segment_metrics(c[lay["segments.acc"]].reshape(2, 8), c[lay["segments.counts_sum"]]))
+    if flags.routes:
+        acc = c[lay["routes.acc"]]
+        out.update(hostio.route_metrics(acc[:4], acc[4:], c[lay["routes.info"]]))
     return out
 
 
@@ -198,8 +220,9 @@ class MaskMetrics:
     every chunk's head, then decode() of the all-reduced acc. Every launch treats ignored pixels (labels other than 0 / 1) as background
     on both sides, so a chunk's padding patches add exactly nothing."""
 
-    def __init__(self, flags, device, B, P, connectivity, max_iters, max_segments, relaxed_slack):
+    def __init__(self, flags, device, B, P, connectivity, max_iters, max_segments, relaxed_slack, max_nodes=256, route_snap=8):
         self.flags, self.lay = flags, layout(flags)
+        self.max_nodes, self.route_snap = int(max_nodes), int(route_snap)
         self.connectivity, self.max_iters, self.max_segments, self.relaxed_slack = int(connectivity), int(max_iters), int(max_segments), int(relaxed_slack)
         shape, small = (B, P, P), B * P * P * 8 < 0x7ffffff0   # (the labels below 2 GiB)
         labels_limit = " (sides up to %d, the labels below 2 GiB)"
@@ -233,6 +256,13 @@ class MaskMetrics:
                                                      % SEGMENTS_MAX_SIDE), (self.max_segments,))
             w.update(edges_pred=zeros((B, self.max_segments, 8), torch.int32), edges_true=zeros((B, self.max_segments, 8), torch.int32),
                      counts=zeros((B, 4), torch.int32))
+        if flags.routes:   # the two node maps of rsu_line_segments; per side the node table, the distances and info; match and the workspace
+            w["routes"] = kept("routes", outside("--validate_routes", "rsu_routes.h", " (sides up to %d, --max_graph_nodes^2 distances per patch "
+                                                 "below 2 GiB)" % hostio.ROUTES_MAX_SIDE), (self.max_nodes,))
+            for side in ("pred", "true"):
+                w.update({"node_" + side: zeros(shape, torch.int32), "rt_nodes_" + side: zeros((B, self.max_nodes, 4), torch.int32),
+                          "rt_dist_" + side: zeros((B, self.max_nodes, self.max_nodes), torch.int32), "rt_info_" + side: zeros((B, 4), torch.int32)})
+            w["match"] = zeros((B, self.max_nodes), torch.int32)
         self.acc = zeros(total(flags), torch.int64)
         self.part = {name: self.acc[s] for name, s in self.lay.items()}
 
@@ -255,9 +285,18 @@ class MaskMetrics:
                                part["graph.nodes"], w["graph"], st)
             distance_hist(sp, 0.5, sl, part["centerlines.hist"], w["dist"], st)
             if f.segments:   # the segments of the two (pruned) skeletons; the patches' counts are summed on the device
-                line_segments(sp, 0.5, sl, self.max_segments, w["edges_pred"], w["edges_true"], w["counts"], None, None, None, None,
-                              part["segments.acc"], w["segments"], st)
+                line_segments(sp, 0.5, sl, self.max_segments, w["edges_pred"], w["edges_true"], w["counts"], None, None, w.get("node_pred"),
+                              w.get("node_true"), part["segments.acc"], w["segments"], st)
                 part["segments.counts_sum"].add_(w["counts"].sum(dim=0))
+                if f.routes:   # both graphs' distances, then the score from the truth to the prediction and back
+                    graphs = []
+                    for side, name in enumerate(("pred", "true")):
+                        g = (w["rt_nodes_" + name], w["rt_dist_" + name], w["rt_info_" + name])
+                        graph_routes(w["node_" + name], w["edges_" + name], w["counts"], side, *g, w["routes"], st)
+                        part["routes.info"][4 * side:4 * side + 4].add_(g[2].sum(dim=0))
+                        graphs.append(g)
+                    route_score(graphs[1], graphs[0], self.route_snap, w["match"], part["routes.acc"][:4], st)
+                    route_score(graphs[0], graphs[1], self.route_snap, w["match"], part["routes.acc"][4:], st)
             part["centerlines.unconverged"].add_((w["info"] != 0).sum())   # (on the device: no read-back)
             if f.junctions:   # how far the junction pixels of one side lie from the other's, and the junctions as 8-connected clusters
                 distance_hist(w["junc_pred"], 0.5, w["junc_true"], part["graph.jn_hist"], w["dist"], st)

@@ -22,6 +22,7 @@ from ._lib import call
 from .hostio import GRAPH_MAX_BRANCH, SEGMENTS_MAX_EDGES, SEGMENTS_MAX_SIDE, THIN_MAX_ITERS, THIN_MAX_SIDE
 from .hostio import road_graph as hostio_road_graph
 from .hostio import PATHS_MAX_LEN, PATHS_MAX_SIDE, simplify_path
+from .hostio import ROUTES_INF, ROUTES_MAX_NODES, ROUTES_MAX_SIDE
 from .dist import GradBucketer, micro_indices, shard_indices, tune_overlap  # noqa: F401  (shard_indices: importable from here as before)
 from .pool import BatchUploader, DevicePatchPool, PatchPool
 from .summary import Summary
@@ -112,7 +113,8 @@ EXTRA_FLAG_DEFS = [
     ("relaxed_slack", int, 3, "RHO, an int in [0, 62]: a predicted road pixel counts as correct when a true road pixel lies within RHO "
                               "pixels, and a true one as found when a predicted one does (3 on the Massachusetts roads set; 0 = the plain "
                               "pixel precision and recall). Used with --validate_distances"),
-    ("save_best_metric", str, "f1", "f1|relaxed_f1|cl_quality: the validation figure --save_best compares; relaxed_f1 requires "
+    ("save_best_metric", str, "f1", "f1|relaxed_f1|cl_quality|apls: the validation figure --save_best compares; apls requires "
+                                    "--validate_routes; relaxed_f1 requires "
                                     "--validate_distances, cl_quality requires --validate_centerlines"),
     ("validate_centerlines", bool, False, "Extract centre-lines during validation: evaluate() thins the predicted and the true road mask "
                                           "of every patch to one-pixel skeletons on the GPU (Guo & Hall's parallel thinning: "
@@ -147,6 +149,18 @@ EXTRA_FLAG_DEFS = [
                                        "road that leaves its patch ends there"),
     ("max_segments", int, 4096, "An int in [1, 65536]: the rows of the segment table per image and side. Segments past it are counted "
                                 "(segments_dropped_*) but not measured. Used by --validate_segments and --save_road_graph"),
+    ("validate_routes", bool, False, "Requires --validate_segments: evaluate() also measures both road networks as networks on the GPU "
+                                     "(rsu_routes.h): the length of the shortest path between every two nodes (junction zones and line "
+                                     "ends) of each graph, and the average path length similarity of Van Etten et al. with those nodes as "
+                                     "control points: apls_true_to_pred, apls_pred_to_true, apls (their harmonic mean), route_pairs_*, "
+                                     "route_unmatched_*, route_broken_*, graph_nodes_* and graph_nodes_dropped_* (nodes past "
+                                     "--max_graph_nodes in a patch). No points are injected along the edges; everything is per patch"),
+    ("max_graph_nodes", int, 256, "An int in [1, 1024]: the rows of the node table per image and side, and the side of its distance "
+                                  "matrix. Nodes past it are counted (graph_nodes_dropped_*) and their edges skipped. Used by "
+                                  "--validate_routes and --road_graph_distances"),
+    ("route_snap", int, 8, "An int in [0, 1023]: the pixels within which a node of one graph finds its counterpart in the other "
+                           "(--validate_routes). A junction's centroid moves by a few pixels between a prediction and the truth, so "
+                           "--relaxed_slack's 3 is too tight here; 8 is a choice, not a measurement"),
     ("save_road_graph", bool, False, "Inference: also write the road network of every predicted mask (after --min_road_area / "
                                      "--max_hole_area, at threshold 0.5; thinned, pruned by --centerline_min_branch, cut into segments) "
                                      "as graph_%03d.json beside the overlays: nodes (junctions, ends, isolated pixels) and edges with "
@@ -159,6 +173,10 @@ EXTRA_FLAG_DEFS = [
                                    "--road_graph_paths"),
     ("road_graph_simplify", float, 0.0, "EPS >= 0: simplify every path of --road_graph_paths with Ramer-Douglas-Peucker at EPS pixels (the "
                                         "first and last point stay); 0 = every pixel"),
+    ("road_graph_distances", bool, False, "With --save_road_graph (and road_graph()): also give every graph \"node_index\", its node ids in "
+                                          "the order of the GPU's node table (rsu_routes.h, --max_graph_nodes rows), and \"distances\", the "
+                                          "length in pixels of the shortest path between every two of them, row-major over node_index, "
+                                          "null where there is no path"),
     ("border_weight", float, 0.0, "w0 >= 0 of a border-distance weight map computed on the GPU from each batch's labels: a pixel counts "
                                   "1 + w0 * exp(-d^2 / (2 border_sigma^2)) times in the loss, d its distance to the other class inside its patch; "
                                   "0 = off (the U-Net paper uses 10). The loss stays normalised by the pixel count and the mean weight is above 1, "
@@ -353,9 +371,9 @@ def parse_relaxed_slack(value):
 
 
 def parse_save_best_metric(value):
-    """The --save_best_metric value: "f1", "relaxed_f1" or "cl_quality". Anything else raises ValueError."""
-    if not isinstance(value, str) or value not in ("f1", "relaxed_f1", "cl_quality"):
-        raise ValueError("--save_best_metric must be f1, relaxed_f1 or cl_quality, not %r" % (value,))
+    """The --save_best_metric value: "f1", "relaxed_f1", "cl_quality" or "apls". Anything else raises ValueError."""
+    if not isinstance(value, str) or value not in ("f1", "relaxed_f1", "cl_quality", "apls"):
+        raise ValueError("--save_best_metric must be f1, relaxed_f1 or cl_quality, or apls, not %r" % (value,))
     return value
 
 
@@ -393,6 +411,30 @@ def parse_max_segments(value):
         v, ok = 0, False
     if not ok:
         raise ValueError("--max_segments must be an integer in [1, %d], not %r" % (SEGMENTS_MAX_EDGES, value))
+    return v
+
+
+def parse_max_graph_nodes(value):
+    """The --max_graph_nodes value as an int in [1, 1024] (rsu_routes.h RSU_ROUTES_MAX_NODES). Anything else raises ValueError."""
+    try:
+        v = int(value)
+        ok = not isinstance(value, bool) and v == (float(value) if not isinstance(value, str) else v) and 1 <= v <= ROUTES_MAX_NODES
+    except (TypeError, ValueError, OverflowError):
+        v, ok = 0, False
+    if not ok:
+        raise ValueError("--max_graph_nodes must be an integer in [1, %d], not %r" % (ROUTES_MAX_NODES, value))
+    return v
+
+
+def parse_route_snap(value):
+    """The --route_snap value as an int in [0, 1023] (rsu_routes.h: slack). Anything else raises ValueError."""
+    try:
+        v = int(value)
+        ok = not isinstance(value, bool) and v == (float(value) if not isinstance(value, str) else v) and 0 <= v <= 1023
+    except (TypeError, ValueError, OverflowError):
+        v, ok = 0, False
+    if not ok:
+        raise ValueError("--route_snap must be an integer in [0, 1023], not %r" % (value,))
     return v
 
 
@@ -771,6 +813,12 @@ class Options(object):
         self.road_graph_simplify = parse_road_graph_simplify(self.road_graph_simplify)
         if self.validate_segments and not self.validate_centerlines:
             raise ValueError("--validate_segments requires --validate_centerlines: without it validation extracts no centre-lines")
+        self.validate_routes, self.road_graph_distances = bool(self.validate_routes), bool(self.road_graph_distances)
+        self.max_graph_nodes, self.route_snap = parse_max_graph_nodes(self.max_graph_nodes), parse_route_snap(self.route_snap)
+        if self.validate_routes and not self.validate_segments:
+            raise ValueError("--validate_routes requires --validate_segments: without it validation extracts no road segments")
+        if self.save_best_metric == "apls" and not self.validate_routes:
+            raise ValueError("--save_best_metric=apls requires --validate_routes: without it validation measures no path lengths")
         self.border_weight, self.border_sigma = parse_border_weight(self.border_weight), parse_border_sigma(self.border_sigma)
         self.clip_grad_norm = parse_clip_grad_norm(self.clip_grad_norm)
         self.ema_decay, self.ema_warmup = parse_ema_decay(self.ema_decay), bool(self.ema_warmup)
@@ -1113,7 +1161,8 @@ class ConvolutionalModel:
             self._mask_metrics = mask_metrics.MaskMetrics(
                 flags, self.net.device, self.local_batch, self.net.P, connectivity=getattr(opts, "component_connectivity", 8),
                 max_iters=getattr(opts, "centerline_max_iters", 64), max_segments=getattr(opts, "max_segments", 4096),
-                relaxed_slack=getattr(opts, "relaxed_slack", 0))
+                relaxed_slack=getattr(opts, "relaxed_slack", 0), max_nodes=getattr(opts, "max_graph_nodes", 256),
+                route_snap=getattr(opts, "route_snap", 8))
         return self._mask_metrics
 
     def _validate(self, validation, step):
@@ -1150,6 +1199,13 @@ class ConvolutionalModel:
                       .format(step, v["segments_pred"], v["segments_true"], v["road_length_pred"], v["road_length_true"], v["length_ratio"],
                               v["nodes_pred"], v["nodes_true"], v["dangling_pred"], v["dangling_true"], v["multi_pred"], v["multi_true"],
                               v["segments_dropped_pred"], v["segments_dropped_true"]))
+            if "apls" in v:
+                print("step {} validation path lengths: APLS {:.4f} (truth to prediction {:.4f} over {} pairs, {} unmatched, {} broken; "
+                      "prediction to truth {:.4f} over {} pairs, {} unmatched, {} broken); nodes predicted {} true {}, past --max_graph_nodes {} {}"
+                      .format(step, v["apls"], v["apls_true_to_pred"], v["route_pairs_true_to_pred"], v["route_unmatched_true_to_pred"],
+                              v["route_broken_true_to_pred"], v["apls_pred_to_true"], v["route_pairs_pred_to_true"],
+                              v["route_unmatched_pred_to_true"], v["route_broken_pred_to_true"], v["graph_nodes_pred"], v["graph_nodes_true"],
+                              v["graph_nodes_dropped_pred"], v["graph_nodes_dropped_true"]))
             if self._summary is not None:
                 self._summary.add({"val_loss": v["loss"], "val_objective": v["objective"], "val_dice": v["dice"], "val_f1": v["f1"],
                                    "val_iou": v["iou"], "val_best_threshold": v["best_threshold"]}, global_step=step)
@@ -1172,6 +1228,9 @@ class ConvolutionalModel:
                 if "length_ratio" in v:
                     self._summary.add({"val_length_ratio": v["length_ratio"], "val_road_length_pred": v["road_length_pred"],
                                        "val_road_length_true": v["road_length_true"]}, global_step=step)
+                if "apls" in v:
+                    self._summary.add({"val_apls": v["apls"], "val_apls_true_to_pred": v["apls_true_to_pred"],
+                                       "val_apls_pred_to_true": v["apls_pred_to_true"]}, global_step=step)
         # (the same numbers on every rank: they come out of the all-reduce)
         if self.best_val_f1 is None or v["f1"] > self.best_val_f1:
             self.best_val_f1 = v["f1"]
@@ -1531,14 +1590,17 @@ class ConvolutionalModel:
             "centerlines (--save_centerlines): %d masks of %d x %d pixels are outside rsu_thin.h's limits (sides up to %d, n * H * W * 4 below "
             "2 GiB): thin them in smaller stacks" % (tuple(a.shape) + (THIN_MAX_SIDE,)))
 
-    def road_graph(self, masks, threshold=0.5):
+    def road_graph(self, masks, threshold=0.5, distances=None):
         """The road network of predicted masks, one plain dict per image (hostio.road_graph: nodes and edges with their lengths): masks
         [n, H, W] or [n, H, W, 1] probabilities -> the centre-lines of {p >= threshold} (rsu_mask_thin, pruned by --centerline_min_branch:
         centerlines()), cut at their junctions into segments and measured on the device (rsu_line_segments, --max_segments rows per
         image; a dict carries "segments" = the true segment count, which may exceed its edges). Integer decisions on the same input:
         every rank computes the same network. With --road_graph_paths the segment labels are asked for too, rsu_segment_paths orders the
         pixels of every stored segment of at most --max_path_length pixels along it, every edge gains "kind" and "path" (hostio.road_graph,
-        simplified at --road_graph_simplify) and every dict "unordered" = its branched and too long segments."""
+        simplified at --road_graph_simplify) and every dict "unordered" = its branched and too long segments. With distances=True
+        (None: --road_graph_distances) rsu_graph_routes runs on the same tables and every dict gains "node_index", the node ids in the
+        order of the device's node table (--max_graph_nodes rows; "nodes_dropped" = those past it), and "distances", the length in
+        pixels (w / 70) of the shortest path between every two of them, row-major over node_index, None where there is no path."""
         lines = self._centerlines_device(masks, threshold)   # (exactly 0.0 / 1.0, and they stay on the device)
         n, H, W = (int(v) for v in lines.shape)
         opts = self._options
@@ -1562,6 +1624,15 @@ class ConvolutionalModel:
             paths, offsets, kind, info = zeros(n, H * W), zeros(n, cap + 1), zeros(n, cap), zeros(n, 4)
             mask_metrics.segment_paths(seg, edges, counts, 0, max_len, H * W, paths, offsets, kind, None, info, pws, st)
             paths, offsets, kind, info = (t.cpu().numpy() for t in (paths, offsets, kind, info))
+        routed = bool(getattr(opts, "road_graph_distances", False)) if distances is None else bool(distances)
+        if routed:
+            cap_nodes = int(getattr(opts, "max_graph_nodes", 256))
+            rws = mask_metrics.workspace("routes", (n, H, W), (cap_nodes,), dev, "road_graph (--road_graph_distances): %d masks of %d x %d "
+                                         "pixels with %d nodes each are outside rsu_routes.h's limits (sides up to %d, n * max_graph_nodes^2 * 4 "
+                                         "below 2 GiB): use smaller stacks" % (n, H, W, cap_nodes, ROUTES_MAX_SIDE))
+            rt_nodes, rt_dist, rt_info = zeros(n, cap_nodes, 4), zeros(n, cap_nodes, cap_nodes), zeros(n, 4)
+            mask_metrics.graph_routes(node, edges, counts, 0, rt_nodes, rt_dist, rt_info, rws, st)
+            rt_nodes, rt_dist, rt_info = (t.cpu().numpy() for t in (rt_nodes, rt_dist, rt_info))
         edges, counts, node = edges.cpu().numpy(), counts.cpu().numpy(), node.cpu().numpy()
         out = []
         for i in range(n):
@@ -1572,6 +1643,11 @@ class ConvolutionalModel:
                 for e in g["edges"] if eps > 0.0 else ():
                     if len(e["path"]) > 2:
                         e["path"] = simplify_path(np.asarray(e["path"], np.int64), eps).tolist()
+            if routed:
+                k = int(rt_info[i, 1])
+                g["node_index"] = [int(v) for v in rt_nodes[i, :k, 0]]
+                g["nodes_dropped"] = int(rt_info[i, 0]) - k
+                g["distances"] = [[None if int(v) >= ROUTES_INF else int(v) / 70.0 for v in row] for row in rt_dist[i, :k, :k]]
             out.append(g)
         return out
 
